@@ -4,6 +4,7 @@ HVG(2000) -> 50-PC PCA  on synthetic CSR resident in HBM, plus the SpMM's achiev
 
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR      (also the last timed step's outputs as DIR/<name>.npy, to compare builds)
 
 A "step" is one srx_pipeline() call over one fresh copy of the raw count matrix (the pipeline normalises X in place,
 so every step gets its own copy, cloned — with its pattern-only index structures and its reserved result block —
@@ -63,6 +64,42 @@ ROOF_NOTE = {
 }
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: bound of all the arrays together
+DUMP_SAMPLE = 3 << 20          # elements kept of each of the two large outputs (scores, normalised values)
+DUMP_SEED = 20260              # seed of the fixed sample: the same rows / non-zeros on every run of the same arguments
+
+
+def fetch_outputs(F, mat, res, storage):
+    """What a caller of srx_pipeline receives from the step that last ran on `mat`: the PCA results (srx_result_fetch) and X
+    normalised + log1p-transformed in place (at its storage precision), as float arrays.  The scores (N x n_pc) and the values
+    (nnz) are cut to a fixed seeded sample of rows / of non-zeros, the same for every build at the same arguments."""
+    import numpy as np
+    k, n_pc = int(res.pca.k), int(res.pca.n_pc)
+    info = mat.info()
+    n = int(info.n_rows)
+    scores, comps = np.zeros((n, n_pc)), np.zeros((k, n_pc))
+    evr, mean, sd, sel = np.zeros(n_pc), np.zeros(k), np.zeros(k), np.zeros(k, np.uint64)
+    F.check(F.lib().srx_result_fetch(mat.handle, F.ptr(scores), F.ptr(comps), F.ptr(evr), F.ptr(mean), F.ptr(sd), F.ptr(sel)),
+            mat.ctx.handle)
+    vals = mat.values(np.float64 if info.store == F.STORE_F64 else np.float32)
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(n, size=min(n, DUMP_SAMPLE // max(n_pc, 1)), replace=False))
+    nz = np.sort(rng.choice(len(vals), size=min(len(vals), DUMP_SAMPLE), replace=False))
+    return {"scores": scores[rows], "components": comps, "explained_variance_ratio": evr, "mean": mean, "std": sd,
+            "selected_features": sel.astype(np.float64), "x_values": vals[nz]}
+
+
+def dump_outputs(directory, outputs):
+    import numpy as np
+    total = sum(v.nbytes for v in outputs.values())
+    assert total <= DUMP_BYTES, total
+    os.makedirs(directory, exist_ok=True)
+    for name, v in outputs.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(v))
+    return {"dir": directory, "bytes": total, "arrays": {name: list(v.shape) for name, v in outputs.items()},
+            "sample": f"scores: rows, x_values: non-zeros, drawn with numpy default_rng({DUMP_SEED}); every other array whole"}
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -91,7 +128,14 @@ def parse():
     ap.add_argument("--host-sample-cells", type=int, default=0,
                     help="cells of the host-side legs (incl_h2d blocks, threaded CPU baseline); 0 = the whole configuration")
     ap.add_argument("--max-copies-gb", type=float, default=180.0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's rows) as DIR/<name>.npy "
+                         f"(float32 / float64, at most {DUMP_BYTES >> 20} MB: the scores and the normalised values as a fixed "
+                         "seeded sample)")
+    a = ap.parse_args()
+    if a.dump_outputs and a.backed:
+        ap.error("--dump-outputs dumps the resident pipeline's step; it is not available with --backed")
+    return a
 
 
 def cpu_model():
@@ -256,9 +300,9 @@ class Bench:
         return int(cut[self.rank]), int(cut[self.rank + 1])
 
     def run(self, config, n_global, row0, row1, storage, steps, warmup, solver=0, hvg=None, skew=0, tolerate_noconv=False, headline=False,
-            per_step=False):
+            per_step=False, fetch=False):
         """K timed pipeline steps on rows [row0, row1) of the synthetic matrix; returns the measurements of this rank
-        (times already maxed over ranks)."""
+        (times already maxed over ranks).  fetch: also the outputs of the last timed step (fetch_outputs), under `outputs`."""
         a, F, sr, lib, ctx = self.a, self.F, self.sr, self.lib, self.ctx
         hvg = hvg or a.hvg
         p = self.params(config, n_global, skew)
@@ -363,6 +407,7 @@ class Bench:
             # on the records themselves cost 0.05-0.08 ms of a 9.7 ms step (measured: 9.74-9.81 against 9.66-9.74 with none).
             # The other classes are timed in a SEPARATE pass of a few steps behind the clock, reported as such.
             elapsed, prof, stage, iters = timed_pass(steps, sum(1 << c for c in stage_classes))
+            outputs = fetch_outputs(F, copies[used - 1], res, storage) if fetch else None      # before the breakdown pass reuses it
             bd_steps = max(3, min(steps, 8))
             bd_elapsed, bd_prof, _, _ = timed_pass(bd_steps, all_mask)
             for name, rec in bd_prof.items():
@@ -374,12 +419,14 @@ class Bench:
                          "note": "all class timers on, behind the timed region: the source of every class time outside the Gram formation stage"}
         else:
             elapsed, prof, stage, iters = timed_pass(steps, all_mask)
+            outputs = fetch_outputs(F, copies[used - 1], res, storage) if fetch else None
         ctx.prof_enable(0)
         out = {"elapsed": elapsed, "ms_per_step": elapsed / steps * 1e3, "nnz": nnz, "prof": prof,
                "stage_ms_per_step": {k_: v / steps for k_, v in stage.items()}, "iters": iters,
                "residual": float(res.pca.residual), "nnz_selected": int(res.pca.nnz_selected),
                "solver": {1: "gram", 2: "spmm"}.get(int(res.pca.solver), "?"), "generate_s": t_gen, "copies": n_copies,
-               "noconv_steps": len(failures), "genes": int(info.n_cols), "breakdown": breakdown, "step_ms": sorted(step_ms)}
+               "noconv_steps": len(failures), "genes": int(info.n_cols), "breakdown": breakdown, "step_ms": sorted(step_ms),
+               "outputs": outputs}
         for c in copies:
             c.free()
         pristine.free()
@@ -594,10 +641,12 @@ def incl_h2d(B, H, what):
 
 
 def _blas_limit(n):
-    """Context manager limiting the BLAS / OpenMP pools numpy and scipy call into (threadpoolctl; a no-op without it)."""
+    """Context manager limiting the BLAS / OpenMP pools numpy and scipy call into (threadpoolctl; a no-op without it).
+    It only ever lowers a pool: OpenBLAS (0.3.28 / 0.3.29 as scipy ships it) segfaults in its worker threads when a pool is
+    raised above the size it started with (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS at import)."""
     try:
-        from threadpoolctl import threadpool_limits
-        return threadpool_limits(limits=n)
+        from threadpoolctl import threadpool_info, threadpool_limits
+        return threadpool_limits(limits=min([n] + [p["num_threads"] for p in threadpool_info() if p.get("num_threads")]))
     except Exception:       # noqa: BLE001
         import contextlib
         return contextlib.nullcontext()
@@ -625,10 +674,20 @@ def physical_cores():
         return usable_cores()
 
 
+def omp_budget():
+    """The thread count OMP_NUM_THREADS grants this process (its first level), 0 when it is unset: the CPUs the host legs may use
+    on a machine shared by several jobs, where the affinity set shows every core of the box."""
+    try:
+        return max(0, int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0]))
+    except ValueError:
+        return 0
+
+
 def cpu_baselines(B, H):
     """Three CPU legs on this box's host cores (oracle/ = the checker, here as the thing timed):
     cpu_baseline                     — the OpenMP restatement over the WHOLE host matrix `H` (the metric's configuration at full
-                                       size by default) on every physical core (SURVEY.md 8(d) ii, BASELINE.md section 3 row C3);
+                                       size by default) on every physical core, at most OMP_NUM_THREADS (SURVEY.md 8(d) ii,
+                                       BASELINE.md section 3 row C3);
     cpu_baseline_reference_faithful  — the reference's own algorithm (serial loops, densify, full SVD) on a 24k-cell sample,
                                        BLAS pinned to <= 64 threads, extrapolated linearly in cells (said so);
     cpu_baseline_c1_serial           — BASELINE.md section 3's C1 (2.7k x 32k, 7 %) whole, one thread."""
@@ -640,7 +699,7 @@ def cpu_baselines(B, H):
     out = {}
     model, cores, phys = cpu_model(), usable_cores(), physical_cores()
     env_threads = int(os.environ.get("SRX_BENCH_CPU_THREADS", "0"))
-    threads = max(1, env_threads or min(cores, phys))
+    threads = max(1, env_threads or min(cores, phys, omp_budget() or cores))
     ip, idx, val, genes = H.ip, H.idx, H.val, H.genes
     # (ii) threaded: OpenMP over every loop + k x k covariance and a symmetric eigen-solve instead of the full SVD
     n2 = H.n
@@ -965,7 +1024,10 @@ def main():
     n_global = cells if scaling == "strong" or world == 1 else cells * world
     p = B.params(a.config, n_global, a.skew)
     row0, row1 = B.shard(p, n_global)
-    main_ = B.run(a.config, n_global, row0, row1, a.storage, a.steps, a.warmup, solver=a.solver, skew=a.skew, headline=True)
+    main_ = B.run(a.config, n_global, row0, row1, a.storage, a.steps, a.warmup, solver=a.solver, skew=a.skew, headline=True,
+                  fetch=bool(a.dump_outputs) and rank == 0)
+    outputs = main_.pop("outputs")
+    dumped = dump_outputs(a.dump_outputs, outputs) if outputs is not None else None
     weak = None
     if world > 1 and scaling == "strong" and not a.lean:
         # the other reading of the scaling question: per-GPU work fixed (the config's cells on EVERY GPU)
@@ -1202,6 +1264,8 @@ def main():
         }
         if weak:
             out["weak"] = weak
+        if dumped:
+            out["dump_outputs"] = dumped
         out.update(extra)
         if "cpu_baseline" in out and out["cpu_baseline"].get("value"):
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]

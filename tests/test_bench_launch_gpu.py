@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -124,3 +125,28 @@ def test_default_command_prints_a_bounded_record():
     with open(os.path.join(ROOT, "bench_full.json")) as fh:
         full = json.loads(fh.read())
     assert full["value"] == d["value"] and "kernels" in full and "strong_scaling_budget" in full
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs: after the timed steps the outputs of the last one land in DIR as float .npy files — the PCA results whole,
+    the scores as rows (all of them at this size), the normalised values as a sample — consistent with one another."""
+    cells, d = 20000, tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c2", "--cells", str(cells), "--steps", "2",
+           "--warmup", "1", "--lean", "--dump-outputs", str(d)]
+    p = subprocess.run(cmd, env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=ROOT, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    rec = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.strip()][-1])
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+    got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert set(got) == {"scores", "components", "explained_variance_ratio", "mean", "std", "selected_features", "x_values"}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    k, n_pc = 2000, 50
+    scores, evr, sel = got["scores"], got["explained_variance_ratio"], got["selected_features"]
+    assert scores.shape == (cells, n_pc) and got["components"].shape == (k, n_pc) and evr.shape == (n_pc,)
+    assert got["mean"].shape == got["std"].shape == sel.shape == (k,)
+    assert np.array_equal(sel, np.round(sel)) and len(np.unique(sel)) == k and sel.min() >= 0 and sel.max() < 20000
+    assert got["x_values"].dtype == np.float32 and np.isfinite(got["x_values"]).all() and got["x_values"].min() >= 0
+    # standardised columns: evr[c] = ||scores[:, c]||^2 / (cells * k), the components orthonormal
+    assert np.allclose(evr, (scores ** 2).sum(axis=0) / (cells * k), rtol=1e-4)
+    assert np.all(np.diff(evr) <= 1e-12) and np.allclose(got["components"].T @ got["components"], np.eye(n_pc), atol=1e-6)
