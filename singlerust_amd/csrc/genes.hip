@@ -6,8 +6,8 @@
 // privatised in LDS.  3 accumulators x G genes do not fit 160 KiB, hence GENE TILING: the
 // gene axis is cut into tiles of <= 8000 genes (20 B of LDS each: u32 count + f64 sum + f64
 // sum of squares); because column indices are sorted inside a row, a tile's entries are one
-// contiguous segment of every row, found once per sparsity pattern by binary search
-// (k_tile_ptr) and cached on the matrix.  A 1024-thread workgroup (one per CU: it owns the
+// contiguous segment of every row, found once per sparsity pattern (ensure_tiles) and
+// cached on the matrix.  A 1024-thread workgroup (one per CU: it owns the
 // whole LDS) takes one (gene tile, row block), walks the row segments one wave per row with
 // coalesced loads of indices/values, accumulates with LDS atomics, and flushes its tile to
 // a per-block partial buffer; a second tiny kernel sums the partials in fixed order.
@@ -65,12 +65,7 @@ __device__ __forceinline__ void seg_bounds(const int64_t* __restrict__ indptr, c
 //  test and one ds_read_b64 instead of the ~30-instruction logarithm.  Bit-identical results, 16x fewer logarithms, and
 //  3.64 ms against 3.18: the four dependent LDS reads of a chunk queue behind the other waves' atomics, and the arithmetic
 //  they replace was what hid that latency.)
-// BL (round 6): the accumulators in BLOCKS of 32 genes — 32 sums (256 bytes: every bank once), then the 32 sums of squares — instead
-// of {sum, sum of squares} pairs side by side.  With the pairs a wave's 64 sum atomics only ever touch the banks 0, 1 mod 4 and its
-// 64 square atomics the banks 2, 3 mod 4: half of the LDS's bank pairs per instruction (68 % of the LDS pipe's active cycles were
-// bank conflicts, profiles/r05_pmc_gram.md).  One more VALU instruction per value for the address; the second atomic stays at an
-// immediate offset (256 bytes).
-template <typename T, typename I, bool XF, bool WB = false, bool BL = false>
+template <typename T, typename I, bool XF, bool WB = false>
 __global__ __launch_bounds__(kMomThreads) void k_gene_moments(
     const int64_t* __restrict__ indptr, const int64_t* __restrict__ tp, const I* __restrict__ idx,
     std::conditional_t<WB, T, const T>* __restrict__ vals, uint64_t n_rows, uint64_t n_cols, int n_tiles, int tile_genes,
@@ -81,12 +76,9 @@ __global__ __launch_bounds__(kMomThreads) void k_gene_moments(
                                     // atomic at the instruction's immediate offset
     // behind the accumulators (tile_genes * 16 B): the log1p table
     // (the table from global memory instead — 2 KB, L1-resident, one vector load per value — was tried: 5.7 ms against 3.5)
-    const int tile_pad = BL ? (tile_genes + 31) & ~31 : tile_genes;
-    constexpr int kSqOff = BL ? 32 : 1;                      // 8-byte words between a gene's sum and its sum of squares
-    auto acc_slot = [](int g0) -> int { return BL ? ((g0 >> 5) << 6) + (g0 & 31) : 2 * g0; };
-    const Log1pTabEntry* s_tab = reinterpret_cast<const Log1pTabEntry*>(reinterpret_cast<char*>(lds) + (size_t)tile_pad * 16);
+    const Log1pTabEntry* s_tab = reinterpret_cast<const Log1pTabEntry*>(reinterpret_cast<char*>(lds) + (size_t)tile_genes * 16);
     if constexpr (XF) stage_log1p_table(const_cast<Log1pTabEntry*>(s_tab));
-    for (int g = threadIdx.x; g < 2 * tile_pad; g += kMomThreads) s_acc[g] = 0.0;
+    for (int g = threadIdx.x; g < 2 * tile_genes; g += kMomThreads) s_acc[g] = 0.0;
     __syncthreads();
 
     // The gene tiles of one row block run on the SAME XCD (consecutive workgroup ids go round the 8 XCDs): a row's tile segments
@@ -217,13 +209,13 @@ __global__ __launch_bounds__(kMomThreads) void k_gene_moments(
                     const unsigned long long iq = (unsigned long long)__double_as_longlong(__builtin_fma(x0 * x0, fx_sq, kMagic));
                     // (a poisoned value adds nothing while the reduction still takes its magic bits off: the gene's sums are
                     //  replaced by NaN anyway)
-                    unsigned long long* a2 = reinterpret_cast<unsigned long long*>(s_acc) + acc_slot(g0);
+                    unsigned long long* a2 = reinterpret_cast<unsigned long long*>(s_acc) + 2 * g0;
                     __hip_atomic_fetch_add(a2, is, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(a2 + kSqOff, iq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(a2 + 1, iq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     continue;
                 }
-                __hip_atomic_fetch_add(&s_acc[acc_slot(g0)], x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_add(&s_acc[acc_slot(g0) + kSqOff], x0 * x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(&s_acc[2 * g0], x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(&s_acc[2 * g0 + 1], x0 * x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
     };
@@ -348,8 +340,8 @@ __global__ __launch_bounds__(kMomThreads) void k_gene_moments(
     for (int g = threadIdx.x; g < tile_genes; g += kMomThreads) {
         uint64_t gene = (uint64_t)gbase + g;
         if (gene < n_cols) {
-            part_sum[rb * n_cols + gene] = s_acc[acc_slot(g)];
-            part_sq[rb * n_cols + gene] = s_acc[acc_slot(g) + kSqOff];
+            part_sum[rb * n_cols + gene] = s_acc[2 * g];
+            part_sq[rb * n_cols + gene] = s_acc[2 * g + 1];
         }
     }
 }
@@ -611,18 +603,12 @@ int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const int32_t* idx,
     return SRX_OK;
 }
 
-// d_indices -> 16-bit mirror (entries past nnz: 0, the arrays are padded for the vector walks)
-__global__ void k_narrow16(const int32_t* __restrict__ idx, uint64_t nnz, uint64_t n_out, uint16_t* __restrict__ out) {
-    uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (; e < n_out; e += stride) out[e] = e < nnz ? (uint16_t)idx[e] : (uint16_t)0;
-}
-
-// Both pattern-only structures of a fresh CSR matrix in ONE walk over its 32-bit column indices: the 16-bit mirror and the
-// NB = n_tiles - 1 interior gene-tile cuts of every row.  A wave per row, 256 entries per step; a row is sorted by column, so
-// the cut at `bound` is the row's start + the number of entries below it = the popcounts of the waves' `idx < bound` ballots
-// (scalar instructions; no search, no second pass).  k_tile_ptr's binary searches + k_narrow16 read the indices twice and
-// moved 10.9 GB at c3 (2.3 ms of a cold step's 14.7); this moves 6.6.
+// Both pattern-only structures of a fresh CSR matrix in ONE walk over its 32-bit column indices: the 16-bit mirror (entries
+// past nnz: 0, the arrays are padded for the vector walks) and the NB = n_tiles - 1 interior gene-tile cuts of every row.  A
+// wave per row, 256 entries per step; a row is sorted by column, so the cut at `bound` is the row's start + the number of
+// entries below it = the popcounts of the waves' `idx < bound` ballots (scalar instructions; no search, no second pass).
+// k_tile_ptr's binary searches + a separate narrowing pass read the indices twice and moved 10.9 GB at c3 (2.3 ms of a cold
+// step's 14.7); this moves 6.6.
 // WIDEN: the other way round — the 16-bit mirror came over PCIe (upload_on: a quarter of the host's index bytes cross the
 // link) and the 32-bit indices are made from it, with the same cuts.
 // COUNT (round 6): the walk also makes the per-gene non-zero counts (csr.rs:24-36) — a 32-bit counter per gene in LDS (n_cols <= 38 000:
@@ -745,31 +731,21 @@ int32_t tiles_from_idx16(srx_mat* m, hipStream_t stream) {
     return SRX_OK;
 }
 
+// The gene-tile geometry of a matrix and its pattern-only structures, once per pattern: up to 65536 columns the 16-bit mirror,
+// the cuts and (up to 38000 columns) the per-gene counts in ONE walk, as the upload makes them; beyond, the cuts by binary
+// search and no mirror.  A matrix without rows has nothing to walk (as in tiles_from_idx16: an upload of a shard without rows
+// reaches here with its mirror and no geometry); the passes still read the cuts of row 0, so it gets one row of them.
 int32_t ensure_tiles(srx_mat* m) {
     srx_ctx* ctx = m->ctx;
     if (m->n_tiles) return SRX_OK;
     int nt, tg;
     tile_geometry(m, nt, tg);
-    if (nt > 1 && nt <= 9 && m->n_cols <= 65536 && !m->d_idx16 && !m->d_tile_ptr && m->n_rows > 0) {
-        SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_tile_ptr, (size_t)(nt - 1) * m->n_rows * sizeof(int64_t)));
+    if (nt > 1) SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_tile_ptr, (size_t)(nt - 1) * (m->n_rows ? m->n_rows : 1) * sizeof(int64_t)));
+    if (m->n_rows > 0 && m->n_cols <= 65536) {
         SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_idx16, (m->nnz + 16) * sizeof(uint16_t)));
         SRX_TRY(launch_narrow16_tiles<false>(m, nt, tg, ctx->stream));
-        m->n_tiles = nt;
-        m->tile_genes = tg;
-        return SRX_OK;
-    }
-    if (nt > 1) {
-        SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_tile_ptr, (size_t)(nt - 1) * (m->n_rows ? m->n_rows : 1) * sizeof(int64_t)));
+    } else if (m->n_rows > 0) {
         SRX_TRY(launch_tile_ptr(ctx, m->d_indptr, m->d_indices, m->n_rows, nt, tg, m->d_tile_ptr));
-    }
-    if (m->n_cols <= 65536 && !m->d_idx16) {
-        SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_idx16, (m->nnz + 16) * sizeof(uint16_t)));
-        uint64_t g = (m->nnz + 16 + 1023) / 1024;
-        if (g < 1) g = 1;
-        if (g > 65535) g = 65535;
-        hipLaunchKernelGGL(k_narrow16, dim3((unsigned)g), dim3(256), 0, ctx->stream, m->d_indices, m->nnz, m->nnz + 16,
-                           m->d_idx16);
-        SRX_HIP(ctx, hipGetLastError());
     }
     m->n_tiles = nt;
     m->tile_genes = tg;
@@ -816,10 +792,7 @@ static int32_t local_moments(srx_mat* m, double** packed_out, RowXf xf = RowXf{}
     // the per-gene counts depend on the sparsity pattern only: counted once per pattern (here, or by srx_matrix_prepare), kept
     // on the matrix (clones inherit them)
     SRX_TRY(ensure_pattern_counts(m));
-    // SRX_MOM_BLOCKED=1: the accumulators in blocks of 32 genes (no half-bank restriction; measured slower: 2.81 against 2.75 ms,
-    // profiles/r06_knockouts.md); default: the {sum, sum of squares} pairs
-    const bool blocked = xf.row_sum && getenv("SRX_MOM_BLOCKED") && atoi(getenv("SRX_MOM_BLOCKED"));
-    const size_t lds = (size_t)(blocked ? (m->tile_genes + 31) & ~31 : m->tile_genes) * 16 + (xf.row_sum ? (size_t)kLog1pTabBytes : 0);
+    const size_t lds = (size_t)m->tile_genes * 16 + (xf.row_sum ? (size_t)kLog1pTabBytes : 0);
     // s_i = 2 when the 16-bit index mirror exists (n_cols <= 65536), 4 otherwise
     const double bytes = (double)m->nnz * ((m->n_cols <= 65536 ? 2.0 : 4.0) + val_bytes(m)) + (double)(m->n_rows + 1) * 8.0 +
                          (double)G * 24.0 + (xf.row_sum ? (double)m->n_rows * 8.0 : 0.0) +
@@ -850,9 +823,7 @@ static int32_t local_moments(srx_mat* m, double** packed_out, RowXf xf = RowXf{}
         auto pick = [&](auto tval, auto tidx, const auto* idxp, const auto* valp) -> int32_t {
             using T = decltype(tval);
             using I = decltype(tidx);
-            if (xf.row_sum && xf.write_back && blocked) return launch(k_gene_moments<T, I, true, true, true>, idxp, const_cast<T*>(valp));
             if (xf.row_sum && xf.write_back) return launch(k_gene_moments<T, I, true, true>, idxp, const_cast<T*>(valp));
-            if (xf.row_sum && blocked) return launch(k_gene_moments<T, I, true, false, true>, idxp, valp);
             if (xf.row_sum) return launch(k_gene_moments<T, I, true>, idxp, valp);
             return launch(k_gene_moments<T, I, false>, idxp, valp);
         };

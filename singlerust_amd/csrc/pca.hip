@@ -148,8 +148,7 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
     RowMajor rm;
     Range r_compact("srx:compact");
     // the 256-tiled view only where something reads it
-    const bool fits_rows = is_f32(m) ? fwd_rows_fits<float, float>(k) : fwd_rows_fits<double, double>(k);
-    const bool need_t256 = o.solver == 2 || !fits_rows;
+    const bool need_t256 = o.solver == 2;
     if (dev_sel) {
         SRX_TRY(build_tiled_fused(m, hv.d_bits, hv.n_words, k, rm, need_t256 ? &t256 : nullptr, xf, o.solver == 1));
     } else if ((k + KG - 1) / KG <= kWave) {

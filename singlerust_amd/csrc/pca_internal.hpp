@@ -85,15 +85,6 @@ template <> struct Vec4<double> {
     __device__ __forceinline__ double& operator[](int i) { return i == 0 ? a.x : i == 1 ? a.y : i == 2 ? b.x : b.y; }
 };
 
-// f(integral_constant<int, I>) for I = 0 .. N-1: a loop whose index is a compile-time constant in the body
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
-
 // DPP row rotate inside each 16-lane row (v_mov_b32_dpp row_ror:S) — no LDS traffic.
 template <int S>
 __device__ __forceinline__ int ror16(int x) {
@@ -196,8 +187,6 @@ inline size_t gram_packed_count(int k) { return (size_t)k * (size_t)(k + 1) / 2;
 
 // ---- pca_solve.hip: products, iteration, solver ------------------------------------------------------
 int32_t build_row_order(srx_ctx* ctx, RowMajor& r);
-template <typename VT, typename PT>
-bool fwd_rows_fits(int k);
 int scores_ld(int n_pc);
 void result_layout(uint64_t n_rows, int k, int n_pc, int dim, size_t& score_bytes, size_t& small_doubles,
                    std::vector<int>* plan_a_out = nullptr, std::vector<int>* plan_b_out = nullptr);

@@ -329,19 +329,25 @@ def test_spmm_and_gram_kernels_vs_scipy(ctx, store, n, g, density, k):
     assert np.array_equal(gram, want_g)                     # integer counts: exact in f64, any order
 
 
+# Genes added to k for the "ranges" cases: past the 10 236 f32 genes of the widest single panel slice in LDS, so that
+# launch_fwd_rows cuts the genes into ranges (k_spmm_rows<.., RANGE = true>: one launch per range, the later ones accumulating).
+RANGE_GENES = 10_240
+
+
 @pytest.mark.parametrize("kernel", ["ranges", "rows"])
 @pytest.mark.parametrize("k", [64, 512, 513, 1500, 2000, 4096, 4100])
 def test_forward_spmm_from_row_major_records(ctx, kernel, k, monkeypatch):
-    """The transform's kernel k_spmm_rows (column slices of the panel in LDS) and round 6's k_spmm_ranges (one quad per row, gene
-    ranges of 512 through the LDS, chunks of 32 records; built, conflict-free, slower: SRX_FWD_RANGES=1) against scipy, through srx_spmm's row-major
-    route: rows of 0, 1, 31 .. 33, 63 .. 65 and 200 kept entries (chunk boundaries), runs of > 32 entries inside ONE gene range
-    (the rare second chunk of a run), rows whose entries all fall in the last range, a row count that is not a multiple of 16,
-    k on both sides of the range size and of the 8-range limit (4100: the launcher falls back on the column-slice kernel)."""
+    """The transform's kernel k_spmm_rows (column slices of the panel in LDS) against scipy, through srx_spmm's row-major route:
+    rows of 0, 1, 31 .. 33, 63 .. 65 and 200 kept entries, runs of up to 90 entries packed into a few hundred genes, rows whose
+    entries all fall at the top of the column space, a row count that is not a multiple of 16, and k from one slice's worth of
+    genes to past the widest four-lane slice (2559 f32 genes: two lanes per row then).  "ranges": the same with RANGE_GENES more
+    genes, a product over gene ranges of the panel (the top-of-the-column-space rows then fall in the last range only)."""
     import scipy.sparse as sp
     from singlerust_amd import _ffi
     import singlerust_amd as sr
     monkeypatch.setenv("SRX_SPMM_ROWS", "1")
-    monkeypatch.setenv("SRX_FWD_RANGES", "1" if kernel == "ranges" else "0")
+    if kernel == "ranges":
+        k += RANGE_GENES
     rng = np.random.default_rng(k)
     g = k + 37
     lens = [0, 1, 2, 31, 32, 33, 0, 63, 64, 65, 200, 5, 17, 18, 19, 0, 1]
@@ -364,7 +370,15 @@ def test_forward_spmm_from_row_major_records(ctx, kernel, k, monkeypatch):
     a = sr.IMAnnData.new_basic(x, ctx=ctx, store=1)
     P = rng.standard_normal((k, 64))
     y = np.zeros((n_rows, 64))
-    _ffi.check(_ffi.lib().srx_spmm(a.x().handle, _ffi.ptr(sel), k, _ffi.ptr(P), _ffi.ptr(y), None, None), ctx.handle)
+    ctx.prof_enable(1 << _ffi.K_SPMM_FWD)
+    try:
+        ctx.prof_reset()
+        _ffi.check(_ffi.lib().srx_spmm(a.x().handle, _ffi.ptr(sel), k, _ffi.ptr(P), _ffi.ptr(y), None, None), ctx.handle)
+        launches = ctx.prof_get(_ffi.K_SPMM_FWD)[1]
+    finally:
+        ctx.prof_enable(0)
+        ctx.prof_reset()
+    assert launches == (2 if kernel == "ranges" else 1)          # one launch per gene range
     want = x[:, sel.astype(np.int64)] @ P.astype(np.float32).astype(np.float64)
     assert np.abs(y - want).max() <= 2e-6 * np.abs(want).max()
     assert not y[np.array(lens) == 0].any()
@@ -372,13 +386,13 @@ def test_forward_spmm_from_row_major_records(ctx, kernel, k, monkeypatch):
 
 @pytest.mark.parametrize("kernel", ["ranges", "rows"])
 def test_forward_spmm_row_major_kernels_agree_on_a_bench_shaped_matrix(ctx, kernel, monkeypatch):
-    """60k cells of the bench generator, 2000 selected genes: the new kernel's panel product against scipy (several blocks per wave,
-    every workgroup of the grid busy, rows in length order)."""
+    """60k cells of the bench generator, 2000 selected genes: k_spmm_rows' panel product against scipy (several blocks per wave,
+    every workgroup of the grid busy, rows in length order); "ranges": 2000 + RANGE_GENES selected genes, the product over gene
+    ranges of the panel."""
     import scipy.sparse as sp
     from singlerust_amd import _ffi
     monkeypatch.setenv("SRX_SPMM_ROWS", "1")
-    monkeypatch.setenv("SRX_FWD_RANGES", "1" if kernel == "ranges" else "0")
-    n, g, k = 60_000, 28_000, 2000
+    n, g, k = 60_000, 28_000, 2000 + (RANGE_GENES if kernel == "ranges" else 0)
     m, _ = synth_host(3, n, g, 0.03)
     a = adata_of(m, ctx, 1)
     rng = np.random.default_rng(6)

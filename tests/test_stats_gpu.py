@@ -299,6 +299,42 @@ def test_synth_device_equals_host_generator(ctx):
     assert np.array_equal(statistics.compute_sum(a, sr.Direction.Row), oracle.compute_sum(m, ROW))
 
 
+@pytest.mark.parametrize("n_genes", [9000, 28000])
+def test_generated_handle_leaves_with_the_counts_an_upload_makes(ctx, n_genes):
+    """A generated handle leaves in the state an upload of the same matrix does (srx_synth.h): with the per-gene counts too, for
+    one gene tile (9000 genes) as for several (28000) — its first column statistic is the moments pass alone, no count pass
+    before it (both are SRX_K_MOMENTS launches)."""
+    import ctypes as C
+    import singlerust_amd as sr
+    from singlerust_amd import _ffi as F
+    from singlerust_amd.memory import statistics
+    lib = F.lib()
+    n = 3000
+    p = F.SynthParams()
+    lib.srx_synth_defaults(C.byref(p), 91, n, n_genes, 0.03)
+    h = C.c_void_p()
+    F.check(lib.srx_synth_generate(ctx.handle, C.byref(p), 0, n, F.F32, F.STORE_F32, C.byref(h)), ctx.handle)
+    gen = sr.IMAnnData(sr.DeviceCsr(ctx, h), None, None, range(n), range(n_genes))
+    ip = np.zeros(n + 1, np.uint64)
+    lib.srx_synth_indptr(C.byref(p), 0, n, F.ptr(ip))
+    idx, val = np.zeros(int(ip[-1]), np.uint64), np.zeros(int(ip[-1]), np.float32)
+    lib.srx_synth_fill_host(C.byref(p), 0, n, F.ptr(ip), F.ptr(idx), F.ptr(val))
+    up = sr.IMAnnData.new_basic((n, n_genes, ip, idx, val), ctx=ctx, store=F.STORE_F32)
+    got = {}
+    ctx.prof_enable(1 << F.K_MOMENTS)
+    try:
+        for name, a in (("generated", gen), ("uploaded", up)):
+            ctx.prof_reset()
+            num = statistics.compute_number(a, sr.Direction.Column)
+            got[name] = (ctx.prof_get(F.K_MOMENTS)[1], num, statistics.compute_sum(a, sr.Direction.Column))
+    finally:
+        ctx.prof_enable(0)
+        ctx.prof_reset()
+    assert got["generated"][0] == got["uploaded"][0], {k: v[0] for k, v in got.items()}
+    assert np.array_equal(got["generated"][1], got["uploaded"][1])
+    assert np.array_equal(got["generated"][2], got["uploaded"][2])
+    assert np.array_equal(got["uploaded"][1], oracle.compute_number(oracle.Csr(n, n_genes, ip, idx, val), COLUMN))
+
 def test_log1p_f32_accuracy(ctx):
     """The f32 ln_1p of the fused pass (hardware log2 + Goldberg correction) against f64 log1p over
     the whole positive range, tiny and huge arguments included; F32 stays F32 (transform/mod.rs:43-47)."""
