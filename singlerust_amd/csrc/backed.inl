@@ -34,11 +34,13 @@ struct srx_backed {
     int phase = 0;                      // 0: sweep 1, 1: selected (sweep 2), 2: solved
     // selection
     bool dev_sel = false;
+    // the selection table the compaction of every tile reads: made by select_hvg_device, or (a host-side selection: d_bits /
+    // n_words alone) uploaded once by upload_selection.  Either way it lives in the context's scratch buffer "pca_selbits" from
+    // select to the last Gram tile: one session per context in that span, and no other PCA call on the context
     srx::HvgDev hv;
     srx::Resolved o;
     int l_act = 0, k = 0;
     std::vector<uint64_t> selv;
-    std::vector<int32_t> remap;
     std::vector<double> mu, sd, dinv;
     double trace = 0.0;
     // sweep 2
@@ -105,10 +107,8 @@ template <typename VT>
 static int32_t backed_gram_tile(srx_backed* b, srx_mat* m, RowXf xf) {
     srx_ctx* ctx = b->ctx;
     RowMajor rm;
-    if (b->dev_sel) SRX_TRY(build_tiled_fused(m, b->hv.d_bits, b->hv.n_words, b->k, rm, nullptr, xf, true));
-    else SRX_TRY(build_tiled_fused(m, b->remap, b->k, rm, nullptr, xf, true));
+    SRX_TRY(compact_selection(m, b->hv.d_bits, b->hv.n_words, b->k, rm, xf, true));
     SRX_TRY(launch_gram<VT>(ctx, rm, b->d_gram));            // accumulates into the session's packed matrix
-    if (!rm.perm) SRX_TRY(build_row_order(ctx, rm));          // (made inside the fused compaction where that one ran)
     // keep the row-major records of this tile for the transform: exact-size copies out of the scratch buffers
     RowMajor keep = rm;
     keep.ptr = nullptr;
@@ -255,7 +255,7 @@ static int32_t backed_select_impl(srx_backed* b, uint64_t n_hvg, const uint64_t*
     SRX_TRY(moments_install(acc, b->d_packed));
     const uint64_t G = b->n_cols;
     const uint64_t take = n_hvg < G ? n_hvg : G;
-    b->dev_sel = n_hvg > 0 && take <= (uint64_t)kWave * KG && G <= 65536;
+    b->dev_sel = n_hvg > 0 && take <= kDevSelMaxK && G <= 65536;
     if (n_hvg > 0 && !b->dev_sel) {                       // HighlyVariable(n) on the host (wide matrices)
         std::vector<double> var;
         SRX_TRY(gene_variances(acc, var));
@@ -268,8 +268,8 @@ static int32_t backed_select_impl(srx_backed* b, uint64_t n_hvg, const uint64_t*
     }
     const int k = (int)b->selv.size();
     b->k = k;
-    if ((k + KG - 1) / KG > kWave)
-        return fail(ctx, SRX_E_ARG, "backed: %d selected features exceed the %d the fused compaction takes", k, kWave * KG);
+    if ((uint64_t)k > kDevSelMaxK)
+        return fail(ctx, SRX_E_ARG, "backed: %d selected features exceed the %d a session takes", k, (int)kDevSelMaxK);
     // (the scores are written by the row-major forward kernel: any k — beyond its widest LDS slice it walks gene ranges)
     SRX_TRY(resolve_opts(ctx, opts, k, acc->n_rows_global, b->store == SRX_STORE_F32, b->o, b->l_act));
     if (opts && opts->solver == 2) return fail(ctx, SRX_E_ARG, "backed: only the Gram solver works on row tiles");
@@ -280,7 +280,8 @@ static int32_t backed_select_impl(srx_backed* b, uint64_t n_hvg, const uint64_t*
         SRX_TRY(select_hvg_device(acc, n_hvg, b->o.center, b->o.scale, b->hv));
     } else {
         std::vector<int> order(k), slot_of_sel(k);
-        SRX_TRY(prepare_host_selection(acc, b->selv, b->o, order, slot_of_sel, b->remap, b->mu, b->sd, b->dinv, b->trace));
+        SRX_TRY(prepare_host_selection(acc, b->selv, b->o, order, slot_of_sel, b->mu, b->sd, b->dinv, b->trace));
+        SRX_TRY(upload_selection(ctx, b->selv.data(), b->selv.size(), G, &b->hv.d_bits, &b->hv.n_words));
     }
     b->n_packed = gram_packed_count(k);
     SRX_HIP(ctx, hipMalloc((void**)&b->d_gram, b->n_packed * sizeof(double)));

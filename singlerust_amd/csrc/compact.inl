@@ -1,50 +1,6 @@
 // compact.inl — included by pca_form.hip inside namespace srx (the kernels share pca_internal.hpp's helpers and constants).
 // HVG compaction of the CSR matrix to the selected features: counts, scans, fill passes (row-major records, tile-major views), the selection table in LDS, the owner-record format of the Gram kernel.
 
-// ---- HVG compaction --------------------------------------------------------------------------
-// remap[g] = position of gene g among the selected genes in ascending gene order, or -1.
-__global__ __launch_bounds__(256) void k_compact_count(const int64_t* __restrict__ indptr,
-                                                       const int32_t* __restrict__ idx,
-                                                       const int32_t* __restrict__ remap, uint64_t n_rows,
-                                                       int64_t* __restrict__ counts) {
-    const uint64_t wave = global_wave_id();
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) / kWave;
-    const int lane = lane_id();
-    for (uint64_t r = wave; r < n_rows; r += n_waves) {
-        const int64_t lo = indptr[r], hi = indptr[r + 1];
-        int c = 0;
-        for (int64_t p = lo + lane; p < hi; p += kWave) c += remap[idx[p]] >= 0;
-        c = wave_sum(c);
-        if (lane == 0) counts[r] = c;
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_compact_fill(const int64_t* __restrict__ indptr,
-                                                      const int32_t* __restrict__ idx, const T* __restrict__ vals,
-                                                      const int32_t* __restrict__ remap, uint64_t n_rows,
-                                                      const int64_t* __restrict__ out_ptr,
-                                                      int32_t* __restrict__ out_idx, T* __restrict__ out_vals) {
-    const uint64_t wave = global_wave_id();
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) / kWave;
-    const int lane = lane_id();
-    for (uint64_t r = wave; r < n_rows; r += n_waves) {
-        const int64_t lo = indptr[r], hi = indptr[r + 1];
-        int64_t o = out_ptr[r];
-        for (int64_t base = lo; base < hi; base += kWave) {
-            int64_t p = base + lane;
-            int32_t c = p < hi ? remap[idx[p]] : -1;
-            unsigned long long mask = __ballot(c >= 0);
-            if (c >= 0) {
-                int pos = __popcll(mask & ((1ull << lane) - 1ull));
-                out_idx[o + pos] = c;
-                out_vals[o + pos] = vals[p];
-            }
-            o += __popcll(mask);
-        }
-    }
-}
-
 // ---- exclusive scan of int64 counts (3 phases, 4096 elements per block) ------------------------
 constexpr int kScanItems = 4;
 constexpr int kScanBlock = 1024;
@@ -131,16 +87,15 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_apply(const int64_t* __rest
     if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = *total;
 }
 
-// ---- tile-major layout of the compacted matrix --------------------------------------------------
-// The compacted N x k matrix is stored as n_t = ceil(k / kt) sub-matrices, one per GENE TILE of
-// kt compacted columns, back to back: sub-matrix t holds, row by row, the entries of every
-// cell that fall in columns [kt t, kt t + kt), with LOCAL column indices and row pointers
+// ---- tile-major view of the compacted matrix ---------------------------------------------------
+// The compacted N x k matrix is stored as n_t = ceil(k / KT) sub-matrices, one per GENE TILE of
+// KT = 256 compacted columns, back to back: sub-matrix t holds, row by row, the entries of every
+// cell that fall in columns [KT t, KT t + KT), with LOCAL column indices and row pointers
 // tptr[t*N + i].  A workgroup that owns (tile, row range) therefore streams ONE contiguous
-// index/value range, fully coalesced, instead of ~9-entry pieces of 1.3M rows.
-//   kt = 256 (KT)  SpMM kernels: 256 x 64 panel entries are what LDS holds — 64 KiB as f32
-//                  (forward panel tile, two workgroups per CU), 128 KiB as f64 (transposed
-//                  accumulators, one workgroup per CU);
-//   kt = 128 (KG)  Gram kernel: a 128 x 128 f64 tile of A^T A is 128 KiB.
+// index/value range, fully coalesced, instead of ~9-entry pieces of 1.3M rows.  256 x 64 panel
+// entries are what LDS holds: 64 KiB as f32 (forward panel tile, two workgroups per CU), 128 KiB as
+// f64 (transposed accumulators, one workgroup per CU).  The view is cut from the row-major records
+// (retile: tile cuts of every row, segment lengths, scan, copy), whose rows are sorted by column.
 __global__ void k_seglen(const int64_t* __restrict__ indptr, const int64_t* __restrict__ tp, uint64_t n_rows, int nt,
                          int64_t* __restrict__ seglen) {
     uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -154,44 +109,36 @@ __global__ void k_seglen(const int64_t* __restrict__ indptr, const int64_t* __re
     }
 }
 
-// One entry of a tile-major layout: local column and value side by side, so that every consumer (Gram kernel,
-// forward / transposed SpMM) fetches an entry with ONE 8-byte (f32 storage) or 16-byte (f64) load and the
-// compaction writes it with one store.
+// One entry of a tile-major view: local column and value side by side, so that every consumer (forward / transposed SpMM)
+// fetches an entry with ONE 8-byte (f32 storage) or 16-byte (f64) load.  The row-major record is copied with its column made
+// local to its tile.
 template <typename T>
 __global__ __launch_bounds__(256) void k_retile(const int64_t* __restrict__ indptr, const int64_t* __restrict__ tp,
-                                                const int32_t* __restrict__ idx, const T* __restrict__ vals,
-                                                uint64_t n_rows, int nt, int kt, const int64_t* __restrict__ tptr,
-                                                GramPk<T>* __restrict__ tpk) {
+                                                const GramPk<T>* __restrict__ rm, uint64_t n_rows, int nt,
+                                                const int64_t* __restrict__ tptr, GramPk<T>* __restrict__ tpk) {
     const uint64_t wave = global_wave_id();
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) / kWave;
     const int lane = lane_id();
     for (uint64_t r = wave; r < n_rows; r += n_waves) {
         const int64_t lo = indptr[r], hi = indptr[r + 1];
         for (int64_t p = lo + lane; p < hi; p += kWave) {
-            int32_t c = idx[p];
-            int t = c / kt;
-            int64_t seg_lo = t == 0 ? lo : tp[(uint64_t)(t - 1) * n_rows + r];
-            int64_t dst = tptr[(uint64_t)t * n_rows + r] + (p - seg_lo);
-            GramPk<T> e{};
-            e.j = c - t * kt;
-            e.v = vals[p];
-            tpk[dst] = e;
+            GramPk<T> e = rm[p];
+            const int t = e.j / KT;
+            const int64_t seg_lo = t == 0 ? lo : tp[(uint64_t)(t - 1) * n_rows + r];
+            e.j -= t * KT;
+            tpk[tptr[(uint64_t)t * n_rows + r] + (p - seg_lo)] = e;
         }
     }
 }
 
-// ---- fused HVG compaction straight into the tile-major layouts (<= 64 tiles of 128) ----------------
-// Pass 1 (k_tcount): per cell, the number of kept entries in each 128-column tile (and, summed in
-// pairs, in each 256-column tile).  Kept entries of a row are sorted by compacted column, so the
-// tiles present in a 64-entry chunk are found with a short ballot-match loop; lane t of the wave
-// is the counter of tile t.  Pass 2 (k_tfill) re-reads the row and scatters every kept entry to
-//   tptr[tile*N + i] + (rank of the entry among the row's kept entries - kept entries in earlier tiles)
-// in BOTH layouts.  The scans of the counts in between give tptr.
-// Membership + compacted column of a gene WITHOUT a G-entry remap table in L2 (a 4-byte gather per
-// non-zero drags a 64-byte line each: 70 GB of L2 traffic at c3): the selection is a bitmask
-// (G/32 words) plus the number of selected genes before each word, both staged in LDS (7 KB at
-// G = 28k); column = prefix[w] + popcount(bits[w] below the gene's bit).
-// ---- owner buckets of the Gram kernel (k_gram_stripes, below) -----------------------------------------
+// ---- HVG compaction: count, scan, fill into the row-major records ----------------------------------------------------------
+// The count pass makes the number of kept entries of every row, the exclusive scan of them the row pointers, and the fill
+// pass re-reads each row and stores its kept entries in order (k_rowcount + k_tfill; with the 16-bit index mirror the count
+// pass leaves a list of what it kept, k_rowcount_list + k_tfill_list, below).
+// Membership + compacted column of a gene WITHOUT a G-entry remap table in L2 (a 4-byte gather per non-zero drags a 64-byte
+// line each: 70 GB of L2 traffic at c3): the selection is a bitmask (G/32 words) plus the number of selected genes before each
+// word, staged in LDS where it fits (7 KB at G = 28k), read from global memory otherwise; column = prefix[w] + popcount(bits[w]
+// below the gene's bit).
 struct SelLds {
     const uint32_t* bits;
     const uint32_t* prefix;
@@ -201,14 +148,20 @@ struct SelLds {
         return (w & bit) ? (int)(prefix[gene >> 5] + __popc(w & (bit - 1u))) : -1;
     }
 };
+// LDS: the table is copied to `lds` (2 n_words words); otherwise it is read where it is
+template <bool LDS>
 __device__ __forceinline__ SelLds stage_selection(const uint32_t* __restrict__ g_bits,
                                                   const uint32_t* __restrict__ g_prefix, int n_words, uint32_t* lds) {
-    for (int e = threadIdx.x; e < n_words; e += blockDim.x) {
-        lds[e] = g_bits[e];
-        lds[n_words + e] = g_prefix[e];
+    if constexpr (!LDS) {
+        return SelLds{g_bits, g_prefix};
+    } else {
+        for (int e = threadIdx.x; e < n_words; e += blockDim.x) {
+            lds[e] = g_bits[e];
+            lds[n_words + e] = g_prefix[e];
+        }
+        __syncthreads();
+        return SelLds{lds, lds + n_words};
     }
-    __syncthreads();
-    return SelLds{lds, lds + n_words};
 }
 
 constexpr int kFillUnroll = 4;       // 64-entry chunks of a row in flight per wave in k_tfill
@@ -218,17 +171,21 @@ __device__ __forceinline__ uint64_t next_compact_row(uint64_t r, uint64_t n_wave
     return ((r + 1) % kCompactRows) ? r + 1 : r + 1 + (n_waves - 1) * kCompactRows;
 }
 
-// Kept entries per row, nothing else (the row-major layout's row lengths; the tile counters of k_tcount are only wanted by
-// the matrix-free solver's 256-tiled view): the bit of the gene in the selection mask is the whole test — one LDS read per
-// entry, no prefix lookup, no LDS atomic.  The mask holds at most k bits (k_sel_finish / the host route make sure).
-template <typename I>
+// Kept entries per row, nothing else (the row-major layout's row lengths): the bit of the gene in the selection mask is the
+// whole test — one read of the mask per entry (from LDS where it fits), no prefix lookup, no LDS atomic.  The mask holds at most k
+// bits (k_sel_finish / upload_selection make sure).
+template <typename I, bool LDS>
 __global__ __launch_bounds__(256) void k_rowcount(const int64_t* __restrict__ indptr, const I* __restrict__ idx,
                                                   const uint32_t* __restrict__ g_bits, int n_words, uint64_t n_rows,
                                                   int64_t* __restrict__ cntrow) {
-    extern __shared__ double lds_raw[];
-    uint32_t* bits = reinterpret_cast<uint32_t*>(lds_raw);
-    for (int e = threadIdx.x; e < n_words; e += blockDim.x) bits[e] = g_bits[e];
-    __syncthreads();
+    const uint32_t* bits = g_bits;
+    if constexpr (LDS) {
+        extern __shared__ double lds_raw[];
+        uint32_t* s_bits = reinterpret_cast<uint32_t*>(lds_raw);
+        for (int e = threadIdx.x; e < n_words; e += blockDim.x) s_bits[e] = g_bits[e];
+        __syncthreads();
+        bits = s_bits;
+    }
     const uint64_t wave = global_wave_id();
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) / kWave;
     const int lane = lane_id();
@@ -261,7 +218,7 @@ __global__ __launch_bounds__(256) void k_rowcount(const int64_t* __restrict__ in
 // word (position in the row << 16 | compacted column) at kept[indptr[r] + rank], i.e. at the start of the row's own span of a
 // scratch array as long as the matrix — so that the fill pass never walks the column indices again: per row it reads its
 // ~72 words (one coalesced load), gathers the ~72 values and stores the entries.  Needs n_cols <= 65536 (16-bit positions and
-// columns) and the row-major layout alone (no 256-tiled view).
+// columns) and k <= 65535 (0xffff marks a dropped gene).
 // Round 5: the same list, 0.82 -> 0.67 ms.  The selection is expanded into a 16-bit table in LDS — gene -> compacted column,
 // 0xffff = dropped, one entry more for the lanes behind a row's end — so that the test of an entry is ONE 2-byte LDS read at the
 // gene's own address (round 4: the mask word and the prefix word, two reads: the LDS pipe was its bound); a lane's rank comes
@@ -534,106 +491,30 @@ __global__ __launch_bounds__(256) void k_tfill_list(const int64_t* __restrict__ 
     }
 }
 
-template <typename I>
-__global__ __launch_bounds__(256) void k_tcount(const int64_t* __restrict__ indptr, const I* __restrict__ idx,
-                                                const uint32_t* __restrict__ g_bits,
-                                                const uint32_t* __restrict__ g_prefix, int n_words, uint64_t n_rows,
-                                                int nt128, int nt256, int k, int64_t* __restrict__ cntrow,
-                                                int64_t* __restrict__ cnt256) {
-    extern __shared__ double lds_raw[];
-    const SelLds sel = stage_selection(g_bits, g_prefix, n_words, reinterpret_cast<uint32_t*>(lds_raw));
-    const uint64_t wave = global_wave_id();
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) / kWave;
-    const int lane = lane_id();
-    // per-wave tile counters in LDS (after the selection table): a kept entry is one ds_add_u32 on its
-    // tile's counter — ~5 active lanes per 64-entry chunk — instead of a ballot-match loop over the tiles
-    // present in the chunk (the loop made this pass VALU-bound);
-    // one 64-counter row per row of the wave's current block of kCompactRows rows
-    uint32_t* tcnt = reinterpret_cast<uint32_t*>(lds_raw) + 2 * n_words + (threadIdx.x / kWave) * (kCompactRows * kWave);
-#pragma unroll
-    for (int i = 0; i < kCompactRows; ++i) tcnt[i * kWave + lane] = 0u;
-    // A wave takes kCompactRows CONSECUTIVE rows at a time and writes their counters out together: lane (tile, row)
-    // stores 8 bytes next to its 7 neighbours, i.e. one full 64-byte line per tile — stored row by row, the 24
-    // strided 8-byte counters of a row cost ~44 bytes of HBM write each (1.39 GB written for 0.25 GB of counters).
-    // Lane l of a chunk takes entry l (2-byte loads): consecutive entries of a row are ~1 bitmask word apart, so
-    // the 64 lookups of a chunk fall into 64 different LDS banks — 8 consecutive entries per lane (16-byte loads)
-    // were tried and cost an 8-way bank conflict per lookup.  kCountUnroll chunks (1024 entries) are issued
-    // together: with 4 a ~840-entry row was 4 dependent round trips to HBM.
-    constexpr int kCountUnroll = 16;
-    for (uint64_t r0 = wave * kCompactRows; r0 < n_rows; r0 += n_waves * kCompactRows) {
-        const int nr = (int)(n_rows - r0 < (uint64_t)kCompactRows ? n_rows - r0 : kCompactRows);
-        for (int i = 0; i < nr; ++i) {
-            const int64_t lo = indptr[r0 + i], hi = indptr[r0 + i + 1];
-            uint32_t* row_cnt = tcnt + i * kWave;
-            for (int64_t base = lo; base < hi; base += kCountUnroll * kWave) {
-                int32_t g[kCountUnroll];
-#pragma unroll
-                for (int u = 0; u < kCountUnroll; ++u) {
-                    const int64_t p = base + u * kWave + lane;
-                    g[u] = p < hi ? (int32_t)idx[p] : -1;
-                }
-#pragma unroll
-                for (int u = 0; u < kCountUnroll; ++u) {
-                    int col = g[u] >= 0 ? sel.column(g[u]) : -1;             // -1 for dropped entries
-                    if (col >= k) col = -1;          // only a broken selection (NaN variances) has such columns: dropped
-                    if (col >= 0) __hip_atomic_fetch_add(&row_cnt[col >> 7], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        // lane q -> (tile q / 8, row q % 8)
-        if (lane < nr) {                                   // kept entries of row r0 + lane (the row-major layout's row length)
-            uint32_t tot = 0;
-            for (int t = 0; t < nt128; ++t) tot += tcnt[lane * kWave + t];
-            cntrow[r0 + lane] = (int64_t)tot;
-        }
-        for (int q = lane; q < nt256 * kCompactRows; q += kWave) {
-            const int t = q / kCompactRows, i = q % kCompactRows;
-            if (i < nr) cnt256[(uint64_t)t * n_rows + r0 + i] = (int64_t)(tcnt[i * kWave + 2 * t] + tcnt[i * kWave + 2 * t + 1]);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-        for (int i = 0; i < kCompactRows; ++i) tcnt[i * kWave + lane] = 0u;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    }
-}
-
 // XF: `vals` are the raw values and the kept entries are stored as ln_1p(f64(v) * scale_row), rounded once (RowXf).
-template <typename T, typename I, bool XF>
+// LDS: the selection table staged there (stage_selection).
+template <typename T, typename I, bool XF, bool LDS>
 __global__ __launch_bounds__(256) void k_tfill(const int64_t* __restrict__ indptr, const I* __restrict__ idx,
                                                const T* __restrict__ vals, const uint32_t* __restrict__ g_bits,
-                                               const uint32_t* __restrict__ g_prefix, int n_words, uint64_t n_rows,
-                                               int nt256, int k, const int64_t* __restrict__ cnt256,
-                                               const int64_t* __restrict__ rm_ptr,
-                                               const int64_t* __restrict__ tptr256, const double* __restrict__ row_sum,
-                                               double target, GramPk<T>* __restrict__ rm, GramPk<T>* __restrict__ pk256) {
+                                               const uint32_t* __restrict__ g_prefix, int n_words, uint64_t n_rows, int k,
+                                               const int64_t* __restrict__ rm_ptr, const double* __restrict__ row_sum,
+                                               double target, GramPk<T>* __restrict__ rm) {
     extern __shared__ double lds_raw[];
     __shared__ Log1pTabEntry s_tab[XF ? 128 : 1];
     if constexpr (XF) stage_log1p_table(s_tab);
-    const SelLds sel = stage_selection(g_bits, g_prefix, n_words, reinterpret_cast<uint32_t*>(lds_raw));
+    const SelLds sel = stage_selection<LDS>(g_bits, g_prefix, n_words, reinterpret_cast<uint32_t*>(lds_raw));
+    if constexpr (XF && !LDS) __syncthreads();          // (the logarithm table; stage_selection<true> waits for both)
     const uint64_t wave = global_wave_id();
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) / kWave;
     const int lane = lane_id();
     for (uint64_t r = (wave * kCompactRows); r < n_rows; r = next_compact_row(r, n_waves)) {
         const int64_t lo = indptr[r], hi = indptr[r + 1];
-        // lane t: kept entries before 256-tile t in this row (exclusive prefix over the tile counters)
-        const int c_t = lane < nt256 ? (int)cnt256[(uint64_t)lane * n_rows + r] : 0;
-        int inc = c_t;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const int o = __shfl_up(inc, off, kWave);
-            if (lane >= off) inc += o;
-        }
-        const int before256 = inc - c_t;
-        // destination bias of each tile: tptr - (kept entries before the tile)
-        const int64_t off256 = (lane < nt256 ? tptr256[(uint64_t)lane * n_rows + r] : 0) - before256;
         const int64_t row_base = rm_ptr[r];
-        double scale = 1.0, row_table = 0.0;
+        double scale = 1.0;
         if constexpr (XF) {
             const double sr = row_sum[r];
             scale = sr == 0.0 ? 0.0 : target / sr;      // scale/mod.rs:9-15
         }
-        (void)row_table;
         int rank0 = 0;                                  // kept entries of the row before this chunk
         // (tried and slower at c3: 16 chunks in flight, 2.42 ms — the ballots / shuffles of the masked-out tail
         //  chunks cost more than the loads gain; parking the kept entries in LDS and writing them out per row,
@@ -652,8 +533,6 @@ __global__ __launch_bounds__(256) void k_tfill(const int64_t* __restrict__ indpt
                 int32_t c = g[u] >= 0 ? sel.column(g[u]) : -1;
                 if (c >= k) c = -1;
                 const unsigned long long mask = __ballot(c >= 0);
-                const int cc = c >= 0 ? c : 0;
-                const int64_t o256 = __shfl(off256, cc >> 8, kWave);   // shuffles run with all lanes active
                 if (c >= 0) {
                     const int rank = rank0 + __popcll(mask & ((1ull << lane) - 1ull));
                     T v = vals[p];
@@ -662,10 +541,6 @@ __global__ __launch_bounds__(256) void k_tfill(const int64_t* __restrict__ indpt
                     e.j = c;
                     e.v = v;
                     rm[row_base + rank] = e;
-                    if (nt256 > 0) {
-                        e.j = c & 255;
-                        pk256[o256 + rank] = e;
-                    }
                 }
                 rank0 += __popcll(mask);
             }

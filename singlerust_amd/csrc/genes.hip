@@ -13,7 +13,7 @@
 // a per-block partial buffer; a second tiny kernel sums the partials in fixed order.
 //
 // Algorithmic bytes: nnz*(4 + s_v) + (N+1)*8 + G*24.
-#include "common.hpp"
+#include "pca_internal.hpp"     // (GramPk: the records whose tile cuts k_tile_ptr also finds)
 #include "log1p64.hpp"
 
 #include <algorithm>
@@ -27,8 +27,13 @@ constexpr int kMaxTileGenes = 10000;      // 10000 * 16 B (two 64-bit sums per g
                                           // the other way round, 5 / 6 tiles: 3.28 / 3.66 ms (round 4 A/B, SRX_EXP_TILE_GENES)
 constexpr int kMomThreads = 1024;
 
-// lower_bound of `bound` inside each row's sorted column list, for the interior tile cuts.
-__global__ void k_tile_ptr(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+// lower_bound of `bound` inside each row's sorted column list, for the interior tile cuts.  E: a column index (the gene tiles
+// of X) or a record of the compacted matrix (the 256-column tiles of its tile-major view, retile).
+__device__ __forceinline__ int32_t entry_column(int32_t c) { return c; }
+template <typename T>
+__device__ __forceinline__ int32_t entry_column(const GramPk<T>& e) { return e.j; }
+template <typename E>
+__global__ void k_tile_ptr(const int64_t* __restrict__ indptr, const E* __restrict__ idx,
                            uint64_t n_rows, int n_tiles, int tile_genes, int64_t* __restrict__ tp) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t total = (uint64_t)(n_tiles - 1) * n_rows;
@@ -39,7 +44,7 @@ __global__ void k_tile_ptr(const int64_t* __restrict__ indptr, const int32_t* __
         int64_t lo = indptr[r], hi = indptr[r + 1];
         while (lo < hi) {
             int64_t mid = lo + ((hi - lo) >> 1);
-            if (idx[mid] < bound) lo = mid + 1; else hi = mid;
+            if (entry_column(idx[mid]) < bound) lo = mid + 1; else hi = mid;
         }
         tp[i] = lo;
     }
@@ -591,17 +596,21 @@ static void tile_geometry(const srx_mat* m, int& n_tiles, int& tile_genes) {
     tile_genes = (int)((G + n_tiles - 1) / n_tiles);
 }
 
-int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const int32_t* idx, uint64_t n_rows, int n_tiles,
-                        int tile_genes, int64_t* tp) {
+template <typename E>
+int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const E* idx, uint64_t n_rows, int n_tiles, int tile_genes,
+                        int64_t* tp) {
     uint64_t total = (uint64_t)(n_tiles - 1) * n_rows;
     uint64_t g = (total + 255) / 256;
     if (g < 1) g = 1;
     if (g > 65535) g = 65535;
-    hipLaunchKernelGGL(k_tile_ptr, dim3((unsigned)g), dim3(256), 0, ctx->stream, indptr, idx, n_rows, n_tiles,
+    hipLaunchKernelGGL(k_tile_ptr<E>, dim3((unsigned)g), dim3(256), 0, ctx->stream, indptr, idx, n_rows, n_tiles,
                        tile_genes, tp);
     SRX_HIP(ctx, hipGetLastError());
     return SRX_OK;
 }
+template int32_t launch_tile_ptr<int32_t>(srx_ctx*, const int64_t*, const int32_t*, uint64_t, int, int, int64_t*);
+template int32_t launch_tile_ptr<GramPk<float>>(srx_ctx*, const int64_t*, const GramPk<float>*, uint64_t, int, int, int64_t*);
+template int32_t launch_tile_ptr<GramPk<double>>(srx_ctx*, const int64_t*, const GramPk<double>*, uint64_t, int, int, int64_t*);
 
 // Both pattern-only structures of a fresh CSR matrix in ONE walk over its 32-bit column indices: the 16-bit mirror (entries
 // past nnz: 0, the arrays are padded for the vector walks) and the NB = n_tiles - 1 interior gene-tile cuts of every row.  A

@@ -37,26 +37,24 @@
 
 namespace srx {
 
-// Host-side view of an explicit selection: ascending-gene order, remap table, and the all-cells mean / std
-// (ddof 0) of the selected genes from the (global) moments of `m`.
+// Host-side view of an explicit selection: ascending-gene order, and the all-cells mean / std (ddof 0) of the selected genes
+// from the (global) moments of `m`.
 static int32_t prepare_host_selection(srx_mat* m, const std::vector<uint64_t>& selv, const Resolved& o,
                                       std::vector<int>& order, std::vector<int>& slot_of_sel,
-                                      std::vector<int32_t>& remap, std::vector<double>& mu, std::vector<double>& sd,
+                                      std::vector<double>& mu, std::vector<double>& sd,
                                       std::vector<double>& dinv, double& trace) {
     srx_ctx* ctx = m->ctx;
     const uint64_t G = m->n_cols;
     const int k = (int)selv.size();
     const double Nd = (double)m->n_rows_global;
-    // ascending-gene-order view of the selection; remap table; permutation back to selection order
+    // ascending-gene-order view of the selection; permutation back to selection order
     std::iota(order.begin(), order.end(), 0);
     std::sort(order.begin(), order.end(), [&](int a, int b) { return selv[a] < selv[b]; });
-    remap.assign(G, -1);
     for (int s = 0; s < k; ++s) {
         uint64_t g = selv[order[s]];
         if (g >= G) return fail(ctx, SRX_E_BOUNDS, "selected feature index %llu out of bounds (n_vars = %llu)",
                                 (unsigned long long)g, (unsigned long long)G);
-        if (remap[g] >= 0) return fail(ctx, SRX_E_ARG, "selected feature index %llu appears twice", (unsigned long long)g);
-        remap[g] = s;
+        if (s > 0 && g == selv[order[s - 1]]) return fail(ctx, SRX_E_ARG, "selected feature index %llu appears twice", (unsigned long long)g);
         slot_of_sel[order[s]] = s;
     }
     // all-cells column mean / std (ddof 0) of the selected genes from the one moments pass
@@ -82,8 +80,8 @@ static int32_t prepare_host_selection(srx_mat* m, const std::vector<uint64_t>& s
 }
 
 // The in-place normalise + log1p of a matrix whose pipeline has been reading it raw (RowXf) and did not get as far as the
-// moments pass that stores the transformed values itself (an error on the way, or a selection too wide for the fused
-// compaction): from the row sums in m->d_row_sum, on the context's stream.
+// moments pass that stores the transformed values itself (an error on the way): from the row sums in m->d_row_sum, on the
+// context's stream.
 static int32_t launch_writeback(srx_mat* m) {
     if (!m->lazy_pending) return SRX_OK;
     m->lazy_pending = false;
@@ -113,8 +111,8 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
     srx_pca_state& st = m->pca;
     st.valid = false;
     const uint64_t G = m->n_cols;
-    // the fused compaction holds one tile counter per lane (<= 64 tiles of 128) and the rank kernel is O(G^2)
-    const bool dev_sel = hvg_n > 0 && (hvg_n < G ? hvg_n : G) <= (uint64_t)kWave * KG && G <= 65536;
+    // the device selection's rank kernel is O(G^2); kDevSelMaxK is the envelope the device selection is tested in
+    const bool dev_sel = hvg_n > 0 && (hvg_n < G ? hvg_n : G) <= kDevSelMaxK && G <= 65536;
     std::vector<uint64_t> selv;
     if (dev_sel) selv.resize(hvg_n < G ? hvg_n : G);                          // filled after the solve
     else if (sel) selv.assign(sel, sel + k64);
@@ -127,40 +125,28 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
     SRX_TRY(resolve_opts(ctx, opts, k, Ng, is_f32(m), o, l_act));
 
     std::vector<int> order(k), slot_of_sel(k);
-    std::vector<int32_t> remap;
     std::vector<double> mu(k), sd(k), dinv(k);
     double trace = 0.0;
     const double Nd = (double)Ng;
-    HvgDev hv;
+    HvgDev hv;                                    // (an explicit selection fills d_bits / n_words alone)
     if (dev_sel) {
         Range r_("srx:select_hvg");
         ProfScope ps_sel(ctx, SRX_K_SELECT, (double)G * 24.0);
         SRX_TRY(select_hvg_device(m, hvg_n, o.center, o.scale, hv));
     } else {
-        SRX_TRY(prepare_host_selection(m, selv, o, order, slot_of_sel, remap, mu, sd, dinv, trace));
+        SRX_TRY(prepare_host_selection(m, selv, o, order, slot_of_sel, mu, sd, dinv, trace));
+        SRX_TRY(upload_selection(ctx, selv.data(), selv.size(), G, &hv.d_bits, &hv.n_words));
     }
     std::vector<double> mu_eff = mu;
     if (!o.center) std::fill(mu_eff.begin(), mu_eff.end(), 0.0);
 
-    // tile-major views of X[:, sel]: fused count/fill when the tile counters fit a wave, else the
-    // general route through a row-major compacted CSR
+    // X[:, sel] as row-major records; the 256-tiled view of them only where something reads it (the matrix-free solver)
     Tiled t256;
     RowMajor rm;
     Range r_compact("srx:compact");
-    // the 256-tiled view only where something reads it
     const bool need_t256 = o.solver == 2;
-    if (dev_sel) {
-        SRX_TRY(build_tiled_fused(m, hv.d_bits, hv.n_words, k, rm, need_t256 ? &t256 : nullptr, xf, o.solver == 1));
-    } else if ((k + KG - 1) / KG <= kWave) {
-        SRX_TRY(build_tiled_fused(m, remap, k, rm, need_t256 ? &t256 : nullptr, xf, o.solver == 1));
-    } else {
-        // the general route reads stored values: the matrix is transformed in place first
-        if (xf.row_sum) SRX_TRY(launch_writeback(m));
-        CompactCsr cc;
-        SRX_TRY(build_compact(m, remap, k, cc, rm));
-        if (need_t256) SRX_TRY(retile(m, cc, KT, t256));
-    }
-    if (!need_t256 && !rm.perm) SRX_TRY(build_row_order(ctx, rm));      // the transform walks rows by length (the fused compaction has made it already)
+    SRX_TRY(compact_selection(m, hv.d_bits, hv.n_words, k, rm, xf, o.solver == 1));
+    if (need_t256) SRX_TRY(retile(m, rm, t256));
     st.info = srx_pca_info{};
     st.info.n_cells_global = Ng;
     st.info.k = (uint32_t)k;
@@ -376,9 +362,10 @@ int32_t srx_pipeline(srx_mat* m, double target_sum, uint64_t n_hvg, const srx_pc
     }
     (void)hipEventRecord(ev[2], ctx->stream);
     // FeatureSelection::HighlyVariable(n_hvg): on the device, inside pca_device (the selection is fetched with the
-    // other results once the solve is over); the host route only for shapes the device kernels do not take
+    // other results once the solve is over); the host route for the shapes outside the device selection's envelope: G <= 65536
+    // (its rank kernel is O(G^2)) and take <= kDevSelMaxK (what the device selection is tested in), as in pca_device
     std::vector<uint64_t> sel;
-    const bool dev_sel = !m->csc && n_hvg > 0 && take <= (uint64_t)kWave * KG && m->n_cols <= 65536;
+    const bool dev_sel = !m->csc && n_hvg > 0 && take <= kDevSelMaxK && m->n_cols <= 65536;
     if (rc == SRX_OK && m->csc) {                 // HighlyVariable(n) with the CSC variance (csc.rs:164-177)
         uint64_t n_out = 0;
         sel.resize(n_hvg < m->n_rows ? n_hvg : m->n_rows);

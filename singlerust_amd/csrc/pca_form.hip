@@ -102,143 +102,54 @@ int32_t scan_exclusive(srx_ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d
     return SRX_OK;
 }
 
-// (idx, vals) of a compacted CSR -> packed row-major records
-template <typename T>
-__global__ void k_pack_records(const int32_t* __restrict__ idx, const T* __restrict__ vals, uint64_t n,
-                               GramPk<T>* __restrict__ out) {
-    uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (; e < n; e += stride) {
-        GramPk<T> r{};
-        r.j = idx[e];
-        r.v = vals[e];
-        out[e] = r;
-    }
-}
-
-// X[:, sel] -> row-major compacted CSR (count, scan, fill); columns renumbered by `remap`.  General route
-// (more than 8192 selected features); `rm` receives the packed-record view of it.
-int32_t build_compact(srx_mat* m, const std::vector<int32_t>& remap, int k, CompactCsr& c, RowMajor& rm) {
+// Tile-major view of the row-major records for tiles of KT compacted columns (cut, scan, copy).
+int32_t retile(srx_mat* m, const RowMajor& rm, Tiled& t) {
     srx_ctx* ctx = m->ctx;
-    const uint64_t N = m->n_rows;
-    int32_t* d_remap;
-    int64_t *d_counts, *d_total;
-    SRX_TRY(scratch(ctx, "pca_remap", (remap.size() ? remap.size() : 1) * sizeof(int32_t), (void**)&d_remap));
-    SRX_TRY(h2d(ctx, d_remap, remap.data(), remap.size() * sizeof(int32_t)));
-    SRX_TRY(scratch(ctx, "pca_counts", (N ? N : 1) * sizeof(int64_t), (void**)&d_counts));
-    SRX_TRY(scratch(ctx, "pca_rm_ptr", (N + 1) * sizeof(int64_t), (void**)&c.indptr));
-    const double in_bytes = (double)m->nnz * 4.0 * 2.0 + (double)(N + 1) * 8.0 * 2.0;   // idx read by count + fill
-    ProfScope ps(ctx, SRX_K_COMPACT, in_bytes);
-    hipLaunchKernelGGL(k_compact_count, dim3(grid_rows(ctx, N, 4)), dim3(256), 0, ctx->stream, m->d_indptr,
-                       m->d_indices, d_remap, N, d_counts);
-    SRX_TRY(scan_exclusive(ctx, d_counts, N, c.indptr, &d_total));
-    int64_t total = 0;
-    SRX_TRY(d2h(ctx, &total, d_total, sizeof(int64_t)));
-    c.nnz = (uint64_t)total;
-    c.n_rows = N;
-    c.k = k;
-    const size_t vb = val_bytes(m);
-    SRX_TRY(scratch(ctx, "pca_cidx", (c.nnz ? c.nnz : 1) * sizeof(int32_t), (void**)&c.idx));
-    SRX_TRY(scratch(ctx, "pca_cvals", (c.nnz ? c.nnz : 1) * vb, &c.vals));
-    const size_t pb = vb == 4 ? sizeof(GramPk<float>) : sizeof(GramPk<double>);
-    SRX_TRY(scratch(ctx, "pca_rm_pk", (c.nnz + 64) * pb, &rm.pk));
-    // the 64 entries behind the last row are READ by the forward kernel (a row's last chunk runs past its end: value masked
-    // to 0, column used as is): they must name a real column, or 0 x panel[garbage] is NaN
-    SRX_HIP(ctx, hipMemsetAsync((char*)rm.pk + c.nnz * pb, 0, 64 * pb, ctx->stream));
-    const unsigned pg = (unsigned)std::min<uint64_t>((c.nnz + 255) / 256 + 1, 65536);
-    if (is_f32(m)) {
-        hipLaunchKernelGGL((k_compact_fill<float>), dim3(grid_rows(ctx, N, 4)), dim3(256), 0, ctx->stream, m->d_indptr,
-                           m->d_indices, (const float*)m->d_values, d_remap, N, c.indptr, c.idx, (float*)c.vals);
-        hipLaunchKernelGGL((k_pack_records<float>), dim3(pg), dim3(256), 0, ctx->stream, c.idx, (const float*)c.vals, c.nnz,
-                           (GramPk<float>*)rm.pk);
-    } else {
-        hipLaunchKernelGGL((k_compact_fill<double>), dim3(grid_rows(ctx, N, 4)), dim3(256), 0, ctx->stream,
-                           m->d_indptr, m->d_indices, (const double*)m->d_values, d_remap, N, c.indptr, c.idx,
-                           (double*)c.vals);
-        hipLaunchKernelGGL((k_pack_records<double>), dim3(pg), dim3(256), 0, ctx->stream, c.idx, (const double*)c.vals, c.nnz,
-                           (GramPk<double>*)rm.pk);
-    }
-    SRX_HIP(ctx, hipGetLastError());
-    rm.n_rows = N;
-    rm.nnz = c.nnz;
-    rm.k = k;
-    rm.ptr = c.indptr;
-    if (ctx->prof_mask & (1u << SRX_K_COMPACT)) ctx->prof[SRX_K_COMPACT].bytes += (double)c.nnz * (4.0 + vb) * 3.0;
-    return SRX_OK;
-}
-
-// Tile-major copy of a compacted CSR for gene tiles of kt columns (cut, scan, copy).
-int32_t retile(srx_mat* m, const CompactCsr& c, int kt, Tiled& t) {
-    srx_ctx* ctx = m->ctx;
-    const uint64_t N = c.n_rows;
-    const size_t vb = val_bytes(m);
-    const std::string tag = "pca_t" + std::to_string(kt) + "_";
+    const uint64_t N = rm.n_rows;
     t.n_rows = N;
-    t.nnz = c.nnz;
-    t.k = c.k;
-    t.kt = kt;
-    t.nt = (c.k + kt - 1) / kt;
+    t.nnz = rm.nnz;
+    t.k = rm.k;
+    t.nt = (rm.k + KT - 1) / KT;
     int64_t* d_tp = nullptr;
     if (t.nt > 1) {
         SRX_TRY(scratch(ctx, "pca_tp", (size_t)(t.nt - 1) * (N ? N : 1) * sizeof(int64_t), (void**)&d_tp));
-        SRX_TRY(launch_tile_ptr(ctx, c.indptr, c.idx, N, t.nt, kt, d_tp));
+        if (is_f32(m)) SRX_TRY(launch_tile_ptr(ctx, rm.ptr, (const GramPk<float>*)rm.pk, N, t.nt, KT, d_tp));
+        else SRX_TRY(launch_tile_ptr(ctx, rm.ptr, (const GramPk<double>*)rm.pk, N, t.nt, KT, d_tp));
     }
     const uint64_t nseg = (uint64_t)t.nt * N;
     int64_t* d_seglen;
     SRX_TRY(scratch(ctx, "pca_seglen", (nseg ? nseg : 1) * sizeof(int64_t), (void**)&d_seglen));
-    SRX_TRY(scratch(ctx, (tag + "ptr").c_str(), (nseg + 1) * sizeof(int64_t), (void**)&t.tptr));
+    SRX_TRY(scratch(ctx, "pca_t256_ptr", (nseg + 1) * sizeof(int64_t), (void**)&t.tptr));
     uint64_t g = (nseg + 255) / 256;
     if (g < 1) g = 1;
     if (g > 16384) g = 16384;
-    hipLaunchKernelGGL(k_seglen, dim3((unsigned)g), dim3(256), 0, ctx->stream, c.indptr, d_tp, N, t.nt, d_seglen);
+    hipLaunchKernelGGL(k_seglen, dim3((unsigned)g), dim3(256), 0, ctx->stream, rm.ptr, d_tp, N, t.nt, d_seglen);
     SRX_TRY(scan_exclusive(ctx, d_seglen, nseg, t.tptr, nullptr));
     // +64 records of padding: the forward kernel reads 16-wide chunks unconditionally
-    const size_t pb = vb == 4 ? sizeof(GramPk<float>) : sizeof(GramPk<double>);
-    SRX_TRY(scratch(ctx, (tag + "pk").c_str(), (c.nnz + 64) * pb, &t.tpk));
-    SRX_HIP(ctx, hipMemsetAsync((char*)t.tpk + c.nnz * pb, 0, 64 * pb, ctx->stream));
+    const size_t pb = is_f32(m) ? sizeof(GramPk<float>) : sizeof(GramPk<double>);
+    SRX_TRY(scratch(ctx, "pca_t256_pk", (rm.nnz + 64) * pb, &t.tpk));
+    SRX_HIP(ctx, hipMemsetAsync((char*)t.tpk + rm.nnz * pb, 0, 64 * pb, ctx->stream));
     if (is_f32(m))
-        hipLaunchKernelGGL((k_retile<float>), dim3(grid_rows(ctx, N, 4)), dim3(256), 0, ctx->stream, c.indptr, d_tp, c.idx,
-                           (const float*)c.vals, N, t.nt, kt, t.tptr, (GramPk<float>*)t.tpk);
+        hipLaunchKernelGGL((k_retile<float>), dim3(grid_rows(ctx, N, 4)), dim3(256), 0, ctx->stream, rm.ptr, d_tp,
+                           (const GramPk<float>*)rm.pk, N, t.nt, t.tptr, (GramPk<float>*)t.tpk);
     else
-        hipLaunchKernelGGL((k_retile<double>), dim3(grid_rows(ctx, N, 4)), dim3(256), 0, ctx->stream, c.indptr, d_tp,
-                           c.idx, (const double*)c.vals, N, t.nt, kt, t.tptr, (GramPk<double>*)t.tpk);
+        hipLaunchKernelGGL((k_retile<double>), dim3(grid_rows(ctx, N, 4)), dim3(256), 0, ctx->stream, rm.ptr, d_tp,
+                           (const GramPk<double>*)rm.pk, N, t.nt, t.tptr, (GramPk<double>*)t.tpk);
     SRX_HIP(ctx, hipGetLastError());
     return SRX_OK;
 }
 
-// Fast path: the 256-tiled layout and the row-major records straight from X (count, two scans, fill); needs
-// <= 64 tiles of 128 columns (k <= 8192) because lane t of a wave is the counter of tile t.
-static int32_t alloc_tiled(srx_mat* m, uint64_t N, uint64_t nnz, int k, int kt, Tiled& t) {
-    srx_ctx* ctx = m->ctx;
-    const size_t vb = val_bytes(m);
-    const std::string tag = "pca_t" + std::to_string(kt) + "_";
-    t.n_rows = N;
-    t.nnz = nnz;
-    t.k = k;
-    t.kt = kt;
-    t.nt = (k + kt - 1) / kt;
-    const size_t pb = vb == 4 ? sizeof(GramPk<float>) : sizeof(GramPk<double>);
-    SRX_TRY(scratch(ctx, (tag + "pk").c_str(), (nnz + 64) * pb, &t.tpk));
-    SRX_HIP(ctx, hipMemsetAsync((char*)t.tpk + nnz * pb, 0, 64 * pb, ctx->stream));
-    return SRX_OK;
-}
-
-// `d_sel`: n_words selection bits followed by n_words prefix counts, on the device (the compacted column of a
-// gene is its rank among the selected genes in ascending gene order)
-int32_t build_tiled_fused(srx_mat* m, const uint32_t* d_sel, int n_words, int k, RowMajor& rm, Tiled* t256p, RowXf xf, bool want_recs) {
-    Tiled t256_dummy;
-    Tiled& t256 = t256p ? *t256p : t256_dummy;          // the 256-tiled view is only made for the matrix-free solver
+// X[:, sel] -> row-major records (count, scan, fill).  `d_sel`: n_words selection bits followed by n_words prefix counts, on
+// the device (the compacted column of a gene is its rank among the selected genes in ascending gene order)
+int32_t compact_selection(srx_mat* m, const uint32_t* d_sel, int n_words, int k, RowMajor& rm, RowXf xf, bool want_recs) {
     srx_ctx* ctx = m->ctx;
     const uint64_t N = m->n_rows;
-    const int nt128 = (k + KG - 1) / KG, nt256 = t256p ? (k + KT - 1) / KT : 0;
-    int64_t *cntrow, *cnt256, *d_total;
+    int64_t *cntrow, *d_total;
+    // the selection table goes to LDS where it fits beside the fill pass's logarithm table (else it is read from global memory)
     const size_t sel_lds = 2 * (size_t)n_words * sizeof(uint32_t);
-    if (sel_lds > 60000) return fail(ctx, SRX_E_ARG, "pca: %llu genes exceed the LDS selection table", (unsigned long long)m->n_cols);
-    const uint64_t n256 = (uint64_t)nt256 * N;
+    const bool sel_in_lds = sel_lds <= 60000;
     SRX_TRY(scratch(ctx, "pca_cntrow", (N ? N : 1) * sizeof(int64_t), (void**)&cntrow));
-    SRX_TRY(scratch(ctx, "pca_cnt256", (n256 ? n256 : 1) * sizeof(int64_t), (void**)&cnt256));
     SRX_TRY(scratch(ctx, "pca_rm_ptr", (N + 1) * sizeof(int64_t), (void**)&rm.ptr));
-    SRX_TRY(scratch(ctx, "pca_t256_ptr", (n256 + 1) * sizeof(int64_t), (void**)&t256.tptr));
     // (A single-pass form — count, decoupled look-back over groups of 8 rows, fill from the indices still in L2; the output
     //  size known beforehand from the cached per-gene counts — was built and measured in round 3: 3.0 ms against 1.73 for
     //  count + scan + fill.  The groups have to stay small for the second walk to hit L2 (16 KB of L2 per resident
@@ -246,12 +157,12 @@ int32_t build_tiled_fused(srx_mat* m, const uint32_t* d_sel, int n_words, int k,
     //  of the grid resident, which the occupancy query over-promised at 8 workgroups per CU.  Not kept.)
     const double s_i = m->d_idx16 ? 2.0 : 4.0;          // bytes per column index streamed by the passes
     const size_t pb = is_f32(m) ? sizeof(GramPk<float>) : sizeof(GramPk<double>);
+    // the list route: the 16-bit index mirror (there whenever n_cols <= 65536, ensure_tiles) and compacted columns below 0xffff,
+    // its table's mark of a dropped gene (k = 65536: every column of a 65536-column matrix selected)
+    const bool list = m->n_cols <= 65536 && m->d_idx16 && k < 0xffff + 1;
     // algorithmic bytes: the column indices of the whole matrix once per pass (count, fill) + row pointers in, row pointers
     // out; the KEPT values read and the compacted entries written are added below, once their number is known
-    ProfScope ps(ctx, SRX_K_COMPACT, (double)m->nnz * s_i * ((!t256p && m->n_cols <= 65536) ? 1.0 : 2.0) +
-                                         (double)(N + 1) * 8.0 * 2.0);
-    const size_t cnt_lds = sel_lds + 4 * (size_t)kCompactRows * kWave * sizeof(uint32_t);      // + 8 x 64 counters per wave
-    const bool list = !t256p && m->n_cols <= 65536 && m->d_idx16;      // (the 16-bit index mirror: there whenever n_cols <= 65536, ensure_tiles)
+    ProfScope ps(ctx, SRX_K_COMPACT, (double)m->nnz * s_i * (list ? 1.0 : 2.0) + (double)(N + 1) * 8.0 * 2.0);
     uint32_t* kept = nullptr;
     if (list) {
         SRX_TRY(scratch(ctx, "pca_keptlist", (m->nnz + 64) * sizeof(uint32_t), (void**)&kept));
@@ -264,20 +175,19 @@ int32_t build_tiled_fused(srx_mat* m, const uint32_t* d_sel, int n_words, int k,
         SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_rowcount_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)col_lds));
         hipLaunchKernelGGL(k_rowcount_list, dim3(cgrid), dim3(kCountThreads), col_lds, ctx->stream, m->d_indptr,
                            (const uint16_t*)m->d_idx16, d_sel, d_sel + n_words, n_words, N, m->nnz, k, cntrow, kept);
-    } else if (!t256p) {
+    } else {
+        auto count = [&](auto kern, const auto* idxp, size_t lds) {
+            hipLaunchKernelGGL(kern, dim3(grid_rows(ctx, N, 4)), dim3(256), lds, ctx->stream, m->d_indptr, idxp, d_sel, n_words, N, cntrow);
+        };
         const size_t bits_lds = (size_t)n_words * sizeof(uint32_t);
-        if (m->d_idx16)
-            hipLaunchKernelGGL((k_rowcount<uint16_t>), dim3(grid_rows(ctx, N, 4)), dim3(256), bits_lds, ctx->stream, m->d_indptr,
-                               (const uint16_t*)m->d_idx16, d_sel, n_words, N, cntrow);
-        else
-            hipLaunchKernelGGL((k_rowcount<int32_t>), dim3(grid_rows(ctx, N, 4)), dim3(256), bits_lds, ctx->stream, m->d_indptr,
-                               (const int32_t*)m->d_indices, d_sel, n_words, N, cntrow);
-    } else if (m->d_idx16)
-        hipLaunchKernelGGL((k_tcount<uint16_t>), dim3(grid_rows(ctx, N, 4)), dim3(256), cnt_lds, ctx->stream, m->d_indptr,
-                           (const uint16_t*)m->d_idx16, d_sel, d_sel + n_words, n_words, N, nt128, nt256, k, cntrow, cnt256);
-    else
-        hipLaunchKernelGGL((k_tcount<int32_t>), dim3(grid_rows(ctx, N, 4)), dim3(256), cnt_lds, ctx->stream, m->d_indptr,
-                           (const int32_t*)m->d_indices, d_sel, d_sel + n_words, n_words, N, nt128, nt256, k, cntrow, cnt256);
+        if (m->d_idx16) {
+            if (sel_in_lds) count(k_rowcount<uint16_t, true>, (const uint16_t*)m->d_idx16, bits_lds);
+            else count(k_rowcount<uint16_t, false>, (const uint16_t*)m->d_idx16, 0);
+        } else {
+            if (sel_in_lds) count(k_rowcount<int32_t, true>, (const int32_t*)m->d_indices, bits_lds);
+            else count(k_rowcount<int32_t, false>, (const int32_t*)m->d_indices, 0);
+        }
+    }
     SRX_TRY(scan_exclusive(ctx, cntrow, N, rm.ptr, &d_total));
     // The Gram kernel's record counts only need the row lengths: made HERE, before the read-back of the compacted size, so
     // that both numbers come back behind ONE drain of the stream (the second wait cost ~90 us of idle device per step)
@@ -301,10 +211,8 @@ int32_t build_tiled_fused(srx_mat* m, const uint32_t* d_sel, int n_words, int k,
         SRX_TRY(d2h_begin(ctx, d_nrecs ? (const void*)d_nrecs : (const void*)d_total, d_nrecs ? sizeof both : sizeof(int64_t)));
         // the order of the rows by length (what the transform walks) needs the row pointers only: queued HERE, it runs while
         // the host is woken by the copy (the device used to idle through that round trip, ~30 us per step)
-        if (!t256p) {
-            rm.n_rows = N;
-            SRX_TRY(build_row_order(ctx, rm));
-        }
+        rm.n_rows = N;
+        SRX_TRY(build_row_order(ctx, rm));
         SRX_TRY(d2h_end(ctx, both, d_nrecs ? sizeof both : sizeof(int64_t)));
         if (d_nrecs) {
             rm.n_recs = both[0];
@@ -313,33 +221,31 @@ int32_t build_tiled_fused(srx_mat* m, const uint32_t* d_sel, int n_words, int k,
             total = both[0];
         }
     }
-    if (t256p) {
-        SRX_TRY(scan_exclusive(ctx, cnt256, n256, t256.tptr, nullptr));
-        SRX_TRY(alloc_tiled(m, N, (uint64_t)total, k, KT, t256));
-    }
     SRX_TRY(scratch(ctx, "pca_rm_pk", ((size_t)total + 64) * pb, &rm.pk));
     // (the 64 entries behind the last row, read by the forward kernel: zeroed by the fill kernel — the list route's by its
-    //  first workgroup, the others by a memset)
+    //  first workgroup, the other's by a memset)
     if (!list) SRX_HIP(ctx, hipMemsetAsync((char*)rm.pk + (size_t)total * pb, 0, 64 * pb, ctx->stream));
-    rm.n_rows = N;
     rm.nnz = (uint64_t)total;
     rm.k = k;
-    auto fill = [&](auto kern, const auto* idxp, const auto* valp, auto* rmp, auto* pk256) {
-        hipLaunchKernelGGL(kern, dim3(grid_rows(ctx, N, 4)), dim3(256), sel_lds, ctx->stream, m->d_indptr, idxp, valp, d_sel,
-                           d_sel + n_words, n_words, N, nt256, k, cnt256, rm.ptr, t256.tptr, xf.row_sum, xf.target, rmp, pk256);
+    auto fill = [&](auto kern, const auto* idxp, const auto* valp, auto* rmp) {
+        hipLaunchKernelGGL(kern, dim3(grid_rows(ctx, N, 4)), dim3(256), sel_in_lds ? sel_lds : 0, ctx->stream, m->d_indptr, idxp,
+                           valp, d_sel, d_sel + n_words, n_words, N, k, rm.ptr, xf.row_sum, xf.target, rmp);
     };
-    auto fill_t = [&](auto tval, auto* rmp, auto* pk256) {
+    auto fill_t = [&](auto tval, auto* rmp) {
         using T = decltype(tval);
         const T* valp = (const T*)m->d_values;
-        if (m->d_idx16) {
-            const uint16_t* ip = (const uint16_t*)m->d_idx16;
-            if (xf.row_sum) fill(k_tfill<T, uint16_t, true>, ip, valp, rmp, pk256);
-            else fill(k_tfill<T, uint16_t, false>, ip, valp, rmp, pk256);
-        } else {
-            const int32_t* ip = (const int32_t*)m->d_indices;
-            if (xf.row_sum) fill(k_tfill<T, int32_t, true>, ip, valp, rmp, pk256);
-            else fill(k_tfill<T, int32_t, false>, ip, valp, rmp, pk256);
-        }
+        auto by_sel = [&](auto xf_tag, const auto* ip) {
+            constexpr bool XF = decltype(xf_tag)::value;
+            using I = std::remove_cv_t<std::remove_pointer_t<decltype(ip)>>;
+            if (sel_in_lds) fill(k_tfill<T, I, XF, true>, ip, valp, rmp);
+            else fill(k_tfill<T, I, XF, false>, ip, valp, rmp);
+        };
+        auto by_xf = [&](const auto* ip) {
+            if (xf.row_sum) by_sel(std::true_type{}, ip);
+            else by_sel(std::false_type{}, ip);
+        };
+        if (m->d_idx16) by_xf((const uint16_t*)m->d_idx16);
+        else by_xf((const int32_t*)m->d_indices);
     };
     if (list) {
         const unsigned g2 = (unsigned)grid_rows(ctx, N, 8);
@@ -350,33 +256,31 @@ int32_t build_tiled_fused(srx_mat* m, const uint32_t* d_sel, int n_words, int k,
             if (xf.row_sum) hipLaunchKernelGGL((k_tfill_list<double, true>), dim3(g2), dim3(256), 0, ctx->stream, m->d_indptr, (const double*)m->d_values, kept, N, rm.ptr, xf.row_sum, xf.target, (GramPk<double>*)rm.pk);
             else hipLaunchKernelGGL((k_tfill_list<double, false>), dim3(g2), dim3(256), 0, ctx->stream, m->d_indptr, (const double*)m->d_values, kept, N, rm.ptr, xf.row_sum, xf.target, (GramPk<double>*)rm.pk);
         }
-    } else if (is_f32(m)) fill_t(float{}, (GramPk<float>*)rm.pk, (GramPk<float>*)t256.tpk);
-    else fill_t(double{}, (GramPk<double>*)rm.pk, (GramPk<double>*)t256.tpk);
+    } else if (is_f32(m)) fill_t(float{}, (GramPk<float>*)rm.pk);
+    else fill_t(double{}, (GramPk<double>*)rm.pk);
     SRX_HIP(ctx, hipGetLastError());
     if (ctx->prof_mask & (1u << SRX_K_COMPACT))
     {
-        ctx->prof[SRX_K_COMPACT].bytes += (double)total * (val_bytes(m) + (double)pb * (t256p ? 2.0 : 1.0));   // kept values read, entries written once or twice
+        ctx->prof[SRX_K_COMPACT].bytes += (double)total * (val_bytes(m) + (double)pb);   // kept values read, entries written
         if (list) ctx->prof[SRX_K_COMPACT].aux_bytes += (double)total * 4.0 * 2.0;      // the list of kept entries: written, read
     }
     return SRX_OK;
 }
 
-// host-side selection (srx_pca with an explicit feature list): bitmask + prefix counts from the remap table
-int32_t build_tiled_fused(srx_mat* m, const std::vector<int32_t>& remap, int k, RowMajor& rm, Tiled* t256, RowXf xf, bool want_recs) {
-    srx_ctx* ctx = m->ctx;
-    const int n_words = (int)((remap.size() + 31) / 32);
-    std::vector<uint32_t> hsel(2 * (size_t)n_words, 0u);
-    for (size_t g = 0; g < remap.size(); ++g)
-        if (remap[g] >= 0) hsel[g >> 5] |= 1u << (g & 31);
+// An explicit selection as the bitmask + prefix counts compact_selection reads
+int32_t upload_selection(srx_ctx* ctx, const uint64_t* genes, size_t k, uint64_t n_cols, uint32_t** d_sel, int* n_words) {
+    const int nw = (int)((n_cols + 31) / 32);
+    std::vector<uint32_t> hsel(2 * (size_t)nw, 0u);
+    for (size_t s = 0; s < k; ++s) hsel[genes[s] >> 5] |= 1u << (genes[s] & 31);
     uint32_t run = 0;
-    for (int w = 0; w < n_words; ++w) {
-        hsel[n_words + w] = run;
+    for (int w = 0; w < nw; ++w) {
+        hsel[nw + w] = run;
         run += (uint32_t)__builtin_popcount(hsel[w]);
     }
-    uint32_t* d_sel;
-    SRX_TRY(scratch(ctx, "pca_selbits", (hsel.size() ? hsel.size() : 1) * sizeof(uint32_t), (void**)&d_sel));
-    SRX_TRY(h2d(ctx, d_sel, hsel.data(), hsel.size() * sizeof(uint32_t)));
-    return build_tiled_fused(m, d_sel, n_words, k, rm, t256, xf, want_recs);
+    SRX_TRY(scratch(ctx, "pca_selbits", (hsel.size() ? hsel.size() : 1) * sizeof(uint32_t), (void**)d_sel));
+    SRX_TRY(h2d(ctx, *d_sel, hsel.data(), hsel.size() * sizeof(uint32_t)));
+    *n_words = nw;
+    return SRX_OK;
 }
 
 // The Gram kernel's second half runs on a stream whose CU mask leaves `kCommFreeCus` CUs alone when the rows are sharded: the
@@ -445,7 +349,7 @@ int32_t launch_gram(srx_ctx* ctx, const RowMajor& rm, double* Gp, bool* reduce, 
         ProfScope ps(ctx, SRX_K_BUCKET, (double)rm.nnz * sizeof(GramPk<VT>) + (double)(rm.n_rows + 1) * 8.0 * 2.0);
         // how many records each block makes (a suffix longer than a wave is several), and where its records start
         if (rm.n_recs >= 0) {
-            n_recs = rm.n_recs;                  // counted with the compaction (build_tiled_fused): blk_total / rec_base are filled
+            n_recs = rm.n_recs;                  // counted with the compaction (compact_selection): blk_total / rec_base are filled
         } else {
             hipLaunchKernelGGL(k_rec_count, dim3((unsigned)g.n_rblk), dim3(256), 0, ctx->stream, rm.ptr, rm.n_rows, g.rblk, blk_total);
             hipLaunchKernelGGL(k_rec_scan, dim3(1), dim3(1024), 0, ctx->stream, blk_total, g.n_rblk, rec_base);

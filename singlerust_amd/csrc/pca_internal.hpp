@@ -18,9 +18,10 @@ namespace srx {
 constexpr int L = 64;               // panel width l
 constexpr int kTThreads = 1024;     // transposed / Gram kernels: one workgroup per CU
 
-// Tile-major layouts of the compacted matrix: the selected features are cut into tiles of kt compacted columns:
+// Tile-major view of the compacted matrix: the selected features are cut into tiles of KT compacted columns
 constexpr int KT = 256;
-constexpr int KG = 128;
+// The widest device-side HighlyVariable(n) selection (and backed session): the envelope those routes are tested in
+constexpr uint64_t kDevSelMaxK = 8192;
 
 template <typename VT> struct GramPk;
 template <> struct __attribute__((aligned(8))) GramPk<float> { int32_t j; float v; };
@@ -113,17 +114,10 @@ __device__ __forceinline__ double readlane_v(double x, int l) {
     return __builtin_bit_cast(double, readlane64(__builtin_bit_cast(long long, x), l));
 }
 
-// ---- compacted matrix: row-major records + the tile-major view of the forward SpMM ------------------
-struct CompactCsr {
-    uint64_t n_rows = 0, nnz = 0;
-    int k = 0;
-    int64_t* indptr = nullptr;
-    int32_t* idx = nullptr;
-    void* vals = nullptr;
-};
+// ---- compacted matrix: row-major records + the tile-major view of the matrix-free solver ------------
 struct Tiled {
     uint64_t n_rows = 0, nnz = 0;
-    int k = 0, kt = 0, nt = 0;
+    int k = 0, nt = 0;         // nt = ceil(k / KT) tiles
     int64_t* tptr = nullptr;   // nt * n_rows + 1
     void* tpk = nullptr;       // GramPk<VT> records: (local column within the tile, value)
 };
@@ -164,8 +158,10 @@ struct Resolved {
 // ---- genes.hip -------------------------------------------------------------------------------------
 int32_t gene_variances(srx_mat* m, std::vector<double>& var);
 int32_t select_hvg_host(srx_ctx* ctx, const std::vector<double>& var, uint64_t n, std::vector<uint64_t>& out);
-int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const int32_t* idx, uint64_t n_rows, int n_tiles,
-                        int tile_genes, int64_t* tp);
+// E: int32_t column indices or GramPk<VT> records
+template <typename E>
+int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const E* idx, uint64_t n_rows, int n_tiles, int tile_genes,
+                        int64_t* tp);
 
 // ---- pca_form.hip: the HVG-compacted matrix and G = A^T A --------------------------------------------
 // (entries_per_cell, entry_bytes: the compacted matrix's mean row length and entry size — they size the stripe kernel's chunks; 0 where
@@ -173,14 +169,15 @@ int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const int32_t* idx,
 int32_t gram_plan(srx_ctx* ctx, int k, uint64_t n_rows, GramPlan& g, double entries_per_cell = 0.0, int entry_bytes = 0);
 int grid_rows(const srx_ctx* ctx, uint64_t n_rows, int rows_per_block);
 int32_t scan_exclusive(srx_ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d_out, int64_t** total_dev);
-int32_t build_compact(srx_mat* m, const std::vector<int32_t>& remap, int k, CompactCsr& c, RowMajor& rm);
-int32_t retile(srx_mat* m, const CompactCsr& c, int kt, Tiled& t);
 // `d_sel`: n_words selection bits followed by n_words prefix counts, on the device (the compacted column of a gene is its rank
-// among the selected genes in ascending gene order); the second form takes a host remap table (explicit feature lists)
-int32_t build_tiled_fused(srx_mat* m, const uint32_t* d_sel, int n_words, int k, RowMajor& rm, Tiled* t256p, RowXf xf = RowXf{},
+// among the selected genes in ascending gene order).  Makes the row-major records, their row order (rm.perm) and, with
+// `want_recs`, the Gram kernel's record counts.
+int32_t compact_selection(srx_mat* m, const uint32_t* d_sel, int n_words, int k, RowMajor& rm, RowXf xf = RowXf{},
                           bool want_recs = false);
-int32_t build_tiled_fused(srx_mat* m, const std::vector<int32_t>& remap, int k, RowMajor& rm, Tiled* t256, RowXf xf = RowXf{},
-                          bool want_recs = false);
+// the tile-major view of the records (the matrix-free solver)
+int32_t retile(srx_mat* m, const RowMajor& rm, Tiled& t);
+// an explicit selection (distinct genes below n_cols, any order) as the device table compact_selection takes
+int32_t upload_selection(srx_ctx* ctx, const uint64_t* genes, size_t k, uint64_t n_cols, uint32_t** d_sel, int* n_words);
 template <typename VT>
 int32_t launch_gram(srx_ctx* ctx, const RowMajor& rm, double* Gp, bool* reduce = nullptr, bool zero_first = false);
 inline size_t gram_packed_count(int k) { return (size_t)k * (size_t)(k + 1) / 2; }

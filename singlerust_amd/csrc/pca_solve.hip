@@ -700,7 +700,7 @@ int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t
                        const HvgDev* hv, int l_act, double n_cells, srx_pca_state& st) {
     // `parts`: the row-major compacted rows of this rank — one for a resident matrix, one per row tile in backed mode (then
     // `gram_packed` holds the packed Gram matrix already summed over the row tiles); `t256p`: the 256-tiled view, made for
-    // the matrix-free solver and for selections too wide for the row kernel's LDS panel slice
+    // the matrix-free solver
     const RowMajor* rmp = n_parts == 1 ? &parts[0] : nullptr;
     const int k = parts[0].k;
     struct { uint64_t n_rows, max_rows; } cc{0, 0};
@@ -967,7 +967,7 @@ int32_t resolve_opts(srx_ctx* ctx, const srx_pca_opts* opts, int k, uint64_t Ng,
     if (o.solver < 0 || o.solver > 2) return fail(ctx, SRX_E_ARG, "pca: solver must be 0 (auto), 1 (gram) or 2 (spmm)");
     // auto: the explicit Gram matrix as long as it fits (k <= 16384: 2 GB of f64).  At c2's size k = 6000 / 8000 cost
     // 13.6 / 20.5 ms per pipeline against 23.7 / 30 of the matrix-free iteration, and on a flat-tailed spectrum at
-    // k = 9000 (general compaction route) 105 ms against 297
+    // k = 9000 105 ms against 297 (round 6)
     if (o.solver == 0) o.solver = k <= 16384 ? 1 : 2;
     // a sweep is `power` applications of C: the same default budget of 600 applications for both solvers
     if (o.max_iter == 0) o.max_iter = o.solver == 1 ? 200 : 600;
@@ -1057,21 +1057,17 @@ int32_t srx_spmm(srx_mat* m, const uint64_t* sel, uint64_t k64, const double* pa
     SRX_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (int)k64;
     const uint64_t G = m->n_cols;
-    std::vector<int32_t> remap(G, -1);
     for (int s = 0; s < k; ++s) {
         if (sel[s] >= G) return fail(ctx, SRX_E_BOUNDS, "selected feature index out of bounds");
         if (s > 0 && sel[s] <= sel[s - 1]) return fail(ctx, SRX_E_ARG, "srx_spmm: sel must be strictly ascending");
-        remap[sel[s]] = s;
     }
-    Tiled c256;
+    uint32_t* d_sel;
+    int n_words;
+    SRX_TRY(upload_selection(ctx, sel, (size_t)k, G, &d_sel, &n_words));
     RowMajor crm;
-    if ((k + KG - 1) / KG <= kWave) {
-        SRX_TRY(build_tiled_fused(m, remap, k, crm, &c256));
-    } else {
-        CompactCsr cc;
-        SRX_TRY(build_compact(m, remap, k, cc, crm));
-        SRX_TRY(retile(m, cc, KT, c256));
-    }
+    Tiled c256;
+    SRX_TRY(compact_selection(m, d_sel, n_words, k, crm));
+    SRX_TRY(retile(m, crm, c256));
     const size_t kl = (size_t)k * L;
     double* T;
     SRX_TRY(scratch(ctx, "pca_T", (kl + L) * 8, (void**)&T));
@@ -1089,7 +1085,6 @@ int32_t srx_spmm(srx_mat* m, const uint64_t* sel, uint64_t k64, const double* pa
             // SRX_SPMM_ROWS=1 (kernel-level parity tests): the product from the row-major records — the kernel the transform
             // runs (k_spmm_rows) — instead of the tile-major view
             if (getenv("SRX_SPMM_ROWS") && atoi(getenv("SRX_SPMM_ROWS"))) {
-                if (!crm.perm) SRX_TRY(build_row_order(ctx, crm));
                 SRX_TRY((launch_fwd_rows<VT, PT>(ctx, crm, P, P + kl, L, (double*)nullptr, Y, L)));
             } else {
                 SRX_TRY((launch_fwd<VT, PT>(ctx, c, P, P + kl, Y)));

@@ -149,6 +149,25 @@ def test_backed_pipeline_explicit_selection_and_errors(ctx, tmp_path):
     s.close()
 
 
+@pytest.mark.parametrize("k", [100, 5000])
+def test_backed_explicit_selection_on_a_300k_column_matrix(ctx, tmp_path, k):
+    """An explicit list on a 300 000-column matrix over row tiles: no 16-bit index mirror, a selection table (75 KB) too large
+    for the LDS — read from global memory by the compaction — and the values normalised + log1p'd on the fly (the session's
+    tiles are never written back).  Against the oracle's exact SVD."""
+    from singlerust_amd import backed
+    m, _ = synth_host(3003, 400, 300000, 0.01)
+    lg = oracle.log1p_transform(oracle.normalize_total(m, 1e4, ROW))
+    cand = np.flatnonzero(oracle.compute_variance(lg, COLUMN) > 0.0)      # std > 0: the reference divides by the std
+    sel = np.random.default_rng(k).permutation(cand)[:k].astype(np.uint64)
+    assert sel.max() > 65536
+    ad = backed.BackedAnnData.open(store_of(m, tmp_path), ctx)
+    r = backed.processing.pca_pipeline(ad, 150, 1e4, 0, 5, selected=sel)
+    assert np.array_equal(r.selected, sel) and int(r.info.k) == k
+    want, wc, wevr, *_ = pca_oracle.pca_inplace(lg, 5, None, None, sel)
+    assert col_err(r.x_pca, want) < TOL and col_err(r.components, wc) < TOL
+    assert np.allclose(r.explained_variance_ratio, wevr, rtol=1e-6)
+
+
 def test_wide_selection_at_f64_storage_walks_gene_ranges(ctx, tmp_path):
     """6000 selected features at f64 storage: the forward kernel's panel slice of four f64 columns holds 5118 genes, so the
     scores come from two gene ranges, the second accumulating (round 2 refused this selection in backed mode).  Resident

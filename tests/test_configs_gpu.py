@@ -155,8 +155,9 @@ def test_wide_matrix_without_the_16bit_index_mirror(ctx, tmp_path):
 
 @pytest.mark.parametrize("solver", [0, 2])
 def test_more_than_8192_selected_features(ctx, solver):
-    """FeatureSelection::None on 9000 genes: past the 64 tile counters of the fused compaction (general route: row-major
-    compaction, then re-tiling), with the Gram solver (auto up to k = 16384) and the matrix-free SpMM solver."""
+    """FeatureSelection::None on 9000 genes: an explicit selection wider than the device selection's 8192 (row-major
+    compaction, then, for the matrix-free SpMM solver, the tile-major view cut from it), with the Gram solver (auto up to
+    k = 16384) and the matrix-free solver."""
     import singlerust_amd as sr
     from singlerust_amd.memory import processing
     from singlerust_amd.memory.processing import dim_red
@@ -171,6 +172,33 @@ def test_more_than_8192_selected_features(ctx, solver):
     assert np.array_equal(sel, np.flatnonzero(oracle.compute_variance(lg, COLUMN) > 0.0))
     assert info.k == len(sel) > 8192 and info.solver == (1 if solver == 0 else 2)
     want, wc, wevr, *_ = pca_oracle.pca_inplace(lg, 6, None, None, sel)
+    assert np.allclose(a.uns["pca"]["explained_variance_ratio"], wevr, rtol=1e-6)
+    assert col_err(a.obsm["X_pca"], want) < 1e-6 and col_err(a.uns["pca"]["components"], wc) < 1e-6
+
+
+@pytest.mark.parametrize("k", [9000, 100])
+def test_explicit_selection_on_a_300k_column_matrix(ctx, k):
+    """An explicit selection of 9000 and of 100 features on a 300 000-column matrix: no 16-bit index mirror, and a
+    selection table (bits + prefix counts, 75 KB) too large for the LDS — the compaction reads it from global memory.
+    Gram solver, against the exact-SVD oracle."""
+    import singlerust_amd as sr
+    from singlerust_amd.memory import processing
+    from singlerust_amd.memory.processing import dim_red
+    m, _ = synth_host(3003, 400, 300000, 0.01)
+    a = adata_of(m, ctx, 2)
+    processing.normalize_total_inplace(a, 1e4, sr.Direction.Row)
+    processing.log1p_transform_inplace(a)
+    lg = oracle.log1p_transform(oracle.normalize_total(m, 1e4, ROW))
+    # genes whose values differ (std > 0: the reference divides by the std), k of them spread over the whole width; five
+    # components: the sixth lies within 0.1 % of the seventh at k = 9000
+    cand = np.flatnonzero(oracle.compute_variance(lg, COLUMN) > 0.0)
+    sel = np.sort(np.random.default_rng(k).choice(cand, k, replace=False)).astype(np.uint64)
+    assert sel[-1] > 65536
+    a.var["pick"] = np.isin(np.arange(m.n_cols), sel)
+    info = dim_red.pca_inplace(a, 5, None, None, None, sr.FeatureSelection.HighlyVariableCol("pick"), None, solver=0)
+    assert np.array_equal(a.uns["pca"]["selected_features"], sel)
+    assert info.k == k and info.solver == 1
+    want, wc, wevr, *_ = pca_oracle.pca_inplace(lg, 5, None, None, sel)
     assert np.allclose(a.uns["pca"]["explained_variance_ratio"], wevr, rtol=1e-6)
     assert col_err(a.obsm["X_pca"], want) < 1e-6 and col_err(a.uns["pca"]["components"], wc) < 1e-6
 

@@ -329,6 +329,38 @@ def test_spmm_and_gram_kernels_vs_scipy(ctx, store, n, g, density, k):
     assert np.array_equal(gram, want_g)                     # integer counts: exact in f64, any order
 
 
+@pytest.mark.parametrize("kernel", ["tiles", "rows"])
+def test_spmm_with_every_column_of_a_65536_column_matrix(ctx, kernel, monkeypatch):
+    """k = 65536: every column of a matrix as wide as the 16-bit index mirror goes, selected.  The last compacted column is
+    0xffff, the mark of a dropped gene in the list compaction's 16-bit table, so this selection takes the other count / fill
+    pair; the last two columns hold an entry in every row.  The forward product (tile-major view, or the row-major records
+    over gene ranges) and its transpose against scipy."""
+    import scipy.sparse as sp
+    from singlerust_amd import _ffi
+    import singlerust_amd as sr
+    if kernel == "rows":
+        monkeypatch.setenv("SRX_SPMM_ROWS", "1")
+    g = k = 65536
+    n = 200
+    rng = np.random.default_rng(65536)
+    x = sp.random(n, g, density=0.01, format="lil", random_state=rng, data_rvs=lambda c: rng.integers(1, 9, c))
+    x[:, g - 2:] = rng.integers(1, 9, (n, 2))
+    x = x.tocsr()
+    x.sort_indices()
+    a = sr.IMAnnData.new_basic(x, ctx=ctx, store=1)
+    sel = np.arange(g, dtype=np.uint64)
+    P = rng.standard_normal((k, 64))
+    y = np.zeros((n, 64))
+    t = np.zeros((k, 64))
+    _ffi.check(_ffi.lib().srx_spmm(a.x().handle, _ffi.ptr(sel), k, _ffi.ptr(P), _ffi.ptr(y), _ffi.ptr(t), None), ctx.handle)
+    A = x.astype(np.float64)
+    want_y = A @ P.astype(np.float32).astype(np.float64)
+    assert np.abs(y - want_y).max() <= 2e-6 * np.abs(want_y).max()
+    want_t = A.T @ y
+    assert np.abs(t - want_t).max() <= 1e-12 * np.abs(want_t).max()
+    assert np.abs(t[-1]).max() > 0.0
+
+
 # Genes added to k for the "ranges" cases: past the 10 236 f32 genes of the widest single panel slice in LDS, so that
 # launch_fwd_rows cuts the genes into ranges (k_spmm_rows<.., RANGE = true>: one launch per range, the later ones accumulating).
 RANGE_GENES = 10_240
@@ -690,7 +722,7 @@ def test_fixed_point_moments_range_boundary(ctx, store):
     (901, 333, 1000, 4, 1),      # n_hvg > n_vars
 ])
 def test_fused_pipeline_odd_shapes(ctx, n, g, hvg, npc, store):
-    """srx_pipeline (device-side selection, fused compaction, Gram solver, graphs) at shapes that sit on the
+    """srx_pipeline (device-side selection, compaction, Gram solver, graphs) at shapes that sit on the
     tile / block boundaries, against the oracle end to end: selection identical (f64 storage), the spanned
     subspace of the leading components and the scores to 1e-5."""
     from singlerust_amd import _ffi
