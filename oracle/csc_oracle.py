@@ -105,14 +105,14 @@ def compute_min_max(m: Csc, direction: int):
         mn = np.full(m.n_rows, np.inf)
         mx = np.full(m.n_rows, -np.inf)
         r = m.row_indices.astype(np.int64)
-        np.minimum.at(mn, r, v)
-        np.maximum.at(mx, r, v)
+        np.fmin.at(mn, r, v)                                        # f64::min / max ignore a NaN operand: fmin / fmax
+        np.fmax.at(mx, r, v)
         return mn, mx
     mn = np.full(m.n_cols, np.inf)                                  # csc.rs:202-212
     mx = np.full(m.n_cols, -np.inf)
     for c, col in m._cols():
         if col.size:
-            mn[c], mx[c] = col.min(), col.max()
+            mn[c], mx[c] = np.fmin.reduce(col, initial=np.inf), np.fmax.reduce(col, initial=-np.inf)
     return mn, mx
 
 

@@ -7,8 +7,9 @@
 //   u = fl(1 + x) = 2^e m,  i = top 7 mantissa bits,  r = m * T[i].inv - 1  (|r| < 2^-7, fma),  T[i].inv = fl(1 / (1 + i/128))
 //   ln(1 + x) = e ln2 + T[i].log + (r - r^2/2 + ... - r^8/8) + (x - (u - 1)) / u
 // with T[i].log = -ln(T[i].inv) to 50 digits (so that the table pair is consistent), ln2 split in two, and the last term
-// the rounding of 1 + x (a float reciprocal is enough for it).  Every term is >= 0 for x >= 0: no cancellation.  Measured
-// against log1pl over 2^-30 .. 2^15: <= 2.7e-16 relative (2.5 ulp); tests/test_stats_gpu.py::test_log1p_f64_fast_accuracy.
+// the rounding of 1 + x (a float reciprocal is enough for it).  Every term is >= 0 for x >= 0: no cancellation.  <= 2.7e-16
+// relative (2.5 ulp) for x >= 0: tests/test_log1p_table_cpu.py restates the arithmetic on the host (2^-40 .. 2^40 and both
+// edges of every table slot, against longdouble) and checks the table; tests/test_log1p_gpu.py checks what srx_pipeline stores.
 // Negative, NaN and infinite arguments take ocml's log1p (never on count data).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -175,8 +176,10 @@ __device__ __forceinline__ double log1p_f64_fast(double x, const Log1pTabEntry* 
     return y + (lr + __builtin_fma(de, 0x1.a39ef35793c76p-33, c));
 }
 
-// The same with a degree-5 polynomial and without the (1 + x)-rounding term: <= 2e-13 relative for x >= 2^-10 (smaller arguments take the full routine; the
-// dropped terms are r^6/6 < 4e-14 and the rounding of 1 + x, 1.1e-16 absolute), ~17 operations.  Used per value where
+// The same with a degree-5 polynomial and without the (1 + x)-rounding term, ~17 operations: <= 4e-14 absolute and <= 5e-12
+// relative for x >= 2^-10 (smaller arguments take the full routine).  The dropped terms are r^6/6 < 3.8e-14 and the rounding
+// of 1 + x, 1.1e-16 absolute; the relative worst case is near x = 2^-7 (table slot 1), where ln(1 + x) is 2^-7.  Asserted by
+// tests/test_log1p_table_cpu.py (arithmetic) and tests/test_log1p_gpu.py (stored f32 values, fixed-point moments).  Used per value where
 // the result is rounded to f32 or summed into per-gene moments that only have to rank the genes (f32 storage).
 __device__ __forceinline__ double log1p_f64_lite(double x, const Log1pTabEntry* __restrict__ tab) {
     if (!(x >= 0x1p-10) || !(x < INFINITY)) return x == 0.0 ? 0.0 : log1p_f64_fast(x, tab);
@@ -199,8 +202,9 @@ template <typename T>
 __device__ __forceinline__ T apply_log1p(T x);
 // f32 ln(1+x) in ~10 instructions (ocml's log1pf is ~100 and made the fused pass VALU-bound):
 // u = fl(1 + x); ln(1+x) = ln(u) * x / (u - 1) compensates the rounding of u (Goldberg / Kahan),
-// with ln(u) = v_log_f32(u) * ln 2 (1 ulp hardware log2).  Measured <= 3e-7 relative against f64
-// log1p over 1e-30 .. 1e30 (tests/test_stats_gpu.py::test_log1p_f32_accuracy).
+// with ln(u) = v_log_f32(u) * ln 2 (1 ulp hardware log2).  <= 3e-7 relative against f64 log1p over 1e-30 .. 1e30
+// (tests/test_stats_gpu.py::test_log1p_f32_accuracy) and over (-1, 0), special values IEEE's
+// (tests/test_log1p_gpu.py::test_log1p_f32_negative_range_and_special_values).
 template <>
 __device__ __forceinline__ float apply_log1p<float>(float x) {
     const float u = 1.0f + x;
@@ -209,8 +213,9 @@ __device__ __forceinline__ float apply_log1p<float>(float x) {
     const float q = x >= 16777216.0f ? 1.0f : x * __builtin_amdgcn_rcpf(d);   // u == x there; rcp would flush
     return (d == 0.0f || !(u < INFINITY)) ? (d == 0.0f ? x : u) : lg * q;
 }
+// ocml's log1p returns +0 for -0: ln_1p keeps the sign of a zero (IEEE 754; Rust f64::ln_1p)
 template <>
-__device__ __forceinline__ double apply_log1p<double>(double x) { return log1p(x); }
+__device__ __forceinline__ double apply_log1p<double>(double x) { return x == 0.0 ? x : log1p(x); }
 
 // out-of-line: the rare arguments of the routine below (keeps the hot loop's code and register footprint small)
 static __device__ __attribute__((noinline)) double log1p_f64_rare(double x, const Log1pTabEntry* tab) {
@@ -219,7 +224,7 @@ static __device__ __attribute__((noinline)) double log1p_f64_rare(double x, cons
 
 // ln_1p for the per-gene moments of the pipeline, written for the instruction count: the argument's class is read off the
 // high word of x (one unsigned compare: 2^-10 <= x < inf), exponent / table index / mantissa come from the high word of
-// u = 1 + x with 32-bit operations, degree-5 polynomial (same arithmetic as log1p_f64_lite: <= 2e-13 for those arguments);
+// u = 1 + x with 32-bit operations, degree-5 polynomial (same arithmetic and bound as log1p_f64_lite);
 // everything else (x < 2^-10, negative, NaN, inf) takes the full routine.
 // the class test and the straight-line part on their own: a caller with several independent arguments evaluates the
 // straight-line part for all of them (garbage, but no trap, for the rare classes) and patches the rare ones afterwards,
@@ -278,7 +283,8 @@ __device__ __forceinline__ double xf_apply(T v, double scale, double row_table, 
 
 // What the pipeline leaves in X for a raw value v of a row with this scale — so that a pass which reads the raw matrix (the
 // compaction of a backed tile) produces exactly the stored values: the f64 logarithm the moments pass forms (degree-5 variant
-// for f32 storage, rounded once to f32: correctly rounded but for ~3 values in a million; the full-accuracy one for f64).
+// for f32 storage, rounded once to f32: within 1 ulp, correctly rounded but for at most 1 in 10^5, tests/test_log1p_gpu.py; the
+// full-accuracy one for f64).
 // (The three separate calls on an f32 matrix round v * scale to f32 first and take the f32 logarithm: k_row_pass; <= 3e-7 apart.)
 __device__ __forceinline__ float xf_stored(float v, double scale, const Log1pTabEntry* __restrict__ tab) {
     return (float)log1p_f64_moment((double)v * scale, tab);

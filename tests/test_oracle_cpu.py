@@ -276,6 +276,24 @@ def test_csc_oracle_is_the_csr_oracle_of_the_transpose():
     assert np.array_equal(dense, x.toarray()[:, [3, 1, 59]])
 
 
+def test_csc_oracle_min_max_ignores_nan_like_f64_min():
+    """csc.rs:186-212 fold with f64::min / f64::max, which ignore a NaN operand (as the CSR loops do, csr.rs:194-223): a NaN
+    among other values leaves them the extremes, a row or column of NaN alone stays at +inf / -inf."""
+    from oracle import csc_oracle
+    dense = np.array([[1.0, np.nan, 0.0], [np.nan, np.nan, -2.0], [-3.0, np.nan, np.inf]])
+    cols = [np.flatnonzero(dense[:, j] != 0) for j in range(3)]
+    ptr = np.concatenate([[0], np.cumsum([len(c) for c in cols])])
+    m = csc_oracle.Csc(3, 3, ptr, np.concatenate(cols), np.concatenate([dense[c, j] for j, c in enumerate(cols)]))
+    t = Csr(3, 3, ptr, np.concatenate(cols), m.values)              # the CSR arrays of X^T
+    for d, fd in ((ROW, COLUMN), (COLUMN, ROW)):
+        a, b = csc_oracle.compute_min_max(m, d), oracle.compute_min_max(t, fd)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    mn, mx = csc_oracle.compute_min_max(m, COLUMN)
+    assert mn.tolist() == [-3.0, np.inf, -2.0] and mx.tolist() == [1.0, -np.inf, np.inf]
+    mn, mx = csc_oracle.compute_min_max(m, ROW)
+    assert mn.tolist() == [1.0, -2.0, -3.0] and mx.tolist() == [1.0, -2.0, np.inf]
+
+
 def test_oracle_under_address_and_ub_sanitizers():
     """SURVEY.md 5 (race detection / sanitizers): the C restatement is raw-pointer code and it is the checker — its
     entry points are walked on the KAT, on empty rows / genes and on random matrices of every dtype under ASan + UBSan."""
