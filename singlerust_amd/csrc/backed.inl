@@ -10,7 +10,8 @@
 // processed in two sweeps over its row tiles:
 //
 //   sweep 1, per tile:  H2D -> normalize_total(Row) + log1p -> per-gene (cnt, sum, sumsq) ADDED to the session
-//   select:             one all-reduce of the moments, HighlyVariable(n) on the device, mean / std per gene
+//   select:             one all-reduce of the moments, the selection table and mean / std per gene on the device
+//                       (HighlyVariable(n) ranked there, or on the host outside its envelope; or the caller's list)
 //   sweep 2, per tile:  H2D -> normalize + log1p -> compaction to the selected genes -> Gram tiles ADDED to the
 //                       session; the tile's 256-tiled compacted view is kept (exact-size allocation)
 //   solve:              one all-reduce of the Gram tiles, the subspace iteration on C, then the scores of every
@@ -32,17 +33,12 @@ struct srx_backed {
     srx_mat* prev = nullptr;            // tile whose kernels may still be running
     uint64_t rows1 = 0, nnz1 = 0, rows2 = 0, nnz_sel = 0;
     int phase = 0;                      // 0: sweep 1, 1: selected (sweep 2), 2: solved
-    // selection
-    bool dev_sel = false;
-    // the selection table the compaction of every tile reads: made by select_hvg_device, or (a host-side selection: d_bits /
-    // n_words alone) uploaded once by upload_selection.  Either way it lives in the context's scratch buffer "pca_selbits" from
-    // select to the last Gram tile: one session per context in that span, and no other PCA call on the context
-    srx::HvgDev hv;
+    // the selection (select_hvg_device or select_list): the table the compaction of every tile reads, the centring / scaling
+    // vectors and the selected genes.  It lives in the context's scratch buffers from select to the solve: one session per
+    // context in that span, and no other PCA call on the context
+    srx::SelDev sel;
     srx::Resolved o;
     int l_act = 0, k = 0;
-    std::vector<uint64_t> selv;
-    std::vector<double> mu, sd, dinv;
-    double trace = 0.0;
     // sweep 2
     std::vector<srx::RowMajor> parts;   // owned copies of the row-major compacted rows of every tile (the transform walks them)
     double* d_gram = nullptr;
@@ -107,7 +103,7 @@ template <typename VT>
 static int32_t backed_gram_tile(srx_backed* b, srx_mat* m, RowXf xf) {
     srx_ctx* ctx = b->ctx;
     RowMajor rm;
-    SRX_TRY(compact_selection(m, b->hv.d_bits, b->hv.n_words, b->k, rm, xf, true));
+    SRX_TRY(compact_selection(m, b->sel.d_bits, b->sel.n_words, b->k, rm, xf, true));
     SRX_TRY(launch_gram<VT>(ctx, rm, b->d_gram));            // accumulates into the session's packed matrix
     // keep the row-major records of this tile for the transform: exact-size copies out of the scratch buffers
     RowMajor keep = rm;
@@ -254,19 +250,16 @@ static int32_t backed_select_impl(srx_backed* b, uint64_t n_hvg, const uint64_t*
     acc->version = 1;
     SRX_TRY(moments_install(acc, b->d_packed));
     const uint64_t G = b->n_cols;
-    const uint64_t take = n_hvg < G ? n_hvg : G;
-    b->dev_sel = n_hvg > 0 && take <= kDevSelMaxK && G <= 65536;
-    if (n_hvg > 0 && !b->dev_sel) {                       // HighlyVariable(n) on the host (wide matrices)
+    const bool on_device = hvg_on_device(n_hvg, G);
+    std::vector<uint64_t> selv;
+    if (n_hvg > 0 && !on_device) {                          // HighlyVariable(n) on the host (wide matrices)
         std::vector<double> var;
         SRX_TRY(gene_variances(acc, var));
-        SRX_TRY(select_hvg_host(ctx, var, n_hvg, b->selv));
-    } else if (n_hvg == 0) {
-        if (sel) b->selv.assign(sel, sel + n_sel);
-        else { b->selv.resize(G); std::iota(b->selv.begin(), b->selv.end(), 0ull); }
-    } else {
-        b->selv.resize(take);                              // filled from the device once the solve is over
+        SRX_TRY(select_hvg_host(ctx, var, n_hvg, selv));
+        sel = selv.data();
+        n_sel = selv.size();
     }
-    const int k = (int)b->selv.size();
+    const int k = (int)(on_device ? std::min(n_hvg, G) : sel || n_hvg > 0 ? n_sel : G);
     b->k = k;
     if ((uint64_t)k > kDevSelMaxK)
         return fail(ctx, SRX_E_ARG, "backed: %d selected features exceed the %d a session takes", k, (int)kDevSelMaxK);
@@ -274,30 +267,19 @@ static int32_t backed_select_impl(srx_backed* b, uint64_t n_hvg, const uint64_t*
     SRX_TRY(resolve_opts(ctx, opts, k, acc->n_rows_global, b->store == SRX_STORE_F32, b->o, b->l_act));
     if (opts && opts->solver == 2) return fail(ctx, SRX_E_ARG, "backed: only the Gram solver works on row tiles");
     if (b->o.solver != 1) { b->o.solver = 1; b->o.power = 3; b->o.warm = 2; }
-    b->mu.assign(k, 0.0); b->sd.assign(k, 0.0); b->dinv.assign(k, 0.0);
-    b->trace = 0.0;
-    if (b->dev_sel) {
-        SRX_TRY(select_hvg_device(acc, n_hvg, b->o.center, b->o.scale, b->hv));
-    } else {
-        std::vector<int> order(k), slot_of_sel(k);
-        SRX_TRY(prepare_host_selection(acc, b->selv, b->o, order, slot_of_sel, b->mu, b->sd, b->dinv, b->trace));
-        SRX_TRY(upload_selection(ctx, b->selv.data(), b->selv.size(), G, &b->hv.d_bits, &b->hv.n_words));
-    }
+    if (on_device) SRX_TRY(select_hvg_device(acc, n_hvg, b->o.center, b->o.scale, b->sel));
+    else SRX_TRY(select_list(acc, sel, k, b->o.center, b->o.scale, b->sel));       // (sel null: FeatureSelection::None)
     b->n_packed = gram_packed_count(k);
     SRX_HIP(ctx, hipMalloc((void**)&b->d_gram, b->n_packed * sizeof(double)));
     SRX_HIP(ctx, hipMemsetAsync(b->d_gram, 0, b->n_packed * sizeof(double), ctx->stream));
     if (n_out) *n_out = (uint64_t)k;
     if (sel_out) {
-        if (b->dev_sel) {
-            std::vector<int32_t> r(k);
-            SRX_TRY(d2h(ctx, r.data(), b->hv.d_sel_rank, (size_t)k * sizeof(int32_t)));
-            int st = 0;
-            SRX_TRY(d2h(ctx, &st, b->hv.d_status, sizeof(int)));
-            if (st & 1) return fail(ctx, SRX_E_NAN, "NaN gene variance: called `Option::unwrap()` on a `None` value (partial_cmp)");
-            for (int i = 0; i < k; ++i) sel_out[i] = (uint64_t)r[i];
-        } else {
-            memcpy(sel_out, b->selv.data(), (size_t)k * 8);
-        }
+        std::vector<int32_t> r(k);
+        SRX_TRY(d2h(ctx, r.data(), b->sel.d_sel_rank, (size_t)k * sizeof(int32_t)));
+        int st = 0;
+        SRX_TRY(d2h(ctx, &st, b->sel.d_status, sizeof(int)));
+        if (st & 1) return fail(ctx, SRX_E_NAN, "NaN gene variance: called `Option::unwrap()` on a `None` value (partial_cmp)");
+        for (int i = 0; i < k; ++i) sel_out[i] = (uint64_t)r[i];
     }
     return SRX_OK;
 }
@@ -334,8 +316,6 @@ int32_t srx_backed_solve(srx_backed* b, srx_pca_info* info) {
     srx_pca_state& st = acc->pca;
     st.valid = false;
     const int k = b->k;
-    std::vector<double> mu_eff = b->mu;
-    if (!b->o.center) std::fill(mu_eff.begin(), mu_eff.end(), 0.0);
     st.info = srx_pca_info{};
     st.info.n_cells_global = acc->n_rows_global;
     st.info.k = (uint32_t)k;
@@ -343,18 +323,15 @@ int32_t srx_backed_solve(srx_backed* b, srx_pca_info* info) {
     st.info.block = L;
     st.info.nnz_selected = b->nnz_sel;
     st.info.solver = 1;
-    const HvgDev* hvp = b->dev_sel ? &b->hv : nullptr;
     const double Nd = (double)acc->n_rows_global;
     int32_t rc;
     if (b->store == SRX_STORE_F32)
-        rc = run_pca<float, float>(ctx, b->parts.data(), (int)b->parts.size(), nullptr, b->d_gram, b->o, mu_eff, b->dinv, hvp,
-                                   b->l_act, Nd, st);
+        rc = run_pca<float, float>(ctx, b->parts.data(), (int)b->parts.size(), nullptr, b->d_gram, b->o, b->sel, b->l_act, Nd, st);
     else
-        rc = run_pca<double, double>(ctx, b->parts.data(), (int)b->parts.size(), nullptr, b->d_gram, b->o, mu_eff, b->dinv,
-                                     hvp, b->l_act, Nd, st);
+        rc = run_pca<double, double>(ctx, b->parts.data(), (int)b->parts.size(), nullptr, b->d_gram, b->o, b->sel, b->l_act, Nd, st);
     b->phase = 2;
     if ((rc != SRX_OK && rc != SRX_E_NOCONV) || !st.d_small) return rc;
-    SRX_TRY(stash_results(ctx, st, k, b->o.n_pc, hvp, b->mu, b->sd, b->trace, b->selv));
+    SRX_TRY(stash_results(ctx, st, k, b->o.n_pc, b->sel));
     acc->n_rows = b->rows2;                      // what srx_result_fetch sizes the scores by
     SRX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_parts(b);

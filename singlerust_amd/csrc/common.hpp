@@ -140,13 +140,11 @@ struct srx_pca_state {           // what the last srx_pca / srx_pipeline left in
     srx_pca_info info{};
     // Deferred host copies ("results stay on the device until fetched"): the solve leaves its small results in
     // `d_small` (carved from the d_scores allocation) and the host vectors above are produced by the first
-    // fetch — pca_materialize() in pca.hip.  Layout in doubles:
+    // fetch — pca_materialize() in pca.hip.  Layout in doubles (the tail: k_sel_finish's vectors and selection, whatever the
+    // selection was, copied in by stash_results):
     //   rounds x [ V k*64 | theta 64 | sgn 64 ] | mu k | sd k | trace 1 | pad 1 | sel_rank (int32) k
     double* d_small = nullptr;
     bool host_pending = false;
-    bool dev_sel = false;            // mu / sd / trace / selection are in d_small (else in the pend_* fields)
-    std::vector<double> pend_mu, pend_sd;      // slot order
-    double pend_trace = 0.0;
 };
 
 struct srx_mat {
@@ -276,15 +274,6 @@ void pool_clear(srx_ctx* ctx);
 int32_t ensure_tiles(srx_mat* m);
 int32_t promote_to_f64(srx_mat* m);                   // ctx.hip: f32 storage -> f64 storage, values unchanged
 int32_t ensure_pattern_counts(srx_mat* m);            // genes.hip
-// device-resident result of FeatureSelection::HighlyVariable(n) (genes.hip), consumed by the PCA driver
-struct HvgDev {
-    int k = 0, n_words = 0;
-    int32_t* d_sel_rank = nullptr;   // k gene ids in variance-rank order (what select_features returns)
-    uint32_t* d_bits = nullptr;      // n_words selection bits, then n_words prefix counts
-    double *d_mu = nullptr, *d_sd = nullptr, *d_dinv = nullptr, *d_tr = nullptr, *d_trace = nullptr;   // slot order
-    int* d_status = nullptr;         // bit 0: NaN variance
-};
-int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, HvgDev& out);
 int32_t ensure_moments(srx_mat* m);   // fills d_cnt/d_sum/d_sq (global) for the current values
 int32_t moments_accumulate(srx_mat* m, double* d_acc, RowXf xf);     // backed mode: this tile's (cnt,sum,sumsq,N) += into d_acc
 int32_t moments_install(srx_mat* m, double* d_packed);     // all-reduce d_packed and make it m's global moments

@@ -173,7 +173,7 @@ __device__ __forceinline__ uint64_t next_compact_row(uint64_t r, uint64_t n_wave
 
 // Kept entries per row, nothing else (the row-major layout's row lengths): the bit of the gene in the selection mask is the
 // whole test — one read of the mask per entry (from LDS where it fits), no prefix lookup, no LDS atomic.  The mask holds at most k
-// bits (k_sel_finish / upload_selection make sure).
+// bits (k_sel_finish makes sure).
 template <typename I, bool LDS>
 __global__ __launch_bounds__(256) void k_rowcount(const int64_t* __restrict__ indptr, const I* __restrict__ idx,
                                                   const uint32_t* __restrict__ g_bits, int n_words, uint64_t n_rows,

@@ -1204,10 +1204,15 @@ __global__ __launch_bounds__(256) void k_rank_selected(const double* __restrict_
     if (rank) atomicAdd(&rank_out[gi], rank);
 }
 
-// One workgroup: selection bitmask + per-word prefix counts (what the compaction kernels stage in LDS), and
-// the per-slot (ascending gene order) centring / scaling vectors of the PCA from the all-cells moments
-// (pca/mod.rs:87-91: mean = sum/N, var = sumsq/N - mean^2, ddof 0); trace = sum_s dinv_s^2 ss_s, summed in a
-// fixed tree.  n_words <= 2048 (G <= 65536).
+// One workgroup: selection bitmask + per-word prefix counts (what the compaction kernels read), the selected genes in
+// selection order, and the per-slot (ascending gene order) centring / scaling vectors of the PCA from the all-cells moments
+// (pca/mod.rs:87-91: mean = sum/N, var = sumsq/N - mean^2, ddof 0); trace = sum_s dinv_s^2 ss_s, summed in a fixed tree.
+// `rank`: per gene its place in the selection, 0xffffffff for none — the HighlyVariable(n) ranking or the positions in an
+// explicit list (select_list).  `gene_var` null: no NaN test (an explicit list: the reference only panics on NaN when it
+// sorts); `sum` null: no vectors.  LDS: the bits and prefix counts are made in LDS (n_words <= 2048: G <= 65536), else in
+// place in global memory.
+constexpr int kSelLdsWords = 2048;
+template <bool LDS>
 __global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict__ rank, const double* __restrict__ gene_var,
                                                      const double* __restrict__ sum,
                                                      const double* __restrict__ sq, uint32_t G, uint32_t take, int n_words,
@@ -1216,9 +1221,11 @@ __global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict_
                                                      uint32_t* __restrict__ prefix, double* __restrict__ mu,
                                                      double* __restrict__ sd, double* __restrict__ dinv,
                                                      double* __restrict__ trace) {
-    __shared__ uint32_t s_bits[2048], s_pre[2048], s_wave[16];
+    __shared__ uint32_t s_bits[LDS ? kSelLdsWords : 1], s_pre[LDS ? kSelLdsWords : 1], s_wave[16];
     __shared__ double s_tr[1024];
     __shared__ int s_nan;
+    uint32_t* const wbits = LDS ? s_bits : bits;
+    uint32_t* const wpre = LDS ? s_pre : prefix;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     if (t == 0) s_nan = 0;
     __syncthreads();
@@ -1233,7 +1240,7 @@ __global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict_
         for (int a = 0; a < kAhead; ++a) {
             const uint32_t g = base + a * 1024 + t;
             rk[a] = g < G ? rank[g] : 0xffffffffu;
-            v[a] = g < G ? gene_var[g] : 0.0;
+            v[a] = g < G && gene_var ? gene_var[g] : 0.0;
         }
 #pragma unroll
         for (int a = 0; a < kAhead; ++a) {
@@ -1242,49 +1249,55 @@ __global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict_
             const bool in = rk[a] < take;      // (a gene behind G: 0xffffffff, never below `take`)
             if (in) sel_rank[rk[a]] = (int32_t)g;
             const unsigned long long m = __ballot(in);
-            if (lane == 0 && (g >> 5) < (uint32_t)n_words) s_bits[g >> 5] = (uint32_t)m;
-            if (lane == 32 && (g >> 5) < (uint32_t)n_words) s_bits[g >> 5] = (uint32_t)(m >> 32);
+            if (lane == 0 && (g >> 5) < (uint32_t)n_words) wbits[g >> 5] = (uint32_t)m;
+            if (lane == 32 && (g >> 5) < (uint32_t)n_words) wbits[g >> 5] = (uint32_t)(m >> 32);
         }
     }
     if (nan) s_nan = 1;
     __syncthreads();
-    uint32_t b[2] = {0u, 0u};
-    if (2 * t < n_words) b[0] = s_bits[2 * t];
-    if (2 * t + 1 < n_words) b[1] = s_bits[2 * t + 1];
-    // exclusive scan of the popcounts: per-thread pair, wave scan, wave totals
-    const uint32_t c0 = (uint32_t)__popc(b[0]), c1 = (uint32_t)__popc(b[1]);
-    uint32_t inc = c0 + c1;
+    // exclusive scan of the popcounts, 2048 words per round: per-thread pair, wave scan, wave totals
+    uint32_t carry = 0;
+    for (int w0 = 0; w0 < n_words; w0 += 2 * 1024) {
+        const int w = w0 + 2 * t;
+        uint32_t b[2] = {0u, 0u};
+        if (w < n_words) b[0] = wbits[w];
+        if (w + 1 < n_words) b[1] = wbits[w + 1];
+        const uint32_t c0 = (uint32_t)__popc(b[0]), c1 = (uint32_t)__popc(b[1]);
+        uint32_t inc = c0 + c1;
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(inc, off, 64);
+            if (lane >= off) inc += o;
+        }
+        if (lane == 63) s_wave[wv] = inc;
+        __syncthreads();
+        uint32_t before = carry;
+        for (int q = 0; q < wv; ++q) before += s_wave[q];
+        const uint32_t excl = before + inc - (c0 + c1);
+        if (w < n_words) wpre[w] = excl;
+        if (w + 1 < n_words) wpre[w + 1] = excl + c0;
+        for (int q = 0; q < 16; ++q) carry += s_wave[q];
+        __syncthreads();
     }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int w = 0; w < wv; ++w) before += s_wave[w];
-    const uint32_t excl = before + inc - (c0 + c1);
-    if (2 * t < n_words) s_pre[2 * t] = excl;
-    if (2 * t + 1 < n_words) s_pre[2 * t + 1] = excl + c0;
-    __syncthreads();
     // never more than `take` selected genes, whatever the flags say (a ranking broken by NaN variances can flag more): the
     // passes over the matrix test the bit alone and the compacted columns must stay below `take`
     for (int w = t; w < n_words; w += 1024) {
-        uint32_t b_ = s_bits[w];
-        const uint32_t e = s_pre[w], room = e < take ? take - e : 0u;
+        uint32_t b_ = wbits[w];
+        const uint32_t e = wpre[w], room = e < take ? take - e : 0u;
         while ((uint32_t)__popc(b_) > room) b_ &= ~(1u << (31 - __clz((int)b_)));
-        s_bits[w] = b_;
+        wbits[w] = b_;
     }
     __syncthreads();
-    for (int w = t; w < n_words; w += 1024) {
-        bits[w] = s_bits[w];
-        prefix[w] = s_pre[w];
-    }
+    if constexpr (LDS)
+        for (int w = t; w < n_words; w += 1024) {
+            bits[w] = s_bits[w];
+            prefix[w] = s_pre[w];
+        }
     double tr = 0.0;
-    for (uint32_t g = t; g < G; g += 1024) {
-        const uint32_t w = s_bits[g >> 5], bit = 1u << (g & 31);
+    for (uint32_t g = t; sum && g < G; g += 1024) {
+        const uint32_t w = wbits[g >> 5], bit = 1u << (g & 31);
         if (!(w & bit)) continue;
-        const uint32_t s = s_pre[g >> 5] + (uint32_t)__popc(w & (bit - 1u));
+        const uint32_t s = wpre[g >> 5] + (uint32_t)__popc(w & (bit - 1u));
         const double mean = sum[g] / n_cells;
         double var = sq[g] / n_cells - mean * mean;
         if (var < 0) var = 0;
@@ -1309,17 +1322,12 @@ __global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict_
     }
 }
 
-// Device-side HighlyVariable(n): fills the scratch buffers named below; nothing is read back.
-int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, HvgDev& out) {
-    srx_ctx* ctx = m->ctx;
-    SRX_TRY(ensure_moments(m));
-    const uint64_t G = m->n_cols;
-    const uint64_t take = n < G ? n : G;
+// The buffers of a selection of `take` of G genes (context scratch, read by the PCA that follows: a backed session keeps them
+// from its selection to its solve), and the per-gene rank table k_sel_finish reads.
+static int32_t sel_buffers(srx_ctx* ctx, uint64_t G, uint64_t take, SelDev& out, uint32_t** d_rank) {
     const int n_words = (int)((G + 31) / 32);
-    double *d_var, *d_f;
-    uint32_t* d_rank;
-    SRX_TRY(scratch(ctx, "hvg_var", (G ? G : 1) * sizeof(double), (void**)&d_var));
-    SRX_TRY(scratch(ctx, "hvg_rankv", (G ? G : 1) * sizeof(uint32_t), (void**)&d_rank));
+    double* d_f;
+    SRX_TRY(scratch(ctx, "hvg_rankv", (G ? G : 1) * sizeof(uint32_t), (void**)d_rank));
     SRX_TRY(scratch(ctx, "hvg_rank", (take ? take : 1) * sizeof(int32_t), (void**)&out.d_sel_rank));
     SRX_TRY(scratch(ctx, "pca_selbits", (size_t)(2 * n_words ? 2 * n_words : 1) * sizeof(uint32_t), (void**)&out.d_bits));
     SRX_TRY(scratch(ctx, "hvg_f", (3 * (take ? take : 1) + 8) * sizeof(double), (void**)&d_f));
@@ -1327,10 +1335,38 @@ int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, HvgDev&
     out.d_mu = d_f;
     out.d_sd = d_f + take;
     out.d_dinv = d_f + 2 * take;
-    out.d_tr = nullptr;
     out.d_trace = d_f + 3 * take;
     out.k = (int)take;
     out.n_words = n_words;
+    return SRX_OK;
+}
+
+static int32_t launch_sel_finish(srx_mat* m, const uint32_t* d_rank, const double* d_var, bool vectors, int center, int scale,
+                                 const SelDev& out) {
+    srx_ctx* ctx = m->ctx;
+    auto kern = out.n_words <= kSelLdsWords ? k_sel_finish<true> : k_sel_finish<false>;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, d_rank, d_var, vectors ? m->d_sum : nullptr, m->d_sq,
+                       (uint32_t)m->n_cols, (uint32_t)out.k, out.n_words, (double)m->n_rows_global, center, scale, out.d_sel_rank,
+                       out.d_status, out.d_bits, out.d_bits + out.n_words, out.d_mu, out.d_sd, out.d_dinv, out.d_trace);
+    SRX_HIP(ctx, hipGetLastError());
+    return SRX_OK;
+}
+
+// the device ranking's envelope: G <= 65536 (the fallback rank kernel is O(G^2)) and take <= kDevSelMaxK (what it is tested in)
+bool hvg_on_device(uint64_t n, uint64_t n_cols) {
+    return n > 0 && std::min(n, n_cols) <= kDevSelMaxK && n_cols <= 65536;
+}
+
+// Device-side HighlyVariable(n): fills the scratch buffers named in sel_buffers; nothing is read back.
+int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, SelDev& out) {
+    srx_ctx* ctx = m->ctx;
+    SRX_TRY(ensure_moments(m));
+    const uint64_t G = m->n_cols;
+    const uint64_t take = n < G ? n : G;
+    double* d_var;
+    uint32_t* d_rank;
+    SRX_TRY(scratch(ctx, "hvg_var", (G ? G : 1) * sizeof(double), (void**)&d_var));
+    SRX_TRY(sel_buffers(ctx, G, take, out, &d_rank));
     const unsigned gb = (unsigned)((G + 255) / 256 ? (G + 255) / 256 : 1);
     const unsigned gy = (unsigned)((G + kRankTile - 1) / kRankTile ? (G + kRankTile - 1) / kRankTile : 1);
     static const bool full_rank = getenv("SRX_HVG_FULL_RANK") != nullptr;       // A/B switch: rank every gene
@@ -1350,11 +1386,26 @@ int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, HvgDev&
         hipLaunchKernelGGL(k_rank_selected, dim3((cap + 255) / 256, (cap + kCandTile - 1) / kCandTile), dim3(256), 0, ctx->stream, d_var,
                            (uint32_t)G, d_counter, d_cand, d_rank);
     }
-    hipLaunchKernelGGL(k_sel_finish, dim3(1), dim3(1024), 0, ctx->stream, d_rank, d_var, m->d_sum, m->d_sq, (uint32_t)G, (uint32_t)take, n_words,
-                       (double)m->n_rows_global, center, scale, out.d_sel_rank, out.d_status, out.d_bits, out.d_bits + n_words, out.d_mu,
-                       out.d_sd, out.d_dinv, out.d_trace);
-    SRX_HIP(ctx, hipGetLastError());
-    return SRX_OK;
+    return launch_sel_finish(m, d_rank, d_var, true, center, scale, out);
+}
+
+// An explicit list: its rank table is the position of every gene in the list, so that the selection comes out in the
+// caller's order (1.2 MB to upload at 300 000 columns).  Needs the global moments of `m` where `vectors`.
+int32_t select_list(srx_mat* m, const uint64_t* genes, uint64_t k, int center, int scale, SelDev& out, bool vectors) {
+    srx_ctx* ctx = m->ctx;
+    const uint64_t G = m->n_cols;
+    std::vector<uint32_t> rank(G, 0xffffffffu);
+    for (uint64_t s = 0; s < k; ++s) {
+        const uint64_t g = genes ? genes[s] : s;
+        if (g >= G) return fail(ctx, SRX_E_BOUNDS, "selected feature index %llu out of bounds (n_vars = %llu)",
+                                (unsigned long long)g, (unsigned long long)G);
+        if (rank[g] != 0xffffffffu) return fail(ctx, SRX_E_ARG, "selected feature index %llu appears twice", (unsigned long long)g);
+        rank[g] = (uint32_t)s;
+    }
+    uint32_t* d_rank;
+    SRX_TRY(sel_buffers(ctx, G, k, out, &d_rank));
+    SRX_TRY(h2d(ctx, d_rank, rank.data(), G * sizeof(uint32_t)));
+    return launch_sel_finish(m, d_rank, nullptr, vectors, center, scale, out);
 }
 
 int32_t row_number(srx_mat* m, uint32_t* out);

@@ -772,7 +772,7 @@ __global__ void k_signs(const double* __restrict__ colmax, double* __restrict__ 
 //            components asked than the data have rank — are judged on the scale of the problem), out[1] = status bits,
 //   out[2] = theta[l_act - 1] / theta[n_pc - 1]: the smallest Ritz value of the block over the last wanted one — an upper
 //            estimate of the per-application convergence factor of the wanted pairs,
-//   out[3] = status of the device-side feature selection (bit 0 = NaN variance), out[4] = theta_1 / theta_l (spread of the
+//   out[3] = status of the feature selection (k_sel_finish: bit 0 = NaN variance), out[4] = theta_1 / theta_l (spread of the
 //            block: bounds the filter degree).  1024 threads:
 // 16 slices of the blocks per column (a single wave walking 128 x 3 dependent loads took 45 us), combined in fixed order.
 __global__ __launch_bounds__(1024) void k_resid_final(const double* __restrict__ part, int n_blocks, const double* __restrict__ theta,
@@ -821,7 +821,7 @@ __global__ __launch_bounds__(1024) void k_resid_final(const double* __restrict__
     out[0] = resid;
     out[1] = (double)*status;
     out[2] = theta[n_pc - 1] > 0 ? theta[l_act - 1] / theta[n_pc - 1] : 1.0;
-    out[3] = status_sel ? (double)*status_sel : 0.0;
+    out[3] = (double)*status_sel;
     out[4] = theta[l_act - 1] > 0 ? theta[0] / theta[l_act - 1] : 1.0;
     out[5] = (double)status[1];               // full sweeps the eigen-solve of this step took (trace output)
 }

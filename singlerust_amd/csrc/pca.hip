@@ -37,48 +37,6 @@
 
 namespace srx {
 
-// Host-side view of an explicit selection: ascending-gene order, and the all-cells mean / std (ddof 0) of the selected genes
-// from the (global) moments of `m`.
-static int32_t prepare_host_selection(srx_mat* m, const std::vector<uint64_t>& selv, const Resolved& o,
-                                      std::vector<int>& order, std::vector<int>& slot_of_sel,
-                                      std::vector<double>& mu, std::vector<double>& sd,
-                                      std::vector<double>& dinv, double& trace) {
-    srx_ctx* ctx = m->ctx;
-    const uint64_t G = m->n_cols;
-    const int k = (int)selv.size();
-    const double Nd = (double)m->n_rows_global;
-    // ascending-gene-order view of the selection; permutation back to selection order
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return selv[a] < selv[b]; });
-    for (int s = 0; s < k; ++s) {
-        uint64_t g = selv[order[s]];
-        if (g >= G) return fail(ctx, SRX_E_BOUNDS, "selected feature index %llu out of bounds (n_vars = %llu)",
-                                (unsigned long long)g, (unsigned long long)G);
-        if (s > 0 && g == selv[order[s - 1]]) return fail(ctx, SRX_E_ARG, "selected feature index %llu appears twice", (unsigned long long)g);
-        slot_of_sel[order[s]] = s;
-    }
-    // all-cells column mean / std (ddof 0) of the selected genes from the one moments pass
-    // (pca/mod.rs:87-91): mean = sum/N, var = sumsq/N - mean^2
-    std::vector<double> hsum(G), hsq(G);
-    SRX_TRY(d2h(ctx, hsum.data(), m->d_sum, G * 8));
-    SRX_TRY(d2h(ctx, hsq.data(), m->d_sq, G * 8));
-    for (int s = 0; s < k; ++s) {
-        uint64_t g = selv[order[s]];
-        double mean = hsum[g] / Nd;
-        double var = hsq[g] / Nd - mean * mean;
-        if (var < 0) var = 0;
-        double std_ = std::sqrt(var);
-        mu[s] = (o.center || o.scale) ? mean : 0.0;            // :85-119: mean/std stored only if center||scale
-        sd[s] = o.scale ? std_ : 1.0;
-        // zero-variance column: the reference divides by 0 (NaN, :108); treated as std 1 here
-        dinv[s] = (o.scale && std_ > 0) ? 1.0 / std_ : 1.0;
-        double ss = o.center ? (hsq[g] - Nd * mean * mean) : hsq[g];
-        if (ss < 0) ss = 0;
-        trace += dinv[s] * dinv[s] * ss;
-    }
-    return SRX_OK;
-}
-
 // The in-place normalise + log1p of a matrix whose pipeline has been reading it raw (RowXf) and did not get as far as the
 // moments pass that stores the transformed values itself (an error on the way): from the row sums in m->d_row_sum, on the
 // context's stream.
@@ -91,8 +49,9 @@ static int32_t launch_writeback(srx_mat* m) {
 }
 
 // Everything up to and including the scores, left in m->pca (device scores + small host vectors).
-// `hvg_n` > 0: FeatureSelection::HighlyVariable(hvg_n) made on the device (the pipeline's route: no host round
-// trip between the moments pass and the compaction); otherwise `sel` (nullptr = all features).
+// Either `hvg_n` > 0: FeatureSelection::HighlyVariable(hvg_n) ranked on the device (the pipeline's route: no host round trip
+// between the moments pass and the compaction; only inside hvg_on_device's envelope), or the list `sel` (nullptr = all
+// features, FeatureSelection::None).
 static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const srx_pca_opts* opts, uint64_t hvg_n = 0,
                           RowXf xf = RowXf{}) {
     srx_ctx* ctx = m->ctx;
@@ -111,41 +70,31 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
     srx_pca_state& st = m->pca;
     st.valid = false;
     const uint64_t G = m->n_cols;
-    // the device selection's rank kernel is O(G^2); kDevSelMaxK is the envelope the device selection is tested in
-    const bool dev_sel = hvg_n > 0 && (hvg_n < G ? hvg_n : G) <= kDevSelMaxK && G <= 65536;
-    std::vector<uint64_t> selv;
-    if (dev_sel) selv.resize(hvg_n < G ? hvg_n : G);                          // filled after the solve
-    else if (sel) selv.assign(sel, sel + k64);
-    else { selv.resize(G); std::iota(selv.begin(), selv.end(), 0ull); }      // FeatureSelection::None, :154
-    const int k = (int)selv.size();
+    if (hvg_n > 0 && (sel || !hvg_on_device(hvg_n, G)))
+        return fail(ctx, SRX_E_ARG, "pca: HighlyVariable(%llu) of %llu features is not ranked on the device", (unsigned long long)hvg_n,
+                    (unsigned long long)G);
+    if (!sel && hvg_n == 0) k64 = G;                                           // FeatureSelection::None, :154
+    const int k = (int)(hvg_n > 0 ? std::min(hvg_n, G) : k64);
     SRX_TRY(ensure_moments(m));                                                // also fixes n_rows_global
     const uint64_t Ng = m->n_rows_global;
     Resolved o;
     int l_act = 0;
     SRX_TRY(resolve_opts(ctx, opts, k, Ng, is_f32(m), o, l_act));
-
-    std::vector<int> order(k), slot_of_sel(k);
-    std::vector<double> mu(k), sd(k), dinv(k);
-    double trace = 0.0;
-    const double Nd = (double)Ng;
-    HvgDev hv;                                    // (an explicit selection fills d_bits / n_words alone)
-    if (dev_sel) {
+    SelDev sd;
+    if (hvg_n > 0) {
         Range r_("srx:select_hvg");
         ProfScope ps_sel(ctx, SRX_K_SELECT, (double)G * 24.0);
-        SRX_TRY(select_hvg_device(m, hvg_n, o.center, o.scale, hv));
+        SRX_TRY(select_hvg_device(m, hvg_n, o.center, o.scale, sd));
     } else {
-        SRX_TRY(prepare_host_selection(m, selv, o, order, slot_of_sel, mu, sd, dinv, trace));
-        SRX_TRY(upload_selection(ctx, selv.data(), selv.size(), G, &hv.d_bits, &hv.n_words));
+        SRX_TRY(select_list(m, sel, k64, o.center, o.scale, sd));
     }
-    std::vector<double> mu_eff = mu;
-    if (!o.center) std::fill(mu_eff.begin(), mu_eff.end(), 0.0);
 
     // X[:, sel] as row-major records; the 256-tiled view of them only where something reads it (the matrix-free solver)
     Tiled t256;
     RowMajor rm;
     Range r_compact("srx:compact");
     const bool need_t256 = o.solver == 2;
-    SRX_TRY(compact_selection(m, hv.d_bits, hv.n_words, k, rm, xf, o.solver == 1));
+    SRX_TRY(compact_selection(m, sd.d_bits, sd.n_words, k, rm, xf, o.solver == 1));
     if (need_t256) SRX_TRY(retile(m, rm, t256));
     st.info = srx_pca_info{};
     st.info.n_cells_global = Ng;
@@ -155,16 +104,16 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
     st.info.nnz_selected = rm.nnz;
     st.info.solver = (uint32_t)o.solver;
     int32_t rc;
-    const HvgDev* hvp = dev_sel ? &hv : nullptr;
+    const double Nd = (double)Ng;
     // f32 storage: f32 panels and products for the one transform of the Gram route; the matrix-free iteration runs its
     // panels in f64 (f32 products of Z W level the residuals of the small components off at ~1e-7 theta_1 / theta_i:
     // 6.6e-5 at k = 9000 on a flat-tailed matrix, however many sweeps)
-    if (is_f32(m) && o.solver == 2)
-        rc = run_pca<float, double>(ctx, &rm, 1, need_t256 ? &t256 : nullptr, nullptr, o, mu_eff, dinv, hvp, l_act, Nd, st);
-    else if (is_f32(m)) rc = run_pca<float, float>(ctx, &rm, 1, need_t256 ? &t256 : nullptr, nullptr, o, mu_eff, dinv, hvp, l_act, Nd, st);
-    else rc = run_pca<double, double>(ctx, &rm, 1, need_t256 ? &t256 : nullptr, nullptr, o, mu_eff, dinv, hvp, l_act, Nd, st);
+    const Tiled* t256p = need_t256 ? &t256 : nullptr;
+    if (is_f32(m) && o.solver == 2) rc = run_pca<float, double>(ctx, &rm, 1, t256p, nullptr, o, sd, l_act, Nd, st);
+    else if (is_f32(m)) rc = run_pca<float, float>(ctx, &rm, 1, t256p, nullptr, o, sd, l_act, Nd, st);
+    else rc = run_pca<double, double>(ctx, &rm, 1, t256p, nullptr, o, sd, l_act, Nd, st);
     if ((rc != SRX_OK && rc != SRX_E_NOCONV) || !st.d_small) return rc;      // d_small unset: the solve broke down early
-    SRX_TRY(stash_results(ctx, st, k, o.n_pc, dev_sel ? &hv : nullptr, mu, sd, trace, selv));
+    SRX_TRY(stash_results(ctx, st, k, o.n_pc, sd));
     return rc;
 }
 
@@ -194,20 +143,9 @@ static int32_t pca_materialize(srx_mat* m) {
         theta = hV + kl;
         sgn = theta + L;
     };
-    std::vector<double> mu, sd;
-    double trace;
-    if (st.dev_sel) {
-        mu.assign(tail, tail + k);
-        sd.assign(tail + k, tail + 2 * (size_t)k);
-        trace = tail[2 * (size_t)k];
-        const int32_t* hsel = reinterpret_cast<const int32_t*>(tail + 2 * (size_t)k + 2);
-        st.sel.resize(k);
-        for (int i = 0; i < k; ++i) st.sel[i] = (uint64_t)hsel[i];
-    } else {
-        mu = st.pend_mu;
-        sd = st.pend_sd;
-        trace = st.pend_trace;
-    }
+    const double *mu = tail, *sd = tail + k, trace = tail[2 * (size_t)k];
+    const int32_t* hsel = reinterpret_cast<const int32_t*>(tail + 2 * (size_t)k + 2);
+    st.sel.assign(hsel, hsel + k);
     // slot (ascending gene order) of every selected feature
     std::vector<int> order(k), slot_of_sel(k);
     std::iota(order.begin(), order.end(), 0);
@@ -329,7 +267,6 @@ int32_t srx_pipeline(srx_mat* m, double target_sum, uint64_t n_hvg, const srx_pc
     // and form y = ln_1p(v * scale_row) on the fly in f64 (RowXf) — so the per-gene moments behind HighlyVariable(n)
     // are those of the reference's f64 values whatever the storage type — and the in-place write-back of y runs on the
     // side stream beside the Gram kernel.  CSC (cells are columns): the two calls, then the stored values.
-    const uint64_t take = n_hvg < m->n_cols ? n_hvg : m->n_cols;
     const bool lazy = !m->csc;
     RowXf xf;
     bool wrote_back = false;
@@ -362,16 +299,16 @@ int32_t srx_pipeline(srx_mat* m, double target_sum, uint64_t n_hvg, const srx_pc
     }
     (void)hipEventRecord(ev[2], ctx->stream);
     // FeatureSelection::HighlyVariable(n_hvg): on the device, inside pca_device (the selection is fetched with the
-    // other results once the solve is over); the host route for the shapes outside the device selection's envelope: G <= 65536
-    // (its rank kernel is O(G^2)) and take <= kDevSelMaxK (what the device selection is tested in), as in pca_device
+    // other results once the solve is over); ranked here for the shapes outside the device ranking's envelope (hvg_on_device)
+    // and for CSC, and passed on as a list
     std::vector<uint64_t> sel;
-    const bool dev_sel = !m->csc && n_hvg > 0 && take <= kDevSelMaxK && m->n_cols <= 65536;
+    const bool on_device = !m->csc && hvg_on_device(n_hvg, m->n_cols);
     if (rc == SRX_OK && m->csc) {                 // HighlyVariable(n) with the CSC variance (csc.rs:164-177)
         uint64_t n_out = 0;
         sel.resize(n_hvg < m->n_rows ? n_hvg : m->n_rows);
         rc = srx_select_hvg(m, n_hvg, sel.data(), &n_out);
         sel.resize(rc == SRX_OK ? n_out : 0);
-    } else if (rc == SRX_OK && !dev_sel) {
+    } else if (rc == SRX_OK && !on_device) {
         std::vector<double> var;
         rc = gene_variances(m, var);
         if (rc == SRX_OK) rc = select_hvg_host(ctx, var, n_hvg, sel);
@@ -379,7 +316,7 @@ int32_t srx_pipeline(srx_mat* m, double target_sum, uint64_t n_hvg, const srx_pc
     (void)hipEventRecord(ev[3], ctx->stream);
     if (rc == SRX_OK) {
         Range r_("srx:pca");
-        rc = dev_sel ? pca_device(m, nullptr, 0, opts, n_hvg, xf) : pca_device(m, sel.data(), sel.size(), opts, 0, xf);
+        rc = on_device ? pca_device(m, nullptr, 0, opts, n_hvg, xf) : pca_device(m, sel.data(), sel.size(), opts, 0, xf);
     }
     // whatever happened above, X ends up normalised and log1p'd (the two in-place calls come first in the reference)
     if (m->lazy_pending) {

@@ -267,22 +267,6 @@ int32_t compact_selection(srx_mat* m, const uint32_t* d_sel, int n_words, int k,
     return SRX_OK;
 }
 
-// An explicit selection as the bitmask + prefix counts compact_selection reads
-int32_t upload_selection(srx_ctx* ctx, const uint64_t* genes, size_t k, uint64_t n_cols, uint32_t** d_sel, int* n_words) {
-    const int nw = (int)((n_cols + 31) / 32);
-    std::vector<uint32_t> hsel(2 * (size_t)nw, 0u);
-    for (size_t s = 0; s < k; ++s) hsel[genes[s] >> 5] |= 1u << (genes[s] & 31);
-    uint32_t run = 0;
-    for (int w = 0; w < nw; ++w) {
-        hsel[nw + w] = run;
-        run += (uint32_t)__builtin_popcount(hsel[w]);
-    }
-    SRX_TRY(scratch(ctx, "pca_selbits", (hsel.size() ? hsel.size() : 1) * sizeof(uint32_t), (void**)d_sel));
-    SRX_TRY(h2d(ctx, *d_sel, hsel.data(), hsel.size() * sizeof(uint32_t)));
-    *n_words = nw;
-    return SRX_OK;
-}
-
 // The Gram kernel's second half runs on a stream whose CU mask leaves `kCommFreeCus` CUs alone when the rows are sharded: the
 // collective's workgroups (RCCL: one per channel, persistent) then find a CU with room whatever the dispatcher does with the
 // stripe kernel's 10 000 queued workgroups — measured in round 3: a second stream's first kernel sat 2.8 ms in its queue

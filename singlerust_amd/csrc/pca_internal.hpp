@@ -158,6 +158,20 @@ struct Resolved {
 // ---- genes.hip -------------------------------------------------------------------------------------
 int32_t gene_variances(srx_mat* m, std::vector<double>& var);
 int32_t select_hvg_host(srx_ctx* ctx, const std::vector<double>& var, uint64_t n, std::vector<uint64_t>& out);
+// The selection of a PCA on the device, made by k_sel_finish from a per-gene rank table (context scratch buffers)
+struct SelDev {
+    int k = 0, n_words = 0;
+    int32_t* d_sel_rank = nullptr;   // the k selected gene ids in selection order (what select_features returns)
+    uint32_t* d_bits = nullptr;      // n_words selection bits, then n_words prefix counts
+    double *d_mu = nullptr, *d_sd = nullptr, *d_dinv = nullptr, *d_trace = nullptr;   // slot order (ascending gene)
+    int* d_status = nullptr;         // bit 0: NaN variance (HighlyVariable(n) only)
+};
+// is FeatureSelection::HighlyVariable(n) ranked on the device (select_hvg_device)?  Else on the host, and passed on as a list
+bool hvg_on_device(uint64_t n, uint64_t n_cols);
+int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, SelDev& out);
+// an explicit list (`genes`: k distinct features below n_cols in the caller's order; null: every feature, k = n_cols),
+// validated; `vectors` false: the selection alone, the moments of `m` are not read
+int32_t select_list(srx_mat* m, const uint64_t* genes, uint64_t k, int center, int scale, SelDev& out, bool vectors = true);
 // E: int32_t column indices or GramPk<VT> records
 template <typename E>
 int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const E* idx, uint64_t n_rows, int n_tiles, int tile_genes,
@@ -176,8 +190,6 @@ int32_t compact_selection(srx_mat* m, const uint32_t* d_sel, int n_words, int k,
                           bool want_recs = false);
 // the tile-major view of the records (the matrix-free solver)
 int32_t retile(srx_mat* m, const RowMajor& rm, Tiled& t);
-// an explicit selection (distinct genes below n_cols, any order) as the device table compact_selection takes
-int32_t upload_selection(srx_ctx* ctx, const uint64_t* genes, size_t k, uint64_t n_cols, uint32_t** d_sel, int* n_words);
 template <typename VT>
 int32_t launch_gram(srx_ctx* ctx, const RowMajor& rm, double* Gp, bool* reduce = nullptr, bool zero_first = false);
 inline size_t gram_packed_count(int k) { return (size_t)k * (size_t)(k + 1) / 2; }
@@ -191,11 +203,8 @@ int32_t ensure_result_capacity(srx_ctx* ctx, srx_pca_state& st, size_t need);
 int32_t resolve_opts(srx_ctx* ctx, const srx_pca_opts* opts, int k, uint64_t Ng, bool f32, Resolved& o, int& l_act);
 template <typename VT, typename PT>
 int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed, const Resolved& o,
-                const std::vector<double>& mu, const std::vector<double>& dinv, const HvgDev* hv, int l_act, double n_cells,
-                srx_pca_state& st);
+                const SelDev& sel, int l_act, double n_cells, srx_pca_state& st);
 // the small results of a solve move from the context's scratch into the matrix's own result block (host copies: pca_materialize)
-int32_t stash_results(srx_ctx* ctx, srx_pca_state& st, int k, int n_pc, const HvgDev* hv,
-                             const std::vector<double>& mu, const std::vector<double>& sd, double trace,
-                             const std::vector<uint64_t>& selv);
+int32_t stash_results(srx_ctx* ctx, srx_pca_state& st, int k, int n_pc, const SelDev& sel);
 
 }  // namespace srx

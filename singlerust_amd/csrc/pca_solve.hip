@@ -696,8 +696,7 @@ int32_t ensure_result_capacity(srx_ctx* ctx, srx_pca_state& st, size_t need) {
 
 template <typename VT, typename PT>
 int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed,
-                       const Resolved& o, const std::vector<double>& mu, const std::vector<double>& dinv,
-                       const HvgDev* hv, int l_act, double n_cells, srx_pca_state& st) {
+                       const Resolved& o, const SelDev& sel, int l_act, double n_cells, srx_pca_state& st) {
     // `parts`: the row-major compacted rows of this rank — one for a resident matrix, one per row tile in backed mode (then
     // `gram_packed` holds the packed Gram matrix already summed over the row tiles); `t256p`: the 256-tiled view, made for
     // the matrix-free solver
@@ -712,14 +711,11 @@ int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t
     Work w;
     st.d_small = nullptr;
     SRX_TRY(alloc_work(ctx, k, w));
-    if (hv) {                          // selection made on the device: centring / scaling vectors are already there — read in place
-        if (o.center) w.mu = hv->d_mu;      // (they are only ever read; two device copies per step were 9 us on the critical path)
-        else SRX_HIP(ctx, hipMemsetAsync(w.mu, 0, (size_t)k * 8, ctx->stream));
-        w.d = hv->d_dinv;
-    } else {
-        SRX_TRY(h2d(ctx, w.mu, mu.data(), (size_t)k * 8));
-        SRX_TRY(h2d(ctx, w.d, dinv.data(), (size_t)k * 8));
-    }
+    // the centring / scaling vectors of the selection are read in place (they are only ever read; two device copies per step
+    // were 9 us on the critical path)
+    if (o.center) w.mu = sel.d_mu;
+    else SRX_HIP(ctx, hipMemsetAsync(w.mu, 0, (size_t)k * 8, ctx->stream));
+    w.d = sel.d_dinv;
     PT *P, *cvec, *Y;
     SRX_TRY(scratch(ctx, "pca_P", (kl + L) * sizeof(PT), (void**)&P));
     cvec = P + kl;
@@ -804,7 +800,7 @@ int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t
             bool conv_r = false;
             {
                 ProfScope ps_it(ctx, SRX_K_ITERATE, (double)k * k * 8.0);
-                SRX_TRY(subspace_iterate(ctx, w, k, l_r, o_r, apply, apply_id, graphable, hv ? hv->d_status : nullptr, resid_r,
+                SRX_TRY(subspace_iterate(ctx, w, k, l_r, o_r, apply, apply_id, graphable, sel.d_status, resid_r,
                                          iters_r, conv_r, acc_apply, resume && r == 0 && l_r == l_act, &bailed_first));
             }
             resid = std::max(resid, resid_r);
@@ -1003,28 +999,17 @@ int32_t resolve_opts(srx_ctx* ctx, const srx_pca_opts* opts, int k, uint64_t Ng,
 }
 
 // Everything the host side of the result needs stays on the device until the first fetch (pca_materialize).
-int32_t stash_results(srx_ctx* ctx, srx_pca_state& st, int k, int n_pc, const HvgDev* hv,
-                             const std::vector<double>& mu, const std::vector<double>& sd, double trace,
-                             const std::vector<uint64_t>& selv) {
-    // Everything the host side of the result needs stays on the device until the first fetch.
+int32_t stash_results(srx_ctx* ctx, srx_pca_state& st, int k, int n_pc, const SelDev& sel) {
     const size_t kl = (size_t)k * L;
     double* sm = st.d_small + (size_t)st.rounds * (kl + 2 * L);      // behind the per-round blocks
-    st.dev_sel = hv != nullptr;
-    if (hv) {
-        CopySegs cs;                                           // (four runtime copies were 20 us of dispatches)
-        cs.src[0] = (const uint32_t*)hv->d_mu;       cs.dst[0] = (uint32_t*)sm;                          cs.words[0] = (uint32_t)k * 2;
-        cs.src[1] = (const uint32_t*)hv->d_sd;       cs.dst[1] = (uint32_t*)(sm + k);                    cs.words[1] = (uint32_t)k * 2;
-        cs.src[2] = (const uint32_t*)hv->d_trace;    cs.dst[2] = (uint32_t*)(sm + 2 * (size_t)k);        cs.words[2] = 2;
-        cs.src[3] = (const uint32_t*)hv->d_sel_rank; cs.dst[3] = (uint32_t*)(sm + 2 * (size_t)k + 2);    cs.words[3] = (uint32_t)k;
-        hipLaunchKernelGGL(k_copy_segs, dim3(16), dim3(256), 0, ctx->stream, cs);
-        SRX_HIP(ctx, hipGetLastError());
-        st.sel.clear();
-    } else {
-        st.pend_mu = mu;
-        st.pend_sd = sd;
-        st.pend_trace = trace;
-        st.sel = selv;
-    }
+    CopySegs cs;                                           // (four runtime copies were 20 us of dispatches)
+    cs.src[0] = (const uint32_t*)sel.d_mu;       cs.dst[0] = (uint32_t*)sm;                          cs.words[0] = (uint32_t)k * 2;
+    cs.src[1] = (const uint32_t*)sel.d_sd;       cs.dst[1] = (uint32_t*)(sm + k);                    cs.words[1] = (uint32_t)k * 2;
+    cs.src[2] = (const uint32_t*)sel.d_trace;    cs.dst[2] = (uint32_t*)(sm + 2 * (size_t)k);        cs.words[2] = 2;
+    cs.src[3] = (const uint32_t*)sel.d_sel_rank; cs.dst[3] = (uint32_t*)(sm + 2 * (size_t)k + 2);    cs.words[3] = (uint32_t)k;
+    hipLaunchKernelGGL(k_copy_segs, dim3(16), dim3(256), 0, ctx->stream, cs);
+    SRX_HIP(ctx, hipGetLastError());
+    st.sel.clear();
     st.k = (uint32_t)k;
     st.n_pc = (uint32_t)n_pc;
     st.host_pending = true;
@@ -1032,12 +1017,12 @@ int32_t stash_results(srx_ctx* ctx, srx_pca_state& st, int k, int n_pc, const Hv
     return SRX_OK;
 }
 
-template int32_t run_pca<float, float>(srx_ctx*, const RowMajor*, int, const Tiled*, double*, const Resolved&, const std::vector<double>&,
-                                        const std::vector<double>&, const HvgDev*, int, double, srx_pca_state&);
-template int32_t run_pca<float, double>(srx_ctx*, const RowMajor*, int, const Tiled*, double*, const Resolved&, const std::vector<double>&,
-                                         const std::vector<double>&, const HvgDev*, int, double, srx_pca_state&);
-template int32_t run_pca<double, double>(srx_ctx*, const RowMajor*, int, const Tiled*, double*, const Resolved&, const std::vector<double>&,
-                                          const std::vector<double>&, const HvgDev*, int, double, srx_pca_state&);
+template int32_t run_pca<float, float>(srx_ctx*, const RowMajor*, int, const Tiled*, double*, const Resolved&, const SelDev&, int, double,
+                                        srx_pca_state&);
+template int32_t run_pca<float, double>(srx_ctx*, const RowMajor*, int, const Tiled*, double*, const Resolved&, const SelDev&, int, double,
+                                         srx_pca_state&);
+template int32_t run_pca<double, double>(srx_ctx*, const RowMajor*, int, const Tiled*, double*, const Resolved&, const SelDev&, int, double,
+                                          srx_pca_state&);
 
 }  // namespace srx
 
@@ -1056,17 +1041,13 @@ int32_t srx_spmm(srx_mat* m, const uint64_t* sel, uint64_t k64, const double* pa
     srx_ctx* ctx = m->ctx;
     SRX_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (int)k64;
-    const uint64_t G = m->n_cols;
-    for (int s = 0; s < k; ++s) {
-        if (sel[s] >= G) return fail(ctx, SRX_E_BOUNDS, "selected feature index out of bounds");
-        if (s > 0 && sel[s] <= sel[s - 1]) return fail(ctx, SRX_E_ARG, "srx_spmm: sel must be strictly ascending");
-    }
-    uint32_t* d_sel;
-    int n_words;
-    SRX_TRY(upload_selection(ctx, sel, (size_t)k, G, &d_sel, &n_words));
+    for (int s = 1; s < k; ++s)
+        if (sel[s] <= sel[s - 1]) return fail(ctx, SRX_E_ARG, "srx_spmm: sel must be strictly ascending");
+    SelDev sd;                                     // (the bits alone: no moments, no vectors)
+    SRX_TRY(select_list(m, sel, k64, 0, 0, sd, false));
     RowMajor crm;
     Tiled c256;
-    SRX_TRY(compact_selection(m, d_sel, n_words, k, crm));
+    SRX_TRY(compact_selection(m, sd.d_bits, sd.n_words, k, crm));
     SRX_TRY(retile(m, crm, c256));
     const size_t kl = (size_t)k * L;
     double* T;

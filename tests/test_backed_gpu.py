@@ -168,6 +168,41 @@ def test_backed_explicit_selection_on_a_300k_column_matrix(ctx, tmp_path, k):
     assert np.allclose(r.explained_variance_ratio, wevr, rtol=1e-6)
 
 
+def test_backed_hvg_ranked_on_the_host(ctx, tmp_path):
+    """HighlyVariable(100) on a 70 000-column matrix: outside the device ranking's envelope, ranked on the host and passed
+    on as a list.  Selection (set and order), mean / std, explained variance ratio, scores and components against the
+    oracle.  HighlyVariable(9000) on 9500 genes ranks on the host too, and is refused by the session (at most 8192)."""
+    from singlerust_amd import _ffi, backed
+    m, _ = synth_host(7001, 400, 70000, 0.01)
+    lg = oracle.log1p_transform(oracle.normalize_total(m, 1e4, ROW))
+    r = backed.processing.pca_pipeline(open_backed(m, tmp_path, ctx), 150, 1e4, 100, 5, store=2)
+    assert np.array_equal(r.selected, oracle.select_hvg(oracle.compute_variance(lg, COLUMN), 100))
+    want, wc, wevr, wmean, wstd = pca_oracle.pca_inplace(lg, 5, None, None, r.selected)
+    assert np.allclose(r.mean, wmean, rtol=1e-9, atol=1e-12) and np.allclose(r.std, wstd, rtol=1e-9, atol=1e-12)
+    assert np.allclose(r.explained_variance_ratio, wevr, rtol=1e-6)
+    assert col_err(r.x_pca, want) < 1e-6 and col_err(r.components, wc) < 1e-6
+    m9, _ = synth_host(9501, 1500, 9500, 0.02)
+    with pytest.raises(_ffi.SrxError) as e:
+        backed.processing.pca_pipeline(open_backed(m9, tmp_path, ctx, "x9"), 500, 1e4, 9000, 5)
+    assert e.value.code == _ffi.E_ARG
+
+
+def test_backed_explicit_selection_validation(ctx, tmp_path):
+    """An explicit list with an index beyond the matrix (SRX_E_BOUNDS) and one that names a feature twice (SRX_E_ARG)."""
+    from singlerust_amd import _ffi, backed
+    m, _ = synth_host(5, 600, 300, 0.1)
+    ad = open_backed(m, tmp_path, ctx)
+    for sel, code in [([3, 7, 300], _ffi.E_BOUNDS), ([3, 7, 3], _ffi.E_ARG)]:
+        with pytest.raises(_ffi.SrxError) as e:
+            backed.processing.pca_pipeline(ad, 200, 1e4, 0, 2, selected=np.array(sel, np.uint64))
+        assert e.value.code == code
+
+
+def open_backed(m, tmp_path, ctx, name="x"):
+    from singlerust_amd import backed
+    return backed.BackedAnnData.open(store_of(m, tmp_path, name), ctx)
+
+
 def test_wide_selection_at_f64_storage_walks_gene_ranges(ctx, tmp_path):
     """6000 selected features at f64 storage: the forward kernel's panel slice of four f64 columns holds 5118 genes, so the
     scores come from two gene ranges, the second accumulating (round 2 refused this selection in backed mode).  Resident

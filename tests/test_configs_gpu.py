@@ -203,6 +203,21 @@ def test_explicit_selection_on_a_300k_column_matrix(ctx, k):
     assert col_err(a.obsm["X_pca"], want) < 1e-6 and col_err(a.uns["pca"]["components"], wc) < 1e-6
 
 
+@pytest.mark.parametrize("seed,n,g,density,n_hvg", [(9501, 1500, 9500, 0.02, 9000), (7001, 400, 70000, 0.01, 100)])
+def test_pipeline_hvg_ranked_on_the_host(ctx, seed, n, g, density, n_hvg):
+    """HighlyVariable(n) outside the device ranking's envelope (more than 8192 selected; more than 65536 columns): ranked on
+    the host and passed on as a list, whose selection table, mean / std and trace k_sel_finish makes.  Selection (set and
+    order), mean / std, explained variance ratio, scores and components against the oracle."""
+    m, _ = synth_host(seed, n, g, density)
+    _, scores, comps, evr, mean, std, hv = pipeline(ctx, m, 2, n_hvg, 5)
+    lg = oracle.log1p_transform(oracle.normalize_total(m, 1e4, ROW))
+    assert np.array_equal(hv, oracle.select_hvg(oracle.compute_variance(lg, COLUMN), n_hvg))
+    want, wc, wevr, wmean, wstd = pca_oracle.pca_inplace(lg, 5, None, None, hv)
+    assert np.allclose(mean, wmean, rtol=1e-9, atol=1e-12) and np.allclose(std, wstd, rtol=1e-9, atol=1e-12)
+    assert np.allclose(evr, wevr, rtol=1e-6)
+    assert col_err(scores, want) < 1e-6 and col_err(comps, wc) < 1e-6
+
+
 def test_reference_integration_flow(ctx):
     """tests/test_basic_load.rs:108-230 of the reference (load_file_with_test_plot_small_faer / _lapack), on a synthetic
     matrix instead of the h5ad file it reads: filter_cells_inplace(Absolute(200), None) -> filter_genes_inplace(

@@ -200,6 +200,52 @@ def test_center_scale_options(ctx, center, scale, solver):
     np.testing.assert_allclose(a.uns["pca"]["explained_variance_ratio"], evr, rtol=1e-8)
 
 
+def srx_pca(ctx, a, n_rows, sel, n_pc, center=-1, scale=-1):
+    from singlerust_amd import _ffi
+    sel = np.ascontiguousarray(sel, dtype=np.uint64)
+    k = len(sel)
+    opts = _ffi.PcaOpts(n_pc, int(center), int(scale), -1, 0, 0, 0, 0.0, 0)
+    info = _ffi.PcaInfo()
+    scores, comps, evr, mean, std = np.zeros((n_rows, n_pc)), np.zeros((k, n_pc)), np.zeros(n_pc), np.zeros(k), np.zeros(k)
+    _ffi.check(_ffi.lib().srx_pca(a.x().handle, _ffi.ptr(sel), k, C.byref(opts), _ffi.ptr(scores), _ffi.ptr(comps), _ffi.ptr(evr),
+                                  _ffi.ptr(mean), _ffi.ptr(std), C.byref(info)), ctx.handle)
+    return scores, comps, evr, mean, std
+
+
+def test_explicit_selection_validation(ctx):
+    """An explicit list with an index beyond the matrix (SRX_E_BOUNDS) and one that names a feature twice (SRX_E_ARG)."""
+    from singlerust_amd import _ffi
+    m, _ = synth_host(5, 600, 300, 0.1)
+    a = adata_of(m, ctx, 2)
+    for sel, code in [([3, 7, 300], _ffi.E_BOUNDS), ([3, 7, 3], _ffi.E_ARG)]:
+        with pytest.raises(_ffi.SrxError) as e:
+            srx_pca(ctx, a, m.n_rows, sel, 2)
+        assert e.value.code == code
+
+
+@pytest.mark.parametrize("center", [True, False])
+def test_constant_selected_feature_is_not_scaled(ctx, center):
+    """An explicitly selected feature that is non-zero and the same in every cell, with scale = true: its std is exactly 0
+    and the PCA divides by 1 in its place (the reference divides by 0).  Against the exact SVD of that standardisation."""
+    rng = np.random.default_rng(3)
+    n, g = 200, 40
+    dense = np.where(rng.random((n, g)) < 0.2, rng.integers(1, 30, (n, g)), 0).astype(np.float64)
+    dense[:, 17] = 3.0
+    indptr = np.concatenate([[0], np.cumsum((dense != 0).sum(axis=1))]).astype(np.uint64)
+    rows, cols = np.nonzero(dense)
+    m = oracle.Csr(n, g, indptr, cols.astype(np.uint64), dense[rows, cols].astype(np.float32))
+    sel = np.array([5, 17, 0, 39, 22, 8, 11, 30], np.uint64)
+    scores, comps, evr, mean, std = srx_pca(ctx, adata_of(m, ctx, 2), n, sel, 4, center, True)
+    x = dense[:, sel.astype(np.int64)]
+    sd = x.std(axis=0)
+    assert std[1] == 0.0 and mean[1] == 3.0
+    assert np.allclose(mean, x.mean(axis=0), rtol=1e-14) and np.allclose(std, sd, rtol=1e-12)
+    z = (x - (x.mean(axis=0) if center else 0.0)) / np.where(sd > 0, sd, 1.0)
+    u, s, vt = np.linalg.svd(z, full_matrices=False)
+    assert np.allclose(evr, (s * s)[:4] / (s * s).sum(), rtol=1e-9)
+    assert col_err(comps, vt[:4].T) < 1e-9 and col_err(scores, u[:, :4] * s[:4]) < 1e-9
+
+
 def test_defaults_and_small_k(ctx):
     """n_components None -> 2 (dim_red/mod.rs:52); k < 64 panel columns; FeatureSelection::None."""
     import singlerust_amd as sr
