@@ -5,6 +5,7 @@ HVG(2000) -> 50-PC PCA  on synthetic CSR resident in HBM, plus the SpMM's achiev
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py ... --dump-outputs DIR      (also the last timed step's outputs as DIR/<name>.npy, to compare builds)
+    python bench.py ... --full                  (also every side measurement below)
 
 A "step" is one srx_pipeline() call over one fresh copy of the raw count matrix (the pipeline normalises X in place,
 so every step gets its own copy, cloned — with its pattern-only index structures and its reserved result block —
@@ -12,11 +13,14 @@ before the timed region: a step makes no device allocation).
 
 N = 1: BASELINE.json configs[2], the configuration the north_star targets are quoted on (1.3M x 28k, ~3 % nnz; it
 fits one GPU).  N > 1: configs[3] read literally — the SAME 1.3M cells row-sharded over the N GPUs (strong scaling,
-nnz-balanced shards, RCCL all-reduce of the gene moments and of the packed Gram triangle); a `weak` block (1.3M cells
-per GPU) is measured after it with fewer steps.
+nnz-balanced shards, RCCL all-reduce of the gene moments and of the packed Gram triangle); with --full a `weak` block
+(1.3M cells per GPU) is measured after it with fewer steps.
 
-One JSON line on rank 0.  Besides the contract's fields it carries (N = 1 only, each a short bounded run after the
-timed region): the f64-storage pipeline (`f64_storage`), the matrix-free solver's SpMM kernels (`roofline_spmm_iter`),
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps (with the class timers of the `roofline`
+object's stage on, as ever), dumps the outputs if asked to and prints the line: nothing else.  --full adds, after the
+timed region: the other kernel classes' times in a breakdown pass of their own (`roofline_next`, `roofline_spmm`,
+`unattributed_ms_per_step`, `step_roofline`) and (N = 1 only, each a short bounded run):
+the f64-storage pipeline (`f64_storage`), the matrix-free solver's SpMM kernels (`roofline_spmm_iter`),
 a skewed-gene matrix (`skewed_genes`), a hard spectrum (`hard_spectrum`), the rate including the upload of a host CSR
 and the download of the scores (`incl_h2d`), the pipeline on a fresh un-prepared handle (`cold_step`), configs[4] streamed
 from pinned host memory through the backed session (`c5_backed`), and three CPU baselines timed on this box (`cpu_baseline`:
@@ -122,11 +126,16 @@ def parse():
                     help="out-of-core form (configs[4]): the matrix stays in pinned host memory and is streamed as row tiles "
                          "through the srx_backed_* session, two sweeps; reports H2D-bound cells/s")
     ap.add_argument("--tile-rows", type=int, default=250_000, help="--backed: cells per streamed tile")
-    ap.add_argument("--lean", action="store_true", help="only the headline measurement (no extra blocks, no CPU baselines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample-cells", type=int, default=24000, help="reference-faithful CPU baseline: cells of the sample")
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument("--full", action="store_true",
+                      help="after the headline: the breakdown pass of every kernel class, the side blocks (other storage, cold "
+                           "step, skewed genes, hard spectrum, scaling budget, weak scaling at N > 1, configs[4] out of core) and "
+                           "the CPU baselines")
+    mode.add_argument("--lean", action="store_true", help="the headline only: what a run without --full does (kept for old command lines)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the host-side legs and CPU baselines")
+    ap.add_argument("--cpu-sample-cells", type=int, default=24000, help="--full: cells of the reference-faithful CPU baseline's sample")
     ap.add_argument("--host-sample-cells", type=int, default=0,
-                    help="cells of the host-side legs (incl_h2d blocks, threaded CPU baseline); 0 = the whole configuration")
+                    help="--full: cells of the host-side legs (incl_h2d blocks, threaded CPU baseline); 0 = the whole configuration")
     ap.add_argument("--max-copies-gb", type=float, default=180.0)
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (rank 0's rows) as DIR/<name>.npy "
@@ -300,9 +309,11 @@ class Bench:
         return int(cut[self.rank]), int(cut[self.rank + 1])
 
     def run(self, config, n_global, row0, row1, storage, steps, warmup, solver=0, hvg=None, skew=0, tolerate_noconv=False, headline=False,
-            per_step=False, fetch=False):
+            breakdown=False, per_step=False, fetch=False):
         """K timed pipeline steps on rows [row0, row1) of the synthetic matrix; returns the measurements of this rank
-        (times already maxed over ranks).  fetch: also the outputs of the last timed step (fetch_outputs), under `outputs`."""
+        (times already maxed over ranks).  headline: the timed steps carry the Gram formation stage's class timers only, and
+        with `breakdown` every class is timed in a pass of its own behind them.  fetch: also the outputs of the last timed
+        step (fetch_outputs), under `outputs`."""
         a, F, sr, lib, ctx = self.a, self.F, self.sr, self.lib, self.ctx
         hvg = hvg or a.hvg
         p = self.params(config, n_global, skew)
@@ -400,23 +411,24 @@ class Bench:
 
         all_mask = sum(1 << c for c in classes)
         step_ms = []
-        breakdown = None
+        bd_record = None
         if headline:
             # The K timed steps carry the class timers of the roofline object's stage only (compaction, owner records, stripe
             # kernel: six event records per step); a timer is two event records around its launches, and with all eight classes
             # on the records themselves cost 0.05-0.08 ms of a 9.7 ms step (measured: 9.74-9.81 against 9.66-9.74 with none).
-            # The other classes are timed in a SEPARATE pass of a few steps behind the clock, reported as such.
+            # The other classes are timed in a SEPARATE pass of a few steps behind the clock (`breakdown`), reported as such.
             elapsed, prof, stage, iters = timed_pass(steps, sum(1 << c for c in stage_classes))
             outputs = fetch_outputs(F, copies[used - 1], res, storage) if fetch else None      # before the breakdown pass reuses it
-            bd_steps = max(3, min(steps, 8))
-            bd_elapsed, bd_prof, _, _ = timed_pass(bd_steps, all_mask)
-            for name, rec in bd_prof.items():
-                if name not in prof:
-                    # (downstream divides a class's launches by the K timed steps: the record is scaled to K steps' worth)
-                    prof[name] = {**rec, "launches": rec["launches"] * steps / bd_steps, "timed_in": "breakdown pass"}
-            breakdown = {"steps": bd_steps, "ms_per_step": bd_elapsed / bd_steps * 1e3,
-                         "kernel_ms_per_step": {name: rec["avg_ms"] * rec["launches"] / bd_steps for name, rec in bd_prof.items()},
-                         "note": "all class timers on, behind the timed region: the source of every class time outside the Gram formation stage"}
+            if breakdown:
+                bd_steps = max(3, min(steps, 8))
+                bd_elapsed, bd_prof, _, _ = timed_pass(bd_steps, all_mask)
+                for name, rec in bd_prof.items():
+                    if name not in prof:
+                        # (downstream divides a class's launches by the K timed steps: the record is scaled to K steps' worth)
+                        prof[name] = {**rec, "launches": rec["launches"] * steps / bd_steps, "timed_in": "breakdown pass"}
+                bd_record = {"steps": bd_steps, "ms_per_step": bd_elapsed / bd_steps * 1e3,
+                             "kernel_ms_per_step": {name: rec["avg_ms"] * rec["launches"] / bd_steps for name, rec in bd_prof.items()},
+                             "note": "all class timers on, behind the timed region: the source of every class time outside the Gram formation stage"}
         else:
             elapsed, prof, stage, iters = timed_pass(steps, all_mask)
             outputs = fetch_outputs(F, copies[used - 1], res, storage) if fetch else None
@@ -425,7 +437,7 @@ class Bench:
                "stage_ms_per_step": {k_: v / steps for k_, v in stage.items()}, "iters": iters,
                "residual": float(res.pca.residual), "nnz_selected": int(res.pca.nnz_selected),
                "solver": {1: "gram", 2: "spmm"}.get(int(res.pca.solver), "?"), "generate_s": t_gen, "copies": n_copies,
-               "noconv_steps": len(failures), "genes": int(info.n_cols), "breakdown": breakdown, "step_ms": sorted(step_ms),
+               "noconv_steps": len(failures), "genes": int(info.n_cols), "breakdown": bd_record, "step_ms": sorted(step_ms),
                "outputs": outputs}
         for c in copies:
             c.free()
@@ -1025,11 +1037,11 @@ def main():
     p = B.params(a.config, n_global, a.skew)
     row0, row1 = B.shard(p, n_global)
     main_ = B.run(a.config, n_global, row0, row1, a.storage, a.steps, a.warmup, solver=a.solver, skew=a.skew, headline=True,
-                  fetch=bool(a.dump_outputs) and rank == 0)
+                  breakdown=a.full, fetch=bool(a.dump_outputs) and rank == 0)
     outputs = main_.pop("outputs")
     dumped = dump_outputs(a.dump_outputs, outputs) if outputs is not None else None
     weak = None
-    if world > 1 and scaling == "strong" and not a.lean:
+    if a.full and world > 1 and scaling == "strong":
         # the other reading of the scaling question: per-GPU work fixed (the config's cells on EVERY GPU)
         ng = cells * world
         pw = B.params(a.config, ng, a.skew)
@@ -1040,7 +1052,7 @@ def main():
                 "value": ng * wk / w["elapsed"], "unit": "cells/s", "subspace_iterations": w["iters"]}
 
     extra = {}
-    if rank == 0 and world == 1 and not a.lean:
+    if a.full and rank == 0 and world == 1:
         def attempt(name, fn):
             try:
                 extra[name] = fn()
@@ -1154,7 +1166,7 @@ def main():
         for name, d in prof.items():
             per_step = traffic.get(name)
             d["hbm_traffic_per_launch"] = per_step / (d["launches"] / a.steps) if per_step else None
-        per, serial = attributed(prof, a.steps)
+        per, _ = attributed(prof, a.steps)
         # the step as a whole against the HBM peak: algorithmic bytes of every serial class (dense_apply sits inside iterate)
         serial_cls = [k_ for k_ in prof if k_ not in ("dense_apply", "normalize_log1p")]
         step_alg = sum(prof[k_]["alg_bytes_per_launch"] * prof[k_]["launches"] / a.steps for k_ in serial_cls)
@@ -1239,25 +1251,26 @@ def main():
             "roofline_next": ({**roof(prof.get(dom2_name, {}), KERNEL_SYMBOL.get(dom2_name, dom2_name), ROOF_NOTE.get(dom2_name, ""),
                                       other_bounds(dom2_name, prof.get(dom2_name, {}), main_["nnz_selected"], row1 - row0)),
                                "stage": stage_block(order[1])} if dom2_name else None),
-            # BASELINE.json's second metric: the CSR x 64-column-panel SpMM against the HBM peak
-            "roofline_spmm": roof(prof.get("spmm_fwd", {}), KERNEL_SYMBOL["spmm_fwd"], ROOF_NOTE["spmm_fwd"],
-                                  other_bounds("spmm_fwd", prof.get("spmm_fwd", {}), main_["nnz_selected"], row1 - row0)),
+            # BASELINE.json's second metric: the CSR x 64-column-panel SpMM against the HBM peak (timed in the breakdown pass)
+            "roofline_spmm": (roof(prof.get("spmm_fwd", {}), KERNEL_SYMBOL["spmm_fwd"], ROOF_NOTE["spmm_fwd"],
+                                   other_bounds("spmm_fwd", prof.get("spmm_fwd", {}), main_["nnz_selected"], row1 - row0))
+                              if main_["breakdown"] else None),
             "kernels": prof,
             "kernel_ms_per_step": per,
             # step time outside every bracketed class (launch gaps, host waits, scans, small copies) — of the breakdown pass, whose
-            # step carries all the class timers (its own step time minus its own class times); the timed steps carry three
+            # step carries all the class timers (its own step time minus its own class times); the timed steps carry three.
+            # Without --full there is no breakdown pass, and neither this nor `step_roofline` (every class of the step) is known
             "unattributed_ms_per_step": ((main_["breakdown"]["ms_per_step"] - sum(v for k_, v in main_["breakdown"]["kernel_ms_per_step"].items()
                                                                                   if k_ not in ("dense_apply", "normalize_log1p")))
-                                         if main_.get("breakdown") else main_["ms_per_step"] - serial),
-            "class_timers": ({"timed_region": ["hvg_compact", "gram_bucket", "gram_sparse"], "breakdown_pass": main_["breakdown"]}
-                             if main_.get("breakdown") else None),
-            "step_roofline": {"step_alg_bytes": step_alg, "step_aux_bytes": step_aux, "step_hbm_traffic": step_traffic,
-                              "achieved_GBps": step_alg / (main_["ms_per_step"] * 1e-3) / 1e9,
-                              "frac_of_peak": step_alg / (main_["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              "traffic_GBps": step_traffic / (main_["ms_per_step"] * 1e-3) / 1e9 if step_traffic else None,
-                              "note": "algorithmic bytes of every kernel class of a step (minimum data each must move, SURVEY.md "
-                                      "8(d)) over the whole step time; step_hbm_traffic = PMC counter traffic of the same classes "
-                                      "from the committed profile"},
+                                         if main_["breakdown"] else None),
+            "class_timers": {"timed_region": ["hvg_compact", "gram_bucket", "gram_sparse"], "breakdown_pass": main_["breakdown"]},
+            "step_roofline": ({"step_alg_bytes": step_alg, "step_aux_bytes": step_aux, "step_hbm_traffic": step_traffic,
+                               "achieved_GBps": step_alg / (main_["ms_per_step"] * 1e-3) / 1e9,
+                               "frac_of_peak": step_alg / (main_["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               "traffic_GBps": step_traffic / (main_["ms_per_step"] * 1e-3) / 1e9 if step_traffic else None,
+                               "note": "algorithmic bytes of every kernel class of a step (minimum data each must move, SURVEY.md "
+                                       "8(d)) over the whole step time; step_hbm_traffic = PMC counter traffic of the same classes "
+                                       "from the committed profile"} if main_["breakdown"] else None),
             "stage_ms_per_step": main_["stage_ms_per_step"],
             "traffic_source": f"profiles/{traffic_round}_traffic_{a.config}.json" if traffic_round else None,
             "setup": {"generate_s": main_["generate_s"], "copies": main_["copies"]},

@@ -19,7 +19,7 @@ def test_two_rank_bench_line():
     env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(20000 + os.getpid() % 20000),
                SRX_BENCH_DEVICE="0", SRX_BENCH_COLLECTIVE="host", TORCHELASTIC_RUN_ID=f"t{os.getpid()}")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--cells", str(cells), "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-cpu-baseline"]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                               cwd=ROOT) for r in range(world)]
     outs = [p.communicate(timeout=600) for p in procs]
@@ -30,8 +30,8 @@ def test_two_rank_bench_line():
     assert not outs[1][0].decode().strip()                 # and nothing at all on the other rank's
     assert len(lines0[0]) < 8000                           # a record the driver parses, not a document
     d = json.loads(lines0[0])
-    # N > 1 defaults to STRONG scaling (BASELINE.json configs[3]: the same cells row-sharded over the GPUs) and carries a
-    # `weak` block measured after it
+    # N > 1 defaults to STRONG scaling (BASELINE.json configs[3]: the same cells row-sharded over the GPUs); with --full it
+    # carries a `weak` block measured after it
     assert d["n_gpus"] == world and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "strong"
     assert d["unit"] == "cells/s" and d["higher_is_better"] is True and d["vs_baseline"] is None
     c = d["config"]
@@ -104,13 +104,12 @@ def test_backed_run_across_two_ranks():
     assert abs(d2["value"] - cells / (d2["ms_per_step"] * 1e-3)) <= 1e-6 * d2["value"]
 
 
-def test_default_command_prints_a_bounded_record():
-    """The driver's own command shape (one GPU, no --lean, every side block and the CPU baselines on — at a reduced cell count
-    so that the test stays short): ONE stdout line under 8000 bytes with roofline and cpu_baseline in it; the full document in
-    bench_full.json."""
+def test_full_command_prints_a_bounded_record():
+    """The --full command shape (one GPU, every side block and the CPU baselines on — at a reduced cell count so that the test
+    stays short): ONE stdout line under 8000 bytes with roofline and cpu_baseline in it; the full document in bench_full.json."""
     cells = 60000
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cells", str(cells), "--steps", "3", "--warmup", "1",
-           "--cpu-sample-cells", "2000"]
+           "--full", "--cpu-sample-cells", "2000"]
     p = subprocess.run(cmd, env=_clean_env(SRX_BENCH_NO_C5="1"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=ROOT, timeout=1200)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
@@ -125,6 +124,34 @@ def test_default_command_prints_a_bounded_record():
     with open(os.path.join(ROOT, "bench_full.json")) as fh:
         full = json.loads(fh.read())
     assert full["value"] == d["value"] and "kernels" in full and "strong_scaling_budget" in full
+
+
+def test_plain_command_measures_the_headline_only():
+    """Without --full the run is the headline alone: the timed steps (the Gram formation stage's class timers on, as with
+    --full), the one record line — no breakdown pass, no side block, no CPU baseline, in the line or in bench_full.json."""
+    cells = 20000
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c2", "--cells", str(cells), "--steps", "2",
+           "--warmup", "1"]
+    p = subprocess.run(cmd, env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=ROOT, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f32" and d["unit"] == "cells/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - cells / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["config"]["pca_residual"] < 1e-6
+    # the only class times are those of the timed steps' own timers
+    assert d["roofline"]["frac"] > 0 and "gram_sparse" in d["kernel_ms_per_step"]
+    assert set(d["kernel_ms_per_step"]) <= {"hvg_compact", "gram_bucket", "gram_sparse"}
+    for k in ("roofline_next", "roofline_spmm", "cpu_baseline", "gpu_over_cpu", "cold_cells_per_s", "unattributed_ms_per_step",
+              "step_frac_of_hbm_peak", "weak"):
+        assert k not in d, k
+    with open(os.path.join(ROOT, "bench_full.json")) as fh:
+        full = json.loads(fh.read())
+    assert full["value"] == d["value"] and full["class_timers"]["breakdown_pass"] is None
+    for k in ("f64_storage", "cold_step", "roofline_spmm_iter", "skewed_genes", "hard_spectrum", "strong_scaling_budget", "incl_h2d",
+              "cpu_baseline", "c5_backed"):
+        assert k not in full, k
 
 
 def test_dump_outputs_of_the_last_timed_step(tmp_path):
