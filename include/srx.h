@@ -32,7 +32,9 @@ extern "C" {
 #endif
 
 #define SRX_ABI_VERSION 6      /* 2: srx_matrix_reserve_results, kernel classes 7-9, srx_synth_params.skew; 3: kernel class 10;
-                                  4: srx_comm_info, srx_prof_get_aux; 5: srx_comm_overlap_info; 6: srx_gram_mode_info, srx_gram_exchange_ranges */
+                                  4: srx_comm_info, srx_prof_get_aux; 5: srx_comm_overlap_info; 6: srx_gram_mode_info, srx_gram_exchange_ranges.
+                                  Purely additive entry points leave the version as it is and are detected by symbol:
+                                  srx_pca_model_* / srx_pca_transform (fitted-PCA projection) came that way at 6 */
 
 typedef struct srx_ctx srx_ctx;   /* one GPU + stream + (optional) RCCL communicator      */
 typedef struct srx_mat srx_mat;   /* device-resident CSR (the `X` of an IMAnnData)        */
@@ -326,6 +328,40 @@ int32_t srx_pca(srx_mat* m, const uint64_t* sel, uint64_t k, const srx_pca_opts*
  * loadings row i = components[i,:] * std[i] (pca/mod.rs:204-215), other rows 0. */
 int32_t srx_pca_loadings(const double* components, const double* std_, const uint64_t* sel,
                          uint64_t k, uint64_t n_pc, uint64_t n_vars, double* out);
+
+/* ---- a fitted PCA applied to other cells: Pca::transform (src/shared/processing/pca/mod.rs:156-185)
+ * A model is k feature rows (V: k x n_pc, mu, sd, flags center / scale) held on the device.  For a query
+ * matrix Xq (cells x its own genes) and a feature map feat (k entries: the query column of model row i,
+ * UINT64_MAX = the gene is absent from the query):
+ *     scores[r, j] = sum_i ((x(r, i) - (center ? mu_i : 0)) / (scale ? sd'_i : 1)) * V[i, j]
+ *     x(r, i) = Xq'[r, feat[i]], 0 for an absent gene;  sd'_i = sd_i, or 1 where sd_i == 0 (as srx_pca)
+ *     Xq' = Xq, or normalize_total(target_sum, Row) then ln_1p per the SRX_BACKED_NORMALIZE / _LOG1P bits,
+ *           applied on the fly (both bits: the rounding of the pipeline's write-back) — the query's values
+ *           are never modified.
+ * Absent genes still contribute their -mu_i / sd'_i V[i, :] term (every model row enters the constant).
+ * No sign flip: the components were sign-fixed by the fit.  The transform is row-local: on a sharded
+ * context each rank scores its own rows, no collective.  The same model and query give bit-identical
+ * scores on every call, and the query's own resident PCA result is left as it was. */
+typedef struct srx_pca_model srx_pca_model;
+/* The model the last srx_pca / srx_pipeline on m left in HBM, copied device to device (no host round trip);
+ * it owns its copies, so m may be freed or re-fitted afterwards.  SRX_E_ARG when m holds no result. */
+int32_t srx_pca_model_from_result(srx_mat* m, srx_pca_model** out);
+/* A model fitted elsewhere: components k x n_pc row-major, mean / std k (as srx_pca returns them; mean may be
+ * NULL when !center, std NULL when !scale).  sel (k gene ids of the fitted matrix, may be NULL) is only
+ * remembered for srx_pca_model_info and for srx_pca_transform with feat == NULL.  SRX_E_ARG for k < 1,
+ * n_pc < 1, n_pc > k, NaN in components or mean, a negative or non-finite std. */
+int32_t srx_pca_model_create(srx_ctx* ctx, uint64_t k, uint64_t n_pc, const double* components, const double* mean,
+                             const double* std_, const uint64_t* sel, int32_t center, int32_t scale, srx_pca_model** out);
+/* Shape of a model; sel_out (room for k, may be NULL) receives its sel — SRX_E_ARG if it has none. */
+int32_t srx_pca_model_info(const srx_pca_model* p, uint64_t* k_out, uint64_t* n_pc_out, uint64_t* sel_out);
+void    srx_pca_model_free(srx_pca_model* p);
+/* feat: k query columns aligned with the model's rows (UINT64_MAX = absent; a column named twice is
+ * SRX_E_ARG, one >= the query's gene count SRX_E_BOUNDS); NULL = the model's own sel (the query has the fitted
+ * matrix's gene axis).  transform: SRX_BACKED_NORMALIZE | SRX_BACKED_LOG1P bits (0 = the values as they are).
+ * scores_out: n_rows x n_pc row-major f64 (obsm["X_pca"] layout); a query with 0 rows writes nothing.  A CSC
+ * query is transposed on the device first.  Model and query must share the context. */
+int32_t srx_pca_transform(srx_pca_model* p, srx_mat* q, const uint64_t* feat, double target_sum, int32_t transform,
+                          double* scores_out);
 
 /* The raw operators the PCA is built from, for a caller-supplied 64-column panel (k x 64
  * row-major): y_out (n_rows x 64) = X[:, sel] * panel, t_out (k x 64) = X[:, sel]^T * y, and

@@ -661,6 +661,77 @@ pub mod processing_free {
             attach_pca_results(anndata, transformed, None, Some(evr), selected, n_pc)
         }
 
+        /// `Pca` after `fit` (src/shared/processing/pca/mod.rs:74), held on the device: `transform` (:156-185) projects the
+        /// cells of another IMAnnData into the fitted PC space.  The model owns its device copies: the fitted matrix may be
+        /// dropped or re-fitted afterwards.
+        pub struct PcaModel { h: *mut SrxPcaModel, genes: Option<Vec<String>> }
+        impl Drop for PcaModel { fn drop(&mut self) { unsafe { srx_pca_model_free(self.h) } } }
+        /// Feature-map entry of a model gene the query does not have.
+        pub const ABSENT: u64 = u64::MAX;
+        impl PcaModel {
+            /// The model the last `pca_inplace` on `adata` left in HBM (the resident handle's result, device to device).
+            pub fn from_adata(adata: &IMAnnData) -> anyhow::Result<PcaModel> {
+                let names = adata.var_names().into_vec();
+                let mut h: *mut SrxPcaModel = null_mut();
+                with_resident(adata, |x| x.ctx.check(unsafe { srx_pca_model_from_result(x.mat, &mut h) }))?;
+                let mut m = PcaModel { h, genes: None };
+                let (k, _) = m.shape()?;
+                let mut sel = vec![0u64; k];
+                with_ctx(|c| c.check(unsafe { srx_pca_model_info(m.h, null_mut(), null_mut(), sel.as_mut_ptr()) }))?;
+                m.genes = Some(sel.iter().map(|&i| names[i as usize].clone()).collect());
+                Ok(m)
+            }
+            /// A model from its parts: components k x n_pc, mean / std k (as `Pca` keeps them), the fitted matrix's selected
+            /// feature ids and gene names (`var_names` of the fitted matrix) for the feature map.
+            pub fn from_parts(components: &Array2<f64>, mean: &[f64], std: &[f64], selected: &[usize], var_names: &[String],
+                              center: bool, scale: bool) -> anyhow::Result<PcaModel> {
+                let (k, n_pc) = components.dim();
+                if mean.len() != k || std.len() != k || selected.len() != k {
+                    bail!("PcaModel::from_parts: mean, std and the selection need k = {k} entries");
+                }
+                let comps: Vec<f64> = components.iter().copied().collect();            // row-major k x n_pc
+                let sel: Vec<u64> = selected.iter().map(|&i| i as u64).collect();
+                let mut h: *mut SrxPcaModel = null_mut();
+                with_ctx(|c| c.check(unsafe {
+                    srx_pca_model_create(c.0, k as u64, n_pc as u64, comps.as_ptr(), mean.as_ptr(), std.as_ptr(), sel.as_ptr(),
+                                         center as i32, scale as i32, &mut h)
+                }))?;
+                let genes = selected.iter().map(|&i| var_names.get(i).cloned().ok_or_else(|| anyhow!("feature {i} out of bounds")))
+                    .collect::<anyhow::Result<Vec<String>>>()?;
+                Ok(PcaModel { h, genes: Some(genes) })
+            }
+            fn shape(&self) -> anyhow::Result<(usize, usize)> {
+                let (mut k, mut n_pc) = (0u64, 0u64);
+                with_ctx(|c| c.check(unsafe { srx_pca_model_info(self.h, &mut k, &mut n_pc, null_mut()) }))?;
+                Ok((k as usize, n_pc as usize))
+            }
+            /// The query column of each model gene, by name (`ABSENT` where the query lacks it).
+            pub fn feature_map(&self, query_names: &[String]) -> anyhow::Result<Vec<u64>> {
+                let genes = self.genes.as_ref().ok_or_else(|| anyhow!("the model has no gene names"))?;
+                let at: std::collections::HashMap<&str, u64> = query_names.iter().enumerate().map(|(j, n)| (n.as_str(), j as u64)).collect();
+                Ok(genes.iter().map(|g| at.get(g.as_str()).copied().unwrap_or(ABSENT)).collect())
+            }
+            /// Pca::transform (pca/mod.rs:156-185) of the cells of `adata`, X as it is: n_obs x n_pc scores.  The gene axes are
+            /// matched by name when they differ; a gene of the model the query lacks contributes its centring term only.
+            pub fn transform(&self, adata: &IMAnnData) -> anyhow::Result<Array2<f64>> {
+                self.transform_with(adata, None, false)
+            }
+            /// The same with normalize_total(target_sum, Row) and / or ln_1p applied to the raw values on the fly (X is not
+            /// modified).
+            pub fn transform_with(&self, adata: &IMAnnData, target_sum: Option<f64>, log1p: bool) -> anyhow::Result<Array2<f64>> {
+                let (_, n_pc) = self.shape()?;
+                let names = adata.var_names().into_vec();
+                let feat = self.feature_map(&names)?;
+                let bits = if target_sum.is_some() { SRX_BACKED_NORMALIZE } else { 0 } | if log1p { SRX_BACKED_LOG1P } else { 0 };
+                let mut scores = vec![0.0f64; adata.n_obs() * n_pc];
+                with_resident(adata, |x| x.ctx.check(unsafe {
+                    srx_pca_transform(self.h, x.mat, feat.as_ptr(), target_sum.unwrap_or(0.0), bits as i32,
+                                      if scores.is_empty() { null_mut() } else { scores.as_mut_ptr() })
+                }))?;
+                Ok(Array2::from_shape_vec((adata.n_obs(), n_pc), scores)?)
+            }
+        }
+
         /// dim_red/mod.rs:96-121, UNCHANGED (copied call for call so that the module is self-contained): obsm["X_pca"] and,
         /// when loadings are given, varm["PCA_loadings"] with row selected[i] <- loadings row i.
         fn attach_pca_results(anndata: &mut IMAnnData, transformed: Array2<f64>, loadings: Option<Array2<f64>>,

@@ -56,6 +56,7 @@ pub const SRX_K_COUNT_: i32 = 11;
 
 #[repr(C)] pub struct SrxCtx { _private: [u8; 0] }      // opaque `srx_ctx`
 #[repr(C)] pub struct SrxMat { _private: [u8; 0] }      // opaque `srx_mat`
+#[repr(C)] pub struct SrxPcaModel { _private: [u8; 0] }      // opaque `srx_pca_model`
 #[repr(C)] pub struct SrxBacked { _private: [u8; 0] }      // opaque `srx_backed`
 
 #[repr(C)]
@@ -188,6 +189,14 @@ extern "C" {
                    components: *mut f64, evr: *mut f64, mean: *mut f64, std: *mut f64, info: *mut SrxPcaInfo) -> i32;
     pub fn srx_pca_loadings(components: *const f64, std: *const f64, sel: *const u64, k: u64, n_pc: u64,
                             n_vars: u64, out: *mut f64) -> i32;
+    pub fn srx_pca_model_from_result(m: *mut SrxMat, out: *mut *mut SrxPcaModel) -> i32;
+    pub fn srx_pca_model_create(ctx: *mut SrxCtx, k: u64, n_pc: u64, components: *const f64, mean: *const f64,
+                                std: *const f64, sel: *const u64, center: i32, scale: i32,
+                                out: *mut *mut SrxPcaModel) -> i32;
+    pub fn srx_pca_model_info(p: *const SrxPcaModel, k_out: *mut u64, n_pc_out: *mut u64, sel_out: *mut u64) -> i32;
+    pub fn srx_pca_model_free(p: *mut SrxPcaModel);
+    pub fn srx_pca_transform(p: *mut SrxPcaModel, q: *mut SrxMat, feat: *const u64, target_sum: f64,
+                             transform: i32, scores_out: *mut f64) -> i32;
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,

@@ -127,6 +127,11 @@ _SIGS = {
     "srx_select_hvg": (C.c_int32, [P, C.c_uint64, P, C.POINTER(C.c_uint64)]),
     "srx_pca": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PcaOpts), P, P, P, P, P, C.POINTER(PcaInfo)]),
     "srx_pca_loadings": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint64, C.c_uint64, P]),
+    "srx_pca_model_from_result": (C.c_int32, [P, C.POINTER(P)]),
+    "srx_pca_model_create": (C.c_int32, [P, C.c_uint64, C.c_uint64, P, P, P, P, C.c_int32, C.c_int32, C.POINTER(P)]),
+    "srx_pca_model_info": (C.c_int32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), P]),
+    "srx_pca_model_free": (None, [P]),
+    "srx_pca_transform": (C.c_int32, [P, P, P, C.c_double, C.c_int32, P]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),

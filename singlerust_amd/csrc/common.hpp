@@ -131,6 +131,7 @@ struct srx_pca_state {           // what the last srx_pca / srx_pipeline left in
     bool valid = false;
     uint32_t k = 0, n_pc = 0;
     uint32_t rounds = 1;             // deflation rounds of the solve
+    int center = 1, scale = 1;       // the flags the solve ran with (srx_pca_model_from_result)
     std::vector<int> round_counts;   // components resolved by each round (sums to n_pc)
     double* d_scores = nullptr;      // n_rows x n_pc, row-major f64
     size_t scores_cap = 0;
@@ -280,7 +281,7 @@ int32_t moments_install(srx_mat* m, double* d_packed);     // all-reduce d_packe
 int32_t launch_row_apply(srx_mat* m, double target, hipStream_t stream);   // in-place write-back from the row sums in m->d_row_sum
 int32_t launch_normalize(srx_mat* m, double target, bool do_norm, bool do_log, hipStream_t stream = nullptr,
                          bool precise = false, int wgs_per_cu = 0);
-int32_t launch_row_sums(srx_mat* m);
+int32_t launch_row_sums(srx_mat* m, double* out = nullptr);     // out null: into m->d_row_sum
 int32_t ensure_moments_xf(srx_mat* m, RowXf xf);      // moments of the TRANSFORMED values from the raw matrix
 inline void touch(srx_mat* m) { m->version++; m->pca.valid = false; }
 

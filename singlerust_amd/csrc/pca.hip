@@ -80,6 +80,8 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
     Resolved o;
     int l_act = 0;
     SRX_TRY(resolve_opts(ctx, opts, k, Ng, is_f32(m), o, l_act));
+    st.center = o.center;
+    st.scale = o.scale;
     SelDev sd;
     if (hvg_n > 0) {
         Range r_("srx:select_hvg");

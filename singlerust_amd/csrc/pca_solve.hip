@@ -1,7 +1,8 @@
 // pca_solve.hip — the solver half of dim_red::pca_inplace on the GPU (pca.hip has the overview): the sparse products with a
 // k x 64 panel (spmm.inl), the k x 64 subspace iteration on the device (iterate.inl, jacobi.inl: dense apply on the f64 matrix
 // cores, CholeskyQR, Jacobi eigen-solve, Chebyshev filter, residuals; replayed from hipGraphs), the solver driver run_pca
-// (deflation rounds, plans A / B, the transform) and srx_spmm (the raw operators, for kernel-level parity tests).
+// (deflation rounds, plans A / B, the transform), srx_spmm (the raw operators, for kernel-level parity tests) and the PCA model
+// of srx_pca_transform (pca_model.inl).
 #include "pca_internal.hpp"
 
 namespace srx {
@@ -1097,3 +1098,6 @@ int32_t srx_spmm(srx_mat* m, const uint64_t* sel, uint64_t k64, const double* pa
 }
 
 }  // extern "C"
+
+// Pca::transform: a fitted model applied to other cells (the forward product of the scores above, on a query)
+#include "pca_model.inl"

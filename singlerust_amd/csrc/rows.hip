@@ -392,19 +392,21 @@ int32_t launch_row_apply(srx_mat* m, double target, hipStream_t stream) {
 }
 
 // Row sums of the current values into m->d_row_sum (the first step of the pipeline: the per-gene passes apply the
-// normalise + log1p transform on the fly from them, the in-place write-back follows on the side stream).
-int32_t launch_row_sums(srx_mat* m) {
+// normalise + log1p transform on the fly from them, the in-place write-back follows on the side stream), or into `out`
+// (n_rows f64: srx_pca_transform, which leaves the query's own buffers alone).
+int32_t launch_row_sums(srx_mat* m, double* out) {
     srx_ctx* ctx = m->ctx;
     SRX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!m->d_row_sum) SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_row_sum, (m->n_rows ? m->n_rows : 1) * sizeof(double)));
+    if (!out && !m->d_row_sum) SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_row_sum, (m->n_rows ? m->n_rows : 1) * sizeof(double)));
+    double* const dst = out ? out : m->d_row_sum;
     const int g = row_grid(m);
     ProfScope ps(ctx, SRX_K_ROWSUM, (double)m->nnz * val_bytes(m) + (double)(m->n_rows + 1) * 8.0 + (double)m->n_rows * 8.0);
     if (is_f32(m))
         hipLaunchKernelGGL((k_row_sum<float>), dim3(g), dim3(256), 0, ctx->stream, m->d_indptr, (const float*)m->d_values,
-                           m->n_rows, m->d_row_sum);
+                           m->n_rows, dst);
     else
         hipLaunchKernelGGL((k_row_sum<double>), dim3(g), dim3(256), 0, ctx->stream, m->d_indptr, (const double*)m->d_values,
-                           m->n_rows, m->d_row_sum);
+                           m->n_rows, dst);
     SRX_HIP(ctx, hipGetLastError());
     return SRX_OK;
 }

@@ -394,6 +394,87 @@ inline srx_pca_info pca_inplace(IMAnnData& a, std::optional<std::size_t> n_compo
     a.obsm()["X_pca"] = std::move(scores);
     return info;
 }
+
+// Pca after fit (src/shared/processing/pca/mod.rs:74): an owning wrapper of an srx_pca_model whose transform (:156-185)
+// projects other cells into the fitted PC space on the device.
+class PcaModel {
+public:
+    static constexpr std::uint64_t kAbsent = UINT64_MAX;     // feature-map entry of a model gene the query does not have
+    // the model the last pca_inplace / pipeline on `a` left in HBM (a device-to-device copy: `a` may change afterwards)
+    static PcaModel from_result(const IMAnnData& a) {
+        PcaModel p(a.ctx());
+        a.ctx().check(srx_pca_model_from_result(a.x(), &p.h_));
+        return p;
+    }
+    // components k x n_pc row-major, mean / std k; sel (k feature ids, may be empty) for transform without a feature map
+    static PcaModel from_parts(Context& ctx, std::size_t k, std::size_t n_pc, const std::vector<double>& components,
+                               const std::vector<double>& mean, const std::vector<double>& std_,
+                               const std::vector<std::uint64_t>& sel, bool center = true, bool scale = true) {
+        if (components.size() != k * n_pc || (!mean.empty() && mean.size() != k) || (!std_.empty() && std_.size() != k) ||
+            (!sel.empty() && sel.size() != k))
+            throw Error(SRX_E_ARG, "PcaModel::from_parts: inconsistent sizes");
+        PcaModel p(ctx);
+        ctx.check(srx_pca_model_create(ctx.handle(), k, n_pc, components.data(), mean.empty() ? nullptr : mean.data(),
+                                       std_.empty() ? nullptr : std_.data(), sel.empty() ? nullptr : sel.data(), center, scale,
+                                       &p.h_));
+        return p;
+    }
+    PcaModel(PcaModel&& o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    PcaModel& operator=(PcaModel&& o) noexcept {
+        std::swap(ctx_, o.ctx_);
+        std::swap(h_, o.h_);
+        return *this;
+    }
+    PcaModel(const PcaModel&) = delete;
+    PcaModel& operator=(const PcaModel&) = delete;
+    ~PcaModel() { srx_pca_model_free(h_); }
+
+    std::size_t k() const { return shape().first; }
+    std::size_t n_pc() const { return shape().second; }
+    // Pca::transform of the cells of `a`: feat = the query column of each model row (kAbsent where missing; empty = the
+    // model's own feature ids); target_sum / log1p: normalize_total(Row) / ln_1p applied to the raw values on the fly
+    Array2 transform(const IMAnnData& a, const std::vector<std::uint64_t>& feat = {}, std::optional<double> target_sum = {},
+                     bool log1p = false) const {
+        if (!feat.empty() && feat.size() != k()) throw Error(SRX_E_ARG, "PcaModel::transform: the feature map needs k entries");
+        Array2 out;
+        out.nrows = a.n_obs();
+        out.ncols = n_pc();
+        out.data.resize(out.nrows * out.ncols);
+        const int bits = (target_sum ? SRX_BACKED_NORMALIZE : 0) | (log1p ? SRX_BACKED_LOG1P : 0);
+        ctx_->check(srx_pca_transform(h_, a.x(), feat.empty() ? nullptr : feat.data(), target_sum.value_or(0.0), bits,
+                                      out.data.empty() ? nullptr : out.data.data()));
+        return out;
+    }
+    // the feature map from the model's gene names to the query's (var_names of the two objects)
+    static std::vector<std::uint64_t> feature_map(const std::vector<std::string>& model_names,
+                                                  const std::vector<std::string>& query_names) {
+        std::map<std::string, std::uint64_t> where;
+        for (std::size_t j = 0; j < query_names.size(); ++j) where.emplace(query_names[j], j);
+        std::vector<std::uint64_t> f(model_names.size(), kAbsent);
+        for (std::size_t i = 0; i < model_names.size(); ++i) {
+            auto it = where.find(model_names[i]);
+            if (it != where.end()) f[i] = it->second;
+        }
+        return f;
+    }
+    srx_pca_model* handle() const { return h_; }
+
+private:
+    explicit PcaModel(Context& ctx) : ctx_(&ctx) {}
+    std::pair<std::size_t, std::size_t> shape() const {
+        std::uint64_t k = 0, n = 0;
+        ctx_->check(srx_pca_model_info(h_, &k, &n, nullptr));
+        return {k, n};
+    }
+    Context* ctx_;
+    srx_pca_model* h_ = nullptr;
+};
+
+// transform stored as obsm["X_pca"]
+inline void pca_transform_inplace(IMAnnData& a, const PcaModel& model, const std::vector<std::uint64_t>& feat = {},
+                                  std::optional<double> target_sum = {}, bool log1p = false) {
+    a.obsm()["X_pca"] = model.transform(a, feat, target_sum, log1p);
+}
 }  // namespace dim_red
 }  // namespace processing
 }  // namespace memory
