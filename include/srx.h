@@ -160,7 +160,10 @@ int32_t srx_matrix_upload(srx_ctx* ctx, const srx_csr* host, int32_t store, srx_
 int32_t srx_matrix_upload_csc(srx_ctx* ctx, const srx_csr* host, int32_t store, srx_mat** out);
 enum { SRX_FORMAT_CSR = 0, SRX_FORMAT_CSC = 1 };
 int32_t srx_matrix_format(const srx_mat* m, int32_t* format_out);
-/* Storage conversion on the device (a copy; the input is left as it is). */
+/* Storage conversion on the device (a copy; the input is left as it is).  The copy keeps the input's dtype and value
+ * storage, SRX_STORE_AUTO included: f32 storage of an AUTO matrix still widens to f64 at normalize_total.  The row-ordering
+ * pass holds a bitmap of the input's STORED rows in LDS: more than 655,360 of them (cells of a CSR input, genes of a CSC
+ * one) are refused with SRX_E_ARG. */
 int32_t srx_matrix_to_csr(srx_mat* m, srx_mat** out);
 int32_t srx_matrix_to_csc(srx_mat* m, srx_mat** out);
 /* Uninitialised device CSR for producers that fill HBM directly (synthetic generator, a
@@ -228,7 +231,8 @@ int32_t srx_gene_moments(srx_mat* m, uint64_t* cnt, double* sum, double* sumsq);
  * FlexValue (src/shared/mod.rs:62-66): Absolute(u32) thresholds the nnz COUNT of the cell / gene, Relative(p)
  * the linear-interpolated p-quantile of the SUMS (calculate_percentiles, mod.rs:148-174), None = no limit; the
  * nine (lower, upper) combinations of create_filter_mask (mod.rs:33-84).  `*out` receives a NEW matrix holding
- * the kept rows / columns in their original order (the reference's `subset`; the in-place forms swap it in);
+ * the kept rows / columns in their original order (the reference's `subset`; the in-place forms swap it in), in the
+ * input's format, dtype and value storage (SRX_STORE_AUTO included, as srx_subset);
  * `mask_out` (n_rows resp. n_cols bytes, may be NULL) receives the boolean mask. */
 enum { SRX_FLEX_NONE = 0, SRX_FLEX_ABSOLUTE = 1, SRX_FLEX_RELATIVE = 2 };
 typedef struct srx_flex {
@@ -238,7 +242,9 @@ typedef struct srx_flex {
 } srx_flex;
 int32_t srx_filter_cells(srx_mat* m, srx_flex lower, srx_flex upper, srx_mat** out, uint8_t* mask_out);
 int32_t srx_filter_genes(srx_mat* m, srx_flex lower, srx_flex upper, srx_mat** out, uint8_t* mask_out);
-/* anndata `subset` on X: boolean masks over rows / columns (NULL = keep all), order preserved. */
+/* anndata `subset` on X: boolean masks over rows / columns (NULL = keep all), order preserved.  The result keeps the
+ * input's format, dtype and value storage; a matrix created with SRX_STORE_AUTO stays AUTO (its f32 storage widens to
+ * f64 at normalize_total, like the reference's DynCsrMatrix::F64), as srx_matrix_clone. */
 int32_t srx_subset(srx_mat* m, const uint8_t* row_mask, const uint8_t* col_mask, srx_mat** out);
 /* Sparsity pattern back to the host in the reference's layout (u64 offsets / indices); either may be NULL. */
 int32_t srx_matrix_download_pattern(srx_mat* m, uint64_t* indptr_out, uint64_t* indices_out);

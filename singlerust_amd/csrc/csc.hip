@@ -114,10 +114,12 @@ int32_t transpose_device(srx_mat* m, srx_mat** out) {
     if (R >= (1ull << 31)) return fail(ctx, SRX_E_BOUNDS, "transpose: %llu rows exceed int32 device indices", (unsigned long long)R);
     const int words = (int)((R + 31) / 32);              // columns of the OUTPUT = rows of the stored matrix
     const size_t lds_per_wave = 2 * (size_t)words * sizeof(uint32_t);
+    // a one-wave workgroup with all 160 KiB of dynamic LDS (R = 655,360) launches on gfx950 (tests/test_subset_gpu.py)
     if (lds_per_wave > 160 * 1024)
         return fail(ctx, SRX_E_ARG, "transpose: %llu columns exceed the LDS bitmap of the row-ordering pass", (unsigned long long)R);
     srx_mat* t = nullptr;
     SRX_TRY(srx_matrix_alloc(ctx, Cn, R, nnz, m->dtype, m->store, &t));
+    t->store_auto = m->store_auto;               // as srx_matrix_clone: f32 storage still widens at normalize_total
     auto bail = [&](int32_t rc) { srx_matrix_free(t); return rc; };
     int64_t* d_cnt;
     unsigned long long* d_cur;
@@ -145,16 +147,17 @@ int32_t transpose_device(srx_mat* m, srx_mat** out) {
     uint64_t go = (Cn + waves - 1) / waves;
     go = std::min<uint64_t>(std::max<uint64_t>(go, 1), (uint64_t)ctx->n_cus * 16);
     const size_t lds = lds_per_wave * waves;
+    const void* order_fn = is_f32(m) ? (const void*)k_row_order<float> : (const void*)k_row_order<double>;
+    e = hipFuncSetAttribute(order_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return bail(fail(ctx, SRX_E_HIP, "transpose: %zu bytes of LDS: %s", lds, hipGetErrorString(e)));
     if (is_f32(m)) {
         hipLaunchKernelGGL((k_scatter<float>), dim3((unsigned)gr), dim3(256), 0, ctx->stream, m->d_indptr, m->d_indices,
                            (const float*)m->d_values, R, t->d_indptr, d_cur, tmp_idx, (float*)tmp_val);
-        (void)hipFuncSetAttribute((const void*)k_row_order<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((k_row_order<float>), dim3((unsigned)go), dim3(waves * kWave), lds, ctx->stream, t->d_indptr, tmp_idx,
                            (const float*)tmp_val, Cn, words, t->d_indices, (float*)t->d_values, d_flag);
     } else {
         hipLaunchKernelGGL((k_scatter<double>), dim3((unsigned)gr), dim3(256), 0, ctx->stream, m->d_indptr, m->d_indices,
                            (const double*)m->d_values, R, t->d_indptr, d_cur, tmp_idx, (double*)tmp_val);
-        (void)hipFuncSetAttribute((const void*)k_row_order<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((k_row_order<double>), dim3((unsigned)go), dim3(waves * kWave), lds, ctx->stream, t->d_indptr, tmp_idx,
                            (const double*)tmp_val, Cn, words, t->d_indices, (double*)t->d_values, d_flag);
     }

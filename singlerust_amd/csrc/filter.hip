@@ -121,6 +121,7 @@ static int32_t subset_device(srx_mat* m, const uint8_t* row_mask, const uint8_t*
     srx_mat* c = nullptr;
     SRX_TRY(srx_matrix_alloc(ctx, n_keep_rows, n_keep_cols, (uint64_t)total, m->dtype, m->store, &c));
     c->row_offset = m->row_offset;
+    c->store_auto = m->store_auto;               // as srx_matrix_clone: f32 storage still widens at normalize_total
     if (m->store == SRX_STORE_F32)
         hipLaunchKernelGGL((k_subset_fill<float>), dim3((unsigned)gw), dim3(256), 0, ctx->stream, m->d_indptr, m->d_indices,
                            (const float*)m->d_values, d_rowmask, d_colmap, N, d_off, d_newid, c->d_indptr, c->d_indices,

@@ -172,8 +172,18 @@ def test_csc_pipeline_and_pca_match_oracle(ctx):
     assert e.value.code == _ffi.E_NAN
 
 
+def _same_csc(a, want):
+    """`a` (an IMAnnData over a CSC matrix) holds exactly the scipy CSC matrix `want`: a gather, bit-exact."""
+    want = want.tocsc()
+    want.sort_indices()
+    assert a.x().is_csc() and (a.n_obs(), a.n_vars()) == want.shape and a.x().info().nnz == want.nnz
+    assert np.array_equal(a.indptr, want.indptr) and np.array_equal(a.indices, want.indices)
+    assert np.array_equal(a.x_values(np.float64), want.data.astype(np.float64))
+
+
 def test_csc_filters(ctx):
-    """filter_cells / filter_genes on a CSC matrix == the same filters on the CSR matrix of the same X."""
+    """filter_cells / filter_genes on a CSC matrix == the same filters on the CSR matrix of the same X, and the CSC arrays
+    of the result == scipy's of the kept cells / genes."""
     import scipy.sparse as sp
     import singlerust_amd as sr
     from singlerust_amd.memory import processing
@@ -185,9 +195,13 @@ def test_csc_filters(ctx):
         f1, f2 = processing.filter_cells(a_csc, lo, hi), processing.filter_cells(a_csr, lo, hi)
         assert f1.x().is_csc() and (f1.n_obs(), f1.n_vars()) == (f2.n_obs(), f2.n_vars()) and f1.obs_names == f2.obs_names
         assert f1.n_obs() < 800
+        assert np.array_equal(f1.uns["filter_mask"], f2.uns["filter_mask"])
+        _same_csc(f1, x.tocsr()[f2.uns["filter_mask"]])
     for lo, hi in ((sr.FlexValue.Absolute(80), sr.FlexValue.Absolute(100)), (sr.FlexValue.Relative(0.1), sr.FlexValue.NoLimit())):
         g1, g2 = processing.filter_genes(a_csc, lo, hi), processing.filter_genes(a_csr, lo, hi)
         assert (g1.n_obs(), g1.n_vars()) == (g2.n_obs(), g2.n_vars()) and g1.var_names == g2.var_names
         assert g1.n_vars() < 100
+        assert np.array_equal(g1.uns["filter_mask"], g2.uns["filter_mask"])
+        _same_csc(g1, x[:, g2.uns["filter_mask"]])
         back = g1.x().to_csr()
-        assert np.array_equal(np.sort(back.values(np.float64)), np.sort(g2.x_values(np.float64)))
+        assert np.array_equal(back.values(np.float64), g2.x_values(np.float64))          # same order: CSR of the same X
