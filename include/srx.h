@@ -34,7 +34,8 @@ extern "C" {
 #define SRX_ABI_VERSION 6      /* 2: srx_matrix_reserve_results, kernel classes 7-9, srx_synth_params.skew; 3: kernel class 10;
                                   4: srx_comm_info, srx_prof_get_aux; 5: srx_comm_overlap_info; 6: srx_gram_mode_info, srx_gram_exchange_ranges.
                                   Purely additive entry points leave the version as it is and are detected by symbol:
-                                  srx_pca_model_* / srx_pca_transform (fitted-PCA projection) came that way at 6 */
+                                  srx_pca_model_* / srx_pca_transform (fitted-PCA projection) and srx_knn_result /
+                                  srx_knn_points (kernel class 11) came that way at 6 */
 
 typedef struct srx_ctx srx_ctx;   /* one GPU + stream + (optional) RCCL communicator      */
 typedef struct srx_mat srx_mat;   /* device-resident CSR (the `X` of an IMAnnData)        */
@@ -369,6 +370,44 @@ void    srx_pca_model_free(srx_pca_model* p);
 int32_t srx_pca_transform(srx_pca_model* p, srx_mat* q, const uint64_t* feat, double target_sum, int32_t transform,
                           double* scores_out);
 
+/* Exact k-nearest-neighbour search (Euclidean) on the device: the step that consumes obsm["X_pca"].  Not in the
+ * reference; it stands in front of what its commented-out tsne / tsne_inplace (dim_red/mod.rs:159-227) would
+ * build from the scores.  The distance of a pair is sqrt(sum_j (q_j - r_j)^2) summed in f64 in this difference
+ * form; the result is the exact k nearest under it, every row ascending by (distance, reference index) — ties go
+ * to the lower index, at the k-th place too — and bit-identical from call to call.  An f32 matrix-core pass keeps
+ * n_candidates = k + 8 candidates per row, f64 re-ranks them and proves the row exact or sends it through a full
+ * f64 pass (srx_knn_info counts both).  SRX_E_ARG: k outside 1..64 or above the number of admissible references
+ * (n_ref - 1 for a self graph without self), n_dims above the coordinates there are, more than SRX_KNN_MAX_DIMS
+ * coordinates in use, NaN / Inf in the points, a context with more than one rank (rows are sharded; neighbours
+ * need all cells).  Outputs are n_query x k row-major; either may be NULL, info too.  n_query == 0 writes nothing. */
+#define SRX_KNN_MAX_DIMS 128
+typedef struct srx_knn_opts {
+    int32_t k;             /* neighbours per query row, 1..64                                        */
+    int32_t n_dims;        /* use the first n_dims coordinates (leading PCs); 0 = all                */
+    int32_t include_self;  /* self graph only: 0 = a row is never its own neighbour (default), 1 = it
+                              may be (it then comes first at distance 0 unless an exact duplicate with
+                              a lower index ties with it)                                            */
+    int32_t reserved_;
+} srx_knn_opts;
+typedef struct srx_knn_info {
+    uint64_t n_ref, n_query;
+    uint32_t d, k;
+    uint32_t n_candidates;     /* candidates per row kept by the f32 pass                            */
+    uint32_t reserved_;
+    uint64_t rows_certified;   /* rows whose result was proven exact from the f32 pass + f64 re-rank */
+    uint64_t rows_recomputed;  /* rows that went through the full f64 pass; the two sum to n_query   */
+} srx_knn_info;
+/* Self graph of the cells of m in the space of the scores its last srx_pca / srx_pipeline left in HBM (no host
+ * round trip; the result stays as it is).  SRX_E_ARG when m holds no result. */
+int32_t srx_knn_result(srx_mat* m, const srx_knn_opts* opts, uint32_t* indices_out, double* distances_out,
+                       srx_knn_info* info);
+/* The same search on caller-supplied points (row-major f64, n x d): neighbours of every query row among the
+ * reference rows.  query == NULL: the self graph of ref (n_query is ignored).  This is how projected cells
+ * (srx_pca_transform output) find their neighbours in the fitted data set. */
+int32_t srx_knn_points(srx_ctx* ctx, const double* ref, uint64_t n_ref, const double* query, uint64_t n_query,
+                       uint64_t d, const srx_knn_opts* opts, uint32_t* indices_out, double* distances_out,
+                       srx_knn_info* info);
+
 /* The raw operators the PCA is built from, for a caller-supplied 64-column panel (k x 64
  * row-major): y_out (n_rows x 64) = X[:, sel] * panel, t_out (k x 64) = X[:, sel]^T * y, and
  * gram_out (k x k) = X[:, sel]^T X[:, sel] (panel not needed).  `sel` must be strictly
@@ -449,7 +488,8 @@ typedef enum srx_kernel_class {
     SRX_K_SELECT = 9,      /* device-side HighlyVariable(n): variances, ranks, selection    */
     SRX_K_BUCKET = 10,     /* the Gram kernel's owner records: counts, their read-back, bucket pass;
                               SRX_K_GRAM is the stripe kernel alone                         */
-    SRX_K_COUNT_ = 11
+    SRX_K_KNN = 11,        /* srx_knn_*: centre, f32 copy, candidate pass, f64 re-rank and recompute  */
+    SRX_K_COUNT_ = 12
 } srx_kernel_class;
 int32_t srx_prof_enable(srx_ctx* ctx, uint32_t class_mask);
 int32_t srx_prof_reset(srx_ctx* ctx);

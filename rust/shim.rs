@@ -751,6 +751,44 @@ pub mod processing_free {
             }
             Ok(())
         }
+
+        /// Exact k-nearest-neighbour graph of the cells in the space of the scores the last PCA left on the device
+        /// (srx_knn_result; not in the reference — it stands in front of what the commented-out tsne / tsne_inplace,
+        /// dim_red/mod.rs:159-227, would build from obsm["X_pca"]).  Returns (indices n_obs x k, Euclidean distances), every
+        /// row ascending by (distance, index); `n_pcs` = 0 uses every component.
+        pub fn neighbors(adata: &IMAnnData, n_neighbors: usize, n_pcs: usize, include_self: bool)
+                         -> anyhow::Result<(Array2<u32>, Array2<f64>)> {
+            let (n, k) = (adata.n_obs(), n_neighbors);
+            let opts = SrxKnnOpts { k: k as i32, n_dims: n_pcs as i32, include_self: include_self as i32, reserved: 0 };
+            let mut idx = vec![0u32; n * k];
+            let mut dist = vec![0.0f64; n * k];
+            let mut info: SrxKnnInfo = unsafe { std::mem::zeroed() };
+            with_resident(adata, |x| x.ctx.check(unsafe {
+                srx_knn_result(x.mat, &opts, if idx.is_empty() { null_mut() } else { idx.as_mut_ptr() },
+                               if dist.is_empty() { null_mut() } else { dist.as_mut_ptr() }, &mut info)
+            }))?;
+            Ok((Array2::from_shape_vec((n, k), idx)?, Array2::from_shape_vec((n, k), dist)?))
+        }
+        /// Neighbours of projected cells (PcaModel::transform output) among the fitted cells' scores: srx_knn_points.
+        pub fn neighbors_of(reference: &Array2<f64>, query: &Array2<f64>, n_neighbors: usize)
+                            -> anyhow::Result<(Array2<u32>, Array2<f64>)> {
+            let ((n_ref, d), (n_q, dq)) = (reference.dim(), query.dim());
+            if d != dq {
+                bail!("neighbors_of: reference has {d} coordinates, query {dq}");
+            }
+            let r: Vec<f64> = reference.iter().copied().collect();                 // row-major
+            let q: Vec<f64> = query.iter().copied().collect();
+            let opts = SrxKnnOpts { k: n_neighbors as i32, n_dims: 0, include_self: 0, reserved: 0 };
+            let mut idx = vec![0u32; n_q * n_neighbors];
+            let mut dist = vec![0.0f64; n_q * n_neighbors];
+            if n_q > 0 {
+                with_ctx(|c| c.check(unsafe {
+                    srx_knn_points(c.0, r.as_ptr(), n_ref as u64, q.as_ptr(), n_q as u64, d as u64, &opts, idx.as_mut_ptr(),
+                                   dist.as_mut_ptr(), null_mut())
+                }))?;
+            }
+            Ok((Array2::from_shape_vec((n_q, n_neighbors), idx)?, Array2::from_shape_vec((n_q, n_neighbors), dist)?))
+        }
     }
 }
 

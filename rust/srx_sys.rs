@@ -7,6 +7,7 @@ use std::os::raw::{c_char, c_void};
 
 pub const SRX_ABI_VERSION: i32 = 6;
 pub const SRX_UNIQUE_ID_BYTES: usize = 128;
+pub const SRX_KNN_MAX_DIMS: i32 = 128;
 pub const SRX_OK: i32 = 0;
 pub const SRX_E_ARG: i32 = -1;
 pub const SRX_E_DTYPE: i32 = -2;
@@ -52,7 +53,8 @@ pub const SRX_K_ROWSUM: i32 = 7;
 pub const SRX_K_ITERATE: i32 = 8;
 pub const SRX_K_SELECT: i32 = 9;
 pub const SRX_K_BUCKET: i32 = 10;
-pub const SRX_K_COUNT_: i32 = 11;
+pub const SRX_K_KNN: i32 = 11;
+pub const SRX_K_COUNT_: i32 = 12;
 
 #[repr(C)] pub struct SrxCtx { _private: [u8; 0] }      // opaque `srx_ctx`
 #[repr(C)] pub struct SrxMat { _private: [u8; 0] }      // opaque `srx_mat`
@@ -117,6 +119,28 @@ pub struct SrxPcaInfo {      // `srx_pca_info`
     pub nnz_selected: u64,
     pub solver: u32,
     pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxKnnOpts {      // `srx_knn_opts`
+    pub k: i32,
+    pub n_dims: i32,
+    pub include_self: i32,
+    pub reserved: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxKnnInfo {      // `srx_knn_info`
+    pub n_ref: u64,
+    pub n_query: u64,
+    pub d: u32,
+    pub k: u32,
+    pub n_candidates: u32,
+    pub reserved: u32,
+    pub rows_certified: u64,
+    pub rows_recomputed: u64,
 }
 
 #[repr(C)]
@@ -197,6 +221,11 @@ extern "C" {
     pub fn srx_pca_model_free(p: *mut SrxPcaModel);
     pub fn srx_pca_transform(p: *mut SrxPcaModel, q: *mut SrxMat, feat: *const u64, target_sum: f64,
                              transform: i32, scores_out: *mut f64) -> i32;
+    pub fn srx_knn_result(m: *mut SrxMat, opts: *const SrxKnnOpts, indices_out: *mut u32, distances_out: *mut f64,
+                          info: *mut SrxKnnInfo) -> i32;
+    pub fn srx_knn_points(ctx: *mut SrxCtx, ref_: *const f64, n_ref: u64, query: *const f64, n_query: u64, d: u64,
+                          opts: *const SrxKnnOpts, indices_out: *mut u32, distances_out: *mut f64,
+                          info: *mut SrxKnnInfo) -> i32;
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,

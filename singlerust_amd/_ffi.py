@@ -23,6 +23,8 @@ I8, I16, I32, U8, U16, U32, F32, F64 = range(8)
 ROW, COLUMN = 0, 1
 STORE_AUTO, STORE_F32, STORE_F64 = 0, 1, 2
 K_NORMALIZE, K_MOMENTS, K_COMPACT, K_SPMM_FWD, K_SPMM_T, K_GRAM, K_DENSE, K_ROWSUM, K_ITERATE, K_SELECT, K_BUCKET = range(11)
+K_KNN = 11
+KNN_MAX_DIMS = 128
 SOLVER_AUTO, SOLVER_GRAM, SOLVER_SPMM = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 
@@ -61,6 +63,16 @@ class PcaInfo(C.Structure):
 class PipelineResult(C.Structure):
     _fields_ = [("pca", PcaInfo), ("ms_normalize", C.c_double), ("ms_moments", C.c_double),
                 ("ms_select", C.c_double), ("ms_compact", C.c_double), ("ms_pca", C.c_double)]
+
+
+class KnnOpts(C.Structure):
+    _fields_ = [("k", C.c_int32), ("n_dims", C.c_int32), ("include_self", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class KnnInfo(C.Structure):
+    _fields_ = [("n_ref", C.c_uint64), ("n_query", C.c_uint64), ("d", C.c_uint32), ("k", C.c_uint32),
+                ("n_candidates", C.c_uint32), ("reserved_", C.c_uint32), ("rows_certified", C.c_uint64),
+                ("rows_recomputed", C.c_uint64)]
 
 
 class SynthParams(C.Structure):
@@ -132,6 +144,8 @@ _SIGS = {
     "srx_pca_model_info": (C.c_int32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), P]),
     "srx_pca_model_free": (None, [P]),
     "srx_pca_transform": (C.c_int32, [P, P, P, C.c_double, C.c_int32, P]),
+    "srx_knn_result": (C.c_int32, [P, C.POINTER(KnnOpts), P, P, C.POINTER(KnnInfo)]),
+    "srx_knn_points": (C.c_int32, [P, P, C.c_uint64, P, C.c_uint64, C.c_uint64, C.POINTER(KnnOpts), P, P, C.POINTER(KnnInfo)]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),

@@ -476,6 +476,43 @@ inline void pca_transform_inplace(IMAnnData& a, const PcaModel& model, const std
     a.obsm()["X_pca"] = model.transform(a, feat, target_sum, log1p);
 }
 }  // namespace dim_red
+
+// Exact k-nearest-neighbour graph (Euclidean, f64; rows ascending by (distance, index)).  Not in the reference: the step
+// that consumes obsm["X_pca"], in front of what its commented-out tsne (dim_red/mod.rs:159-227) would build.
+struct KnnGraph {
+    std::size_t n_query = 0, k = 0;
+    std::vector<std::uint32_t> indices;      // n_query x k row-major
+    std::vector<double> distances;
+    srx_knn_info info{};
+};
+// self graph of the cells of `a` over the scores its last PCA left on the device (srx_knn_result)
+inline KnnGraph neighbors(const IMAnnData& a, int n_neighbors = 15, int n_pcs = 0, bool include_self = false) {
+    KnnGraph g;
+    g.n_query = a.n_obs();
+    g.k = n_neighbors > 0 ? static_cast<std::size_t>(n_neighbors) : 0;
+    g.indices.resize(g.n_query * g.k);
+    g.distances.resize(g.n_query * g.k);
+    const srx_knn_opts o{n_neighbors, n_pcs, include_self ? 1 : 0, 0};
+    a.ctx().check(srx_knn_result(a.x(), &o, g.indices.empty() ? nullptr : g.indices.data(),
+                                 g.distances.empty() ? nullptr : g.distances.data(), &g.info));
+    return g;
+}
+// neighbours of every query row among the reference rows (row-major n x d); an empty query: the self graph of ref
+inline KnnGraph knn_points(Context& ctx, const std::vector<double>& ref, const std::vector<double>& query, std::size_t d,
+                           int k = 15, bool include_self = false) {
+    if (d == 0 || ref.size() % d || query.size() % d) throw Error(SRX_E_ARG, "knn_points: sizes are not multiples of d");
+    KnnGraph g;
+    const std::size_t n_ref = ref.size() / d;
+    g.n_query = query.empty() ? n_ref : query.size() / d;
+    g.k = k > 0 ? static_cast<std::size_t>(k) : 0;
+    g.indices.resize(g.n_query * g.k);
+    g.distances.resize(g.n_query * g.k);
+    const srx_knn_opts o{k, 0, include_self ? 1 : 0, 0};
+    ctx.check(srx_knn_points(ctx.handle(), ref.data(), n_ref, query.empty() ? nullptr : query.data(), g.n_query, d, &o,
+                             g.indices.empty() ? nullptr : g.indices.data(),
+                             g.distances.empty() ? nullptr : g.distances.data(), &g.info));
+    return g;
+}
 }  // namespace processing
 }  // namespace memory
 
