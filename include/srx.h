@@ -35,7 +35,8 @@ extern "C" {
                                   4: srx_comm_info, srx_prof_get_aux; 5: srx_comm_overlap_info; 6: srx_gram_mode_info, srx_gram_exchange_ranges.
                                   Purely additive entry points leave the version as it is and are detected by symbol:
                                   srx_pca_model_* / srx_pca_transform (fitted-PCA projection) and srx_knn_result /
-                                  srx_knn_points (kernel class 11) came that way at 6 */
+                                  srx_knn_points (kernel class 11) came that way at 6, as did srx_neighbors_* / srx_graph_*
+                                  (kernel class 12) */
 
 typedef struct srx_ctx srx_ctx;   /* one GPU + stream + (optional) RCCL communicator      */
 typedef struct srx_mat srx_mat;   /* device-resident CSR (the `X` of an IMAnnData)        */
@@ -408,6 +409,55 @@ int32_t srx_knn_points(srx_ctx* ctx, const double* ref, uint64_t n_ref, const do
                        uint64_t d, const srx_knn_opts* opts, uint32_t* indices_out, double* distances_out,
                        srx_knn_info* info);
 
+/* ---- the weighted neighbour graph: obsp["distances"] and obsp["connectivities"] -------------------------------
+ * What clustering, UMAP, diffusion maps and PAGA read.  Not in the reference; it is scanpy's pp.neighbors graph, i.e.
+ * umap-learn's fuzzy_simplicial_set with local_connectivity = 1 and set_op_mix_ratio = 1, restated for k-NN rows that
+ * do NOT carry the cell itself (scanpy's n_neighbors counts the cell: n_neighbors = k + 1 there, hence log2(k + 1) and
+ * the k + 1 of the floor below).  The formulas here are what is tested; the output has NOT been compared with
+ * umap-learn or scanpy.
+ *
+ * Input: for every row i, k distinct neighbours j != i with finite Euclidean distances d_ij >= 0; 1 <= k <= 64.
+ * T = log2(k + 1).  Per row:
+ *   rho_i    = the smallest strictly positive distance of the row; a row without one (k exact duplicates) has
+ *              rho_i = sigma_i = 0 and every weight 1 (rows_all_zero; such a row also counts in rows_no_root).
+ *   c_i      = neighbours with d_ij <= rho_i;  S_i(s) = c_i + sum over {d_ij > rho_i} exp(-(d_ij - rho_i) / s).
+ *   sigma*_i = the root of S_i(s) = T when c_i < T, solved to |S_i - T| <= 1e-9 (umap-learn stops at 1e-5), else 0
+ *              (rows_no_root: enough neighbours tie at the minimum).
+ *   sigma_i  = max(sigma*_i, 1e-3 * (sum_j d_ij) / (k + 1))      (rows_clamped: the floor is the larger).
+ *   a_ij     = 1 when d_ij <= rho_i, else exp(-(d_ij - rho_i) / sigma_i), in f64.
+ * Connectivities C = A + A^T - A o A^T: for every pair joined in either direction C[i,j] = fma(-a, b, a + b) with
+ * a = a_ij, b = a_ji (0 when absent).  Entries that are exactly 0.0 are not stored (entries_dropped).  Distances D:
+ * D[i,j] = d_ij on the k-NN edges, all n k entries stored.  Both are CSR with u64 indptr (n + 1), u32 indices
+ * ascending within a row and f64 data.  C is exactly symmetric (C[i,j] and C[j,i] are the same bits), has no
+ * diagonal, 0 < C[i,j] <= 1, and the whole result is bit-identical from call to call and independent of the order of
+ * the entries within an input row.
+ *
+ * The handle owns its device buffers (a later k-NN or graph call does not touch them); free it before its context. */
+typedef struct srx_graph srx_graph;
+typedef struct srx_graph_info {
+    uint64_t n;
+    uint32_t k, reserved_;
+    uint64_t nnz_distances, nnz_connectivities;
+    uint64_t n_mutual;         /* unordered pairs present in both directions of the k-NN list            */
+    uint64_t rows_no_root, rows_clamped, rows_all_zero;
+    uint64_t entries_dropped;  /* exact zeros of A + A^T - A o A^T that are not stored                   */
+    uint64_t max_row_nnz;      /* longest row of the connectivities                                      */
+} srx_graph_info;
+/* srx_knn_result (opts as there, include_self must be 0: else SRX_E_ARG) on the scores the last fit left in HBM, then
+ * the graph of that list; indices and distances never leave the device.  knn_info may be NULL. */
+int32_t srx_neighbors_result(srx_mat* m, const srx_knn_opts* opts, srx_knn_info* knn_info, srx_graph** out);
+/* The graph of a caller-supplied k-NN list (n x k row-major, e.g. what srx_knn_points returned).  SRX_E_ARG: k outside
+ * 1..64, k > n - 1, an index >= n, a row naming itself or one neighbour twice, a negative / NaN / Inf distance, a
+ * context with more than one rank.  Rows need not be sorted.  n == 0 gives an empty graph. */
+int32_t srx_neighbors_from_knn(srx_ctx* ctx, const uint32_t* indices, const double* distances, uint64_t n, uint32_t k,
+                               srx_graph** out);
+int32_t srx_graph_info_get(const srx_graph* g, srx_graph_info* info);
+enum { SRX_GRAPH_DISTANCES = 0, SRX_GRAPH_CONNECTIVITIES = 1 };
+/* Copy one of the two matrices to the host; any pointer may be NULL, sizes from srx_graph_info. */
+int32_t srx_graph_fetch(srx_graph* g, int32_t which, uint64_t* indptr, uint32_t* indices, double* data);
+int32_t srx_graph_fetch_scales(srx_graph* g, double* rho, double* sigma);   /* n each */
+void    srx_graph_free(srx_graph* g);
+
 /* The raw operators the PCA is built from, for a caller-supplied 64-column panel (k x 64
  * row-major): y_out (n_rows x 64) = X[:, sel] * panel, t_out (k x 64) = X[:, sel]^T * y, and
  * gram_out (k x k) = X[:, sel]^T X[:, sel] (panel not needed).  `sel` must be strictly
@@ -489,7 +539,8 @@ typedef enum srx_kernel_class {
     SRX_K_BUCKET = 10,     /* the Gram kernel's owner records: counts, their read-back, bucket pass;
                               SRX_K_GRAM is the stripe kernel alone                         */
     SRX_K_KNN = 11,        /* srx_knn_*: centre, f32 copy, candidate pass, f64 re-rank and recompute  */
-    SRX_K_COUNT_ = 12
+    SRX_K_GRAPH = 12,      /* srx_neighbors_*: scales and weights, reverse lookup, in-only lists, merge           */
+    SRX_K_COUNT_ = 13
 } srx_kernel_class;
 int32_t srx_prof_enable(srx_ctx* ctx, uint32_t class_mask);
 int32_t srx_prof_reset(srx_ctx* ctx);

@@ -789,6 +789,54 @@ pub mod processing_free {
             }
             Ok((Array2::from_shape_vec((n_q, n_neighbors), idx)?, Array2::from_shape_vec((n_q, n_neighbors), dist)?))
         }
+
+        /// The weighted neighbour graph of the cells (srx_neighbors_result): exact k-NN over the resident scores, then
+        /// scanpy's `pp.neighbors` weights (umap-learn's fuzzy_simplicial_set restated for rows without self; not compared
+        /// with either package) — all on the device.  Returns (distances, connectivities), both n_obs x n_obs CSR.
+        pub fn neighbors_graph(adata: &IMAnnData, n_neighbors: usize, n_pcs: usize)
+                               -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>)> {
+            let opts = SrxKnnOpts { k: n_neighbors as i32, n_dims: n_pcs as i32, include_self: 0, reserved: 0 };
+            with_resident(adata, |x| {
+                let mut g: *mut SrxGraph = null_mut();
+                x.ctx.check(unsafe { srx_neighbors_result(x.mat, &opts, null_mut(), &mut g) })?;
+                let out = graph_to_host(x.ctx, g);
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        /// The same graph from a k-NN list the caller holds (what `neighbors` / `neighbors_of` return): srx_neighbors_from_knn.
+        pub fn connectivities_from_knn(indices: &Array2<u32>, distances: &Array2<f64>)
+                                       -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>)> {
+            let ((n, k), dd) = (indices.dim(), distances.dim());
+            if dd != (n, k) {
+                bail!("connectivities_from_knn: indices are {n} x {k}, distances {} x {}", dd.0, dd.1);
+            }
+            let i: Vec<u32> = indices.iter().copied().collect();                   // row-major
+            let d: Vec<f64> = distances.iter().copied().collect();
+            with_ctx(|c| {
+                let mut g: *mut SrxGraph = null_mut();
+                c.check(unsafe { srx_neighbors_from_knn(c.0, i.as_ptr(), d.as_ptr(), n as u64, k as u32, &mut g) })?;
+                let out = graph_to_host(c, g);
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        fn graph_to_host(c: &Ctx, g: *mut SrxGraph) -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>)> {
+            let mut info: SrxGraphInfo = unsafe { std::mem::zeroed() };
+            c.check(unsafe { srx_graph_info_get(g, &mut info) })?;
+            let n = info.n as usize;
+            let mut fetch = |which: i32, nnz: usize| -> anyhow::Result<CsrMatrix<f64>> {
+                let mut indptr = vec![0u64; n + 1];
+                let mut indices = vec![0u32; nnz];
+                let mut data = vec![0.0f64; nnz];
+                c.check(unsafe { srx_graph_fetch(g, which, indptr.as_mut_ptr(), indices.as_mut_ptr(), data.as_mut_ptr()) })?;
+                CsrMatrix::try_from_csr_data(n, n, indptr.into_iter().map(|v| v as usize).collect(),
+                                             indices.into_iter().map(|v| v as usize).collect(), data)
+                    .map_err(|e| anyhow!("graph: {e}"))
+            };
+            Ok((fetch(SRX_GRAPH_DISTANCES, info.nnz_distances as usize)?,
+                fetch(SRX_GRAPH_CONNECTIVITIES, info.nnz_connectivities as usize)?))
+        }
     }
 }
 

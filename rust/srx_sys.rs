@@ -40,6 +40,8 @@ pub const SRX_FLEX_RELATIVE: i32 = 2;
 pub const SRX_SOLVER_AUTO: i32 = 0;
 pub const SRX_SOLVER_GRAM: i32 = 1;
 pub const SRX_SOLVER_SPMM: i32 = 2;
+pub const SRX_GRAPH_DISTANCES: i32 = 0;
+pub const SRX_GRAPH_CONNECTIVITIES: i32 = 1;
 pub const SRX_BACKED_NORMALIZE: i32 = 1;
 pub const SRX_BACKED_LOG1P: i32 = 2;
 pub const SRX_K_NORMALIZE: i32 = 0;
@@ -54,11 +56,13 @@ pub const SRX_K_ITERATE: i32 = 8;
 pub const SRX_K_SELECT: i32 = 9;
 pub const SRX_K_BUCKET: i32 = 10;
 pub const SRX_K_KNN: i32 = 11;
-pub const SRX_K_COUNT_: i32 = 12;
+pub const SRX_K_GRAPH: i32 = 12;
+pub const SRX_K_COUNT_: i32 = 13;
 
 #[repr(C)] pub struct SrxCtx { _private: [u8; 0] }      // opaque `srx_ctx`
 #[repr(C)] pub struct SrxMat { _private: [u8; 0] }      // opaque `srx_mat`
 #[repr(C)] pub struct SrxPcaModel { _private: [u8; 0] }      // opaque `srx_pca_model`
+#[repr(C)] pub struct SrxGraph { _private: [u8; 0] }      // opaque `srx_graph`
 #[repr(C)] pub struct SrxBacked { _private: [u8; 0] }      // opaque `srx_backed`
 
 #[repr(C)]
@@ -145,6 +149,22 @@ pub struct SrxKnnInfo {      // `srx_knn_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxGraphInfo {      // `srx_graph_info`
+    pub n: u64,
+    pub k: u32,
+    pub reserved: u32,
+    pub nnz_distances: u64,
+    pub nnz_connectivities: u64,
+    pub n_mutual: u64,
+    pub rows_no_root: u64,
+    pub rows_clamped: u64,
+    pub rows_all_zero: u64,
+    pub entries_dropped: u64,
+    pub max_row_nnz: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPipelineResult {      // `srx_pipeline_result`
     pub pca: SrxPcaInfo,
     pub ms_normalize: f64,
@@ -226,6 +246,14 @@ extern "C" {
     pub fn srx_knn_points(ctx: *mut SrxCtx, ref_: *const f64, n_ref: u64, query: *const f64, n_query: u64, d: u64,
                           opts: *const SrxKnnOpts, indices_out: *mut u32, distances_out: *mut f64,
                           info: *mut SrxKnnInfo) -> i32;
+    pub fn srx_neighbors_result(m: *mut SrxMat, opts: *const SrxKnnOpts, knn_info: *mut SrxKnnInfo,
+                                out: *mut *mut SrxGraph) -> i32;
+    pub fn srx_neighbors_from_knn(ctx: *mut SrxCtx, indices: *const u32, distances: *const f64, n: u64, k: u32,
+                                  out: *mut *mut SrxGraph) -> i32;
+    pub fn srx_graph_info_get(g: *const SrxGraph, info: *mut SrxGraphInfo) -> i32;
+    pub fn srx_graph_fetch(g: *mut SrxGraph, which: i32, indptr: *mut u64, indices: *mut u32, data: *mut f64) -> i32;
+    pub fn srx_graph_fetch_scales(g: *mut SrxGraph, rho: *mut f64, sigma: *mut f64) -> i32;
+    pub fn srx_graph_free(g: *mut SrxGraph);
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,

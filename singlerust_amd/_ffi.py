@@ -24,6 +24,8 @@ ROW, COLUMN = 0, 1
 STORE_AUTO, STORE_F32, STORE_F64 = 0, 1, 2
 K_NORMALIZE, K_MOMENTS, K_COMPACT, K_SPMM_FWD, K_SPMM_T, K_GRAM, K_DENSE, K_ROWSUM, K_ITERATE, K_SELECT, K_BUCKET = range(11)
 K_KNN = 11
+K_GRAPH = 12
+GRAPH_DISTANCES, GRAPH_CONNECTIVITIES = 0, 1
 KNN_MAX_DIMS = 128
 SOLVER_AUTO, SOLVER_GRAM, SOLVER_SPMM = 0, 1, 2
 UNIQUE_ID_BYTES = 128
@@ -73,6 +75,13 @@ class KnnInfo(C.Structure):
     _fields_ = [("n_ref", C.c_uint64), ("n_query", C.c_uint64), ("d", C.c_uint32), ("k", C.c_uint32),
                 ("n_candidates", C.c_uint32), ("reserved_", C.c_uint32), ("rows_certified", C.c_uint64),
                 ("rows_recomputed", C.c_uint64)]
+
+
+class GraphInfo(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("k", C.c_uint32), ("reserved_", C.c_uint32), ("nnz_distances", C.c_uint64),
+                ("nnz_connectivities", C.c_uint64), ("n_mutual", C.c_uint64), ("rows_no_root", C.c_uint64),
+                ("rows_clamped", C.c_uint64), ("rows_all_zero", C.c_uint64), ("entries_dropped", C.c_uint64),
+                ("max_row_nnz", C.c_uint64)]
 
 
 class SynthParams(C.Structure):
@@ -146,6 +155,12 @@ _SIGS = {
     "srx_pca_transform": (C.c_int32, [P, P, P, C.c_double, C.c_int32, P]),
     "srx_knn_result": (C.c_int32, [P, C.POINTER(KnnOpts), P, P, C.POINTER(KnnInfo)]),
     "srx_knn_points": (C.c_int32, [P, P, C.c_uint64, P, C.c_uint64, C.c_uint64, C.POINTER(KnnOpts), P, P, C.POINTER(KnnInfo)]),
+    "srx_neighbors_result": (C.c_int32, [P, C.POINTER(KnnOpts), C.POINTER(KnnInfo), C.POINTER(P)]),
+    "srx_neighbors_from_knn": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.POINTER(P)]),
+    "srx_graph_info_get": (C.c_int32, [P, C.POINTER(GraphInfo)]),
+    "srx_graph_fetch": (C.c_int32, [P, C.c_int32, P, P, P]),
+    "srx_graph_fetch_scales": (C.c_int32, [P, P, P]),
+    "srx_graph_free": (None, [P]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),

@@ -250,6 +250,7 @@ class IMAnnData:
         self.var_names = list(var_names)
         self.obsm: dict[str, np.ndarray] = {}
         self.varm: dict[str, np.ndarray] = {}
+        self.obsp: dict[str, object] = {}        # cell x cell sparse matrices (neighbors(connectivities=True))
         self.var: dict[str, np.ndarray] = {}
         self.obs: dict[str, np.ndarray] = {}
         self.uns: dict[str, object] = {}
@@ -308,12 +309,14 @@ class IMAnnData:
         self._x = other._x
         self.indptr, self.indices = other.indptr, other.indices
         self.obs_names, self.var_names = other.obs_names, other.var_names
-        self.obsm, self.varm, self.obs, self.var = {}, {}, {}, {}
+        self.obsm, self.varm, self.obs, self.var, self.obsp = {}, {}, {}, {}, {}
+        self._graph = None               # (its Graph frees the device handle)
 
     def deep_clone(self) -> "IMAnnData":
         c = IMAnnData(self._x.clone(), self.indptr, self.indices, self.obs_names, self.var_names)
         c.obsm = {k: v.copy() for k, v in self.obsm.items()}
         c.varm = {k: v.copy() for k, v in self.varm.items()}
+        c.obsp = {k: (v.copy() if hasattr(v, "copy") else tuple(a.copy() for a in v)) for k, v in self.obsp.items()}
         c.var = {k: v.copy() for k, v in self.var.items()}
         c.obs = {k: v.copy() for k, v in self.obs.items()}
         return c

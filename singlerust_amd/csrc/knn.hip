@@ -483,6 +483,21 @@ static int32_t knn_check(srx_ctx* ctx, const srx_knn_opts* opts, uint64_t n_ref,
     return SRX_OK;
 }
 
+// srx_knn_result with the list left on the device (graph.hip builds the neighbour graph from it): *d_idx / *d_dist are the
+// "knn_idx" / "knn_dist" scratch slots, n x opts->k row-major, valid until the next k-NN call on this context.
+int32_t knn_result_resident(srx_mat* m, const srx_knn_opts* opts, srx_knn_info* info, const uint32_t** d_idx,
+                            const double** d_dist, uint64_t* n_out) {
+    *n_out = 0;
+    SRX_TRY(srx_knn_result(m, opts, nullptr, nullptr, info));
+    srx_ctx* ctx = m->ctx;
+    const uint64_t n = m->csc ? m->n_cols : m->n_rows;
+    if (n == 0) return SRX_OK;
+    SRX_TRY(scratch(ctx, "knn_idx", 0, (void**)d_idx));
+    SRX_TRY(scratch(ctx, "knn_dist", 0, (void**)d_dist));
+    *n_out = n;
+    return SRX_OK;
+}
+
 }  // namespace srx
 
 using namespace srx;

@@ -513,6 +513,78 @@ inline KnnGraph knn_points(Context& ctx, const std::vector<double>& ref, const s
                              g.distances.empty() ? nullptr : g.distances.data(), &g.info));
     return g;
 }
+
+// The weighted neighbour graph (obsp["distances"], obsp["connectivities"]): an owning wrapper of an srx_graph.  Both matrices
+// stay on the device as CSR for the consumers of the graph; csr() copies one to the host.
+struct GraphCsr {
+    std::vector<std::uint64_t> indptr;       // n + 1
+    std::vector<std::uint32_t> indices;      // ascending within a row
+    std::vector<double> data;
+};
+class Graph {
+public:
+    // k-NN over the scores the last PCA on `a` left on the device, then the graph of it (srx_neighbors_result)
+    static Graph of(const IMAnnData& a, int n_neighbors = 15, int n_pcs = 0) {
+        Graph g(a.ctx());
+        const srx_knn_opts o{n_neighbors, n_pcs, 0, 0};
+        a.ctx().check(srx_neighbors_result(a.x(), &o, &g.knn_info_, &g.h_));
+        return g;
+    }
+    // the graph of a k-NN list (n x k row-major; no row names itself): srx_neighbors_from_knn
+    static Graph from_knn(Context& ctx, const std::vector<std::uint32_t>& indices, const std::vector<double>& distances,
+                          std::size_t k) {
+        if (k == 0 || indices.size() % k || indices.size() != distances.size())
+            throw Error(SRX_E_ARG, "Graph::from_knn: indices and distances must both be n x k");
+        Graph g(ctx);
+        ctx.check(srx_neighbors_from_knn(ctx.handle(), indices.empty() ? nullptr : indices.data(),
+                                         distances.empty() ? nullptr : distances.data(), indices.size() / k,
+                                         static_cast<std::uint32_t>(k), &g.h_));
+        return g;
+    }
+    Graph(Graph&& o) noexcept : ctx_(o.ctx_), h_(o.h_), knn_info_(o.knn_info_) { o.h_ = nullptr; }
+    Graph& operator=(Graph&& o) noexcept {
+        std::swap(ctx_, o.ctx_);
+        std::swap(h_, o.h_);
+        std::swap(knn_info_, o.knn_info_);
+        return *this;
+    }
+    Graph(const Graph&) = delete;
+    Graph& operator=(const Graph&) = delete;
+    ~Graph() { srx_graph_free(h_); }
+
+    srx_graph_info info() const {
+        srx_graph_info i{};
+        ctx_->check(srx_graph_info_get(h_, &i));
+        return i;
+    }
+    const srx_knn_info& knn_info() const { return knn_info_; }
+    GraphCsr csr(int which) const {
+        const srx_graph_info i = info();
+        const std::uint64_t nnz = which == SRX_GRAPH_CONNECTIVITIES ? i.nnz_connectivities : i.nnz_distances;
+        GraphCsr m;
+        m.indptr.resize(i.n + 1);
+        m.indices.resize(nnz);
+        m.data.resize(nnz);
+        ctx_->check(srx_graph_fetch(h_, which, m.indptr.data(), nnz ? m.indices.data() : nullptr, nnz ? m.data.data() : nullptr));
+        return m;
+    }
+    GraphCsr distances() const { return csr(SRX_GRAPH_DISTANCES); }
+    GraphCsr connectivities() const { return csr(SRX_GRAPH_CONNECTIVITIES); }
+    // (rho, sigma), one per cell
+    std::pair<std::vector<double>, std::vector<double>> scales() const {
+        const std::uint64_t n = info().n;
+        std::vector<double> rho(n), sigma(n);
+        ctx_->check(srx_graph_fetch_scales(h_, n ? rho.data() : nullptr, n ? sigma.data() : nullptr));
+        return {rho, sigma};
+    }
+    srx_graph* handle() const { return h_; }
+
+private:
+    explicit Graph(Context& ctx) : ctx_(&ctx) {}
+    Context* ctx_;
+    srx_graph* h_ = nullptr;
+    srx_knn_info knn_info_{};
+};
 }  // namespace processing
 }  // namespace memory
 

@@ -8,7 +8,7 @@ import numpy as np
 from ... import _ffi as F
 from ...anndata import DeviceCsr, Direction, FlexValue, IMAnnData
 from . import dim_red
-from .neighbors import knn_points, neighbors
+from .neighbors import connectivities_from_knn, knn_points, neighbors
 
 
 def normalize_total_inplace(adata: IMAnnData, target_sum: float, direction: Direction) -> None:

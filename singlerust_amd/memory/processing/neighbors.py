@@ -1,4 +1,5 @@
-"""Exact k-nearest-neighbour graph of the cells over libsrx_hip (``srx_knn_result`` / ``srx_knn_points``).
+"""Exact k-nearest-neighbour graph of the cells over libsrx_hip (``srx_knn_result`` / ``srx_knn_points``) and the weighted
+graph built from it (``srx_neighbors_result`` / ``srx_neighbors_from_knn``: ``obsp["distances"]``, ``obsp["connectivities"]``).
 
 Not in the reference: it is the step that consumes ``obsm["X_pca"]`` and stands in front of what the reference's
 commented-out ``tsne`` / ``tsne_inplace`` (dim_red/mod.rs:159-227) would build from the scores.  Euclidean distance in
@@ -20,12 +21,117 @@ def _info_dict(info: F.KnnInfo) -> dict:
             "rows_recomputed": int(info.rows_recomputed)}
 
 
-def neighbors(adata: IMAnnData, n_neighbors: int = 15, n_pcs=None, include_self: bool = False) -> dict:
+class Graph:
+    """Owning wrapper of an ``srx_graph``: distances and connectivities as CSR on the device, with rho and sigma."""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self._h = handle
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        i = F.GraphInfo()
+        F.check(F.lib().srx_graph_info_get(self._h, C.byref(i)), self.ctx.handle)
+        return {name: int(getattr(i, name)) for name, _ in F.GraphInfo._fields_ if name != "reserved_"}
+
+    def fetch(self, which: int):
+        """(indptr uint64 n + 1, indices uint32, data f64) of ``F.GRAPH_DISTANCES`` or ``F.GRAPH_CONNECTIVITIES``."""
+        i = self.info()
+        nnz = i["nnz_connectivities"] if which == F.GRAPH_CONNECTIVITIES else i["nnz_distances"]
+        indptr = np.zeros(i["n"] + 1, dtype=np.uint64)
+        indices = np.zeros(nnz, dtype=np.uint32)
+        data = np.zeros(nnz, dtype=np.float64)
+        F.check(F.lib().srx_graph_fetch(self._h, int(which), F.ptr(indptr), F.ptr(indices) if nnz else None,
+                                        F.ptr(data) if nnz else None), self.ctx.handle)
+        return indptr, indices, data
+
+    def scales(self):
+        """(rho, sigma), one f64 per cell."""
+        n = self.info()["n"]
+        rho, sigma = np.zeros(n), np.zeros(n)
+        F.check(F.lib().srx_graph_fetch_scales(self._h, F.ptr(rho) if n else None, F.ptr(sigma) if n else None), self.ctx.handle)
+        return rho, sigma
+
+    def matrix(self, which: int):
+        """The matrix as ``scipy.sparse.csr_matrix`` where scipy imports, else the CSR triple of ``fetch``."""
+        indptr, indices, data = self.fetch(which)
+        try:
+            import scipy.sparse as sp
+        except ImportError:
+            return indptr, indices, data
+        n = len(indptr) - 1
+        return sp.csr_matrix((data, indices.astype(np.int64 if n >= 2 ** 31 else np.int32), indptr.astype(np.int64)), shape=(n, n))
+
+    def free(self) -> None:
+        if self._h:
+            if getattr(self.ctx, "_h", None):          # as DeviceCsr.free: a closed context took the device memory with it
+                F.lib().srx_graph_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def connectivities_from_knn(ctx, indices, distances) -> Graph:
+    """The graph of a k-NN list (n x k; no row names itself): see ``srx_neighbors_from_knn``."""
+    indices = np.ascontiguousarray(indices, dtype=np.uint32)
+    distances = np.ascontiguousarray(distances, dtype=np.float64)
+    if indices.ndim != 2 or indices.shape != distances.shape:
+        raise ValueError("indices and distances must both be n x k")
+    n, k = indices.shape
+    h = C.c_void_p()
+    F.check(F.lib().srx_neighbors_from_knn(ctx.handle, F.ptr(indices) if indices.size else None,
+                                           F.ptr(distances) if distances.size else None, n, k, C.byref(h)), ctx.handle)
+    return Graph(ctx, h)
+
+
+def _neighbors_graph(adata: IMAnnData, k: int, n_pcs, knn_lists: bool) -> dict:
+    ctx = adata.x().ctx
+    opts = F.KnnOpts(k, int(n_pcs or 0), 0, 0)
+    info = F.KnnInfo()
+    h = C.c_void_p()
+    F.check(F.lib().srx_neighbors_result(adata.x().handle, C.byref(opts), C.byref(info), C.byref(h)), ctx.handle)
+    g = Graph(ctx, h)
+    old = getattr(adata, "_graph", None)
+    if old is not None:
+        old.free()
+    adata._graph = g                     # stays on the device for the consumers of the graph
+    adata.obsp["distances"] = g.matrix(F.GRAPH_DISTANCES)
+    adata.obsp["connectivities"] = g.matrix(F.GRAPH_CONNECTIVITIES)
+    if knn_lists:                        # the rows of D, ascending by (distance, index) as srx_knn_result orders them
+        indptr, indices, data = g.fetch(F.GRAPH_DISTANCES)
+        idx, dist = indices.reshape(-1, k), data.reshape(-1, k)
+        order = np.lexsort((idx, dist), axis=1)
+        adata.obsm["knn_indices"] = np.take_along_axis(idx, order, axis=1)
+        adata.obsm["knn_distances"] = np.take_along_axis(dist, order, axis=1)
+    adata.uns["neighbors"] = {"params": {"n_neighbors": k, "n_pcs": None if n_pcs is None else int(n_pcs),
+                                         "include_self": False, "metric": "euclidean", "method": "umap"},
+                              "info": _info_dict(info), "graph": g.info()}
+    return adata.uns["neighbors"]
+
+
+def neighbors(adata: IMAnnData, n_neighbors: int = 15, n_pcs=None, include_self: bool = False,
+              connectivities: bool = False, knn_lists: bool = False) -> dict:
     """Self graph of the cells in the space of the scores the last ``pca_inplace`` left on the device (no host round trip).
     Stores ``obsm["knn_indices"]`` (uint32, n_obs x k), ``obsm["knn_distances"]`` (f64) and ``uns["neighbors"]``
-    (the parameters and the call's ``srx_knn_info``); returns the latter.  ``n_pcs``: use the leading PCs only."""
+    (the parameters and the call's ``srx_knn_info``); returns the latter.  ``n_pcs``: use the leading PCs only.
+
+    ``connectivities=True`` builds the weighted graph on the device instead (``srx_neighbors_result``; ``include_self`` must
+    be False): ``obsp["distances"]`` and ``obsp["connectivities"]`` (scipy CSR, or (indptr, indices, data) without scipy),
+    ``uns["neighbors"]["graph"]`` (the ``srx_graph_info``), the device handle kept on the adata; ``obsm["knn_*"]`` are
+    filled from the rows of the distances only with ``knn_lists=True``."""
     n = adata.n_obs()
     k = int(n_neighbors)
+    if connectivities:
+        if include_self:
+            raise F.SrxError(F.E_ARG, "neighbors: the graph is built from a list that excludes self (include_self=False)")
+        return _neighbors_graph(adata, k, n_pcs, knn_lists)
     opts = F.KnnOpts(k, int(n_pcs or 0), int(bool(include_self)), 0)
     info = F.KnnInfo()
     idx = np.zeros((n, max(k, 0)), dtype=np.uint32)
