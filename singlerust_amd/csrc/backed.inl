@@ -253,9 +253,7 @@ static int32_t backed_select_impl(srx_backed* b, uint64_t n_hvg, const uint64_t*
     const bool on_device = hvg_on_device(n_hvg, G);
     std::vector<uint64_t> selv;
     if (n_hvg > 0 && !on_device) {                          // HighlyVariable(n) on the host (wide matrices)
-        std::vector<double> var;
-        SRX_TRY(gene_variances(acc, var));
-        SRX_TRY(select_hvg_host(ctx, var, n_hvg, selv));
+        SRX_TRY(hvg_list_host(acc, n_hvg, selv));
         sel = selv.data();
         n_sel = selv.size();
     }
@@ -278,7 +276,7 @@ static int32_t backed_select_impl(srx_backed* b, uint64_t n_hvg, const uint64_t*
         SRX_TRY(d2h(ctx, r.data(), b->sel.d_sel_rank, (size_t)k * sizeof(int32_t)));
         int st = 0;
         SRX_TRY(d2h(ctx, &st, b->sel.d_status, sizeof(int)));
-        if (st & 1) return fail(ctx, SRX_E_NAN, "NaN gene variance: called `Option::unwrap()` on a `None` value (partial_cmp)");
+        if (st & 1) return fail(ctx, SRX_E_NAN, "%s", kNanVarianceMsg);
         for (int i = 0; i < k; ++i) sel_out[i] = (uint64_t)r[i];
     }
     return SRX_OK;
@@ -314,24 +312,10 @@ int32_t srx_backed_solve(srx_backed* b, srx_pca_info* info) {
     if (b->parts.empty()) return fail(ctx, SRX_E_SHAPE, "backed: this rank holds no rows");
     srx_mat* acc = b->acc;
     srx_pca_state& st = acc->pca;
-    st.valid = false;
-    const int k = b->k;
-    st.info = srx_pca_info{};
-    st.info.n_cells_global = acc->n_rows_global;
-    st.info.k = (uint32_t)k;
-    st.info.n_pc = (uint32_t)b->o.n_pc;
-    st.info.block = L;
-    st.info.nnz_selected = b->nnz_sel;
-    st.info.solver = 1;
-    const double Nd = (double)acc->n_rows_global;
-    int32_t rc;
-    if (b->store == SRX_STORE_F32)
-        rc = run_pca<float, float>(ctx, b->parts.data(), (int)b->parts.size(), nullptr, b->d_gram, b->o, b->sel, b->l_act, Nd, st);
-    else
-        rc = run_pca<double, double>(ctx, b->parts.data(), (int)b->parts.size(), nullptr, b->d_gram, b->o, b->sel, b->l_act, Nd, st);
+    const int32_t rc = solve_and_stash(ctx, b->store == SRX_STORE_F32, b->parts.data(), (int)b->parts.size(), nullptr, b->d_gram, b->o,
+                                       b->sel, b->l_act, acc->n_rows_global, b->nnz_sel, st);
     b->phase = 2;
-    if ((rc != SRX_OK && rc != SRX_E_NOCONV) || !st.d_small) return rc;
-    SRX_TRY(stash_results(ctx, st, k, b->o.n_pc, b->sel));
+    if (!st.valid) return rc;                    // nothing was stashed
     acc->n_rows = b->rows2;                      // what srx_result_fetch sizes the scores by
     SRX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     free_parts(b);

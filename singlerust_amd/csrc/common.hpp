@@ -36,6 +36,11 @@ __device__ __forceinline__ T wave_sum(T v) {
     for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
     return v;  // every lane holds the total
 }
+// the LDS writes of this wave's lanes are visible to its other lanes (a wave-private region: no workgroup barrier)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 template <typename T>
 __device__ __forceinline__ T wave_min(T v) {
 #pragma unroll
@@ -130,9 +135,8 @@ struct srx_ctx {
 struct srx_pca_state {           // what the last srx_pca / srx_pipeline left in HBM
     bool valid = false;
     uint32_t k = 0, n_pc = 0;
-    uint32_t rounds = 1;             // deflation rounds of the solve
     int center = 1, scale = 1;       // the flags the solve ran with (srx_pca_model_from_result)
-    std::vector<int> round_counts;   // components resolved by each round (sums to n_pc)
+    std::vector<int> round_counts;   // components resolved by each deflation round (sums to n_pc); set by run_pca with its plan
     double* d_scores = nullptr;      // n_rows x n_pc, row-major f64
     size_t scores_cap = 0;
     std::vector<double> components;  // k x n_pc (host copy; small)
@@ -141,9 +145,7 @@ struct srx_pca_state {           // what the last srx_pca / srx_pipeline left in
     srx_pca_info info{};
     // Deferred host copies ("results stay on the device until fetched"): the solve leaves its small results in
     // `d_small` (carved from the d_scores allocation) and the host vectors above are produced by the first
-    // fetch — pca_materialize() in pca.hip.  Layout in doubles (the tail: k_sel_finish's vectors and selection, whatever the
-    // selection was, copied in by stash_results):
-    //   rounds x [ V k*64 | theta 64 | sgn 64 ] | mu k | sd k | trace 1 | pad 1 | sel_rank (int32) k
+    // fetch — pca_materialize() in pca.hip.  Its layout: PcaResultLayout (pca_result.hpp) of k and round_counts.
     double* d_small = nullptr;
     bool host_pending = false;
 };

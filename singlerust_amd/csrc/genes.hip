@@ -1006,7 +1006,7 @@ void finalize_variance(const uint64_t* cnt, const double* sum, const double* sq,
     }
 }
 
-int32_t gene_variances(srx_mat* m, std::vector<double>& var) {
+static int32_t gene_variances(srx_mat* m, std::vector<double>& var) {
     std::vector<uint64_t> cnt;
     std::vector<double> sum, sq;
     SRX_TRY(fetch_moments(m, cnt, sum, sq));
@@ -1016,9 +1016,9 @@ int32_t gene_variances(srx_mat* m, std::vector<double>& var) {
 }
 
 // dim_red/mod.rs:135-140.  Rust's sort_by is stable; comparator b.partial_cmp(a) = descending.
-int32_t select_hvg_host(srx_ctx* ctx, const std::vector<double>& var, uint64_t n, std::vector<uint64_t>& out) {
+static int32_t select_hvg_host(srx_ctx* ctx, const std::vector<double>& var, uint64_t n, std::vector<uint64_t>& out) {
     for (double v : var)
-        if (v != v) return fail(ctx, SRX_E_NAN, "NaN gene variance: called `Option::unwrap()` on a `None` value (partial_cmp)");
+        if (v != v) return fail(ctx, SRX_E_NAN, "%s", kNanVarianceMsg);
     // stable descending order == the strict total order (variance desc, gene index asc), so a
     // partial sort of the first n under that order gives exactly the stable sort's prefix
     std::vector<uint64_t> order(var.size());
@@ -1412,6 +1412,17 @@ int32_t row_number(srx_mat* m, uint32_t* out);
 int32_t row_qc(srx_mat* m, uint32_t* num, double* sum, double* var);
 int32_t row_stat(srx_mat* m, int which, double* out0, double* out1);
 
+int32_t hvg_list_host(srx_mat* m, uint64_t n, std::vector<uint64_t>& out) {
+    std::vector<double> var;
+    if (m->csc) {                                // compute_variance(Column) of a CSC matrix: csc.rs:164-177 (NaN for an empty gene)
+        var.resize(m->n_rows);
+        SRX_TRY(row_stat(m, 1, var.data(), nullptr));
+    } else {
+        SRX_TRY(gene_variances(m, var));
+    }
+    return select_hvg_host(m->ctx, var, n, out);
+}
+
 }  // namespace srx
 
 using namespace srx;
@@ -1579,15 +1590,8 @@ int32_t srx_normalize_total_inplace(srx_mat* m, double target_sum, int32_t direc
 int32_t srx_select_hvg(srx_mat* m, uint64_t n, uint64_t* idx_out, uint64_t* n_out) {
     if (!m || !n_out) return fail(m ? m->ctx : nullptr, SRX_E_ARG, "null argument");
     SRX_HIP(m->ctx, hipSetDevice(m->ctx->device));
-    std::vector<double> var;
-    if (m->csc) {                                // compute_variance(Column) of a CSC matrix: csc.rs:164-177 (NaN for an empty gene)
-        var.resize(m->n_rows);
-        SRX_TRY(row_stat(m, 1, var.data(), nullptr));
-    } else {
-        SRX_TRY(gene_variances(m, var));
-    }
     std::vector<uint64_t> sel;
-    SRX_TRY(select_hvg_host(m->ctx, var, n, sel));
+    SRX_TRY(hvg_list_host(m, n, sel));
     if (idx_out) memcpy(idx_out, sel.data(), sel.size() * sizeof(uint64_t));
     *n_out = sel.size();
     return SRX_OK;

@@ -65,10 +65,6 @@ constexpr int kCtrSlots = 64;            // counters are spread over slots (row 
 enum { kCtrNoRoot = 0, kCtrClamped, kCtrAllZero, kCtrMutual, kCtrDropped, kCtrN };
 enum { kBadRange = 1, kBadSelf = 2, kBadDup = 4, kBadDist = 8 };
 
-__device__ __forceinline__ void graph_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 __device__ __forceinline__ unsigned long long below(int p) { return p >= 64 ? ~0ull : (1ull << p) - 1ull; }
 // (a + b) - a b in one rounding of the product: symmetric in a and b, 0 < result <= 1 for a, b in [0, 1] not both 0
 __device__ __forceinline__ double fuzzy_union(double a, double b) { return fma(-a, b, a + b); }
@@ -109,12 +105,12 @@ __global__ void __launch_bounds__(256) k_graph_rows(const uint32_t* __restrict__
     // the row in column order
     s_i[wave][lane] = 0xFFFFFFFFu;
     s_d[wave][lane] = 0.0;
-    graph_lds_sync();
+    wave_lds_sync();
     if (act) {
         s_i[wave][rank] = ci;
         s_d[wave][rank] = cd;
     }
-    graph_lds_sync();
+    wave_lds_sync();
     ci = s_i[wave][lane];
     cd = s_d[wave][lane];
 
@@ -272,7 +268,7 @@ __global__ void __launch_bounds__(256) k_graph_order(const int64_t* __restrict__
         s_s[wave][t] = t_src[lo + t];
         s_v[wave][t] = t_val[lo + t];
     }
-    graph_lds_sync();
+    wave_lds_sync();
     for (int t = lane; t < m; t += kWave) {
         const uint32_t key = s_s[wave][t];
         int r = 0;
@@ -355,7 +351,7 @@ __global__ void __launch_bounds__(256) k_graph_merge(const uint32_t* __restrict_
     const bool kept = act && (flags[e] & 1);
     const unsigned long long keptmask = __builtin_amdgcn_ballot_w64(kept);
     s_col[wave][lane] = col;
-    graph_lds_sync();
+    wave_lds_sync();
     const int64_t tlo = tptr[row];
     const int m = (int)(tptr[row + 1] - tlo);
     const uint32_t* ts = (m > kShort ? l_src : t_src) + tlo;

@@ -146,19 +146,20 @@ __global__ __launch_bounds__(1024) void k_make_panel_mb(const double* __restrict
                                                         const double* __restrict__ mu, const double* __restrict__ colmax,
                                                         const double* __restrict__ theta, int k, PT* __restrict__ P,
                                                         double* __restrict__ part /* [blocks][64] */, double* __restrict__ sgn_out,
-                                                        double* __restrict__ blk /* k*64 vectors | 64 values | 64 signs */) {
+                                                        double* __restrict__ res_V, double* __restrict__ res_theta,
+                                                        double* __restrict__ res_sgn /* the round's place in the result block */) {
     __shared__ double s_part[16][L];
     const int c = threadIdx.x & (L - 1), sl = threadIdx.x / L;   // 16 row slices x 64 columns
     const double sg = colmax[c] < 0 ? -1.0 : 1.0;
     if (blockIdx.x == 0 && sl == 0) {
         sgn_out[c] = sg;
-        blk[(size_t)k * L + c] = theta[c];
-        blk[(size_t)k * L + L + c] = sg;
+        res_theta[c] = theta[c];
+        res_sgn[c] = sg;
     }
     double acc = 0.0;
     for (int j = blockIdx.x * 16 + sl; j < k; j += gridDim.x * 16) {
         const double wv = W[(size_t)j * L + c];
-        blk[(size_t)j * L + c] = wv;
+        res_V[(size_t)j * L + c] = wv;
         const PT p = (PT)(d[j] * wv * sg);
         P[(size_t)j * L + c] = p;
         acc += mu[j] * (double)p;

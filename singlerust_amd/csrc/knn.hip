@@ -43,10 +43,6 @@ constexpr uint32_t kKnnNone = 0xFFFFFFFFu;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 // f32 -> u32 with the same order (negative scores occur: t = dist^2 - |q|^2)
 __device__ __forceinline__ uint32_t f32_key(float f) {
     const uint32_t b = __float_as_uint(f);

@@ -98,25 +98,7 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
     const bool need_t256 = o.solver == 2;
     SRX_TRY(compact_selection(m, sd.d_bits, sd.n_words, k, rm, xf, o.solver == 1));
     if (need_t256) SRX_TRY(retile(m, rm, t256));
-    st.info = srx_pca_info{};
-    st.info.n_cells_global = Ng;
-    st.info.k = (uint32_t)k;
-    st.info.n_pc = (uint32_t)o.n_pc;
-    st.info.block = L;
-    st.info.nnz_selected = rm.nnz;
-    st.info.solver = (uint32_t)o.solver;
-    int32_t rc;
-    const double Nd = (double)Ng;
-    // f32 storage: f32 panels and products for the one transform of the Gram route; the matrix-free iteration runs its
-    // panels in f64 (f32 products of Z W level the residuals of the small components off at ~1e-7 theta_1 / theta_i:
-    // 6.6e-5 at k = 9000 on a flat-tailed matrix, however many sweeps)
-    const Tiled* t256p = need_t256 ? &t256 : nullptr;
-    if (is_f32(m) && o.solver == 2) rc = run_pca<float, double>(ctx, &rm, 1, t256p, nullptr, o, sd, l_act, Nd, st);
-    else if (is_f32(m)) rc = run_pca<float, float>(ctx, &rm, 1, t256p, nullptr, o, sd, l_act, Nd, st);
-    else rc = run_pca<double, double>(ctx, &rm, 1, t256p, nullptr, o, sd, l_act, Nd, st);
-    if ((rc != SRX_OK && rc != SRX_E_NOCONV) || !st.d_small) return rc;      // d_small unset: the solve broke down early
-    SRX_TRY(stash_results(ctx, st, k, o.n_pc, sd));
-    return rc;
+    return solve_and_stash(ctx, is_f32(m), &rm, 1, need_t256 ? &t256 : nullptr, nullptr, o, sd, l_act, Ng, rm.nnz, st);
 }
 
 // Host copies of the last solve: components (k x n_pc, rows in SELECTION order, sign-fixed), explained variance
@@ -127,26 +109,11 @@ static int32_t pca_materialize(srx_mat* m) {
     if (!st.valid || !st.host_pending) return SRX_OK;
     srx_ctx* ctx = m->ctx;
     const int k = (int)st.k, n_pc = (int)st.n_pc;
-    const size_t kl = (size_t)k * L;
-    const int rounds = (int)st.rounds;
-    const size_t rblk = kl + 2 * L;
-    const size_t small_doubles = (size_t)rounds * rblk + 2 * (size_t)k + 2 + ((size_t)k + 1) / 2;
-    std::vector<double> blk(small_doubles);
-    SRX_TRY(d2h(ctx, blk.data(), st.d_small, small_doubles * 8));
-    const double* tail = blk.data() + (size_t)rounds * rblk;
-    // component p lives in the round whose range of components holds it, at column p - first component of that round
-    std::vector<int> first(rounds + 1, 0);
-    for (int r = 0; r < rounds; ++r) first[r + 1] = first[r] + (r < (int)st.round_counts.size() ? st.round_counts[r] : 0);
-    auto locate = [&](int p, const double*& hV, const double*& theta, const double*& sgn, int& c) {
-        int r = 0;
-        while (r + 1 < rounds && p >= first[r + 1]) ++r;
-        c = p - first[r];
-        hV = blk.data() + (size_t)r * rblk;
-        theta = hV + kl;
-        sgn = theta + L;
-    };
-    const double *mu = tail, *sd = tail + k, trace = tail[2 * (size_t)k];
-    const int32_t* hsel = reinterpret_cast<const int32_t*>(tail + 2 * (size_t)k + 2);
+    const PcaResultLayout lay = result_block(st);
+    std::vector<double> blk(lay.total_doubles());
+    SRX_TRY(d2h(ctx, blk.data(), st.d_small, blk.size() * 8));
+    const double *mu = blk.data() + lay.mu(), *sd = blk.data() + lay.sd(), trace = blk[lay.trace()];
+    const int32_t* hsel = reinterpret_cast<const int32_t*>(blk.data() + lay.sel_rank());
     st.sel.assign(hsel, hsel + k);
     // slot (ascending gene order) of every selected feature
     std::vector<int> order(k), slot_of_sel(k);
@@ -158,22 +125,12 @@ static int32_t pca_materialize(srx_mat* m) {
     st.std_.resize(k);
     for (int i = 0; i < k; ++i) {
         const int sl = slot_of_sel[i];
-        for (int p = 0; p < n_pc; ++p) {
-            const double *hV, *theta, *sgn;
-            int c;
-            locate(p, hV, theta, sgn, c);
-            st.components[(size_t)i * n_pc + p] = hV[(size_t)sl * L + c] * sgn[c];
-        }
+        for (int p = 0; p < n_pc; ++p) st.components[(size_t)i * n_pc + p] = blk[(size_t)sl * L + lay.col_offset(p)] * blk[lay.sgn_offset(p)];
         st.mean[i] = mu[sl];
         st.std_[i] = sd[sl];
     }
     st.evr.resize(n_pc);
-    for (int p = 0; p < n_pc; ++p) {
-        const double *hV, *theta, *sgn;
-        int c;
-        locate(p, hV, theta, sgn, c);
-        st.evr[p] = trace > 0 ? theta[c] / trace : 0.0;
-    }
+    for (int p = 0; p < n_pc; ++p) st.evr[p] = trace > 0 ? blk[lay.theta_offset(p)] / trace : 0.0;
     st.host_pending = false;
     return SRX_OK;
 }
@@ -305,16 +262,7 @@ int32_t srx_pipeline(srx_mat* m, double target_sum, uint64_t n_hvg, const srx_pc
     // and for CSC, and passed on as a list
     std::vector<uint64_t> sel;
     const bool on_device = !m->csc && hvg_on_device(n_hvg, m->n_cols);
-    if (rc == SRX_OK && m->csc) {                 // HighlyVariable(n) with the CSC variance (csc.rs:164-177)
-        uint64_t n_out = 0;
-        sel.resize(n_hvg < m->n_rows ? n_hvg : m->n_rows);
-        rc = srx_select_hvg(m, n_hvg, sel.data(), &n_out);
-        sel.resize(rc == SRX_OK ? n_out : 0);
-    } else if (rc == SRX_OK && !on_device) {
-        std::vector<double> var;
-        rc = gene_variances(m, var);
-        if (rc == SRX_OK) rc = select_hvg_host(ctx, var, n_hvg, sel);
-    }
+    if (rc == SRX_OK && !on_device) rc = hvg_list_host(m, n_hvg, sel);      // (CSC: with the CSC variance, csc.rs:164-177)
     (void)hipEventRecord(ev[3], ctx->stream);
     if (rc == SRX_OK) {
         Range r_("srx:pca");

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "pca_result.hpp"
 
 namespace srx {
 
@@ -156,8 +157,10 @@ struct Resolved {
 
 
 // ---- genes.hip -------------------------------------------------------------------------------------
-int32_t gene_variances(srx_mat* m, std::vector<double>& var);
-int32_t select_hvg_host(srx_ctx* ctx, const std::vector<double>& var, uint64_t n, std::vector<uint64_t>& out);
+// FeatureSelection::HighlyVariable(n) ranked on the host (the CSC variance for a CSC matrix): the route of srx_select_hvg, and of
+// the PCA drivers outside hvg_on_device's envelope, which pass the list on
+int32_t hvg_list_host(srx_mat* m, uint64_t n, std::vector<uint64_t>& out);
+constexpr const char* kNanVarianceMsg = "NaN gene variance: called `Option::unwrap()` on a `None` value (partial_cmp)";
 // The selection of a PCA on the device, made by k_sel_finish from a per-gene rank table (context scratch buffers)
 struct SelDev {
     int k = 0, n_words = 0;
@@ -201,10 +204,13 @@ void result_layout(uint64_t n_rows, int k, int n_pc, int dim, size_t& score_byte
                    std::vector<int>* plan_a_out = nullptr, std::vector<int>* plan_b_out = nullptr);
 int32_t ensure_result_capacity(srx_ctx* ctx, srx_pca_state& st, size_t need);
 int32_t resolve_opts(srx_ctx* ctx, const srx_pca_opts* opts, int k, uint64_t Ng, bool f32, Resolved& o, int& l_act);
-template <typename VT, typename PT>
-int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed, const Resolved& o,
-                const SelDev& sel, int l_act, double n_cells, srx_pca_state& st);
-// the small results of a solve move from the context's scratch into the matrix's own result block (host copies: pca_materialize)
-int32_t stash_results(srx_ctx* ctx, srx_pca_state& st, int k, int n_pc, const SelDev& sel);
+inline PcaResultLayout result_block(const srx_pca_state& st) { return PcaResultLayout(st.k, L, st.round_counts); }
+// What the resident and the backed driver do with their compacted rows (`parts`: one for a resident matrix, one per row tile in
+// backed mode, then `gram_packed` is the packed Gram matrix summed over the tiles; `t256p`: the 256-tiled view, matrix-free
+// solver only): st.info, the solve at the precisions of (f32 storage, o.solver), and the small results moved from the context's
+// scratch into the matrix's own result block (host copies: pca_materialize).  A solve that broke down before it had a block
+// returns its code with st.valid false.
+int32_t solve_and_stash(srx_ctx* ctx, bool f32, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed,
+                        const Resolved& o, const SelDev& sel, int l_act, uint64_t n_cells, uint64_t nnz_selected, srx_pca_state& st);
 
 }  // namespace srx

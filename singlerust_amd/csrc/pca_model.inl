@@ -201,16 +201,12 @@ int32_t srx_pca_model_from_result(srx_mat* m, srx_pca_model** out) {
     const uint64_t k = st.k, n_pc = st.n_pc;
     srx_pca_model* p = nullptr;
     SRX_TRY(model_alloc(ctx, k, n_pc, st.center, st.scale, true, &p));
-    // the result block: rounds x [V k*64 | theta 64 | sgn 64] | mu k | sd k | trace 1 | pad 1 | sel_rank (int32) k, rows in slot
-    // (ascending gene) order; component j lives in the round whose range holds it
-    const size_t kl = (size_t)k * L, rblk = kl + 2 * L;
-    const double* tail = st.d_small + (size_t)st.rounds * rblk;
-    const int32_t* d_sel_rank = reinterpret_cast<const int32_t*>(tail + 2 * k + 2);
+    const PcaResultLayout lay = result_block(st);         // (rows of V in slot — ascending gene — order)
+    const int32_t* d_sel_rank = reinterpret_cast<const int32_t*>(st.d_small + lay.sel_rank());
     std::vector<int64_t> col_off(n_pc), sgn_off(n_pc);
-    for (uint64_t j = 0, r = 0, first = 0; j < n_pc; ++j) {
-        while (r + 1 < st.rounds && r < st.round_counts.size() && j >= first + (uint64_t)st.round_counts[r]) first += st.round_counts[r++];
-        col_off[j] = (int64_t)(r * rblk + (j - first));
-        sgn_off[j] = (int64_t)(r * rblk + kl + L + (j - first));
+    for (uint64_t j = 0; j < n_pc; ++j) {
+        col_off[j] = (int64_t)lay.col_offset(j);
+        sgn_off[j] = (int64_t)lay.sgn_offset(j);
     }
     int32_t* slots;
     int32_t rc = scratch(ctx, "pcam_slots", k * sizeof(int32_t), (void**)&slots);
@@ -219,7 +215,7 @@ int32_t srx_pca_model_from_result(srx_mat* m, srx_pca_model** out) {
         const hipError_t e = hipMemcpyAsync(p->d_sel, d_sel_rank, k * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream);
         rc = e == hipSuccess ? SRX_OK : fail(ctx, SRX_E_HIP, "srx_pca_model_from_result: copy of the selection failed");
     }
-    if (rc == SRX_OK) rc = model_build(p, st.d_small, L, col_off, sgn_off, slots, tail, tail + k);
+    if (rc == SRX_OK) rc = model_build(p, st.d_small, L, col_off, sgn_off, slots, st.d_small + lay.mu(), st.d_small + lay.sd());
     if (rc != SRX_OK) {
         srx_pca_model_free(p);
         return rc;

@@ -392,7 +392,7 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
         ratio = ctx->pin_async[kSlotDoubles * slot + 2];
         spread = ctx->pin_async[kSlotDoubles * slot + 4];
         if ((int)ctx->pin_async[kSlotDoubles * slot + 3] & 1)
-            return fail(ctx, SRX_E_NAN, "NaN gene variance: called `Option::unwrap()` on a `None` value (partial_cmp)");
+            return fail(ctx, SRX_E_NAN, "%s", kNanVarianceMsg);
         if (st & kStatChol) return fail(ctx, SRX_E_NOCONV, "pca: block lost rank (Cholesky pivot <= 0)");
         if (st & kStatEig) return fail(ctx, SRX_E_NOCONV, "pca: l x l eigen-solver did not converge");
         if (r != r) return fail(ctx, SRX_E_NOCONV, "pca: NaN in the Ritz residual");
@@ -663,7 +663,7 @@ __global__ void k_deflate(double* __restrict__ C, int k, const double* __restric
 }
 
 // Size of a matrix's result allocation: the N x n_pc f64 scores followed by the block of small results
-// (layout: srx_pca_state::d_small) for the most rounds either plan can take.
+// (PcaResultLayout) for the most rounds either plan can take.
 // Row stride (in doubles) of the score matrix IN HBM: n_pc rounded up to a whole number of 128-byte pieces (16 doubles), so
 // that the 16-column piece a panel-slice workgroup of the forward SpMM writes for a cell is its own two aligned 64-byte lines
 // — with the reference's N x n_pc layout (400-byte rows at n_pc = 50) every piece straddled lines shared with another
@@ -674,13 +674,11 @@ int scores_ld(int n_pc) {
 }
 void result_layout(uint64_t n_rows, int k, int n_pc, int dim, size_t& score_bytes, size_t& small_doubles,
                    std::vector<int>* plan_a_out, std::vector<int>* plan_b_out) {
-    const size_t kl = (size_t)k * L;
     const std::vector<int> pa = plan_rounds(dim, n_pc, n_pc <= L - 8 ? n_pc : kPcaPerRound);
     const int n_b = (n_pc + kPcaPerRoundSafe - 1) / kPcaPerRoundSafe;
     const std::vector<int> pb = plan_rounds(dim, n_pc, (n_pc + n_b - 1) / n_b);
-    const int rounds_cap = (int)std::max(pa.size(), pb.size());
     score_bytes = (n_rows ? n_rows : 1) * (size_t)scores_ld(n_pc) * 8;
-    small_doubles = (size_t)rounds_cap * (kl + 2 * L) + 2 * (size_t)k + 2 + ((size_t)k + 1) / 2;
+    small_doubles = PcaResultLayout(k, L, std::max(pa.size(), pb.size())).total_doubles();
     if (plan_a_out) *plan_a_out = pa;
     if (plan_b_out) *plan_b_out = pb;
 }
@@ -696,11 +694,8 @@ int32_t ensure_result_capacity(srx_ctx* ctx, srx_pca_state& st, size_t need) {
 }
 
 template <typename VT, typename PT>
-int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed,
+static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed,
                        const Resolved& o, const SelDev& sel, int l_act, double n_cells, srx_pca_state& st) {
-    // `parts`: the row-major compacted rows of this rank — one for a resident matrix, one per row tile in backed mode (then
-    // `gram_packed` holds the packed Gram matrix already summed over the row tiles); `t256p`: the 256-tiled view, made for
-    // the matrix-free solver
     const RowMajor* rmp = n_parts == 1 ? &parts[0] : nullptr;
     const int k = parts[0].k;
     struct { uint64_t n_rows, max_rows; } cc{0, 0};
@@ -751,9 +746,10 @@ int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t
     // the matrix's own block; their host copies are made by the first fetch (pca_materialize).
     auto finish_round = [&](int r, int col0, int n_r) -> int32_t {
         // signs, panel, centring partials and the copy of (Ritz vectors, values, signs) into the result block: one pass
-        double* blk = d_small + (size_t)r * (kl + 2 * L);
+        const PcaResultLayout lay(k, L, st.round_counts);
         hipLaunchKernelGGL((k_make_panel_mb<PT>), dim3(kPanelBlocks), dim3(1024), 0, ctx->stream, (const double*)w.A2, (const double*)w.d,
-                           (const double*)w.mu, (const double*)w.dColmax, (const double*)w.dTheta, k, P, w.gpart, w.dSgn, blk);
+                           (const double*)w.mu, (const double*)w.dColmax, (const double*)w.dTheta, k, P, w.gpart, w.dSgn, d_small + lay.V(r),
+                           d_small + lay.theta(r), d_small + lay.sgn(r));
         hipLaunchKernelGGL((k_cvec_reduce<PT>), dim3(1), dim3(L), 0, ctx->stream, (const double*)w.gpart, kPanelBlocks, o.center, cvec);
         SRX_HIP(ctx, hipGetLastError());
         // scores = Z V: the transform from the row-major records, one launch per row tile (the tile-major kernel — 1.22 ms
@@ -778,6 +774,7 @@ int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t
     auto run_plan = [&](const std::vector<int>& plan, int budget, bool robust, auto& apply, const void* apply_id, bool graphable,
                         auto& reset, auto& deflate, double bail = 0.0, bool resume = false) -> int32_t {
         if (!resume) SRX_TRY(reset());      // (resume: nothing was deflated, C is as expanded)
+        st.round_counts = plan;             // the layout of the result block, for finish_round and every reader
         resid = 0.0;
         converged = true;
         iters = 0;
@@ -814,8 +811,6 @@ int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t
             if (r + 1 < rounds) SRX_TRY(deflate(done, o_r.n_pc));
             done += o_r.n_pc;
         }
-        st.rounds = (uint32_t)rounds;
-        st.round_counts = plan;
         return SRX_OK;
     };
     // plan A, then plan B if it stalled or broke down.  One round for everything gets a short budget before the safe
@@ -1000,30 +995,44 @@ int32_t resolve_opts(srx_ctx* ctx, const srx_pca_opts* opts, int k, uint64_t Ng,
 }
 
 // Everything the host side of the result needs stays on the device until the first fetch (pca_materialize).
-int32_t stash_results(srx_ctx* ctx, srx_pca_state& st, int k, int n_pc, const SelDev& sel) {
-    const size_t kl = (size_t)k * L;
-    double* sm = st.d_small + (size_t)st.rounds * (kl + 2 * L);      // behind the per-round blocks
+static int32_t stash_results(srx_ctx* ctx, srx_pca_state& st, int k, int n_pc, const SelDev& sel) {
+    st.k = (uint32_t)k;
+    st.n_pc = (uint32_t)n_pc;
+    const PcaResultLayout lay = result_block(st);
+    double* const sm = st.d_small;
     CopySegs cs;                                           // (four runtime copies were 20 us of dispatches)
-    cs.src[0] = (const uint32_t*)sel.d_mu;       cs.dst[0] = (uint32_t*)sm;                          cs.words[0] = (uint32_t)k * 2;
-    cs.src[1] = (const uint32_t*)sel.d_sd;       cs.dst[1] = (uint32_t*)(sm + k);                    cs.words[1] = (uint32_t)k * 2;
-    cs.src[2] = (const uint32_t*)sel.d_trace;    cs.dst[2] = (uint32_t*)(sm + 2 * (size_t)k);        cs.words[2] = 2;
-    cs.src[3] = (const uint32_t*)sel.d_sel_rank; cs.dst[3] = (uint32_t*)(sm + 2 * (size_t)k + 2);    cs.words[3] = (uint32_t)k;
+    cs.src[0] = (const uint32_t*)sel.d_mu;       cs.dst[0] = (uint32_t*)(sm + lay.mu());        cs.words[0] = (uint32_t)k * 2;
+    cs.src[1] = (const uint32_t*)sel.d_sd;       cs.dst[1] = (uint32_t*)(sm + lay.sd());        cs.words[1] = (uint32_t)k * 2;
+    cs.src[2] = (const uint32_t*)sel.d_trace;    cs.dst[2] = (uint32_t*)(sm + lay.trace());     cs.words[2] = 2;
+    cs.src[3] = (const uint32_t*)sel.d_sel_rank; cs.dst[3] = (uint32_t*)(sm + lay.sel_rank());  cs.words[3] = (uint32_t)k;
     hipLaunchKernelGGL(k_copy_segs, dim3(16), dim3(256), 0, ctx->stream, cs);
     SRX_HIP(ctx, hipGetLastError());
     st.sel.clear();
-    st.k = (uint32_t)k;
-    st.n_pc = (uint32_t)n_pc;
     st.host_pending = true;
     st.valid = true;
     return SRX_OK;
 }
 
-template int32_t run_pca<float, float>(srx_ctx*, const RowMajor*, int, const Tiled*, double*, const Resolved&, const SelDev&, int, double,
-                                        srx_pca_state&);
-template int32_t run_pca<float, double>(srx_ctx*, const RowMajor*, int, const Tiled*, double*, const Resolved&, const SelDev&, int, double,
-                                         srx_pca_state&);
-template int32_t run_pca<double, double>(srx_ctx*, const RowMajor*, int, const Tiled*, double*, const Resolved&, const SelDev&, int, double,
-                                          srx_pca_state&);
+int32_t solve_and_stash(srx_ctx* ctx, bool f32, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed,
+                        const Resolved& o, const SelDev& sel, int l_act, uint64_t n_cells, uint64_t nnz_selected, srx_pca_state& st) {
+    const int k = parts[0].k;
+    st.valid = false;
+    st.info = srx_pca_info{};
+    st.info.n_cells_global = n_cells;
+    st.info.k = (uint32_t)k;
+    st.info.n_pc = (uint32_t)o.n_pc;
+    st.info.block = L;
+    st.info.nnz_selected = nnz_selected;
+    st.info.solver = (uint32_t)o.solver;
+    // f32 storage: f32 panels and products for the one transform of the Gram route; the matrix-free iteration runs its
+    // panels in f64 (f32 products of Z W level the residuals of the small components off at ~1e-7 theta_1 / theta_i:
+    // 6.6e-5 at k = 9000 on a flat-tailed matrix, however many sweeps)
+    const auto run = !f32 ? run_pca<double, double> : o.solver == 2 ? run_pca<float, double> : run_pca<float, float>;
+    const int32_t rc = run(ctx, parts, n_parts, t256p, gram_packed, o, sel, l_act, (double)n_cells, st);
+    if ((rc != SRX_OK && rc != SRX_E_NOCONV) || !st.d_small) return rc;      // d_small unset: the solve broke down early
+    SRX_TRY(stash_results(ctx, st, k, o.n_pc, sel));
+    return rc;
+}
 
 }  // namespace srx
 
