@@ -47,9 +47,6 @@ struct srx_backed {
 
 namespace srx {
 
-int32_t row_number(srx_mat* m, uint32_t* out);                 // rows.hip
-int32_t row_stat(srx_mat* m, int which, double* out0, double* out1);
-
 static __global__ void k_acc_f64(double* __restrict__ acc, const double* __restrict__ x, uint64_t n) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) acc[i] += x[i];
@@ -213,7 +210,7 @@ int32_t srx_backed_moments(srx_backed* b, uint64_t* cnt, double* sum, double* su
         SRX_TRY(scratch(ctx, "backed_packed", n * sizeof(double), (void**)&tmp));
         SRX_HIP(ctx, hipMemcpyAsync(tmp, b->d_packed, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
         SRX_TRY(moments_install(b->acc, tmp));
-        if (b->phase == 0) b->acc->moments_version = 0;       // sweep 1 still open: recompute on the next call
+        if (b->phase == 0) moments_retire(b->acc);            // sweep 1 still open: recompute on the next call
     }
     const uint64_t G = b->n_cols;
     if (cnt) SRX_TRY(d2h(ctx, cnt, b->acc->d_cnt, G * sizeof(uint64_t)));

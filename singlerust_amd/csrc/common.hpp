@@ -174,7 +174,7 @@ struct srx_mat {
     // inherited by clones); with them the moments passes drop the count atomic
     uint32_t* d_cnt_pat = nullptr;
     bool cnt_pat_valid = false;
-    // per-gene moment cache, keyed by the value version
+    // per-gene moment cache, keyed by the value version (moments_version: written by its owner, genes.hip, alone)
     uint64_t version = 1;
     uint64_t moments_version = 0;
     uint64_t* d_cnt = nullptr;      // n_cols (global after all-reduce)
@@ -182,9 +182,6 @@ struct srx_mat {
     double* d_sq = nullptr;
     uint64_t n_rows_global = 0;     // valid with moments
     double* d_row_sum = nullptr;    // n_rows f64, filled by the normalise pass
-    // pipeline: the matrix is still RAW and the in-place normalise(lazy_target) + log1p is owed (launch_writeback, pca.hip)
-    bool lazy_pending = false;
-    double lazy_target = 0.0;
     // CSC storage (DynCscMatrix): the arrays above are the CSR of X^T (n_rows = n_vars, n_cols = n_obs) and the
     // entry points exchange Row and Column (csc.hip)
     bool csc = false;
@@ -272,19 +269,31 @@ struct RowXf {
 };
 int32_t upload_on(srx_ctx* ctx, const srx_csr* h, int32_t store, hipStream_t stream, srx_mat** out);   // ctx.hip
 int32_t tiles_from_idx16(srx_mat* m, hipStream_t stream);     // genes.hip: 32-bit indices + gene-tile cuts from an uploaded 16-bit mirror
+inline uint64_t at_least_one(uint64_t n) { return n ? n : 1; }   // sizes of buffers and grids that must not be empty
 hipError_t dev_malloc(srx_ctx* ctx, void** p, size_t bytes);     // ctx.hip: hipMalloc, or a recycled buffer while ctx->pool_on
 void pool_clear(srx_ctx* ctx);
 int32_t ensure_tiles(srx_mat* m);
 int32_t promote_to_f64(srx_mat* m);                   // ctx.hip: f32 storage -> f64 storage, values unchanged
 int32_t ensure_pattern_counts(srx_mat* m);            // genes.hip
-int32_t ensure_moments(srx_mat* m);   // fills d_cnt/d_sum/d_sq (global) for the current values
+// The per-gene moments cache of a matrix (genes.hip):
+int32_t ensure_moments(srx_mat* m);   // fills d_cnt/d_sum/d_sq (global) and n_rows_global for the current values
 int32_t moments_accumulate(srx_mat* m, double* d_acc, RowXf xf);     // backed mode: this tile's (cnt,sum,sumsq,N) += into d_acc
 int32_t moments_install(srx_mat* m, double* d_packed);     // all-reduce d_packed and make it m's global moments
+// moments of the TRANSFORMED values from the raw matrix, NOT stamped as current; `stored`: the pass has stored the transformed
+// values in place and booked X as normalised + log1p'd — set as soon as its kernel is in the stream, also when the call fails later
+int32_t ensure_moments_xf(srx_mat* m, RowXf xf, bool* stored);
+void moments_adopt(srx_mat* m);       // the moments just installed belong to the current values (although computed from the f64 transform)
+void moments_retire(srx_mat* m);      // the cached moments are not those of the values as stored: the next reader recomputes
 int32_t launch_row_apply(srx_mat* m, double target, hipStream_t stream);   // in-place write-back from the row sums in m->d_row_sum
 int32_t launch_normalize(srx_mat* m, double target, bool do_norm, bool do_log, hipStream_t stream = nullptr,
                          bool precise = false, int wgs_per_cu = 0);
 int32_t launch_row_sums(srx_mat* m, double* out = nullptr);     // out null: into m->d_row_sum
-int32_t ensure_moments_xf(srx_mat* m, RowXf xf);      // moments of the TRANSFORMED values from the raw matrix
+// rows.hip: the Row-direction halves of the statistics entry points
+int32_t row_number(srx_mat* m, uint32_t* out);
+int32_t row_stat(srx_mat* m, int which, double* out0, double* out1);
+int32_t row_qc(srx_mat* m, uint32_t* num, double* sum, double* var);
+// pca_form.hip: out[0..n] = exclusive scan of in[0..n), out[n] = total (also left in *total_dev)
+int32_t scan_exclusive(srx_ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d_out, int64_t** total_dev);
 inline void touch(srx_mat* m) { m->version++; m->pca.valid = false; }
 
 inline bool is_f32(const srx_mat* m) { return m->store == SRX_STORE_F32; }

@@ -11,10 +11,6 @@
 
 namespace srx {
 
-int32_t row_number(srx_mat* m, uint32_t* out);
-int32_t row_stat(srx_mat* m, int which, double* out0, double* out1);
-int32_t scan_exclusive(srx_ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d_out, int64_t** total_dev);
-
 // kept entries of every OLD row (0 for dropped rows); colmap == nullptr keeps every column
 __global__ __launch_bounds__(256) void k_subset_count(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
                                                       const uint8_t* __restrict__ rowmask,

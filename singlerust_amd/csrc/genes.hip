@@ -1,5 +1,6 @@
-// genes.hip — per-gene (column-direction) passes over the row-major CSR, and the statistics
-// entry points of the C ABI.
+// genes.hip — per-gene (column-direction) passes over the row-major CSR: the gene-tile structures, the moments / count /
+// min-max passes, the moments cache of a matrix, and the statistics entry points of the C ABI.  (The feature selection that
+// reads the moments: select.hip.)
 //
 // Per-gene accumulation from a CSR is a scatter: global atomics (one per non-zero, 3.3e9
 // for the 1.3M-cell config) are two orders of magnitude too slow, so the accumulators are
@@ -591,7 +592,7 @@ __global__ void k_col_scale(const int32_t* __restrict__ idx, T* __restrict__ val
 }
 
 static void tile_geometry(const srx_mat* m, int& n_tiles, int& tile_genes) {
-    uint64_t G = m->n_cols ? m->n_cols : 1;
+    const uint64_t G = at_least_one(m->n_cols);
     n_tiles = (int)((G + kMaxTileGenes - 1) / kMaxTileGenes);
     tile_genes = (int)((G + n_tiles - 1) / n_tiles);
 }
@@ -676,8 +677,6 @@ __global__ __launch_bounds__(COUNT ? 1024 : 256) void k_narrow16_tiles(const int
     }
 }
 
-__global__ void k_gene_count_reduce(const uint32_t* __restrict__ part, uint64_t n_cols, uint64_t n_blocks, uint32_t* __restrict__ cnt);
-
 template <bool WIDEN>
 static int32_t launch_narrow16_tiles(srx_mat* m, int nt, int tg, hipStream_t stream) {
     srx_ctx* ctx = m->ctx;
@@ -749,7 +748,7 @@ int32_t ensure_tiles(srx_mat* m) {
     if (m->n_tiles) return SRX_OK;
     int nt, tg;
     tile_geometry(m, nt, tg);
-    if (nt > 1) SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_tile_ptr, (size_t)(nt - 1) * (m->n_rows ? m->n_rows : 1) * sizeof(int64_t)));
+    if (nt > 1) SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_tile_ptr, (size_t)(nt - 1) * at_least_one(m->n_rows) * sizeof(int64_t)));
     if (m->n_rows > 0 && m->n_cols <= 65536) {
         SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_idx16, (m->nnz + 16) * sizeof(uint16_t)));
         SRX_TRY(launch_narrow16_tiles<false>(m, nt, tg, ctx->stream));
@@ -786,6 +785,17 @@ static int32_t block_geometry(const srx_mat* m, uint64_t& n_blocks, uint64_t& ro
     return SRX_OK;
 }
 
+// The storage x index-width dispatch of the per-gene passes: f(the values, typed by the storage) and f(the column indices:
+// the 16-bit mirror where the matrix has one); a pass over both nests the two.
+template <typename F>
+static int32_t by_values(const srx_mat* m, F&& f) {
+    return is_f32(m) ? f((float*)m->d_values) : f((double*)m->d_values);
+}
+template <typename F>
+static int32_t by_indices(const srx_mat* m, F&& f) {
+    return m->d_idx16 ? f((const uint16_t*)m->d_idx16) : f((const int32_t*)m->d_indices);
+}
+
 // This shard's (cnt, sum, sumsq) per gene and its row count, packed as 3G+1 doubles in a scratch buffer.
 // `xf`: moments of the transformed values ln_1p(v * scale_row) formed on the fly from the raw matrix.
 static int32_t local_moments(srx_mat* m, double** packed_out, RowXf xf = RowXf{}) {
@@ -795,8 +805,8 @@ static int32_t local_moments(srx_mat* m, double** packed_out, RowXf xf = RowXf{}
     uint64_t nb, rpb;
     SRX_TRY(block_geometry(m, nb, rpb));
     double *p_sum, *p_sq, *packed;
-    SRX_TRY(scratch(ctx, "mom_part_sum", nb * (G ? G : 1) * sizeof(double), (void**)&p_sum));
-    SRX_TRY(scratch(ctx, "mom_part_sq", nb * (G ? G : 1) * sizeof(double), (void**)&p_sq));
+    SRX_TRY(scratch(ctx, "mom_part_sum", nb * at_least_one(G) * sizeof(double), (void**)&p_sum));
+    SRX_TRY(scratch(ctx, "mom_part_sq", nb * at_least_one(G) * sizeof(double), (void**)&p_sq));
     SRX_TRY(scratch(ctx, "mom_packed", (3 * G + 1) * sizeof(double), (void**)&packed));
     // the per-gene counts depend on the sparsity pattern only: counted once per pattern (here, or by srx_matrix_prepare), kept
     // on the matrix (clones inherit them)
@@ -811,14 +821,14 @@ static int32_t local_moments(srx_mat* m, double** packed_out, RowXf xf = RowXf{}
     double fx_sum = 0.0, fx_sq = 0.0;
     if (xf.row_sum) {
         int lg = 0;
-        while ((1ull << lg) < (m->n_rows ? m->n_rows : 1)) ++lg;
+        while ((1ull << lg) < at_least_one(m->n_rows)) ++lg;
         fx_sum = std::ldexp(1.0, std::min(62 - 6 - lg, 44));
         fx_sq = std::ldexp(1.0, std::min(62 - 12 - lg, 38));
     }
     uint32_t* d_poison = nullptr;
     if (xf.row_sum) {
-        SRX_TRY(scratch(ctx, "mom_poison", (G ? G : 1) * sizeof(uint32_t), (void**)&d_poison));
-        SRX_HIP(ctx, hipMemsetAsync(d_poison, 0, (G ? G : 1) * sizeof(uint32_t), ctx->stream));
+        SRX_TRY(scratch(ctx, "mom_poison", at_least_one(G) * sizeof(uint32_t), (void**)&d_poison));
+        SRX_HIP(ctx, hipMemsetAsync(d_poison, 0, at_least_one(G) * sizeof(uint32_t), ctx->stream));
     }
     {
         ProfScope ps(ctx, SRX_K_MOMENTS, bytes);
@@ -829,21 +839,16 @@ static int32_t local_moments(srx_mat* m, double** packed_out, RowXf xf = RowXf{}
                                m->n_rows, G, m->n_tiles, m->tile_genes, rpb, xf.row_sum, xf.target, fx_sum, fx_sq, d_poison, p_sum, p_sq);
             return SRX_OK;
         };
-        auto pick = [&](auto tval, auto tidx, const auto* idxp, const auto* valp) -> int32_t {
-            using T = decltype(tval);
-            using I = decltype(tidx);
-            if (xf.row_sum && xf.write_back) return launch(k_gene_moments<T, I, true, true>, idxp, const_cast<T*>(valp));
-            if (xf.row_sum) return launch(k_gene_moments<T, I, true>, idxp, valp);
-            return launch(k_gene_moments<T, I, false>, idxp, valp);
-        };
-        if (is_f32(m)) {
-            if (m->d_idx16) SRX_TRY(pick(float{}, uint16_t{}, (const uint16_t*)m->d_idx16, (const float*)m->d_values));
-            else SRX_TRY(pick(float{}, int32_t{}, (const int32_t*)m->d_indices, (const float*)m->d_values));
-        } else {
-            if (m->d_idx16) SRX_TRY(pick(double{}, uint16_t{}, (const uint16_t*)m->d_idx16, (const double*)m->d_values));
-            else SRX_TRY(pick(double{}, int32_t{}, (const int32_t*)m->d_indices, (const double*)m->d_values));
-        }
-        hipLaunchKernelGGL(k_moments_reduce, dim3((unsigned)((G + 63) / 64 ? (G + 63) / 64 : 1)), dim3(64 * kRedSlices), 0, ctx->stream, p_sum, p_sq, G, nb,
+        SRX_TRY(by_values(m, [&](auto* vals) {
+            return by_indices(m, [&](const auto* idx) {
+                using T = std::remove_pointer_t<decltype(vals)>;
+                using I = std::remove_cv_t<std::remove_pointer_t<decltype(idx)>>;
+                if (xf.row_sum && xf.write_back) return launch(k_gene_moments<T, I, true, true>, idx, vals);
+                if (xf.row_sum) return launch(k_gene_moments<T, I, true>, idx, (const T*)vals);
+                return launch(k_gene_moments<T, I, false>, idx, (const T*)vals);
+            });
+        }));
+        hipLaunchKernelGGL(k_moments_reduce, dim3((unsigned)at_least_one((G + 63) / 64)), dim3(64 * kRedSlices), 0, ctx->stream, p_sum, p_sq, G, nb,
                            m->n_rows, (const uint32_t*)m->d_cnt_pat, fx_sum != 0.0 ? 1.0 / fx_sum : 0.0,
                            fx_sq != 0.0 ? 1.0 / fx_sq : 0.0, (const uint32_t*)d_poison, packed);
     }
@@ -859,8 +864,8 @@ int32_t ensure_pattern_counts(srx_mat* m) {
     srx_ctx* ctx = m->ctx;
     SRX_TRY(ensure_tiles(m));
     const uint64_t G = m->n_cols;
-    if (!m->d_cnt_pat) SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_cnt_pat, (G ? G : 1) * sizeof(uint32_t)));
-    SRX_HIP(ctx, hipMemsetAsync(m->d_cnt_pat, 0, (G ? G : 1) * sizeof(uint32_t), ctx->stream));
+    if (!m->d_cnt_pat) SRX_HIP(ctx, dev_malloc(ctx, (void**)&m->d_cnt_pat, at_least_one(G) * sizeof(uint32_t)));
+    SRX_HIP(ctx, hipMemsetAsync(m->d_cnt_pat, 0, at_least_one(G) * sizeof(uint32_t), ctx->stream));
     if (m->n_rows && m->nnz) {
         uint64_t nb, rpb;
         SRX_TRY(block_geometry(m, nb, rpb));
@@ -869,12 +874,12 @@ int32_t ensure_pattern_counts(srx_mat* m) {
         const dim3 grid((unsigned)(nb * m->n_tiles));
         const size_t lds = (size_t)m->tile_genes * 4;
         ProfScope ps(ctx, SRX_K_MOMENTS, (double)m->nnz * (m->d_idx16 ? 2.0 : 4.0) + (double)(m->n_rows + 1) * 8.0 + (double)G * 4.0);
-        if (m->d_idx16)
-            hipLaunchKernelGGL(k_gene_count<uint16_t>, grid, dim3(kMomThreads), lds, ctx->stream, m->d_indptr, m->d_tile_ptr,
-                               (const uint16_t*)m->d_idx16, m->n_rows, G, m->n_tiles, m->tile_genes, rpb, part);
-        else
-            hipLaunchKernelGGL(k_gene_count<int32_t>, grid, dim3(kMomThreads), lds, ctx->stream, m->d_indptr, m->d_tile_ptr,
-                               (const int32_t*)m->d_indices, m->n_rows, G, m->n_tiles, m->tile_genes, rpb, part);
+        by_indices(m, [&](const auto* idx) {
+            using I = std::remove_cv_t<std::remove_pointer_t<decltype(idx)>>;
+            hipLaunchKernelGGL(k_gene_count<I>, grid, dim3(kMomThreads), lds, ctx->stream, m->d_indptr, m->d_tile_ptr, idx, m->n_rows, G,
+                               m->n_tiles, m->tile_genes, rpb, part);
+            return SRX_OK;
+        });
         hipLaunchKernelGGL(k_gene_count_reduce, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)part, G, nb,
                            m->d_cnt_pat);
         SRX_HIP(ctx, hipGetLastError());
@@ -900,96 +905,86 @@ int32_t moments_accumulate(srx_mat* m, double* d_acc, RowXf xf) {
     return SRX_OK;
 }
 
+// ---- the moments cache of a matrix: d_cnt / d_sum / d_sq and n_rows_global, valid while moments_version == version ----
 static int32_t alloc_moments(srx_mat* m) {
     srx_ctx* ctx = m->ctx;
-    const uint64_t G = m->n_cols;
+    SRX_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t G = at_least_one(m->n_cols);
     if (!m->d_cnt) {
-        SRX_HIP(ctx, hipMalloc((void**)&m->d_cnt, (G ? G : 1) * sizeof(uint64_t)));
-        SRX_HIP(ctx, hipMalloc((void**)&m->d_sum, (G ? G : 1) * sizeof(double)));
-        SRX_HIP(ctx, hipMalloc((void**)&m->d_sq, (G ? G : 1) * sizeof(double)));
+        SRX_HIP(ctx, hipMalloc((void**)&m->d_cnt, G * sizeof(uint64_t)));
+        SRX_HIP(ctx, hipMalloc((void**)&m->d_sum, G * sizeof(double)));
+        SRX_HIP(ctx, hipMalloc((void**)&m->d_sq, G * sizeof(double)));
     }
     return SRX_OK;
 }
 
-// All-reduces `d_packed` (3G+1 doubles, this rank's totals) and installs it as the global moments of `m`.
-int32_t moments_install(srx_mat* m, double* d_packed) {
+// The one route from this rank's packed totals (3G+1 doubles: cnt | sum | sq | rows) to the global moments of `m`: ONE
+// all-reduce across the row shards, the unpack into d_cnt / d_sum / d_sq, and n_rows_global.  `n_is_local`: the packed row
+// count is m->n_rows (a resident matrix), so a single-rank context needs no read-back for N; false: N always comes from the
+// packed buffer (a backed accumulator's n_rows is not the global count).  Does not stamp moments_version.
+static int32_t reduce_unpack_moments(srx_mat* m, double* d_packed, bool n_is_local) {
     srx_ctx* ctx = m->ctx;
     const uint64_t G = m->n_cols;
-    SRX_HIP(ctx, hipSetDevice(ctx->device));
-    SRX_TRY(alloc_moments(m));
     SRX_TRY(allreduce_f64(ctx, d_packed, 3 * G + 1));
     hipLaunchKernelGGL(k_moments_unpack, dim3((unsigned)((G + 255) / 256 + 1)), dim3(256), 0, ctx->stream, d_packed, G,
                        m->d_cnt, m->d_sum, m->d_sq);
     SRX_HIP(ctx, hipGetLastError());
-    double ng = 0.0;
-    SRX_TRY(d2h(ctx, &ng, d_packed + 3 * G, sizeof(double)));
-    m->n_rows_global = (uint64_t)ng;
-    m->moments_version = m->version;
+    if (n_is_local && !ctx->comm && !ctx->host_allreduce) {
+        m->n_rows_global = m->n_rows;
+    } else {
+        double ng = 0.0;
+        SRX_TRY(d2h(ctx, &ng, d_packed + 3 * G, sizeof(double)));
+        m->n_rows_global = (uint64_t)ng;
+    }
+    return SRX_OK;
+}
+
+void moments_adopt(srx_mat* m) { m->moments_version = m->version; }
+void moments_retire(srx_mat* m) { m->moments_version = 0; }       // (a version is never 0)
+
+// All-reduces `d_packed` (3G+1 doubles, this rank's totals) and installs it as the global moments of `m`.
+int32_t moments_install(srx_mat* m, double* d_packed) {
+    SRX_TRY(alloc_moments(m));
+    SRX_TRY(reduce_unpack_moments(m, d_packed, false));
+    moments_adopt(m);
     return SRX_OK;
 }
 
 int32_t ensure_moments(srx_mat* m) {
-    srx_ctx* ctx = m->ctx;
     if (m->moments_version == m->version) return SRX_OK;
-    SRX_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t G = m->n_cols;
     SRX_TRY(alloc_moments(m));
     double* packed;
     SRX_TRY(local_moments(m, &packed));
-    // one all-reduce for (cnt, sum, sumsq, N) across the row shards
-    SRX_TRY(allreduce_f64(ctx, packed, 3 * G + 1));
-    hipLaunchKernelGGL(k_moments_unpack, dim3((unsigned)((G + 255) / 256 + 1)), dim3(256), 0, ctx->stream, packed, G,
-                       m->d_cnt, m->d_sum, m->d_sq);
-    SRX_HIP(ctx, hipGetLastError());
-    if (ctx->comm || ctx->host_allreduce) {
-        double ng = 0.0;
-        SRX_TRY(d2h(ctx, &ng, packed + 3 * G, sizeof(double)));
-        m->n_rows_global = (uint64_t)ng;
-    } else {
-        m->n_rows_global = m->n_rows;
-    }
-    m->moments_version = m->version;
+    SRX_TRY(reduce_unpack_moments(m, packed, true));
+    moments_adopt(m);
     return SRX_OK;
 }
 
-// Moments of the transformed values y = ln_1p(v * scale_row), computed from the RAW matrix (pipeline): installed as the
-// moments of the version the in-place write-back is about to create (the caller bumps the version right after).
-int32_t ensure_moments_xf(srx_mat* m, RowXf xf) {
-    srx_ctx* ctx = m->ctx;
-    SRX_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t G = m->n_cols;
+// Moments of the transformed values y = ln_1p(v * scale_row), computed from the RAW matrix (pipeline).  With xf.write_back
+// the pass stores y in place, and from the moment its kernel is in the stream X is booked as normalised + log1p'd (`stored`
+// true) — whatever fails behind it (all-reduce, read-back), the caller must not transform X a second time: the bookkeeping of
+// normalize_total + log1p (scale/mod.rs:74-83 -> F64, transform/mod.rs:43-55) belongs to that moment.  The moments are those
+// of the f64 transform, not of the values as stored: the caller adopts them for the solve that follows and retires them after.
+int32_t ensure_moments_xf(srx_mat* m, RowXf xf, bool* stored) {
+    *stored = false;
     SRX_TRY(alloc_moments(m));
     double* packed;
     SRX_TRY(local_moments(m, &packed, xf));
     if (xf.write_back) {
-        // the pass above has stored the transformed values in place: whatever fails from here on (all-reduce, read-back), X
-        // must not be transformed a second time by the pipeline's epilogue — the bookkeeping of normalize_total + log1p
-        // (scale/mod.rs:74-83 -> F64, transform/mod.rs:43-55) belongs to the moment the kernel is in the stream
-        m->lazy_pending = false;
         m->dtype = SRX_F64;
         touch(m);
+        *stored = true;
     }
-    SRX_TRY(allreduce_f64(ctx, packed, 3 * G + 1));
-    hipLaunchKernelGGL(k_moments_unpack, dim3((unsigned)((G + 255) / 256 + 1)), dim3(256), 0, ctx->stream, packed, G,
-                       m->d_cnt, m->d_sum, m->d_sq);
-    SRX_HIP(ctx, hipGetLastError());
-    if (ctx->comm || ctx->host_allreduce) {
-        double ng = 0.0;
-        SRX_TRY(d2h(ctx, &ng, packed + 3 * G, sizeof(double)));
-        m->n_rows_global = (uint64_t)ng;
-    } else {
-        m->n_rows_global = m->n_rows;
-    }
-    return SRX_OK;
+    return reduce_unpack_moments(m, packed, true);
 }
 
-static int32_t fetch_moments(srx_mat* m, std::vector<uint64_t>& cnt, std::vector<double>& sum, std::vector<double>& sq) {
+// The global per-column moments of the STORED matrix (for a CSC matrix: per cell) on the host; null destinations are skipped.
+static int32_t fetch_moments(srx_mat* m, uint64_t* cnt, double* sum, double* sq) {
     SRX_TRY(ensure_moments(m));
     const uint64_t G = m->n_cols;
-    cnt.resize(G); sum.resize(G); sq.resize(G);
-    SRX_TRY(d2h(m->ctx, cnt.data(), m->d_cnt, G * sizeof(uint64_t)));
-    SRX_TRY(d2h(m->ctx, sum.data(), m->d_sum, G * sizeof(double)));
-    SRX_TRY(d2h(m->ctx, sq.data(), m->d_sq, G * sizeof(double)));
+    if (cnt) SRX_TRY(d2h(m->ctx, cnt, m->d_cnt, G * sizeof(uint64_t)));
+    if (sum) SRX_TRY(d2h(m->ctx, sum, m->d_sum, G * sizeof(double)));
+    if (sq) SRX_TRY(d2h(m->ctx, sq, m->d_sq, G * sizeof(double)));
     return SRX_OK;
 }
 
@@ -1006,421 +1001,14 @@ void finalize_variance(const uint64_t* cnt, const double* sum, const double* sq,
     }
 }
 
-static int32_t gene_variances(srx_mat* m, std::vector<double>& var) {
-    std::vector<uint64_t> cnt;
-    std::vector<double> sum, sq;
-    SRX_TRY(fetch_moments(m, cnt, sum, sq));
-    var.resize(m->n_cols);
-    finalize_variance(cnt.data(), sum.data(), sq.data(), m->n_cols, var.data());
-    return SRX_OK;
-}
-
-// dim_red/mod.rs:135-140.  Rust's sort_by is stable; comparator b.partial_cmp(a) = descending.
-static int32_t select_hvg_host(srx_ctx* ctx, const std::vector<double>& var, uint64_t n, std::vector<uint64_t>& out) {
-    for (double v : var)
-        if (v != v) return fail(ctx, SRX_E_NAN, "%s", kNanVarianceMsg);
-    // stable descending order == the strict total order (variance desc, gene index asc), so a
-    // partial sort of the first n under that order gives exactly the stable sort's prefix
-    std::vector<uint64_t> order(var.size());
-    for (uint64_t j = 0; j < order.size(); ++j) order[j] = j;
-    uint64_t take = n < order.size() ? n : order.size();
-    auto before = [&](uint64_t a, uint64_t b) { return var[a] > var[b] || (var[a] == var[b] && a < b); };
-    std::nth_element(order.begin(), order.begin() + (take ? take - 1 : 0), order.end(), before);
-    std::sort(order.begin(), order.begin() + take, before);
-    out.assign(order.begin(), order.begin() + take);
-    return SRX_OK;
-}
-
-// ---- FeatureSelection::HighlyVariable(n) on the device (the pipeline's route: no host round trip) ----
-// Same semantics as select_hvg_host / dim_red/mod.rs:135-140: nz-only population variance in the reference's
-// operation order (csr.rs:179-185: no FMA contraction — explicit _rn intrinsics), stable descending order
-// (ties keep the ascending gene index), NaN -> status bit 1 (the reference panics).
-__global__ void k_gene_var(const uint64_t* __restrict__ cnt, const double* __restrict__ sum, const double* __restrict__ sq,
-                           uint64_t G, double* __restrict__ var, uint32_t* __restrict__ rank, uint32_t rank_init) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= G) return;
-    double v = 0.0;
-    if (cnt[j] > 0) {
-        const double c = (double)(uint32_t)cnt[j];
-        const double mean = __ddiv_rn(sum[j], c);
-        v = __dsub_rn(__ddiv_rn(sq[j], c), __dmul_rn(mean, mean));
-    }
-    var[j] = v;
-    rank[j] = rank_init;          // (candidate route: 0xffffffff = not a candidate; full ranking: the partial ranks start at 0)
-}
-
-// rank of every gene under (variance desc, index asc) by counting.  Block (x, y): genes 256 x .. 256 x + 255
-// against the comparison slice y (kRankTile variances staged in LDS, read as broadcast b128 pairs); a tile
-// wholly before the block's genes wins ties (>=), wholly after loses them (>), only the tile holding the
-// block's own genes needs the index compare.  Partial ranks are summed with integer atomics (exact, any order).
-constexpr int kRankTile = 2048;
-// one (block of 256 genes, comparison tile) pair of the full ranking; `tile`: kRankTile doubles of LDS; all 256 threads
-__device__ __forceinline__ void full_rank_pair(const double* __restrict__ var, uint32_t G, uint32_t* __restrict__ rank_out, uint32_t bx,
-                                               uint32_t by, double* tile) {
-    const uint32_t j = bx * 256 + threadIdx.x;
-    const uint32_t base = by * kRankTile;
-    for (uint32_t e = threadIdx.x; e < kRankTile; e += 256) tile[e] = base + e < G ? var[base + e] : -INFINITY;
-    __syncthreads();
-    if (j < G) {
-        const double mine = var[j];
-        const uint32_t j_lo = bx * 256, j_hi = j_lo + 255;
-        uint32_t rank = 0;
-        if (base + kRankTile - 1 < j_lo) {                       // every gene of the tile precedes every gene of the block
-#pragma unroll 8
-            for (int e = 0; e < kRankTile; ++e) rank += tile[e] >= mine ? 1u : 0u;
-        } else if (base > j_hi) {
-#pragma unroll 8
-            for (int e = 0; e < kRankTile; ++e) rank += tile[e] > mine ? 1u : 0u;
-        } else {
-#pragma unroll 4
-            for (int e = 0; e < kRankTile; ++e) {
-                const double o = tile[e];
-                rank += (o > mine || (o == mine && base + e < j)) ? 1u : 0u;
-            }
-        }
-        atomicAdd(&rank_out[j], rank);
-    }
-    __syncthreads();                                             // (the tile is re-filled by the caller's next pair)
-}
-__global__ __launch_bounds__(256) void k_hvg_rank(const double* __restrict__ var, uint32_t G, uint32_t* __restrict__ rank_out) {
-    __shared__ double tile[kRankTile];
-    full_rank_pair(var, G, rank_out, blockIdx.x, blockIdx.y, tile);
-}
-
-// ---- the same ranks for the genes that can be selected only --------------------------------------------------------------
-// HighlyVariable(n) needs the ranks below n.  A threshold taken from a SAMPLE of the variances (512 of them, the sample
-// quantile n / G pushed down by four standard deviations of a sample quantile) leaves ~n + 10 % of G candidates; they are
-// ranked among themselves, every gene below the threshold keeps rank 0xffffffff.  If the sample misled (fewer than n
-// candidates: probability ~3e-5 per call; more than `cap`, the size the candidate kernel is launched for; NaN variances)
-// the full ranking runs instead — decided on the device.
-// O(M^2) instead of O(G^2) comparisons: 173 -> ~25 us at 28k genes, n = 2000.
-constexpr int kRankSample = 512;
-constexpr int kSelThreads = 1024;
-// One workgroup: the threshold from the sample, the candidate list (gene ids in any order: the ranks are a strict total order),
-// rank_out[candidate] = 0, and the decision: `counter` = number of candidates M if n <= M <= cap, else 0xffffffff with
-// rank_out zeroed for EVERY gene — the full ranking takes over in k_rank_selected.  (Round 5: threshold, gather, the fallback's
-// reset and its early-exit launch were four kernels of 5-17 us each on the step's critical path.)
-__global__ __launch_bounds__(kSelThreads) void k_hvg_candidates(const double* __restrict__ var, uint32_t G, uint32_t n, uint32_t cap,
-                                                                uint32_t* __restrict__ counter, uint32_t* __restrict__ cand,
-                                                                uint32_t* __restrict__ rank_out,
-                                                                int force_miss /* test switch: a threshold nothing reaches */) {
-    __shared__ double sv[kRankSample];
-    __shared__ double s_thr;
-    __shared__ uint32_t s_cnt;
-    const uint32_t S = G < (uint32_t)kRankSample ? G : (uint32_t)kRankSample;
-    const uint32_t t = threadIdx.x, lane = t & 63;
-    if (t < (uint32_t)kRankSample) sv[t] = t < S ? var[(uint64_t)t * G / S] : -INFINITY;
-    if (t == 0) {
-        s_thr = force_miss ? INFINITY : -INFINITY;      // every gene a candidate unless a sample element says otherwise
-        s_cnt = 0u;
-    }
-    __syncthreads();
-    if (!force_miss && S == (uint32_t)kRankSample) {          // (uniform)
-        const double q = (double)n / (double)G;
-        const double kq = (q + 4.0 * sqrt(q * (1.0 - q) / (double)S)) * (double)S + 1.0;
-        // the sample in descending order (bitonic network in LDS, 256 compare-exchanges per step: ranking every element against
-        // every other one took 17 us of one workgroup); equal values may stand in any order — the threshold is a VALUE
-        for (uint32_t size = 2; size <= (uint32_t)kRankSample; size <<= 1)
-            for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-                if (t < (uint32_t)kRankSample / 2) {
-                    const uint32_t lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                    const bool desc = (lo & size) == 0;
-                    const double a = sv[lo], b = sv[hi];
-                    if (desc ? a < b : a > b) {
-                        sv[lo] = b;
-                        sv[hi] = a;
-                    }
-                }
-                __syncthreads();
-            }
-        if (t == 0 && kq < (double)(S - 1)) s_thr = sv[(uint32_t)kq];       // (NaN variances in the sample: whatever stands there — the status word reports them)
-    }
-    __syncthreads();
-    const double thr = s_thr;
-    constexpr int kAhead = 8;                 // variances of eight rounds in flight (a round per load was 0.5 us of latency each)
-    for (uint32_t base = 0; base < G; base += kSelThreads * kAhead) {
-        double v[kAhead];
-#pragma unroll
-        for (int a = 0; a < kAhead; ++a) {
-            const uint32_t j = base + a * kSelThreads + t;
-            v[a] = j < G ? var[j] : -INFINITY;
-        }
-#pragma unroll
-        for (int a = 0; a < kAhead; ++a) {
-            const uint32_t j = base + a * kSelThreads + t;
-            const bool in = j < G && v[a] >= thr;
-            const unsigned long long m = __ballot(in);
-            uint32_t at = 0;
-            if (lane == 0 && m) at = atomicAdd(&s_cnt, (uint32_t)__popcll(m));
-            at = __shfl(at, 0, 64);
-            if (in) {
-                cand[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = j;
-                rank_out[j] = 0u;
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t M = s_cnt;
-    const bool ok = M >= n && M <= cap;
-    if (!ok)
-        for (uint32_t j = t; j < G; j += kSelThreads) rank_out[j] = 0u;          // the full ranking's partial sums start from zero
-    if (t == 0) *counter = ok ? M : 0xffffffffu;
-}
-// rank_out[gene] for every candidate: candidates above it under (variance desc, index asc).  Pair (x, y): candidates 256 x ..
-// against the y-th tile of kCandTile of the candidate list; partial ranks are summed with integer atomics.  Where the
-// candidates cannot be used (`counter` = 0xffffffff: fewer than n, more than the list the launch was sized for, NaN variances)
-// the same workgroups walk the pairs of the FULL ranking instead.
-constexpr int kCandTile = 128;      // (512: 44 us per launch at c3 — each thread walks a whole tile; 128: four times the workgroups, a quarter of the walk)
-__global__ __launch_bounds__(256) void k_rank_selected(const double* __restrict__ var, uint32_t G, const uint32_t* __restrict__ counter,
-                                                       const uint32_t* __restrict__ cand, uint32_t* __restrict__ rank_out) {
-    __shared__ double tile[kRankTile];
-    const uint32_t M = *counter;
-    if (M == 0xffffffffu) {
-        const uint32_t gb = (G + 255) / 256, gy = (G + kRankTile - 1) / kRankTile;
-        for (uint32_t p = blockIdx.y * gridDim.x + blockIdx.x; p < gb * gy; p += gridDim.x * gridDim.y)
-            full_rank_pair(var, G, rank_out, p % gb, p / gb, tile);
-        return;
-    }
-    double* tv = tile;
-    uint32_t* ti = reinterpret_cast<uint32_t*>(tile + kCandTile);
-    const uint32_t base = blockIdx.y * kCandTile;
-    if (blockIdx.x * 256 >= M || base >= M) return;           // (uniform)
-    for (uint32_t e = threadIdx.x; e < kCandTile; e += 256) {
-        const uint32_t g = base + e < M ? cand[base + e] : 0xffffffffu;
-        ti[e] = g;
-        tv[e] = g != 0xffffffffu ? var[g] : -INFINITY;
-    }
-    __syncthreads();
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= M) return;
-    const uint32_t gi = cand[i];
-    const double mine = var[gi];
-    uint32_t rank = 0;
-#pragma unroll 4
-    for (int e = 0; e < kCandTile; ++e) {
-        const double o = tv[e];
-        rank += (o > mine || (o == mine && ti[e] < gi)) ? 1u : 0u;
-    }
-    if (rank) atomicAdd(&rank_out[gi], rank);
-}
-
-// One workgroup: selection bitmask + per-word prefix counts (what the compaction kernels read), the selected genes in
-// selection order, and the per-slot (ascending gene order) centring / scaling vectors of the PCA from the all-cells moments
-// (pca/mod.rs:87-91: mean = sum/N, var = sumsq/N - mean^2, ddof 0); trace = sum_s dinv_s^2 ss_s, summed in a fixed tree.
-// `rank`: per gene its place in the selection, 0xffffffff for none — the HighlyVariable(n) ranking or the positions in an
-// explicit list (select_list).  `gene_var` null: no NaN test (an explicit list: the reference only panics on NaN when it
-// sorts); `sum` null: no vectors.  LDS: the bits and prefix counts are made in LDS (n_words <= 2048: G <= 65536), else in
-// place in global memory.
-constexpr int kSelLdsWords = 2048;
-template <bool LDS>
-__global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict__ rank, const double* __restrict__ gene_var,
-                                                     const double* __restrict__ sum,
-                                                     const double* __restrict__ sq, uint32_t G, uint32_t take, int n_words,
-                                                     double n_cells, int center, int scale, int32_t* __restrict__ sel_rank,
-                                                     int* __restrict__ status, uint32_t* __restrict__ bits,
-                                                     uint32_t* __restrict__ prefix, double* __restrict__ mu,
-                                                     double* __restrict__ sd, double* __restrict__ dinv,
-                                                     double* __restrict__ trace) {
-    __shared__ uint32_t s_bits[LDS ? kSelLdsWords : 1], s_pre[LDS ? kSelLdsWords : 1], s_wave[16];
-    __shared__ double s_tr[1024];
-    __shared__ int s_nan;
-    uint32_t* const wbits = LDS ? s_bits : bits;
-    uint32_t* const wpre = LDS ? s_pre : prefix;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    if (t == 0) s_nan = 0;
-    __syncthreads();
-    // the gene of rank r < take goes to sel_rank[r] and into the mask (two words per thread); a NaN variance anywhere is the
-    // status word's bit 0 (the reference panics there: select_hvg_host)
-    bool nan = false;
-    constexpr int kAhead = 8;                 // (the loads of eight rounds in flight)
-    for (uint32_t base = 0; base < (uint32_t)n_words * 32; base += 1024 * kAhead) {       // (a wave: 64 consecutive genes = two mask words)
-        uint32_t rk[kAhead];
-        double v[kAhead];
-#pragma unroll
-        for (int a = 0; a < kAhead; ++a) {
-            const uint32_t g = base + a * 1024 + t;
-            rk[a] = g < G ? rank[g] : 0xffffffffu;
-            v[a] = g < G && gene_var ? gene_var[g] : 0.0;
-        }
-#pragma unroll
-        for (int a = 0; a < kAhead; ++a) {
-            const uint32_t g = base + a * 1024 + t;
-            nan |= v[a] != v[a];
-            const bool in = rk[a] < take;      // (a gene behind G: 0xffffffff, never below `take`)
-            if (in) sel_rank[rk[a]] = (int32_t)g;
-            const unsigned long long m = __ballot(in);
-            if (lane == 0 && (g >> 5) < (uint32_t)n_words) wbits[g >> 5] = (uint32_t)m;
-            if (lane == 32 && (g >> 5) < (uint32_t)n_words) wbits[g >> 5] = (uint32_t)(m >> 32);
-        }
-    }
-    if (nan) s_nan = 1;
-    __syncthreads();
-    // exclusive scan of the popcounts, 2048 words per round: per-thread pair, wave scan, wave totals
-    uint32_t carry = 0;
-    for (int w0 = 0; w0 < n_words; w0 += 2 * 1024) {
-        const int w = w0 + 2 * t;
-        uint32_t b[2] = {0u, 0u};
-        if (w < n_words) b[0] = wbits[w];
-        if (w + 1 < n_words) b[1] = wbits[w + 1];
-        const uint32_t c0 = (uint32_t)__popc(b[0]), c1 = (uint32_t)__popc(b[1]);
-        uint32_t inc = c0 + c1;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) s_wave[wv] = inc;
-        __syncthreads();
-        uint32_t before = carry;
-        for (int q = 0; q < wv; ++q) before += s_wave[q];
-        const uint32_t excl = before + inc - (c0 + c1);
-        if (w < n_words) wpre[w] = excl;
-        if (w + 1 < n_words) wpre[w + 1] = excl + c0;
-        for (int q = 0; q < 16; ++q) carry += s_wave[q];
-        __syncthreads();
-    }
-    // never more than `take` selected genes, whatever the flags say (a ranking broken by NaN variances can flag more): the
-    // passes over the matrix test the bit alone and the compacted columns must stay below `take`
-    for (int w = t; w < n_words; w += 1024) {
-        uint32_t b_ = wbits[w];
-        const uint32_t e = wpre[w], room = e < take ? take - e : 0u;
-        while ((uint32_t)__popc(b_) > room) b_ &= ~(1u << (31 - __clz((int)b_)));
-        wbits[w] = b_;
-    }
-    __syncthreads();
-    if constexpr (LDS)
-        for (int w = t; w < n_words; w += 1024) {
-            bits[w] = s_bits[w];
-            prefix[w] = s_pre[w];
-        }
-    double tr = 0.0;
-    for (uint32_t g = t; sum && g < G; g += 1024) {
-        const uint32_t w = wbits[g >> 5], bit = 1u << (g & 31);
-        if (!(w & bit)) continue;
-        const uint32_t s = wpre[g >> 5] + (uint32_t)__popc(w & (bit - 1u));
-        const double mean = sum[g] / n_cells;
-        double var = sq[g] / n_cells - mean * mean;
-        if (var < 0) var = 0;
-        const double std_ = sqrt(var);
-        mu[s] = (center || scale) ? mean : 0.0;          // pca/mod.rs:85-119: stored only if center || scale
-        sd[s] = scale ? std_ : 1.0;
-        const double di = (scale && std_ > 0) ? 1.0 / std_ : 1.0;      // zero-variance column: std treated as 1
-        dinv[s] = di;
-        double ss = center ? (sq[g] - n_cells * mean * mean) : sq[g];
-        if (ss < 0) ss = 0;
-        tr += di * di * ss;
-    }
-    s_tr[t] = tr;
-    __syncthreads();
-    for (int half = 512; half > 0; half >>= 1) {
-        if (t < half) s_tr[t] += s_tr[t + half];
-        __syncthreads();
-    }
-    if (t == 0) {
-        *trace = s_tr[0];
-        *status = s_nan;
-    }
-}
-
-// The buffers of a selection of `take` of G genes (context scratch, read by the PCA that follows: a backed session keeps them
-// from its selection to its solve), and the per-gene rank table k_sel_finish reads.
-static int32_t sel_buffers(srx_ctx* ctx, uint64_t G, uint64_t take, SelDev& out, uint32_t** d_rank) {
-    const int n_words = (int)((G + 31) / 32);
-    double* d_f;
-    SRX_TRY(scratch(ctx, "hvg_rankv", (G ? G : 1) * sizeof(uint32_t), (void**)d_rank));
-    SRX_TRY(scratch(ctx, "hvg_rank", (take ? take : 1) * sizeof(int32_t), (void**)&out.d_sel_rank));
-    SRX_TRY(scratch(ctx, "pca_selbits", (size_t)(2 * n_words ? 2 * n_words : 1) * sizeof(uint32_t), (void**)&out.d_bits));
-    SRX_TRY(scratch(ctx, "hvg_f", (3 * (take ? take : 1) + 8) * sizeof(double), (void**)&d_f));
-    SRX_TRY(scratch(ctx, "hvg_status", 256, (void**)&out.d_status));
-    out.d_mu = d_f;
-    out.d_sd = d_f + take;
-    out.d_dinv = d_f + 2 * take;
-    out.d_trace = d_f + 3 * take;
-    out.k = (int)take;
-    out.n_words = n_words;
-    return SRX_OK;
-}
-
-static int32_t launch_sel_finish(srx_mat* m, const uint32_t* d_rank, const double* d_var, bool vectors, int center, int scale,
-                                 const SelDev& out) {
-    srx_ctx* ctx = m->ctx;
-    auto kern = out.n_words <= kSelLdsWords ? k_sel_finish<true> : k_sel_finish<false>;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, d_rank, d_var, vectors ? m->d_sum : nullptr, m->d_sq,
-                       (uint32_t)m->n_cols, (uint32_t)out.k, out.n_words, (double)m->n_rows_global, center, scale, out.d_sel_rank,
-                       out.d_status, out.d_bits, out.d_bits + out.n_words, out.d_mu, out.d_sd, out.d_dinv, out.d_trace);
-    SRX_HIP(ctx, hipGetLastError());
-    return SRX_OK;
-}
-
-// the device ranking's envelope: G <= 65536 (the fallback rank kernel is O(G^2)) and take <= kDevSelMaxK (what it is tested in)
-bool hvg_on_device(uint64_t n, uint64_t n_cols) {
-    return n > 0 && std::min(n, n_cols) <= kDevSelMaxK && n_cols <= 65536;
-}
-
-// Device-side HighlyVariable(n): fills the scratch buffers named in sel_buffers; nothing is read back.
-int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, SelDev& out) {
-    srx_ctx* ctx = m->ctx;
-    SRX_TRY(ensure_moments(m));
+int32_t gene_variances(srx_mat* m, std::vector<double>& var) {
     const uint64_t G = m->n_cols;
-    const uint64_t take = n < G ? n : G;
-    double* d_var;
-    uint32_t* d_rank;
-    SRX_TRY(scratch(ctx, "hvg_var", (G ? G : 1) * sizeof(double), (void**)&d_var));
-    SRX_TRY(sel_buffers(ctx, G, take, out, &d_rank));
-    const unsigned gb = (unsigned)((G + 255) / 256 ? (G + 255) / 256 : 1);
-    const unsigned gy = (unsigned)((G + kRankTile - 1) / kRankTile ? (G + kRankTile - 1) / kRankTile : 1);
-    static const bool full_rank = getenv("SRX_HVG_FULL_RANK") != nullptr;       // A/B switch: rank every gene
-    const bool all = full_rank || take == 0 || G < (uint64_t)kRankSample;
-    // four launches (round 4: eleven): variances; threshold + candidate list + the decision; the ranks; mask, vectors, status
-    hipLaunchKernelGGL(k_gene_var, dim3(gb), dim3(256), 0, ctx->stream, m->d_cnt, m->d_sum, m->d_sq, G, d_var, d_rank, all ? 0u : 0xffffffffu);
-    if (all) {
-        hipLaunchKernelGGL(k_hvg_rank, dim3(gb, gy), dim3(256), 0, ctx->stream, d_var, (uint32_t)G, d_rank);
-    } else {
-        uint32_t* d_cand;
-        SRX_TRY(scratch(ctx, "hvg_cand", ((G ? G : 1) + 8) * sizeof(uint32_t), (void**)&d_cand));
-        uint32_t* d_counter = d_cand + G + 4;
-        static const int force_miss = getenv("SRX_HVG_FORCE_MISS") ? 1 : 0;       // exercises the device-side fallback
-        const uint32_t cap = (uint32_t)std::min<uint64_t>(G, std::max<uint64_t>(4 * take, 4096));
-        hipLaunchKernelGGL(k_hvg_candidates, dim3(1), dim3(kSelThreads), 0, ctx->stream, d_var, (uint32_t)G, (uint32_t)take, cap, d_counter, d_cand,
-                           d_rank, force_miss);
-        hipLaunchKernelGGL(k_rank_selected, dim3((cap + 255) / 256, (cap + kCandTile - 1) / kCandTile), dim3(256), 0, ctx->stream, d_var,
-                           (uint32_t)G, d_counter, d_cand, d_rank);
-    }
-    return launch_sel_finish(m, d_rank, d_var, true, center, scale, out);
-}
-
-// An explicit list: its rank table is the position of every gene in the list, so that the selection comes out in the
-// caller's order (1.2 MB to upload at 300 000 columns).  Needs the global moments of `m` where `vectors`.
-int32_t select_list(srx_mat* m, const uint64_t* genes, uint64_t k, int center, int scale, SelDev& out, bool vectors) {
-    srx_ctx* ctx = m->ctx;
-    const uint64_t G = m->n_cols;
-    std::vector<uint32_t> rank(G, 0xffffffffu);
-    for (uint64_t s = 0; s < k; ++s) {
-        const uint64_t g = genes ? genes[s] : s;
-        if (g >= G) return fail(ctx, SRX_E_BOUNDS, "selected feature index %llu out of bounds (n_vars = %llu)",
-                                (unsigned long long)g, (unsigned long long)G);
-        if (rank[g] != 0xffffffffu) return fail(ctx, SRX_E_ARG, "selected feature index %llu appears twice", (unsigned long long)g);
-        rank[g] = (uint32_t)s;
-    }
-    uint32_t* d_rank;
-    SRX_TRY(sel_buffers(ctx, G, k, out, &d_rank));
-    SRX_TRY(h2d(ctx, d_rank, rank.data(), G * sizeof(uint32_t)));
-    return launch_sel_finish(m, d_rank, nullptr, vectors, center, scale, out);
-}
-
-int32_t row_number(srx_mat* m, uint32_t* out);
-int32_t row_qc(srx_mat* m, uint32_t* num, double* sum, double* var);
-int32_t row_stat(srx_mat* m, int which, double* out0, double* out1);
-
-int32_t hvg_list_host(srx_mat* m, uint64_t n, std::vector<uint64_t>& out) {
-    std::vector<double> var;
-    if (m->csc) {                                // compute_variance(Column) of a CSC matrix: csc.rs:164-177 (NaN for an empty gene)
-        var.resize(m->n_rows);
-        SRX_TRY(row_stat(m, 1, var.data(), nullptr));
-    } else {
-        SRX_TRY(gene_variances(m, var));
-    }
-    return select_hvg_host(m->ctx, var, n, out);
+    std::vector<uint64_t> cnt(G);
+    std::vector<double> sum(G), sq(G);
+    SRX_TRY(fetch_moments(m, cnt.data(), sum.data(), sq.data()));
+    var.resize(G);
+    finalize_variance(cnt.data(), sum.data(), sq.data(), G, var.data());
+    return SRX_OK;
 }
 
 }  // namespace srx
@@ -1429,20 +1017,10 @@ using namespace srx;
 
 extern "C" {
 
-// per-column moments of the STORED matrix (for a CSC matrix: per cell)
-static int32_t stored_col_moments(srx_mat* m, uint64_t* cnt, double* sum, double* sumsq) {
-    SRX_TRY(ensure_moments(m));
-    const uint64_t G = m->n_cols;
-    if (cnt) SRX_TRY(d2h(m->ctx, cnt, m->d_cnt, G * sizeof(uint64_t)));
-    if (sum) SRX_TRY(d2h(m->ctx, sum, m->d_sum, G * sizeof(double)));
-    if (sumsq) SRX_TRY(d2h(m->ctx, sumsq, m->d_sq, G * sizeof(double)));
-    return SRX_OK;
-}
-
 int32_t srx_gene_moments(srx_mat* m, uint64_t* cnt, double* sum, double* sumsq) {
     if (!m) return fail(nullptr, SRX_E_ARG, "null matrix");
     if (m->csc) return fail(m->ctx, SRX_E_FORMAT, "srx_gene_moments walks cells: convert the CSC matrix with srx_matrix_to_csr");
-    return stored_col_moments(m, cnt, sum, sumsq);
+    return fetch_moments(m, cnt, sum, sumsq);
 }
 
 int32_t srx_compute_number(srx_mat* m, int32_t direction, uint32_t* out) {
@@ -1452,7 +1030,7 @@ int32_t srx_compute_number(srx_mat* m, int32_t direction, uint32_t* out) {
     if (direction == SRX_ROW) return row_number(m, out);
     if (direction != SRX_COLUMN) return fail(m->ctx, SRX_E_ARG, "bad direction %d", direction);
     std::vector<uint64_t> cnt(m->n_cols);
-    SRX_TRY(stored_col_moments(m, cnt.data(), nullptr, nullptr));
+    SRX_TRY(fetch_moments(m, cnt.data(), nullptr, nullptr));
     for (uint64_t j = 0; j < m->n_cols; ++j) out[j] = (uint32_t)cnt[j];   // reference counts in u32
     return SRX_OK;
 }
@@ -1463,7 +1041,7 @@ int32_t srx_compute_sum(srx_mat* m, int32_t direction, double* out) {
     direction = eff_dir(m, direction);           // csc.rs:71-95
     if (direction == SRX_ROW) return row_stat(m, 0, out, nullptr);
     if (direction != SRX_COLUMN) return fail(m->ctx, SRX_E_ARG, "bad direction %d", direction);
-    return stored_col_moments(m, nullptr, out, nullptr);
+    return fetch_moments(m, nullptr, out, nullptr);
 }
 
 int32_t srx_compute_variance(srx_mat* m, int32_t direction, double* out) {
@@ -1508,10 +1086,10 @@ int32_t srx_compute_qc_variables(srx_mat* m, uint32_t* num_per_cell, uint32_t* n
     }
     // per gene: ONE column pass (the cached moments)
     if (num_per_gene || expr_per_gene || variance_per_gene || std_dev_per_gene) {
-        std::vector<uint64_t> cnt;
-        std::vector<double> sum, sq;
-        SRX_TRY(fetch_moments(m, cnt, sum, sq));
         const uint64_t G = m->n_cols;
+        std::vector<uint64_t> cnt(G);
+        std::vector<double> sum(G), sq(G);
+        SRX_TRY(fetch_moments(m, cnt.data(), sum.data(), sq.data()));
         if (num_per_gene) for (uint64_t j = 0; j < G; ++j) num_per_gene[j] = (uint32_t)cnt[j];
         if (expr_per_gene) memcpy(expr_per_gene, sum.data(), G * sizeof(double));
         if (variance_per_gene || std_dev_per_gene) {
@@ -1539,7 +1117,7 @@ int32_t srx_compute_min_max(srx_mat* m, int32_t direction, double* mn, double* m
     SRX_TRY(ensure_tiles(m));
     const uint64_t G = m->n_cols;
     unsigned long long* d;
-    SRX_TRY(scratch(ctx, "minmax_keys", 2 * (G ? G : 1) * sizeof(unsigned long long), (void**)&d));
+    SRX_TRY(scratch(ctx, "minmax_keys", 2 * at_least_one(G) * sizeof(unsigned long long), (void**)&d));
     unsigned g1 = (unsigned)((G + 255) / 256 + 1);
     hipLaunchKernelGGL(k_fill_u64, dim3(g1), dim3(256), 0, ctx->stream, d, G, (unsigned long long)f64_key(INFINITY));
     hipLaunchKernelGGL(k_fill_u64, dim3(g1), dim3(256), 0, ctx->stream, d + G, G, (unsigned long long)f64_key(-INFINITY));
@@ -1547,15 +1125,13 @@ int32_t srx_compute_min_max(srx_mat* m, int32_t direction, double* mn, double* m
     SRX_TRY(block_geometry(m, nb, rpb));
     const size_t lds = (size_t)m->tile_genes * 16;
     dim3 grid((unsigned)(nb * m->n_tiles));
-    if (is_f32(m)) {
-        SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_gene_minmax<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_gene_minmax<float>), grid, dim3(kMomThreads), lds, ctx->stream, m->d_indptr, m->d_tile_ptr,
-                           m->d_indices, (const float*)m->d_values, m->n_rows, G, m->n_tiles, m->tile_genes, rpb, d, d + G);
-    } else {
-        SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_gene_minmax<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_gene_minmax<double>), grid, dim3(kMomThreads), lds, ctx->stream, m->d_indptr, m->d_tile_ptr,
-                           m->d_indices, (const double*)m->d_values, m->n_rows, G, m->n_tiles, m->tile_genes, rpb, d, d + G);
-    }
+    SRX_TRY(by_values(m, [&](auto* vals) -> int32_t {
+        using T = std::remove_pointer_t<decltype(vals)>;
+        SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_gene_minmax<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_gene_minmax<T>), grid, dim3(kMomThreads), lds, ctx->stream, m->d_indptr, m->d_tile_ptr,
+                           m->d_indices, (const T*)vals, m->n_rows, G, m->n_tiles, m->tile_genes, rpb, d, d + G);
+        return SRX_OK;
+    }));
     SRX_HIP(ctx, hipGetLastError());
     std::vector<unsigned long long> keys(2 * G);
     SRX_TRY(d2h(ctx, keys.data(), d, 2 * G * sizeof(unsigned long long)));
@@ -1575,25 +1151,14 @@ int32_t srx_normalize_total_inplace(srx_mat* m, double target_sum, int32_t direc
     uint64_t g = (m->nnz + 255) / 256;
     if (g < 1) g = 1;
     if (g > 8192) g = 8192;
-    if (is_f32(m))
-        hipLaunchKernelGGL((k_col_scale<float>), dim3((unsigned)g), dim3(256), 0, ctx->stream, m->d_indices,
-                           (float*)m->d_values, m->nnz, m->d_sum, target_sum);
-    else
-        hipLaunchKernelGGL((k_col_scale<double>), dim3((unsigned)g), dim3(256), 0, ctx->stream, m->d_indices,
-                           (double*)m->d_values, m->nnz, m->d_sum, target_sum);
+    by_values(m, [&](auto* vals) {
+        using T = std::remove_pointer_t<decltype(vals)>;
+        hipLaunchKernelGGL((k_col_scale<T>), dim3((unsigned)g), dim3(256), 0, ctx->stream, m->d_indices, vals, m->nnz, m->d_sum, target_sum);
+        return SRX_OK;
+    });
     SRX_HIP(ctx, hipGetLastError());
     m->dtype = SRX_F64;
     touch(m);
-    return SRX_OK;
-}
-
-int32_t srx_select_hvg(srx_mat* m, uint64_t n, uint64_t* idx_out, uint64_t* n_out) {
-    if (!m || !n_out) return fail(m ? m->ctx : nullptr, SRX_E_ARG, "null argument");
-    SRX_HIP(m->ctx, hipSetDevice(m->ctx->device));
-    std::vector<uint64_t> sel;
-    SRX_TRY(hvg_list_host(m, n, sel));
-    if (idx_out) memcpy(idx_out, sel.data(), sel.size() * sizeof(uint64_t));
-    *n_out = sel.size();
     return SRX_OK;
 }
 

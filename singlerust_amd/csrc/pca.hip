@@ -37,23 +37,11 @@
 
 namespace srx {
 
-// The in-place normalise + log1p of a matrix whose pipeline has been reading it raw (RowXf) and did not get as far as the
-// moments pass that stores the transformed values itself (an error on the way): from the row sums in m->d_row_sum, on the
-// context's stream.
-static int32_t launch_writeback(srx_mat* m) {
-    if (!m->lazy_pending) return SRX_OK;
-    m->lazy_pending = false;
-    // (the moments cached on the matrix are those of the f64 transform, not of the values as stored: the version bump of
-    //  launch_row_apply retires them — a later compute_variance sees what X holds)
-    return launch_row_apply(m, m->lazy_target, m->ctx->stream);
-}
-
 // Everything up to and including the scores, left in m->pca (device scores + small host vectors).
 // Either `hvg_n` > 0: FeatureSelection::HighlyVariable(hvg_n) ranked on the device (the pipeline's route: no host round trip
 // between the moments pass and the compaction; only inside hvg_on_device's envelope), or the list `sel` (nullptr = all
 // features, FeatureSelection::None).
-static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const srx_pca_opts* opts, uint64_t hvg_n = 0,
-                          RowXf xf = RowXf{}) {
+static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const srx_pca_opts* opts, uint64_t hvg_n = 0) {
     srx_ctx* ctx = m->ctx;
     SRX_HIP(ctx, hipSetDevice(ctx->device));
     if (m->csc) {
@@ -62,7 +50,7 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
         // dense matrix from either storage)
         srx_mat* t = nullptr;
         SRX_TRY(transpose_device(m, &t));
-        const int32_t rc = pca_device(t, sel, k64, opts, hvg_n, RowXf{});
+        const int32_t rc = pca_device(t, sel, k64, opts, hvg_n);
         std::swap(m->pca, t->pca);
         srx_matrix_free(t);
         return rc;
@@ -75,7 +63,7 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
                     (unsigned long long)G);
     if (!sel && hvg_n == 0) k64 = G;                                           // FeatureSelection::None, :154
     const int k = (int)(hvg_n > 0 ? std::min(hvg_n, G) : k64);
-    SRX_TRY(ensure_moments(m));                                                // also fixes n_rows_global
+    SRX_TRY(ensure_moments(m));                                                // for the selection below; also fixes n_rows_global
     const uint64_t Ng = m->n_rows_global;
     Resolved o;
     int l_act = 0;
@@ -96,7 +84,7 @@ static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const s
     RowMajor rm;
     Range r_compact("srx:compact");
     const bool need_t256 = o.solver == 2;
-    SRX_TRY(compact_selection(m, sd.d_bits, sd.n_words, k, rm, xf, o.solver == 1));
+    SRX_TRY(compact_selection(m, sd.d_bits, sd.n_words, k, rm, RowXf{}, o.solver == 1));      // (the stored values)
     if (need_t256) SRX_TRY(retile(m, rm, t256));
     return solve_and_stash(ctx, is_f32(m), &rm, 1, need_t256 ? &t256 : nullptr, nullptr, o, sd, l_act, Ng, rm.nnz, st);
 }
@@ -222,39 +210,21 @@ int32_t srx_pipeline(srx_mat* m, double target_sum, uint64_t n_hvg, const srx_pc
         return rc;
     }
     (void)hipEventRecord(ev[0], ctx->stream);
-    // normalize_total_inplace(target, Row) + log1p_transform_inplace.  CSR: the passes that follow read the RAW matrix
-    // and form y = ln_1p(v * scale_row) on the fly in f64 (RowXf) — so the per-gene moments behind HighlyVariable(n)
-    // are those of the reference's f64 values whatever the storage type — and the in-place write-back of y runs on the
-    // side stream beside the Gram kernel.  CSC (cells are columns): the two calls, then the stored values.
-    const bool lazy = !m->csc;
-    RowXf xf;
-    bool wrote_back = false;
+    // normalize_total_inplace(target, Row) + log1p_transform_inplace.  CSR: the row sums, then the moments pass reads the RAW
+    // matrix, forms y = ln_1p(v * scale_row) on the fly in f64 (RowXf) — so the per-gene moments behind HighlyVariable(n) are
+    // those of the reference's f64 values whatever the storage type — and stores y in place at the storage precision: every
+    // pass behind it reads the stored values.  CSC (cells are columns): the two calls, then the stored values.
+    bool stored = m->csc;       // the transform is no longer owed: the CSC route's own calls, or the moments pass once it is in the stream
     {
     Range r_("srx:normalize");
-    if (m->csc) rc = srx_normalize_log1p_inplace(m, target_sum, nullptr);
-    else {
-        rc = launch_row_sums(m);
-        xf.row_sum = m->d_row_sum;
-        xf.target = target_sum;
-        xf.write_back = true;
-        m->lazy_pending = true;
-        m->lazy_target = target_sum;
-    }
+    rc = m->csc ? srx_normalize_log1p_inplace(m, target_sum, nullptr) : launch_row_sums(m);
     }
     (void)hipEventRecord(ev[1], ctx->stream);
-    // per-gene moments of the transformed values (one pass, all-reduced across shards)
+    // per-gene moments of the transformed values (one pass, all-reduced across shards), adopted for pca_device's selection
     if (rc == SRX_OK && !m->csc) {
         Range r_("srx:gene_moments");
-        if (lazy) {
-            rc = ensure_moments_xf(m, xf);
-            if (xf.write_back && !m->lazy_pending) {
-                // X now holds the transformed values (ensure_moments_xf did the bookkeeping of the two in-place calls as soon
-                // as its kernel was in the stream, also when a later step of it failed): the passes below read them as stored
-                xf = RowXf{};
-                wrote_back = true;
-            }
-            if (rc == SRX_OK) m->moments_version = m->version;          // what pca_device's ensure_moments looks at
-        } else rc = ensure_moments(m);
+        rc = ensure_moments_xf(m, RowXf{m->d_row_sum, target_sum, true}, &stored);
+        if (rc == SRX_OK) moments_adopt(m);
     }
     (void)hipEventRecord(ev[2], ctx->stream);
     // FeatureSelection::HighlyVariable(n_hvg): on the device, inside pca_device (the selection is fetched with the
@@ -266,16 +236,18 @@ int32_t srx_pipeline(srx_mat* m, double target_sum, uint64_t n_hvg, const srx_pc
     (void)hipEventRecord(ev[3], ctx->stream);
     if (rc == SRX_OK) {
         Range r_("srx:pca");
-        rc = on_device ? pca_device(m, nullptr, 0, opts, n_hvg, xf) : pca_device(m, sel.data(), sel.size(), opts, 0, xf);
+        rc = on_device ? pca_device(m, nullptr, 0, opts, n_hvg) : pca_device(m, sel.data(), sel.size(), opts);
     }
-    // whatever happened above, X ends up normalised and log1p'd (the two in-place calls come first in the reference)
-    if (m->lazy_pending) {
-        const int32_t rc_wb = launch_writeback(m);
+    if (!stored) {
+        // whatever happened above, X ends up normalised and log1p'd (the two in-place calls come first in the reference): an
+        // error before the moments pass was in the stream — in place from the row sums in m->d_row_sum
+        const int32_t rc_wb = launch_row_apply(m, target_sum, ctx->stream);
         if (rc == SRX_OK) rc = rc_wb;
+    } else if (!m->csc) {
+        // the moments cached on the matrix are those of the f64 transform, not of the values as stored: retired (a later
+        // compute_variance sees what X holds)
+        moments_retire(m);
     }
-    // the moments cached on the matrix are those of the f64 transform, not of the values as stored: retired (a later
-    // compute_variance sees what X holds)
-    if (wrote_back) m->moments_version = m->version - 1;
     (void)hipEventRecord(ev[4], ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
     if (res) {

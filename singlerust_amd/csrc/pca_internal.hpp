@@ -156,10 +156,12 @@ struct Resolved {
 };
 
 
-// ---- genes.hip -------------------------------------------------------------------------------------
+// ---- select.hip (and, from genes.hip, the two things it needs beyond common.hpp) ---------------------
 // FeatureSelection::HighlyVariable(n) ranked on the host (the CSC variance for a CSC matrix): the route of srx_select_hvg, and of
 // the PCA drivers outside hvg_on_device's envelope, which pass the list on
 int32_t hvg_list_host(srx_mat* m, uint64_t n, std::vector<uint64_t>& out);
+// genes.hip: the nz-only population variance of every gene from the cached moments (csr.rs:179-185), on the host
+int32_t gene_variances(srx_mat* m, std::vector<double>& var);
 constexpr const char* kNanVarianceMsg = "NaN gene variance: called `Option::unwrap()` on a `None` value (partial_cmp)";
 // The selection of a PCA on the device, made by k_sel_finish from a per-gene rank table (context scratch buffers)
 struct SelDev {
@@ -171,11 +173,12 @@ struct SelDev {
 };
 // is FeatureSelection::HighlyVariable(n) ranked on the device (select_hvg_device)?  Else on the host, and passed on as a list
 bool hvg_on_device(uint64_t n, uint64_t n_cols);
+// needs the global moments of `m` (ensure_moments / moments_install: the callers have them for n_rows_global already)
 int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, SelDev& out);
 // an explicit list (`genes`: k distinct features below n_cols in the caller's order; null: every feature, k = n_cols),
 // validated; `vectors` false: the selection alone, the moments of `m` are not read
 int32_t select_list(srx_mat* m, const uint64_t* genes, uint64_t k, int center, int scale, SelDev& out, bool vectors = true);
-// E: int32_t column indices or GramPk<VT> records
+// genes.hip.  E: int32_t column indices or GramPk<VT> records
 template <typename E>
 int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const E* idx, uint64_t n_rows, int n_tiles, int tile_genes,
                         int64_t* tp);
@@ -185,7 +188,6 @@ int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const E* idx, uint6
 //  only the blocks are wanted)
 int32_t gram_plan(srx_ctx* ctx, int k, uint64_t n_rows, GramPlan& g, double entries_per_cell = 0.0, int entry_bytes = 0);
 int grid_rows(const srx_ctx* ctx, uint64_t n_rows, int rows_per_block);
-int32_t scan_exclusive(srx_ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d_out, int64_t** total_dev);
 // `d_sel`: n_words selection bits followed by n_words prefix counts, on the device (the compacted column of a gene is its rank
 // among the selected genes in ascending gene order).  Makes the row-major records, their row order (rm.perm) and, with
 // `want_recs`, the Gram kernel's record counts.

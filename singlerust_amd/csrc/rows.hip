@@ -392,7 +392,7 @@ int32_t launch_row_apply(srx_mat* m, double target, hipStream_t stream) {
 }
 
 // Row sums of the current values into m->d_row_sum (the first step of the pipeline: the per-gene passes apply the
-// normalise + log1p transform on the fly from them, the in-place write-back follows on the side stream), or into `out`
+// normalise + log1p transform on the fly from them, the moments pass among them storing the result in place), or into `out`
 // (n_rows f64: srx_pca_transform, which leaves the query's own buffers alone).
 int32_t launch_row_sums(srx_mat* m, double* out) {
     srx_ctx* ctx = m->ctx;
