@@ -36,7 +36,8 @@ extern "C" {
                                   Purely additive entry points leave the version as it is and are detected by symbol:
                                   srx_pca_model_* / srx_pca_transform (fitted-PCA projection) and srx_knn_result /
                                   srx_knn_points (kernel class 11) came that way at 6, as did srx_neighbors_* / srx_graph_*
-                                  (kernel class 12) */
+                                  (kernel class 12) and srx_louvain / srx_louvain_csr / srx_graph_labels_fetch (no class of
+                                  their own: the time is in srx_louvain_info.ms) */
 
 typedef struct srx_ctx srx_ctx;   /* one GPU + stream + (optional) RCCL communicator      */
 typedef struct srx_mat srx_mat;   /* device-resident CSR (the `X` of an IMAnnData)        */
@@ -457,6 +458,62 @@ enum { SRX_GRAPH_DISTANCES = 0, SRX_GRAPH_CONNECTIVITIES = 1 };
 int32_t srx_graph_fetch(srx_graph* g, int32_t which, uint64_t* indptr, uint32_t* indices, double* data);
 int32_t srx_graph_fetch_scales(srx_graph* g, double* rho, double* sigma);   /* n each */
 void    srx_graph_free(srx_graph* g);
+
+/* ---- Louvain communities of a symmetric weighted graph: what sc.tl.louvain / leiden give obs["louvain"] ----------
+ * Not in the reference.  The method is a parallel Louvain with synchronous sweeps, defined here; it is tested against this
+ * definition and, for quality, against networkx's louvain_communities.  Leiden's refinement phase is not part of it.
+ *
+ * Input: a symmetric graph W as CSR (u64 indptr, u32 indices ascending within a row, f64 weights > 0, no diagonal).
+ *   k_i = sum_j W_ij (plus the self weight of a coarse vertex),  2m = sum_i k_i,  gamma = resolution.
+ * Modularity of a labelling:  Q = sum_c [ in_c / 2m - gamma (tot_c / 2m)^2 ],  in_c = sum of W_ij over the ORDERED pairs
+ * inside c (a coarse vertex's self weight counts both directions, as S^T W S does),  tot_c = sum over i in c of k_i.
+ * A level starts from singletons and runs sweeps t = 0, 1, ...  In sweep t only the vertices with (i + t) even may move.
+ * Against the labelling and the tot_c as they stood BEFORE the sweep a vertex evaluates, for every community c among its
+ * neighbours and for its own (there it counts as removed),
+ *     g(c) = w_{i->c} - gamma k_i (tot_c - [c = c_i] k_i) / 2m
+ * and moves to the best c only if g(c) > g(own) strictly; ties between targets go to the lowest community id; a vertex
+ * alone in its community does not move into another singleton community with a LOWER id (no swap oscillation: of two
+ * lone neighbours only the lower-numbered one may join the other).  The level ends when two consecutive sweeps (both
+ * parities) move nothing, or after max_sweeps (a synchronous scheme can cycle; the labelling the last sweep left is the
+ * level's).  Then the communities become
+ * vertices: weights are summed, the weight inside a community becomes a self weight that takes part in k and tot but is
+ * never a "neighbour community"; levels repeat on the coarse graph.  A level whose labelling does not raise Q above the
+ * previous level's (for the first level: above the singletons') by more than min_gain is discarded and ends the run, so
+ * level_modularity is strictly increasing; the run also ends when a level moves nothing or at max_levels.
+ * Final labels number the communities 0, 1, ... by descending size, ties to the community with the smallest member
+ * (scanpy's convention).  Isolated vertices are communities of their own; n = 0 gives an empty result; a graph without
+ * edges gives singletons, Q = 0 and n_levels = 0.
+ * The result is bit-identical from call to call: every sum that atomics make is 64-bit fixed point at the scale
+ * 2^(60 - ceil(log2(2m))) — tot_c, the sums of Q, the weights of a long row per community, the coarse weights — and the run
+ * is refused (SRX_E_ARG) if 2m at that scale would reach 2^61.  tot_c and coarse weights therefore carry an absolute
+ * error of at most half a unit of 2m 2^-60 per summand; info.modularity agrees with an f64 evaluation of Q on the
+ * returned labels to about nnz 2^-53. */
+#define SRX_LOUVAIN_MAX_LEVELS 32
+typedef struct srx_louvain_opts {
+    double  resolution;   /* gamma; <= 0 or NaN: SRX_E_ARG; NULL opts = {1.0, 0.0, 0, 0}               */
+    double  min_gain;     /* a level must raise Q by more than this (default 0)                        */
+    int32_t max_levels;   /* 0 = SRX_LOUVAIN_MAX_LEVELS */
+    int32_t max_sweeps;   /* per level, 0 = 200 */
+} srx_louvain_opts;
+typedef struct srx_louvain_info {
+    uint64_t n, n_communities;
+    uint32_t n_levels, reserved_;
+    uint64_t sweeps, moves;                              /* over all kept levels */
+    double   modularity;                                 /* of the returned labels, f64 */
+    double   ms;                                         /* hipEvent time of the device work */
+    uint64_t level_communities[SRX_LOUVAIN_MAX_LEVELS];
+    double   level_modularity[SRX_LOUVAIN_MAX_LEVELS];
+} srx_louvain_info;
+/* The communities of the handle's connectivities, read where they lie (no host round trip; C is left untouched).  The
+ * labels stay on the device with the handle (srx_graph_labels_fetch); labels_out (n u32) and info may be NULL. */
+int32_t srx_louvain(srx_graph* g, const srx_louvain_opts* opts, uint32_t* labels_out, srx_louvain_info* info);
+/* The same on a caller-supplied symmetric graph.  Validated on the device, SRX_E_ARG with a message for: an index >= n, a
+ * diagonal entry, a row not strictly ascending, a weight that is <= 0, NaN or Inf, W_ij and W_ji not the same bits or not
+ * both present; also for an indptr that does not start at 0 or decreases, and a context with more than one rank. */
+int32_t srx_louvain_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* indices, const double* weights, uint64_t n,
+                        const srx_louvain_opts* opts, uint32_t* labels_out, srx_louvain_info* info);
+/* The last srx_louvain's labels, kept on the device (n u32).  SRX_E_ARG when none has run on the handle. */
+int32_t srx_graph_labels_fetch(srx_graph* g, uint32_t* labels_out);
 
 /* The raw operators the PCA is built from, for a caller-supplied 64-column panel (k x 64
  * row-major): y_out (n_rows x 64) = X[:, sel] * panel, t_out (k x 64) = X[:, sel]^T * y, and

@@ -821,6 +821,53 @@ pub mod processing_free {
                 out
             })
         }
+        /// Louvain communities of the cells (srx_neighbors_result, then srx_louvain on the graph where it lies): k-NN with
+        /// `n_neighbors` over the first `n_pcs` resident scores (0 = all), the connectivities, parallel Louvain at
+        /// `resolution` — all on the device.  Returns one label per cell, communities numbered by descending size, and Q.
+        pub fn louvain(adata: &IMAnnData, resolution: f64) -> anyhow::Result<(Vec<u32>, f64)> {
+            louvain_with(adata, resolution, 15, 0)
+        }
+        pub fn louvain_with(adata: &IMAnnData, resolution: f64, n_neighbors: usize, n_pcs: usize)
+                            -> anyhow::Result<(Vec<u32>, f64)> {
+            let kopts = SrxKnnOpts { k: n_neighbors as i32, n_dims: n_pcs as i32, include_self: 0, reserved: 0 };
+            let lopts = SrxLouvainOpts { resolution, min_gain: 0.0, max_levels: 0, max_sweeps: 0 };
+            with_resident(adata, |x| {
+                let mut g: *mut SrxGraph = null_mut();
+                x.ctx.check(unsafe { srx_neighbors_result(x.mat, &kopts, null_mut(), &mut g) })?;
+                let mut ginfo: SrxGraphInfo = unsafe { std::mem::zeroed() };
+                let mut info: SrxLouvainInfo = unsafe { std::mem::zeroed() };
+                let out = x.ctx.check(unsafe { srx_graph_info_get(g, &mut ginfo) }).and_then(|_| {
+                    let mut labels = vec![0u32; ginfo.n as usize];
+                    x.ctx.check(unsafe { srx_louvain(g, &lopts, labels.as_mut_ptr(), &mut info) })?;
+                    Ok((labels, info.modularity))
+                });
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        /// Louvain communities of a symmetric weighted graph the caller holds (srx_louvain_csr validates it on the device).
+        pub fn louvain_csr(w: &CsrMatrix<f64>, resolution: f64) -> anyhow::Result<(Vec<u32>, f64)> {
+            let n = w.nrows();
+            let indptr: Vec<u64> = w.row_offsets().iter().map(|&v| v as u64).collect();
+            let indices: Vec<u32> = w.col_indices().iter().map(|&v| v as u32).collect();
+            let lopts = SrxLouvainOpts { resolution, min_gain: 0.0, max_levels: 0, max_sweeps: 0 };
+            with_ctx(|c| {
+                let mut labels = vec![0u32; n];
+                let mut info: SrxLouvainInfo = unsafe { std::mem::zeroed() };
+                c.check(unsafe {
+                    srx_louvain_csr(c.0, indptr.as_ptr(), indices.as_ptr(), w.values().as_ptr(), n as u64, &lopts,
+                                    labels.as_mut_ptr(), &mut info)
+                })?;
+                Ok((labels, info.modularity))
+            })
+        }
+        /// The labels the last srx_louvain left with a graph handle (srx_graph_labels_fetch).
+        #[allow(dead_code)]
+        fn graph_labels(c: &Ctx, g: *mut SrxGraph, n: usize) -> anyhow::Result<Vec<u32>> {
+            let mut labels = vec![0u32; n];
+            c.check(unsafe { srx_graph_labels_fetch(g, labels.as_mut_ptr()) })?;
+            Ok(labels)
+        }
         fn graph_to_host(c: &Ctx, g: *mut SrxGraph) -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>)> {
             let mut info: SrxGraphInfo = unsafe { std::mem::zeroed() };
             c.check(unsafe { srx_graph_info_get(g, &mut info) })?;

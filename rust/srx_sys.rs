@@ -8,6 +8,7 @@ use std::os::raw::{c_char, c_void};
 pub const SRX_ABI_VERSION: i32 = 6;
 pub const SRX_UNIQUE_ID_BYTES: usize = 128;
 pub const SRX_KNN_MAX_DIMS: i32 = 128;
+pub const SRX_LOUVAIN_MAX_LEVELS: i32 = 32;
 pub const SRX_OK: i32 = 0;
 pub const SRX_E_ARG: i32 = -1;
 pub const SRX_E_DTYPE: i32 = -2;
@@ -165,6 +166,30 @@ pub struct SrxGraphInfo {      // `srx_graph_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxLouvainOpts {      // `srx_louvain_opts`
+    pub resolution: f64,
+    pub min_gain: f64,
+    pub max_levels: i32,
+    pub max_sweeps: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxLouvainInfo {      // `srx_louvain_info`
+    pub n: u64,
+    pub n_communities: u64,
+    pub n_levels: u32,
+    pub reserved: u32,
+    pub sweeps: u64,
+    pub moves: u64,
+    pub modularity: f64,
+    pub ms: f64,
+    pub level_communities: [u64; SRX_LOUVAIN_MAX_LEVELS as usize],
+    pub level_modularity: [f64; SRX_LOUVAIN_MAX_LEVELS as usize],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPipelineResult {      // `srx_pipeline_result`
     pub pca: SrxPcaInfo,
     pub ms_normalize: f64,
@@ -254,6 +279,11 @@ extern "C" {
     pub fn srx_graph_fetch(g: *mut SrxGraph, which: i32, indptr: *mut u64, indices: *mut u32, data: *mut f64) -> i32;
     pub fn srx_graph_fetch_scales(g: *mut SrxGraph, rho: *mut f64, sigma: *mut f64) -> i32;
     pub fn srx_graph_free(g: *mut SrxGraph);
+    pub fn srx_louvain(g: *mut SrxGraph, opts: *const SrxLouvainOpts, labels_out: *mut u32,
+                       info: *mut SrxLouvainInfo) -> i32;
+    pub fn srx_louvain_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,
+                           opts: *const SrxLouvainOpts, labels_out: *mut u32, info: *mut SrxLouvainInfo) -> i32;
+    pub fn srx_graph_labels_fetch(g: *mut SrxGraph, labels_out: *mut u32) -> i32;
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,

@@ -84,6 +84,19 @@ class GraphInfo(C.Structure):
                 ("max_row_nnz", C.c_uint64)]
 
 
+LOUVAIN_MAX_LEVELS = 32
+
+
+class LouvainOpts(C.Structure):
+    _fields_ = [("resolution", C.c_double), ("min_gain", C.c_double), ("max_levels", C.c_int32), ("max_sweeps", C.c_int32)]
+
+
+class LouvainInfo(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_communities", C.c_uint64), ("n_levels", C.c_uint32), ("reserved_", C.c_uint32),
+                ("sweeps", C.c_uint64), ("moves", C.c_uint64), ("modularity", C.c_double), ("ms", C.c_double),
+                ("level_communities", C.c_uint64 * LOUVAIN_MAX_LEVELS), ("level_modularity", C.c_double * LOUVAIN_MAX_LEVELS)]
+
+
 class SynthParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_rows_global", C.c_uint64), ("n_cols", C.c_uint64),
                 ("density", C.c_double), ("lib_sigma", C.c_double), ("type_decay", C.c_double),
@@ -161,6 +174,9 @@ _SIGS = {
     "srx_graph_fetch": (C.c_int32, [P, C.c_int32, P, P, P]),
     "srx_graph_fetch_scales": (C.c_int32, [P, P, P]),
     "srx_graph_free": (None, [P]),
+    "srx_louvain": (C.c_int32, [P, C.POINTER(LouvainOpts), P, C.POINTER(LouvainInfo)]),
+    "srx_louvain_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(LouvainOpts), P, C.POINTER(LouvainInfo)]),
+    "srx_graph_labels_fetch": (C.c_int32, [P, P]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),

@@ -31,27 +31,11 @@
 // Whatever order the atomics ran in, every stored row is sorted by column and every value depends only on its pair: the
 // result is bit-identical from call to call, and C[i, j] and C[j, i] are the same bits (fma(-a, b, a + b) is symmetric).
 #include "common.hpp"
+#include "graph_handle.hpp"
 #include "pca_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
-
-struct srx_graph {
-    srx_ctx* ctx = nullptr;
-    uint64_t n = 0;
-    uint32_t k = 0;
-    // one allocation: D (indptr, indices, data), the directed weights in D's order, rho, sigma
-    void* d_block = nullptr;
-    uint64_t* d_dptr = nullptr;
-    uint32_t* d_dind = nullptr;
-    double *d_ddat = nullptr, *d_a = nullptr, *d_rho = nullptr, *d_sigma = nullptr;
-    // a second one, sized once nnz is known: C
-    void* d_cblock = nullptr;
-    uint64_t* d_cptr = nullptr;
-    uint32_t* d_cind = nullptr;
-    double* d_cdat = nullptr;
-    srx_graph_info info{};
-};
 
 namespace srx {
 
@@ -613,11 +597,12 @@ int32_t srx_graph_fetch_scales(srx_graph* g, double* rho, double* sigma) {
 
 void srx_graph_free(srx_graph* g) {
     if (!g) return;
-    if (g->d_block || g->d_cblock) {
+    if (g->d_block || g->d_cblock || g->d_labels) {
         (void)hipSetDevice(g->ctx->device);
         (void)hipStreamSynchronize(g->ctx->stream);
         if (g->d_block) (void)hipFree(g->d_block);
         if (g->d_cblock) (void)hipFree(g->d_cblock);
+        if (g->d_labels) (void)hipFree(g->d_labels);
     }
     delete g;
 }

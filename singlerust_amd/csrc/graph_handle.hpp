@@ -1,0 +1,24 @@
+// graph_handle.hpp — the srx_graph handle of srx.h: built by graph.hip, read where it lies by the graph algorithms (louvain.hip).
+#pragma once
+
+#include "common.hpp"
+
+struct srx_graph {
+    srx_ctx* ctx = nullptr;
+    uint64_t n = 0;
+    uint32_t k = 0;
+    // one allocation: D (indptr, indices, data), the directed weights in D's order, rho, sigma
+    void* d_block = nullptr;
+    uint64_t* d_dptr = nullptr;
+    uint32_t* d_dind = nullptr;
+    double *d_ddat = nullptr, *d_a = nullptr, *d_rho = nullptr, *d_sigma = nullptr;
+    // a second one, sized once nnz is known: C
+    void* d_cblock = nullptr;
+    uint64_t* d_cptr = nullptr;
+    uint32_t* d_cind = nullptr;
+    double* d_cdat = nullptr;
+    srx_graph_info info{};
+    // the labels of the last srx_louvain on this handle (louvain.hip): n u32, allocated by the first call
+    uint32_t* d_labels = nullptr;
+    bool labels_valid = false;
+};

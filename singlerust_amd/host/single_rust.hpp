@@ -577,14 +577,42 @@ public:
         ctx_->check(srx_graph_fetch_scales(h_, n ? rho.data() : nullptr, n ? sigma.data() : nullptr));
         return {rho, sigma};
     }
+    // Louvain communities of the connectivities, read where they lie (srx_louvain): one label per cell, communities
+    // numbered by descending size; `info` (may be null) receives the call's srx_louvain_info
+    std::vector<std::uint32_t> louvain(double resolution = 1.0, srx_louvain_info* info = nullptr, double min_gain = 0.0,
+                                       int max_levels = 0, int max_sweeps = 0) const {
+        const srx_louvain_opts o{resolution, min_gain, max_levels, max_sweeps};
+        std::vector<std::uint32_t> labels(info_n());
+        ctx_->check(srx_louvain(h_, &o, labels.empty() ? nullptr : labels.data(), info));
+        return labels;
+    }
+    // the labels the last louvain() left on the device (srx_graph_labels_fetch)
+    std::vector<std::uint32_t> labels() const {
+        std::vector<std::uint32_t> labels(info_n());
+        ctx_->check(srx_graph_labels_fetch(h_, labels.empty() ? nullptr : labels.data()));
+        return labels;
+    }
     srx_graph* handle() const { return h_; }
 
 private:
     explicit Graph(Context& ctx) : ctx_(&ctx) {}
+    std::uint64_t info_n() const { return info().n; }
     Context* ctx_;
     srx_graph* h_ = nullptr;
     srx_knn_info knn_info_{};
 };
+// Louvain communities of any symmetric weighted graph (CSR, ascending columns, weights > 0, no diagonal): srx_louvain_csr
+inline std::vector<std::uint32_t> louvain_csr(Context& ctx, const std::vector<std::uint64_t>& indptr,
+                                              const std::vector<std::uint32_t>& indices, const std::vector<double>& weights,
+                                              double resolution = 1.0, srx_louvain_info* info = nullptr) {
+    if (indptr.empty() || indices.size() != weights.size() || indptr.back() != indices.size())
+        throw Error(SRX_E_ARG, "louvain_csr: indptr (n + 1), indices and weights (indptr[n] each) expected");
+    const srx_louvain_opts o{resolution, 0.0, 0, 0};
+    std::vector<std::uint32_t> labels(indptr.size() - 1);
+    ctx.check(srx_louvain_csr(ctx.handle(), indptr.data(), indices.empty() ? nullptr : indices.data(),
+                              weights.empty() ? nullptr : weights.data(), labels.size(), &o, labels.empty() ? nullptr : labels.data(), info));
+    return labels;
+}
 }  // namespace processing
 }  // namespace memory
 

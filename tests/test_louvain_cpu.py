@@ -1,0 +1,157 @@
+"""srx_louvain / srx_louvain_csr / srx_graph_labels_fetch without a GPU: exported and bound in every layer, the struct layout
+as the C compiler lays it out, a loud failure without a device (no CPU fallback), the kernels' gfx950 listings free of
+register spills and scratch, the host restatement against the golden quality and the known answers, and the golden file
+against a fresh networkx run where networkx is installed."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import louvain_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("srx_louvain", "srx_louvain_csr", "srx_graph_labels_fetch")
+KERNELS = ("k_louvain_check", "k_louvain_degree", "k_louvain_scale", "k_louvain_quant", "k_louvain_classify", "k_louvain_biglist",
+           "k_louvain_move", "k_louvain_move_big", "k_louvain_apply", "k_louvain_q_in", "k_louvain_q_tot", "k_louvain_flag",
+           "k_louvain_oldof", "k_louvain_members", "k_louvain_coarse", "k_louvain_unfix", "k_louvain_compose", "k_louvain_sizes",
+           "k_louvain_keys", "k_louvain_bitonic", "k_louvain_rank", "k_louvain_relabel")
+
+
+def test_louvain_symbols_are_exported_and_bound():
+    from singlerust_amd import _ffi
+    from singlerust_amd.memory import processing
+    lib = _ffi.lib()
+    header = open(os.path.join(ROOT, "include", "srx.h")).read()
+    rust = open(os.path.join(ROOT, "rust", "srx_sys.rs")).read()
+    shim = open(os.path.join(ROOT, "rust", "shim.rs")).read()
+    mirror = open(os.path.join(ROOT, "singlerust_amd", "host", "single_rust.hpp")).read()
+    for name in NEW:
+        assert hasattr(lib, name), name
+        assert name in _ffi.EXPORTS, name
+        assert re.search(r"\b%s\s*\(" % name, header), name
+        assert re.search(r"pub fn %s\(" % name, rust), name
+        assert re.search(r"\b%s\s*\(" % name, mirror), name
+        assert re.search(r"\b%s\s*\(" % name, shim), name
+    assert "pub struct SrxLouvainOpts" in rust and "pub struct SrxLouvainInfo" in rust
+    assert "pub const SRX_LOUVAIN_MAX_LEVELS: i32 = 32;" in rust
+    assert "pub fn louvain(adata: &IMAnnData, resolution: f64)" in shim
+    assert "louvain(double resolution" in mirror
+    assert callable(processing.louvain) and callable(processing.louvain_csr)
+    # additive: the ABI version and the number of profiling classes stay
+    assert re.search(r"#define\s+SRX_ABI_VERSION\s+6\b", header) and lib.srx_abi_version() == 6
+    assert re.search(r"SRX_K_COUNT_ = 13\b", header)
+    assert re.search(r"#define\s+SRX_LOUVAIN_MAX_LEVELS\s+32\b", header) and _ffi.LOUVAIN_MAX_LEVELS == 32
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "gen_rust_bindings.py"), "--check"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
+@pytest.mark.parametrize("cname,struct", [("srx_louvain_opts", "LouvainOpts"), ("srx_louvain_info", "LouvainInfo")])
+def test_louvain_struct_layout_matches_header(tmp_path, cname, struct):
+    """sizeof() and the field offsets of the ctypes mirrors equal what gcc lays out."""
+    from singlerust_amd import _ffi
+    st = getattr(_ffi, struct)
+    fields = [n for n, _ in st._fields_]
+    prog = ('#include <stdio.h>\n#include <stddef.h>\n#include "srx.h"\nint main(void){printf("%%zu", sizeof(%s));\n' % cname
+            + "".join('printf(" %%zu", offsetof(%s, %s));\n' % (cname, f) for f in fields) + "return 0;}\n")
+    src, exe = str(tmp_path / "t.c"), str(tmp_path / "t")
+    open(src, "w").write(prog)
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
+    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    assert got == [C.sizeof(st)] + [getattr(st, f).offset for f in fields]
+    assert C.sizeof(st) == {"LouvainOpts": 24, "LouvainInfo": 56 + 2 * 8 * 32}[struct]
+
+
+def test_louvain_fails_loudly_without_a_device():
+    """Null handles are SRX_E_ARG with a message; with no device visible nothing is computed on the host (a child process
+    with every device hidden, so the test means the same on a GPU machine)."""
+    from singlerust_amd import _ffi
+    lib = _ffi.lib()
+    ip, ix, w = np.array([0, 1, 2], np.uint64), np.array([1, 0], np.uint32), np.ones(2)
+    assert lib.srx_louvain(None, None, None, None) == _ffi.E_ARG
+    assert lib.srx_last_error(None)
+    assert lib.srx_louvain_csr(None, _ffi.ptr(ip), _ffi.ptr(ix), _ffi.ptr(w), 2, None, None, None) == _ffi.E_ARG
+    assert lib.srx_graph_labels_fetch(None, None) == _ffi.E_ARG
+    code = ("import numpy as np, singlerust_amd as sr\n"
+            "from singlerust_amd.memory.processing import louvain_csr\n"
+            "try:\n"
+            "    louvain_csr(sr.Context(0), (np.array([0, 1, 2], np.uint64), np.array([1, 0], np.uint32), np.ones(2)))\n"
+            "except sr.SrxError as e:\n"
+            "    print('refused', e.code, e)\n")
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1", PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("refused %d " % _ffi.E_HIP) and "no CPU fallback" in r.stdout, (r.stdout, r.stderr)
+
+
+def test_louvain_kernels_do_not_spill_registers(tmp_path):
+    """The gfx950 code-object metadata of every kernel of louvain.hip shows no VGPR / SGPR spill and no scratch."""
+    from singlerust_amd import build
+    assert "louvain.hip" in build.SOURCES
+    out = str(tmp_path / "louvain.s")
+    subprocess.check_call([build._hipcc(), *[f for f in build.FLAGS if f != "-Wall"], "-w", "-S", "--cuda-device-only", "-o", out,
+                           os.path.join(ROOT, "singlerust_amd", "csrc", "louvain.hip")], stderr=subprocess.DEVNULL)
+    meta = open(out).read()
+    seen, n_kernels = set(), 0
+    for m in re.finditer(r"\.name:\s+(\S*k_louvain_\S*)\n(.*?)\.wavefront_size", meta, flags=re.S):
+        body = m.group(2)
+        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", body).group(1))
+        sspill = int(re.search(r"\.sgpr_spill_count:\s+(\d+)", body).group(1))
+        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
+        assert spill == 0 and sspill == 0 and scratch == 0, f"{m.group(1)}: {spill} / {sspill} spilled V/SGPRs, {scratch} B of scratch"
+        n_kernels += 1
+        seen |= {k for k in KERNELS if re.search(r"\d%s(I|E|\b)" % k, m.group(1))}
+    assert seen == set(KERNELS), set(KERNELS) - seen
+    assert n_kernels == len(KERNELS) + 2                   # k_louvain_move<32> / <64>, k_louvain_coarse<false> / <true>
+
+
+# ---- the restatement -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["separated_3000", "separated_20011", "overlapping_6000", "karate_stored", "karate_unit"])
+def test_restatement_reaches_the_golden_quality(name):
+    """The quality rule of the GPU tests, on the host restatement: Q >= q_min - (q_max - q_min) over networkx's five seeds."""
+    W, planted = ref.fixture_graph(name)
+    labels, info = ref.louvain(W)
+    floor = ref.quality_floor(name)
+    print(name, info["modularity"], "floor", floor, info["level_communities"])
+    assert abs(info["modularity"] - ref.modularity(W, labels)) <= 1e-12
+    assert info["modularity"] >= floor
+    if name.startswith("separated"):
+        assert info["n_communities"] == 12 and ref.ari(labels, planted) == 1.0
+
+
+def test_restatement_known_answers():
+    labels, info = ref.louvain(ref.ring_of_cliques(8, 6))
+    assert np.array_equal(np.bincount(labels), [6] * 8) and abs(info["modularity"] - 0.8125) <= 1e-12
+    labels, info = ref.louvain(ref.two_cliques())
+    assert np.array_equal(labels, [1, 1, 1, 0, 0, 0, 0]) and abs(info["modularity"] - 4.0 / 9.0) <= 1e-12
+    labels, info = ref.louvain(ref.karate(False))
+    assert info["n_communities"] == 3 and abs(info["modularity"] - 0.434521) <= 1e-6
+    labels, info = ref.louvain(ref.karate(True))
+    assert info["n_communities"] == 4 and abs(info["modularity"] - 0.418803) <= 1e-6
+    import scipy.sparse as sp
+    labels, info = ref.louvain(sp.csr_matrix((5, 5)))
+    assert np.array_equal(labels, np.arange(5)) and info["modularity"] == 0.0 and info["n_levels"] == 0
+    labels, info = ref.louvain(sp.csr_matrix(np.array([[0, 0.7], [0.7, 0]])))
+    assert np.array_equal(labels, [0, 0]) and info["n_communities"] == 1
+    # a converged first level cannot be improved
+    W = ref.fixture_graph("separated_3000")[0]
+    l0, i0 = ref.louvain(W, max_levels=1)
+    assert i0["n_levels"] == 1 and ref.max_excess(W, l0) <= 0.0
+    assert ref.max_excess(W, np.arange(W.shape[0])) > 0.0
+
+
+def test_golden_file_matches_networkx():
+    """Where networkx imports, the golden file is regenerated and equals the committed one to 1e-9."""
+    pytest.importorskip("networkx")
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_louvain_golden as gen
+    have = ref.golden()
+    doc = gen.build()
+    assert doc["karate_edges"] == have["karate_edges"] and list(doc["fixtures"]) == list(have["fixtures"])
+    for name, f in doc["fixtures"].items():
+        g = have["fixtures"][name]
+        assert (f["n"], f["nnz"]) == (g["n"], g["nnz"])
+        for a, b in zip(f["seeds"], g["seeds"]):
+            assert a["seed"] == b["seed"] and a["n_communities"] == b["n_communities"] and abs(a["modularity"] - b["modularity"]) <= 1e-9
