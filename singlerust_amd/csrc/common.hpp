@@ -117,8 +117,8 @@ struct srx_ctx {
     bool graphs_off = false;                 // capture failed once (or SRX_NO_GRAPH): plain launches from then on
     bool capturing = false;                  // ProfScope and friends stay out of a capture
     double* pin_async = nullptr;             // kAsyncSlots x 8 doubles, pinned
-    // H2D workers of srx_matrix_upload / the backed sessions (ctx.hip): each owns a stream, two pinned staging
-    // buffers and two events, and moves its own contiguous share of an array
+    // transfer workers of srx_matrix_upload / the backed sessions and the large downloads (transfer.hip): each owns a
+    // stream, two pinned staging buffers and two events, and moves its own contiguous share of an array
     struct UpWorker {
         hipStream_t stream = nullptr;
         void* pin[2] = {nullptr, nullptr};
@@ -219,8 +219,10 @@ inline int32_t fail(srx_ctx* ctx, int32_t code, const char* fmt, ...) {
         if (rc__ != SRX_OK) return rc__;       \
     } while (0)
 
-// ---- scratch / staging ---------------------------------------------------------------------
+// ---- ctx.hip: named scratch buffers --------------------------------------------------------
 int32_t scratch(srx_ctx* ctx, const char* name, size_t bytes, void** out);
+
+// ---- transfer.hip: staging and the transfer workers ---------------------------------------
 int32_t pinned(srx_ctx* ctx, size_t bytes, void** out);
 int32_t d2h(srx_ctx* ctx, void* host, const void* dev, size_t bytes);   // via pinned, synchronises
 // the same small copy in two halves: `begin` queues it (pinned staging + an event), `end` waits for THAT event only — what the
@@ -229,6 +231,17 @@ int32_t d2h_begin(srx_ctx* ctx, const void* dev, size_t bytes);
 int32_t d2h_end(srx_ctx* ctx, void* host, size_t bytes);
 int32_t h2d(srx_ctx* ctx, void* dev, const void* host, size_t bytes);
 int32_t d2h_rows(srx_ctx* ctx, void* host, const void* dev, uint64_t rows, size_t width, size_t dev_pitch);   // strided rows -> dense
+// a whole array through the workers: `n` elements of elem_bytes, or with `narrow` u64 -> i32 / u16 (elem_bytes 4 / 2) with
+// *bad set by a value >= n_cols; the caller has drained what still uses `dst`
+int32_t parallel_h2d(srx_ctx* ctx, const void* src, void* dst, uint64_t n, bool narrow, size_t elem_bytes, uint64_t n_cols,
+                     bool* bad);
+void transfer_destroy(srx_ctx* ctx);     // the workers, the staging buffers and their events (srx_ctx_destroy)
+
+// ---- matrix.hip: the matrix handle ---------------------------------------------------------------
+int32_t upload_on(srx_ctx* ctx, const srx_csr* h, int32_t store, hipStream_t stream, srx_mat** out);
+hipError_t dev_malloc(srx_ctx* ctx, void** p, size_t bytes);     // hipMalloc, or a recycled buffer while ctx->pool_on
+void pool_clear(srx_ctx* ctx);
+int32_t promote_to_f64(srx_mat* m);                   // f32 storage -> f64 storage, values unchanged
 
 // ---- profiling -------------------------------------------------------------------------------
 struct ProfScope {
@@ -267,13 +280,9 @@ struct RowXf {
     double target = 0.0;
     bool write_back = false;      // moments pass only: store the transformed value in place (at the storage precision)
 };
-int32_t upload_on(srx_ctx* ctx, const srx_csr* h, int32_t store, hipStream_t stream, srx_mat** out);   // ctx.hip
 int32_t tiles_from_idx16(srx_mat* m, hipStream_t stream);     // genes.hip: 32-bit indices + gene-tile cuts from an uploaded 16-bit mirror
 inline uint64_t at_least_one(uint64_t n) { return n ? n : 1; }   // sizes of buffers and grids that must not be empty
-hipError_t dev_malloc(srx_ctx* ctx, void** p, size_t bytes);     // ctx.hip: hipMalloc, or a recycled buffer while ctx->pool_on
-void pool_clear(srx_ctx* ctx);
 int32_t ensure_tiles(srx_mat* m);
-int32_t promote_to_f64(srx_mat* m);                   // ctx.hip: f32 storage -> f64 storage, values unchanged
 int32_t ensure_pattern_counts(srx_mat* m);            // genes.hip
 // The per-gene moments cache of a matrix (genes.hip):
 int32_t ensure_moments(srx_mat* m);   // fills d_cnt/d_sum/d_sq (global) and n_rows_global for the current values
