@@ -487,7 +487,12 @@ void    srx_graph_free(srx_graph* g);
  * 2^(60 - ceil(log2(2m))) — tot_c, the sums of Q, the weights of a long row per community, the coarse weights — and the run
  * is refused (SRX_E_ARG) if 2m at that scale would reach 2^61.  tot_c and coarse weights therefore carry an absolute
  * error of at most half a unit of 2m 2^-60 per summand; info.modularity agrees with an f64 evaluation of Q on the
- * returned labels to about nnz 2^-53. */
+ * returned labels to about nnz 2^-53.
+ * Where every weight is a multiple of 2^-20 and 2m < 2^32, every k_i, tot_c, w_{i->c} and coarse weight is exact both in
+ * f64 and at these scales, and the result (labels, sweeps, moves, the communities of every level) is exactly that of this
+ * definition evaluated in f64 with g(c) computed as  w - gamma * k_i * t / 2m  from left to right, as long as no level's
+ * Q comes within 1e-9 of its keep-or-discard threshold; this is the condition the exact tests use
+ * (tests/test_louvain_exact_gpu.py). */
 #define SRX_LOUVAIN_MAX_LEVELS 32
 typedef struct srx_louvain_opts {
     double  resolution;   /* gamma; <= 0 or NaN: SRX_E_ARG; NULL opts = {1.0, 0.0, 0, 0}               */

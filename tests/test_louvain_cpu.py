@@ -155,3 +155,138 @@ def test_golden_file_matches_networkx():
         assert (f["n"], f["nnz"]) == (g["n"], g["nnz"])
         for a, b in zip(f["seeds"], g["seeds"]):
             assert a["seed"] == b["seed"] and a["n_communities"] == b["n_communities"] and abs(a["modularity"] - b["modularity"]) <= 1e-9
+
+
+# ---- the exact cases: what tests/test_louvain_exact_gpu.py presupposes ---------------------------------------------------------
+ALL_RUNS = ref.EXACT_RUNS + ref.prefix_runs() + [r[:2] for r in ref.guard_runs()]
+
+
+@pytest.mark.parametrize("name", sorted({r[0] for r in ALL_RUNS}))
+def test_exact_case_is_dyadic_and_valid(name):
+    """Every weight is a multiple of 2^-20 and 2m < 2^32 (so every sum of the definition is exact in f64 and in the device's
+    fixed point), and the graph passes what srx_louvain_csr checks."""
+    W = ref.exact_graph(name)
+    assert W.shape[0] == W.shape[1] and W.has_sorted_indices and W.data.dtype == np.float64
+    assert np.array_equal(np.rint(W.data * ref.DYADIC), W.data * ref.DYADIC) and (W.data > 0).all()
+    assert W.data.sum() < 2.0 ** 32
+    rows = np.repeat(np.arange(W.shape[0]), np.diff(W.indptr))
+    assert (rows != W.indices).all()                                                 # no diagonal
+    inner = np.ones(W.nnz, dtype=bool)
+    inner[W.indptr[:-1][np.diff(W.indptr) > 0]] = False                              # first entry of every row
+    assert (np.diff(W.indices.astype(np.int64), prepend=-1)[inner] > 0).all()        # strictly ascending: no duplicates either
+    T = W.T.tocsr()
+    T.sort_indices()
+    assert np.array_equal(T.indptr, W.indptr) and np.array_equal(T.indices, W.indices)
+    assert np.array_equal(T.data.view(np.uint64), W.data.view(np.uint64))            # symmetric bit for bit
+
+
+@pytest.mark.parametrize("run", ALL_RUNS, ids=ref.run_id)
+def test_exact_run_decides_levels_with_a_margin(run):
+    """The one decision that is not bit for bit on the device, keeping or discarding a level, rests on its Q, which is held to
+    1e-9: no decision of the restatement is closer than 1e-8.  A condition on the inputs; a case that fails it gets another
+    seed."""
+    labels, info = ref.exact_result(*run)
+    W = ref.exact_graph(run[0])
+    print(ref.run_id(run), "n", W.shape[0], "nnz", W.nnz, "levels", info["level_communities"], "sweeps", info["level_sweeps"],
+          "moves", info["moves"], "Q", info["modularity"], "margin", info["min_margin"])
+    assert info["min_margin"] >= 1e-8
+    assert W.nnz * 2.0 ** -53 < 1e-9
+    assert abs(info["modularity"] - ref.modularity(W, labels, run[1].get("gamma", 1.0))) <= 1e-12
+
+
+def _first_coarse_graph(name):
+    W = ref.exact_graph(name)
+    zero = np.zeros(W.shape[0])
+    comm = ref._level(W, zero, 1.0, 200)[0]
+    return ref.aggregate(W, zero, comm)[:2]
+
+
+def _deciding_ties(W, k, twom, comm, gamma, active):
+    """A copy of ref.gains as far as the candidates' gains: the number of vertices whose best admissible gain beats their own
+    and is reached by two targets, so that only the lowest-id rule decides where they go."""
+    n = W.shape[0]
+    coo = W.tocoo()
+    rows, cols, data = coo.row.astype(np.int64), coo.col.astype(np.int64), coo.data
+    m = active[rows]
+    rows, cols, data = rows[m], cols[m], data[m]
+    tot = np.bincount(comm, weights=k, minlength=n)
+    size = np.bincount(comm, minlength=n)
+    key, inv = np.unique(rows * n + comm[cols], return_inverse=True)
+    w_to = np.bincount(inv.ravel(), weights=data, minlength=len(key))
+    ur, uc = key // n, key % n
+    own = comm[ur]
+    is_own = uc == own
+    w_own = np.zeros(n)
+    w_own[ur[is_own]] = w_to[is_own]
+    g_own = w_own - gamma * k * (tot[comm] - k) / twom
+    cand = ~is_own & ~((size[own] == 1) & (size[uc] == 1) & (uc < own))
+    ur, g = ur[cand], (w_to - gamma * k[ur] * tot[uc] / twom)[cand]
+    order = np.lexsort((-g, ur))
+    ur, g = ur[order], g[order]
+    second = np.zeros(len(ur), dtype=bool)
+    second[1:] = (ur[1:] == ur[:-1]) & (g[1:] == g[:-1])
+    first = np.ones(len(ur), dtype=bool)
+    first[1:] = ur[1:] != ur[:-1]
+    tied_best = np.zeros(len(ur), dtype=bool)
+    tied_best[:-1] = first[:-1] & second[1:]
+    return int((tied_best & (g > g_own[ur])).sum())
+
+
+def test_exact_cases_reach_what_they_are_there_for():
+    """So that a later edit of a generator cannot quietly empty the device test."""
+    for name in ("row_classes_last", "row_classes_first"):
+        lens = np.diff(ref.exact_graph(name).indptr)
+        assert set(ref.ROW_CLASS_LENGTHS) <= set(lens.tolist()), name
+    first, last = ref.exact_graph("row_classes_first"), ref.exact_graph("row_classes_last")
+    ne = len(ref.ROW_CLASS_LENGTHS)
+    assert tuple(np.diff(first.indptr)[:ne]) == tuple(np.diff(last.indptr)[-ne:]) == ref.ROW_CLASS_LENGTHS
+    # the second level of coarse_long_rows: rows of every class, with self weights
+    Wc, selfc = _first_coarse_graph("coarse_long_rows")
+    lens = np.diff(Wc.indptr)
+    print("coarse_long_rows level 2:", Wc.shape[0], "vertices, rows of", lens.min(), "to", lens.max(), "entries")
+    assert (lens > 64).any() and (lens <= 64).any() and (selfc[lens > 64] > 0).any()
+    info = ref.exact_result("coarse_long_rows", {})[1]
+    assert info["n_levels"] >= 2
+    # chain_300k: more coarse ids than one bitmap pass of the aggregation holds
+    info = ref.exact_result("chain_300k", {})[1]
+    assert info["level_communities"][0] > 2 ** 17 and info["n_levels"] >= 2
+    # ties_int: a level that runs into max_sweeps, an early end by min_gain, and exact ties that only the lowest id decides
+    info = ref.exact_result("ties_int", {})[1]
+    assert 200 in info["level_sweeps"]
+    early = ref.exact_result("ties_int", {"min_gain": ref.TIES_INT_MIN_GAIN})[1]
+    assert 0 < early["n_levels"] < info["n_levels"]
+    assert [ref.exact_result("ties_int", {"max_levels": m})[1]["n_levels"] for m in (1, 2, 3)] == [1, 2, 3]
+    for name in ("ties_int", "unit"):
+        W = ref.exact_graph(name)
+        k = np.asarray(W.sum(axis=1)).ravel()
+        comm, ids, ties = np.arange(W.shape[0], dtype=np.int64), np.arange(W.shape[0]), 0
+        for t in range(4):
+            active = (ids + t) % 2 == 0
+            ties += _deciding_ties(W, k, k.sum(), comm, 1.0, active)
+            v, c, g, g_own = ref.gains(W, k, k.sum(), comm, 1.0, active)
+            comm = comm.copy()
+            comm[v[g > g_own[v]]] = c[g > g_own[v]]
+        print(name, "vertices moved by the lowest-id rule in the first four sweeps:", ties)
+        assert ties > 0
+
+
+def test_guard_cases_by_hand():
+    """The restatement on the small graphs whose outcome the singleton guard and the lowest-id rule decide, against labels worked
+    out by hand from include/srx.h.  The traces (communities by the id they carry during the level):
+      path_2 (0-1-2, 2m = 4): sweep 0: 0 joins 1 (g = 1 - 1*2/4 > 0); 2 may not join the lower singleton 1 -> {0,1}{2}.  Sweep 1:
+        1 stays (g(own) = g({2}) = 0.5).  Sweep 2: 2 joins {0,1} (0.25 > 0).  One community.
+      path_3 (2m = 6): sweep 0: 0 joins 1; 2 may not join 1 and joins 3 -> {0,1}{2,3}; nothing beats that (0.667 against 0).
+      path_4 (2m = 8): sweep 0: 0 joins 1, 2 joins 3, 4 may not join 3 -> {0,1}{2,3}{4}.  Sweep 1: 3 joins 4 (0.75 > 0.5)
+        -> {0,1}{2}{3,4}.  Sweep 2: 2, alone, meets g({0,1}) = g({3,4}) = 0.25: the lower id, {0,1} -> {0,1,2}{3,4}.
+      star_hub_last (hub 4, 2m = 8): sweep 0: 0 and 2 join the hub, which may not join its lower singletons.  Sweep 1: 1 and 3.
+      star_hub_first (hub 0): sweep 0: the hub meets four equal gains and joins 1, the lowest; 2 and 4 may not join 0.  Then
+        3, then 2 and 4, join {0,1}.
+      tie_third: sweep 0: 0 joins 2 (2 and 4 are barred from their lower singletons).  Sweep 1: 1, alone, meets g({0,2}) =
+        g({4}) = 12: the lower id, {0,2}.  Sweep 2: 4 joins.  Vertex 3 is isolated."""
+    for name, opts, want in ref.guard_runs():
+        labels, info = ref.exact_result(name, opts)
+        assert np.array_equal(labels, want), (name, opts, labels, want)
+    assert [ref.exact_result(n, {})[1][k] for n in ("path_2", "path_4", "star_hub_last", "star_hub_first") for k in ("sweeps", "moves")] \
+        == [5, 2, 5, 4, 4, 4, 5, 4]
+    info = ref.exact_result("karate_unit", {})[1]
+    assert info["level_communities"] == [10, 5, 4] and info["level_sweeps"] == [200, 4, 3]
