@@ -149,11 +149,11 @@ def test_fused_normalize_log1p_equals_two_calls(ctx):
 
 
 def test_long_rows_take_the_streaming_path(ctx):
-    """Rows longer than the 1024-value register cache (kRowCache*64) re-read from memory."""
+    """Rows longer than the 2048-value register cache (kRowCache * 64 = 32 * 64) re-read the rest from memory."""
     import singlerust_amd as sr
     from singlerust_amd.memory import processing, statistics
     rng = np.random.default_rng(2)
-    lens = np.array([0, 1, 63, 64, 65, 1023, 1024, 1025, 4000, 7000, 2, 0])
+    lens = np.array([0, 1, 63, 64, 65, 1023, 1024, 1025, 2047, 2048, 2049, 4000, 7000, 2, 0])
     G = 8000
     indptr = np.zeros(len(lens) + 1, dtype=np.uint64)
     indptr[1:] = np.cumsum(lens)
