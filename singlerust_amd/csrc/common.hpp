@@ -301,7 +301,7 @@ int32_t launch_row_sums(srx_mat* m, double* out = nullptr);     // out null: int
 int32_t row_number(srx_mat* m, uint32_t* out);
 int32_t row_stat(srx_mat* m, int which, double* out0, double* out1);
 int32_t row_qc(srx_mat* m, uint32_t* num, double* sum, double* var);
-// pca_form.hip: out[0..n] = exclusive scan of in[0..n), out[n] = total (also left in *total_dev)
+// scan.hip: out[0..n] = exclusive scan of in[0..n), out[n] = total (also left in *total_dev)
 int32_t scan_exclusive(srx_ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d_out, int64_t** total_dev);
 inline void touch(srx_mat* m) { m->version++; m->pca.valid = false; }
 

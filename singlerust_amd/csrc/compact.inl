@@ -1,91 +1,5 @@
 // compact.inl — included by pca_form.hip inside namespace srx (the kernels share pca_internal.hpp's helpers and constants).
-// HVG compaction of the CSR matrix to the selected features: counts, scans, fill passes (row-major records, tile-major views), the selection table in LDS, the owner-record format of the Gram kernel.
-
-// ---- exclusive scan of int64 counts (3 phases, 4096 elements per block) ------------------------
-constexpr int kScanItems = 4;
-constexpr int kScanBlock = 1024;
-__global__ __launch_bounds__(kScanBlock) void k_scan_block_sums(const int64_t* __restrict__ in, uint64_t n,
-                                                                int64_t* __restrict__ block_sums) {
-    __shared__ int64_t s_w[kScanBlock / kWave];
-    uint64_t base = (uint64_t)blockIdx.x * kScanBlock * kScanItems;
-    int64_t s = 0;
-    for (int t = 0; t < kScanItems; ++t) {
-        uint64_t i = base + (uint64_t)threadIdx.x * kScanItems + t;
-        if (i < n) s += in[i];
-    }
-    s = wave_sum(s);
-    if (lane_id() == 0) s_w[threadIdx.x / kWave] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t tot = 0;
-        for (int w = 0; w < kScanBlock / kWave; ++w) tot += s_w[w];
-        block_sums[blockIdx.x] = tot;
-    }
-}
-// Exclusive scan of the block sums in place by ONE workgroup (nb is n/4096: a few thousand).
-__global__ __launch_bounds__(kScanBlock) void k_scan_serial(int64_t* __restrict__ block_sums, uint64_t nb,
-                                                            int64_t* __restrict__ total) {
-    __shared__ int64_t s_w[kScanBlock / kWave];
-    const uint64_t per = (nb + kScanBlock - 1) / kScanBlock;
-    const uint64_t b0 = (uint64_t)threadIdx.x * per;
-    const uint64_t b1 = b0 + per < nb ? b0 + per : nb;
-    int64_t s = 0;
-    for (uint64_t b = b0; b < b1; ++b) s += block_sums[b];
-    int64_t inc = s;
-    const int lane = lane_id();
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        int64_t o = __shfl_up(inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (lane == kWave - 1) s_w[threadIdx.x / kWave] = inc;
-    __syncthreads();
-    int64_t wave_off = 0, all = 0;
-    for (int w = 0; w < kScanBlock / kWave; ++w) {
-        if (w < (int)(threadIdx.x / kWave)) wave_off += s_w[w];
-        all += s_w[w];
-    }
-    int64_t acc = wave_off + inc - s;
-    for (uint64_t b = b0; b < b1; ++b) {
-        int64_t v = block_sums[b];
-        block_sums[b] = acc;
-        acc += v;
-    }
-    if (threadIdx.x == 0) *total = all;
-}
-__global__ __launch_bounds__(kScanBlock) void k_scan_apply(const int64_t* __restrict__ in, uint64_t n,
-                                                           const int64_t* __restrict__ block_offs,
-                                                           const int64_t* __restrict__ total,
-                                                           int64_t* __restrict__ out /* n + 1 */) {
-    __shared__ int64_t s_w[kScanBlock / kWave];
-    uint64_t base = (uint64_t)blockIdx.x * kScanBlock * kScanItems;
-    int64_t v[kScanItems];
-    int64_t s = 0;
-    for (int t = 0; t < kScanItems; ++t) {
-        uint64_t i = base + (uint64_t)threadIdx.x * kScanItems + t;
-        v[t] = i < n ? in[i] : 0;
-        s += v[t];
-    }
-    // inclusive scan of the per-thread sums across the wave, then across waves
-    int64_t inc = s;
-    const int lane = lane_id();
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        int64_t o = __shfl_up(inc, off, kWave);
-        if (lane >= off) inc += o;
-    }
-    if (lane == kWave - 1) s_w[threadIdx.x / kWave] = inc;
-    __syncthreads();
-    int64_t wave_off = 0;
-    for (int w = 0; w < (int)(threadIdx.x / kWave); ++w) wave_off += s_w[w];
-    int64_t excl = block_offs[blockIdx.x] + wave_off + inc - s;
-    for (int t = 0; t < kScanItems; ++t) {
-        uint64_t i = base + (uint64_t)threadIdx.x * kScanItems + t;
-        if (i < n) out[i] = excl;
-        excl += v[t];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = *total;
-}
+// HVG compaction of the CSR matrix to the selected features: counts, fill passes (row-major records, tile-major views), the selection table in LDS, the owner-record format of the Gram kernel.  The scans between the passes are scan.hip's scan_exclusive.
 
 // ---- tile-major view of the compacted matrix ---------------------------------------------------
 // The compacted N x k matrix is stored as n_t = ceil(k / KT) sub-matrices, one per GENE TILE of
@@ -144,8 +58,7 @@ struct SelLds {
     const uint32_t* prefix;
     __device__ __forceinline__ int column(int32_t gene) const {
         const uint32_t w = bits[gene >> 5];
-        const uint32_t bit = 1u << (gene & 31);
-        return (w & bit) ? (int)(prefix[gene >> 5] + __popc(w & (bit - 1u))) : -1;
+        return ((w >> (gene & 31)) & 1u) ? (int)bitmap_rank_word(w, prefix, (uint32_t)gene) : -1;
     }
 };
 // LDS: the table is copied to `lds` (2 n_words words); otherwise it is read where it is
@@ -245,9 +158,9 @@ __global__ __launch_bounds__(kCountThreads) void k_rowcount_list(const int64_t* 
     for (int g = threadIdx.x; g <= n_genes; g += blockDim.x) {
         uint32_t c = 0xffffu;
         if (g < n_genes) {
-            const uint32_t w = g_bits[g >> 5], bit = 1u << (g & 31);
-            if (w & bit) {
-                c = g_prefix[g >> 5] + (uint32_t)__popc(w & (bit - 1u));
+            const uint32_t w = g_bits[g >> 5];
+            if ((w >> (g & 31)) & 1u) {
+                c = bitmap_rank_word(w, g_prefix, (uint32_t)g);
                 if (c >= (uint32_t)k) c = 0xffffu;       // only a broken selection (NaN variances) has such columns: dropped
             }
         }

@@ -14,13 +14,13 @@
 // The one thing that needs the other orientation is the PCA (compaction, Gram and SpMM walk cells): the device
 // TRANSPOSE below builds the CSR of X from the stored CSR of X^T —
 //   1. k_hist:     entries per output row (global u32 atomics; a format conversion, not a per-step pass)
-//   2. scan_exclusive -> output row offsets
+//   2. scan_exclusive (scan.hip) -> output row offsets
 //   3. k_scatter:  every entry to its output row through an atomic cursor (order inside a row arbitrary)
 //   4. k_row_order: one wave per output row orders the row by column with a BITMAP COUNTING SORT in LDS: the
 //      columns of a canonical row are distinct, so rank(c) = popcount of the row's column bitmap below c
 //      (n_cols bits + one prefix count per 32-bit word per wave); O(nnz_row + n_cols / 32) per row, no comparison
 //      network, deterministic output whatever order step 3 produced.
-#include "common.hpp"
+#include "scan.hpp"
 
 #include <algorithm>
 
@@ -83,19 +83,14 @@ __global__ void k_row_order(const int64_t* __restrict__ ptr, const int32_t* __re
         for (int w0 = 0; w0 < words; w0 += kWave) {
             const int w = w0 + lane;
             const uint32_t pc = w < words ? (uint32_t)__popc(bits[w]) : 0u;
-            uint32_t inc = pc;
-#pragma unroll
-            for (int off = 1; off < kWave; off <<= 1) {
-                const uint32_t o = __shfl_up(inc, off, kWave);
-                if (lane >= off) inc += o;
-            }
+            const uint32_t inc = wave_scan_inclusive(pc);
             if (w < words) pre[w] = run + inc - pc;
             run += __shfl(inc, kWave - 1, kWave);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         for (int64_t p = lo + lane; p < hi; p += kWave) {
             const int32_t c = in_idx[p];
-            const uint32_t rank = pre[c >> 5] + (uint32_t)__popc(bits[c >> 5] & ((1u << (c & 31)) - 1u));
+            const uint32_t rank = bitmap_rank(bits, pre, (uint32_t)c);
             out_idx[lo + rank] = c;
             out_vals[lo + rank] = in_vals[p];
         }

@@ -6,7 +6,7 @@
 // -> boolean mask (the nine FlexValue combinations of mod.rs:33-84) -> subset.  The masks are N or G booleans
 // and the two order statistics are an nth_element: host work on vectors the statistics calls return anyway.
 // The subset (anndata `subset`, third-party in the reference) is a stream compaction on the device: kept
-// entries per kept row (wave ballot), exclusive scan, fill; rows / columns keep their order.
+// entries per kept row (wave ballot), exclusive scan (scan.hip), fill; rows / columns keep their order.
 #include "common.hpp"
 
 namespace srx {

@@ -49,23 +49,14 @@ __global__ __launch_bounds__(1024) void k_rec_scan(const int64_t* __restrict__ b
     __shared__ int64_t carry_s;
     if (threadIdx.x == 0) carry_s = 0;
     __syncthreads();
-    const int lane = lane_id(), wave = threadIdx.x / kWave;
     for (uint64_t i0 = 0; i0 < n; i0 += 1024) {
         const uint64_t i = i0 + threadIdx.x;
         const int64_t v = i < n ? blk_total[i] : 0;
-        int64_t inc = v;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const int64_t o = __shfl_up(inc, off, kWave);
-            if (lane >= off) inc += o;
-        }
-        if (lane == kWave - 1) wsum[wave] = inc;
+        int64_t round_total;
+        const int64_t before = block_scan_exclusive<16>(v, wsum, round_total) + carry_s;
+        if (i < n) base[i] = before;
         __syncthreads();
-        int64_t before = carry_s;
-        for (int w = 0; w < wave; ++w) before += wsum[w];
-        if (i < n) base[i] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = before + inc;
+        if (threadIdx.x == 0) carry_s += round_total;
         __syncthreads();
     }
     if (threadIdx.x == 0) {
@@ -220,12 +211,7 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket(const int64_t* __rest
         for (int c0 = 0; c0 < n_wg; c0 += kWave) {
             const int i = c0 + lane;
             const uint32_t v = i < n_wg ? hist[i] : 0u;
-            uint32_t inc = v;
-#pragma unroll
-            for (int off = 1; off < kWave; off <<= 1) {
-                const uint32_t o = __shfl_up(inc, off, kWave);
-                if (lane >= off) inc += o;
-            }
+            const uint32_t inc = wave_scan_inclusive(v);
             if (i < n_wg) {
                 hist[i] = carry + inc - v;
                 boff[rb * (uint64_t)(n_wg + 1) + i] = carry + inc - v;

@@ -21,7 +21,7 @@
 //                     (a + b) - a b of the pair, whether it is stored; an edge whose reverse is absent is an IN-ONLY entry
 //                     of row j and is counted there (one global atomic per such edge)
 //   k_graph_rowlen    (thread per row) row length of C = stored out-edges + in-only entries; rows whose in-only list is long
-//   scan_exclusive    twice: the offsets of the in-only lists and the indptr of C
+//   scan_exclusive    (scan.hip) twice: the offsets of the in-only lists and the indptr of C
 //   k_graph_scatter   (thread per edge) in-only entries to their row through an atomic cursor, in arbitrary order
 //   k_graph_order     in-only list of a row with at most kShort entries: rank by counting in LDS, written back in place
 //   k_graph_order_long  one workgroup per longer list (a hub: thousands to n - 1 entries): the sources are distinct, so a
@@ -33,6 +33,7 @@
 #include "common.hpp"
 #include "graph_handle.hpp"
 #include "pca_internal.hpp"
+#include "scan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -271,7 +272,7 @@ __global__ void __launch_bounds__(256) k_graph_order_long(const int64_t* __restr
     __shared__ uint32_t bits[W];
     __shared__ uint32_t pre[W];
     __shared__ uint32_t wtot[4];
-    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+    const int tid = threadIdx.x;
     const uint32_t row = long_rows[blockIdx.x];
     const int64_t lo = tptr[row], hi = tptr[row + 1];
     uint32_t done = 0;
@@ -283,33 +284,14 @@ __global__ void __launch_bounds__(256) k_graph_order_long(const int64_t* __restr
             if (s < (uint64_t)kBits) atomicOr(&bits[s >> 5], 1u << (s & 31));
         }
         __syncthreads();
-        // exclusive prefix of the word popcounts: PER consecutive words per thread, then a scan over the 256 threads
-        uint32_t mine = 0;
-        for (int w = 0; w < PER; ++w) mine += (uint32_t)__popc(bits[tid * PER + w]);
-        uint32_t inc = mine;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, kWave);
-            if (lane >= off) inc += o;
-        }
-        if (lane == kWave - 1) wtot[wave] = inc;
-        __syncthreads();
-        uint32_t run = inc - mine, total = 0;
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) run += wtot[w];
-            total += wtot[w];
-        }
-        for (int w = 0; w < PER; ++w) {
-            pre[tid * PER + w] = run;
-            run += (uint32_t)__popc(bits[tid * PER + w]);
-        }
+        const uint32_t total = bitmap_prefix_fill<W, PER>(bits, pre, wtot);
         __syncthreads();
         if (total)
             for (int64_t p = lo + tid; p < hi; p += 256) {
                 const uint32_t src = t_src[p];
                 const uint64_t s = (uint64_t)src - base;
                 if (s < (uint64_t)kBits) {
-                    const uint32_t r = done + pre[s >> 5] + (uint32_t)__popc(bits[s >> 5] & ((1u << (s & 31)) - 1u));
+                    const uint32_t r = done + bitmap_rank(bits, pre, (uint32_t)s);
                     o_src[lo + r] = src;
                     o_val[lo + r] = t_val[p];
                 }

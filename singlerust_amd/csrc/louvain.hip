@@ -30,9 +30,10 @@
 //                       global workspace (a row of L entries meets at most L communities), fixed-point sums
 //   k_louvain_apply     the moved vertices update tot and the community sizes; counts the moves
 //   k_louvain_q_in / k_louvain_q_tot   the two sums of Q and the number of communities
-//   k_louvain_flag / k_louvain_oldof / k_louvain_members   compact ids (flag + scan) and the member list of each community
+//   k_louvain_flag / k_louvain_oldof / k_louvain_members   compact ids (flag + scan.hip's scan_exclusive) and the member list
+//                       of each community
 //   k_louvain_coarse<FILL>  a workgroup per coarse vertex walks its members' rows: a bitmap of kLvBits coarse ids at a time
-//                       with prefix popcounts (as k_graph_order_long) gives the row length, then every column its place,
+//                       with prefix popcounts (scan.hpp's bitmap ranks) gives the row length, then every column its place,
 //                       and the weights are added there in fixed point; self weight apart
 //   k_louvain_unfix     fixed point -> f64 for the coarse weights
 //   k_louvain_compose   cell -> community through a kept level
@@ -40,6 +41,7 @@
 //                       ordered by (size descending, smallest member)
 #include "common.hpp"
 #include "graph_handle.hpp"
+#include "scan.hpp"
 
 #include <cmath>
 
@@ -441,27 +443,11 @@ __global__ void __launch_bounds__(256) k_louvain_coarse(LvGraph g, const uint32_
             if (!FILL && base == 0 && lane == 0 && g.self) self_acc += lv_fix(g.self[i], scale);
         }
         __syncthreads();
-        // exclusive prefix of the word popcounts: PER consecutive words per thread, then a scan over the 256 threads
-        uint32_t mine = 0;
-        for (int w = 0; w < PER; ++w) mine += (uint32_t)__popc(bits[tid * PER + w]);
-        uint32_t inc = mine;
-#pragma unroll
-        for (int off = 1; off < kWave; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, kWave);
-            if (lane >= off) inc += o;
-        }
-        if (lane == kWave - 1) wtot[wave] = inc;
-        __syncthreads();
-        uint32_t run = inc - mine, total = 0;
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) run += wtot[w];
-            total += wtot[w];
-        }
+        const uint32_t total = bitmap_prefix_fill<W, PER>(bits, FILL ? pre : nullptr, wtot);      // (!FILL: the row's length alone)
         if (FILL && total) {
-            for (int w = 0; w < PER; ++w) {
+            for (int w = 0; w < PER; ++w) {                  // the columns of this thread's own words
                 const int word = tid * PER + w;
-                pre[word] = run;
-                uint32_t bw = bits[word];
+                uint32_t run = pre[word], bw = bits[word];
                 while (bw) {
                     const int bit = __ffs((int)bw) - 1;
                     bw &= bw - 1;
@@ -476,7 +462,7 @@ __global__ void __launch_bounds__(256) k_louvain_coarse(LvGraph g, const uint32_
                     const uint32_t b = (uint32_t)newid[comm[g.ind[e]]];
                     const uint64_t s = (uint64_t)b - base;
                     if (b != a && s < (uint64_t)kLvBits) {
-                        const uint32_t r = pre[s >> 5] + (uint32_t)__popc(bits[s >> 5] & ((1u << (s & 31)) - 1u));
+                        const uint32_t r = bitmap_rank(bits, pre, (uint32_t)s);
                         atomicAdd(&cacc[out0 + done + r], (unsigned long long)lv_fix(g.w[e], scale));
                     }
                 }
@@ -620,17 +606,16 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
     SRX_TRY(scratch(ctx, "louvain_s0", (n + 1) * 8, (void**)&d_s0));
     SRX_TRY(scratch(ctx, "louvain_s1", (n + 1) * 8, (void**)&d_s1));
 
-    hipEvent_t e0, e1;
-    SRX_HIP(ctx, hipEventCreate(&e0));
-    SRX_HIP(ctx, hipEventCreate(&e1));
-    struct EvGuard {
-        hipEvent_t a, b;
+    struct EvGuard {                     // destroys what was created, whichever return is taken
+        hipEvent_t a = nullptr, b = nullptr;
         ~EvGuard() {
-            (void)hipEventDestroy(a);
-            (void)hipEventDestroy(b);
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
         }
-    } guard{e0, e1};
-    SRX_HIP(ctx, hipEventRecord(e0, st));
+    } ev;
+    SRX_HIP(ctx, hipEventCreate(&ev.a));
+    SRX_HIP(ctx, hipEventCreate(&ev.b));
+    SRX_HIP(ctx, hipEventRecord(ev.a, st));
 
     LvGraph g{d_ptr, d_ind, d_w, nullptr, n, nnz};
     hipLaunchKernelGGL(k_louvain_compose, dim3(lv_grid(n)), dim3(256), 0, st, d_cell, n, (const uint32_t*)nullptr, (const int64_t*)nullptr);
@@ -767,10 +752,10 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
     hipLaunchKernelGGL(k_louvain_rank, dim3(lv_grid(n_comm)), dim3(256), 0, st, d_keys, n_comm, d_cell, d_rank);
     hipLaunchKernelGGL(k_louvain_relabel, dim3(lv_grid(n)), dim3(256), 0, st, d_cell, n, d_rank, d_labels);
     SRX_HIP(ctx, hipGetLastError());
-    SRX_HIP(ctx, hipEventRecord(e1, st));
-    SRX_HIP(ctx, hipEventSynchronize(e1));
+    SRX_HIP(ctx, hipEventRecord(ev.b, st));
+    SRX_HIP(ctx, hipEventSynchronize(ev.b));
     float ms = 0.f;
-    SRX_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+    SRX_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
     info->n = n;
     info->n_communities = n_comm;
     info->modularity = have_q ? q_prev : 0.0;

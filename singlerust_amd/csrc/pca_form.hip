@@ -1,9 +1,10 @@
 // pca_form.hip — the HVG-compacted matrix and its Gram matrix (first half of dim_red::pca_inplace on the GPU; pca.hip has the
-// overview): the compaction of X to the selected features (compact.inl: counts, scans, fill passes; row-major entries and,
+// overview): the compaction of X to the selected features (compact.inl: counts, fill passes, scan.hip's scan between them; row-major entries and,
 // where a consumer wants it, a tile-major view), the owner records of the Gram kernel and G = A^T A itself (gram.inl), with
 // the exchange of the packed triangle across row shards.
 #include "pca_internal.hpp"
 #include "log1p64.hpp"
+#include "scan.hpp"
 
 namespace srx {
 
@@ -84,22 +85,6 @@ int grid_rows(const srx_ctx* ctx, uint64_t n_rows, int rows_per_block) {
     uint64_t cap = (uint64_t)ctx->n_cus * 8;
     if (want < 1) want = 1;
     return (int)(want < cap ? want : cap);
-}
-
-// out[0..n] = exclusive scan of in[0..n), out[n] = total (also left in *total_dev).
-int32_t scan_exclusive(srx_ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d_out, int64_t** total_dev) {
-    const uint64_t per_block = (uint64_t)kScanBlock * kScanItems;
-    const uint64_t nb = (n + per_block - 1) / per_block > 0 ? (n + per_block - 1) / per_block : 1;
-    int64_t* d_bsum;
-    SRX_TRY(scratch(ctx, "scan_bsum", (nb + 1) * sizeof(int64_t), (void**)&d_bsum));
-    int64_t* d_total = d_bsum + nb;
-    hipLaunchKernelGGL(k_scan_block_sums, dim3((unsigned)nb), dim3(kScanBlock), 0, ctx->stream, d_in, n, d_bsum);
-    hipLaunchKernelGGL(k_scan_serial, dim3(1), dim3(kScanBlock), 0, ctx->stream, d_bsum, nb, d_total);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(kScanBlock), 0, ctx->stream, d_in, n, d_bsum, d_total,
-                       d_out);
-    SRX_HIP(ctx, hipGetLastError());
-    if (total_dev) *total_dev = d_total;
-    return SRX_OK;
 }
 
 // Tile-major view of the row-major records for tiles of KT compacted columns (cut, scan, copy).

@@ -1,0 +1,67 @@
+// scan.hpp — device-side prefix sums and bitmap ranks, stated once for every kernel that needs one (device code only;
+// scan.hip has the device-wide scan_exclusive built on them).
+#pragma once
+
+#include "common.hpp"
+
+namespace srx {
+
+// Inclusive prefix sum of v over the wave's lanes.  ALL 64 LANES MUST BE ACTIVE (the shuffle reads lanes that sit out as
+// garbage): call it from wave-uniform control flow and give the lanes behind the data a zero.
+template <typename T>
+__device__ __forceinline__ T wave_scan_inclusive(T v) {
+    const int lane = lane_id();
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const T o = __shfl_up(v, off, kWave);
+        if (lane >= off) v += o;
+    }
+    return v;
+}
+
+// Exclusive prefix sum of v over the threads of a workgroup of WAVES full waves; `total` = the sum over all of them, in
+// every thread.  `s_wave` (LDS) holds the wave totals: the ONE barrier in here lies between writing and reading them, so
+// the CALLER owns the barrier between this call's reads and the next call's writes (a looped site ends its round with one).
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_scan_exclusive(T v, T* s_wave, T& total) {
+    const int wave = threadIdx.x / kWave;
+    const T inc = wave_scan_inclusive(v);
+    if (lane_id() == kWave - 1) s_wave[wave] = inc;
+    __syncthreads();
+    T before = 0;
+    total = 0;
+    for (int w = 0; w < WAVES; ++w) {
+        const T t = s_wave[w];
+        if (w < wave) before += t;
+        total += t;
+    }
+    return before + inc - v;
+}
+
+// ---- bitmap ranks: one bit per key in `bits`, pre[w] = set bits in the words before w; the place of key s among the set
+// keys is pre[s / 32] + the set bits of its word below it.
+// `word` = bits[s >> 5] as the caller has loaded it (to test the key's own bit first)
+__device__ __forceinline__ uint32_t bitmap_rank_word(uint32_t word, const uint32_t* pre, uint32_t s) {
+    return pre[s >> 5] + (uint32_t)__popc(word & ((1u << (s & 31)) - 1u));
+}
+__device__ __forceinline__ uint32_t bitmap_rank(const uint32_t* bits, const uint32_t* pre, uint32_t s) {
+    return bitmap_rank_word(bits[s >> 5], pre, s);
+}
+// pre[0 .. W) from bits[0 .. W) by a workgroup of W / PER threads, thread t taking the PER consecutive words from t * PER;
+// returns the number of set bits (`pre` null: that number alone).  The bits are visible to the workgroup on entry; barriers
+// as block_scan_exclusive, and the caller's barrier also stands between these writes of `pre` and the other threads' reads.
+template <int W, int PER>
+__device__ __forceinline__ uint32_t bitmap_prefix_fill(const uint32_t* bits, uint32_t* pre, uint32_t* s_wave) {
+    const int w0 = threadIdx.x * PER;
+    uint32_t mine = 0;
+    for (int w = 0; w < PER; ++w) mine += (uint32_t)__popc(bits[w0 + w]);
+    uint32_t total;
+    uint32_t run = block_scan_exclusive<W / PER / kWave>(mine, s_wave, total);
+    for (int w = 0; pre && w < PER; ++w) {
+        pre[w0 + w] = run;
+        run += (uint32_t)__popc(bits[w0 + w]);
+    }
+    return total;
+}
+
+}  // namespace srx

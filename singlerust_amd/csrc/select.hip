@@ -3,6 +3,7 @@
 // selected genes in selection order and the PCA's centring / scaling vectors), the host ranking outside its envelope, and
 // srx_select_hvg.  Reads the global moments genes.hip leaves on the matrix (d_cnt / d_sum / d_sq, n_rows_global).
 #include "pca_internal.hpp"
+#include "scan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict_
     __shared__ int s_nan;
     uint32_t* const wbits = LDS ? s_bits : bits;
     uint32_t* const wpre = LDS ? s_pre : prefix;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
     if (t == 0) s_nan = 0;
     __syncthreads();
     // the gene of rank r < take goes to sel_rank[r] and into the mask (two words per thread); a NaN variance anywhere is the
@@ -261,20 +262,11 @@ __global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict_
         if (w < n_words) b[0] = wbits[w];
         if (w + 1 < n_words) b[1] = wbits[w + 1];
         const uint32_t c0 = (uint32_t)__popc(b[0]), c1 = (uint32_t)__popc(b[1]);
-        uint32_t inc = c0 + c1;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) s_wave[wv] = inc;
-        __syncthreads();
-        uint32_t before = carry;
-        for (int q = 0; q < wv; ++q) before += s_wave[q];
-        const uint32_t excl = before + inc - (c0 + c1);
+        uint32_t round_total;
+        const uint32_t excl = carry + block_scan_exclusive<16>(c0 + c1, s_wave, round_total);
         if (w < n_words) wpre[w] = excl;
         if (w + 1 < n_words) wpre[w + 1] = excl + c0;
-        for (int q = 0; q < 16; ++q) carry += s_wave[q];
+        carry += round_total;
         __syncthreads();
     }
     // never more than `take` selected genes, whatever the flags say (a ranking broken by NaN variances can flag more): the
@@ -293,9 +285,9 @@ __global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict_
         }
     double tr = 0.0;
     for (uint32_t g = t; sum && g < G; g += 1024) {
-        const uint32_t w = wbits[g >> 5], bit = 1u << (g & 31);
-        if (!(w & bit)) continue;
-        const uint32_t s = wpre[g >> 5] + (uint32_t)__popc(w & (bit - 1u));
+        const uint32_t w = wbits[g >> 5];
+        if (!((w >> (g & 31)) & 1u)) continue;
+        const uint32_t s = bitmap_rank_word(w, wpre, g);
         const double mean = sum[g] / n_cells;
         double var = sq[g] / n_cells - mean * mean;
         if (var < 0) var = 0;

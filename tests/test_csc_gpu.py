@@ -122,6 +122,44 @@ def test_transpose_roundtrip(ctx, store):
     assert np.array_equal(back.values(np.float64), x.data.astype(np.float64))
 
 
+@pytest.mark.parametrize("store", [1, 2])
+@pytest.mark.parametrize("n_cols", [31, 32, 33, 2047, 2048, 2049, 4097])
+def test_transpose_roundtrip_at_the_bitmap_word_counts(ctx, n_cols, store):
+    """The row-ordering pass of the transpose back to CSR keeps one bit per column and scans the word counts 64 words at a
+    time: 1 word, 1 and then 2, 64, 64 and then 65, 129.  300 rows, one of them holding every column (every word full), one
+    empty and some of a single entry (nothing to order); pattern and values bit-exact against scipy in both directions."""
+    import scipy.sparse as sp
+    import singlerust_amd as sr
+    from singlerust_amd import _ffi
+    n = 300
+    rng = np.random.default_rng(n_cols)
+    dense = rng.random((n, n_cols)) < 0.05
+    dense[7] = True
+    dense[11] = False
+    dense[13] = False
+    dense[13, n_cols - 1] = True
+    x = sp.csr_matrix(dense, dtype=np.float32)
+    x.data = rng.uniform(0.5, 50.0, x.nnz).astype(np.float32)
+    lens = np.diff(x.indptr)
+    assert lens[7] == n_cols and lens[11] == 0 and lens[13] == 1
+
+    def pattern(dev, n_major):
+        ip, ix = np.zeros(n_major + 1, np.uint64), np.zeros(x.nnz, np.uint64)
+        _ffi.check(_ffi.lib().srx_matrix_download_pattern(dev.handle, _ffi.ptr(ip), _ffi.ptr(ix)), ctx.handle)
+        return ip, ix
+
+    t = sr.IMAnnData.new_basic(x, ctx=ctx, store=store).x().to_csc()
+    want = x.tocsc()
+    want.sort_indices()
+    ip, ix = pattern(t, n_cols)
+    assert t.is_csc() and np.array_equal(ip, want.indptr) and np.array_equal(ix, want.indices)
+    assert np.array_equal(t.values(np.float64), want.data.astype(np.float64))
+    back = t.to_csr()
+    ip, ix = pattern(back, n)
+    assert not back.is_csc() and np.array_equal(ip, x.indptr) and np.array_equal(ix, x.indices)
+    assert np.array_equal(back.values(np.float64), x.data.astype(np.float64))
+
+
 def test_csc_pipeline_and_pca_match_oracle(ctx):
     """normalize_total(Row) -> log1p -> HighlyVariable -> pca_inplace on a CSC matrix: the HVG list follows the CSC
     variance (two-pass form), scores / components within 1e-5 of the exact-SVD oracle on the densified CSC matrix."""

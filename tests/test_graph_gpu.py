@@ -238,6 +238,46 @@ def test_hub_row(ctx):
     assert ptr[1] == n - 1 and np.array_equal(ind[:n - 1], np.arange(1, n, dtype=np.uint32))
 
 
+HUB_LENGTHS = (1, 2, 63, 64, 65, 511, 512, 513, 1024)        # in-only entries: both sides of a wave and of the short-list limit
+
+
+def hub_list(n=3000, k=5, seed=33):
+    """Nine hubs with in-only lists of exactly HUB_LENGTHS entries: every other cell names four cells of the ring of
+    non-hubs behind it, and its first neighbour is its hub (the sources) or one more cell of the ring (the rest); a hub names
+    five cells of the rest, so nobody names a hub back.  Cell numbers are shuffled: the lists arrive in no order."""
+    rng = np.random.default_rng(seed)
+    ids = rng.permutation(n).astype(np.uint32)
+    hubs, ring = ids[:len(HUB_LENGTHS)], ids[len(HUB_LENGTHS):]
+    m = len(ring)
+    assert sum(HUB_LENGTHS) + k <= m
+    idx = np.zeros((n, k), dtype=np.uint32)
+    idx[ring] = ring[(np.arange(m)[:, None] + np.arange(1, k + 1)[None, :]) % m]
+    sources, at = {}, 0
+    for h, length in zip(hubs, HUB_LENGTHS):
+        sources[int(h)] = np.sort(ring[at:at + length])
+        idx[ring[at:at + length], 0] = h
+        at += length
+    idx[hubs] = ring[at:at + k]                                # cells that name no hub
+    return idx, rng.uniform(0.5, 2.0, (n, k)), sources
+
+
+def test_hub_rows_at_the_list_length_edges(ctx):
+    idx, dist, sources = hub_list()
+    n, k = idx.shape
+    B = sp.csr_matrix((np.ones(n * k, bool), idx.ravel().astype(np.int64), np.arange(0, n * k + 1, k)), shape=(n, n))
+    in_only = (B.T > B).tocsr()                                # j names i and i does not name j
+    in_only.sort_indices()
+    for (h, src), length in zip(sources.items(), HUB_LENGTHS):
+        assert len(src) == length and np.array_equal(in_only[h].indices, src)
+    got = fetch_all(build(ctx, idx, dist))
+    check_against_restatement(idx, dist, got, "hub lengths")
+    ptr, ind, dat = got[2]
+    for h, src in sources.items():
+        cols = ind[int(ptr[h]):int(ptr[h + 1])]
+        assert np.array_equal(cols, np.sort(np.concatenate([idx[h], src])))
+        assert np.array_equal(cols[~np.isin(cols, idx[h])], src)
+
+
 # ---- 6. resident path ---------------------------------------------------------------------------------------------------
 def _pipeline_matrix(ctx, cells=6000, genes=1500, n_pc=20):
     import singlerust_amd as sr

@@ -275,6 +275,19 @@ def test_subset_beyond_4m_rows(ctx, store, dtype):
     assert_holds(ctx, got, _scipy_subset(x, rm, None), dtype, store)
 
 
+@pytest.mark.parametrize("n", [1, 4095, 4096, 4097, 8193, 4096 * 1024 + 1])
+def test_subset_scan_lengths(ctx, n):
+    """The device-wide scan at its own edges, through the row mask it scans: one element, one short of / exactly / one past
+    a 4096-element block, past two blocks, and the first length at which the one-workgroup pass over the block sums walks
+    more than one of them per thread.  One entry per row, about half of the rows kept."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(n)
+    x = sp.csr_matrix((rng.uniform(0.5, 50.0, n).astype(np.float32), rng.integers(0, 8, n), np.arange(n + 1)), shape=(n, 8))
+    rm = rng.random(n) < 0.5
+    got = _subset(ctx, _upload(ctx, x, STORE_F32).x(), rm, None)
+    assert_holds(ctx, got, _scipy_subset(x, rm, None), np.float32, STORE_F32)
+
+
 # ---- c. the filters at their edges --------------------------------------------------------------------------------
 
 def _assert_filter(ctx, got, want, wmask, store=STORE_F32):
