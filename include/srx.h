@@ -37,7 +37,8 @@ extern "C" {
                                   srx_pca_model_* / srx_pca_transform (fitted-PCA projection) and srx_knn_result /
                                   srx_knn_points (kernel class 11) came that way at 6, as did srx_neighbors_* / srx_graph_*
                                   (kernel class 12) and srx_louvain / srx_louvain_csr / srx_graph_labels_fetch (no class of
-                                  their own: the time is in srx_louvain_info.ms) */
+                                  their own: the time is in srx_louvain_info.ms) and srx_group_moments / srx_rank_genes_groups[_graph] /
+                                  srx_markers_* (no class either: srx_markers_info.ms) */
 
 typedef struct srx_ctx srx_ctx;   /* one GPU + stream + (optional) RCCL communicator      */
 typedef struct srx_mat srx_mat;   /* device-resident CSR (the `X` of an IMAnnData)        */
@@ -519,6 +520,73 @@ int32_t srx_louvain_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* in
                         const srx_louvain_opts* opts, uint32_t* labels_out, srx_louvain_info* info);
 /* The last srx_louvain's labels, kept on the device (n u32).  SRX_E_ARG when none has run on the handle. */
 int32_t srx_graph_labels_fetch(srx_graph* g, uint32_t* labels_out);
+
+/* ---- marker genes per group: grouped per-gene moments and Welch's t statistic, group against rest ---------------------
+ * What sc.tl.rank_genes_groups(method="t-test") gives uns["rank_genes_groups"].  Not in the reference; the definition here is
+ * what is tested.  The output has NOT been compared with scanpy (scanpy is not installed where this was built); the scores
+ * of the host test reference agree with scipy.stats.ttest_ind(equal_var=False).
+ *
+ * Input: the current stored values x of a CSR matrix (N = n_rows cells x n_cols genes) and one label < n_groups per cell.
+ * Moments.  Group g has n_g cells.  Per (group, gene) over the STORED entries of the group's rows (a stored 0 counts):
+ *   c_g = their number,  S_g = sum of x,  Q_g = sum of x * x (the product rounded to f64 first).
+ * S and Q are accumulated as 64-bit fixed-point integers round(x 2^sum_scale_log2), round(x x 2^sq_scale_log2), ties to even:
+ *   max_abs = the largest |x| over all stored values (found by one reduction pass that also refuses NaN / Inf: SRX_E_NAN),
+ *   e = the smallest integer with max_abs < 2^e (0 when max_abs == 0), taken no lower than -30 (the cap: 2^(62 + 60) is the
+ *       largest scale formed),  L = ceil(log2(max(N, 1))),
+ *   sum_scale_log2 = 62 - e - L,   sq_scale_log2 = 62 - 2 e - L       (no other cap; either may be negative).
+ * Every total therefore stays below 2^62, |S_dev - S_exact| <= n_g 2^-(sum_scale_log2 + 1) (likewise Q), the tables are
+ * bit-identical from call to call and independent of the order of the rows, and integer-valued data gives exact moments
+ * as long as the scales are not negative.  SUM = f64(S_int) 2^-sum_scale_log2, SUMSQ likewise.
+ * Totals and rest: S_total = sum over g of S_int (integer), S_rest = S_total - S_g (integer subtraction, THEN converted to
+ * f64); c_rest and Q_rest the same way; n_r = N - n_g.
+ * Statistics, all f64, no FMA contraction, in exactly this order (group: S, Q, c, n = n_g; rest: the rest values, n = n_r):
+ *   mean = S / n                                         (0 when n == 0)
+ *   var  = max(0, (Q / n - mean * mean) * (n / (n - 1)))   (a value that is not > 0 gives +0)
+ *   d = var_g / n_g + var_r / n_r;   score = (mean_g - mean_r) / sqrt(d) when d > 0, else 0
+ *   pct = c / n                                          (0 when n == 0)
+ *   lfc = log2((expm1(mean_g) + 1e-9) / (expm1(mean_r) + 1e-9)) when logged, else log2((mean_g + 1e-9) / (mean_r + 1e-9))
+ * A group with n_g < 2 or n_r < 2 is degenerate (an empty group and n_groups == 1 included): its variances (both sides) and
+ * its scores are 0, its means, pct and lfc are as above; info.groups_degenerate counts such groups.
+ * Ranking: per group the genes by (score descending, gene index ascending); the first n_top are kept. */
+#define SRX_GROUPS_MAX 4096
+typedef struct srx_markers srx_markers;   /* owns its device tables; free it before its context */
+typedef struct srx_rank_genes_opts {
+    int32_t n_top;     /* genes kept per group; 0 = min(100, n_cols); above n_cols or negative: SRX_E_ARG */
+    int32_t logged;    /* the values are ln(1 + x) (lfc through expm1); < 0 = yes.  NULL opts = {0, -1}    */
+} srx_rank_genes_opts;
+typedef struct srx_markers_info {
+    uint64_t n_rows, n_cols;
+    uint32_t n_groups, n_top;
+    int32_t sum_scale_log2, sq_scale_log2;
+    uint32_t groups_degenerate, reserved_;
+    double max_abs;
+    double ms;             /* hipEvent time of the device work */
+} srx_markers_info;
+enum { SRX_MARKERS_CNT = 0, SRX_MARKERS_SUM = 1, SRX_MARKERS_SUMSQ = 2, SRX_MARKERS_MEAN = 3, SRX_MARKERS_VAR = 4,
+       SRX_MARKERS_MEAN_REST = 5, SRX_MARKERS_VAR_REST = 6, SRX_MARKERS_SCORE = 7, SRX_MARKERS_LFC = 8, SRX_MARKERS_PCT = 9,
+       SRX_MARKERS_PCT_REST = 10 };
+/* The primitive (pseudobulk sums, dot-plot fractions): labels = n_rows host u32, each < n_groups; n_cells_out n_groups u64;
+ * cnt_out (u64), sum_out, sumsq_out (f64) n_groups x n_cols row-major; any output may be NULL.
+ * Refusals of this and the two calls below, each with a message.  SRX_E_ARG: n_groups outside 1 .. SRX_GROUPS_MAX, a label
+ * >= n_groups (validated on the device), a CSC handle, a context with more than one rank (labels live on one rank; sharding
+ * is out of scope), 2^32 rows or more.  SRX_E_NAN: a stored value is NaN or Inf.  SRX_E_OOM: the tables do not fit.
+ * m is never modified: its values, version, moments cache and resident PCA result stay as they were (the pattern-only gene
+ * tiles of srx_matrix_prepare are built if the handle has none yet). */
+int32_t srx_group_moments(srx_mat* m, const uint32_t* labels, uint32_t n_groups, uint64_t* n_cells_out, uint64_t* cnt_out,
+                          double* sum_out, double* sumsq_out);
+/* Moments, statistics and ranking for host labels.  *out is written on success only. */
+int32_t srx_rank_genes_groups(srx_mat* m, const uint32_t* labels, uint32_t n_groups, const srx_rank_genes_opts* opts,
+                              srx_markers** out);
+/* The same with the labels the last srx_louvain left on g, read on the device (no host round trip); n_groups = the largest
+ * label + 1.  SRX_E_ARG also when g holds no labels, g's n differs from m's n_rows, or the two handles' contexts differ. */
+int32_t srx_rank_genes_groups_graph(srx_mat* m, srx_graph* g, const srx_rank_genes_opts* opts, srx_markers** out);
+int32_t srx_markers_info_get(const srx_markers* mk, srx_markers_info* info);
+/* n_groups x n_top row-major each; any pointer may be NULL. */
+int32_t srx_markers_fetch_top(srx_markers* mk, uint32_t* genes_out, double* scores_out, double* lfc_out);
+/* One full n_groups x n_cols table, row-major: SRX_MARKERS_CNT is u64, every other one f64. */
+int32_t srx_markers_fetch_table(srx_markers* mk, int32_t which, void* out);
+int32_t srx_markers_fetch_sizes(srx_markers* mk, uint64_t* n_cells_out);   /* n_groups */
+void    srx_markers_free(srx_markers* mk);
 
 /* The raw operators the PCA is built from, for a caller-supplied 64-column panel (k x 64
  * row-major): y_out (n_rows x 64) = X[:, sel] * panel, t_out (k x 64) = X[:, sel]^T * y, and

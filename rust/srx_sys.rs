@@ -9,6 +9,7 @@ pub const SRX_ABI_VERSION: i32 = 6;
 pub const SRX_UNIQUE_ID_BYTES: usize = 128;
 pub const SRX_KNN_MAX_DIMS: i32 = 128;
 pub const SRX_LOUVAIN_MAX_LEVELS: i32 = 32;
+pub const SRX_GROUPS_MAX: i32 = 4096;
 pub const SRX_OK: i32 = 0;
 pub const SRX_E_ARG: i32 = -1;
 pub const SRX_E_DTYPE: i32 = -2;
@@ -43,6 +44,17 @@ pub const SRX_SOLVER_GRAM: i32 = 1;
 pub const SRX_SOLVER_SPMM: i32 = 2;
 pub const SRX_GRAPH_DISTANCES: i32 = 0;
 pub const SRX_GRAPH_CONNECTIVITIES: i32 = 1;
+pub const SRX_MARKERS_CNT: i32 = 0;
+pub const SRX_MARKERS_SUM: i32 = 1;
+pub const SRX_MARKERS_SUMSQ: i32 = 2;
+pub const SRX_MARKERS_MEAN: i32 = 3;
+pub const SRX_MARKERS_VAR: i32 = 4;
+pub const SRX_MARKERS_MEAN_REST: i32 = 5;
+pub const SRX_MARKERS_VAR_REST: i32 = 6;
+pub const SRX_MARKERS_SCORE: i32 = 7;
+pub const SRX_MARKERS_LFC: i32 = 8;
+pub const SRX_MARKERS_PCT: i32 = 9;
+pub const SRX_MARKERS_PCT_REST: i32 = 10;
 pub const SRX_BACKED_NORMALIZE: i32 = 1;
 pub const SRX_BACKED_LOG1P: i32 = 2;
 pub const SRX_K_NORMALIZE: i32 = 0;
@@ -64,6 +76,7 @@ pub const SRX_K_COUNT_: i32 = 13;
 #[repr(C)] pub struct SrxMat { _private: [u8; 0] }      // opaque `srx_mat`
 #[repr(C)] pub struct SrxPcaModel { _private: [u8; 0] }      // opaque `srx_pca_model`
 #[repr(C)] pub struct SrxGraph { _private: [u8; 0] }      // opaque `srx_graph`
+#[repr(C)] pub struct SrxMarkers { _private: [u8; 0] }      // opaque `srx_markers`
 #[repr(C)] pub struct SrxBacked { _private: [u8; 0] }      // opaque `srx_backed`
 
 #[repr(C)]
@@ -190,6 +203,28 @@ pub struct SrxLouvainInfo {      // `srx_louvain_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxRankGenesOpts {      // `srx_rank_genes_opts`
+    pub n_top: i32,
+    pub logged: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxMarkersInfo {      // `srx_markers_info`
+    pub n_rows: u64,
+    pub n_cols: u64,
+    pub n_groups: u32,
+    pub n_top: u32,
+    pub sum_scale_log2: i32,
+    pub sq_scale_log2: i32,
+    pub groups_degenerate: u32,
+    pub reserved: u32,
+    pub max_abs: f64,
+    pub ms: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPipelineResult {      // `srx_pipeline_result`
     pub pca: SrxPcaInfo,
     pub ms_normalize: f64,
@@ -284,6 +319,17 @@ extern "C" {
     pub fn srx_louvain_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,
                            opts: *const SrxLouvainOpts, labels_out: *mut u32, info: *mut SrxLouvainInfo) -> i32;
     pub fn srx_graph_labels_fetch(g: *mut SrxGraph, labels_out: *mut u32) -> i32;
+    pub fn srx_group_moments(m: *mut SrxMat, labels: *const u32, n_groups: u32, n_cells_out: *mut u64,
+                             cnt_out: *mut u64, sum_out: *mut f64, sumsq_out: *mut f64) -> i32;
+    pub fn srx_rank_genes_groups(m: *mut SrxMat, labels: *const u32, n_groups: u32, opts: *const SrxRankGenesOpts,
+                                 out: *mut *mut SrxMarkers) -> i32;
+    pub fn srx_rank_genes_groups_graph(m: *mut SrxMat, g: *mut SrxGraph, opts: *const SrxRankGenesOpts,
+                                       out: *mut *mut SrxMarkers) -> i32;
+    pub fn srx_markers_info_get(mk: *const SrxMarkers, info: *mut SrxMarkersInfo) -> i32;
+    pub fn srx_markers_fetch_top(mk: *mut SrxMarkers, genes_out: *mut u32, scores_out: *mut f64, lfc_out: *mut f64) -> i32;
+    pub fn srx_markers_fetch_table(mk: *mut SrxMarkers, which: i32, out: *mut c_void) -> i32;
+    pub fn srx_markers_fetch_sizes(mk: *mut SrxMarkers, n_cells_out: *mut u64) -> i32;
+    pub fn srx_markers_free(mk: *mut SrxMarkers);
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,

@@ -97,6 +97,21 @@ class LouvainInfo(C.Structure):
                 ("level_communities", C.c_uint64 * LOUVAIN_MAX_LEVELS), ("level_modularity", C.c_double * LOUVAIN_MAX_LEVELS)]
 
 
+GROUPS_MAX = 4096
+(MARKERS_CNT, MARKERS_SUM, MARKERS_SUMSQ, MARKERS_MEAN, MARKERS_VAR, MARKERS_MEAN_REST, MARKERS_VAR_REST, MARKERS_SCORE,
+ MARKERS_LFC, MARKERS_PCT, MARKERS_PCT_REST) = range(11)
+
+
+class RankGenesOpts(C.Structure):
+    _fields_ = [("n_top", C.c_int32), ("logged", C.c_int32)]
+
+
+class MarkersInfo(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("n_groups", C.c_uint32), ("n_top", C.c_uint32),
+                ("sum_scale_log2", C.c_int32), ("sq_scale_log2", C.c_int32), ("groups_degenerate", C.c_uint32),
+                ("reserved_", C.c_uint32), ("max_abs", C.c_double), ("ms", C.c_double)]
+
+
 class SynthParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_rows_global", C.c_uint64), ("n_cols", C.c_uint64),
                 ("density", C.c_double), ("lib_sigma", C.c_double), ("type_decay", C.c_double),
@@ -177,6 +192,14 @@ _SIGS = {
     "srx_louvain": (C.c_int32, [P, C.POINTER(LouvainOpts), P, C.POINTER(LouvainInfo)]),
     "srx_louvain_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(LouvainOpts), P, C.POINTER(LouvainInfo)]),
     "srx_graph_labels_fetch": (C.c_int32, [P, P]),
+    "srx_group_moments": (C.c_int32, [P, P, C.c_uint32, P, P, P, P]),
+    "srx_rank_genes_groups": (C.c_int32, [P, P, C.c_uint32, C.POINTER(RankGenesOpts), C.POINTER(P)]),
+    "srx_rank_genes_groups_graph": (C.c_int32, [P, P, C.POINTER(RankGenesOpts), C.POINTER(P)]),
+    "srx_markers_info_get": (C.c_int32, [P, C.POINTER(MarkersInfo)]),
+    "srx_markers_fetch_top": (C.c_int32, [P, P, P, P]),
+    "srx_markers_fetch_table": (C.c_int32, [P, C.c_int32, P]),
+    "srx_markers_fetch_sizes": (C.c_int32, [P, P]),
+    "srx_markers_free": (None, [P]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),

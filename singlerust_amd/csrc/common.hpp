@@ -60,6 +60,14 @@ __device__ __forceinline__ T wave_max(T v) {
     return v;
 }
 
+// row r's entries in gene tile `tile`: [lo, hi) — indptr and the cached interior tile cuts of a matrix (ensure_tiles: d_tile_ptr)
+__device__ __forceinline__ void seg_bounds(const int64_t* __restrict__ indptr, const int64_t* __restrict__ tp,
+                                           uint64_t n_rows, int n_tiles, int tile, uint64_t r,
+                                           int64_t& lo, int64_t& hi) {
+    lo = tile == 0 ? indptr[r] : tp[(uint64_t)(tile - 1) * n_rows + r];
+    hi = tile == n_tiles - 1 ? indptr[r + 1] : tp[(uint64_t)tile * n_rows + r];
+}
+
 // ---- profiling accumulators ---------------------------------------------------------------
 struct ProfAcc {
     double ms = 0.0;

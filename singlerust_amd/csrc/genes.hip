@@ -51,13 +51,6 @@ __global__ void k_tile_ptr(const int64_t* __restrict__ indptr, const E* __restri
     }
 }
 
-__device__ __forceinline__ void seg_bounds(const int64_t* __restrict__ indptr, const int64_t* __restrict__ tp,
-                                           uint64_t n_rows, int n_tiles, int tile, uint64_t r,
-                                           int64_t& lo, int64_t& hi) {
-    lo = tile == 0 ? indptr[r] : tp[(uint64_t)(tile - 1) * n_rows + r];
-    hi = tile == n_tiles - 1 ? indptr[r + 1] : tp[(uint64_t)tile * n_rows + r];
-}
-
 // The two value passes of the reference over the columns — scatter-add of x (csr.rs:94-100) and of x^2 (csr.rs:175-178) — in
 // ONE walk; the third, the histogram of the indices (csr.rs:29-36), depends on the pattern only and is k_gene_count's.
 // XF: the values are the RAW matrix and x = ln_1p(f64(v) * scale_row) is formed on the fly in f64 (RowXf, common.hpp):

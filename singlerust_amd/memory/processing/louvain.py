@@ -38,6 +38,7 @@ def louvain(adata: IMAnnData, resolution: float = 1.0, key_added: str = "louvain
     opts = _opts(resolution, min_gain, max_levels, max_sweeps)
     F.check(F.lib().srx_louvain(g.handle, C.byref(opts), F.ptr(labels) if labels.size else None, C.byref(info)), g.ctx.handle)
     adata.obs[key_added] = labels
+    g.labels_key = key_added          # whose labels the handle holds now (rank_genes_groups reads them where they lie)
     adata.uns[key_added] = {"params": {"resolution": float(resolution), "min_gain": float(min_gain), "max_levels": int(max_levels),
                                        "max_sweeps": int(max_sweeps)}, "info": _info_dict(info)}
     return adata.uns[key_added]["info"]
