@@ -588,6 +588,87 @@ int32_t srx_markers_fetch_table(srx_markers* mk, int32_t which, void* out);
 int32_t srx_markers_fetch_sizes(srx_markers* mk, uint64_t* n_cells_out);   /* n_groups */
 void    srx_markers_free(srx_markers* mk);
 
+/* ---- UMAP layout of a symmetric weighted graph in 2 or 3 dimensions: what sc.tl.umap gives obsm["X_umap"] -----------------
+ * Not in the reference (it stops at plot_pca and a commented-out tsne).  This is umap-learn's optimize_layout_euclidean
+ * RESTATED as a synchronous, vertex-owned iteration so that the result is bit-identical from call to call (the original
+ * lets threads add into positions that other threads are reading).  The definition here is what is tested; the output has
+ * NOT been compared with umap-learn, which is not installed where this was built.
+ *
+ * Input: a symmetric graph W as CSR with exactly the contract of srx_louvain_csr (u64 indptr, u32 indices strictly
+ *   ascending within a row, f64 weights > 0, no diagonal, W_ij and W_ji the same bits); nnz stored entries, entry e is its
+ *   position in that CSR; n < 2^32; dim = n_components (2 or 3); E = n_epochs; curve parameters a, b > 0; gamma (repulsion
+ *   strength); R = negative_sample_rate (0..32); alpha0; a 64-bit seed; start positions Y^0 (n x dim f64, finite).
+ * Schedule (stateless).  w_max = the largest stored weight, r_e = w_e / w_max (one f64 division), c_e(t) = floor(t * r_e)
+ *   in f64 (t converted to f64, one multiplication).  Entry e is SAMPLED in epoch t (t = 1..E) iff c_e(t) > c_e(t - 1).  An
+ *   entry with c_e(E) = 0 never acts (umap-learn's pruning of weights below max / n_epochs); info.entries_active counts the
+ *   entries with c_e(E) > 0.
+ * Negative samples.  mix(z) is splitmix64's finaliser: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *   z *= 0x94D049BB133111EB; z ^= z >> 31 (all mod 2^64).  For a sampled entry e in epoch t and p = 0..R-1:
+ *   z = mix(seed + 0x9E3779B97F4A7C15 * (1 + (t * nnz + e) * R + p))  (mod 2^64),  target k = ((z >> 32) * n) >> 32.
+ * Epoch t.  Every vertex i reads only Y^{t-1}.  alpha_t = alpha0 * (1 - (t - 1) / E).  All arithmetic is f64, every operation
+ *   rounded once (no FMA contraction), d2 summed over the coordinates in ascending order.
+ *   For every sampled entry (i, j) of row i:
+ *     attraction: d2 = |y_i - y_j|^2;  q = ((-2 a b) * d2^(b-1)) / (a * d2^b + 1) if d2 > 0, else 0;
+ *                 g = clip(q * (y_i - y_j), -4, 4) per coordinate;  delta_i += (2 alpha_t) * g.
+ *       The factor 2 is the head move of (i, j) plus the tail move of (j, i): the same vector, because W is bit-symmetric,
+ *       both entries carry the same schedule, and both ends are read as they stood before the epoch.
+ *     repulsion, for each of its R targets k:  k == i is skipped and counted in info.negatives_skipped; otherwise
+ *       d2 = |y_i - y_k|^2; if d2 > 0: q = (2 gamma b) / ((0.001 + d2) * (a * d2^b + 1)), g = clip(q * (y_i - y_k), -4, 4),
+ *       delta_i += alpha_t * g; if d2 == 0 nothing is added.
+ *   Then Y^t = Y^{t-1} + delta.  The sum of a row's terms may be taken in any order that is fixed by (n, indptr) alone: here
+ *   SRX_UMAP_GROUP lanes own a vertex, lane s sums the terms of the entries lo + s, lo + s + SRX_UMAP_GROUP, ... of its row
+ *   in that order (an entry's attraction, then its targets p = 0..R-1), and the lanes' sums meet in a butterfly.  The result
+ *   is bit-identical from call to call.  x^y is the device library's pow(double, double) (ocml, documented to 1 ulp; not
+ *   -ffast-math, no native_ / half_ variant).
+ * stop_after = s (0 = E) runs only epochs 1..s of the E-epoch schedule.
+ * Counters, exact integers: samples = the sampled (entry, epoch) pairs of the epochs run; negatives_skipped;
+ *   negatives = samples * R - negatives_skipped; entries_active.
+ * Starts.  SRX_UMAP_INIT_GIVEN: `init`, a host pointer to n x dim f64.  SRX_UMAP_INIT_RANDOM: coordinate c = i * dim + j is
+ *   -10 + 20 * ((mix(seed + 0x9E3779B97F4A7C15 * (c + 1)) >> 11) * 2^-53).  SRX_UMAP_INIT_PCA: the first dim columns of the
+ *   scores the last fit left on the matrix handle, each times s = 10 / max |score| over those columns (s one f64 division);
+ *   read on the device, deterministic.
+ * Curve.  srx_umap_fit_ab(spread, min_dist) is host only: the least-squares fit of 1 / (1 + a x^(2b)) to y(x) = 1 for
+ *   x < min_dist and exp(-(x - min_dist) / spread) otherwise, on 300 equally spaced x in [0, 3 spread], by a two-parameter
+ *   Levenberg-Marquardt from (1, 1).  opts.a == opts.b == 0 means "fit from min_dist, spread".
+ * Defaults (NULL opts): min_dist 0.5, spread 1.0 (scanpy's), gamma 1, alpha0 1, R 5, dim 2, seed 0, the PCA start;
+ *   n_epochs == 0 means 500 for n <= 10 000, else 200.
+ * Out of scope: spectral initialisation, transforming new points, densMAP, supervised and non-Euclidean outputs.
+ * Refused with SRX_E_ARG and a message, nothing written: dim not 2 or 3; R outside 0..32; a, b (unless both 0), gamma,
+ *   alpha0 or spread not finite or <= 0; min_dist < 0 or > spread (or NaN); n_epochs < 0 or > 2^20; stop_after < 0 or
+ *   > n_epochs; an unknown start; a NaN or Inf start; the PCA start without a usable result (none, or fewer than dim
+ *   components), with m's n_rows != n, or with m on another context; SRX_UMAP_INIT_GIVEN with init == NULL; a context with
+ *   more than one rank; for srx_umap_csr also everything srx_louvain_csr refuses, and the PCA start (there is no matrix).
+ * n = 0 gives an empty result; a graph without entries returns the start unchanged with samples = 0. */
+#define SRX_UMAP_GROUP 8         /* lanes that own one vertex */
+#define SRX_UMAP_MAX_EPOCHS 1048576
+enum { SRX_UMAP_INIT_GIVEN = 0, SRX_UMAP_INIT_RANDOM = 1, SRX_UMAP_INIT_PCA = 2 };
+typedef struct srx_umap_opts {
+    double   a, b;                  /* both 0: fitted from min_dist, spread */
+    double   min_dist, spread, gamma, alpha0;
+    uint64_t seed;
+    int32_t  n_epochs;              /* 0 = 500 for n <= 10 000, else 200 */
+    int32_t  stop_after;            /* 0 = n_epochs */
+    int32_t  n_components, negative_sample_rate, init, reserved_;
+} srx_umap_opts;
+typedef struct srx_umap_info {
+    uint64_t n, nnz, entries_active, samples, negatives, negatives_skipped;
+    uint32_t n_epochs, epochs_run, dim, reserved_;
+    double   a, b, w_max;
+    double   ms;                    /* hipEvent time of the device work */
+} srx_umap_info;
+/* The layout of the handle's connectivities, read where they lie (C and the labels are left untouched).  The embedding stays
+ * on the device with the handle (srx_graph_embedding_fetch).  m: the matrix whose scores start the layout, NULL unless
+ * init = SRX_UMAP_INIT_PCA; init: NULL unless SRX_UMAP_INIT_GIVEN; embedding_out (n x dim f64, row-major) and info may be NULL. */
+int32_t srx_umap(srx_graph* g, srx_mat* m, const srx_umap_opts* opts, const double* init, double* embedding_out,
+                 srx_umap_info* info);
+/* The same on a caller-supplied symmetric graph, validated on the device as srx_louvain_csr validates its input. */
+int32_t srx_umap_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* indices, const double* weights, uint64_t n,
+                     const srx_umap_opts* opts, const double* init, double* embedding_out, srx_umap_info* info);
+/* The last srx_umap's embedding, kept on the device (n x dim f64; dim_out may be NULL).  SRX_E_ARG when none has run. */
+int32_t srx_graph_embedding_fetch(srx_graph* g, double* out, uint32_t* dim_out);
+/* Host only.  SRX_E_ARG: spread or min_dist not finite, spread <= 0, min_dist < 0 or > spread, a null output. */
+int32_t srx_umap_fit_ab(double spread, double min_dist, double* a, double* b);
+
 /* The raw operators the PCA is built from, for a caller-supplied 64-column panel (k x 64
  * row-major): y_out (n_rows x 64) = X[:, sel] * panel, t_out (k x 64) = X[:, sel]^T * y, and
  * gram_out (k x k) = X[:, sel]^T X[:, sel] (panel not needed).  `sel` must be strictly

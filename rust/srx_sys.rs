@@ -10,6 +10,8 @@ pub const SRX_UNIQUE_ID_BYTES: usize = 128;
 pub const SRX_KNN_MAX_DIMS: i32 = 128;
 pub const SRX_LOUVAIN_MAX_LEVELS: i32 = 32;
 pub const SRX_GROUPS_MAX: i32 = 4096;
+pub const SRX_UMAP_GROUP: i32 = 8;
+pub const SRX_UMAP_MAX_EPOCHS: i32 = 1048576;
 pub const SRX_OK: i32 = 0;
 pub const SRX_E_ARG: i32 = -1;
 pub const SRX_E_DTYPE: i32 = -2;
@@ -55,6 +57,9 @@ pub const SRX_MARKERS_SCORE: i32 = 7;
 pub const SRX_MARKERS_LFC: i32 = 8;
 pub const SRX_MARKERS_PCT: i32 = 9;
 pub const SRX_MARKERS_PCT_REST: i32 = 10;
+pub const SRX_UMAP_INIT_GIVEN: i32 = 0;
+pub const SRX_UMAP_INIT_RANDOM: i32 = 1;
+pub const SRX_UMAP_INIT_PCA: i32 = 2;
 pub const SRX_BACKED_NORMALIZE: i32 = 1;
 pub const SRX_BACKED_LOG1P: i32 = 2;
 pub const SRX_K_NORMALIZE: i32 = 0;
@@ -225,6 +230,43 @@ pub struct SrxMarkersInfo {      // `srx_markers_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxUmapOpts {      // `srx_umap_opts`
+    pub a: f64,
+    pub b: f64,
+    pub min_dist: f64,
+    pub spread: f64,
+    pub gamma: f64,
+    pub alpha0: f64,
+    pub seed: u64,
+    pub n_epochs: i32,
+    pub stop_after: i32,
+    pub n_components: i32,
+    pub negative_sample_rate: i32,
+    pub init: i32,
+    pub reserved: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxUmapInfo {      // `srx_umap_info`
+    pub n: u64,
+    pub nnz: u64,
+    pub entries_active: u64,
+    pub samples: u64,
+    pub negatives: u64,
+    pub negatives_skipped: u64,
+    pub n_epochs: u32,
+    pub epochs_run: u32,
+    pub dim: u32,
+    pub reserved: u32,
+    pub a: f64,
+    pub b: f64,
+    pub w_max: f64,
+    pub ms: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPipelineResult {      // `srx_pipeline_result`
     pub pca: SrxPcaInfo,
     pub ms_normalize: f64,
@@ -330,6 +372,12 @@ extern "C" {
     pub fn srx_markers_fetch_table(mk: *mut SrxMarkers, which: i32, out: *mut c_void) -> i32;
     pub fn srx_markers_fetch_sizes(mk: *mut SrxMarkers, n_cells_out: *mut u64) -> i32;
     pub fn srx_markers_free(mk: *mut SrxMarkers);
+    pub fn srx_umap(g: *mut SrxGraph, m: *mut SrxMat, opts: *const SrxUmapOpts, init: *const f64,
+                    embedding_out: *mut f64, info: *mut SrxUmapInfo) -> i32;
+    pub fn srx_umap_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,
+                        opts: *const SrxUmapOpts, init: *const f64, embedding_out: *mut f64, info: *mut SrxUmapInfo) -> i32;
+    pub fn srx_graph_embedding_fetch(g: *mut SrxGraph, out: *mut f64, dim_out: *mut u32) -> i32;
+    pub fn srx_umap_fit_ab(spread: f64, min_dist: f64, a: *mut f64, b: *mut f64) -> i32;
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,

@@ -112,6 +112,24 @@ class MarkersInfo(C.Structure):
                 ("reserved_", C.c_uint32), ("max_abs", C.c_double), ("ms", C.c_double)]
 
 
+UMAP_GROUP = 8
+UMAP_MAX_EPOCHS = 1 << 20
+UMAP_INIT_GIVEN, UMAP_INIT_RANDOM, UMAP_INIT_PCA = 0, 1, 2
+
+
+class UmapOpts(C.Structure):
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("min_dist", C.c_double), ("spread", C.c_double), ("gamma", C.c_double),
+                ("alpha0", C.c_double), ("seed", C.c_uint64), ("n_epochs", C.c_int32), ("stop_after", C.c_int32),
+                ("n_components", C.c_int32), ("negative_sample_rate", C.c_int32), ("init", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class UmapInfo(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("entries_active", C.c_uint64), ("samples", C.c_uint64),
+                ("negatives", C.c_uint64), ("negatives_skipped", C.c_uint64), ("n_epochs", C.c_uint32), ("epochs_run", C.c_uint32),
+                ("dim", C.c_uint32), ("reserved_", C.c_uint32), ("a", C.c_double), ("b", C.c_double), ("w_max", C.c_double),
+                ("ms", C.c_double)]
+
+
 class SynthParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_rows_global", C.c_uint64), ("n_cols", C.c_uint64),
                 ("density", C.c_double), ("lib_sigma", C.c_double), ("type_decay", C.c_double),
@@ -200,6 +218,10 @@ _SIGS = {
     "srx_markers_fetch_table": (C.c_int32, [P, C.c_int32, P]),
     "srx_markers_fetch_sizes": (C.c_int32, [P, P]),
     "srx_markers_free": (None, [P]),
+    "srx_umap": (C.c_int32, [P, P, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
+    "srx_umap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
+    "srx_graph_embedding_fetch": (C.c_int32, [P, P, C.POINTER(C.c_uint32)]),
+    "srx_umap_fit_ab": (C.c_int32, [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),

@@ -1,4 +1,5 @@
-// graph_handle.hpp — the srx_graph handle of srx.h: built by graph.hip, read where it lies by the graph algorithms (louvain.hip).
+// graph_handle.hpp — the srx_graph handle of srx.h: built by graph.hip, read where it lies by the graph algorithms (louvain.hip,
+// umap.hip).
 #pragma once
 
 #include "common.hpp"
@@ -21,4 +22,8 @@ struct srx_graph {
     // the labels of the last srx_louvain on this handle (louvain.hip): n u32, allocated by the first call
     uint32_t* d_labels = nullptr;
     bool labels_valid = false;
+    // the embedding of the last srx_umap on this handle (umap.hip): n x embed_dim f64, row-major
+    double* d_embed = nullptr;
+    uint32_t embed_dim = 0;
+    bool embed_valid = false;
 };

@@ -19,7 +19,7 @@
 // first, coarser scale), and every level's 2m is read back and checked against the range.
 //
 // Kernels:
-//   k_louvain_check     (srx_louvain_csr) wave per row: index range, diagonal, order, weights, W_ij == W_ji by binary search
+//   k_louvain_check     (srx_louvain_csr; symcsr_check.hpp) wave per row: index range, diagonal, order, weights, W_ij == W_ji
 //   k_louvain_degree    thread per row: k_i in row order, singleton start, max k_i
 //   k_louvain_scale     one thread: S from max k_i * n, then from 2m; 2m of the level
 //   k_louvain_quant     q(k_i), tot of the singletons, their sum
@@ -42,6 +42,7 @@
 #include "common.hpp"
 #include "graph_handle.hpp"
 #include "scan.hpp"
+#include "symcsr_check.hpp"
 
 #include <cmath>
 
@@ -53,7 +54,6 @@ constexpr uint32_t kLvEmpty = 0xFFFFFFFFu;
 // the small block (8-byte words)
 enum { LV_KMAX = 0, LV_MOVES, LV_NCOMM, LV_FLAG, LV_SHIFT, LV_SCALE, LV_INV, LV_TWOM, LV_WSCALE, LV_WINV, LV_ACC, LV_IN = LV_ACC + kLvSlots,
        LV_SQ = LV_IN + kLvSlots, LV_WORDS = LV_SQ + kLvSlots };
-enum { kLvBadRange = 1, kLvBadDiag = 2, kLvBadOrder = 4, kLvBadWeight = 8, kLvBadSym = 16 };
 
 struct LvGraph {                         // one level's graph; self == nullptr: no self weights (the input)
     const uint64_t* ptr;
@@ -67,39 +67,6 @@ __device__ __forceinline__ long long lv_fix(double x, double scale) { return __d
 __device__ __forceinline__ void lv_slot_add(unsigned long long* slots, long long v) {
     v = wave_sum(v);
     if (lane_id() == 0 && v) atomicAdd(&slots[(blockIdx.x * 4 + (threadIdx.x >> 6)) & (kLvSlots - 1)], (unsigned long long)v);
-}
-
-__global__ void __launch_bounds__(256) k_louvain_check(const uint64_t* __restrict__ ptr, const uint32_t* __restrict__ ind,
-                                                       const double* __restrict__ w, uint64_t n, unsigned long long* __restrict__ small) {
-    const int lane = lane_id();
-    const uint64_t row = global_wave_id();
-    if (row >= n) return;
-    const uint64_t lo = ptr[row], hi = ptr[row + 1];
-    int bad = 0;
-    for (uint64_t e = lo + lane; e < hi; e += kWave) {
-        const uint32_t j = ind[e];
-        const double v = w[e];
-        if (!(v > 0.0 && v <= 1.79769313486231570815e308)) bad |= kLvBadWeight;
-        if (e > lo && ind[e - 1] >= j) bad |= kLvBadOrder;
-        if (j >= n) {
-            bad |= kLvBadRange;
-            continue;
-        }
-        if (j == row) {
-            bad |= kLvBadDiag;
-            continue;
-        }
-        // the entry (j, row): a binary search stays inside row j whatever its order
-        uint64_t a = ptr[j], b = ptr[j + 1];
-        const uint64_t end = b;
-        while (a < b) {
-            const uint64_t mid = a + ((b - a) >> 1);
-            if (ind[mid] < (uint32_t)row) a = mid + 1;
-            else b = mid;
-        }
-        if (!(a < end && ind[a] == (uint32_t)row && __double_as_longlong(w[a]) == __double_as_longlong(v))) bad |= kLvBadSym;
-    }
-    if (bad) atomicOr(&small[LV_FLAG], (unsigned long long)bad);
 }
 
 __global__ void __launch_bounds__(256) k_louvain_degree(LvGraph g, double* __restrict__ kdeg, uint32_t* __restrict__ comm,
@@ -801,40 +768,12 @@ int32_t srx_louvain_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* in
         if (info) *info = li;
         return SRX_OK;
     }
-    if (!indptr) return fail(ctx, SRX_E_ARG, "louvain: null indptr");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, SRX_E_ARG, "louvain: more than 2^32 - 2 vertices");
-    // the row offsets are checked here: everything on the device indexes through them
-    if (indptr[0] != 0) return fail(ctx, SRX_E_ARG, "louvain: indptr[0] is not 0");
-    for (uint64_t i = 0; i < n; ++i)
-        if (indptr[i + 1] < indptr[i]) return fail(ctx, SRX_E_ARG, "louvain: indptr decreases at row %llu", (unsigned long long)i);
-    const uint64_t nnz = indptr[n];
-    if (nnz && (!indices || !weights)) return fail(ctx, SRX_E_ARG, "louvain: null indices or weights");
     Range rg("louvain");
-    uint64_t* d_ptr;
-    uint32_t *d_ind, *d_labels;
-    double* d_w;
-    unsigned long long* d_small;
-    SRX_TRY(scratch(ctx, "louvain_in_ptr", (n + 1) * 8, (void**)&d_ptr));
-    SRX_TRY(scratch(ctx, "louvain_in_ind", at_least_one(nnz) * 4, (void**)&d_ind));
-    SRX_TRY(scratch(ctx, "louvain_in_w", at_least_one(nnz) * 8, (void**)&d_w));
+    SymCsrDev in;
+    SRX_TRY(symcsr_to_device(ctx, "louvain", indptr, indices, weights, n, &in));
+    uint32_t* d_labels;
     SRX_TRY(scratch(ctx, "louvain_labels", n * 4, (void**)&d_labels));
-    SRX_TRY(scratch(ctx, "louvain_small", LV_WORDS * 8, (void**)&d_small));
-    SRX_TRY(h2d(ctx, d_ptr, indptr, (n + 1) * 8));
-    if (nnz) {
-        SRX_TRY(h2d(ctx, d_ind, indices, nnz * 4));
-        SRX_TRY(h2d(ctx, d_w, weights, nnz * 8));
-    }
-    SRX_HIP(ctx, hipMemsetAsync(d_small + LV_FLAG, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_louvain_check, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, d_ptr, d_ind, d_w, n, d_small);
-    SRX_HIP(ctx, hipGetLastError());
-    uint64_t flag = 0;
-    SRX_TRY(d2h(ctx, &flag, d_small + LV_FLAG, 8));
-    if (flag & kLvBadRange) return fail(ctx, SRX_E_ARG, "louvain: a column index is not below n = %llu", (unsigned long long)n);
-    if (flag & kLvBadDiag) return fail(ctx, SRX_E_ARG, "louvain: the graph has a diagonal entry");
-    if (flag & kLvBadOrder) return fail(ctx, SRX_E_ARG, "louvain: the columns of a row are not strictly ascending");
-    if (flag & kLvBadWeight) return fail(ctx, SRX_E_ARG, "louvain: a weight is <= 0, NaN or Inf");
-    if (flag & kLvBadSym) return fail(ctx, SRX_E_ARG, "louvain: the graph is not symmetric (W[i,j] and W[j,i] must both be stored, with the same bits)");
-    SRX_TRY(louvain_run(ctx, d_ptr, d_ind, d_w, n, nnz, o, d_labels, &li));
+    SRX_TRY(louvain_run(ctx, in.ptr, in.ind, in.w, n, in.nnz, o, d_labels, &li));
     if (labels_out) SRX_TRY(d2h(ctx, labels_out, d_labels, n * 4));
     if (info) *info = li;
     return SRX_OK;

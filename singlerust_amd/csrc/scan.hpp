@@ -1,4 +1,4 @@
-// scan.hpp — device-side prefix sums and bitmap ranks, stated once for every kernel that needs one (device code only;
+// scan.hpp — device-side prefix sums, lane-group sums and bitmap ranks, stated once for every kernel that needs one (device code only;
 // scan.hip has the device-wide scan_exclusive built on them).
 #pragma once
 
@@ -36,6 +36,16 @@ __device__ __forceinline__ T block_scan_exclusive(T v, T* s_wave, T& total) {
         total += t;
     }
     return before + inc - v;
+}
+
+// Sum of v over each aligned group of G consecutive lanes (G a power of two <= 64), in every lane of the group: a butterfly
+// of log2(G) steps whose shape depends on G alone, so a floating-point sum is the same bits from call to call.  ALL 64
+// LANES MUST BE ACTIVE, as for the scan above.
+template <int G, typename T>
+__device__ __forceinline__ T group_sum(T v) {
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
+    return v;
 }
 
 // ---- bitmap ranks: one bit per key in `bits`, pre[w] = set bits in the words before w; the place of key s among the set

@@ -11,6 +11,7 @@ from . import dim_red
 from .louvain import graph_labels, louvain, louvain_csr
 from .markers import group_moments, rank_genes_groups
 from .neighbors import connectivities_from_knn, knn_points, neighbors
+from .umap import fit_ab, graph_embedding, umap, umap_csr
 
 
 def normalize_total_inplace(adata: IMAnnData, target_sum: float, direction: Direction) -> None:
