@@ -564,7 +564,8 @@ typedef struct srx_markers_info {
 } srx_markers_info;
 enum { SRX_MARKERS_CNT = 0, SRX_MARKERS_SUM = 1, SRX_MARKERS_SUMSQ = 2, SRX_MARKERS_MEAN = 3, SRX_MARKERS_VAR = 4,
        SRX_MARKERS_MEAN_REST = 5, SRX_MARKERS_VAR_REST = 6, SRX_MARKERS_SCORE = 7, SRX_MARKERS_LFC = 8, SRX_MARKERS_PCT = 9,
-       SRX_MARKERS_PCT_REST = 10 };
+       SRX_MARKERS_PCT_REST = 10,
+       SRX_MARKERS_RANKSUM2 = 11 /* u64; a handle of srx_rank_genes_wilcoxon only (below) */ };
 /* The primitive (pseudobulk sums, dot-plot fractions): labels = n_rows host u32, each < n_groups; n_cells_out n_groups u64;
  * cnt_out (u64), sum_out, sumsq_out (f64) n_groups x n_cols row-major; any output may be NULL.
  * Refusals of this and the two calls below, each with a message.  SRX_E_ARG: n_groups outside 1 .. SRX_GROUPS_MAX, a label
@@ -587,6 +588,65 @@ int32_t srx_markers_fetch_top(srx_markers* mk, uint32_t* genes_out, double* scor
 int32_t srx_markers_fetch_table(srx_markers* mk, int32_t which, void* out);
 int32_t srx_markers_fetch_sizes(srx_markers* mk, uint64_t* n_cells_out);   /* n_groups */
 void    srx_markers_free(srx_markers* mk);
+
+/* ---- marker genes per group: the Wilcoxon rank-sum statistic, group against rest, from exact grouped rank sums ---------
+ * What sc.tl.rank_genes_groups(method="wilcoxon") gives uns["rank_genes_groups"].  Not in the reference; the definition here
+ * is what is tested.  The output has NOT been compared with scanpy (scanpy is not installed where this was built); the rank
+ * sums of the host test reference equal scipy.stats.rankdata / mannwhitneyu, its tie-corrected scores give scipy's p-value.
+ *
+ * Input: that of srx_rank_genes_groups.  Per gene j the column holds N values: its c_j stored entries and N - c_j implicit
+ * zeros.
+ * Ordering.  Values are compared as real numbers, each storage (f32, f64) in its own precision; a stored 0.0 or -0.0 ties
+ *   with the implicit zeros; NaN / Inf are refused (SRX_E_NAN).
+ * Doubled rank.  A value whose tie run has t members, with b strictly smaller values in the column, has r2 = 2 b + t + 1:
+ *   twice the average rank (scipy's rankdata), always an integer.
+ * Rank sums.  R2[g][j] = the sum of r2 over the cells of group g (u64); the implicit zeros of group g contribute
+ *   (n_g - c_gj) r2_zero, c_gj the stored count of the grouped moments.  The sum over g of R2[g][j] is N (N + 1) for every gene.
+ * Tie term.  T[j] = the sum over the column's tie runs of t^3 - t (u64); computed only with tie_correct.
+ * Score, all f64, no FMA contraction, in exactly this order (n_r = N - n_g):
+ *   num = (double)(int64)(R2 - n_g (N + 1)) * 0.5                     (the subtraction in integers)
+ *   tc  = 1.0 - (double)T / (double)(N^3 - N)  with tie_correct and N >= 2 (N^3 - N formed as an integer), else 1.0
+ *   d   = (((double)(n_g n_r) * (double)(N + 1)) / 12.0) * tc           (n_g n_r formed as an integer)
+ *   score = num / sqrt(d) when d > 0, else 0
+ * This is scanpy's z (tie_correct = 0 is scanpy's default); with tie_correct it is the asymptotic Mann-Whitney z without
+ * continuity correction.  A group with n_g == 0 or n_r == 0 is degenerate: its scores are 0 and info.groups_degenerate counts
+ * it (the t-test's rule, n < 2, still governs VAR / VAR_REST).  Ranking as above: score descending, gene index ascending.
+ * Everything is integer arithmetic up to the score, so R2, T, the scores and the top lists are exact, independent of the order
+ * of the rows and bit-identical from call to call, whatever the staging order and however the genes were chunked.
+ * The other tables (CNT, SUM, SUMSQ, MEAN, VAR, PCT, LFC, the _REST ones) are those of srx_rank_genes_groups for the same
+ * input, from the same grouped moments. */
+typedef struct srx_wilcoxon_opts {
+    int32_t n_top;             /* as srx_rank_genes_opts                                                                */
+    int32_t logged;            /* as srx_rank_genes_opts                                                                */
+    int32_t tie_correct;       /* non-zero: form T and apply tc                                                         */
+    int32_t reserved_;
+    uint64_t scratch_bytes;    /* cap of the gene-major staging buffer (both sides of the sort's ping-pong: 12 B per
+                                  stored entry at f32 storage, 20 B at f64); the genes are cut into chunks that fit.  0 =
+                                  2 GiB.  A cap below the longest single gene is raised to fit that gene and reported in
+                                  srx_wilcoxon_info.scratch_bytes, not refused.  (The tile table of the long-segment sort,
+                                  about 1 B per entry of a long segment, is not counted.)  The buffer and that table are
+                                  allocated by the call and released before it returns: a context keeps neither.
+                                  NULL opts = {0, -1, 0, 0, 0}                                                          */
+} srx_wilcoxon_opts;
+typedef struct srx_wilcoxon_info {
+    int32_t tie_correct;
+    uint32_t n_chunks;         /* gene chunks the staging was cut into                                                  */
+    uint64_t scratch_bytes;    /* staging bytes the largest chunk used                                                  */
+    uint64_t segment_limit;    /* the longest stored segment (entries of one gene) the one-workgroup LDS sort takes      */
+    uint64_t segments_short;   /* genes with 1 .. segment_limit stored entries                                          */
+    uint64_t segments_long;    /* genes with more: the radix route                                                      */
+    double ms_stage, ms_sort, ms_ranks;   /* hipEvent times, summed over the chunks; part of srx_markers_info.ms        */
+} srx_wilcoxon_info;
+/* Refusals as srx_rank_genes_groups[_graph], and SRX_E_ARG for n_rows >= 2^31 (the doubled rank sums must stay below 2^63)
+ * and for tie_correct with n_rows > 2^21 (N^3 - N must fit 64 bits).  m is never modified.  The result is an ordinary
+ * srx_markers: srx_markers_info_get, _fetch_top, _fetch_table (SRX_MARKERS_SCORE is the score above), _fetch_sizes, _free. */
+int32_t srx_rank_genes_wilcoxon(srx_mat* m, const uint32_t* labels, uint32_t n_groups, const srx_wilcoxon_opts* opts,
+                                srx_markers** out);
+int32_t srx_rank_genes_wilcoxon_graph(srx_mat* m, srx_graph* g, const srx_wilcoxon_opts* opts, srx_markers** out);
+/* T, n_cols u64.  SRX_E_ARG unless the handle was made by srx_rank_genes_wilcoxon with tie_correct. */
+int32_t srx_markers_fetch_ties(srx_markers* mk, uint64_t* out);
+/* SRX_E_ARG on a handle of the t-test. */
+int32_t srx_markers_wilcoxon_info_get(const srx_markers* mk, srx_wilcoxon_info* info);
 
 /* ---- UMAP layout of a symmetric weighted graph in 2 or 3 dimensions: what sc.tl.umap gives obsm["X_umap"] -----------------
  * Not in the reference (it stops at plot_pca and a commented-out tsne).  This is umap-learn's optimize_layout_euclidean

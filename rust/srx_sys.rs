@@ -57,6 +57,7 @@ pub const SRX_MARKERS_SCORE: i32 = 7;
 pub const SRX_MARKERS_LFC: i32 = 8;
 pub const SRX_MARKERS_PCT: i32 = 9;
 pub const SRX_MARKERS_PCT_REST: i32 = 10;
+pub const SRX_MARKERS_RANKSUM2: i32 = 11;
 pub const SRX_UMAP_INIT_GIVEN: i32 = 0;
 pub const SRX_UMAP_INIT_RANDOM: i32 = 1;
 pub const SRX_UMAP_INIT_PCA: i32 = 2;
@@ -230,6 +231,30 @@ pub struct SrxMarkersInfo {      // `srx_markers_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxWilcoxonOpts {      // `srx_wilcoxon_opts`
+    pub n_top: i32,
+    pub logged: i32,
+    pub tie_correct: i32,
+    pub reserved: i32,
+    pub scratch_bytes: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxWilcoxonInfo {      // `srx_wilcoxon_info`
+    pub tie_correct: i32,
+    pub n_chunks: u32,
+    pub scratch_bytes: u64,
+    pub segment_limit: u64,
+    pub segments_short: u64,
+    pub segments_long: u64,
+    pub ms_stage: f64,
+    pub ms_sort: f64,
+    pub ms_ranks: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxUmapOpts {      // `srx_umap_opts`
     pub a: f64,
     pub b: f64,
@@ -372,6 +397,12 @@ extern "C" {
     pub fn srx_markers_fetch_table(mk: *mut SrxMarkers, which: i32, out: *mut c_void) -> i32;
     pub fn srx_markers_fetch_sizes(mk: *mut SrxMarkers, n_cells_out: *mut u64) -> i32;
     pub fn srx_markers_free(mk: *mut SrxMarkers);
+    pub fn srx_rank_genes_wilcoxon(m: *mut SrxMat, labels: *const u32, n_groups: u32, opts: *const SrxWilcoxonOpts,
+                                   out: *mut *mut SrxMarkers) -> i32;
+    pub fn srx_rank_genes_wilcoxon_graph(m: *mut SrxMat, g: *mut SrxGraph, opts: *const SrxWilcoxonOpts,
+                                         out: *mut *mut SrxMarkers) -> i32;
+    pub fn srx_markers_fetch_ties(mk: *mut SrxMarkers, out: *mut u64) -> i32;
+    pub fn srx_markers_wilcoxon_info_get(mk: *const SrxMarkers, info: *mut SrxWilcoxonInfo) -> i32;
     pub fn srx_umap(g: *mut SrxGraph, m: *mut SrxMat, opts: *const SrxUmapOpts, init: *const f64,
                     embedding_out: *mut f64, info: *mut SrxUmapInfo) -> i32;
     pub fn srx_umap_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,

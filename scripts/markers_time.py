@@ -5,7 +5,13 @@ calls after --warmup): info.ms and its stages (the library prints them under SRX
 moments pass (SRX_K_MOMENTS via srx_prof_get) on a handle with the same values in the same process, and a host numpy / scipy
 `onehot @ X` + Welch t-test over the first --host-rows rows of the same matrix.  Report only: prints one JSON document.
 
+With --method wilcoxon the rank-sum route (srx_rank_genes_wilcoxon[_graph]) is timed instead, on one random labelling of 32
+groups and the Louvain labelling: info.ms, the three stage times, the chunks and the staging bytes of srx_wilcoxon_info, beside
+the t-test call on the same input in the same process (the yardstick for everything but the staging, the sort and the ranks)
+and scipy.stats.rankdata / mannwhitneyu over the first --host-rows rows.
+
     python scripts/markers_time.py [--cells 1300000 --genes 28000 --density 0.03 --runs 10 --warmup 2 --host-rows 130000]
+    python scripts/markers_time.py --method wilcoxon [--tie-correct --scratch-bytes B]
 """
 import argparse
 import ctypes as C
@@ -48,6 +54,70 @@ def min_med(v):
     return {"min": round(min(v), 4), "median": round(statistics.median(v), 4)}
 
 
+def wilcoxon_report(a, lib, ctx, m, p, graph, timed, out, rng):
+    """The rank-sum route on random_32 and the Louvain labelling, the t-test call beside it, scipy on a tenth of the rows."""
+    from singlerust_amd import _ffi as F
+    wopts = F.WilcoxonOpts(0, -1, 1 if a.tie_correct else 0, 0, a.scratch_bytes)
+    ropts = F.RankGenesOpts(0, -1)
+    out["method"] = "wilcoxon"
+    out["tie_correct"] = bool(a.tie_correct)
+
+    def timed_wilcoxon(call):
+        ms, stages, wi = [], [], F.WilcoxonInfo()
+        for i in range(a.warmup + a.runs):
+            hk = C.c_void_p()
+            call(hk)
+            info = F.MarkersInfo()
+            F.check(lib.srx_markers_info_get(hk, C.byref(info)), ctx.handle)
+            F.check(lib.srx_markers_wilcoxon_info_get(hk, C.byref(wi)), ctx.handle)
+            lib.srx_markers_free(hk)
+            print("wilcoxon call %d: info.ms %.1f (stage %.1f sort %.1f ranks %.1f), %d chunks" % (i, info.ms, wi.ms_stage, wi.ms_sort, wi.ms_ranks,
+                                                                                                  wi.n_chunks), file=sys.stderr, flush=True)
+            if i >= a.warmup:
+                ms.append(info.ms)
+                stages.append([wi.ms_stage, wi.ms_sort, wi.ms_ranks])
+        st = np.array(stages)
+        r = {"n_groups": int(info.n_groups), "info_ms": min_med(ms), "n_chunks": int(wi.n_chunks), "scratch_bytes": int(wi.scratch_bytes),
+             "segment_limit": int(wi.segment_limit), "segments_short": int(wi.segments_short), "segments_long": int(wi.segments_long)}
+        for j, name in enumerate(("stage", "sort", "ranks")):
+            r[name + "_ms"] = min_med(list(st[:, j]))
+        return r
+
+    labels = rng.integers(0, 32, a.cells).astype(np.uint32)
+    calls = {"random_32": (lambda hk: F.check(lib.srx_rank_genes_wilcoxon(m.handle, F.ptr(labels), 32, C.byref(wopts), C.byref(hk)), ctx.handle),
+                           lambda hk: F.check(lib.srx_rank_genes_groups(m.handle, F.ptr(labels), 32, C.byref(ropts), C.byref(hk)), ctx.handle))}
+    if graph is not None:
+        calls["louvain"] = (lambda hk: F.check(lib.srx_rank_genes_wilcoxon_graph(m.handle, graph, C.byref(wopts), C.byref(hk)), ctx.handle),
+                            lambda hk: F.check(lib.srx_rank_genes_groups_graph(m.handle, graph, C.byref(ropts), C.byref(hk)), ctx.handle))
+    for name, (wx, tt) in calls.items():
+        out["labellings"][name] = {"wilcoxon": timed_wilcoxon(wx), "t_test": timed(tt)}
+
+    # the host: scipy's ranking over the first host_rows rows of the same matrix, 200 genes, one group against the rest
+    import scipy.sparse as sp
+    import scipy.stats
+    nh = min(a.host_rows, a.cells)
+    ip = np.zeros(nh + 1, np.uint64)
+    lib.srx_synth_indptr(C.byref(p), 0, nh, F.ptr(ip))
+    idx, val = np.zeros(int(ip[-1]), np.uint64), np.zeros(int(ip[-1]), np.float32)
+    lib.srx_synth_fill_host(C.byref(p), 0, nh, F.ptr(ip), F.ptr(idx), F.ptr(val))
+    X = sp.csr_matrix((val.astype(np.float64), idx.astype(np.int64), ip.astype(np.int64)), shape=(nh, a.genes))
+    X = sp.diags(1e4 / np.maximum(np.asarray(X.sum(axis=1)).ravel(), 1.0)) @ X
+    X.data = np.log1p(X.data)
+    D = X[:, :200].toarray()
+    lab = rng.integers(0, 32, nh)
+    t0 = time.perf_counter()
+    ranks = scipy.stats.rankdata(D, axis=0)
+    np.stack([ranks[lab == g].sum(axis=0) for g in range(32)])
+    t_rank = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    scipy.stats.mannwhitneyu(D[lab == 0], D[lab != 0], axis=0, use_continuity=False, method="asymptotic")
+    t_mwu = (time.perf_counter() - t0) * 1e3
+    out["host_scipy"] = {"rows": nh, "genes": 200, "rankdata_and_32_group_sums_ms": round(t_rank, 1),
+                         "mannwhitneyu_one_group_ms": round(t_mwu, 1),
+                         "note": "dense columns, on the host CPUs; all %d genes would take %d times as long" % (a.genes, a.genes // 200)}
+    print(json.dumps(out, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=1_300_000)
@@ -58,6 +128,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--host-rows", type=int, default=130_000)
     ap.add_argument("--no-louvain", action="store_true")
+    ap.add_argument("--method", choices=("t-test", "wilcoxon"), default="t-test")
+    ap.add_argument("--tie-correct", action="store_true")
+    ap.add_argument("--scratch-bytes", type=int, default=0)
     a = ap.parse_args()
     import singlerust_amd as sr
     from singlerust_amd import _ffi as F
@@ -104,6 +177,9 @@ def main():
 
     ropts = F.RankGenesOpts(0, -1)
     rng = np.random.default_rng(1)
+    if a.method == "wilcoxon":
+        wilcoxon_report(a, lib, ctx, m, p, graph, timed, out, rng)
+        return
     for k in (8, 32, 256):
         labels = rng.integers(0, k, a.cells).astype(np.uint32)
         out["labellings"]["random_%d" % k] = timed(

@@ -100,6 +100,7 @@ class LouvainInfo(C.Structure):
 GROUPS_MAX = 4096
 (MARKERS_CNT, MARKERS_SUM, MARKERS_SUMSQ, MARKERS_MEAN, MARKERS_VAR, MARKERS_MEAN_REST, MARKERS_VAR_REST, MARKERS_SCORE,
  MARKERS_LFC, MARKERS_PCT, MARKERS_PCT_REST) = range(11)
+MARKERS_RANKSUM2 = 11
 
 
 class RankGenesOpts(C.Structure):
@@ -110,6 +111,17 @@ class MarkersInfo(C.Structure):
     _fields_ = [("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("n_groups", C.c_uint32), ("n_top", C.c_uint32),
                 ("sum_scale_log2", C.c_int32), ("sq_scale_log2", C.c_int32), ("groups_degenerate", C.c_uint32),
                 ("reserved_", C.c_uint32), ("max_abs", C.c_double), ("ms", C.c_double)]
+
+
+class WilcoxonOpts(C.Structure):
+    _fields_ = [("n_top", C.c_int32), ("logged", C.c_int32), ("tie_correct", C.c_int32), ("reserved_", C.c_int32),
+                ("scratch_bytes", C.c_uint64)]
+
+
+class WilcoxonInfo(C.Structure):
+    _fields_ = [("tie_correct", C.c_int32), ("n_chunks", C.c_uint32), ("scratch_bytes", C.c_uint64),
+                ("segment_limit", C.c_uint64), ("segments_short", C.c_uint64), ("segments_long", C.c_uint64),
+                ("ms_stage", C.c_double), ("ms_sort", C.c_double), ("ms_ranks", C.c_double)]
 
 
 UMAP_GROUP = 8
@@ -218,6 +230,10 @@ _SIGS = {
     "srx_markers_fetch_table": (C.c_int32, [P, C.c_int32, P]),
     "srx_markers_fetch_sizes": (C.c_int32, [P, P]),
     "srx_markers_free": (None, [P]),
+    "srx_rank_genes_wilcoxon": (C.c_int32, [P, P, C.c_uint32, C.POINTER(WilcoxonOpts), C.POINTER(P)]),
+    "srx_rank_genes_wilcoxon_graph": (C.c_int32, [P, P, C.POINTER(WilcoxonOpts), C.POINTER(P)]),
+    "srx_markers_fetch_ties": (C.c_int32, [P, P]),
+    "srx_markers_wilcoxon_info_get": (C.c_int32, [P, C.POINTER(WilcoxonInfo)]),
     "srx_umap": (C.c_int32, [P, P, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
     "srx_umap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
     "srx_graph_embedding_fetch": (C.c_int32, [P, P, C.POINTER(C.c_uint32)]),

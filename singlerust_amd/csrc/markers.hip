@@ -39,6 +39,12 @@ struct srx_markers {
     uint32_t* d_top_gene = nullptr;
     double *d_top_score = nullptr, *d_top_lfc = nullptr;
     srx_markers_info info{};
+    // the rank-sum route (wilcoxon.inl): an allocation of its own with the doubled rank sums R2 (n_groups x G u64) and the tie
+    // terms T (G u64); null on a handle of the t-test
+    bool wilcoxon = false;
+    void* d_wx = nullptr;
+    uint64_t *d_R2 = nullptr, *d_T = nullptr;
+    srx_wilcoxon_info winfo{};
 };
 
 namespace srx {
@@ -401,11 +407,16 @@ static void mk_free(srx_markers* mk) {
         (void)hipStreamSynchronize(mk->ctx->stream);
         (void)hipFree(mk->d_block);
     }
+    if (mk->d_wx) {
+        (void)hipSetDevice(mk->ctx->device);
+        (void)hipStreamSynchronize(mk->ctx->stream);
+        (void)hipFree(mk->d_wx);
+    }
     delete mk;
 }
 
 struct MkEvents {
-    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     ~MkEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
 };
 
@@ -416,10 +427,12 @@ static uint32_t mk_chunk_groups(const srx_markers* mk) {
     return (uint32_t)std::min<uint64_t>(mk->n_groups, std::max<uint64_t>(1, kMkChunkBytes / per));
 }
 
+#include "wilcoxon.inl"
+
 // The whole call.  d_labels: n_rows u32 on the device (n_groups known: every label is validated against it).  want_rank false:
-// the moments alone (srx_group_moments).
+// the moments alone (srx_group_moments).  wx: the rank-sum route (its scores are ranked in place of Welch's t).
 static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_groups, const srx_rank_genes_opts* opts, bool want_rank,
-                           srx_markers** out) {
+                           srx_markers** out, const WxOpts* wx = nullptr) {
     srx_ctx* ctx = m->ctx;
     const uint64_t N = m->n_rows, G = m->n_cols;
     uint32_t n_top = 0;
@@ -512,7 +525,7 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
     info.sum_scale_log2 = 62 - e - L;
     info.sq_scale_log2 = 62 - 2 * e - L;
     info.max_abs = max_abs;
-    for (uint64_t s : sizes) info.groups_degenerate += (s < 2 || N - s < 2) ? 1u : 0u;
+    for (uint64_t s : sizes) info.groups_degenerate += (wx ? (s == 0 || N - s == 0) : (s < 2 || N - s < 2)) ? 1u : 0u;
 
     // the blocks: at most rows_per_block consecutive places of ONE group each
     const uint64_t rpb = mk_rows_per_block(N, m->n_tiles);
@@ -557,6 +570,12 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
                               (const uint32_t*)mk->d_C, n_groups, G, mk->d_totS, mk->d_totQ, mk->d_totC);
     SRX_HIP(ctx, hipGetLastError());
     SRX_HIP(ctx, hipEventRecord(ev.e[2], st));
+    if (wx) {
+        mk->wilcoxon = true;
+        SRX_TRY(wilcoxon_run(m, d_labels, mk, *wx));
+        SRX_HIP(ctx, hipEventRecord(ev.e[5], st));        // (the three stages keep their own times: winfo)
+    }
+    hipEvent_t ev_stat = wx ? ev.e[5] : ev.e[2];
 
     // -- stages 3 and 4: the scores of a chunk of groups, then their ranking
     float ms_stat = 0.f, ms_rank = 0.f;
@@ -569,7 +588,8 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
         for (uint32_t g0 = 0; g0 < n_groups; g0 += per) {
             const uint32_t ng = std::min(per, n_groups - g0);
             const uint64_t cells = (uint64_t)ng * G;
-            hipLaunchKernelGGL(k_mk_table, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, t, (int)SRX_MARKERS_SCORE, g0, ng, (void*)d_score);
+            if (wx) hipLaunchKernelGGL(k_wx_table, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, wx_tables(mk), (int)SRX_MARKERS_SCORE, g0, ng, (void*)d_score);
+            else hipLaunchKernelGGL(k_mk_table, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, t, (int)SRX_MARKERS_SCORE, g0, ng, (void*)d_score);
             SRX_HIP(ctx, hipGetLastError());
             if (n_groups <= per) SRX_HIP(ctx, hipEventRecord(a, st));
             hipLaunchKernelGGL(k_mk_rank, dim3((unsigned)((G + 255) / 256), ng), dim3(256), 0, st, (const double*)d_score, (uint32_t)G, g0, n_top,
@@ -583,10 +603,10 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
         SRX_HIP(ctx, hipEventRecord(b, st));
         SRX_HIP(ctx, hipEventSynchronize(b));
         if (n_groups <= per) {                    // (several chunks interleave the two stages: their sum is reported as ranking)
-            SRX_HIP(ctx, hipEventElapsedTime(&ms_stat, ev.e[2], a));
+            SRX_HIP(ctx, hipEventElapsedTime(&ms_stat, ev_stat, a));
             SRX_HIP(ctx, hipEventElapsedTime(&ms_rank, a, b));
         } else {
-            SRX_HIP(ctx, hipEventElapsedTime(&ms_rank, ev.e[2], b));
+            SRX_HIP(ctx, hipEventElapsedTime(&ms_rank, ev_stat, b));
         }
     }
     SRX_HIP(ctx, hipEventSynchronize(ev.e[2]));
@@ -594,9 +614,14 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
     SRX_HIP(ctx, hipEventElapsedTime(&ms_prep, ev.e[0], ev.e[1]));
     SRX_HIP(ctx, hipEventElapsedTime(&ms_mom, ev.e[1], ev.e[2]));
     info.ms = (double)ms_prep + (double)ms_mom + (double)ms_stat + (double)ms_rank;
+    if (wx) info.ms += mk->winfo.ms_stage + mk->winfo.ms_sort + mk->winfo.ms_ranks;
     if (getenv("SRX_MARKERS_TRACE"))
         fprintf(stderr, "srx markers: groups %u blocks %zu prepare %.3f moments %.3f statistics %.3f ranking %.3f ms\n", n_groups, blocks.size(),
                 ms_prep, ms_mom, ms_stat, ms_rank);
+    if (wx && getenv("SRX_MARKERS_TRACE"))
+        fprintf(stderr, "srx markers: wilcoxon chunks %u stage %.3f sort %.3f ranks %.3f ms (short %llu long %llu segments)\n", mk->winfo.n_chunks,
+                mk->winfo.ms_stage, mk->winfo.ms_sort, mk->winfo.ms_ranks, (unsigned long long)mk->winfo.segments_short,
+                (unsigned long long)mk->winfo.segments_long);
     guard.p = nullptr;
     *out = mk;
     return SRX_OK;
@@ -614,7 +639,9 @@ static int32_t markers_fetch_table(srx_markers* mk, int32_t which, void* out) {
     for (uint32_t g0 = 0; g0 < mk->n_groups; g0 += per) {
         const uint32_t ng = std::min(per, mk->n_groups - g0);
         const uint64_t cells = (uint64_t)ng * G;
-        hipLaunchKernelGGL(k_mk_table, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, t, (int)which, g0, ng, d_tab);
+        if (mk->wilcoxon && (which == SRX_MARKERS_SCORE || which == SRX_MARKERS_RANKSUM2))
+            hipLaunchKernelGGL(k_wx_table, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, wx_tables(mk), (int)which, g0, ng, d_tab);
+        else hipLaunchKernelGGL(k_mk_table, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, t, (int)which, g0, ng, d_tab);
         SRX_HIP(ctx, hipGetLastError());
         SRX_TRY(d2h(ctx, (char*)out + (uint64_t)g0 * G * 8, d_tab, cells * 8));
     }
@@ -637,6 +664,28 @@ static int32_t markers_host_labels(srx_mat* m, const uint32_t* labels, uint32_t 
     if (m->n_rows && !labels) return fail(ctx, SRX_E_ARG, "%s: null labels", what);
     SRX_TRY(scratch(ctx, "mk_labels", at_least_one(m->n_rows) * 4, (void**)d_labels));
     return h2d(ctx, *d_labels, labels, m->n_rows * 4);
+}
+
+// the labels the last srx_louvain left on g: the handle checked against m, n_groups = the largest label + 1
+static int32_t markers_graph_labels(srx_mat* m, srx_graph* g, const char* what, uint32_t* n_groups) {
+    srx_ctx* ctx = m->ctx;
+    if (!g) return fail(ctx, SRX_E_ARG, "%s: null graph", what);
+    if (g->ctx != ctx) return fail(ctx, SRX_E_ARG, "%s: the matrix and the graph belong to different contexts", what);
+    if (!g->labels_valid) return fail(ctx, SRX_E_ARG, "%s: no srx_louvain has run on this graph", what);
+    if (g->n != m->n_rows)
+        return fail(ctx, SRX_E_ARG, "%s: the graph has %llu cells, the matrix %llu rows", what, (unsigned long long)g->n, (unsigned long long)m->n_rows);
+    if (!g->n) return fail(ctx, SRX_E_ARG, "%s: no cells, hence no groups", what);
+    unsigned long long* d_small;
+    SRX_TRY(scratch(ctx, "mk_small", MK_WORDS * 8, (void**)&d_small));
+    SRX_HIP(ctx, hipMemsetAsync(d_small, 0, MK_WORDS * 8, ctx->stream));
+    const unsigned grid = (unsigned)std::min<uint64_t>((g->n + 255) / 256, (uint64_t)ctx->n_cus * 4);
+    hipLaunchKernelGGL(k_mk_label_max, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t*)g->d_labels, g->n, d_small);
+    SRX_HIP(ctx, hipGetLastError());
+    unsigned long long mx = 0;
+    SRX_TRY(d2h(ctx, &mx, d_small + MK_MAXLABEL, 8));
+    if (mx >= SRX_GROUPS_MAX) return fail(ctx, SRX_E_ARG, "%s: %llu communities, more than %d groups", what, mx + 1, SRX_GROUPS_MAX);
+    *n_groups = (uint32_t)mx + 1;
+    return SRX_OK;
 }
 
 }  // namespace srx
@@ -671,25 +720,60 @@ int32_t srx_rank_genes_groups(srx_mat* m, const uint32_t* labels, uint32_t n_gro
 
 int32_t srx_rank_genes_groups_graph(srx_mat* m, srx_graph* g, const srx_rank_genes_opts* opts, srx_markers** out) {
     SRX_TRY(markers_check(m, "srx_rank_genes_groups_graph"));
-    srx_ctx* ctx = m->ctx;
-    if (!g || !out) return fail(ctx, SRX_E_ARG, "srx_rank_genes_groups_graph: null %s", g ? "output" : "graph");
-    if (g->ctx != ctx) return fail(ctx, SRX_E_ARG, "srx_rank_genes_groups_graph: the matrix and the graph belong to different contexts");
-    if (!g->labels_valid) return fail(ctx, SRX_E_ARG, "srx_rank_genes_groups_graph: no srx_louvain has run on this graph");
-    if (g->n != m->n_rows)
-        return fail(ctx, SRX_E_ARG, "srx_rank_genes_groups_graph: the graph has %llu cells, the matrix %llu rows", (unsigned long long)g->n,
-                    (unsigned long long)m->n_rows);
-    if (!g->n) return fail(ctx, SRX_E_ARG, "srx_rank_genes_groups_graph: no cells, hence no groups");
-    unsigned long long* d_small;
-    SRX_TRY(scratch(ctx, "mk_small", MK_WORDS * 8, (void**)&d_small));
-    SRX_HIP(ctx, hipMemsetAsync(d_small, 0, MK_WORDS * 8, ctx->stream));
-    const unsigned grid = (unsigned)std::min<uint64_t>((g->n + 255) / 256, (uint64_t)ctx->n_cus * 4);
-    hipLaunchKernelGGL(k_mk_label_max, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t*)g->d_labels, g->n, d_small);
-    SRX_HIP(ctx, hipGetLastError());
-    unsigned long long mx = 0;
-    SRX_TRY(d2h(ctx, &mx, d_small + MK_MAXLABEL, 8));
-    if (mx >= SRX_GROUPS_MAX)
-        return fail(ctx, SRX_E_ARG, "srx_rank_genes_groups_graph: %llu communities, more than %d groups", mx + 1, SRX_GROUPS_MAX);
-    return markers_run(m, g->d_labels, (uint32_t)mx + 1, opts, true, out);
+    if (!out) return fail(m->ctx, SRX_E_ARG, "srx_rank_genes_groups_graph: null output");
+    uint32_t n_groups = 0;
+    SRX_TRY(markers_graph_labels(m, g, "srx_rank_genes_groups_graph", &n_groups));
+    return markers_run(m, g->d_labels, n_groups, opts, true, out);
+}
+
+// the rank-sum route's own refusals and options: N below 2^31 (the doubled rank sums stay below 2^63), with the tie term N at
+// most 2^21 (N^3 - N fits 64 bits)
+static int32_t wilcoxon_begin(srx_mat* m, const srx_wilcoxon_opts* opts, const char* what, srx_rank_genes_opts* ro, WxOpts* wx) {
+    ro->n_top = opts ? opts->n_top : 0;
+    ro->logged = opts ? opts->logged : -1;
+    wx->tie_correct = opts && opts->tie_correct;
+    wx->scratch_bytes = opts ? opts->scratch_bytes : 0;
+    if (m->n_rows >= (1ull << 31)) return fail(m->ctx, SRX_E_ARG, "%s: 2^31 rows or more: the doubled rank sums would pass 2^63", what);
+    if (wx->tie_correct && m->n_rows > (1ull << 21))
+        return fail(m->ctx, SRX_E_ARG, "%s: tie_correct with more than 2^21 rows (%llu): N^3 - N would pass 64 bits", what, (unsigned long long)m->n_rows);
+    return SRX_OK;
+}
+
+int32_t srx_rank_genes_wilcoxon(srx_mat* m, const uint32_t* labels, uint32_t n_groups, const srx_wilcoxon_opts* opts, srx_markers** out) {
+    SRX_TRY(markers_check(m, "srx_rank_genes_wilcoxon"));
+    if (!out) return fail(m->ctx, SRX_E_ARG, "srx_rank_genes_wilcoxon: null output");
+    srx_rank_genes_opts ro;
+    WxOpts wx;
+    SRX_TRY(wilcoxon_begin(m, opts, "srx_rank_genes_wilcoxon", &ro, &wx));
+    uint32_t* d_labels;
+    SRX_TRY(markers_host_labels(m, labels, n_groups, "srx_rank_genes_wilcoxon", &d_labels));
+    return markers_run(m, d_labels, n_groups, &ro, true, out, &wx);
+}
+
+int32_t srx_rank_genes_wilcoxon_graph(srx_mat* m, srx_graph* g, const srx_wilcoxon_opts* opts, srx_markers** out) {
+    SRX_TRY(markers_check(m, "srx_rank_genes_wilcoxon_graph"));
+    if (!out) return fail(m->ctx, SRX_E_ARG, "srx_rank_genes_wilcoxon_graph: null output");
+    srx_rank_genes_opts ro;
+    WxOpts wx;
+    SRX_TRY(wilcoxon_begin(m, opts, "srx_rank_genes_wilcoxon_graph", &ro, &wx));
+    uint32_t n_groups = 0;
+    SRX_TRY(markers_graph_labels(m, g, "srx_rank_genes_wilcoxon_graph", &n_groups));
+    return markers_run(m, g->d_labels, n_groups, &ro, true, out, &wx);
+}
+
+int32_t srx_markers_wilcoxon_info_get(const srx_markers* mk, srx_wilcoxon_info* info) {
+    if (!mk || !info) return fail(mk ? mk->ctx : nullptr, SRX_E_ARG, "srx_markers_wilcoxon_info_get: null argument");
+    if (!mk->wilcoxon) return fail(mk->ctx, SRX_E_ARG, "srx_markers_wilcoxon_info_get: this handle is a t-test's, not srx_rank_genes_wilcoxon's");
+    *info = mk->winfo;
+    return SRX_OK;
+}
+
+int32_t srx_markers_fetch_ties(srx_markers* mk, uint64_t* out) {
+    if (!mk || !out) return fail(mk ? mk->ctx : nullptr, SRX_E_ARG, "srx_markers_fetch_ties: null argument");
+    if (!mk->wilcoxon || !mk->winfo.tie_correct)
+        return fail(mk->ctx, SRX_E_ARG, "srx_markers_fetch_ties: the tie terms exist on a handle of srx_rank_genes_wilcoxon made with tie_correct only");
+    SRX_HIP(mk->ctx, hipSetDevice(mk->ctx->device));
+    return d2h(mk->ctx, out, mk->d_T, (size_t)mk->n_cols * 8);
 }
 
 int32_t srx_markers_info_get(const srx_markers* mk, srx_markers_info* info) {
@@ -712,7 +796,9 @@ int32_t srx_markers_fetch_top(srx_markers* mk, uint32_t* genes_out, double* scor
 int32_t srx_markers_fetch_table(srx_markers* mk, int32_t which, void* out) {
     if (!mk) return fail(nullptr, SRX_E_ARG, "srx_markers_fetch_table: null handle");
     srx_ctx* ctx = mk->ctx;
-    if (which < SRX_MARKERS_CNT || which > SRX_MARKERS_PCT_REST) return fail(ctx, SRX_E_ARG, "srx_markers_fetch_table: no table %d", which);
+    if (which == SRX_MARKERS_RANKSUM2 && !mk->wilcoxon)
+        return fail(ctx, SRX_E_ARG, "srx_markers_fetch_table: the rank sums belong to srx_rank_genes_wilcoxon; this handle is a t-test's");
+    if (which < SRX_MARKERS_CNT || which > SRX_MARKERS_RANKSUM2) return fail(ctx, SRX_E_ARG, "srx_markers_fetch_table: no table %d", which);
     if (!out) return fail(ctx, SRX_E_ARG, "srx_markers_fetch_table: null output");
     SRX_HIP(ctx, hipSetDevice(ctx->device));
     return markers_fetch_table(mk, which, out);

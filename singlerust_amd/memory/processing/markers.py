@@ -1,8 +1,9 @@
 """Marker genes per group over libsrx_hip (``srx_group_moments`` / ``srx_rank_genes_groups[_graph]``): what fills
 ``uns["rank_genes_groups"]``.
 
-Not in the reference.  The statistic (Welch's t, group against rest, from 64-bit fixed-point grouped moments) is defined in
-include/srx.h; everything runs on the device over the resident matrix and nothing computes on the CPU.
+Not in the reference.  The statistics (Welch's t from 64-bit fixed-point grouped moments; the Wilcoxon rank-sum z from exact
+grouped rank sums, ``srx_rank_genes_wilcoxon[_graph]``), group against rest, are defined in include/srx.h; everything runs on
+the device over the resident matrix and nothing computes on the CPU.
 """
 from __future__ import annotations
 
@@ -15,7 +16,8 @@ from ...anndata import IMAnnData
 
 TABLES = {"cnt": F.MARKERS_CNT, "sum": F.MARKERS_SUM, "sumsq": F.MARKERS_SUMSQ, "mean": F.MARKERS_MEAN, "var": F.MARKERS_VAR,
           "mean_rest": F.MARKERS_MEAN_REST, "var_rest": F.MARKERS_VAR_REST, "score": F.MARKERS_SCORE, "lfc": F.MARKERS_LFC,
-          "pct": F.MARKERS_PCT, "pct_rest": F.MARKERS_PCT_REST}
+          "pct": F.MARKERS_PCT, "pct_rest": F.MARKERS_PCT_REST, "ranksum2": F.MARKERS_RANKSUM2}
+_U64_TABLES = (F.MARKERS_CNT, F.MARKERS_RANKSUM2)
 
 
 def _labels(labels, n_obs: int):
@@ -56,9 +58,21 @@ class Markers:
         """One full n_groups x n_genes table: a ``TABLES`` name or an ``SRX_MARKERS_*`` value."""
         which = TABLES[which] if isinstance(which, str) else int(which)
         i = self.info()
-        out = np.zeros((i["n_groups"], i["n_cols"]), np.uint64 if which == F.MARKERS_CNT else np.float64)
+        out = np.zeros((i["n_groups"], i["n_cols"]), np.uint64 if which in _U64_TABLES else np.float64)
         F.check(F.lib().srx_markers_fetch_table(self._h, which, F.ptr(out)), self.ctx.handle)
         return out
+
+    def ties(self) -> np.ndarray:
+        """The tie term T per gene (uint64): a handle of the Wilcoxon route made with ``tie_correct`` only."""
+        out = np.zeros(self.info()["n_cols"], np.uint64)
+        F.check(F.lib().srx_markers_fetch_ties(self._h, F.ptr(out)), self.ctx.handle)
+        return out
+
+    def wilcoxon_info(self) -> dict:
+        """Chunks, staging bytes, segment routes and stage times of the Wilcoxon route (refused on a t-test handle)."""
+        i = F.WilcoxonInfo()
+        F.check(F.lib().srx_markers_wilcoxon_info_get(self._h, C.byref(i)), self.ctx.handle)
+        return {k: getattr(i, k) for k, _ in F.WilcoxonInfo._fields_}
 
     def sizes(self) -> np.ndarray:
         out = np.zeros(self.info()["n_groups"], np.uint64)
@@ -92,26 +106,34 @@ def group_moments(adata: IMAnnData, labels) -> dict:
 
 
 def rank_genes_groups(adata: IMAnnData, groupby: str = "louvain", n_genes: int = 100, logged: bool = True,
-                      key_added: str = "rank_genes_groups") -> dict:
-    """Welch's t-test of every group against the rest, scanpy's ``tl.rank_genes_groups`` default.  Where the graph on the
+                      key_added: str = "rank_genes_groups", method: str = "t-test", tie_correct: bool = False) -> dict:
+    """Welch's t-test of every group against the rest, scanpy's ``tl.rank_genes_groups`` default, or with
+    ``method="wilcoxon"`` the Wilcoxon rank-sum z (``tie_correct`` as scanpy's flag of that name).  Where the graph on the
     device still holds the labels of ``obs[groupby]`` (the last ``louvain`` wrote them) they are read there, with no host round
     trip; otherwise ``obs[groupby]`` (integers 0 .. n_groups - 1) is uploaded.  Writes ``adata.uns[key_added]``: ``names``,
     ``scores``, ``logfoldchanges`` (n_groups x n_genes, best first), ``pts`` / ``pts_rest`` (n_groups x n_vars), ``params``,
     ``info``; the device tables stay reachable as ``adata._markers``.  Returns the info."""
     x = adata.x()
+    if method not in ("t-test", "wilcoxon"):
+        raise F.SrxError(F.E_ARG, f"rank_genes_groups: method '{method}' is neither 't-test' nor 'wilcoxon'")
+    if tie_correct and method != "wilcoxon":
+        raise F.SrxError(F.E_ARG, "rank_genes_groups: tie_correct belongs to method='wilcoxon'")
     if groupby not in adata.obs:
         raise F.SrxError(F.E_ARG, f"rank_genes_groups: obs has no '{groupby}'")
     n_top = min(int(n_genes), adata.n_vars())
-    opts = F.RankGenesOpts(n_top, 1 if logged else 0)
+    wilcoxon = method == "wilcoxon"
+    opts = F.WilcoxonOpts(n_top, 1 if logged else 0, 1 if tie_correct else 0, 0, 0) if wilcoxon else F.RankGenesOpts(n_top, 1 if logged else 0)
+    lib = F.lib()
+    on_graph, on_labels = ((lib.srx_rank_genes_wilcoxon_graph, lib.srx_rank_genes_wilcoxon) if wilcoxon
+                           else (lib.srx_rank_genes_groups_graph, lib.srx_rank_genes_groups))
     h = C.c_void_p()
     g = getattr(adata, "_graph", None)
     resident = bool(g is not None and g.handle and getattr(g, "labels_key", None) == groupby)
     if resident:
-        F.check(F.lib().srx_rank_genes_groups_graph(x.handle, g.handle, C.byref(opts), C.byref(h)), x.ctx.handle)
+        F.check(on_graph(x.handle, g.handle, C.byref(opts), C.byref(h)), x.ctx.handle)
     else:
         labels, n_groups = _labels(adata.obs[groupby], adata.n_obs())
-        F.check(F.lib().srx_rank_genes_groups(x.handle, F.ptr(labels) if labels.size else None, n_groups, C.byref(opts), C.byref(h)),
-                x.ctx.handle)
+        F.check(on_labels(x.handle, F.ptr(labels) if labels.size else None, n_groups, C.byref(opts), C.byref(h)), x.ctx.handle)
     old = getattr(adata, "_markers", None)
     if old is not None:
         old.free()
@@ -121,7 +143,8 @@ def rank_genes_groups(adata: IMAnnData, groupby: str = "louvain", n_genes: int =
     info = mk.info()
     adata.uns[key_added] = {"names": names, "scores": scores, "logfoldchanges": lfc, "pts": mk.table("pct"),
                             "pts_rest": mk.table("pct_rest"),
-                            "params": {"groupby": groupby, "method": "t-test", "reference": "rest", "n_genes": n_top,
-                                       "logged": bool(logged), "resident_labels": resident},
+                            "params": {"groupby": groupby, "method": method, "reference": "rest", "n_genes": n_top,
+                                       "logged": bool(logged), "resident_labels": resident,
+                                       "tie_correct": bool(tie_correct)},
                             "info": info}
     return info
