@@ -433,6 +433,10 @@ int32_t srx_knn_points(srx_ctx* ctx, const double* ref, uint64_t n_ref, const do
  * ascending within a row and f64 data.  C is exactly symmetric (C[i,j] and C[j,i] are the same bits), has no
  * diagonal, 0 < C[i,j] <= 1, and the whole result is bit-identical from call to call and independent of the order of
  * the entries within an input row.
+ * The formulas are evaluated literally in IEEE f64: a row whose sum_j d_ij overflows has floor = sigma_i = +inf, every
+ * weight of that row is 1 and it counts in rows_clamped.  The 1e-9 of sigma*_i holds for distances in the normal range:
+ * with subnormal distances sigma*_i is the upper end of the last one-ulp bracket of the root, and on that grid S_i can
+ * miss T by more.
  *
  * The handle owns its device buffers (a later k-NN or graph call does not touch them); free it before its context. */
 typedef struct srx_graph srx_graph;

@@ -11,7 +11,9 @@ def _S(c, one, x, s):
 
 
 def scales(dist):
-    """dist: n x k distances (any order within a row).  Returns a dict of per-row arrays and the n x k weights."""
+    """dist: n x k distances (any order within a row).  Returns a dict of per-row arrays and the n x k weights.  "lo" and
+    "hi" are the final bracket of the root (adjacent doubles unless the bisection met S == T on the way; 0 where the row
+    has no root): sigma_star is one of the two."""
     d = np.asarray(dist, dtype=np.float64)
     n, k = d.shape
     T = np.log2(k + 1.0)
@@ -22,7 +24,7 @@ def scales(dist):
     c = one.sum(axis=1).astype(np.float64)
     x = np.where(one, 0.0, d - rho[:, None])
     has_root = ~all_zero & (c < T)
-    sig = np.zeros(n)
+    sig, sig_lo, sig_hi = np.zeros(n), np.zeros(n), np.zeros(n)
     r = np.nonzero(has_root)[0]
     if len(r):
         cr, oner, xr = c[r], one[r], x[r]
@@ -55,12 +57,13 @@ def scales(dist):
             hi = np.where(m & ~up, mid, hi)
         better_lo = np.abs(_S(cr, oner, xr, lo) - T) < np.abs(_S(cr, oner, xr, hi) - T)
         sig[r] = np.where(better_lo & (lo > 0), lo, hi)
+        sig_lo[r], sig_hi[r] = lo, hi
     floor = 1e-3 * d.sum(axis=1) / (k + 1.0)
     clamped = ~all_zero & (floor > sig)
     sigma = np.where(all_zero, 0.0, np.maximum(sig, floor))
     a = weights(d, rho, sigma)
     return {"T": T, "rho": rho, "c": c, "sigma_star": sig, "floor": floor, "sigma": sigma, "has_root": has_root,
-            "clamped": clamped, "all_zero": all_zero}, a
+            "clamped": clamped, "all_zero": all_zero, "lo": sig_lo, "hi": sig_hi}, a
 
 
 def weights(d, rho, sigma):
