@@ -38,7 +38,8 @@ extern "C" {
                                   srx_knn_points (kernel class 11) came that way at 6, as did srx_neighbors_* / srx_graph_*
                                   (kernel class 12) and srx_louvain / srx_louvain_csr / srx_graph_labels_fetch (no class of
                                   their own: the time is in srx_louvain_info.ms) and srx_group_moments / srx_rank_genes_groups[_graph] /
-                                  srx_markers_* (no class either: srx_markers_info.ms) */
+                                  srx_markers_* (no class either: srx_markers_info.ms) and srx_diffmap[_csr] /
+                                  srx_graph_diffmap_fetch / srx_graph_transitions_fetch / srx_dpt[_from] (srx_diffmap_info.ms) */
 
 typedef struct srx_ctx srx_ctx;   /* one GPU + stream + (optional) RCCL communicator      */
 typedef struct srx_mat srx_mat;   /* device-resident CSR (the `X` of an IMAnnData)        */
@@ -732,6 +733,92 @@ int32_t srx_umap_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* indic
 int32_t srx_graph_embedding_fetch(srx_graph* g, double* out, uint32_t* dim_out);
 /* Host only.  SRX_E_ARG: spread or min_dist not finite, spread <= 0, min_dist < 0 or > spread, a null output. */
 int32_t srx_umap_fit_ab(double spread, double min_dist, double* a, double* b);
+
+/* ---- Diffusion maps and pseudotime: what sc.tl.diffmap gives obsm["X_diffmap"], uns["diffmap_evals"], and sc.tl.dpt
+ * (without branchings) gives obs["dpt_pseudotime"] ---------------------------------------------------------------------------
+ * Not in the reference.  This is scanpy's compute_transitions with its _transitions_sym, compute_eigen and
+ * DPT._set_pseudotime RESTATED below; the definition here is what is tested, and the output has NOT been compared with
+ * scanpy, which is not installed where this was built.
+ *
+ * Input: a symmetric graph C as CSR with exactly the contract of srx_louvain_csr (u64 indptr, u32 indices strictly ascending
+ *   within a row, f64 weights > 0, no diagonal, C_ij and C_ji the same bits), and every row holds an entry; 2 <= n < 2^32.
+ * Transition operator.  With density_normalize: q_i = sum_j C_ij, K_ij = C_ij / (q_i * q_j); without: K = C.  Then
+ *   z_i = sum_j K_ij and T_ij = K_ij / (sqrt(z_i) * sqrt(z_j)).  All f64, every operation rounded once (no FMA contraction),
+ *   each product formed before its division, so T_ij and T_ji are the same bits.  A row sum is taken in an order fixed by
+ *   (n, indptr) alone: SRX_DIFFMAP_GROUP lanes own a row, lane s adds the entries lo + s, lo + s + SRX_DIFFMAP_GROUP, ... in
+ *   that order and the lanes' sums meet in a butterfly.  T shares C's indptr and indices; srx_graph_transitions_fetch
+ *   returns its nnz values in C's order.  T is symmetric with spectrum in [-1, 1] and largest eigenvalue 1 (once per
+ *   connected component).
+ * Eigenpairs.  The n_comps ALGEBRAICALLY largest eigenvalues of T, descending, with orthonormal eigenvectors (n x n_comps,
+ *   row-major).  n_comps is clamped to n - 1 as scanpy clamps it; info.n_comps is the value used.  scanpy asks ARPACK for the
+ *   eigenvalues largest in MAGNITUDE: the two agree whenever |lambda_min| < lambda_{n_comps}, which holds on k-NN graphs
+ *   (lambda_min about -0.4 .. -0.5) and fails on, e.g., an odd ring (lambda_min close to -1).  scanpy also reverses ARPACK's
+ *   ascending order, as is done here.
+ *   Contract, whatever the algorithm: the returned block is re-orthonormalised once, then
+ *     lambda_l = v_l . (T v_l),  max_residual = max_l |T v_l - lambda_l v_l|_2,  max_ortho = max |V^T V - I|
+ *   are evaluated on the device from the block as returned (sums in a fixed order) and reported.  The call succeeds only if
+ *   max_residual <= tol; otherwise SRX_E_NOCONV, with info filled (max_residual is then the residual estimate of the last
+ *   restart, Inf when there was none, unless the final evaluation itself failed the test) and nothing else written; the
+ *   handle then holds no eigenpairs.  For symmetric T every returned lambda_l lies within max_residual of an eigenvalue.
+ *   Sign: the component of largest magnitude of each vector is positive, the lowest index winning ties.
+ *   Determinism: the whole result, and every field of info except ms, is bit-identical from call to call: no floating-point
+ *   atomics, dot products through fixed per-workgroup slots added in a fixed order.
+ * Algorithm (diffmap.hip): thick-restart Lanczos with full reorthogonalisation (classical Gram-Schmidt twice)
+ *   on a resident basis of ncv columns, the projected problem solved on the host by a cyclic Jacobi once per restart.  The
+ *   start vector is u_i = (mix(seed + 0x9E3779B97F4A7C15 * (i + 1)) >> 11) * 2^-53 - 0.5 with UMAP's mix(); the s-th fresh
+ *   vector after it (a breakdown, beta <= 2^-40; or the start of a completeness check) uses i + 1 + s * n.  A Krylov space of
+ *   one vector holds one vector per eigenspace, so after the block has converged it is locked and the iteration runs again
+ *   in its orthogonal complement until that run's largest pair has converged: a value above the block's smallest (by more
+ *   than tol) replaces it and the check repeats.  info.matvecs counts the products y = T x of all these runs (not the n_comps
+ *   products of the final evaluation) and never exceeds max_matvecs; info.restarts the thick restarts; info.breakdowns the
+ *   breakdowns (at least one whenever the basis reaches n columns).
+ * Pseudotime.  Given lambda_l, V (n x m), a root r and a cap c: w_l = lambda_l / (1 - lambda_l) if lambda_l < c, else 1;
+ *   d_i = sqrt(sum_{l = 0 .. m-1} (w_l * (V[r, l] - V[i, l]))^2), summed with l ascending, f64, every operation rounded once;
+ *   pseudotime_i = d_i / max_j d_j over the finite d_j, and all zeros when that maximum is 0.  (scanpy: DPT._compute_Dchosen_row
+ *   and _set_pseudotime; 0.9994 is its allowance for float32 eigenvalues.)
+ * Defaults (NULL opts): n_comps 15, ncv max(2 n_comps + 1, 20) (clamped to n, at most 129), tol 1e-10, max_matvecs 10000,
+ *   seed 0, density_normalize on.  In a given opts a zero tol, n_comps, ncv or max_matvecs means its default, and
+ *   density_normalize is taken as it stands (0 = off).
+ * Out of scope: DPT branchings, PAGA, an f32 operator, a spectral start inside srx_umap (pass the fetched components as
+ *   SRX_UMAP_INIT_GIVEN).
+ * Refused with SRX_E_ARG and a message, nothing written: n_comps outside 1..64; a non-zero ncv below n_comps + 2 or above
+ *   129; a negative or NaN tol; a negative max_matvecs; n < 2; a row without entries (q = 0; srx_diffmap_csr only: a built
+ *   graph has none); a context with more than one rank; srx_dpt before a successful srx_diffmap on the handle; root >= n; cap
+ *   outside (0, 1] (0 = 0.9994); for srx_dpt_from m outside 1..64 or a null pointer; for srx_diffmap_csr also everything
+ *   srx_louvain_csr refuses. */
+#ifndef SRX_DIFFMAP_GROUP
+#define SRX_DIFFMAP_GROUP 8      /* lanes that own one row */
+#endif
+typedef struct srx_diffmap_opts {
+    double   tol;                   /* 0 = 1e-10 */
+    uint64_t seed;
+    int32_t  n_comps;               /* 0 = 15 */
+    int32_t  ncv;                   /* 0 = max(2 n_comps + 1, 20) */
+    int32_t  max_matvecs;           /* 0 = 10000 */
+    int32_t  density_normalize;     /* NULL opts: on */
+} srx_diffmap_opts;
+typedef struct srx_diffmap_info {
+    uint64_t n, nnz;
+    uint32_t n_comps, ncv, matvecs, restarts, breakdowns, reserved_;
+    double   max_residual, max_ortho;
+    double   ms;                    /* hipEvent time of the solve (T is built before it) */
+} srx_diffmap_info;
+/* The eigenpairs of the handle's connectivities, read where they lie (C, the labels and the embedding are left untouched).  T
+ * and the eigenpairs stay on the device with the handle.  evals_out (n_comps f64; room for the requested n_comps suffices),
+ * evecs_out (n x n_comps f64, row-major, n_comps = the value used) and info may be NULL. */
+int32_t srx_diffmap(srx_graph* g, const srx_diffmap_opts* opts, double* evals_out, double* evecs_out, srx_diffmap_info* info);
+/* The same on a caller-supplied symmetric graph, validated on the device as srx_louvain_csr validates its input. */
+int32_t srx_diffmap_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* indices, const double* weights, uint64_t n,
+                        const srx_diffmap_opts* opts, double* evals_out, double* evecs_out, srx_diffmap_info* info);
+/* The last successful srx_diffmap's eigenpairs (any pointer may be NULL).  SRX_E_ARG when there is none. */
+int32_t srx_graph_diffmap_fetch(srx_graph* g, double* evals, double* evecs, uint32_t* n_comps_out);
+/* T's values, nnz_connectivities f64 in C's order (srx_graph_fetch has indptr and indices).  SRX_E_ARG before an srx_diffmap. */
+int32_t srx_graph_transitions_fetch(srx_graph* g, double* data);
+/* Pseudotime from the eigenpairs the handle holds: n f64. */
+int32_t srx_dpt(srx_graph* g, uint64_t root, double cap, double* pseudotime_out);
+/* The same from eigenpairs on the host (evals m f64, evecs n x m row-major), e.g. what srx_diffmap_csr returned. */
+int32_t srx_dpt_from(srx_ctx* ctx, const double* evals, const double* evecs, uint64_t n, uint32_t m, uint64_t root, double cap,
+                     double* pseudotime_out);
 
 /* The raw operators the PCA is built from, for a caller-supplied 64-column panel (k x 64
  * row-major): y_out (n_rows x 64) = X[:, sel] * panel, t_out (k x 64) = X[:, sel]^T * y, and

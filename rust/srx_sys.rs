@@ -12,6 +12,7 @@ pub const SRX_LOUVAIN_MAX_LEVELS: i32 = 32;
 pub const SRX_GROUPS_MAX: i32 = 4096;
 pub const SRX_UMAP_GROUP: i32 = 8;
 pub const SRX_UMAP_MAX_EPOCHS: i32 = 1048576;
+pub const SRX_DIFFMAP_GROUP: i32 = 8;
 pub const SRX_OK: i32 = 0;
 pub const SRX_E_ARG: i32 = -1;
 pub const SRX_E_DTYPE: i32 = -2;
@@ -292,6 +293,33 @@ pub struct SrxUmapInfo {      // `srx_umap_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxDiffmapOpts {      // `srx_diffmap_opts`
+    pub tol: f64,
+    pub seed: u64,
+    pub n_comps: i32,
+    pub ncv: i32,
+    pub max_matvecs: i32,
+    pub density_normalize: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxDiffmapInfo {      // `srx_diffmap_info`
+    pub n: u64,
+    pub nnz: u64,
+    pub n_comps: u32,
+    pub ncv: u32,
+    pub matvecs: u32,
+    pub restarts: u32,
+    pub breakdowns: u32,
+    pub reserved: u32,
+    pub max_residual: f64,
+    pub max_ortho: f64,
+    pub ms: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPipelineResult {      // `srx_pipeline_result`
     pub pca: SrxPcaInfo,
     pub ms_normalize: f64,
@@ -409,6 +437,16 @@ extern "C" {
                         opts: *const SrxUmapOpts, init: *const f64, embedding_out: *mut f64, info: *mut SrxUmapInfo) -> i32;
     pub fn srx_graph_embedding_fetch(g: *mut SrxGraph, out: *mut f64, dim_out: *mut u32) -> i32;
     pub fn srx_umap_fit_ab(spread: f64, min_dist: f64, a: *mut f64, b: *mut f64) -> i32;
+    pub fn srx_diffmap(g: *mut SrxGraph, opts: *const SrxDiffmapOpts, evals_out: *mut f64, evecs_out: *mut f64,
+                       info: *mut SrxDiffmapInfo) -> i32;
+    pub fn srx_diffmap_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,
+                           opts: *const SrxDiffmapOpts, evals_out: *mut f64, evecs_out: *mut f64,
+                           info: *mut SrxDiffmapInfo) -> i32;
+    pub fn srx_graph_diffmap_fetch(g: *mut SrxGraph, evals: *mut f64, evecs: *mut f64, n_comps_out: *mut u32) -> i32;
+    pub fn srx_graph_transitions_fetch(g: *mut SrxGraph, data: *mut f64) -> i32;
+    pub fn srx_dpt(g: *mut SrxGraph, root: u64, cap: f64, pseudotime_out: *mut f64) -> i32;
+    pub fn srx_dpt_from(ctx: *mut SrxCtx, evals: *const f64, evecs: *const f64, n: u64, m: u32, root: u64,
+                        cap: f64, pseudotime_out: *mut f64) -> i32;
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,

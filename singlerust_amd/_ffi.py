@@ -142,6 +142,21 @@ class UmapInfo(C.Structure):
                 ("ms", C.c_double)]
 
 
+DIFFMAP_GROUP = 8
+DIFFMAP_MAX_COMPS, DIFFMAP_MAX_NCV = 64, 129
+
+
+class DiffmapOpts(C.Structure):
+    _fields_ = [("tol", C.c_double), ("seed", C.c_uint64), ("n_comps", C.c_int32), ("ncv", C.c_int32), ("max_matvecs", C.c_int32),
+                ("density_normalize", C.c_int32)]
+
+
+class DiffmapInfo(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("n_comps", C.c_uint32), ("ncv", C.c_uint32), ("matvecs", C.c_uint32),
+                ("restarts", C.c_uint32), ("breakdowns", C.c_uint32), ("reserved_", C.c_uint32), ("max_residual", C.c_double),
+                ("max_ortho", C.c_double), ("ms", C.c_double)]
+
+
 class SynthParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_rows_global", C.c_uint64), ("n_cols", C.c_uint64),
                 ("density", C.c_double), ("lib_sigma", C.c_double), ("type_decay", C.c_double),
@@ -238,6 +253,12 @@ _SIGS = {
     "srx_umap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
     "srx_graph_embedding_fetch": (C.c_int32, [P, P, C.POINTER(C.c_uint32)]),
     "srx_umap_fit_ab": (C.c_int32, [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "srx_diffmap": (C.c_int32, [P, C.POINTER(DiffmapOpts), P, P, C.POINTER(DiffmapInfo)]),
+    "srx_diffmap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(DiffmapOpts), P, P, C.POINTER(DiffmapInfo)]),
+    "srx_graph_diffmap_fetch": (C.c_int32, [P, P, P, C.POINTER(C.c_uint32)]),
+    "srx_graph_transitions_fetch": (C.c_int32, [P, P]),
+    "srx_dpt": (C.c_int32, [P, C.c_uint64, C.c_double, P]),
+    "srx_dpt_from": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_double, P]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),

@@ -579,13 +579,15 @@ int32_t srx_graph_fetch_scales(srx_graph* g, double* rho, double* sigma) {
 
 void srx_graph_free(srx_graph* g) {
     if (!g) return;
-    if (g->d_block || g->d_cblock || g->d_labels || g->d_embed) {
+    if (g->d_block || g->d_cblock || g->d_labels || g->d_embed || g->d_dm_t || g->d_dm_evecs) {
         (void)hipSetDevice(g->ctx->device);
         (void)hipStreamSynchronize(g->ctx->stream);
         if (g->d_block) (void)hipFree(g->d_block);
         if (g->d_cblock) (void)hipFree(g->d_cblock);
         if (g->d_labels) (void)hipFree(g->d_labels);
         if (g->d_embed) (void)hipFree(g->d_embed);
+        if (g->d_dm_t) (void)hipFree(g->d_dm_t);
+        if (g->d_dm_evecs) (void)hipFree(g->d_dm_evecs);
     }
     delete g;
 }

@@ -1,5 +1,5 @@
 // graph_handle.hpp — the srx_graph handle of srx.h: built by graph.hip, read where it lies by the graph algorithms (louvain.hip,
-// umap.hip).
+// umap.hip, diffmap.hip).
 #pragma once
 
 #include "common.hpp"
@@ -26,4 +26,11 @@ struct srx_graph {
     double* d_embed = nullptr;
     uint32_t embed_dim = 0;
     bool embed_valid = false;
+    // the last srx_diffmap on this handle (diffmap.hip): T's data in C's order (nnz f64), the eigenvectors (n x dm_n_comps f64,
+    // row-major) and the eigenvalues; dm_t_valid once T is built, dm_valid once a solve has succeeded
+    double* d_dm_t = nullptr;
+    double* d_dm_evecs = nullptr;
+    std::vector<double> dm_evals;
+    uint32_t dm_n_comps = 0;
+    bool dm_t_valid = false, dm_valid = false;
 };

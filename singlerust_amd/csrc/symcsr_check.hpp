@@ -1,5 +1,5 @@
 // symcsr_check.hpp — the device check of a caller-supplied symmetric CSR graph and its upload, stated once for the entry
-// points that take one (srx_louvain_csr in louvain.hip, srx_umap_csr in umap.hip).  The kernel has internal linkage: every
+// points that take one (srx_louvain_csr in louvain.hip, srx_umap_csr in umap.hip, srx_diffmap_csr in diffmap.hip).  The kernel has internal linkage: every
 // translation unit that includes this header carries its own copy.
 #pragma once
 

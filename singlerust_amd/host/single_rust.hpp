@@ -521,6 +521,12 @@ struct GraphCsr {
     std::vector<std::uint32_t> indices;      // ascending within a row
     std::vector<double> data;
 };
+// eigenpairs of a diffusion map: evals descending, evecs n x n_comps row-major
+struct Diffmap {
+    std::uint64_t n = 0;
+    std::uint32_t n_comps = 0;
+    std::vector<double> evals, evecs;
+};
 class Graph {
 public:
     // k-NN over the scores the last PCA on `a` left on the device, then the graph of it (srx_neighbors_result)
@@ -592,6 +598,34 @@ public:
         ctx_->check(srx_graph_labels_fetch(h_, labels.empty() ? nullptr : labels.data()));
         return labels;
     }
+    // Diffusion map of the connectivities, read where they lie (srx_diffmap): the n_comps algebraically largest eigenpairs of
+    // the transition operator, descending; `opts` null: the defaults; `info` (may be null) receives the call's srx_diffmap_info
+    Diffmap diffmap(const srx_diffmap_opts* opts = nullptr, srx_diffmap_info* info = nullptr) const {
+        srx_diffmap_info li{};
+        Diffmap d;
+        d.n = info_n();
+        const std::size_t room = opts && opts->n_comps > 0 ? static_cast<std::size_t>(opts->n_comps) : 15;
+        d.evals.resize(room);
+        d.evecs.resize(d.n * room);
+        ctx_->check(srx_diffmap(h_, opts, d.evals.data(), d.evecs.data(), &li));
+        d.n_comps = li.n_comps;
+        d.evals.resize(d.n_comps);
+        d.evecs.resize(d.n * d.n_comps);
+        if (info) *info = li;
+        return d;
+    }
+    // the values of the transition operator in the order of connectivities() (srx_graph_transitions_fetch)
+    std::vector<double> transitions() const {
+        std::vector<double> t(info().nnz_connectivities);
+        ctx_->check(srx_graph_transitions_fetch(h_, t.empty() ? nullptr : t.data()));
+        return t;
+    }
+    // pseudotime from `root` out of the eigenpairs the last diffmap() left on the device (srx_dpt; cap 0: 0.9994)
+    std::vector<double> dpt(std::uint64_t root, double cap = 0.0) const {
+        std::vector<double> p(info_n());
+        ctx_->check(srx_dpt(h_, root, cap, p.data()));
+        return p;
+    }
     srx_graph* handle() const { return h_; }
 
 private:
@@ -612,6 +646,30 @@ inline std::vector<std::uint32_t> louvain_csr(Context& ctx, const std::vector<st
     ctx.check(srx_louvain_csr(ctx.handle(), indptr.data(), indices.empty() ? nullptr : indices.data(),
                               weights.empty() ? nullptr : weights.data(), labels.size(), &o, labels.empty() ? nullptr : labels.data(), info));
     return labels;
+}
+// Diffusion map of any symmetric weighted graph without empty rows (srx_diffmap_csr), and the pseudotime of such a result
+inline Diffmap diffmap_csr(Context& ctx, const std::vector<std::uint64_t>& indptr, const std::vector<std::uint32_t>& indices,
+                           const std::vector<double>& weights, const srx_diffmap_opts* opts = nullptr, srx_diffmap_info* info = nullptr) {
+    if (indptr.empty() || indices.size() != weights.size() || indptr.back() != indices.size())
+        throw Error(SRX_E_ARG, "diffmap_csr: indptr (n + 1), indices and weights (indptr[n] each) expected");
+    srx_diffmap_info li{};
+    Diffmap d;
+    d.n = indptr.size() - 1;
+    const std::size_t room = opts && opts->n_comps > 0 ? static_cast<std::size_t>(opts->n_comps) : 15;
+    d.evals.resize(room);
+    d.evecs.resize(d.n * room);
+    ctx.check(srx_diffmap_csr(ctx.handle(), indptr.data(), indices.empty() ? nullptr : indices.data(),
+                              weights.empty() ? nullptr : weights.data(), d.n, opts, d.evals.data(), d.evecs.data(), &li));
+    d.n_comps = li.n_comps;
+    d.evals.resize(d.n_comps);
+    d.evecs.resize(d.n * d.n_comps);
+    if (info) *info = li;
+    return d;
+}
+inline std::vector<double> dpt_from(Context& ctx, const Diffmap& d, std::uint64_t root, double cap = 0.0) {
+    std::vector<double> p(d.n);
+    ctx.check(srx_dpt_from(ctx.handle(), d.evals.data(), d.evecs.data(), d.n, d.n_comps, root, cap, p.data()));
+    return p;
 }
 }  // namespace processing
 }  // namespace memory
