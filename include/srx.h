@@ -820,6 +820,100 @@ int32_t srx_dpt(srx_graph* g, uint64_t root, double cap, double* pseudotime_out)
 int32_t srx_dpt_from(srx_ctx* ctx, const double* evals, const double* evecs, uint64_t n, uint32_t m, uint64_t root, double cap,
                      double* pseudotime_out);
 
+/* ---- Harmony: batch integration of the PCA scores, what sc.external.pp.harmony_integrate gives obsm["X_pca_harmony"] --------
+ * Not in the reference.  This is Harmony (Korsunsky et al. 2019) as harmonypy runs it for ONE batch covariate, RESTATED below
+ * with its random choices replaced by hashes so that the result is bit-identical from call to call.  The definition here is
+ * what is tested; the output has NOT been compared with harmonypy or the R package, neither of which is installed where this
+ * was built.
+ *
+ * All arithmetic is f64.
+ * Input.  Z, n x d with finite entries (the leading n_dims coordinates of the points); batch labels b_i < B; a batch may be
+ *   empty.  N_b = the batch's cell count, P_b = N_b / n.  K clusters, K <= n.
+ * Hashes.  mix() is the splitmix64 finaliser of the UMAP section, G = 0x9E3779B97F4A7C15,
+ *   H(a, i) = mix(seed + G * (1 + a * 2^32 + i))  (mod 2^64).
+ * Cosine rows.  Zhat_i = X_i / |X_i|, |X_i|^2 summed in ascending coordinate order; a row of norm 0 gives Zhat_i = 0.
+ * Start.  The K start cells are those with the smallest (H(0, i), i); their Zhat rows are Y_0 .. Y_{K-1} in that order.  Then
+ *   init_iters rounds of spherical k-means: c_i = argmax_k Zhat_i . Y_k (ties to the lowest k), Y_k = s_k / |s_k| with
+ *   s_k = sum_{c_i = k} Zhat_i.  A cluster without a member, or whose s_k is 0, keeps its Y_k; this rule holds wherever a
+ *   centroid is normalised.  Then dist_ik = 2 (1 - Zhat_i . Y_k), R_i = softmax_k(-dist_ik / sigma) (the row maximum is
+ *   subtracted before exp), O_kb = sum_{i in b} R_ik, E_kb = (sum_i R_ik) P_b.
+ * Objective.  o = sum R_ik dist_ik + sigma sum R_ik log R_ik + sigma theta sum_ik R_ik log((O_{k b_i} + 1) / (E_{k b_i} + 1)),
+ *   with 0 log 0 = 0.
+ * Round r = 1 .. max_rounds.  t counts the cluster iterations of the whole run from 0.  Iteration j = 1 .. max_cluster_iters:
+ *   1. Y_k = normalise(sum_i R_ik Zhat_i).
+ *   2. dist from Zhat and Y.
+ *   3. Cell i is in block q_i = H(1 + t, i) mod n_blocks.  For q = 0 .. n_blocks - 1 in order (an empty block changes nothing):
+ *      the block's rows are taken out, O_kb -= sum_{i in q, b} R_ik and E_kb -= (sum_{i in q} R_ik) P_b; for the block's cells
+ *      R_i = softmax_k(-dist_ik / sigma + theta log((E_{k b_i} + 1) / (O_{k b_i} + 1))); the new rows are added back.
+ *   4. t += 1; o_j = the objective.
+ *   5. With epsilon_cluster > 0 the round stops when j >= 6 and (old - new) / |old| < epsilon_cluster, old = o_{j-5} + o_{j-4}
+ *      + o_{j-3}, new = o_{j-2} + o_{j-1} + o_j.
+ *   h_r (info.round_objective[r - 1]) is the last o_j of the round.
+ * Correction, always from the original Z: the closed form of harmonypy's moe_correct_ridge for a one-hot design with an
+ *   unpenalised intercept (it agrees with a dense solve of the (B + 1) x (B + 1) system to rounding):
+ *   m_kb = sum_{i in b} R_ik;  S_kb = sum_{i in b} R_ik Z_i;  s_k = sum_b lambda m_kb / (m_kb + lambda);
+ *   w0_k = (sum_b lambda S_kb / (m_kb + lambda)) / s_k;  W_kb = (S_kb - m_kb w0_k) / (m_kb + lambda), W_k = 0 when s_k == 0;
+ *   Z_corr_i = Z_i - sum_k R_ik W_{k b_i}.  Then Zhat = the cosine rows of Z_corr; Y, R, O and E stay as they are.
+ * Stopping.  With epsilon_harmony > 0 the run stops after round r >= 2 when (h_{r-1} - h_r) / |h_{r-1}| < epsilon_harmony and
+ *   sets info.converged; it also stops at max_rounds.  An epsilon of 0 never stops early.
+ * Order of summation.  A sum over cells is a chain over the cells of a contiguous chunk in ascending order followed by chains
+ *   over the chunks (runs of consecutive chunks, then the runs; for S_kb the chunks hold the cells of batch b in ascending
+ *   order); chunk and run sizes depend on (n, d, K, B) alone.  The
+ *   sums over k of one cell (softmax, objective) are a per-lane chain over k = l, l + 64, .. and a butterfly over the 64 lanes.
+ *   No floating-point atomics: every table, and every field of info except ms, is bit-identical from call to call.  The
+ *   running O and E differ from sums re-derived from the final R by rounding only.
+ * Defaults (NULL opts): theta 2, sigma 0.1, lambda 1, epsilon_cluster 1e-5, epsilon_harmony 1e-4, seed 0.  In a given opts
+ *   the five doubles are taken literally; a zero n_clusters means max(1, min((n + 15) / 30, 100)) (integer division: n / 30
+ *   rounded, halves up), a zero n_blocks 20, max_rounds 10, max_cluster_iters 20, init_iters 10 (-1 = none), n_dims all.
+ * Out of scope: per-batch theta, lambda and sigma; several covariates; the tau discount; lambda estimation; reference mapping.
+ * Refused with SRX_E_ARG and a message, nothing written (*out is left untouched): a null handle pointer, null labels or
+ *   points with n > 0; theta < 0, sigma <= 0, lambda <= 0, a negative epsilon, any of them NaN or Inf; n_clusters outside
+ *   0 .. SRX_HARMONY_MAX_CLUSTERS or above n; n_batches outside 1 .. SRX_HARMONY_MAX_BATCHES; n_blocks outside 0 .. 65536;
+ *   max_rounds outside 0 .. SRX_HARMONY_MAX_ROUNDS; max_cluster_iters or init_iters above 65536 (or below 0, -1); a label
+ *   >= n_batches; NaN or Inf in the points; n_dims above the points' coordinates, or a coordinate count outside
+ *   1 .. SRX_KNN_MAX_DIMS; no PCA result on m; n >= 2^32 - 1; a context with more than one rank.  SRX_E_OOM when device memory
+ *   cannot be had.  n == 0 gives an empty handle (its fetches write nothing). */
+#define SRX_HARMONY_MAX_CLUSTERS 256
+#define SRX_HARMONY_MAX_BATCHES  256
+#define SRX_HARMONY_MAX_ROUNDS   64
+typedef struct srx_harmony srx_harmony;   /* owns Z_corr, R, Y, O, E on the device; free it before its context */
+typedef struct srx_harmony_opts {
+    double   theta, sigma, lambda;
+    double   epsilon_cluster, epsilon_harmony;
+    uint64_t seed;
+    int32_t  n_clusters;            /* 0 = max(1, min((n + 15) / 30, 100)) */
+    int32_t  n_blocks;              /* 0 = 20 */
+    int32_t  max_rounds;            /* 0 = 10 */
+    int32_t  max_cluster_iters;     /* 0 = 20 */
+    int32_t  init_iters;            /* -1 = none, 0 = 10 */
+    int32_t  n_dims;                /* leading coordinates used, 0 = all */
+} srx_harmony_opts;
+typedef struct srx_harmony_info {
+    uint64_t n;
+    uint32_t d, n_batches, n_clusters, n_blocks, rounds, converged;
+    uint64_t cluster_iters;         /* over all rounds */
+    uint32_t round_iters[SRX_HARMONY_MAX_ROUNDS];
+    double   round_objective[SRX_HARMONY_MAX_ROUNDS];
+    double   ms;                    /* hipEvent time of the device work */
+} srx_harmony_info;
+enum { SRX_HARMONY_CORRECTED = 0 /* n x d */, SRX_HARMONY_R = 1 /* n x K */, SRX_HARMONY_CENTROIDS = 2 /* K x d */,
+       SRX_HARMONY_OBSERVED = 3 /* K x B */, SRX_HARMONY_EXPECTED = 4 /* K x B */ };
+/* The scores the last fit left on m, read where they lie with their leading dimension and left untouched (the cells are the
+ * column axis of a CSC handle, as for srx_knn_result); batch: n host labels.  *out is written on success only; info may be NULL. */
+int32_t srx_harmony_result(srx_mat* m, const uint32_t* batch, uint32_t n_batches, const srx_harmony_opts* opts, srx_harmony** out,
+                           srx_harmony_info* info);
+/* The same for caller-supplied points (n x d f64, row-major, host). */
+int32_t srx_harmony_points(srx_ctx* ctx, const double* points, uint64_t n, uint64_t d, const uint32_t* batch, uint32_t n_batches,
+                           const srx_harmony_opts* opts, srx_harmony** out, srx_harmony_info* info);
+/* One table, row-major f64. */
+int32_t srx_harmony_fetch(srx_harmony* h, int32_t which, double* out);
+int32_t srx_harmony_info_get(const srx_harmony* h, srx_harmony_info* info);
+/* srx_knn_result / srx_neighbors_result over the handle's corrected block, read where it lies: the same search, the same
+ * refusals, an ordinary srx_graph (Louvain, UMAP, diffusion maps and the _graph marker entries take it unchanged). */
+int32_t srx_knn_harmony(srx_harmony* h, const srx_knn_opts* opts, uint32_t* indices_out, double* distances_out, srx_knn_info* info);
+int32_t srx_neighbors_harmony(srx_harmony* h, const srx_knn_opts* opts, srx_knn_info* knn_info, srx_graph** out);
+void    srx_harmony_free(srx_harmony* h);
+
 /* The raw operators the PCA is built from, for a caller-supplied 64-column panel (k x 64
  * row-major): y_out (n_rows x 64) = X[:, sel] * panel, t_out (k x 64) = X[:, sel]^T * y, and
  * gram_out (k x k) = X[:, sel]^T X[:, sel] (panel not needed).  `sel` must be strictly

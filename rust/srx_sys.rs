@@ -13,6 +13,9 @@ pub const SRX_GROUPS_MAX: i32 = 4096;
 pub const SRX_UMAP_GROUP: i32 = 8;
 pub const SRX_UMAP_MAX_EPOCHS: i32 = 1048576;
 pub const SRX_DIFFMAP_GROUP: i32 = 8;
+pub const SRX_HARMONY_MAX_CLUSTERS: i32 = 256;
+pub const SRX_HARMONY_MAX_BATCHES: i32 = 256;
+pub const SRX_HARMONY_MAX_ROUNDS: i32 = 64;
 pub const SRX_OK: i32 = 0;
 pub const SRX_E_ARG: i32 = -1;
 pub const SRX_E_DTYPE: i32 = -2;
@@ -62,6 +65,11 @@ pub const SRX_MARKERS_RANKSUM2: i32 = 11;
 pub const SRX_UMAP_INIT_GIVEN: i32 = 0;
 pub const SRX_UMAP_INIT_RANDOM: i32 = 1;
 pub const SRX_UMAP_INIT_PCA: i32 = 2;
+pub const SRX_HARMONY_CORRECTED: i32 = 0;
+pub const SRX_HARMONY_R: i32 = 1;
+pub const SRX_HARMONY_CENTROIDS: i32 = 2;
+pub const SRX_HARMONY_OBSERVED: i32 = 3;
+pub const SRX_HARMONY_EXPECTED: i32 = 4;
 pub const SRX_BACKED_NORMALIZE: i32 = 1;
 pub const SRX_BACKED_LOG1P: i32 = 2;
 pub const SRX_K_NORMALIZE: i32 = 0;
@@ -84,6 +92,7 @@ pub const SRX_K_COUNT_: i32 = 13;
 #[repr(C)] pub struct SrxPcaModel { _private: [u8; 0] }      // opaque `srx_pca_model`
 #[repr(C)] pub struct SrxGraph { _private: [u8; 0] }      // opaque `srx_graph`
 #[repr(C)] pub struct SrxMarkers { _private: [u8; 0] }      // opaque `srx_markers`
+#[repr(C)] pub struct SrxHarmony { _private: [u8; 0] }      // opaque `srx_harmony`
 #[repr(C)] pub struct SrxBacked { _private: [u8; 0] }      // opaque `srx_backed`
 
 #[repr(C)]
@@ -320,6 +329,39 @@ pub struct SrxDiffmapInfo {      // `srx_diffmap_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxHarmonyOpts {      // `srx_harmony_opts`
+    pub theta: f64,
+    pub sigma: f64,
+    pub lambda: f64,
+    pub epsilon_cluster: f64,
+    pub epsilon_harmony: f64,
+    pub seed: u64,
+    pub n_clusters: i32,
+    pub n_blocks: i32,
+    pub max_rounds: i32,
+    pub max_cluster_iters: i32,
+    pub init_iters: i32,
+    pub n_dims: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxHarmonyInfo {      // `srx_harmony_info`
+    pub n: u64,
+    pub d: u32,
+    pub n_batches: u32,
+    pub n_clusters: u32,
+    pub n_blocks: u32,
+    pub rounds: u32,
+    pub converged: u32,
+    pub cluster_iters: u64,
+    pub round_iters: [u32; SRX_HARMONY_MAX_ROUNDS as usize],
+    pub round_objective: [f64; SRX_HARMONY_MAX_ROUNDS as usize],
+    pub ms: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPipelineResult {      // `srx_pipeline_result`
     pub pca: SrxPcaInfo,
     pub ms_normalize: f64,
@@ -447,6 +489,18 @@ extern "C" {
     pub fn srx_dpt(g: *mut SrxGraph, root: u64, cap: f64, pseudotime_out: *mut f64) -> i32;
     pub fn srx_dpt_from(ctx: *mut SrxCtx, evals: *const f64, evecs: *const f64, n: u64, m: u32, root: u64,
                         cap: f64, pseudotime_out: *mut f64) -> i32;
+    pub fn srx_harmony_result(m: *mut SrxMat, batch: *const u32, n_batches: u32, opts: *const SrxHarmonyOpts,
+                              out: *mut *mut SrxHarmony, info: *mut SrxHarmonyInfo) -> i32;
+    pub fn srx_harmony_points(ctx: *mut SrxCtx, points: *const f64, n: u64, d: u64, batch: *const u32,
+                              n_batches: u32, opts: *const SrxHarmonyOpts, out: *mut *mut SrxHarmony,
+                              info: *mut SrxHarmonyInfo) -> i32;
+    pub fn srx_harmony_fetch(h: *mut SrxHarmony, which: i32, out: *mut f64) -> i32;
+    pub fn srx_harmony_info_get(h: *const SrxHarmony, info: *mut SrxHarmonyInfo) -> i32;
+    pub fn srx_knn_harmony(h: *mut SrxHarmony, opts: *const SrxKnnOpts, indices_out: *mut u32,
+                           distances_out: *mut f64, info: *mut SrxKnnInfo) -> i32;
+    pub fn srx_neighbors_harmony(h: *mut SrxHarmony, opts: *const SrxKnnOpts, knn_info: *mut SrxKnnInfo,
+                                 out: *mut *mut SrxGraph) -> i32;
+    pub fn srx_harmony_free(h: *mut SrxHarmony);
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,

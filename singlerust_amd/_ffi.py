@@ -157,6 +157,23 @@ class DiffmapInfo(C.Structure):
                 ("max_ortho", C.c_double), ("ms", C.c_double)]
 
 
+HARMONY_MAX_CLUSTERS, HARMONY_MAX_BATCHES, HARMONY_MAX_ROUNDS = 256, 256, 64
+HARMONY_CORRECTED, HARMONY_R, HARMONY_CENTROIDS, HARMONY_OBSERVED, HARMONY_EXPECTED = range(5)
+
+
+class HarmonyOpts(C.Structure):
+    _fields_ = [("theta", C.c_double), ("sigma", C.c_double), ("lambda_", C.c_double), ("epsilon_cluster", C.c_double),
+                ("epsilon_harmony", C.c_double), ("seed", C.c_uint64), ("n_clusters", C.c_int32), ("n_blocks", C.c_int32),
+                ("max_rounds", C.c_int32), ("max_cluster_iters", C.c_int32), ("init_iters", C.c_int32), ("n_dims", C.c_int32)]
+
+
+class HarmonyInfo(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("d", C.c_uint32), ("n_batches", C.c_uint32), ("n_clusters", C.c_uint32),
+                ("n_blocks", C.c_uint32), ("rounds", C.c_uint32), ("converged", C.c_uint32), ("cluster_iters", C.c_uint64),
+                ("round_iters", C.c_uint32 * HARMONY_MAX_ROUNDS), ("round_objective", C.c_double * HARMONY_MAX_ROUNDS),
+                ("ms", C.c_double)]
+
+
 class SynthParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_rows_global", C.c_uint64), ("n_cols", C.c_uint64),
                 ("density", C.c_double), ("lib_sigma", C.c_double), ("type_decay", C.c_double),
@@ -259,6 +276,14 @@ _SIGS = {
     "srx_graph_transitions_fetch": (C.c_int32, [P, P]),
     "srx_dpt": (C.c_int32, [P, C.c_uint64, C.c_double, P]),
     "srx_dpt_from": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_double, P]),
+    "srx_harmony_result": (C.c_int32, [P, P, C.c_uint32, C.POINTER(HarmonyOpts), C.POINTER(P), C.POINTER(HarmonyInfo)]),
+    "srx_harmony_points": (C.c_int32, [P, P, C.c_uint64, C.c_uint64, P, C.c_uint32, C.POINTER(HarmonyOpts), C.POINTER(P),
+                                       C.POINTER(HarmonyInfo)]),
+    "srx_harmony_fetch": (C.c_int32, [P, C.c_int32, P]),
+    "srx_harmony_info_get": (C.c_int32, [P, C.POINTER(HarmonyInfo)]),
+    "srx_knn_harmony": (C.c_int32, [P, C.POINTER(KnnOpts), P, P, C.POINTER(KnnInfo)]),
+    "srx_neighbors_harmony": (C.c_int32, [P, C.POINTER(KnnOpts), C.POINTER(KnnInfo), C.POINTER(P)]),
+    "srx_harmony_free": (None, [P]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),

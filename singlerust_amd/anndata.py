@@ -311,6 +311,7 @@ class IMAnnData:
         self.obs_names, self.var_names = other.obs_names, other.var_names
         self.obsm, self.varm, self.obs, self.var, self.obsp = {}, {}, {}, {}, {}
         self._graph = None               # (its Graph frees the device handle)
+        self._harmony = None             # (the corrected scores belonged to the cells that left)
 
     def deep_clone(self) -> "IMAnnData":
         c = IMAnnData(self._x.clone(), self.indptr, self.indices, self.obs_names, self.var_names)

@@ -504,6 +504,14 @@ static int32_t graph_empty(srx_ctx* ctx, uint32_t k, srx_graph** out) {
     return SRX_OK;
 }
 
+// The graph of a k-NN list that lies on the device (n x k row-major, no row names itself): what srx_neighbors_result does
+// with the list of knn_result_resident, for the other holders of such a list (harmony.hip).
+int32_t graph_from_device_list(srx_ctx* ctx, const uint32_t* d_idx, const double* d_dist, uint64_t n, uint32_t k, srx_graph** out) {
+    Range rg("graph");
+    if (n == 0) return graph_empty(ctx, k, out);
+    return graph_build(ctx, d_idx, d_dist, n, k, out);
+}
+
 }  // namespace srx
 
 using namespace srx;

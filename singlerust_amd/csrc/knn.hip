@@ -494,6 +494,28 @@ int32_t knn_result_resident(srx_mat* m, const srx_knn_opts* opts, srx_knn_info* 
     return SRX_OK;
 }
 
+// The self search over n points that already lie on the device (harmony.hip: the corrected block of an srx_harmony), through
+// the same checks and the same KnnArgs as srx_knn_result.  d_idx / d_dist non-null: the list is also left on the device as
+// knn_result_resident leaves it (*n_out = 0 for n == 0).
+int32_t knn_self_device(srx_ctx* ctx, const double* d_pts, uint64_t n, uint64_t d_full, size_t ld, const srx_knn_opts* opts,
+                        uint32_t* indices_out, double* distances_out, srx_knn_info* info, const uint32_t** d_idx,
+                        const double** d_dist, uint64_t* n_out) {
+    if (n_out) *n_out = 0;
+    int d = 0;
+    SRX_TRY(knn_check(ctx, opts, n, n, d_full, true, &d));
+    if (info) memset(info, 0, sizeof *info);
+    if (n == 0) return SRX_OK;
+    Range rg("knn");
+    KnnArgs a{d_pts, d_pts, n, n, ld, ld, d, true};
+    SRX_TRY(knn_device(ctx, a, opts, indices_out, distances_out, info));
+    if (d_idx) {
+        SRX_TRY(scratch(ctx, "knn_idx", 0, (void**)d_idx));
+        SRX_TRY(scratch(ctx, "knn_dist", 0, (void**)d_dist));
+        *n_out = n;
+    }
+    return SRX_OK;
+}
+
 }  // namespace srx
 
 using namespace srx;

@@ -91,12 +91,25 @@ def connectivities_from_knn(ctx, indices, distances) -> Graph:
     return Graph(ctx, h)
 
 
-def _neighbors_graph(adata: IMAnnData, k: int, n_pcs, knn_lists: bool) -> dict:
+def _harmony_handle(adata: IMAnnData, use_rep: str):
+    """The ``Harmony`` handle that ``harmony_integrate`` kept on the adata under the basis ``use_rep``."""
+    kept = getattr(adata, "_harmony", None)
+    if kept is None or kept[0] != use_rep or not kept[1].handle:
+        raise F.SrxError(F.E_ARG, f"neighbors: use_rep={use_rep!r} names no representation on the device; run "
+                                  f"harmony_integrate(adata, batch, adjusted_basis={use_rep!r}) first")
+    return kept[1]
+
+
+def _neighbors_graph(adata: IMAnnData, k: int, n_pcs, knn_lists: bool, use_rep=None) -> dict:
     ctx = adata.x().ctx
     opts = F.KnnOpts(k, int(n_pcs or 0), 0, 0)
     info = F.KnnInfo()
     h = C.c_void_p()
-    F.check(F.lib().srx_neighbors_result(adata.x().handle, C.byref(opts), C.byref(info), C.byref(h)), ctx.handle)
+    if use_rep is None:
+        F.check(F.lib().srx_neighbors_result(adata.x().handle, C.byref(opts), C.byref(info), C.byref(h)), ctx.handle)
+    else:
+        F.check(F.lib().srx_neighbors_harmony(_harmony_handle(adata, use_rep).handle, C.byref(opts), C.byref(info), C.byref(h)),
+                ctx.handle)
     g = Graph(ctx, h)
     old = getattr(adata, "_graph", None)
     if old is not None:
@@ -113,11 +126,13 @@ def _neighbors_graph(adata: IMAnnData, k: int, n_pcs, knn_lists: bool) -> dict:
     adata.uns["neighbors"] = {"params": {"n_neighbors": k, "n_pcs": None if n_pcs is None else int(n_pcs),
                                          "include_self": False, "metric": "euclidean", "method": "umap"},
                               "info": _info_dict(info), "graph": g.info()}
+    if use_rep is not None:
+        adata.uns["neighbors"]["params"]["use_rep"] = use_rep
     return adata.uns["neighbors"]
 
 
 def neighbors(adata: IMAnnData, n_neighbors: int = 15, n_pcs=None, include_self: bool = False,
-              connectivities: bool = False, knn_lists: bool = False) -> dict:
+              connectivities: bool = False, knn_lists: bool = False, use_rep=None) -> dict:
     """Self graph of the cells in the space of the scores the last ``pca_inplace`` left on the device (no host round trip).
     Stores ``obsm["knn_indices"]`` (uint32, n_obs x k), ``obsm["knn_distances"]`` (f64) and ``uns["neighbors"]``
     (the parameters and the call's ``srx_knn_info``); returns the latter.  ``n_pcs``: use the leading PCs only.
@@ -125,24 +140,33 @@ def neighbors(adata: IMAnnData, n_neighbors: int = 15, n_pcs=None, include_self:
     ``connectivities=True`` builds the weighted graph on the device instead (``srx_neighbors_result``; ``include_self`` must
     be False): ``obsp["distances"]`` and ``obsp["connectivities"]`` (scipy CSR, or (indptr, indices, data) without scipy),
     ``uns["neighbors"]["graph"]`` (the ``srx_graph_info``), the device handle kept on the adata; ``obsm["knn_*"]`` are
-    filled from the rows of the distances only with ``knn_lists=True``."""
+    filled from the rows of the distances only with ``knn_lists=True``.
+
+    ``use_rep``: the ``adjusted_basis`` of a ``harmony_integrate`` on this adata (``"X_pca_harmony"``): the search reads the
+    corrected scores that call left on the device (``srx_knn_harmony`` / ``srx_neighbors_harmony``) instead of the PCA's."""
     n = adata.n_obs()
     k = int(n_neighbors)
     if connectivities:
         if include_self:
             raise F.SrxError(F.E_ARG, "neighbors: the graph is built from a list that excludes self (include_self=False)")
-        return _neighbors_graph(adata, k, n_pcs, knn_lists)
+        return _neighbors_graph(adata, k, n_pcs, knn_lists, use_rep)
     opts = F.KnnOpts(k, int(n_pcs or 0), int(bool(include_self)), 0)
     info = F.KnnInfo()
     idx = np.zeros((n, max(k, 0)), dtype=np.uint32)
     dist = np.zeros((n, max(k, 0)), dtype=np.float64)
-    F.check(F.lib().srx_knn_result(adata.x().handle, C.byref(opts), F.ptr(idx) if idx.size else None,
-                                   F.ptr(dist) if dist.size else None, C.byref(info)), adata.x().ctx.handle)
+    if use_rep is None:
+        F.check(F.lib().srx_knn_result(adata.x().handle, C.byref(opts), F.ptr(idx) if idx.size else None,
+                                       F.ptr(dist) if dist.size else None, C.byref(info)), adata.x().ctx.handle)
+    else:
+        F.check(F.lib().srx_knn_harmony(_harmony_handle(adata, use_rep).handle, C.byref(opts), F.ptr(idx) if idx.size else None,
+                                        F.ptr(dist) if dist.size else None, C.byref(info)), adata.x().ctx.handle)
     adata.obsm["knn_indices"] = idx
     adata.obsm["knn_distances"] = dist
     adata.uns["neighbors"] = {"params": {"n_neighbors": k, "n_pcs": None if n_pcs is None else int(n_pcs),
                                          "include_self": bool(include_self), "metric": "euclidean"},
                               "info": _info_dict(info)}
+    if use_rep is not None:
+        adata.uns["neighbors"]["params"]["use_rep"] = use_rep
     return adata.uns["neighbors"]
 
 
