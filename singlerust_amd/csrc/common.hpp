@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -59,6 +60,11 @@ __device__ __forceinline__ T wave_max(T v) {
     }
     return v;
 }
+
+// ---- finite tests, host and device: a comparison is false for a NaN, so each form below refuses one ------------------------
+constexpr double kDblMax = 1.79769313486231570815e308;
+__host__ __device__ __forceinline__ bool is_finite(double x) { return fabs(x) <= kDblMax; }
+__host__ __device__ __forceinline__ bool is_pos_finite(double x) { return x > 0.0 && x <= kDblMax; }
 
 // row r's entries in gene tile `tile`: [lo, hi) — indptr and the cached interior tile cuts of a matrix (ensure_tiles: d_tile_ptr)
 __device__ __forceinline__ void seg_bounds(const int64_t* __restrict__ indptr, const int64_t* __restrict__ tp,
@@ -263,6 +269,22 @@ struct ProfScope {
     ~ProfScope();
 };
 
+// A start / stop event pair on a stream.  start() creates both events and records the first; stop() records the second, waits
+// for it and reads the time between the two (an error without a start() that succeeded).
+class StreamTimer {
+  public:
+    StreamTimer(srx_ctx* c, hipStream_t s) : ctx(c), stream(s) {}
+    ~StreamTimer();                       // destroys what was created, whichever return the caller takes
+    int32_t start();
+    int32_t stop(double* ms);
+
+  private:
+    srx_ctx* ctx;
+    hipStream_t stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool started = false;
+};
+
 // ---- roctx ranges (rocprofiler-sdk-roctx, dlopen()ed on first use; a no-op when the library is absent) --------------
 // One range per pipeline stage, so that a `rocprofv3 --marker-trace` timeline shows normalise / moments / select /
 // compact / gram / iterate / transform beside the kernels.
@@ -290,6 +312,8 @@ struct RowXf {
 };
 int32_t tiles_from_idx16(srx_mat* m, hipStream_t stream);     // genes.hip: 32-bit indices + gene-tile cuts from an uploaded 16-bit mirror
 inline uint64_t at_least_one(uint64_t n) { return n ? n : 1; }   // sizes of buffers and grids that must not be empty
+inline unsigned grid256(uint64_t items) { return (unsigned)((at_least_one(items) + 255) / 256); }   // workgroups of 256, one thread per item
+inline size_t up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }                          // the parts of one allocation start 256-aligned
 int32_t ensure_tiles(srx_mat* m);
 int32_t ensure_pattern_counts(srx_mat* m);            // genes.hip
 // The per-gene moments cache of a matrix (genes.hip):

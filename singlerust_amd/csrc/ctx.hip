@@ -85,6 +85,27 @@ ProfScope::~ProfScope() {
     ctx->prof[cls].pending.emplace_back(e0, e1);
 }
 
+int32_t StreamTimer::start() {
+    SRX_HIP(ctx, hipEventCreate(&e0));
+    SRX_HIP(ctx, hipEventCreate(&e1));
+    SRX_HIP(ctx, hipEventRecord(e0, stream));
+    started = true;
+    return SRX_OK;
+}
+StreamTimer::~StreamTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+}
+int32_t StreamTimer::stop(double* ms) {
+    if (!started) return fail(ctx, SRX_E_HIP, "StreamTimer: stop() without start()");
+    SRX_HIP(ctx, hipEventRecord(e1, stream));
+    SRX_HIP(ctx, hipEventSynchronize(e1));
+    float f = 0.f;
+    SRX_HIP(ctx, hipEventElapsedTime(&f, e0, e1));
+    *ms = (double)f;
+    return SRX_OK;
+}
+
 static int32_t prof_drain(srx_ctx* ctx) {
     SRX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->comm_stream) SRX_HIP(ctx, hipStreamSynchronize(ctx->comm_stream));

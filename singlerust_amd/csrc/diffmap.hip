@@ -21,7 +21,7 @@
 // in fixed slots and k_dm_reduce adds the slots in a fixed order, so the whole result is bit-identical from call to call.
 //
 // Kernels:
-//   k_louvain_check    (srx_diffmap_csr; symcsr_check.hpp) the validation srx_louvain_csr runs
+//   (srx_diffmap_csr: k_symcsr_check of symcsr.hip validates the input)
 //   k_dm_rowsum        q_i or z_i: SRX_DIFFMAP_GROUP lanes per row, lane s adds the entries lo + s, lo + s + G, ..., butterfly
 //   k_dm_kernel        K_ij = C_ij / (q_i q_j) and z_i in the same walk
 //   k_dm_transitions   T_ij = K_ij / (sqrt(z_i) sqrt(z_j)), in place
@@ -40,8 +40,9 @@
 // profiles/diffmap.md compares): there is no run-time switch.
 #include "common.hpp"
 #include "graph_handle.hpp"
+#include "hash.hpp"
 #include "scan.hpp"
-#include "symcsr_check.hpp"
+#include "symcsr.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -51,7 +52,6 @@
 namespace srx {
 
 constexpr int kDmGroup = SRX_DIFFMAP_GROUP;
-constexpr uint64_t kDmGold = 0x9E3779B97F4A7C15ull;
 constexpr int kDmRows = 1024;                // rows a workgroup of the tall-skinny kernels owns
 constexpr int kDmMaxNcv = 129, kDmMaxComps = 64;
 constexpr int kDmMaxCols = kDmMaxNcv + kDmMaxComps + 1;
@@ -64,32 +64,6 @@ struct DmCtl {
     unsigned long long dpt_max;              // bits of the largest finite distance
     double alpha[kDmMaxNcv + 3], beta[kDmMaxNcv + 3];
 };
-
-struct DmGraph {
-    const uint64_t* ptr;
-    const uint32_t* ind;
-    const double* t;
-    uint64_t n;
-};
-
-// splitmix64's finaliser, as umap.hip states it
-__host__ __device__ __forceinline__ uint64_t dm_mix(uint64_t z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
-// the sum of v over the workgroup's 256 threads, in every thread, in an order fixed by the thread index alone
-__device__ __forceinline__ double dm_block_sum(double v, double* s_wave) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane_id() == 0) s_wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-}
 
 // ---- the operator ------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_dm_rowsum(const uint64_t* __restrict__ ptr, const double* __restrict__ w, uint64_t n,
@@ -137,7 +111,7 @@ __global__ void __launch_bounds__(256) k_dm_transitions(const uint64_t* __restri
     for (uint64_t e = lo + sub; e < hi; e += G) t[e] = t[e] / (si * sqrt(z[ind[e]]));
 }
 
-__global__ void __launch_bounds__(256) k_dm_matvec(DmGraph g, const double* __restrict__ x, double* __restrict__ y,
+__global__ void __launch_bounds__(256) k_dm_matvec(SymCsr g, const double* __restrict__ x, double* __restrict__ y,
                                                    const DmCtl* __restrict__ ctl) {
     constexpr int G = kDmGroup;
     if (ctl->stop) return;
@@ -146,7 +120,7 @@ __global__ void __launch_bounds__(256) k_dm_matvec(DmGraph g, const double* __re
     double acc = 0.0;
     if (row < g.n) {
         const uint64_t lo = g.ptr[row], hi = g.ptr[row + 1];
-        for (uint64_t e = lo + sub; e < hi; e += G) acc += g.t[e] * x[g.ind[e]];
+        for (uint64_t e = lo + sub; e < hi; e += G) acc += g.w[e] * x[g.ind[e]];
     }
     // every lane of the block is here: the butterfly reads all of them
     acc = group_sum<G>(acc);
@@ -160,8 +134,8 @@ __global__ void __launch_bounds__(256) k_dm_hashvec(double* __restrict__ v, uint
     if (ctl->stop) return;
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= ld) return;
-    const uint64_t z = dm_mix(seed + kDmGold * (serial * n + i + 1));
-    v[i] = i < n ? (double)(z >> 11) * 0x1p-53 - 0.5 : 0.0;
+    const uint64_t z = mix64(seed + kGold64 * (serial * n + i + 1));
+    v[i] = i < n ? unit53(z) - 0.5 : 0.0;
 }
 
 // slots[block * stride + c] = sum over the block's rows of V[c * ld + i] * w[i], c < ncols.  Wave v of the block takes the
@@ -203,7 +177,7 @@ __global__ void __launch_bounds__(256) k_dm_reduce(const double* __restrict__ sl
     const int c = blockIdx.x;
     double s = 0.0;
     for (unsigned b = threadIdx.x; b < nblk; b += 256) s += slots[(uint64_t)b * stride + c];
-    s = dm_block_sum(s, s_wave);
+    s = block_sum<4>(s, s_wave);
     if (threadIdx.x == 0) {
         out[c] = s;
         if (alpha >= 0 && c == (int)gridDim.x - 1) ctl->alpha[alpha] = second ? ctl->alpha[alpha] + s : s;
@@ -238,7 +212,7 @@ __global__ void __launch_bounds__(256) k_dm_update(const double* __restrict__ V,
         }
     }
     if (nslots) {
-        sq = dm_block_sum(sq, s_wave);
+        sq = block_sum<4>(sq, s_wave);
         if (threadIdx.x == 0) nslots[blockIdx.x] = sq;
     }
 }
@@ -250,7 +224,7 @@ __global__ void __launch_bounds__(256) k_dm_append(double* __restrict__ w, uint6
     if (ctl->stop) return;
     double s = 0.0;
     for (unsigned b = threadIdx.x; b < nblk; b += 256) s += nslots[b];
-    const double beta = sqrt(dm_block_sum(s, s_wave));
+    const double beta = sqrt(block_sum<4>(s, s_wave));
     if (!(beta > kDmBreak)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             ctl->beta[step] = 0.0;
@@ -362,14 +336,8 @@ __global__ void __launch_bounds__(256) k_dm_dpt(const double* __restrict__ E, ui
         const unsigned long long b = (unsigned long long)__double_as_longlong(v);
         bits = b < kDmInfBits ? b : 0;           // a NaN's bits lie above Inf's; v >= 0 or NaN
     }
-    bits = wave_max(bits);
-    if (lane_id() == 0) s_max[threadIdx.x >> 6] = bits;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = s_max[0];
-        for (int k = 1; k < 4; ++k) t = s_max[k] > t ? s_max[k] : t;
-        if (t) atomicMax(&ctl->dpt_max, t);      // an integer max: the same whatever the order
-    }
+    bits = block_max<4>(bits, s_max);
+    if (threadIdx.x == 0 && bits) atomicMax(&ctl->dpt_max, bits);      // an integer max: the same whatever the order
 }
 
 __global__ void __launch_bounds__(256) k_dm_dpt_scale(double* __restrict__ d, uint64_t n, const DmCtl* __restrict__ ctl) {
@@ -380,8 +348,6 @@ __global__ void __launch_bounds__(256) k_dm_dpt_scale(double* __restrict__ d, ui
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static unsigned dm_grid(uint64_t items) { return (unsigned)((at_least_one(items) + 255) / 256); }
-
 struct DmOpts {
     double tol;
     uint64_t seed;
@@ -465,7 +431,7 @@ static void dm_jacobi(int m, std::vector<double>& A, std::vector<double>& theta,
 struct DmRun {
     srx_ctx* ctx;
     hipStream_t st;
-    DmGraph g;
+    SymCsr g;
     uint64_t n, ld, seed, serial = 0;
     unsigned nblk;                     // workgroups of the tall-skinny kernels = norm slots
     int cap;                           // columns of V = the stride of the dot slots
@@ -480,7 +446,7 @@ struct DmRun {
     double* col(int c) const { return V + (uint64_t)c * ld; }
 
     void matvec(const double* x, double* y) const {
-        hipLaunchKernelGGL(k_dm_matvec, dim3(dm_grid(n * (uint64_t)kDmGroup)), dim3(256), 0, st, g, x, y, ctl);
+        hipLaunchKernelGGL(k_dm_matvec, dim3(grid256(n * (uint64_t)kDmGroup)), dim3(256), 0, st, g, x, y, ctl);
     }
     // w (a column of n rows, leading dimension ld) made orthogonal to the columns [0, ncols) of B by classical Gram-Schmidt,
     // twice; the partial sums of |w|^2 are left in nslots.  alpha >= 0: the coefficient of the last column is that step's alpha.
@@ -495,7 +461,7 @@ struct DmRun {
     void append(double* w, int step) const { hipLaunchKernelGGL(k_dm_append, dim3(nblk), dim3(256), 0, st, w, ld, nslots, nblk, step, ctl); }
     // column c <- a fresh hashed unit vector orthogonal to the columns before it
     void fresh(int c) {
-        hipLaunchKernelGGL(k_dm_hashvec, dim3(dm_grid(ld)), dim3(256), 0, st, col(c), n, ld, seed, serial++, ctl);
+        hipLaunchKernelGGL(k_dm_hashvec, dim3(grid256(ld)), dim3(256), 0, st, col(c), n, ld, seed, serial++, ctl);
         orth(V, c, col(c), -1);
         append(col(c), kDmDummy);
     }
@@ -509,7 +475,7 @@ struct DmRun {
         for (int j = 0; j < m; ++j)
             for (int c = 0; c < ks; ++c) pack[(size_t)j * ks + c] = Sm[(size_t)j * m + c];
         SRX_TRY(h2d(ctx, S, pack.data(), pack.size() * 8));
-        hipLaunchKernelGGL(k_dm_ritz, dim3(dm_grid(ld / 2), (ks + 7) / 8), dim3(256), 0, st, col(L), ld, m, S, ks, Z);
+        hipLaunchKernelGGL(k_dm_ritz, dim3(grid256(ld / 2), (ks + 7) / 8), dim3(256), 0, st, col(L), ld, m, S, ks, Z);
         SRX_HIP(ctx, hipMemcpyAsync(col(L), Z, (size_t)ks * ld * 8, hipMemcpyDeviceToDevice, st));
         return SRX_OK;
     }
@@ -599,22 +565,21 @@ struct DmResult {
     std::vector<double> evals;
 };
 
-// T from C (or the copy of it): the two normalisation passes.  t: nnz doubles; q, z: n doubles of scratch.
-static void dm_transitions(hipStream_t st, const uint64_t* ptr, const uint32_t* ind, const double* c, uint64_t n, uint64_t nnz, bool density,
-                           double* q, double* z, double* t) {
-    const unsigned blocks = dm_grid(n * (uint64_t)kDmGroup);
+// T from the graph c (C, or the copy of it): the two normalisation passes.  t: nnz doubles; q, z: n doubles of scratch.
+static void dm_transitions(hipStream_t st, const SymCsr& c, bool density, double* q, double* z, double* t) {
+    const unsigned blocks = grid256(c.n * (uint64_t)kDmGroup);
     if (density) {
-        hipLaunchKernelGGL(k_dm_rowsum, dim3(blocks), dim3(256), 0, st, ptr, c, n, q);
-        hipLaunchKernelGGL(k_dm_kernel, dim3(blocks), dim3(256), 0, st, ptr, ind, c, q, n, t, z);
+        hipLaunchKernelGGL(k_dm_rowsum, dim3(blocks), dim3(256), 0, st, c.ptr, c.w, c.n, q);
+        hipLaunchKernelGGL(k_dm_kernel, dim3(blocks), dim3(256), 0, st, c.ptr, c.ind, c.w, q, c.n, t, z);
     } else {
-        (void)hipMemcpyAsync(t, c, nnz * 8, hipMemcpyDeviceToDevice, st);
-        hipLaunchKernelGGL(k_dm_rowsum, dim3(blocks), dim3(256), 0, st, ptr, t, n, z);
+        (void)hipMemcpyAsync(t, c.w, c.nnz * 8, hipMemcpyDeviceToDevice, st);
+        hipLaunchKernelGGL(k_dm_rowsum, dim3(blocks), dim3(256), 0, st, c.ptr, t, c.n, z);
     }
-    hipLaunchKernelGGL(k_dm_transitions, dim3(blocks), dim3(256), 0, st, ptr, ind, z, n, t);
+    hipLaunchKernelGGL(k_dm_transitions, dim3(blocks), dim3(256), 0, st, c.ptr, c.ind, z, c.n, t);
 }
 
 // The whole solve on a T that lies on the device.  SRX_E_NOCONV leaves info's counters filled.
-static int32_t dm_run(srx_ctx* ctx, const DmGraph& g, uint64_t nnz, const DmOpts& o, DmResult* res, srx_diffmap_info* info) {
+static int32_t dm_run(srx_ctx* ctx, const SymCsr& g, const DmOpts& o, DmResult* res, srx_diffmap_info* info) {
     hipStream_t st = ctx->stream;
     const uint64_t n = g.n;
     const int nc = o.n_comps;
@@ -645,28 +610,17 @@ static int32_t dm_run(srx_ctx* ctx, const DmGraph& g, uint64_t nnz, const DmOpts
     r.h = d_small;
     double *d_lam = d_small + kDmMaxCols, *d_res2 = d_lam + kDmMaxComps, *d_sign = d_res2 + kDmMaxComps, *d_gram = d_sign + kDmMaxComps;
 
-    struct EvGuard {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EvGuard() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev;
-    SRX_HIP(ctx, hipEventCreate(&ev.a));
-    SRX_HIP(ctx, hipEventCreate(&ev.b));
-    SRX_HIP(ctx, hipEventRecord(ev.a, st));
+    StreamTimer timer(ctx, st);
+    SRX_TRY(timer.start());
     SRX_HIP(ctx, hipMemsetAsync(r.ctl, 0, sizeof(DmCtl), st));
     // only the padding rows of V need zeros: every column is written (rows < n by k_dm_matvec, all ld rows by the others)
     // before it is read, and Z is written whole by k_dm_ritz
     if (r.ld > n) SRX_HIP(ctx, hipMemset2DAsync(r.V + n, r.ld * 8, 0, (r.ld - n) * 8, (size_t)r.cap, st));
 
     auto finish_info = [&](double max_res, double max_ortho) -> int32_t {
-        SRX_HIP(ctx, hipEventRecord(ev.b, st));
-        SRX_HIP(ctx, hipEventSynchronize(ev.b));
-        float ms = 0.f;
-        SRX_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+        SRX_TRY(timer.stop(&info->ms));
         info->n = n;
-        info->nnz = nnz;
+        info->nnz = g.nnz;
         info->n_comps = (uint32_t)nc;
         info->ncv = (uint32_t)o.ncv;
         info->matvecs = (uint32_t)r.matvecs;
@@ -674,7 +628,6 @@ static int32_t dm_run(srx_ctx* ctx, const DmGraph& g, uint64_t nnz, const DmOpts
         info->breakdowns = (uint32_t)r.breakdowns;
         info->max_residual = max_res;
         info->max_ortho = max_ortho;
-        info->ms = (double)ms;
         return SRX_OK;
     };
 
@@ -736,7 +689,7 @@ static int32_t dm_run(srx_ctx* ctx, const DmGraph& g, uint64_t nnz, const DmOpts
     res->evals.resize(nc);
     for (int l = 0; l < nc; ++l) res->evals[l] = small[perm[l]];
     SRX_TRY(h2d(ctx, d_perm, perm.data(), (size_t)nc * 4));
-    hipLaunchKernelGGL(k_dm_emit, dim3(dm_grid(n * (uint64_t)nc)), dim3(256), 0, st, r.V, n, r.ld, nc, d_perm, d_sign, d_out);
+    hipLaunchKernelGGL(k_dm_emit, dim3(grid256(n * (uint64_t)nc)), dim3(256), 0, st, r.V, n, r.ld, nc, d_perm, d_sign, d_out);
     SRX_HIP(ctx, hipGetLastError());
     res->d_evecs = d_out;
     SRX_TRY(finish_info(max_res, max_ortho));
@@ -757,8 +710,8 @@ static int32_t dm_dpt(srx_ctx* ctx, const double* d_E, const double* evals, uint
     SRX_TRY(scratch(ctx, "dm_ctl", sizeof(DmCtl), (void**)&ctl));
     SRX_TRY(h2d(ctx, d_w, w, (size_t)m * 8));
     SRX_HIP(ctx, hipMemsetAsync(&ctl->dpt_max, 0, 8, st));
-    hipLaunchKernelGGL(k_dm_dpt, dim3(dm_grid(n)), dim3(256), 0, st, d_E, n, m, d_w, root, d_d, ctl);
-    hipLaunchKernelGGL(k_dm_dpt_scale, dim3(dm_grid(n)), dim3(256), 0, st, d_d, n, ctl);
+    hipLaunchKernelGGL(k_dm_dpt, dim3(grid256(n)), dim3(256), 0, st, d_E, n, m, d_w, root, d_d, ctl);
+    hipLaunchKernelGGL(k_dm_dpt_scale, dim3(grid256(n)), dim3(256), 0, st, d_d, n, ctl);
     SRX_HIP(ctx, hipGetLastError());
     return d2h(ctx, out, d_d, n * 8);
 }
@@ -783,30 +736,25 @@ int32_t srx_diffmap(srx_graph* g, const srx_diffmap_opts* opts, double* evals_ou
     SRX_TRY(dm_opts(ctx, opts, g->n, &o));
     SRX_HIP(ctx, hipSetDevice(ctx->device));
     Range rg("diffmap");
-    const uint64_t n = g->n, nnz = g->info.nnz_connectivities;
+    const SymCsr c = connectivities(g);
+    const uint64_t n = c.n, nnz = c.nnz;
     double *d_q, *d_z;
     SRX_TRY(scratch(ctx, "dm_q", n * 8, (void**)&d_q));
     SRX_TRY(scratch(ctx, "dm_z", n * 8, (void**)&d_z));
     g->dm_valid = g->dm_t_valid = false;
     if (!g->d_dm_t) SRX_HIP(ctx, hipMalloc((void**)&g->d_dm_t, at_least_one(nnz) * 8));
-    dm_transitions(ctx->stream, g->d_cptr, g->d_cind, g->d_cdat, n, nnz, o.density, d_q, d_z, g->d_dm_t);
+    dm_transitions(ctx->stream, c, o.density, d_q, d_z, g->d_dm_t);
     SRX_HIP(ctx, hipGetLastError());
     g->dm_t_valid = true;
     srx_diffmap_info li{};
     DmResult res;
-    const DmGraph dg{g->d_cptr, g->d_cind, g->d_dm_t, n};
-    const int32_t rc = dm_run(ctx, dg, nnz, o, &res, &li);
+    const int32_t rc = dm_run(ctx, SymCsr{c.ptr, c.ind, g->d_dm_t, n, nnz}, o, &res, &li);
     if (rc != SRX_OK) {
         if (rc == SRX_E_NOCONV && info) *info = li;
         return rc;
     }
     const size_t bytes = (size_t)n * o.n_comps * 8;
-    if (g->d_dm_evecs && g->dm_n_comps != (uint32_t)o.n_comps) {
-        SRX_HIP(ctx, hipFree(g->d_dm_evecs));
-        g->d_dm_evecs = nullptr;
-    }
-    if (!g->d_dm_evecs) SRX_HIP(ctx, hipMalloc((void**)&g->d_dm_evecs, bytes));
-    SRX_HIP(ctx, hipMemcpyAsync(g->d_dm_evecs, res.d_evecs, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    SRX_TRY(keep_on_handle(ctx, &g->d_dm_evecs, g->dm_n_comps != (uint32_t)o.n_comps, res.d_evecs, bytes));
     if (evecs_out) SRX_TRY(d2h(ctx, evecs_out, g->d_dm_evecs, bytes));
     else SRX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     g->dm_evals = res.evals;
@@ -828,18 +776,17 @@ int32_t srx_diffmap_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* in
             return fail(ctx, SRX_E_ARG, "diffmap: row %llu has no entries (its density q is 0)", (unsigned long long)i);
     SRX_HIP(ctx, hipSetDevice(ctx->device));
     Range rg("diffmap");
-    SymCsrDev in;
+    SymCsr in;
     SRX_TRY(symcsr_to_device(ctx, "diffmap", indptr, indices, weights, n, &in));
     double *d_q, *d_z, *d_t;
     SRX_TRY(scratch(ctx, "dm_q", n * 8, (void**)&d_q));
     SRX_TRY(scratch(ctx, "dm_z", n * 8, (void**)&d_z));
     SRX_TRY(scratch(ctx, "dm_t", at_least_one(in.nnz) * 8, (void**)&d_t));
-    dm_transitions(ctx->stream, in.ptr, in.ind, in.w, n, in.nnz, o.density, d_q, d_z, d_t);
+    dm_transitions(ctx->stream, in, o.density, d_q, d_z, d_t);
     SRX_HIP(ctx, hipGetLastError());
     srx_diffmap_info li{};
     DmResult res;
-    const DmGraph dg{in.ptr, in.ind, d_t, n};
-    const int32_t rc = dm_run(ctx, dg, in.nnz, o, &res, &li);
+    const int32_t rc = dm_run(ctx, SymCsr{in.ptr, in.ind, d_t, n, in.nnz}, o, &res, &li);
     if (rc != SRX_OK) {
         if (rc == SRX_E_NOCONV && info) *info = li;
         return rc;

@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(256) k_graph_rows(const uint32_t* __restrict__
     if (act) {
         if (ci >= n) bad |= kBadRange;
         if (ci == row) bad |= kBadSelf;
-        if (!(cd >= 0.0 && cd <= 1.79769313486231570815e308)) bad |= kBadDist;
+        if (!(cd >= 0.0 && cd <= kDblMax)) bad |= kBadDist;
     }
     int rank = 0;
     for (int m = 0; m < k; ++m) {
@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(256) k_graph_rows(const uint32_t* __restrict__
         if (S < T) {
             for (int it = 0; it < 2200; ++it) {
                 hi = lo * 2.0;
-                if (!(hi <= 1.79769313486231570815e308) || graph_S(one, far, x, hi) >= T) break;
+                if (!(hi <= kDblMax) || graph_S(one, far, x, hi) >= T) break;
                 lo = hi;
             }
         } else {
@@ -338,7 +338,6 @@ __global__ void __launch_bounds__(256) k_graph_merge(const uint32_t* __restrict_
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static int32_t graph_alloc(srx_ctx* ctx, uint64_t n, uint32_t k, srx_graph** out) {
     srx_graph* g = new srx_graph;
@@ -510,6 +509,16 @@ int32_t graph_from_device_list(srx_ctx* ctx, const uint32_t* d_idx, const double
     Range rg("graph");
     if (n == 0) return graph_empty(ctx, k, out);
     return graph_build(ctx, d_idx, d_dist, n, k, out);
+}
+
+int32_t keep_on_handle(srx_ctx* ctx, double** slot, bool resized, const double* d_src, size_t bytes) {
+    if (*slot && resized) {
+        SRX_HIP(ctx, hipFree(*slot));
+        *slot = nullptr;
+    }
+    if (!*slot) SRX_HIP(ctx, hipMalloc((void**)slot, bytes));
+    SRX_HIP(ctx, hipMemcpyAsync(*slot, d_src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return SRX_OK;
 }
 
 }  // namespace srx

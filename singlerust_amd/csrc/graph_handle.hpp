@@ -3,6 +3,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "symcsr.hpp"
 
 struct srx_graph {
     srx_ctx* ctx = nullptr;
@@ -34,3 +35,11 @@ struct srx_graph {
     uint32_t dm_n_comps = 0;
     bool dm_t_valid = false, dm_valid = false;
 };
+
+namespace srx {
+// C as the graph algorithms read it, where it lies
+inline SymCsr connectivities(const srx_graph* g) { return SymCsr{g->d_cptr, g->d_cind, g->d_cdat, g->n, g->info.nnz_connectivities}; }
+// A result kept with the handle (graph.hip): *slot (hipMalloc, freed first when `resized` says the array it holds has another
+// size) <- the `bytes` at d_src, queued on the context's stream.  The caller owns the flag that says whether *slot is valid.
+int32_t keep_on_handle(srx_ctx* ctx, double** slot, bool resized, const double* d_src, size_t bytes);
+}  // namespace srx

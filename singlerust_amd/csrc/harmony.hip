@@ -22,6 +22,7 @@
 // Every sum over cells is a chain over a contiguous chunk followed by chains over the chunks; chunk and run sizes depend on
 // (n, d, K, B) alone, so the result is bit-identical from call to call.
 #include "common.hpp"
+#include "hash.hpp"
 #include "pca_internal.hpp"
 
 #include <algorithm>
@@ -53,16 +54,8 @@ constexpr uint32_t kHmMaxBlocks = 65536;
 enum { kHard = 0, kSoft = 1, kObjective = 2 };
 enum { kFoldInit = 0, kFoldOut = 1, kFoldIn = 2, kFoldM = 3 };
 
-__host__ __device__ __forceinline__ uint64_t hm_mix(uint64_t z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
 __host__ __device__ __forceinline__ uint64_t hm_hash(uint64_t seed, uint64_t a, uint64_t i) {
-    return hm_mix(seed + 0x9E3779B97F4A7C15ull * (1ull + (a << 32) + i));
+    return mix64(seed + kGold64 * (1ull + (a << 32) + i));
 }
 
 __global__ void __launch_bounds__(256) k_hm_cosine(const double* __restrict__ x, size_t ld, uint64_t n, int d,
@@ -74,7 +67,7 @@ __global__ void __launch_bounds__(256) k_hm_cosine(const double* __restrict__ x,
     bool nf = false;
     for (int c = 0; c < d; ++c) {
         const double v = r[c];
-        nf |= !(fabs(v) <= 1.79769313486231570815e308);
+        nf |= !is_finite(v);
         s += v * v;
     }
     if (nf && bad) *bad = 1;
@@ -400,15 +393,13 @@ struct HmOpts {
     int K, n_blocks, max_rounds, max_iters, init_iters, d;
 };
 
-static bool hm_finite(double v) { return std::isfinite(v); }
-
 // options, without anything that depends on n
 static int32_t hm_opts(srx_ctx* ctx, const srx_harmony_opts* in, uint64_t d_full, HmOpts* o) {
     const srx_harmony_opts s = in ? *in : srx_harmony_opts{2.0, 0.1, 1.0, 1e-5, 1e-4, 0, 0, 0, 0, 0, 0, 0};
-    if (!(hm_finite(s.theta) && s.theta >= 0.0)) return fail(ctx, SRX_E_ARG, "harmony: theta must be finite and >= 0");
-    if (!(hm_finite(s.sigma) && s.sigma > 0.0)) return fail(ctx, SRX_E_ARG, "harmony: sigma must be finite and > 0");
-    if (!(hm_finite(s.lambda) && s.lambda > 0.0)) return fail(ctx, SRX_E_ARG, "harmony: lambda must be finite and > 0");
-    if (!(hm_finite(s.epsilon_cluster) && s.epsilon_cluster >= 0.0) || !(hm_finite(s.epsilon_harmony) && s.epsilon_harmony >= 0.0))
+    if (!(is_finite(s.theta) && s.theta >= 0.0)) return fail(ctx, SRX_E_ARG, "harmony: theta must be finite and >= 0");
+    if (!(is_finite(s.sigma) && s.sigma > 0.0)) return fail(ctx, SRX_E_ARG, "harmony: sigma must be finite and > 0");
+    if (!(is_finite(s.lambda) && s.lambda > 0.0)) return fail(ctx, SRX_E_ARG, "harmony: lambda must be finite and > 0");
+    if (!(is_finite(s.epsilon_cluster) && s.epsilon_cluster >= 0.0) || !(is_finite(s.epsilon_harmony) && s.epsilon_harmony >= 0.0))
         return fail(ctx, SRX_E_ARG, "harmony: epsilon_cluster and epsilon_harmony must be finite and >= 0");
     if (s.n_clusters < 0 || s.n_clusters > SRX_HARMONY_MAX_CLUSTERS)
         return fail(ctx, SRX_E_ARG, "harmony: n_clusters = %d outside 0..%d", s.n_clusters, SRX_HARMONY_MAX_CLUSTERS);
@@ -430,8 +421,6 @@ static int32_t hm_opts(srx_ctx* ctx, const srx_harmony_opts* in, uint64_t d_full
     return SRX_OK;
 }
 
-static size_t hm_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static int32_t hm_alloc(srx_ctx* ctx, uint64_t n, uint32_t d, uint32_t K, uint32_t B, srx_harmony** out) {
     srx_harmony* h = new srx_harmony;
     h->ctx = ctx;
@@ -439,8 +428,8 @@ static int32_t hm_alloc(srx_ctx* ctx, uint64_t n, uint32_t d, uint32_t K, uint32
     h->d = d;
     h->K = K;
     h->B = B;
-    const size_t o_r = hm_up(n * d * 8), o_y = o_r + hm_up(n * K * 8), o_o = o_y + hm_up((size_t)K * d * 8),
-                 o_e = o_o + hm_up((size_t)K * B * 8), total = o_e + hm_up((size_t)K * B * 8);
+    const size_t o_r = up256(n * d * 8), o_y = o_r + up256(n * K * 8), o_o = o_y + up256((size_t)K * d * 8),
+                 o_e = o_o + up256((size_t)K * B * 8), total = o_e + up256((size_t)K * B * 8);
     hipError_t e = hipMalloc(&h->d_block, total + 256);
     if (e != hipSuccess) {
         delete h;
@@ -542,16 +531,8 @@ static int32_t hm_run(srx_ctx* ctx, const double* x, size_t ld, uint64_t n, cons
     SRX_TRY(h2d(ctx, d_lo, lo.data(), lo.size() * 8));
     SRX_TRY(h2d(ctx, d_pb, pb.data(), (size_t)B * 8));
 
-    struct EvGuard {
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EvGuard() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev;
-    SRX_HIP(ctx, hipEventCreate(&ev.a));
-    SRX_HIP(ctx, hipEventCreate(&ev.b));
-    SRX_HIP(ctx, hipEventRecord(ev.a, st));
+    StreamTimer timer(ctx, st);
+    SRX_TRY(timer.start());
 
     SRX_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, st));
     hipLaunchKernelGGL(k_hm_cosine, dim3(grid_n), dim3(256), 0, st, x, ld, n, d, d_zh, d_bad);
@@ -631,12 +612,8 @@ static int32_t hm_run(srx_ctx* ctx, const double* x, size_t ld, uint64_t n, cons
             }
         }
     }
-    SRX_HIP(ctx, hipEventRecord(ev.b, st));
-    SRX_HIP(ctx, hipStreamSynchronize(st));
-    float ms = 0.f;
-    SRX_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+    SRX_TRY(timer.stop(&info.ms));
     info.cluster_iters = t;
-    info.ms = (double)ms;
     return SRX_OK;
 }
 

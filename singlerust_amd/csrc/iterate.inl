@@ -363,12 +363,6 @@ __global__ __launch_bounds__(256) void k_right_mul(const double* __restrict__ In
 constexpr int kStatChol = 1, kStatEig = 2;
 
 // Start block: counter-based N(0,1) entries, deterministic in (seed, gene slot, column).
-__device__ __forceinline__ uint64_t dmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __global__ void k_identity_block(int k, double* __restrict__ W) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < k * L) W[e] = (e / L == e % L) ? 1.0 : 0.0;
@@ -386,8 +380,8 @@ __global__ void k_init_block(uint64_t seed, int k, int l_act, double* __restrict
     const int j = e / L, cc = e % L;
     double v = 0.0;
     if (cc < l_act) {
-        const uint64_t base = dmix64(seed ^ dmix64((uint64_t)j));
-        const uint64_t h1 = dmix64(base + 2 * (uint64_t)cc), h2 = dmix64(base + 2 * (uint64_t)cc + 1);
+        const uint64_t base = splitmix64(seed ^ splitmix64((uint64_t)j));
+        const uint64_t h1 = splitmix64(base + 2 * (uint64_t)cc), h2 = splitmix64(base + 2 * (uint64_t)cc + 1);
         const double u1 = ((double)(h1 >> 11) + 0.5) / 9007199254740992.0;
         const double u2 = ((double)(h2 >> 11) + 0.5) / 9007199254740992.0;
         v = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);

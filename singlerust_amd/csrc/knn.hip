@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(256) k_knn_colsum(const double* __restrict__ x
     if (col < d)
         for (uint64_t r = r0 + lane_row; r < r1; r += rows_per_it) {
             const double v = x[r * ld + col];
-            nf |= !(fabs(v) <= 1.79769313486231570815e308);
+            nf |= !is_finite(v);
             s += v;
         }
     if (nf) *bad = 1;

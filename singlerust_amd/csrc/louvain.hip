@@ -19,7 +19,7 @@
 // first, coarser scale), and every level's 2m is read back and checked against the range.
 //
 // Kernels:
-//   k_louvain_check     (srx_louvain_csr; symcsr_check.hpp) wave per row: index range, diagonal, order, weights, W_ij == W_ji
+//   (srx_louvain_csr: k_symcsr_check of symcsr.hip validates the input)
 //   k_louvain_degree    thread per row: k_i in row order, singleton start, max k_i
 //   k_louvain_scale     one thread: S from max k_i * n, then from 2m; 2m of the level
 //   k_louvain_quant     q(k_i), tot of the singletons, their sum
@@ -42,7 +42,7 @@
 #include "common.hpp"
 #include "graph_handle.hpp"
 #include "scan.hpp"
-#include "symcsr_check.hpp"
+#include "symcsr.hpp"
 
 #include <cmath>
 
@@ -55,12 +55,8 @@ constexpr uint32_t kLvEmpty = 0xFFFFFFFFu;
 enum { LV_KMAX = 0, LV_MOVES, LV_NCOMM, LV_FLAG, LV_SHIFT, LV_SCALE, LV_INV, LV_TWOM, LV_WSCALE, LV_WINV, LV_ACC, LV_IN = LV_ACC + kLvSlots,
        LV_SQ = LV_IN + kLvSlots, LV_WORDS = LV_SQ + kLvSlots };
 
-struct LvGraph {                         // one level's graph; self == nullptr: no self weights (the input)
-    const uint64_t* ptr;
-    const uint32_t* ind;
-    const double* w;
+struct LvGraph : SymCsr {                // one level's graph; self == nullptr: no self weights (the input)
     const double* self;
-    uint64_t n, nnz;
 };
 
 __device__ __forceinline__ long long lv_fix(double x, double scale) { return __double2ll_rn(x * scale); }
@@ -100,7 +96,7 @@ __global__ void k_louvain_scale(unsigned long long* __restrict__ small, uint64_t
         // the finer scale of sums that stay inside one row (at most max k_i < 2^e): 2^(60 - e)
         const double kmax = __longlong_as_double((long long)small[LV_KMAX]);
         int ek = 0;
-        if (kmax > 0.0 && kmax <= 1.79769313486231570815e308) (void)frexp(kmax, &ek);
+        if (is_pos_finite(kmax)) (void)frexp(kmax, &ek);
         const int ws = 60 - ek > 1000 ? 1000 : 60 - ek < -1000 ? -1000 : 60 - ek;
         sd[LV_WSCALE] = ldexp(1.0, ws);
         sd[LV_WINV] = ldexp(1.0, -ws);
@@ -108,7 +104,7 @@ __global__ void k_louvain_scale(unsigned long long* __restrict__ small, uint64_t
     }
     const double bound = stage == 0 ? __longlong_as_double((long long)small[LV_KMAX]) * (double)n : (double)total * sd[LV_INV];
     int e = 0;
-    if (bound > 0.0 && bound <= 1.79769313486231570815e308) (void)frexp(bound, &e);        // bound < 2^e
+    if (is_pos_finite(bound)) (void)frexp(bound, &e);        // bound < 2^e
     int shift = 60 - e;
     shift = shift > 1000 ? 1000 : shift < -1000 ? -1000 : shift;
     small[LV_SHIFT] = (unsigned long long)(long long)shift;
@@ -502,11 +498,9 @@ __global__ void __launch_bounds__(256) k_louvain_relabel(const uint32_t* __restr
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static unsigned lv_grid(uint64_t items) { return (unsigned)((at_least_one(items) + 255) / 256); }
-
 static int32_t lv_opts(srx_ctx* ctx, const srx_louvain_opts* in, srx_louvain_opts* o) {
     *o = in ? *in : srx_louvain_opts{1.0, 0.0, 0, 0};
-    if (!(o->resolution > 0.0) || !(o->resolution <= 1.79769313486231570815e308))
+    if (!is_pos_finite(o->resolution))
         return fail(ctx, SRX_E_ARG, "louvain: resolution must be a positive finite number");
     if (!(o->min_gain >= 0.0)) return fail(ctx, SRX_E_ARG, "louvain: min_gain must be >= 0");
     if (o->max_levels < 0 || o->max_levels > SRX_LOUVAIN_MAX_LEVELS)
@@ -528,8 +522,8 @@ static int32_t lv_modularity(srx_ctx* ctx, const LvGraph& g, const uint32_t* d_c
     hipStream_t st = ctx->stream;
     SRX_HIP(ctx, hipMemsetAsync(d_small + LV_IN, 0, 2 * kLvSlots * 8, st));
     SRX_HIP(ctx, hipMemsetAsync(d_small + LV_NCOMM, 0, 8, st));
-    hipLaunchKernelGGL(k_louvain_q_in, dim3(lv_grid(g.n)), dim3(256), 0, st, g, d_comm, d_small);
-    hipLaunchKernelGGL(k_louvain_q_tot, dim3(lv_grid(g.n)), dim3(256), 0, st, d_tot, d_size, g.n, d_small);
+    hipLaunchKernelGGL(k_louvain_q_in, dim3(grid256(g.n)), dim3(256), 0, st, g, d_comm, d_small);
+    hipLaunchKernelGGL(k_louvain_q_tot, dim3(grid256(g.n)), dim3(256), 0, st, d_tot, d_size, g.n, d_small);
     SRX_HIP(ctx, hipGetLastError());
     uint64_t h[LV_WORDS];
     SRX_TRY(d2h(ctx, h, d_small, sizeof h));
@@ -546,10 +540,10 @@ static int32_t lv_modularity(srx_ctx* ctx, const LvGraph& g, const uint32_t* d_c
     return SRX_OK;
 }
 
-// The run.  d_ptr / d_ind / d_w: the input on the device (n >= 1); d_labels: n u32 on the device.
-static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* d_ind, const double* d_w, uint64_t n, uint64_t nnz,
-                           const srx_louvain_opts& o, uint32_t* d_labels, srx_louvain_info* info) {
+// The run.  in: the input on the device (n >= 1); d_labels: n u32 on the device.
+static int32_t louvain_run(srx_ctx* ctx, const SymCsr& in, const srx_louvain_opts& o, uint32_t* d_labels, srx_louvain_info* info) {
     hipStream_t st = ctx->stream;
+    const uint64_t n = in.n;
     const double gamma = o.resolution;
     unsigned long long *d_small, *d_tot, *d_hval = nullptr;
     double* d_kdeg;
@@ -573,19 +567,11 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
     SRX_TRY(scratch(ctx, "louvain_s0", (n + 1) * 8, (void**)&d_s0));
     SRX_TRY(scratch(ctx, "louvain_s1", (n + 1) * 8, (void**)&d_s1));
 
-    struct EvGuard {                     // destroys what was created, whichever return is taken
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EvGuard() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev;
-    SRX_HIP(ctx, hipEventCreate(&ev.a));
-    SRX_HIP(ctx, hipEventCreate(&ev.b));
-    SRX_HIP(ctx, hipEventRecord(ev.a, st));
+    StreamTimer timer(ctx, st);
+    SRX_TRY(timer.start());
 
-    LvGraph g{d_ptr, d_ind, d_w, nullptr, n, nnz};
-    hipLaunchKernelGGL(k_louvain_compose, dim3(lv_grid(n)), dim3(256), 0, st, d_cell, n, (const uint32_t*)nullptr, (const int64_t*)nullptr);
+    LvGraph g{in, nullptr};
+    hipLaunchKernelGGL(k_louvain_compose, dim3(grid256(n)), dim3(256), 0, st, d_cell, n, (const uint32_t*)nullptr, (const int64_t*)nullptr);
     uint64_t n_comm = n;
     double q_prev = 0.0;
     bool have_q = false;
@@ -593,14 +579,14 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
     for (int level = 0; level < o.max_levels; ++level) {
         // singletons, degrees, the scale (first level) and 2m
         SRX_HIP(ctx, hipMemsetAsync(d_small, 0, (level == 0 ? LV_WORDS : LV_SHIFT) * 8, st));
-        hipLaunchKernelGGL(k_louvain_degree, dim3(lv_grid(g.n)), dim3(256), 0, st, g, d_kdeg, d_comm, d_size, d_small);
+        hipLaunchKernelGGL(k_louvain_degree, dim3(grid256(g.n)), dim3(256), 0, st, g, d_kdeg, d_comm, d_size, d_small);
         if (level == 0) {
             hipLaunchKernelGGL(k_louvain_scale, dim3(1), dim3(64), 0, st, d_small, g.n, 0);
-            hipLaunchKernelGGL(k_louvain_quant, dim3(lv_grid(g.n)), dim3(256), 0, st, d_kdeg, g.n, (long long*)nullptr,
+            hipLaunchKernelGGL(k_louvain_quant, dim3(grid256(g.n)), dim3(256), 0, st, d_kdeg, g.n, (long long*)nullptr,
                                (unsigned long long*)nullptr, d_small);
             hipLaunchKernelGGL(k_louvain_scale, dim3(1), dim3(64), 0, st, d_small, g.n, 1);
         }
-        hipLaunchKernelGGL(k_louvain_quant, dim3(lv_grid(g.n)), dim3(256), 0, st, d_kdeg, g.n, d_kq, d_tot, d_small);
+        hipLaunchKernelGGL(k_louvain_quant, dim3(grid256(g.n)), dim3(256), 0, st, d_kdeg, g.n, d_kq, d_tot, d_small);
         hipLaunchKernelGGL(k_louvain_scale, dim3(1), dim3(64), 0, st, d_small, g.n, 2);
         SRX_HIP(ctx, hipGetLastError());
         SRX_TRY(d2h(ctx, h, d_small, sizeof h));
@@ -608,7 +594,7 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
         memcpy(&twom, &h[LV_TWOM], 8);
         memcpy(&kmax, &h[LV_KMAX], 8);
         memcpy(&scale, &h[LV_SCALE], 8);
-        if (!(kmax <= 1.79769313486231570815e308)) return fail(ctx, SRX_E_ARG, "louvain: the weights of a row sum to Inf");
+        if (!(kmax <= kDblMax)) return fail(ctx, SRX_E_ARG, "louvain: the weights of a row sum to Inf");
         if (twom == 0.0) break;                              // no edges: singletons, Q = 0
         // the asserted range of the fixed point: 2m, the largest sum there is, below 2^61
         if (!(twom * scale < 2305843009213693952.0))
@@ -620,10 +606,10 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
             have_q = true;
         }
         // rows longer than a wave: their list and their tables
-        hipLaunchKernelGGL(k_louvain_classify, dim3(lv_grid(g.n)), dim3(256), 0, st, g.ptr, g.n, d_i0, d_i1);
+        hipLaunchKernelGGL(k_louvain_classify, dim3(grid256(g.n)), dim3(256), 0, st, g.ptr, g.n, d_i0, d_i1);
         SRX_TRY(scan_exclusive(ctx, d_i0, g.n, d_s0, nullptr));
         SRX_TRY(scan_exclusive(ctx, d_i1, g.n, d_s1, nullptr));
-        hipLaunchKernelGGL(k_louvain_biglist, dim3(lv_grid(g.n)), dim3(256), 0, st, d_i0, d_s0, g.n, d_big);
+        hipLaunchKernelGGL(k_louvain_biglist, dim3(grid256(g.n)), dim3(256), 0, st, d_i0, d_s0, g.n, d_big);
         SRX_HIP(ctx, hipGetLastError());
         int64_t n_big = 0, n_slots = 0;
         SRX_TRY(d2h(ctx, &n_big, d_s0 + g.n, 8));
@@ -636,14 +622,14 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
         int quiet = 0;
         for (int t = 0; t < o.max_sweeps && quiet < 2; ++t) {
             SRX_HIP(ctx, hipMemsetAsync(d_small + LV_MOVES, 0, 8, st));
-            hipLaunchKernelGGL(k_louvain_move<32>, dim3(lv_grid(g.n * 32)), dim3(256), 0, st, g, 0, d_kdeg, d_kq, d_comm, d_tot, d_size,
+            hipLaunchKernelGGL(k_louvain_move<32>, dim3(grid256(g.n * 32)), dim3(256), 0, st, g, 0, d_kdeg, d_kq, d_comm, d_tot, d_size,
                                d_next, d_small, gamma, t & 1);
-            hipLaunchKernelGGL(k_louvain_move<64>, dim3(lv_grid(g.n * 64)), dim3(256), 0, st, g, 32, d_kdeg, d_kq, d_comm, d_tot, d_size,
+            hipLaunchKernelGGL(k_louvain_move<64>, dim3(grid256(g.n * 64)), dim3(256), 0, st, g, 32, d_kdeg, d_kq, d_comm, d_tot, d_size,
                                d_next, d_small, gamma, t & 1);
             if (n_big)
                 hipLaunchKernelGGL(k_louvain_move_big, dim3((unsigned)n_big), dim3(256), 0, st, g, d_big, d_s1, d_hkey, d_hval, d_kdeg, d_kq,
                                    d_comm, d_tot, d_size, d_next, d_small, gamma, t & 1);
-            hipLaunchKernelGGL(k_louvain_apply, dim3(lv_grid(g.n)), dim3(256), 0, st, d_comm, d_next, g.n, d_kq, d_tot, d_size, d_small);
+            hipLaunchKernelGGL(k_louvain_apply, dim3(grid256(g.n)), dim3(256), 0, st, d_comm, d_next, g.n, d_kq, d_tot, d_size, d_small);
             SRX_HIP(ctx, hipGetLastError());
             uint64_t mv = 0;
             SRX_TRY(d2h(ctx, &mv, d_small + LV_MOVES, 8));
@@ -657,9 +643,9 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
         SRX_TRY(lv_modularity(ctx, g, d_comm, d_tot, d_size, d_small, gamma, &q));
         if (!(q.q > q_prev + o.min_gain)) break;              // the level is discarded
         // compact ids; the level is kept
-        hipLaunchKernelGGL(k_louvain_flag, dim3(lv_grid(g.n)), dim3(256), 0, st, d_size, g.n, d_i0, d_i1);
+        hipLaunchKernelGGL(k_louvain_flag, dim3(grid256(g.n)), dim3(256), 0, st, d_size, g.n, d_i0, d_i1);
         SRX_TRY(scan_exclusive(ctx, d_i0, g.n, d_s0, nullptr));          // newid
-        hipLaunchKernelGGL(k_louvain_compose, dim3(lv_grid(n)), dim3(256), 0, st, d_cell, n, d_comm, d_s0);
+        hipLaunchKernelGGL(k_louvain_compose, dim3(grid256(n)), dim3(256), 0, st, d_cell, n, d_comm, d_s0);
         SRX_HIP(ctx, hipGetLastError());
         q_prev = q.q;
         n_comm = q.n_comm;
@@ -671,9 +657,9 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
         if (level + 1 == o.max_levels || n_comm <= 1) break;
         // the next level's graph
         SRX_TRY(scan_exclusive(ctx, d_i1, g.n, d_s1, nullptr));          // member offsets by old id
-        hipLaunchKernelGGL(k_louvain_oldof, dim3(lv_grid(g.n)), dim3(256), 0, st, d_i0, d_s0, g.n, d_oldof);
+        hipLaunchKernelGGL(k_louvain_oldof, dim3(grid256(g.n)), dim3(256), 0, st, d_i0, d_s0, g.n, d_oldof);
         SRX_HIP(ctx, hipMemsetAsync(d_cursor, 0, g.n * 4, st));
-        hipLaunchKernelGGL(k_louvain_members, dim3(lv_grid(g.n)), dim3(256), 0, st, d_comm, g.n, d_s1, d_cursor, d_members);
+        hipLaunchKernelGGL(k_louvain_members, dim3(grid256(g.n)), dim3(256), 0, st, d_comm, g.n, d_s1, d_cursor, d_members);
         const char* set = (level & 1) ? "b" : "a";
         char name[4][32];
         snprintf(name[0], 32, "louvain_%s_ptr", set);
@@ -697,11 +683,11 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
         SRX_HIP(ctx, hipMemsetAsync(d_cacc, 0, at_least_one((uint64_t)nnz_c) * 8, st));
         hipLaunchKernelGGL(k_louvain_coarse<true>, dim3((unsigned)n_comm), dim3(256), 0, st, g, d_comm, d_s0, d_oldof, d_s1, d_members, n_comm,
                            d_small, (int64_t*)nullptr, (unsigned long long*)nullptr, d_cptr, d_cind, d_cacc);
-        hipLaunchKernelGGL(k_louvain_unfix, dim3(lv_grid((uint64_t)nnz_c)), dim3(256), 0, st, d_cacc, (uint64_t)nnz_c, d_small);
-        hipLaunchKernelGGL(k_louvain_unfix, dim3(lv_grid(n_comm)), dim3(256), 0, st, d_selfq, n_comm, d_small);
+        hipLaunchKernelGGL(k_louvain_unfix, dim3(grid256((uint64_t)nnz_c)), dim3(256), 0, st, d_cacc, (uint64_t)nnz_c, d_small);
+        hipLaunchKernelGGL(k_louvain_unfix, dim3(grid256(n_comm)), dim3(256), 0, st, d_selfq, n_comm, d_small);
         SRX_HIP(ctx, hipGetLastError());
-        g = LvGraph{reinterpret_cast<const uint64_t*>(d_cptr), d_cind, reinterpret_cast<const double*>(d_cacc),
-                    reinterpret_cast<const double*>(d_selfq), n_comm, (uint64_t)nnz_c};
+        g = LvGraph{SymCsr{reinterpret_cast<const uint64_t*>(d_cptr), d_cind, reinterpret_cast<const double*>(d_cacc), n_comm, (uint64_t)nnz_c},
+                    reinterpret_cast<const double*>(d_selfq)};
     }
     // final labels: communities by (size descending, smallest member)
     uint64_t n_pad = 1;
@@ -711,22 +697,18 @@ static int32_t louvain_run(srx_ctx* ctx, const uint64_t* d_ptr, const uint32_t* 
     SRX_TRY(scratch(ctx, "louvain_keys", n_pad * 8, (void**)&d_keys));
     SRX_HIP(ctx, hipMemsetAsync(d_csize, 0, n_comm * 4, st));
     SRX_HIP(ctx, hipMemsetAsync(d_cmin, 0xFF, n_comm * 4, st));
-    hipLaunchKernelGGL(k_louvain_sizes, dim3(lv_grid(n)), dim3(256), 0, st, d_cell, n, d_csize, d_cmin);
-    hipLaunchKernelGGL(k_louvain_keys, dim3(lv_grid(n_pad)), dim3(256), 0, st, d_csize, d_cmin, n_comm, n_pad, d_keys);
+    hipLaunchKernelGGL(k_louvain_sizes, dim3(grid256(n)), dim3(256), 0, st, d_cell, n, d_csize, d_cmin);
+    hipLaunchKernelGGL(k_louvain_keys, dim3(grid256(n_pad)), dim3(256), 0, st, d_csize, d_cmin, n_comm, n_pad, d_keys);
     for (uint64_t k = 2; k <= n_pad; k <<= 1)
         for (uint64_t j = k >> 1; j > 0; j >>= 1)
-            hipLaunchKernelGGL(k_louvain_bitonic, dim3(lv_grid(n_pad)), dim3(256), 0, st, d_keys, n_pad, j, k);
-    hipLaunchKernelGGL(k_louvain_rank, dim3(lv_grid(n_comm)), dim3(256), 0, st, d_keys, n_comm, d_cell, d_rank);
-    hipLaunchKernelGGL(k_louvain_relabel, dim3(lv_grid(n)), dim3(256), 0, st, d_cell, n, d_rank, d_labels);
+            hipLaunchKernelGGL(k_louvain_bitonic, dim3(grid256(n_pad)), dim3(256), 0, st, d_keys, n_pad, j, k);
+    hipLaunchKernelGGL(k_louvain_rank, dim3(grid256(n_comm)), dim3(256), 0, st, d_keys, n_comm, d_cell, d_rank);
+    hipLaunchKernelGGL(k_louvain_relabel, dim3(grid256(n)), dim3(256), 0, st, d_cell, n, d_rank, d_labels);
     SRX_HIP(ctx, hipGetLastError());
-    SRX_HIP(ctx, hipEventRecord(ev.b, st));
-    SRX_HIP(ctx, hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    SRX_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+    SRX_TRY(timer.stop(&info->ms));
     info->n = n;
     info->n_communities = n_comm;
     info->modularity = have_q ? q_prev : 0.0;
-    info->ms = (double)ms;
     return SRX_OK;
 }
 
@@ -748,7 +730,7 @@ int32_t srx_louvain(srx_graph* g, const srx_louvain_opts* opts, uint32_t* labels
     if (g->n) {
         Range rg("louvain");
         if (!g->d_labels) SRX_HIP(ctx, hipMalloc((void**)&g->d_labels, g->n * 4));
-        SRX_TRY(louvain_run(ctx, g->d_cptr, g->d_cind, g->d_cdat, g->n, g->info.nnz_connectivities, o, g->d_labels, &li));
+        SRX_TRY(louvain_run(ctx, connectivities(g), o, g->d_labels, &li));
         if (labels_out) SRX_TRY(d2h(ctx, labels_out, g->d_labels, g->n * 4));
     }
     g->labels_valid = true;
@@ -769,11 +751,11 @@ int32_t srx_louvain_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* in
         return SRX_OK;
     }
     Range rg("louvain");
-    SymCsrDev in;
+    SymCsr in;
     SRX_TRY(symcsr_to_device(ctx, "louvain", indptr, indices, weights, n, &in));
     uint32_t* d_labels;
     SRX_TRY(scratch(ctx, "louvain_labels", n * 4, (void**)&d_labels));
-    SRX_TRY(louvain_run(ctx, in.ptr, in.ind, in.w, n, in.nnz, o, d_labels, &li));
+    SRX_TRY(louvain_run(ctx, in, o, d_labels, &li));
     if (labels_out) SRX_TRY(d2h(ctx, labels_out, d_labels, n * 4));
     if (info) *info = li;
     return SRX_OK;

@@ -459,7 +459,7 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
     {
         const uint64_t cells = (uint64_t)n_groups * at_least_one(G), tops = (uint64_t)n_groups * at_least_one(n_top);
         size_t off = 0;
-        auto carve = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+        auto carve = [&](size_t bytes) { const size_t at = off; off += up256(bytes); return at; };
         const size_t oS = carve(cells * 8), oQ = carve(cells * 8), otS = carve(at_least_one(G) * 8), otQ = carve(at_least_one(G) * 8),
                      osz = carve((size_t)n_groups * 8), ots = carve(tops * 8), otl = carve(tops * 8), oC = carve(cells * 4),
                      otC = carve(at_least_one(G) * 4), otg = carve(tops * 4);

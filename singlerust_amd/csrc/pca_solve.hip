@@ -4,6 +4,7 @@
 // (deflation rounds, plans A / B, the transform), srx_spmm (the raw operators, for kernel-level parity tests) and the PCA model
 // of srx_pca_transform (pca_model.inl).
 #include "pca_internal.hpp"
+#include "hash.hpp"
 
 namespace srx {
 
@@ -145,13 +146,6 @@ static int32_t launch_t(srx_ctx* ctx, const Tiled& c, const YT* Y, double* T /* 
     }
     SRX_HIP(ctx, hipGetLastError());
     return SRX_OK;
-}
-
-static uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
 }
 
 struct Work {                   // k x 64 f64 state, replicated per rank

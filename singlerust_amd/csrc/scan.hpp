@@ -1,4 +1,4 @@
-// scan.hpp — device-side prefix sums, lane-group sums and bitmap ranks, stated once for every kernel that needs one (device code only;
+// scan.hpp — device-side prefix sums, lane-group and workgroup sums and bitmap ranks, stated once for every kernel that needs one (device code only;
 // scan.hip has the device-wide scan_exclusive built on them).
 #pragma once
 
@@ -46,6 +46,48 @@ __device__ __forceinline__ T group_sum(T v) {
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
     return v;
+}
+
+// Sum of v over the threads of a workgroup of WAVES full waves, in every thread: the butterfly of wave_sum, then the wave
+// totals added in ascending wave order, left to right — ((s0 + s1) + s2) + s3 for four waves — so a floating-point sum is
+// the same bits from call to call.  `s_wave` (LDS, WAVES entries): one barrier stands before its write (whoever still
+// reads it from an earlier call is done), one after.  EVERY THREAD of the workgroup calls it.
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_sum(T v, T* s_wave) {
+    v = wave_sum(v);
+    __syncthreads();
+    if (lane_id() == 0) s_wave[threadIdx.x / kWave] = v;
+    __syncthreads();
+    T t = s_wave[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) t += s_wave[w];
+    return t;
+}
+// The same total in THREAD 0 ALONE, zero in every other thread: for a kernel whose thread 0 hands the sum on with an atomic
+// and whose other threads have no use for it (k_umap_epoch: profiles/shared.md).  ONE barrier, between the write of
+// `s_wave` and thread 0's reads: as for block_scan_exclusive, the CALLER owns the barrier between this call's reads and
+// the next writes of `s_wave`.
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_sum_thread0(T v, T* s_wave) {
+    v = wave_sum(v);
+    if (lane_id() == 0) s_wave[threadIdx.x / kWave] = v;
+    __syncthreads();
+    if (threadIdx.x != 0) return 0;
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) v += s_wave[w];
+    return v;
+}
+// the same as block_sum for the maximum
+template <int WAVES, typename T>
+__device__ __forceinline__ T block_max(T v, T* s_wave) {
+    v = wave_max(v);
+    __syncthreads();
+    if (lane_id() == 0) s_wave[threadIdx.x / kWave] = v;
+    __syncthreads();
+    T t = s_wave[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) t = s_wave[w] > t ? s_wave[w] : t;
+    return t;
 }
 
 // ---- bitmap ranks: one bit per key in `bits`, pre[w] = set bits in the words before w; the place of key s among the set

@@ -5,6 +5,7 @@
 
 #include "../../include/srx_synth.h"
 #include "common.hpp"
+#include "hash.hpp"
 
 namespace srx {
 
@@ -15,14 +16,8 @@ struct SynthConst {
     uint32_t thr[SRX_SYNTH_MAX_TYPES];   // cumulative type thresholds on a 32-bit uniform
 };
 
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __host__ __device__ __forceinline__ uint64_t hash2(uint64_t seed, uint64_t i, uint64_t s) {
-    return mix64(mix64(seed ^ mix64(i)) + s);
+    return splitmix64(splitmix64(seed ^ splitmix64(i)) + s);
 }
 constexpr uint64_t kTagType = (1ull << 40) + 0, kTagEmpty = (1ull << 40) + 1, kTagZ1 = (1ull << 40) + 2,
                    kTagZ2 = (1ull << 40) + 3;

@@ -8,7 +8,7 @@
 // floating-point atomic anywhere: the result is the same bits from call to call.
 //
 // Kernels:
-//   k_louvain_check      (srx_umap_csr; symcsr_check.hpp) the validation srx_louvain_csr runs
+//   (srx_umap_csr: k_symcsr_check of symcsr.hip validates the input)
 //   k_umap_wmax          w_max by integer max of the bit patterns (positive doubles order as their bits do)
 //   k_umap_active        the entries with floor(E w_e / w_max) > 0
 //   k_umap_init_random   the hashed start
@@ -23,9 +23,10 @@
 // operation of the definition is rounded once, as numpy rounds it.
 #include "common.hpp"
 #include "graph_handle.hpp"
+#include "hash.hpp"
 #include "pca_internal.hpp"
 #include "scan.hpp"
-#include "symcsr_check.hpp"
+#include "symcsr.hpp"
 
 #include <cmath>
 
@@ -34,54 +35,15 @@
 namespace srx {
 
 constexpr int kUmGroup = SRX_UMAP_GROUP;
-constexpr uint64_t kUmGold = 0x9E3779B97F4A7C15ull;
 constexpr unsigned long long kUmInfBits = 0x7FF0000000000000ull;
 // the small block (8-byte words)
 enum { UM_WMAX = 0, UM_ACTIVE, UM_SAMPLES, UM_SKIPPED, UM_ABSMAX, UM_PCAMAX, UM_WORDS = 8 };
 
-struct UmGraph {
-    const uint64_t* ptr;
-    const uint32_t* ind;
-    const double* w;
-    uint64_t n, nnz;
-};
 struct UmParams {
     double a, b, gamma;
     uint64_t seed;
     int rate;
 };
-
-__host__ __device__ __forceinline__ uint64_t um_mix(uint64_t z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
-// the block's sum of v added to *dst by one integer atomic (every thread of the 256 calls this)
-__device__ __forceinline__ void um_block_add(unsigned long long v, unsigned long long* s_wave, unsigned long long* dst) {
-    v = wave_sum(v);
-    if (lane_id() == 0) s_wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long t = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        if (t) atomicAdd(dst, t);
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ void um_block_max(unsigned long long v, unsigned long long* s_wave, unsigned long long* dst) {
-    v = wave_max(v);
-    if (lane_id() == 0) s_wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = s_wave[0];
-        for (int w = 1; w < 4; ++w) t = s_wave[w] > t ? s_wave[w] : t;
-        if (t) atomicMax(dst, t);
-    }
-    __syncthreads();
-}
 
 __global__ void __launch_bounds__(256) k_umap_wmax(const double* __restrict__ w, uint64_t nnz, unsigned long long* __restrict__ small) {
     __shared__ unsigned long long s_wave[4];
@@ -90,7 +52,8 @@ __global__ void __launch_bounds__(256) k_umap_wmax(const double* __restrict__ w,
         const unsigned long long b = (unsigned long long)__double_as_longlong(w[e]);
         m = b > m ? b : m;
     }
-    um_block_max(m, s_wave, &small[UM_WMAX]);
+    m = block_max<4>(m, s_wave);
+    if (threadIdx.x == 0 && m) atomicMax(&small[UM_WMAX], m);
 }
 
 __global__ void __launch_bounds__(256) k_umap_active(const double* __restrict__ w, uint64_t nnz, double epochs,
@@ -100,14 +63,14 @@ __global__ void __launch_bounds__(256) k_umap_active(const double* __restrict__ 
     unsigned long long c = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (uint64_t)gridDim.x * 256)
         c += floor(epochs * (w[e] / wmax)) > 0.0;
-    um_block_add(c, s_wave, &small[UM_ACTIVE]);
+    c = block_sum<4>(c, s_wave);
+    if (threadIdx.x == 0 && c) atomicAdd(&small[UM_ACTIVE], c);
 }
 
 __global__ void __launch_bounds__(256) k_umap_init_random(double* __restrict__ y, uint64_t count, uint64_t seed) {
     const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= count) return;
-    const uint64_t z = um_mix(seed + kUmGold * (c + 1));
-    y[c] = -10.0 + 20.0 * ((double)(z >> 11) * 0x1p-53);
+    y[c] = -10.0 + 20.0 * unit53(mix64(seed + kGold64 * (c + 1)));
 }
 
 // x: rows x ld row-major; the first dim columns
@@ -119,7 +82,8 @@ __global__ void __launch_bounds__(256) k_umap_absmax(const double* __restrict__ 
         const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(x[(c / dim) * ld + (c % dim)]));
         m = b > m ? b : m;
     }
-    um_block_max(m, s_wave, dst);
+    m = block_max<4>(m, s_wave);
+    if (threadIdx.x == 0 && m) atomicMax(dst, m);
 }
 
 __global__ void __launch_bounds__(256) k_umap_init_pca(const double* __restrict__ scores, uint64_t rows, int dim, uint64_t ld,
@@ -166,7 +130,7 @@ __device__ __forceinline__ void um_term(const double (&yi)[DIM], const double* _
 }
 
 template <int DIM>
-__global__ void __launch_bounds__(256) k_umap_epoch(UmGraph g, const double* __restrict__ yin, double* __restrict__ yout, uint32_t t,
+__global__ void __launch_bounds__(256) k_umap_epoch(SymCsr g, const double* __restrict__ yin, double* __restrict__ yout, uint32_t t,
                                                     double alpha, UmParams p, unsigned long long* __restrict__ small) {
     constexpr int G = kUmGroup;
     __shared__ unsigned long long s_wave[4];
@@ -197,7 +161,7 @@ __global__ void __launch_bounds__(256) k_umap_epoch(UmGraph g, const double* __r
             for (int s = -1; s < p.rate; ++s) {
                 uint64_t o = j;
                 if (s >= 0) {
-                    const uint64_t z = um_mix(p.seed + kUmGold * (first + (uint64_t)s));
+                    const uint64_t z = mix64(p.seed + kGold64 * (first + (uint64_t)s));
                     o = ((z >> 32) * g.n) >> 32;                    // < n < 2^32
                     if (o == row) {
                         ++n_skip;
@@ -219,13 +183,15 @@ __global__ void __launch_bounds__(256) k_umap_epoch(UmGraph g, const double* __r
             for (int c = 0; c < DIM; ++c) yout[row * DIM + c] = yi[c] + acc[c];
         }
     }
-    um_block_add(n_samp, s_wave, &small[UM_SAMPLES]);
-    um_block_add(n_skip, s_wave, &small[UM_SKIPPED]);
+    // the counters: the block's sums in thread 0, one integer atomic each; the barrier frees s_wave for the second sum
+    n_samp = block_sum_thread0<4>(n_samp, s_wave);
+    if (n_samp) atomicAdd(&small[UM_SAMPLES], n_samp);
+    __syncthreads();
+    n_skip = block_sum_thread0<4>(n_skip, s_wave);
+    if (n_skip) atomicAdd(&small[UM_SKIPPED], n_skip);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static bool um_pos(double x) { return x > 0.0 && x <= 1.79769313486231570815e308; }
-static unsigned um_grid(uint64_t items) { return (unsigned)((at_least_one(items) + 255) / 256); }
 static unsigned um_stride_grid(uint64_t items) {              // grid-stride kernels: at most 8 blocks per CU of the 256
     const uint64_t b = (at_least_one(items) + 255) / 256;
     return (unsigned)(b < 2048 ? b : 2048);
@@ -301,7 +267,7 @@ static int32_t um_fit_ab(double spread, double min_dist, double* a_out, double* 
 }
 
 static int32_t um_check_curve(srx_ctx* ctx, double spread, double min_dist) {
-    if (!um_pos(spread)) return fail(ctx, SRX_E_ARG, "umap: spread must be a positive finite number");
+    if (!is_pos_finite(spread)) return fail(ctx, SRX_E_ARG, "umap: spread must be a positive finite number");
     if (!(min_dist >= 0.0 && min_dist <= spread)) return fail(ctx, SRX_E_ARG, "umap: min_dist must lie in 0 .. spread");
     return SRX_OK;
 }
@@ -318,9 +284,9 @@ static int32_t um_opts(srx_ctx* ctx, const srx_umap_opts* in, uint64_t n, UmOpts
         return fail(ctx, SRX_E_ARG, "umap: negative_sample_rate = %d outside 0..32", o.negative_sample_rate);
     SRX_TRY(um_check_curve(ctx, o.spread, o.min_dist));
     if (o.a == 0.0 && o.b == 0.0) SRX_TRY(um_fit_ab(o.spread, o.min_dist, &o.a, &o.b));
-    if (!um_pos(o.a) || !um_pos(o.b)) return fail(ctx, SRX_E_ARG, "umap: a and b must be positive finite numbers (or both 0: fitted)");
-    if (!um_pos(o.gamma)) return fail(ctx, SRX_E_ARG, "umap: gamma must be a positive finite number");
-    if (!um_pos(o.alpha0)) return fail(ctx, SRX_E_ARG, "umap: alpha0 must be a positive finite number");
+    if (!is_pos_finite(o.a) || !is_pos_finite(o.b)) return fail(ctx, SRX_E_ARG, "umap: a and b must be positive finite numbers (or both 0: fitted)");
+    if (!is_pos_finite(o.gamma)) return fail(ctx, SRX_E_ARG, "umap: gamma must be a positive finite number");
+    if (!is_pos_finite(o.alpha0)) return fail(ctx, SRX_E_ARG, "umap: alpha0 must be a positive finite number");
     if (o.n_epochs < 0 || o.n_epochs > SRX_UMAP_MAX_EPOCHS)
         return fail(ctx, SRX_E_ARG, "umap: n_epochs = %d outside 0..%d", o.n_epochs, SRX_UMAP_MAX_EPOCHS);
     if (o.n_epochs == 0) o.n_epochs = n <= 10000 ? 500 : 200;
@@ -351,7 +317,7 @@ static int32_t um_check_start(srx_ctx* ctx, const UmOpts& u, srx_mat* m, const d
 }
 
 // The run (n >= 1).  The result is left in *d_result (one of the two scratch position buffers).
-static int32_t umap_run(srx_ctx* ctx, const UmGraph& g, const UmOpts& u, srx_mat* m, const double* init, double** d_result,
+static int32_t umap_run(srx_ctx* ctx, const SymCsr& g, const UmOpts& u, srx_mat* m, const double* init, double** d_result,
                         srx_umap_info* info) {
     hipStream_t st = ctx->stream;
     const int dim = u.o.n_components;
@@ -363,23 +329,15 @@ static int32_t umap_run(srx_ctx* ctx, const UmGraph& g, const UmOpts& u, srx_mat
     SRX_TRY(scratch(ctx, "umap_small", UM_WORDS * 8, (void**)&d_small));
     if (u.o.init == SRX_UMAP_INIT_GIVEN) SRX_TRY(h2d(ctx, d_y0, init, count * 8));
 
-    struct EvGuard {                     // destroys what was created, whichever return is taken
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EvGuard() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev;
-    SRX_HIP(ctx, hipEventCreate(&ev.a));
-    SRX_HIP(ctx, hipEventCreate(&ev.b));
-    SRX_HIP(ctx, hipEventRecord(ev.a, st));
+    StreamTimer timer(ctx, st);
+    SRX_TRY(timer.start());
     SRX_HIP(ctx, hipMemsetAsync(d_small, 0, UM_WORDS * 8, st));
     if (u.o.init == SRX_UMAP_INIT_RANDOM) {
-        hipLaunchKernelGGL(k_umap_init_random, dim3(um_grid(count)), dim3(256), 0, st, d_y0, count, u.o.seed);
+        hipLaunchKernelGGL(k_umap_init_random, dim3(grid256(count)), dim3(256), 0, st, d_y0, count, u.o.seed);
     } else if (u.o.init == SRX_UMAP_INIT_PCA) {
         const uint64_t ld = (uint64_t)scores_ld((int)m->pca.n_pc);
         hipLaunchKernelGGL(k_umap_absmax, dim3(um_stride_grid(count)), dim3(256), 0, st, m->pca.d_scores, g.n, dim, ld, d_small + UM_PCAMAX);
-        hipLaunchKernelGGL(k_umap_init_pca, dim3(um_grid(count)), dim3(256), 0, st, m->pca.d_scores, g.n, dim, ld, d_small, d_y0);
+        hipLaunchKernelGGL(k_umap_init_pca, dim3(grid256(count)), dim3(256), 0, st, m->pca.d_scores, g.n, dim, ld, d_small, d_y0);
     }
     hipLaunchKernelGGL(k_umap_absmax, dim3(um_stride_grid(count)), dim3(256), 0, st, d_y0, g.n, dim, (uint64_t)dim, d_small + UM_ABSMAX);
     if (g.nnz) {
@@ -399,7 +357,7 @@ static int32_t umap_run(srx_ctx* ctx, const UmGraph& g, const UmOpts& u, srx_mat
     uint32_t ran = 0;
     if (g.nnz) {
         const UmParams p{u.o.a, u.o.b, u.o.gamma, u.o.seed, u.o.negative_sample_rate};
-        const unsigned blocks = um_grid(g.n * (uint64_t)kUmGroup);
+        const unsigned blocks = grid256(g.n * (uint64_t)kUmGroup);
         for (uint32_t t = 1; t <= u.run; ++t) {
             const double alpha = u.o.alpha0 * (1.0 - (double)(t - 1) / (double)u.epochs);
             if (dim == 2) hipLaunchKernelGGL(k_umap_epoch<2>, dim3(blocks), dim3(256), 0, st, g, cur, nxt, t, alpha, p, d_small);
@@ -409,10 +367,8 @@ static int32_t umap_run(srx_ctx* ctx, const UmGraph& g, const UmOpts& u, srx_mat
         ran = u.run;
         SRX_HIP(ctx, hipGetLastError());
     }
-    SRX_HIP(ctx, hipEventRecord(ev.b, st));
+    SRX_TRY(timer.stop(&info->ms));
     SRX_TRY(d2h(ctx, h, d_small, sizeof h));
-    float ms = 0.f;
-    SRX_HIP(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
     info->n = g.n;
     info->nnz = g.nnz;
     info->entries_active = h[UM_ACTIVE];
@@ -421,7 +377,6 @@ static int32_t umap_run(srx_ctx* ctx, const UmGraph& g, const UmOpts& u, srx_mat
     info->negatives = h[UM_SAMPLES] * (uint64_t)u.o.negative_sample_rate - h[UM_SKIPPED];
     info->epochs_run = ran;
     memcpy(&info->w_max, &h[UM_WMAX], 8);
-    info->ms = (double)ms;
     *d_result = cur;
     return SRX_OK;
 }
@@ -455,17 +410,10 @@ int32_t srx_umap(srx_graph* g, srx_mat* m, const srx_umap_opts* opts, const doub
     if (g->n) {
         Range rg("umap");
         double* d_res = nullptr;
-        const UmGraph ug{g->d_cptr, g->d_cind, g->d_cdat, g->n, g->info.nnz_connectivities};
-        SRX_TRY(umap_run(ctx, ug, u, m, init, &d_res, &li));
+        SRX_TRY(umap_run(ctx, connectivities(g), u, m, init, &d_res, &li));
         const size_t bytes = (size_t)g->n * dim * 8;
-        if (g->d_embed && g->embed_dim != dim) {
-            g->embed_valid = false;
-            SRX_HIP(ctx, hipFree(g->d_embed));
-            g->d_embed = nullptr;
-        }
-        if (!g->d_embed) SRX_HIP(ctx, hipMalloc((void**)&g->d_embed, bytes));
         g->embed_valid = false;
-        SRX_HIP(ctx, hipMemcpyAsync(g->d_embed, d_res, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        SRX_TRY(keep_on_handle(ctx, &g->d_embed, g->embed_dim != dim, d_res, bytes));
         if (embedding_out) SRX_TRY(d2h(ctx, embedding_out, g->d_embed, bytes));
     }
     g->embed_dim = dim;
@@ -490,11 +438,10 @@ int32_t srx_umap_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* indic
         return SRX_OK;
     }
     Range rg("umap");
-    SymCsrDev in;
+    SymCsr in;
     SRX_TRY(symcsr_to_device(ctx, "umap", indptr, indices, weights, n, &in));
     double* d_res = nullptr;
-    const UmGraph ug{in.ptr, in.ind, in.w, n, in.nnz};
-    SRX_TRY(umap_run(ctx, ug, u, nullptr, init, &d_res, &li));
+    SRX_TRY(umap_run(ctx, in, u, nullptr, init, &d_res, &li));
     if (embedding_out) SRX_TRY(d2h(ctx, embedding_out, d_res, (size_t)n * u.o.n_components * 8));
     if (info) *info = li;
     return SRX_OK;

@@ -13,11 +13,10 @@ import numpy as np
 
 from ... import _ffi as F
 from ...anndata import IMAnnData
+from ._common import csr_triple, flat_info, graph_of
 
 
-def _info_dict(i: F.DiffmapInfo) -> dict:
-    return {name: (float if name in ("max_residual", "max_ortho", "ms") else int)(getattr(i, name))
-            for name, _ in F.DiffmapInfo._fields_ if name != "reserved_"}
+_info_dict = flat_info          # the name this module had for it
 
 
 def _opts(n_comps, ncv, tol, max_matvecs, seed, density_normalize) -> F.DiffmapOpts:
@@ -30,20 +29,13 @@ def _room(n: int, n_comps: int):
     return np.zeros(m, dtype=np.float64), np.zeros(max(n, 1) * m, dtype=np.float64)
 
 
-def _graph(adata):
-    g = getattr(adata, "_graph", None)
-    if g is None or not g.handle:
-        raise F.SrxError(F.E_ARG, "diffmap: the adata holds no graph; run neighbors(adata, connectivities=True) first")
-    return g
-
-
 def diffmap(adata: IMAnnData, n_comps: int = 15, ncv: int = 0, tol: float = 0.0, max_matvecs: int = 0, seed: int = 0,
             density_normalize: bool = True, key_added: str = "X_diffmap") -> dict:
     """Eigenpairs of the transition operator of the connectivities that ``neighbors(adata, connectivities=True)`` left on the
     device (no host round trip).  Writes ``adata.obsm[key_added]`` (n x n_comps f64, descending eigenvalues),
     ``adata.uns["diffmap_evals"]`` and ``adata.uns["diffmap"]`` (the call's ``srx_diffmap_info``); returns the info.
     ``SrxError`` with code ``E_NOCONV`` when ``max_matvecs`` products did not reach ``tol``."""
-    g = _graph(adata)
+    g = graph_of(adata, "diffmap")
     n = adata.n_obs()
     evals, evecs = _room(n, n_comps)
     info = F.DiffmapInfo()
@@ -52,7 +44,7 @@ def diffmap(adata: IMAnnData, n_comps: int = 15, ncv: int = 0, tol: float = 0.0,
     m = int(info.n_comps)
     adata.obsm[key_added] = evecs[:n * m].reshape(n, m).copy()
     adata.uns["diffmap_evals"] = evals[:m].copy()
-    adata.uns["diffmap"] = _info_dict(info)
+    adata.uns["diffmap"] = flat_info(info)
     return adata.uns["diffmap"]
 
 
@@ -76,7 +68,7 @@ def graph_transitions(graph) -> np.ndarray:
 def dpt(adata: IMAnnData, root: int, cap: float = 0.0, key_added: str = "dpt_pseudotime") -> np.ndarray:
     """Pseudotime from ``root`` out of the eigenpairs the graph handle holds (``srx_dpt``; ``cap=0``: 0.9994).  Writes
     ``adata.obs[key_added]`` and returns it."""
-    g = _graph(adata)
+    g = graph_of(adata, "diffmap")
     out = np.zeros(adata.n_obs(), dtype=np.float64)
     F.check(F.lib().srx_dpt(g.handle, int(root), float(cap), F.ptr(out)), g.ctx.handle)
     adata.obs[key_added] = out
@@ -100,20 +92,7 @@ def diffmap_csr(ctx, matrix, n_comps: int = 15, ncv: int = 0, tol: float = 0.0, 
     """Eigenpairs for any symmetric weighted graph: a scipy sparse matrix or an (indptr, indices, data) CSR triple with
     ascending columns, positive weights, no diagonal and no empty row (``srx_diffmap_csr`` validates on the device as
     ``srx_louvain_csr`` does).  Returns (eigenvalues, eigenvectors n x n_comps f64, info dict)."""
-    if isinstance(matrix, (tuple, list)):
-        indptr, indices, data = matrix
-    else:
-        m = matrix.tocsr()
-        if not m.has_sorted_indices:
-            m = m.sorted_indices()
-        indptr, indices, data = m.indptr, m.indices, m.data
-    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
-    indices = np.ascontiguousarray(indices, dtype=np.uint32)
-    data = np.ascontiguousarray(data, dtype=np.float64)
-    if indptr.ndim != 1 or indptr.size < 1 or indices.shape != data.shape or indices.ndim != 1:
-        raise ValueError("diffmap_csr: indptr (n + 1), indices and data (nnz each) expected")
-    if int(indptr[-1]) != indices.size:
-        raise ValueError("diffmap_csr: indptr[n] does not equal the number of stored entries")
+    indptr, indices, data = csr_triple(matrix, "diffmap_csr")
     n = indptr.size - 1
     evals, evecs = _room(n, n_comps)
     info = F.DiffmapInfo()
@@ -122,4 +101,4 @@ def diffmap_csr(ctx, matrix, n_comps: int = 15, ncv: int = 0, tol: float = 0.0, 
                                     F.ptr(data) if data.size else None, n, C.byref(opts), F.ptr(evals), F.ptr(evecs), C.byref(info)),
             ctx.handle)
     k = int(info.n_comps)
-    return evals[:k].copy(), evecs[:n * k].reshape(n, k).copy(), _info_dict(info)
+    return evals[:k].copy(), evecs[:n * k].reshape(n, k).copy(), flat_info(info)

@@ -8,6 +8,7 @@ import numpy as np
 from ... import _ffi as F
 from ...anndata import FeatureSelection, IMAnnData
 from .. import statistics
+from ._common import OwnedHandle
 
 
 def select_features(adata: IMAnnData, feature_selection) -> np.ndarray:
@@ -79,13 +80,11 @@ def pca_inplace(adata: IMAnnData, n_components=None, center=None, scale=None, n_
 ABSENT = np.iinfo(np.uint64).max          # feature-map entry of a model gene the query does not have
 
 
-class PcaModel:
+class PcaModel(OwnedHandle):
     """A fitted PCA held on the device (``srx_pca_model``): the reference's ``Pca`` after ``fit``, whose
     ``transform`` (src/shared/processing/pca/mod.rs:156-185) projects other cells into the same PC space."""
 
-    def __init__(self, ctx, handle):
-        self.ctx = ctx
-        self._h = handle
+    _free = "srx_pca_model_free"
 
     @classmethod
     def from_result(cls, adata: IMAnnData) -> "PcaModel":
@@ -127,22 +126,6 @@ class PcaModel:
         sel = np.zeros(k.value, dtype=np.uint64)
         rc = F.lib().srx_pca_model_info(self._h, None, None, F.ptr(sel))
         return int(k.value), int(n_pc.value), (sel if rc == F.OK else None)
-
-    @property
-    def handle(self):
-        return self._h
-
-    def free(self) -> None:
-        if self._h:
-            if getattr(self.ctx, "_h", None):
-                F.lib().srx_pca_model_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def feature_map_by_names(model_names, query_names) -> np.ndarray:

@@ -13,6 +13,7 @@ import numpy as np
 
 from ... import _ffi as F
 from ...anndata import IMAnnData
+from ._common import OwnedHandle
 
 _TABLES = {"corrected": F.HARMONY_CORRECTED, "R": F.HARMONY_R, "centroids": F.HARMONY_CENTROIDS,
            "observed": F.HARMONY_OBSERVED, "expected": F.HARMONY_EXPECTED}
@@ -39,16 +40,10 @@ def encode_batches(labels):
     return np.ascontiguousarray(codes, dtype=np.uint32), cats
 
 
-class Harmony:
+class Harmony(OwnedHandle):
     """Owning wrapper of an ``srx_harmony``: the corrected block, R, the centroids, O and E on the device."""
 
-    def __init__(self, ctx, handle):
-        self.ctx = ctx
-        self._h = handle
-
-    @property
-    def handle(self):
-        return self._h
+    _free = "srx_harmony_free"
 
     def info(self) -> dict:
         i = F.HarmonyInfo()
@@ -86,18 +81,6 @@ class Harmony:
         h = C.c_void_p()
         F.check(F.lib().srx_neighbors_harmony(self._h, C.byref(opts), C.byref(info), C.byref(h)), self.ctx.handle)
         return Graph(self.ctx, h), knn_info(info)
-
-    def free(self) -> None:
-        if self._h:
-            if getattr(self.ctx, "_h", None):          # as Graph.free: a closed context took the device memory with it
-                F.lib().srx_harmony_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def harmony_points(ctx, points, batch, n_batches=None, **kw) -> Harmony:

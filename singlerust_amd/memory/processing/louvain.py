@@ -12,6 +12,7 @@ import numpy as np
 
 from ... import _ffi as F
 from ...anndata import IMAnnData
+from ._common import csr_triple, graph_of
 
 
 def _opts(resolution, min_gain, max_levels, max_sweeps) -> F.LouvainOpts:
@@ -30,9 +31,7 @@ def louvain(adata: IMAnnData, resolution: float = 1.0, key_added: str = "louvain
     """Communities of the connectivities that ``neighbors(adata, connectivities=True)`` left on the device (no host round
     trip).  Writes ``adata.obs[key_added]`` (uint32, communities numbered by descending size) and ``adata.uns[key_added]``
     (``params`` and the call's ``srx_louvain_info`` under ``info``); returns the info."""
-    g = getattr(adata, "_graph", None)
-    if g is None or not g.handle:
-        raise F.SrxError(F.E_ARG, "louvain: the adata holds no graph; run neighbors(adata, connectivities=True) first")
+    g = graph_of(adata, "louvain")
     labels = np.zeros(adata.n_obs(), dtype=np.uint32)
     info = F.LouvainInfo()
     opts = _opts(resolution, min_gain, max_levels, max_sweeps)
@@ -55,20 +54,7 @@ def louvain_csr(ctx, matrix, resolution: float = 1.0, min_gain: float = 0.0, max
     """Communities of any symmetric weighted graph: a scipy sparse matrix or an (indptr, indices, data) CSR triple with
     ascending columns, positive weights and no diagonal (``srx_louvain_csr`` validates on the device).  Returns
     (labels uint32, info dict)."""
-    if isinstance(matrix, (tuple, list)):
-        indptr, indices, data = matrix
-    else:
-        m = matrix.tocsr()
-        if not m.has_sorted_indices:
-            m = m.sorted_indices()
-        indptr, indices, data = m.indptr, m.indices, m.data
-    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
-    indices = np.ascontiguousarray(indices, dtype=np.uint32)
-    data = np.ascontiguousarray(data, dtype=np.float64)
-    if indptr.ndim != 1 or indptr.size < 1 or indices.shape != data.shape or indices.ndim != 1:
-        raise ValueError("louvain_csr: indptr (n + 1), indices and data (nnz each) expected")
-    if int(indptr[-1]) != indices.size:
-        raise ValueError("louvain_csr: indptr[n] does not equal the number of stored entries")
+    indptr, indices, data = csr_triple(matrix, "louvain_csr")
     n = indptr.size - 1
     labels = np.zeros(n, dtype=np.uint32)
     info = F.LouvainInfo()

@@ -13,6 +13,7 @@ import numpy as np
 
 from ... import _ffi as F
 from ...anndata import IMAnnData
+from ._common import OwnedHandle, flat_info
 
 TABLES = {"cnt": F.MARKERS_CNT, "sum": F.MARKERS_SUM, "sumsq": F.MARKERS_SUMSQ, "mean": F.MARKERS_MEAN, "var": F.MARKERS_VAR,
           "mean_rest": F.MARKERS_MEAN_REST, "var_rest": F.MARKERS_VAR_REST, "score": F.MARKERS_SCORE, "lfc": F.MARKERS_LFC,
@@ -30,21 +31,15 @@ def _labels(labels, n_obs: int):
     return labels.astype(np.uint32), n_groups
 
 
-class Markers:
+class Markers(OwnedHandle):
     """Owning wrapper of an ``srx_markers`` (the device tables of one ``rank_genes_groups`` call)."""
 
-    def __init__(self, ctx, handle):
-        self.ctx = ctx
-        self._h = handle
-
-    @property
-    def handle(self):
-        return self._h
+    _free = "srx_markers_free"
 
     def info(self) -> dict:
         i = F.MarkersInfo()
         F.check(F.lib().srx_markers_info_get(self._h, C.byref(i)), self.ctx.handle)
-        return {k: getattr(i, k) for k, _ in F.MarkersInfo._fields_ if k != "reserved_"}
+        return flat_info(i)
 
     def top(self):
         """(genes uint32, scores, logfoldchanges), n_groups x n_top each."""
@@ -72,24 +67,12 @@ class Markers:
         """Chunks, staging bytes, segment routes and stage times of the Wilcoxon route (refused on a t-test handle)."""
         i = F.WilcoxonInfo()
         F.check(F.lib().srx_markers_wilcoxon_info_get(self._h, C.byref(i)), self.ctx.handle)
-        return {k: getattr(i, k) for k, _ in F.WilcoxonInfo._fields_}
+        return flat_info(i)
 
     def sizes(self) -> np.ndarray:
         out = np.zeros(self.info()["n_groups"], np.uint64)
         F.check(F.lib().srx_markers_fetch_sizes(self._h, F.ptr(out)), self.ctx.handle)
         return out
-
-    def free(self) -> None:
-        if self._h:
-            if getattr(self.ctx, "_h", None):
-                F.lib().srx_markers_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def group_moments(adata: IMAnnData, labels) -> dict:

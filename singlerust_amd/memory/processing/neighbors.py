@@ -13,6 +13,7 @@ import numpy as np
 
 from ... import _ffi as F
 from ...anndata import IMAnnData
+from ._common import OwnedHandle, flat_info
 
 
 def _info_dict(info: F.KnnInfo) -> dict:
@@ -21,21 +22,15 @@ def _info_dict(info: F.KnnInfo) -> dict:
             "rows_recomputed": int(info.rows_recomputed)}
 
 
-class Graph:
+class Graph(OwnedHandle):
     """Owning wrapper of an ``srx_graph``: distances and connectivities as CSR on the device, with rho and sigma."""
 
-    def __init__(self, ctx, handle):
-        self.ctx = ctx
-        self._h = handle
-
-    @property
-    def handle(self):
-        return self._h
+    _free = "srx_graph_free"
 
     def info(self) -> dict:
         i = F.GraphInfo()
         F.check(F.lib().srx_graph_info_get(self._h, C.byref(i)), self.ctx.handle)
-        return {name: int(getattr(i, name)) for name, _ in F.GraphInfo._fields_ if name != "reserved_"}
+        return flat_info(i)
 
     def fetch(self, which: int):
         """(indptr uint64 n + 1, indices uint32, data f64) of ``F.GRAPH_DISTANCES`` or ``F.GRAPH_CONNECTIVITIES``."""
@@ -64,18 +59,6 @@ class Graph:
             return indptr, indices, data
         n = len(indptr) - 1
         return sp.csr_matrix((data, indices.astype(np.int64 if n >= 2 ** 31 else np.int32), indptr.astype(np.int64)), shape=(n, n))
-
-    def free(self) -> None:
-        if self._h:
-            if getattr(self.ctx, "_h", None):          # as DeviceCsr.free: a closed context took the device memory with it
-                F.lib().srx_graph_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def connectivities_from_knn(ctx, indices, distances) -> Graph:

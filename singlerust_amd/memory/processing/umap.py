@@ -12,6 +12,7 @@ import numpy as np
 
 from ... import _ffi as F
 from ...anndata import IMAnnData
+from ._common import csr_triple, flat_info, graph_of
 
 _INITS = {"pca": F.UMAP_INIT_PCA, "random": F.UMAP_INIT_RANDOM}
 
@@ -21,11 +22,6 @@ def fit_ab(spread: float = 1.0, min_dist: float = 0.5):
     a, b = C.c_double(), C.c_double()
     F.check(F.lib().srx_umap_fit_ab(float(spread), float(min_dist), C.byref(a), C.byref(b)), None)
     return a.value, b.value
-
-
-def _info_dict(i: F.UmapInfo) -> dict:
-    return {name: (float if name in ("a", "b", "w_max", "ms") else int)(getattr(i, name))
-            for name, _ in F.UmapInfo._fields_ if name != "reserved_"}
 
 
 def _start(init, n: int, dim: int):
@@ -53,9 +49,7 @@ def umap(adata: IMAnnData, min_dist: float = 0.5, spread: float = 1.0, n_compone
     n x n_components array.  ``n_epochs=0``: 500 for n <= 10 000, else 200; ``a = b = 0``: fitted from (spread, min_dist).
     Writes ``adata.obsm[key_added]`` (n x n_components f64) and ``adata.uns["umap"]`` (``params`` and the call's
     ``srx_umap_info`` under ``info``); returns the info."""
-    g = getattr(adata, "_graph", None)
-    if g is None or not g.handle:
-        raise F.SrxError(F.E_ARG, "umap: the adata holds no graph; run neighbors(adata, connectivities=True) first")
+    g = graph_of(adata, "umap")
     n, dim = adata.n_obs(), int(n_components)
     code, y0 = _start(init, n, dim)
     emb = np.zeros((n, max(dim, 0)), dtype=np.float64)
@@ -65,7 +59,7 @@ def umap(adata: IMAnnData, min_dist: float = 0.5, spread: float = 1.0, n_compone
                              F.ptr(y0) if y0 is not None and y0.size else None, F.ptr(emb) if emb.size else None, C.byref(info)),
             g.ctx.handle)
     adata.obsm[key_added] = emb
-    d = _info_dict(info)
+    d = flat_info(info)
     adata.uns["umap"] = {"params": {"a": d["a"], "b": d["b"], "min_dist": float(min_dist), "spread": float(spread),
                                     "n_components": dim, "n_epochs": d["n_epochs"], "alpha": float(alpha), "gamma": float(gamma),
                                     "negative_sample_rate": int(negative_sample_rate),
@@ -88,20 +82,7 @@ def umap_csr(ctx, matrix, min_dist: float = 0.5, spread: float = 1.0, n_componen
     """Layout of any symmetric weighted graph: a scipy sparse matrix or an (indptr, indices, data) CSR triple with ascending
     columns, positive weights and no diagonal (``srx_umap_csr`` validates on the device as ``srx_louvain_csr`` does).
     ``init``: "random" or an n x n_components array.  Returns (embedding n x n_components f64, info dict)."""
-    if isinstance(matrix, (tuple, list)):
-        indptr, indices, data = matrix
-    else:
-        m = matrix.tocsr()
-        if not m.has_sorted_indices:
-            m = m.sorted_indices()
-        indptr, indices, data = m.indptr, m.indices, m.data
-    indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
-    indices = np.ascontiguousarray(indices, dtype=np.uint32)
-    data = np.ascontiguousarray(data, dtype=np.float64)
-    if indptr.ndim != 1 or indptr.size < 1 or indices.shape != data.shape or indices.ndim != 1:
-        raise ValueError("umap_csr: indptr (n + 1), indices and data (nnz each) expected")
-    if int(indptr[-1]) != indices.size:
-        raise ValueError("umap_csr: indptr[n] does not equal the number of stored entries")
+    indptr, indices, data = csr_triple(matrix, "umap_csr")
     n, dim = indptr.size - 1, int(n_components)
     code, y0 = _start(init, n, dim)
     emb = np.zeros((n, max(dim, 0)), dtype=np.float64)
@@ -111,4 +92,4 @@ def umap_csr(ctx, matrix, min_dist: float = 0.5, spread: float = 1.0, n_componen
                                  F.ptr(data) if data.size else None, n, C.byref(opts),
                                  F.ptr(y0) if y0 is not None and y0.size else None, F.ptr(emb) if emb.size else None,
                                  C.byref(info)), ctx.handle)
-    return emb, _info_dict(info)
+    return emb, flat_info(info)

@@ -15,7 +15,7 @@ import louvain_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("srx_louvain", "srx_louvain_csr", "srx_graph_labels_fetch")
-KERNELS = ("k_louvain_check", "k_louvain_degree", "k_louvain_scale", "k_louvain_quant", "k_louvain_classify", "k_louvain_biglist",
+KERNELS = ("k_louvain_degree", "k_louvain_scale", "k_louvain_quant", "k_louvain_classify", "k_louvain_biglist",
            "k_louvain_move", "k_louvain_move_big", "k_louvain_apply", "k_louvain_q_in", "k_louvain_q_tot", "k_louvain_flag",
            "k_louvain_oldof", "k_louvain_members", "k_louvain_coarse", "k_louvain_unfix", "k_louvain_compose", "k_louvain_sizes",
            "k_louvain_keys", "k_louvain_bitonic", "k_louvain_rank", "k_louvain_relabel")
@@ -105,6 +105,25 @@ def test_louvain_kernels_do_not_spill_registers(tmp_path):
         seen |= {k for k in KERNELS if re.search(r"\d%s(I|E|\b)" % k, m.group(1))}
     assert seen == set(KERNELS), set(KERNELS) - seen
     assert n_kernels == len(KERNELS) + 2                   # k_louvain_move<32> / <64>, k_louvain_coarse<false> / <true>
+
+
+def test_symcsr_kernels_do_not_spill_registers(tmp_path):
+    """The same for every kernel of symcsr.hip (the input check of srx_louvain_csr, srx_umap_csr and srx_diffmap_csr)."""
+    from singlerust_amd import build
+    assert "symcsr.hip" in build.SOURCES
+    out = str(tmp_path / "symcsr.s")
+    subprocess.check_call([build._hipcc(), *[f for f in build.FLAGS if f != "-Wall"], "-w", "-S", "--cuda-device-only", "-o", out,
+                           os.path.join(ROOT, "singlerust_amd", "csrc", "symcsr.hip")], stderr=subprocess.DEVNULL)
+    meta = open(out).read()
+    names = []
+    for m in re.finditer(r"\.name:\s+(\S*k_symcsr_\S*)\n(.*?)\.wavefront_size", meta, flags=re.S):
+        body = m.group(2)
+        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", body).group(1))
+        sspill = int(re.search(r"\.sgpr_spill_count:\s+(\d+)", body).group(1))
+        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
+        assert spill == 0 and sspill == 0 and scratch == 0, f"{m.group(1)}: {spill} / {sspill} spilled V/SGPRs, {scratch} B of scratch"
+        names.append(m.group(1))
+    assert len(names) == 1 and re.search(r"\dk_symcsr_check(E|\b)", names[0]), names
 
 
 # ---- the restatement -------------------------------------------------------------------------------------------------------

@@ -121,12 +121,17 @@ def test_umap_symbols_are_exported_and_bound():
     assert re.search(r"#define\s+SRX_UMAP_GROUP\s+%d\b" % _ffi.UMAP_GROUP, header)
     assert (_ffi.UMAP_INIT_GIVEN, _ffi.UMAP_INIT_RANDOM, _ffi.UMAP_INIT_PCA) == (0, 1, 2)
     assert re.search(r"SRX_UMAP_INIT_GIVEN = 0, SRX_UMAP_INIT_RANDOM = 1, SRX_UMAP_INIT_PCA = 2", header)
-    # the symmetric-CSR check is stated once, in the header both users include
+    # stated once: the symmetric-CSR check in its own translation unit, behind the header its three users include; no
+    # kernel with internal linkage in a header; one splitmix64 finaliser; no event guard of a file's own
     csrc = os.path.join(ROOT, "singlerust_amd", "csrc")
-    sources = [f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".inl"))]
-    assert [f for f in sources if "void __launch_bounds__(256) k_louvain_check(" in open(os.path.join(csrc, f)).read()] == ["symcsr_check.hpp"]
-    for f in ("louvain.hip", "umap.hip"):
-        assert '#include "symcsr_check.hpp"' in open(os.path.join(csrc, f)).read()
+    text = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".inl", ".h"))}
+    assert [f for f in text if "void __launch_bounds__(256) k_symcsr_check(" in text[f]] == ["symcsr.hip"]
+    assert not [f for f in text if "k_louvain_check" in text[f]]
+    assert not [f for f in text if f.endswith((".hpp", ".h")) and re.search(r"static\s+__global__", text[f])]
+    for f in ("louvain.hip", "umap.hip", "diffmap.hip"):
+        assert '#include "symcsr.hpp"' in text[f]
+    assert [f for f in text if "0xBF58476D1CE4E5B9" in text[f]] == ["hash.hpp"]
+    assert not [f for f in text if "struct EvGuard" in text[f]]
 
 
 @pytest.mark.parametrize("cname,struct,size", [("srx_umap_opts", "UmapOpts", 80), ("srx_umap_info", "UmapInfo", 96)])
