@@ -789,6 +789,8 @@ int32_t srx_umap_fit_ab(double spread, double min_dist, double* a, double* b);
 #ifndef SRX_DIFFMAP_GROUP
 #define SRX_DIFFMAP_GROUP 8      /* lanes that own one row */
 #endif
+#define SRX_DIFFMAP_MAX_COMPS 64    /* the largest n_comps (and the largest m of srx_dpt_from) */
+#define SRX_DIFFMAP_MAX_NCV 129     /* the largest ncv */
 typedef struct srx_diffmap_opts {
     double   tol;                   /* 0 = 1e-10 */
     uint64_t seed;

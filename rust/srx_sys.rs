@@ -13,6 +13,8 @@ pub const SRX_GROUPS_MAX: i32 = 4096;
 pub const SRX_UMAP_GROUP: i32 = 8;
 pub const SRX_UMAP_MAX_EPOCHS: i32 = 1048576;
 pub const SRX_DIFFMAP_GROUP: i32 = 8;
+pub const SRX_DIFFMAP_MAX_COMPS: i32 = 64;
+pub const SRX_DIFFMAP_MAX_NCV: i32 = 129;
 pub const SRX_HARMONY_MAX_CLUSTERS: i32 = 256;
 pub const SRX_HARMONY_MAX_BATCHES: i32 = 256;
 pub const SRX_HARMONY_MAX_ROUNDS: i32 = 64;

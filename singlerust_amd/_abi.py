@@ -1,0 +1,344 @@
+"""singlerust_amd/_abi.py — GENERATED from include/srx.h and include/srx_synth.h by scripts/gen_ctypes_bindings.py;
+do not edit.  The ctypes description of libsrx_hip.so's C ABI: constants, structures, the signature of every function.
+To change it, edit the header and run the generator (and scripts/gen_rust_bindings.py).  singlerust_amd/_ffi.py loads
+the library and applies SIGNATURES."""
+import ctypes as C
+
+P = C.c_void_p
+
+ABI_VERSION = 6
+UNIQUE_ID_BYTES = 128
+KNN_MAX_DIMS = 128
+LOUVAIN_MAX_LEVELS = 32
+GROUPS_MAX = 4096
+UMAP_GROUP = 8
+UMAP_MAX_EPOCHS = 1048576
+DIFFMAP_GROUP = 8
+DIFFMAP_MAX_COMPS = 64
+DIFFMAP_MAX_NCV = 129
+HARMONY_MAX_CLUSTERS = 256
+HARMONY_MAX_BATCHES = 256
+HARMONY_MAX_ROUNDS = 64
+SYNTH_MAX_TYPES = 128
+OK = 0
+E_ARG = -1
+E_DTYPE = -2
+E_FORMAT = -3
+E_BOUNDS = -4
+E_HIP = -5
+E_RCCL = -6
+E_OOM = -7
+E_NAN = -8
+E_SHAPE = -9
+E_NOCONV = -10
+I8 = 0
+I16 = 1
+I32 = 2
+U8 = 3
+U16 = 4
+U32 = 5
+F32 = 6
+F64 = 7
+ROW = 0
+COLUMN = 1
+STORE_AUTO = 0
+STORE_F32 = 1
+STORE_F64 = 2
+FORMAT_CSR = 0
+FORMAT_CSC = 1
+FLEX_NONE = 0
+FLEX_ABSOLUTE = 1
+FLEX_RELATIVE = 2
+SOLVER_AUTO = 0
+SOLVER_GRAM = 1
+SOLVER_SPMM = 2
+GRAPH_DISTANCES = 0
+GRAPH_CONNECTIVITIES = 1
+MARKERS_CNT = 0
+MARKERS_SUM = 1
+MARKERS_SUMSQ = 2
+MARKERS_MEAN = 3
+MARKERS_VAR = 4
+MARKERS_MEAN_REST = 5
+MARKERS_VAR_REST = 6
+MARKERS_SCORE = 7
+MARKERS_LFC = 8
+MARKERS_PCT = 9
+MARKERS_PCT_REST = 10
+MARKERS_RANKSUM2 = 11
+UMAP_INIT_GIVEN = 0
+UMAP_INIT_RANDOM = 1
+UMAP_INIT_PCA = 2
+HARMONY_CORRECTED = 0
+HARMONY_R = 1
+HARMONY_CENTROIDS = 2
+HARMONY_OBSERVED = 3
+HARMONY_EXPECTED = 4
+BACKED_NORMALIZE = 1
+BACKED_LOG1P = 2
+K_NORMALIZE = 0
+K_MOMENTS = 1
+K_COMPACT = 2
+K_SPMM_FWD = 3
+K_SPMM_T = 4
+K_GRAM = 5
+K_DENSE = 6
+K_ROWSUM = 7
+K_ITERATE = 8
+K_SELECT = 9
+K_BUCKET = 10
+K_KNN = 11
+K_GRAPH = 12
+K_COUNT_ = 13
+
+STATUS_NAMES = {0: "SRX_OK", -1: "SRX_E_ARG", -2: "SRX_E_DTYPE", -3: "SRX_E_FORMAT", -4: "SRX_E_BOUNDS",
+                -5: "SRX_E_HIP", -6: "SRX_E_RCCL", -7: "SRX_E_OOM", -8: "SRX_E_NAN", -9: "SRX_E_SHAPE",
+                -10: "SRX_E_NOCONV"}
+
+
+class Csr(C.Structure):      # srx_csr
+    _fields_ = [("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("nnz", C.c_uint64), ("indptr", P), ("indices", P),
+                ("values", P), ("dtype", C.c_int32)]
+
+
+class MatInfo(C.Structure):      # srx_mat_info
+    _fields_ = [("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("nnz", C.c_uint64), ("dtype", C.c_int32),
+                ("store", C.c_int32), ("row_offset", C.c_uint64), ("n_rows_global", C.c_uint64)]
+
+
+class Flex(C.Structure):      # srx_flex
+    _fields_ = [("kind", C.c_int32), ("absolute", C.c_uint32), ("relative", C.c_double)]
+
+
+class PcaOpts(C.Structure):      # srx_pca_opts
+    _fields_ = [("n_components", C.c_int32), ("center", C.c_int32), ("scale", C.c_int32), ("n_threads", C.c_int32),
+                ("block", C.c_int32), ("max_iter", C.c_int32), ("solver", C.c_int32), ("tol", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+class PcaInfo(C.Structure):      # srx_pca_info
+    _fields_ = [("n_cells_global", C.c_uint64), ("k", C.c_uint32), ("n_pc", C.c_uint32), ("block", C.c_uint32),
+                ("n_iter", C.c_uint32), ("residual", C.c_double), ("nnz_selected", C.c_uint64),
+                ("solver", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class KnnOpts(C.Structure):      # srx_knn_opts
+    _fields_ = [("k", C.c_int32), ("n_dims", C.c_int32), ("include_self", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class KnnInfo(C.Structure):      # srx_knn_info
+    _fields_ = [("n_ref", C.c_uint64), ("n_query", C.c_uint64), ("d", C.c_uint32), ("k", C.c_uint32),
+                ("n_candidates", C.c_uint32), ("reserved_", C.c_uint32), ("rows_certified", C.c_uint64),
+                ("rows_recomputed", C.c_uint64)]
+
+
+class GraphInfo(C.Structure):      # srx_graph_info
+    _fields_ = [("n", C.c_uint64), ("k", C.c_uint32), ("reserved_", C.c_uint32), ("nnz_distances", C.c_uint64),
+                ("nnz_connectivities", C.c_uint64), ("n_mutual", C.c_uint64), ("rows_no_root", C.c_uint64),
+                ("rows_clamped", C.c_uint64), ("rows_all_zero", C.c_uint64), ("entries_dropped", C.c_uint64),
+                ("max_row_nnz", C.c_uint64)]
+
+
+class LouvainOpts(C.Structure):      # srx_louvain_opts
+    _fields_ = [("resolution", C.c_double), ("min_gain", C.c_double), ("max_levels", C.c_int32),
+                ("max_sweeps", C.c_int32)]
+
+
+class LouvainInfo(C.Structure):      # srx_louvain_info
+    _fields_ = [("n", C.c_uint64), ("n_communities", C.c_uint64), ("n_levels", C.c_uint32), ("reserved_", C.c_uint32),
+                ("sweeps", C.c_uint64), ("moves", C.c_uint64), ("modularity", C.c_double), ("ms", C.c_double),
+                ("level_communities", C.c_uint64 * 32), ("level_modularity", C.c_double * 32)]
+
+
+class RankGenesOpts(C.Structure):      # srx_rank_genes_opts
+    _fields_ = [("n_top", C.c_int32), ("logged", C.c_int32)]
+
+
+class MarkersInfo(C.Structure):      # srx_markers_info
+    _fields_ = [("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("n_groups", C.c_uint32), ("n_top", C.c_uint32),
+                ("sum_scale_log2", C.c_int32), ("sq_scale_log2", C.c_int32), ("groups_degenerate", C.c_uint32),
+                ("reserved_", C.c_uint32), ("max_abs", C.c_double), ("ms", C.c_double)]
+
+
+class WilcoxonOpts(C.Structure):      # srx_wilcoxon_opts
+    _fields_ = [("n_top", C.c_int32), ("logged", C.c_int32), ("tie_correct", C.c_int32), ("reserved_", C.c_int32),
+                ("scratch_bytes", C.c_uint64)]
+
+
+class WilcoxonInfo(C.Structure):      # srx_wilcoxon_info
+    _fields_ = [("tie_correct", C.c_int32), ("n_chunks", C.c_uint32), ("scratch_bytes", C.c_uint64),
+                ("segment_limit", C.c_uint64), ("segments_short", C.c_uint64), ("segments_long", C.c_uint64),
+                ("ms_stage", C.c_double), ("ms_sort", C.c_double), ("ms_ranks", C.c_double)]
+
+
+class UmapOpts(C.Structure):      # srx_umap_opts
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("min_dist", C.c_double), ("spread", C.c_double),
+                ("gamma", C.c_double), ("alpha0", C.c_double), ("seed", C.c_uint64), ("n_epochs", C.c_int32),
+                ("stop_after", C.c_int32), ("n_components", C.c_int32), ("negative_sample_rate", C.c_int32),
+                ("init", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class UmapInfo(C.Structure):      # srx_umap_info
+    _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("entries_active", C.c_uint64), ("samples", C.c_uint64),
+                ("negatives", C.c_uint64), ("negatives_skipped", C.c_uint64), ("n_epochs", C.c_uint32),
+                ("epochs_run", C.c_uint32), ("dim", C.c_uint32), ("reserved_", C.c_uint32), ("a", C.c_double),
+                ("b", C.c_double), ("w_max", C.c_double), ("ms", C.c_double)]
+
+
+class DiffmapOpts(C.Structure):      # srx_diffmap_opts
+    _fields_ = [("tol", C.c_double), ("seed", C.c_uint64), ("n_comps", C.c_int32), ("ncv", C.c_int32),
+                ("max_matvecs", C.c_int32), ("density_normalize", C.c_int32)]
+
+
+class DiffmapInfo(C.Structure):      # srx_diffmap_info
+    _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("n_comps", C.c_uint32), ("ncv", C.c_uint32),
+                ("matvecs", C.c_uint32), ("restarts", C.c_uint32), ("breakdowns", C.c_uint32),
+                ("reserved_", C.c_uint32), ("max_residual", C.c_double), ("max_ortho", C.c_double), ("ms", C.c_double)]
+
+
+class HarmonyOpts(C.Structure):      # srx_harmony_opts
+    _fields_ = [("theta", C.c_double), ("sigma", C.c_double), ("lambda_", C.c_double),
+                ("epsilon_cluster", C.c_double), ("epsilon_harmony", C.c_double), ("seed", C.c_uint64),
+                ("n_clusters", C.c_int32), ("n_blocks", C.c_int32), ("max_rounds", C.c_int32),
+                ("max_cluster_iters", C.c_int32), ("init_iters", C.c_int32), ("n_dims", C.c_int32)]
+
+
+class HarmonyInfo(C.Structure):      # srx_harmony_info
+    _fields_ = [("n", C.c_uint64), ("d", C.c_uint32), ("n_batches", C.c_uint32), ("n_clusters", C.c_uint32),
+                ("n_blocks", C.c_uint32), ("rounds", C.c_uint32), ("converged", C.c_uint32),
+                ("cluster_iters", C.c_uint64), ("round_iters", C.c_uint32 * 64), ("round_objective", C.c_double * 64),
+                ("ms", C.c_double)]
+
+
+class PipelineResult(C.Structure):      # srx_pipeline_result
+    _fields_ = [("pca", PcaInfo), ("ms_normalize", C.c_double), ("ms_moments", C.c_double), ("ms_select", C.c_double),
+                ("ms_compact", C.c_double), ("ms_pca", C.c_double)]
+
+
+class SynthParams(C.Structure):      # srx_synth_params
+    _fields_ = [("seed", C.c_uint64), ("n_rows_global", C.c_uint64), ("n_cols", C.c_uint64), ("density", C.c_double),
+                ("lib_sigma", C.c_double), ("type_decay", C.c_double), ("n_types", C.c_uint32),
+                ("marker_genes", C.c_uint32), ("expr_boost", C.c_uint32), ("value_boost", C.c_uint32),
+                ("skew", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, P, C.POINTER(C.c_double), C.c_uint64)      # srx_host_allreduce_fn
+
+SIGNATURES = {
+    # name: (restype, argtypes)
+    "srx_abi_version": (C.c_int32, []),
+    "srx_device_count": (C.c_int32, [P]),
+    "srx_ctx_create": (C.c_int32, [C.c_int32, C.POINTER(P)]),
+    "srx_ctx_destroy": (None, [P]),
+    "srx_ctx_synchronize": (C.c_int32, [P]),
+    "srx_last_error": (C.c_char_p, [P]),
+    "srx_comm_unique_id": (C.c_int32, [P]),
+    "srx_comm_init": (C.c_int32, [P, C.c_int32, C.c_int32, P]),
+    "srx_comm_init_host": (C.c_int32, [P, C.c_int32, C.c_int32, P, P]),
+    "srx_comm_destroy": (C.c_int32, [P]),
+    "srx_comm_info": (C.c_int32, [P, P, P, P, P]),
+    "srx_comm_overlap_info": (C.c_int32, [P, P, P]),
+    "srx_gram_mode_info": (C.c_int32, [P, P]),
+    "srx_gram_exchange_ranges": (C.c_int32, [C.c_uint64, P]),
+    "srx_partition_rows": (C.c_int32, [P, C.c_uint64, C.c_int32, P]),
+    "srx_matrix_upload": (C.c_int32, [P, C.POINTER(Csr), C.c_int32, C.POINTER(P)]),
+    "srx_matrix_upload_csc": (C.c_int32, [P, C.POINTER(Csr), C.c_int32, C.POINTER(P)]),
+    "srx_matrix_format": (C.c_int32, [P, P]),
+    "srx_matrix_to_csr": (C.c_int32, [P, C.POINTER(P)]),
+    "srx_matrix_to_csc": (C.c_int32, [P, C.POINTER(P)]),
+    "srx_matrix_alloc": (C.c_int32, [P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(P)]),
+    "srx_matrix_device_ptrs": (C.c_int32, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
+    "srx_matrix_info": (C.c_int32, [P, C.POINTER(MatInfo)]),
+    "srx_matrix_set_shard": (C.c_int32, [P, C.c_uint64]),
+    "srx_matrix_download_values": (C.c_int32, [P, P, C.c_int32]),
+    "srx_matrix_prepare": (C.c_int32, [P]),
+    "srx_matrix_reserve_results": (C.c_int32, [P, C.c_uint64, C.c_int32]),
+    "srx_matrix_clone": (C.c_int32, [P, C.POINTER(P)]),
+    "srx_matrix_copy_values": (C.c_int32, [P, P]),
+    "srx_matrix_free": (None, [P]),
+    "srx_compute_number": (C.c_int32, [P, C.c_int32, P]),
+    "srx_compute_sum": (C.c_int32, [P, C.c_int32, P]),
+    "srx_compute_variance": (C.c_int32, [P, C.c_int32, P]),
+    "srx_compute_std_dev": (C.c_int32, [P, C.c_int32, P]),
+    "srx_compute_min_max": (C.c_int32, [P, C.c_int32, P, P]),
+    "srx_compute_qc_variables": (C.c_int32, [P, P, P, P, P, P, P, P, P]),
+    "srx_gene_moments": (C.c_int32, [P, P, P, P]),
+    "srx_filter_cells": (C.c_int32, [P, Flex, Flex, C.POINTER(P), P]),
+    "srx_filter_genes": (C.c_int32, [P, Flex, Flex, C.POINTER(P), P]),
+    "srx_subset": (C.c_int32, [P, P, P, C.POINTER(P)]),
+    "srx_matrix_download_pattern": (C.c_int32, [P, P, P]),
+    "srx_normalize_total_inplace": (C.c_int32, [P, C.c_double, C.c_int32]),
+    "srx_log1p_inplace": (C.c_int32, [P]),
+    "srx_normalize_log1p_inplace": (C.c_int32, [P, C.c_double, P]),
+    "srx_select_hvg": (C.c_int32, [P, C.c_uint64, P, P]),
+    "srx_pca": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PcaOpts), P, P, P, P, P, C.POINTER(PcaInfo)]),
+    "srx_pca_loadings": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint64, C.c_uint64, P]),
+    "srx_pca_model_from_result": (C.c_int32, [P, C.POINTER(P)]),
+    "srx_pca_model_create": (C.c_int32, [P, C.c_uint64, C.c_uint64, P, P, P, P, C.c_int32, C.c_int32, C.POINTER(P)]),
+    "srx_pca_model_info": (C.c_int32, [P, P, P, P]),
+    "srx_pca_model_free": (None, [P]),
+    "srx_pca_transform": (C.c_int32, [P, P, P, C.c_double, C.c_int32, P]),
+    "srx_knn_result": (C.c_int32, [P, C.POINTER(KnnOpts), P, P, C.POINTER(KnnInfo)]),
+    "srx_knn_points": (C.c_int32, [P, P, C.c_uint64, P, C.c_uint64, C.c_uint64, C.POINTER(KnnOpts), P, P,
+                                   C.POINTER(KnnInfo)]),
+    "srx_neighbors_result": (C.c_int32, [P, C.POINTER(KnnOpts), C.POINTER(KnnInfo), C.POINTER(P)]),
+    "srx_neighbors_from_knn": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.POINTER(P)]),
+    "srx_graph_info_get": (C.c_int32, [P, C.POINTER(GraphInfo)]),
+    "srx_graph_fetch": (C.c_int32, [P, C.c_int32, P, P, P]),
+    "srx_graph_fetch_scales": (C.c_int32, [P, P, P]),
+    "srx_graph_free": (None, [P]),
+    "srx_louvain": (C.c_int32, [P, C.POINTER(LouvainOpts), P, C.POINTER(LouvainInfo)]),
+    "srx_louvain_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(LouvainOpts), P, C.POINTER(LouvainInfo)]),
+    "srx_graph_labels_fetch": (C.c_int32, [P, P]),
+    "srx_group_moments": (C.c_int32, [P, P, C.c_uint32, P, P, P, P]),
+    "srx_rank_genes_groups": (C.c_int32, [P, P, C.c_uint32, C.POINTER(RankGenesOpts), C.POINTER(P)]),
+    "srx_rank_genes_groups_graph": (C.c_int32, [P, P, C.POINTER(RankGenesOpts), C.POINTER(P)]),
+    "srx_markers_info_get": (C.c_int32, [P, C.POINTER(MarkersInfo)]),
+    "srx_markers_fetch_top": (C.c_int32, [P, P, P, P]),
+    "srx_markers_fetch_table": (C.c_int32, [P, C.c_int32, P]),
+    "srx_markers_fetch_sizes": (C.c_int32, [P, P]),
+    "srx_markers_free": (None, [P]),
+    "srx_rank_genes_wilcoxon": (C.c_int32, [P, P, C.c_uint32, C.POINTER(WilcoxonOpts), C.POINTER(P)]),
+    "srx_rank_genes_wilcoxon_graph": (C.c_int32, [P, P, C.POINTER(WilcoxonOpts), C.POINTER(P)]),
+    "srx_markers_fetch_ties": (C.c_int32, [P, P]),
+    "srx_markers_wilcoxon_info_get": (C.c_int32, [P, C.POINTER(WilcoxonInfo)]),
+    "srx_umap": (C.c_int32, [P, P, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
+    "srx_umap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
+    "srx_graph_embedding_fetch": (C.c_int32, [P, P, P]),
+    "srx_umap_fit_ab": (C.c_int32, [C.c_double, C.c_double, P, P]),
+    "srx_diffmap": (C.c_int32, [P, C.POINTER(DiffmapOpts), P, P, C.POINTER(DiffmapInfo)]),
+    "srx_diffmap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(DiffmapOpts), P, P, C.POINTER(DiffmapInfo)]),
+    "srx_graph_diffmap_fetch": (C.c_int32, [P, P, P, P]),
+    "srx_graph_transitions_fetch": (C.c_int32, [P, P]),
+    "srx_dpt": (C.c_int32, [P, C.c_uint64, C.c_double, P]),
+    "srx_dpt_from": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_double, P]),
+    "srx_harmony_result": (C.c_int32, [P, P, C.c_uint32, C.POINTER(HarmonyOpts), C.POINTER(P), C.POINTER(HarmonyInfo)]),
+    "srx_harmony_points": (C.c_int32, [P, P, C.c_uint64, C.c_uint64, P, C.c_uint32, C.POINTER(HarmonyOpts),
+                                       C.POINTER(P), C.POINTER(HarmonyInfo)]),
+    "srx_harmony_fetch": (C.c_int32, [P, C.c_int32, P]),
+    "srx_harmony_info_get": (C.c_int32, [P, C.POINTER(HarmonyInfo)]),
+    "srx_knn_harmony": (C.c_int32, [P, C.POINTER(KnnOpts), P, P, C.POINTER(KnnInfo)]),
+    "srx_neighbors_harmony": (C.c_int32, [P, C.POINTER(KnnOpts), C.POINTER(KnnInfo), C.POINTER(P)]),
+    "srx_harmony_free": (None, [P]),
+    "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
+    "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
+    "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),
+    "srx_backed_create": (C.c_int32, [P, C.c_uint64, C.c_int32, C.POINTER(P)]),
+    "srx_backed_destroy": (None, [P]),
+    "srx_backed_stats_tile": (C.c_int32, [P, C.POINTER(Csr), C.c_double, C.c_int32, P, P]),
+    "srx_backed_moments": (C.c_int32, [P, P, P, P, P]),
+    "srx_backed_select": (C.c_int32, [P, C.c_uint64, P, C.c_uint64, C.POINTER(PcaOpts), P, P]),
+    "srx_backed_gram_tile": (C.c_int32, [P, C.POINTER(Csr), C.c_double, C.c_int32]),
+    "srx_backed_solve": (C.c_int32, [P, C.POINTER(PcaInfo)]),
+    "srx_backed_fetch": (C.c_int32, [P, P, P, P, P, P, P]),
+    "srx_prof_enable": (C.c_int32, [P, C.c_uint32]),
+    "srx_prof_reset": (C.c_int32, [P]),
+    "srx_prof_get": (C.c_int32, [P, C.c_int32, P, P, P]),
+    "srx_prof_get_aux": (C.c_int32, [P, C.c_int32, P]),
+    "srx_synth_defaults": (None, [C.POINTER(SynthParams), C.c_uint64, C.c_uint64, C.c_uint64, C.c_double]),
+    "srx_synth_indptr": (C.c_int32, [C.POINTER(SynthParams), C.c_uint64, C.c_uint64, P]),
+    "srx_synth_fill_host": (C.c_int32, [C.POINTER(SynthParams), C.c_uint64, C.c_uint64, P, P, P]),
+    "srx_synth_generate": (C.c_int32, [P, C.POINTER(SynthParams), C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
+                                       C.POINTER(P)]),
+}
+EXPORTS = tuple(SIGNATURES)

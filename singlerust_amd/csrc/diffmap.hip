@@ -53,7 +53,7 @@ namespace srx {
 
 constexpr int kDmGroup = SRX_DIFFMAP_GROUP;
 constexpr int kDmRows = 1024;                // rows a workgroup of the tall-skinny kernels owns
-constexpr int kDmMaxNcv = 129, kDmMaxComps = 64;
+constexpr int kDmMaxNcv = SRX_DIFFMAP_MAX_NCV, kDmMaxComps = SRX_DIFFMAP_MAX_COMPS;
 constexpr int kDmMaxCols = kDmMaxNcv + kDmMaxComps + 1;
 constexpr double kDmBreak = 0x1p-40;         // beta at or below this is a breakdown (|T| = 1)
 constexpr unsigned long long kDmInfBits = 0x7FF0000000000000ull;

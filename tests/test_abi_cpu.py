@@ -20,6 +20,24 @@ def declared_functions():
     return sorted(set(names))
 
 
+def load_script(name):
+    """A module of scripts/ (the header parser, the two binding generators), loaded by path."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "scripts", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[name] = mod                    # @dataclass looks its module up there
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.fixture(scope="module")
+def header():
+    """Both headers as scripts/srx_header.py parses them: what the generated bindings are rendered from."""
+    h = load_script("srx_header")
+    return h.parse(h.SRX_H, h.SRX_SYNTH_H)
+
+
 @pytest.fixture(scope="module")
 def lib():
     from singlerust_amd import build, _ffi
@@ -37,14 +55,31 @@ def test_library_exports_every_declared_symbol(lib):
     assert set(decl) == set(_ffi.EXPORTS)
 
 
+def test_ctypes_bindings_follow_the_headers():
+    """singlerust_amd/_abi.py is generated from include/srx.h and include/srx_synth.h: the committed file must be what the
+    generator produces now."""
+    text = open(os.path.join(ROOT, "singlerust_amd", "_abi.py")).read()
+    assert text == load_script("gen_ctypes_bindings").render(), "singlerust_amd/_abi.py is stale: run python scripts/gen_ctypes_bindings.py"
+
+
+def test_signatures_cover_the_headers_with_their_arity(lib, header):
+    """SIGNATURES names exactly the functions the two headers declare (found by the parser and by the plain search of this
+    file alike) and the library exports, each with as many argtypes as the prototype has parameters."""
+    from singlerust_amd import _abi, _ffi
+    assert set(_abi.SIGNATURES) == set(declared_functions()) == {name for name, _, _ in header.funcs}
+    assert _ffi.EXPORTS == tuple(_abi.SIGNATURES) and len(_abi.SIGNATURES) >= 111
+    for name, ret, params in header.funcs:
+        assert hasattr(lib, name), f"{name} declared in include/*.h but not exported"
+        restype, argtypes = _abi.SIGNATURES[name]
+        assert len(argtypes) == len(params), name
+        assert (restype is None) == (ret == "void"), name
+        assert getattr(lib, name).argtypes == argtypes, name           # _ffi.lib() applied them
+
+
 def test_rust_bindings_follow_the_header():
     """rust/srx_sys.rs (the `extern "C"` module of INTEGRATION.md) is generated from include/srx.h: the committed
     file must be what the generator produces now, and declare every function of that header with its arity."""
-    import importlib.util
-    import re
-    spec = importlib.util.spec_from_file_location("gen_rust_bindings", os.path.join(ROOT, "scripts", "gen_rust_bindings.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
+    gen = load_script("gen_rust_bindings")
     text = open(os.path.join(ROOT, "rust", "srx_sys.rs")).read()
     assert text == gen.render(), "rust/srx_sys.rs is stale: run python scripts/gen_rust_bindings.py"
     header = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "srx.h")).read(), flags=re.S)
@@ -71,25 +106,41 @@ def test_rust_bindings_follow_the_header():
 
 
 def test_abi_version(lib):
-    assert lib.srx_abi_version() == 6
+    from singlerust_amd import _abi
+    assert lib.srx_abi_version() == _abi.ABI_VERSION == 6
 
 
-def test_struct_layouts_match_header():
-    """sizeof() of the ctypes mirrors equals what the C compiler lays out (checked with gcc)."""
-    import subprocess, tempfile
-    from singlerust_amd import _ffi
-    prog = r'''
-#include <stdio.h>
-#include "srx.h"
-#include "srx_synth.h"
-int main(void){printf("%zu %zu %zu %zu %zu %zu\n", sizeof(srx_csr), sizeof(srx_mat_info), sizeof(srx_pca_opts),
- sizeof(srx_pca_info), sizeof(srx_pipeline_result), sizeof(srx_synth_params)); return 0;}'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "t.c"), "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
-        sizes = [int(x) for x in subprocess.check_output([os.path.join(d, "t")]).split()]
-    mirrors = [_ffi.Csr, _ffi.MatInfo, _ffi.PcaOpts, _ffi.PcaInfo, _ffi.PipelineResult, _ffi.SynthParams]
-    assert sizes == [C.sizeof(m) for m in mirrors]
+def test_struct_layouts_match_header(header, tmp_path):
+    """Every struct of the two headers against its ctypes mirror, as the C compiler (gcc) lays it out: sizeof the struct, and
+    offsetof / sizeof of every field.  The C program is written from the parse, so a struct added to a header is covered."""
+    import keyword
+    import subprocess
+    from singlerust_amd import _abi
+    assert len(header.structs) >= 22
+    prog = ['#include <stddef.h>', '#include <stdio.h>', '#include "srx.h"', '#include "srx_synth.h"', 'int main(void) {']
+    for sname, fields in header.structs.items():
+        prog.append(f'    printf("{sname} %zu\\n", sizeof({sname}));')
+        for _, fname, _ in fields:
+            prog.append(f'    printf("{sname}.{fname} %zu %zu\\n", offsetof({sname}, {fname}), sizeof((({sname}*)0)->{fname}));')
+    prog += ['    return 0;', '}', '']
+    (tmp_path / "layout.c").write_text("\n".join(prog))
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")])
+    c_layout = {}
+    for line in subprocess.check_output([str(tmp_path / "layout")], text=True).splitlines():
+        key, *nums = line.split()
+        c_layout[key] = tuple(int(x) for x in nums)
+    checked = 0
+    for sname, fields in header.structs.items():
+        cls = getattr(_abi, "".join(p.capitalize() for p in sname[len("srx_"):].split("_")))
+        assert issubclass(cls, C.Structure)
+        assert c_layout[sname] == (C.sizeof(cls),), sname
+        names = [fname + "_" if keyword.iskeyword(fname) else fname for _, fname, _ in fields]
+        assert [f[0] for f in cls._fields_] == names, sname
+        for (_, fname, _), pyname in zip(fields, names):
+            d = getattr(cls, pyname)
+            assert c_layout[f"{sname}.{fname}"] == (d.offset, d.size), f"{sname}.{fname}"
+        checked += 1
+    assert checked >= 22
 
 
 def test_partition_rows_is_nnz_balanced(lib):
