@@ -734,6 +734,122 @@ int32_t srx_graph_embedding_fetch(srx_graph* g, double* out, uint32_t* dim_out);
 /* Host only.  SRX_E_ARG: spread or min_dist not finite, spread <= 0, min_dist < 0 or > spread, a null output. */
 int32_t srx_umap_fit_ab(double spread, double min_dist, double* a, double* b);
 
+/* ---- t-SNE in 2 dimensions: perplexity affinities of a k-NN list and a Barnes-Hut layout; what sc.tl.tsne gives
+ * obsm["X_tsne"] -------------------------------------------------------------------------------------------------------------
+ * The reference's commented-out tsne / tsne_inplace (dim_red/mod.rs:159-227: linfa's Barnes-Hut t-SNE on top of a PCA).  The
+ * method is RESTATED here so that the result is bit-identical from call to call; this definition is what is tested.  P is
+ * compared with scikit-learn's binary search, and the quality of a layout (KL, label purity) with scikit-learn's exact t-SNE
+ * (tests/golden/make_tsne_golden.py); the layouts themselves are NOT compared with scikit-learn point for point.
+ * All arithmetic is IEEE f64, every operation rounded once: no FMA contraction, no -ffast-math, no floating-point atomics.
+ * exp and log are the device library's (ocml).  mix() and G = 0x9E3779B97F4A7C15 are those of the UMAP section.
+ *
+ * 1. Affinities.  Input as for srx_neighbors_from_knn: every row i names k distinct neighbours j != i with finite distances
+ *   d_ij >= 0; 2 <= k <= SRX_TSNE_MAX_K.  Perplexity u with 1 < u < k; u == 0 means min(30, k / 3) (refused if that is <= 1).
+ *   Per row: D_j = d_ij * d_ij, m_i = min_j D_j, c_i = the number of neighbours with D_j == m_i.  H_i(beta) is the entropy, in
+ *   nats, of p_j = exp(-beta (D_j - m_i)) / sum_l exp(-beta (D_l - m_i)), evaluated as log S + beta * (sum_j x_j e_j) / S with
+ *   x_j = D_j - m_i, e_j = exp(-(beta * x_j)), S = sum_j e_j; it falls from log k at beta = 0 to log c_i.  If c_i >= u there is
+ *   no root (info.rows_no_root): p_j = 1 / c_i on the tied neighbours, 0 elsewhere, beta_i = +inf.  Otherwise beta_i is the
+ *   root of H_i(beta) = log u, solved to |H_i - log u| <= 1e-9: a bracket by factors of two from beta = 1, then bisection.  The
+ *   row is put in column order first and every sum over it is a butterfly over the 64 lanes, so p does not depend on the
+ *   order within an input row.  Directed entries that are exactly 0.0 stay in the pattern.
+ * 2. Joint P.  For every pair joined in either direction P_ij = (p_{j|i} + p_{i|j}) / (2 n) (one addition, one division by
+ *   the f64 2 n; an absent direction counts as 0).  CSR: u64 indptr, u32 indices strictly ascending in a row, f64 data, no
+ *   diagonal; P_ij and P_ji are the same bits; entries equal to 0.0 are dropped and counted in info.entries_dropped (both
+ *   entries of a pair count); info.n_mutual counts the pairs joined in both directions.  Bit-identical from call to call.
+ * 3. Repulsion by a uniform pyramid, for positions Y (n x 2).  lo_c = min_i y_ic; ext = max_c (max_i y_ic - lo_c);
+ *   side = ext * (1 + 2^-20), or 1 when ext == 0.  U_ic = min(floor(((y_ic - lo_c) / side) * 2^32), 2^32 - 1) as a u32.  Level l
+ *   (1 <= l <= L) has 2^l x 2^l cells of side s_l = side * 2^-l; point i lies in cell (U_i0 >> (32 - l), U_i1 >> (32 - l)).  A cell
+ *   holds the count m and the u64 integer sums SX, SY of the U of its points (order-free, exact); its centre of mass is
+ *   com_c = lo_c + (f64(S_c) / f64(m)) * (side * 2^-32).  levels == 0 means L = the smallest integer with 4^(L+1) >= n, clamped
+ *   to 1 .. SRX_TSNE_MAX_LEVELS.
+ *   Walk, per point i, from the four level-1 cells.  An empty cell is skipped.  Otherwise d = y_i - com, d2 = d_0 d_0 + d_1 d_1:
+ *     if s_l * s_l < (theta * theta) * d2 the cell is ACCEPTED (cells_accepted): q = 1 / (1 + d2), rep_i += (m * q * q) * d,
+ *       z_i += m * q;
+ *     otherwise, if l == L, it is OPENED EXACTLY (cells_exact): for each member j != i in ascending j, with
+ *       q = 1 / (1 + |y_i - y_j|^2): rep_i += (q * q) * (y_i - y_j), z_i += q, and pairs_exact += 1;
+ *     otherwise its four children are visited.
+ *   theta = 0 never accepts a cell: the exact O(n^2) sum.  The terms of a point may be summed in any order fixed by (n, the
+ *   cell of every point) alone: here in the order of the walk, children by ascending code 2 * ybit + xbit.  Z = sum_i z_i in an
+ *   order fixed in the same way (the points ordered by finest cell, then index; workgroups of 256 such points summed by
+ *   butterflies, the workgroup sums by one workgroup).
+ * 4. Iteration t = 1..T, everything read from Y^{t-1}.  alpha = exaggeration and mu = 0.5 while t <= exaggeration_iters;
+ *   after that alpha = 1 and mu = 0.8.  attr_i = sum over row i of P of (P_ij * q_ij) * (y_i - y_j), q_ij = 1 / (1 + |y_i - y_j|^2)
+ *   (SRX_TSNE_GROUP lanes own a vertex: lane s sums the entries lo + s, lo + s + SRX_TSNE_GROUP, ... in that order, and the
+ *   lanes' sums meet in a butterfly).  grad = 4 * (alpha * attr - rep / Z) per coordinate.  gain = gain + 0.2 if
+ *   (grad > 0) != (vel > 0), else gain * 0.8; then gain = max(gain, 0.01); gain starts at 1 and vel at 0.
+ *   vel = mu * vel - (eta * gain) * grad; y = y + vel.  learning_rate == 0 means eta = max(n / 48, 50) (scikit-learn's "auto"
+ *   for this form of the gradient).  n_iter == 0 means T = 1000; stop_after = s (0 = T) runs only iterations 1..s.  After
+ *   the last iteration one more pass over that Y gives info.Z and info.kl = sum_e P_e * ((log P_e - log q_e) + log Z), a
+ *   row's entries summed as attr is, the rows as Z is (in index order).
+ * 5. Starts.  SRX_TSNE_INIT_PCA (the default): the first two columns of the scores the last fit left on the matrix handle
+ *   times s = 1e-4 / max |score| over those columns (s one f64 division).  SRX_TSNE_INIT_RANDOM: coordinate c = 2 i + j is
+ *   (((mix(seed + G * (c + 1)) >> 11) * 2^-53) - 0.5) * 2e-4.  SRX_TSNE_INIT_GIVEN: `init`, n x 2 f64, finite.
+ * Defaults (NULL opts, and 0 in a field that says so): theta 0.5 (taken literally in a given opts), exaggeration 12 (0),
+ *   learning_rate auto (0), seed 0, n_iter 1000 (0), exaggeration_iters 250 (taken literally in a given opts: 0 = none), levels
+ *   auto (0), the PCA start.
+ * Refused with SRX_E_ARG and a message, nothing written (*out is left untouched): perplexity outside (1, k) or NaN; k outside
+ *   2 .. SRX_TSNE_MAX_K; theta < 0, NaN or Inf; levels outside 0 .. SRX_TSNE_MAX_LEVELS; exaggeration or learning_rate
+ *   negative, NaN or Inf; n_iter or exaggeration_iters negative or above SRX_TSNE_MAX_ITERS, stop_after < 0 or > T;
+ *   an unknown start, a NaN or Inf start, SRX_TSNE_INIT_GIVEN without init; the PCA start without a usable result of >= 2
+ *   components, with another n, or on another context; everything srx_neighbors_from_knn refuses about a list; a context
+ *   with more than one rank; a null handle.  n == 0 gives an empty result; n == 1 an empty P, and the start is returned.
+ * Out of scope: 3-D output and FFT-interpolated repulsion; an adaptive tree (dense clumps cost pairs_exact); more than 64
+ *   neighbours (scanpy's default perplexity 30 would take 90; what the cut at 64 costs has not been measured); transforming
+ *   new points; a Harmony entry point (go through srx_neighbors_harmony and srx_tsne_affinities_graph). */
+#define SRX_TSNE_MAX_K 64
+#define SRX_TSNE_MAX_LEVELS 12
+#define SRX_TSNE_GROUP 8          /* lanes that own one vertex in the attraction */
+#define SRX_TSNE_MAX_ITERS 1048576
+enum { SRX_TSNE_INIT_GIVEN = 0, SRX_TSNE_INIT_RANDOM = 1, SRX_TSNE_INIT_PCA = 2 };
+typedef struct srx_tsne srx_tsne;         /* owns P, beta and the last embedding on the device; free it before its context */
+typedef struct srx_tsne_info {
+    uint64_t n, nnz, n_mutual, rows_no_root, entries_dropped;
+    uint32_t k, reserved_;
+    double   perplexity;
+} srx_tsne_info;
+typedef struct srx_tsne_opts {
+    double   theta;                 /* taken literally: 0 is the exact sum */
+    double   exaggeration;          /* 0 = 12 */
+    double   learning_rate;         /* 0 = max(n / 48, 50) */
+    uint64_t seed;
+    int32_t  n_iter;                /* 0 = 1000 */
+    int32_t  exaggeration_iters;    /* taken literally: 0 = none (NULL opts: 250) */
+    int32_t  stop_after;            /* 0 = n_iter */
+    int32_t  levels;                /* 0 = from n */
+    int32_t  init, reserved_;
+} srx_tsne_opts;
+typedef struct srx_tsne_run_info {
+    uint64_t n, nnz;
+    uint32_t n_iter, iters_run, levels, reserved_;
+    double   eta, Z, kl, side;      /* Z, kl and side: of the pass over the final Y */
+    uint64_t cells_accepted, cells_exact, pairs_exact;   /* the walk of the last iteration */
+    double   ms;                    /* hipEvent time of the device work */
+} srx_tsne_run_info;
+typedef struct srx_tsne_force_info {
+    uint32_t levels, reserved_;
+    double   side, lo[2];
+    uint64_t cells_accepted, cells_exact, pairs_exact;
+} srx_tsne_force_info;
+/* The affinities of a caller's list (indices n x k u32, distances n x k f64, host).  *out is written on success only. */
+int32_t srx_tsne_affinities_knn(srx_ctx* ctx, const uint32_t* indices, const double* distances, uint64_t n, uint32_t k,
+                                double perplexity, srx_tsne** out);
+/* The same from the distances D a graph handle holds, read where they lie; the graph is left untouched. */
+int32_t srx_tsne_affinities_graph(srx_graph* g, double perplexity, srx_tsne** out);
+int32_t srx_tsne_info_get(const srx_tsne* h, srx_tsne_info* info);
+/* P as CSR (indptr n + 1, indices and data nnz) and beta (n); any pointer may be NULL. */
+int32_t srx_tsne_fetch_affinities(srx_tsne* h, uint64_t* indptr, uint32_t* indices, double* data, double* beta);
+/* A diagnostic: sections 3 and 4's attr (n x 2), rep (n x 2) and z (n) at the given Y (n x 2 f64, host, finite), once, with
+ * the kernels the run uses.  levels as in the options; any output may be NULL. */
+int32_t srx_tsne_forces(srx_tsne* h, const double* Y, double theta, int32_t levels, double* attr_out, double* rep_out,
+                        double* z_out, srx_tsne_force_info* info);
+/* The layout.  m: the matrix whose scores start it, NULL unless init = SRX_TSNE_INIT_PCA; init: NULL unless
+ * SRX_TSNE_INIT_GIVEN; embedding_out (n x 2 f64, row-major) and info may be NULL.  The embedding stays with the handle. */
+int32_t srx_tsne_run(srx_tsne* h, srx_mat* m, const srx_tsne_opts* opts, const double* init, double* embedding_out,
+                     srx_tsne_run_info* info);
+/* The last srx_tsne_run's embedding (n x 2 f64).  SRX_E_ARG when none has run. */
+int32_t srx_tsne_embedding_fetch(srx_tsne* h, double* out);
+void    srx_tsne_free(srx_tsne* h);
+
 /* ---- Diffusion maps and pseudotime: what sc.tl.diffmap gives obsm["X_diffmap"], uns["diffmap_evals"], and sc.tl.dpt
  * (without branchings) gives obs["dpt_pseudotime"] ---------------------------------------------------------------------------
  * Not in the reference.  This is scanpy's compute_transitions with its _transitions_sym, compute_eigen and

@@ -12,6 +12,10 @@ pub const SRX_LOUVAIN_MAX_LEVELS: i32 = 32;
 pub const SRX_GROUPS_MAX: i32 = 4096;
 pub const SRX_UMAP_GROUP: i32 = 8;
 pub const SRX_UMAP_MAX_EPOCHS: i32 = 1048576;
+pub const SRX_TSNE_MAX_K: i32 = 64;
+pub const SRX_TSNE_MAX_LEVELS: i32 = 12;
+pub const SRX_TSNE_GROUP: i32 = 8;
+pub const SRX_TSNE_MAX_ITERS: i32 = 1048576;
 pub const SRX_DIFFMAP_GROUP: i32 = 8;
 pub const SRX_DIFFMAP_MAX_COMPS: i32 = 64;
 pub const SRX_DIFFMAP_MAX_NCV: i32 = 129;
@@ -67,6 +71,9 @@ pub const SRX_MARKERS_RANKSUM2: i32 = 11;
 pub const SRX_UMAP_INIT_GIVEN: i32 = 0;
 pub const SRX_UMAP_INIT_RANDOM: i32 = 1;
 pub const SRX_UMAP_INIT_PCA: i32 = 2;
+pub const SRX_TSNE_INIT_GIVEN: i32 = 0;
+pub const SRX_TSNE_INIT_RANDOM: i32 = 1;
+pub const SRX_TSNE_INIT_PCA: i32 = 2;
 pub const SRX_HARMONY_CORRECTED: i32 = 0;
 pub const SRX_HARMONY_R: i32 = 1;
 pub const SRX_HARMONY_CENTROIDS: i32 = 2;
@@ -94,6 +101,7 @@ pub const SRX_K_COUNT_: i32 = 13;
 #[repr(C)] pub struct SrxPcaModel { _private: [u8; 0] }      // opaque `srx_pca_model`
 #[repr(C)] pub struct SrxGraph { _private: [u8; 0] }      // opaque `srx_graph`
 #[repr(C)] pub struct SrxMarkers { _private: [u8; 0] }      // opaque `srx_markers`
+#[repr(C)] pub struct SrxTsne { _private: [u8; 0] }      // opaque `srx_tsne`
 #[repr(C)] pub struct SrxHarmony { _private: [u8; 0] }      // opaque `srx_harmony`
 #[repr(C)] pub struct SrxBacked { _private: [u8; 0] }      // opaque `srx_backed`
 
@@ -304,6 +312,65 @@ pub struct SrxUmapInfo {      // `srx_umap_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxTsneInfo {      // `srx_tsne_info`
+    pub n: u64,
+    pub nnz: u64,
+    pub n_mutual: u64,
+    pub rows_no_root: u64,
+    pub entries_dropped: u64,
+    pub k: u32,
+    pub reserved: u32,
+    pub perplexity: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxTsneOpts {      // `srx_tsne_opts`
+    pub theta: f64,
+    pub exaggeration: f64,
+    pub learning_rate: f64,
+    pub seed: u64,
+    pub n_iter: i32,
+    pub exaggeration_iters: i32,
+    pub stop_after: i32,
+    pub levels: i32,
+    pub init: i32,
+    pub reserved: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxTsneRunInfo {      // `srx_tsne_run_info`
+    pub n: u64,
+    pub nnz: u64,
+    pub n_iter: u32,
+    pub iters_run: u32,
+    pub levels: u32,
+    pub reserved: u32,
+    pub eta: f64,
+    pub Z: f64,
+    pub kl: f64,
+    pub side: f64,
+    pub cells_accepted: u64,
+    pub cells_exact: u64,
+    pub pairs_exact: u64,
+    pub ms: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxTsneForceInfo {      // `srx_tsne_force_info`
+    pub levels: u32,
+    pub reserved: u32,
+    pub side: f64,
+    pub lo: [f64; 2 as usize],
+    pub cells_accepted: u64,
+    pub cells_exact: u64,
+    pub pairs_exact: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxDiffmapOpts {      // `srx_diffmap_opts`
     pub tol: f64,
     pub seed: u64,
@@ -481,6 +548,18 @@ extern "C" {
                         opts: *const SrxUmapOpts, init: *const f64, embedding_out: *mut f64, info: *mut SrxUmapInfo) -> i32;
     pub fn srx_graph_embedding_fetch(g: *mut SrxGraph, out: *mut f64, dim_out: *mut u32) -> i32;
     pub fn srx_umap_fit_ab(spread: f64, min_dist: f64, a: *mut f64, b: *mut f64) -> i32;
+    pub fn srx_tsne_affinities_knn(ctx: *mut SrxCtx, indices: *const u32, distances: *const f64, n: u64, k: u32,
+                                   perplexity: f64, out: *mut *mut SrxTsne) -> i32;
+    pub fn srx_tsne_affinities_graph(g: *mut SrxGraph, perplexity: f64, out: *mut *mut SrxTsne) -> i32;
+    pub fn srx_tsne_info_get(h: *const SrxTsne, info: *mut SrxTsneInfo) -> i32;
+    pub fn srx_tsne_fetch_affinities(h: *mut SrxTsne, indptr: *mut u64, indices: *mut u32, data: *mut f64,
+                                     beta: *mut f64) -> i32;
+    pub fn srx_tsne_forces(h: *mut SrxTsne, Y: *const f64, theta: f64, levels: i32, attr_out: *mut f64,
+                           rep_out: *mut f64, z_out: *mut f64, info: *mut SrxTsneForceInfo) -> i32;
+    pub fn srx_tsne_run(h: *mut SrxTsne, m: *mut SrxMat, opts: *const SrxTsneOpts, init: *const f64,
+                        embedding_out: *mut f64, info: *mut SrxTsneRunInfo) -> i32;
+    pub fn srx_tsne_embedding_fetch(h: *mut SrxTsne, out: *mut f64) -> i32;
+    pub fn srx_tsne_free(h: *mut SrxTsne);
     pub fn srx_diffmap(g: *mut SrxGraph, opts: *const SrxDiffmapOpts, evals_out: *mut f64, evecs_out: *mut f64,
                        info: *mut SrxDiffmapInfo) -> i32;
     pub fn srx_diffmap_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,

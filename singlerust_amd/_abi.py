@@ -13,6 +13,10 @@ LOUVAIN_MAX_LEVELS = 32
 GROUPS_MAX = 4096
 UMAP_GROUP = 8
 UMAP_MAX_EPOCHS = 1048576
+TSNE_MAX_K = 64
+TSNE_MAX_LEVELS = 12
+TSNE_GROUP = 8
+TSNE_MAX_ITERS = 1048576
 DIFFMAP_GROUP = 8
 DIFFMAP_MAX_COMPS = 64
 DIFFMAP_MAX_NCV = 129
@@ -69,6 +73,9 @@ MARKERS_RANKSUM2 = 11
 UMAP_INIT_GIVEN = 0
 UMAP_INIT_RANDOM = 1
 UMAP_INIT_PCA = 2
+TSNE_INIT_GIVEN = 0
+TSNE_INIT_RANDOM = 1
+TSNE_INIT_PCA = 2
 HARMONY_CORRECTED = 0
 HARMONY_R = 1
 HARMONY_CENTROIDS = 2
@@ -183,6 +190,30 @@ class UmapInfo(C.Structure):      # srx_umap_info
                 ("negatives", C.c_uint64), ("negatives_skipped", C.c_uint64), ("n_epochs", C.c_uint32),
                 ("epochs_run", C.c_uint32), ("dim", C.c_uint32), ("reserved_", C.c_uint32), ("a", C.c_double),
                 ("b", C.c_double), ("w_max", C.c_double), ("ms", C.c_double)]
+
+
+class TsneInfo(C.Structure):      # srx_tsne_info
+    _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("n_mutual", C.c_uint64), ("rows_no_root", C.c_uint64),
+                ("entries_dropped", C.c_uint64), ("k", C.c_uint32), ("reserved_", C.c_uint32),
+                ("perplexity", C.c_double)]
+
+
+class TsneOpts(C.Structure):      # srx_tsne_opts
+    _fields_ = [("theta", C.c_double), ("exaggeration", C.c_double), ("learning_rate", C.c_double),
+                ("seed", C.c_uint64), ("n_iter", C.c_int32), ("exaggeration_iters", C.c_int32),
+                ("stop_after", C.c_int32), ("levels", C.c_int32), ("init", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class TsneRunInfo(C.Structure):      # srx_tsne_run_info
+    _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("n_iter", C.c_uint32), ("iters_run", C.c_uint32),
+                ("levels", C.c_uint32), ("reserved_", C.c_uint32), ("eta", C.c_double), ("Z", C.c_double),
+                ("kl", C.c_double), ("side", C.c_double), ("cells_accepted", C.c_uint64), ("cells_exact", C.c_uint64),
+                ("pairs_exact", C.c_uint64), ("ms", C.c_double)]
+
+
+class TsneForceInfo(C.Structure):      # srx_tsne_force_info
+    _fields_ = [("levels", C.c_uint32), ("reserved_", C.c_uint32), ("side", C.c_double), ("lo", C.c_double * 2),
+                ("cells_accepted", C.c_uint64), ("cells_exact", C.c_uint64), ("pairs_exact", C.c_uint64)]
 
 
 class DiffmapOpts(C.Structure):      # srx_diffmap_opts
@@ -306,6 +337,14 @@ SIGNATURES = {
     "srx_umap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
     "srx_graph_embedding_fetch": (C.c_int32, [P, P, P]),
     "srx_umap_fit_ab": (C.c_int32, [C.c_double, C.c_double, P, P]),
+    "srx_tsne_affinities_knn": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.c_double, C.POINTER(P)]),
+    "srx_tsne_affinities_graph": (C.c_int32, [P, C.c_double, C.POINTER(P)]),
+    "srx_tsne_info_get": (C.c_int32, [P, C.POINTER(TsneInfo)]),
+    "srx_tsne_fetch_affinities": (C.c_int32, [P, P, P, P, P]),
+    "srx_tsne_forces": (C.c_int32, [P, P, C.c_double, C.c_int32, P, P, P, C.POINTER(TsneForceInfo)]),
+    "srx_tsne_run": (C.c_int32, [P, P, C.POINTER(TsneOpts), P, P, C.POINTER(TsneRunInfo)]),
+    "srx_tsne_embedding_fetch": (C.c_int32, [P, P]),
+    "srx_tsne_free": (None, [P]),
     "srx_diffmap": (C.c_int32, [P, C.POINTER(DiffmapOpts), P, P, C.POINTER(DiffmapInfo)]),
     "srx_diffmap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(DiffmapOpts), P, P, C.POINTER(DiffmapInfo)]),
     "srx_graph_diffmap_fetch": (C.c_int32, [P, P, P, P]),

@@ -46,13 +46,12 @@ int32_t knn_result_resident(srx_mat* m, const srx_knn_opts* opts, srx_knn_info* 
 constexpr int kGraphMaxK = 64;
 constexpr int kShort = 512;              // in-only lists up to here are ordered by one wave in LDS
 constexpr int kBits = 1 << 17;           // source numbers per pass of the long-list ordering (16 KiB bitmap + 16 KiB prefix)
-constexpr int kCtrSlots = 64;            // counters are spread over slots (row & 63) and summed on the host
-enum { kCtrNoRoot = 0, kCtrClamped, kCtrAllZero, kCtrMutual, kCtrDropped, kCtrN };
-enum { kBadRange = 1, kBadSelf = 2, kBadDup = 4, kBadDist = 8 };
 
 __device__ __forceinline__ unsigned long long below(int p) { return p >= 64 ? ~0ull : (1ull << p) - 1ull; }
 // (a + b) - a b in one rounding of the product: symmetric in a and b, 0 < result <= 1 for a, b in [0, 1] not both 0
 __device__ __forceinline__ double fuzzy_union(double a, double b) { return fma(-a, b, a + b); }
+// the value of a pair from its two directed weights (an absent direction is 0): symmetric in a and b for either rule
+__device__ __forceinline__ double pair_value(PairRule r, double a, double b) { return r.mean ? (a + b) / r.denom : fuzzy_union(a, b); }
 
 // S(s) of the lane's row: `one` lanes count 1, `far` lanes exp(-x / s), the others nothing.  The butterfly adds in an
 // order that does not depend on the lane, so every lane holds the same bits.
@@ -174,7 +173,7 @@ __device__ __forceinline__ int lower_bound_u32(const uint32_t* __restrict__ p, i
 
 // flags: bit 0 the out-edge's entry of C is stored, bit 1 the edge is an in-only entry of its target's row
 __global__ void __launch_bounds__(256) k_graph_reverse(const uint32_t* __restrict__ dind, const double* __restrict__ a_in,
-                                                       uint64_t n, int k, double* __restrict__ cval,
+                                                       uint64_t n, int k, PairRule rule, double* __restrict__ cval,
                                                        unsigned char* __restrict__ flags, int64_t* __restrict__ cnt_out,
                                                        int64_t* __restrict__ indeg, unsigned long long* __restrict__ ctr) {
     const int lane = lane_id();
@@ -191,7 +190,7 @@ __global__ void __launch_bounds__(256) k_graph_reverse(const uint32_t* __restric
         const int q = lower_bound_u32(rj, k, (uint32_t)row);
         found = q < k && rj[q] == (uint32_t)row;
         const double b = found ? a_in[(size_t)j * k + q] : 0.0;
-        const double v = fuzzy_union(a, b);
+        const double v = pair_value(rule, a, b);
         kept = v != 0.0;
         const bool in_only = !found && kept;
         if (in_only) atomicAdd((unsigned long long*)&indeg[j], 1ull);
@@ -302,7 +301,7 @@ __global__ void __launch_bounds__(256) k_graph_order_long(const int64_t* __restr
 }
 
 __global__ void __launch_bounds__(256) k_graph_merge(const uint32_t* __restrict__ dind, const double* __restrict__ cval,
-                                                     const unsigned char* __restrict__ flags, uint64_t n, int k,
+                                                     const unsigned char* __restrict__ flags, uint64_t n, int k, PairRule rule,
                                                      const int64_t* __restrict__ tptr, const uint32_t* __restrict__ t_src,
                                                      const double* __restrict__ t_val, const uint32_t* __restrict__ l_src,
                                                      const double* __restrict__ l_val, const uint64_t* __restrict__ cptr,
@@ -333,7 +332,7 @@ __global__ void __launch_bounds__(256) k_graph_merge(const uint32_t* __restrict_
         const int r = lower_bound_u32(s_col[wave], k, j);          // out-edges below j (j itself is not among them)
         const uint64_t pos = (uint64_t)q + (uint64_t)__builtin_popcountll(keptmask & below(r));
         cind[base + pos] = j;
-        cdat[base + pos] = fuzzy_union(tv[q], 0.0);
+        cdat[base + pos] = pair_value(rule, tv[q], 0.0);
     }
 }
 
@@ -398,76 +397,28 @@ static int32_t graph_build(srx_ctx* ctx, const uint32_t* d_idx, const double* d_
     } while (0)
     const size_t nk = (size_t)n * k;
     hipStream_t st = ctx->stream;
-    // small: counters kCtrSlots x kCtrN | longest row, long lists | flag
-    constexpr size_t n_small = (size_t)kCtrSlots * kCtrN + 3;
     unsigned long long* d_small;
-    G_TRY(scratch(ctx, "graph_small", n_small * 8, (void**)&d_small));
-    unsigned long long* d_ctr = d_small;
-    unsigned long long* d_two = d_small + (size_t)kCtrSlots * kCtrN;
-    int* d_flag = reinterpret_cast<int*>(d_two + 2);
-    double* d_cval;
-    unsigned char* d_flags;
-    int64_t *d_cnt, *d_indeg, *d_len, *d_tptr;
-    unsigned long long* d_cursor;
-    uint32_t *d_long, *d_tsrc, *d_lsrc = nullptr;
-    double *d_tval, *d_lval = nullptr;
-    G_TRY(scratch(ctx, "graph_cval", nk * 8, (void**)&d_cval));
-    G_TRY(scratch(ctx, "graph_flags", nk, (void**)&d_flags));
-    G_TRY(scratch(ctx, "graph_cnt", n * 8, (void**)&d_cnt));
-    G_TRY(scratch(ctx, "graph_indeg", 2 * n * 8, (void**)&d_indeg));       // in-only counts | cursors
-    d_cursor = reinterpret_cast<unsigned long long*>(d_indeg + n);
-    G_TRY(scratch(ctx, "graph_len", n * 8, (void**)&d_len));
-    G_TRY(scratch(ctx, "graph_tptr", (n + 1) * 8, (void**)&d_tptr));
-    G_TRY(scratch(ctx, "graph_long", (nk / kShort + 1) * 4, (void**)&d_long));     // lists longer than kShort: at most nk / kShort
-    G_TRY(scratch(ctx, "graph_tsrc", nk * 4, (void**)&d_tsrc));
-    G_TRY(scratch(ctx, "graph_tval", nk * 8, (void**)&d_tval));
-
-    const unsigned wg_rows = (unsigned)((n + 3) / 4), wg_thr = (unsigned)((n + 255) / 256), wg_edges = (unsigned)((nk + 255) / 256);
-    uint64_t ctr[kCtrSlots * kCtrN + 2];
+    G_TRY(scratch(ctx, "graph_small", kPairSmallWords * 8, (void**)&d_small));
+    const unsigned wg_rows = (unsigned)((n + 3) / 4);
+    uint64_t ctr[kPairSmallWords];
+    uint64_t nnz = 0;
     {
         // algorithmic bytes: read the list, write D; C is added once its size is known
         ProfScope ps(ctx, SRX_K_GRAPH, (double)nk * 12.0 * 2.0 + (double)(n + 1) * 16.0);
-        G_HIP(hipMemsetAsync(d_small, 0, n_small * 8, st));
-        G_HIP(hipMemsetAsync(d_indeg, 0, 2 * n * 8, st));
+        G_HIP(hipMemsetAsync(d_small, 0, kPairSmallWords * 8, st));
         hipLaunchKernelGGL(k_graph_rows, dim3(wg_rows), dim3(256), 0, st, d_idx, d_dist, n, (int)k, g->d_dptr, g->d_dind, g->d_ddat,
-                           g->d_a, g->d_rho, g->d_sigma, d_ctr, d_flag);
+                           g->d_a, g->d_rho, g->d_sigma, d_small, pair_flag(d_small));
         G_HIP(hipGetLastError());
-        int flag = 0;
-        G_TRY(d2h(ctx, &flag, d_flag, 4));
-        if (flag & kBadRange) return bail(fail(ctx, SRX_E_ARG, "neighbors: a neighbour index is not below n = %llu", (unsigned long long)n));
-        if (flag & kBadSelf) return bail(fail(ctx, SRX_E_ARG, "neighbors: a row names itself (the list must exclude self)"));
-        if (flag & kBadDup) return bail(fail(ctx, SRX_E_ARG, "neighbors: a row names one neighbour twice"));
-        if (flag & kBadDist) return bail(fail(ctx, SRX_E_ARG, "neighbors: a distance is negative, NaN or Inf"));
-        hipLaunchKernelGGL(k_graph_reverse, dim3(wg_rows), dim3(256), 0, st, g->d_dind, g->d_a, n, (int)k, d_cval, d_flags, d_cnt,
-                           d_indeg, d_ctr);
-        hipLaunchKernelGGL(k_graph_rowlen, dim3(wg_thr), dim3(256), 0, st, d_cnt, d_indeg, n, d_len, d_long, d_two);
-        G_HIP(hipGetLastError());
-        G_TRY(scan_exclusive(ctx, d_indeg, n, d_tptr, nullptr));
-        hipLaunchKernelGGL(k_graph_scatter, dim3(wg_edges), dim3(256), 0, st, g->d_dind, g->d_a, d_flags, (uint64_t)nk, (int)k, d_tptr,
-                           d_cursor, d_tsrc, d_tval);
-        hipLaunchKernelGGL(k_graph_order, dim3(wg_rows), dim3(256), 0, st, d_tptr, n, d_tsrc, d_tval);
-        G_HIP(hipGetLastError());
-        G_TRY(d2h(ctx, ctr, d_small, (n_small - 1) * 8));
-        const uint64_t n_long = ctr[kCtrSlots * kCtrN + 1];
-        if (n_long) {
-            G_TRY(scratch(ctx, "graph_lsrc", nk * 4, (void**)&d_lsrc));
-            G_TRY(scratch(ctx, "graph_lval", nk * 8, (void**)&d_lval));
-            hipLaunchKernelGGL(k_graph_order_long, dim3((unsigned)n_long), dim3(256), 0, st, d_tptr, d_long, n, d_tsrc, d_tval, d_lsrc,
-                               d_lval);
-            G_HIP(hipGetLastError());
-        }
-        // indptr of C goes to scratch first: its last entry sizes the allocation it then moves into
-        int64_t* d_cptr_tmp;
-        G_TRY(scratch(ctx, "graph_cptr", (n + 1) * 8, (void**)&d_cptr_tmp));
-        G_TRY(scan_exclusive(ctx, d_len, n, d_cptr_tmp, nullptr));
-        int64_t nnz = 0;
-        G_TRY(d2h(ctx, &nnz, d_cptr_tmp + n, 8));
-        G_TRY(graph_alloc_c(g, (uint64_t)nnz));
-        G_HIP(hipMemcpyAsync(g->d_cptr, d_cptr_tmp, (n + 1) * 8, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_graph_merge, dim3(wg_rows), dim3(256), 0, st, g->d_dind, d_cval, d_flags, n, (int)k, d_tptr, d_tsrc, d_tval,
-                           d_lsrc, d_lval, g->d_cptr, g->d_cind, g->d_cdat);
-        G_HIP(hipGetLastError());
-        g->info.nnz_connectivities = (uint64_t)nnz;
+        G_TRY(list_flag_check(ctx, "neighbors", n, pair_flag(d_small)));
+        G_TRY(pair_union_csr(ctx, PairRule{0, 1.0}, g->d_dind, g->d_a, n, k, d_small, ctr, &nnz,
+                             [&](uint64_t cnt, uint64_t** ptr, uint32_t** ind, double** dat) {
+                                 SRX_TRY(graph_alloc_c(g, cnt));
+                                 *ptr = g->d_cptr;
+                                 *ind = g->d_cind;
+                                 *dat = g->d_cdat;
+                                 return (int32_t)SRX_OK;
+                             }));
+        g->info.nnz_connectivities = nnz;
         if (ps.e0) ctx->prof[SRX_K_GRAPH].bytes += (double)nnz * 12.0;
     }
     G_HIP(hipStreamSynchronize(st));
@@ -484,6 +435,79 @@ static int32_t graph_build(srx_ctx* ctx, const uint32_t* d_idx, const double* d_
     g->info.entries_dropped = sum[kCtrDropped];
     g->info.max_row_nnz = ctr[kCtrSlots * kCtrN];
     *out = g;
+    return SRX_OK;
+}
+
+int32_t list_flag_check(srx_ctx* ctx, const char* who, uint64_t n, const int* d_flag) {
+    int flag = 0;
+    SRX_TRY(d2h(ctx, &flag, d_flag, 4));
+    if (flag & kBadRange) return fail(ctx, SRX_E_ARG, "%s: a neighbour index is not below n = %llu", who, (unsigned long long)n);
+    if (flag & kBadSelf) return fail(ctx, SRX_E_ARG, "%s: a row names itself (the list must exclude self)", who);
+    if (flag & kBadDup) return fail(ctx, SRX_E_ARG, "%s: a row names one neighbour twice", who);
+    if (flag & kBadDist) return fail(ctx, SRX_E_ARG, "%s: a distance is negative, NaN or Inf", who);
+    return SRX_OK;
+}
+
+// The symmetric pattern of a k-NN list and its transpose with one value per pair (graph_handle.hpp): k_graph_reverse to
+// k_graph_merge.  d_small: the caller's zeroed block, whose row counters and flag it may have used already.
+int32_t pair_union_csr(srx_ctx* ctx, PairRule rule, const uint32_t* d_dind, const double* d_a, uint64_t n, uint32_t k,
+                       unsigned long long* d_small, uint64_t* ctr, uint64_t* nnz_out, const PairAlloc& alloc) {
+    const size_t nk = (size_t)n * k;
+    hipStream_t st = ctx->stream;
+    unsigned long long* d_ctr = d_small;
+    unsigned long long* d_two = d_small + (size_t)kCtrSlots * kCtrN;
+    double* d_cval;
+    unsigned char* d_flags;
+    int64_t *d_cnt, *d_indeg, *d_len, *d_tptr;
+    unsigned long long* d_cursor;
+    uint32_t *d_long, *d_tsrc, *d_lsrc = nullptr;
+    double *d_tval, *d_lval = nullptr;
+    SRX_TRY(scratch(ctx, "graph_cval", nk * 8, (void**)&d_cval));
+    SRX_TRY(scratch(ctx, "graph_flags", nk, (void**)&d_flags));
+    SRX_TRY(scratch(ctx, "graph_cnt", n * 8, (void**)&d_cnt));
+    SRX_TRY(scratch(ctx, "graph_indeg", 2 * n * 8, (void**)&d_indeg));       // in-only counts | cursors
+    d_cursor = reinterpret_cast<unsigned long long*>(d_indeg + n);
+    SRX_TRY(scratch(ctx, "graph_len", n * 8, (void**)&d_len));
+    SRX_TRY(scratch(ctx, "graph_tptr", (n + 1) * 8, (void**)&d_tptr));
+    SRX_TRY(scratch(ctx, "graph_long", (nk / kShort + 1) * 4, (void**)&d_long));     // lists longer than kShort: at most nk / kShort
+    SRX_TRY(scratch(ctx, "graph_tsrc", nk * 4, (void**)&d_tsrc));
+    SRX_TRY(scratch(ctx, "graph_tval", nk * 8, (void**)&d_tval));
+
+    const unsigned wg_rows = (unsigned)((n + 3) / 4), wg_thr = (unsigned)((n + 255) / 256), wg_edges = (unsigned)((nk + 255) / 256);
+    SRX_HIP(ctx, hipMemsetAsync(d_indeg, 0, 2 * n * 8, st));
+    hipLaunchKernelGGL(k_graph_reverse, dim3(wg_rows), dim3(256), 0, st, d_dind, d_a, n, (int)k, rule, d_cval, d_flags, d_cnt, d_indeg,
+                       d_ctr);
+    hipLaunchKernelGGL(k_graph_rowlen, dim3(wg_thr), dim3(256), 0, st, d_cnt, d_indeg, n, d_len, d_long, d_two);
+    SRX_HIP(ctx, hipGetLastError());
+    SRX_TRY(scan_exclusive(ctx, d_indeg, n, d_tptr, nullptr));
+    hipLaunchKernelGGL(k_graph_scatter, dim3(wg_edges), dim3(256), 0, st, d_dind, d_a, d_flags, (uint64_t)nk, (int)k, d_tptr, d_cursor,
+                       d_tsrc, d_tval);
+    hipLaunchKernelGGL(k_graph_order, dim3(wg_rows), dim3(256), 0, st, d_tptr, n, d_tsrc, d_tval);
+    SRX_HIP(ctx, hipGetLastError());
+    SRX_TRY(d2h(ctx, ctr, d_small, (kPairSmallWords - 1) * 8));
+    const uint64_t n_long = ctr[kCtrSlots * kCtrN + 1];
+    if (n_long) {
+        SRX_TRY(scratch(ctx, "graph_lsrc", nk * 4, (void**)&d_lsrc));
+        SRX_TRY(scratch(ctx, "graph_lval", nk * 8, (void**)&d_lval));
+        hipLaunchKernelGGL(k_graph_order_long, dim3((unsigned)n_long), dim3(256), 0, st, d_tptr, d_long, n, d_tsrc, d_tval, d_lsrc,
+                           d_lval);
+        SRX_HIP(ctx, hipGetLastError());
+    }
+    // the indptr goes to scratch first: its last entry sizes the allocation it then moves into
+    int64_t* d_cptr_tmp;
+    SRX_TRY(scratch(ctx, "graph_cptr", (n + 1) * 8, (void**)&d_cptr_tmp));
+    SRX_TRY(scan_exclusive(ctx, d_len, n, d_cptr_tmp, nullptr));
+    int64_t nnz = 0;
+    SRX_TRY(d2h(ctx, &nnz, d_cptr_tmp + n, 8));
+    uint64_t* cptr = nullptr;
+    uint32_t* cind = nullptr;
+    double* cdat = nullptr;
+    SRX_TRY(alloc((uint64_t)nnz, &cptr, &cind, &cdat));
+    SRX_HIP(ctx, hipMemcpyAsync(cptr, d_cptr_tmp, (n + 1) * 8, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_graph_merge, dim3(wg_rows), dim3(256), 0, st, d_dind, d_cval, d_flags, n, (int)k, rule, d_tptr, d_tsrc, d_tval,
+                       d_lsrc, d_lval, cptr, cind, cdat);
+    SRX_HIP(ctx, hipGetLastError());
+    *nnz_out = (uint64_t)nnz;
     return SRX_OK;
 }
 

@@ -1,9 +1,11 @@
 // graph_handle.hpp — the srx_graph handle of srx.h: built by graph.hip, read where it lies by the graph algorithms (louvain.hip,
-// umap.hip, diffmap.hip).
+// umap.hip, diffmap.hip, tsne.hip), and the union of a k-NN list with its transpose that graph.hip builds for C and tsne.hip for P.
 #pragma once
 
 #include "common.hpp"
 #include "symcsr.hpp"
+
+#include <functional>
 
 struct srx_graph {
     srx_ctx* ctx = nullptr;
@@ -42,4 +44,29 @@ inline SymCsr connectivities(const srx_graph* g) { return SymCsr{g->d_cptr, g->d
 // A result kept with the handle (graph.hip): *slot (hipMalloc, freed first when `resized` says the array it holds has another
 // size) <- the `bytes` at d_src, queued on the context's stream.  The caller owns the flag that says whether *slot is valid.
 int32_t keep_on_handle(srx_ctx* ctx, double** slot, bool resized, const double* d_src, size_t bytes);
+
+// ---- the union of a k-NN list with its transpose (graph.hip) -------------------------------------------------------------------
+// What a row kernel finds wrong with a list (OR-ed into a flag word), and the refusal that names it: `who` starts the message.
+enum { kBadRange = 1, kBadSelf = 2, kBadDup = 4, kBadDist = 8 };
+int32_t list_flag_check(srx_ctx* ctx, const char* who, uint64_t n, const int* d_flag);
+// The small block of a build: counters spread over kCtrSlots slots (row & 63) of kCtrN words, summed on the host | the longest
+// row, the number of long in-only lists | the flag.  The first three counters belong to the caller's row kernel.
+constexpr int kCtrSlots = 64;
+enum { kCtrNoRoot = 0, kCtrClamped, kCtrAllZero, kCtrMutual, kCtrDropped, kCtrN };
+constexpr size_t kPairSmallWords = (size_t)kCtrSlots * kCtrN + 3;
+inline int* pair_flag(unsigned long long* d_small) { return reinterpret_cast<int*>(d_small + kPairSmallWords - 1); }
+// The value of a pair from its directed weights a and b (0 for an absent direction): the fuzzy union (a + b) - a b, or with
+// `mean` the quotient (a + b) / denom.  Both are symmetric in a and b, so the two entries of a pair are the same bits.
+struct PairRule {
+    int mean;
+    double denom;
+};
+// Where the result goes, once its size is known: (nnz, &indptr (n + 1), &indices, &data), all device pointers.
+using PairAlloc = std::function<int32_t(uint64_t, uint64_t**, uint32_t**, double**)>;
+// d_dind / d_a: the rows of the list in column order (n x k) and their directed weights.  Builds the CSR of every pair joined
+// in either direction, rows ascending by column, pairs whose value is 0.0 dropped.  d_small: kPairSmallWords words the caller
+// zeroed (its row kernel may have counted in them); ctr: the host copy, kPairSmallWords - 1 words (kCtrMutual counts both ends
+// of a mutual pair, kCtrDropped every dropped entry of the symmetric matrix, word kCtrSlots * kCtrN is the longest row).
+int32_t pair_union_csr(srx_ctx* ctx, PairRule rule, const uint32_t* d_dind, const double* d_a, uint64_t n, uint32_t k,
+                       unsigned long long* d_small, uint64_t* ctr, uint64_t* nnz_out, const PairAlloc& alloc);
 }  // namespace srx
