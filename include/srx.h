@@ -1032,6 +1032,117 @@ int32_t srx_knn_harmony(srx_harmony* h, const srx_knn_opts* opts, uint32_t* indi
 int32_t srx_neighbors_harmony(srx_harmony* h, const srx_knn_opts* opts, srx_knn_info* knn_info, srx_graph** out);
 void    srx_harmony_free(srx_harmony* h);
 
+/* ---- Doublet detection: simulate, project, score; what sc.pp.scrublet gives obs["doublet_score"], obs["predicted_doublet"] ---
+ * Not in the reference.  This is Scrublet (Wolock et al. 2019) RESTATED below, with its random parent pairs replaced by a hash
+ * so that the result is bit-identical from call to call and its embedding replaced by this library's pipeline.  The definition
+ * here is what is tested; the output has NOT been compared with the `scrublet` package, scanpy or scikit-image, none of which
+ * is installed where this was built.  n = the observed cells; mix() and G = 0x9E3779B97F4A7C15 are those of the UMAP section.
+ *
+ * 1. Simulation.  n_sim = round(sim_ratio * n), r = n_sim / n as a double; round(x) = floor(x + 0.5) here and in section 3.  The
+ *    parents of synthetic row s are
+ *      p(s, c) = ((mix(seed + G * (1 + 2 s + c)) >> 32) * n) >> 32,   c = 0, 1   (mod 2^64; with replacement, p(s, 0) == p(s, 1)
+ *    allowed as in Scrublet), or the 2 n_sim parents the caller gives.  Row s of the synthetic matrix is
+ *    counts[p(s, 0), :] + counts[p(s, 1), :]: the union of the two patterns, columns ascending and unique; a column of both
+ *    parents holds a + b rounded once in the storage type (exact for counts below 2^24 at f32 storage, 2^53 at f64), a column
+ *    of one parent that value.  A stored entry stays stored when its sum is 0.0.  The result is an ordinary srx_mat in the
+ *    parent's value storage, logical dtype F32 at f32 storage and F64 at f64 storage (a u8 parent does not wrap at 255 + 255),
+ *    with the parent's n_cols; every entry point that takes an srx_mat accepts it.  It is bit-identical from call to call: no
+ *    atomics, every output position is computed on its own.
+ * 2. Embedding.  `fitted` holds a PCA result for the same n cells and the same gene axis (in practice a clone of the counts after
+ *    srx_pipeline).  Rows [0, n) of the point block are its resident scores, copied device to device bit for bit; rows
+ *    [n, n + n_sim) are what srx_pca_transform gives for the synthetic matrix under srx_pca_model_from_result(fitted),
+ *    feat == NULL and the caller's target_sum and transform bits (the caller names what was applied to `fitted`; both bits =
+ *    the pipeline's write-back rounding, as documented there), written straight into the block.
+ * 3. Neighbours.  k_adj = round(k * (1 + r)); k == 0 means round(0.5 * sqrt(n)).  The exact self search of srx_knn_result over
+ *    all n + n_sim points, include_self = 0, the first n_dims coordinates, that section's tie rule.  k_adj outside
+ *    1 .. SRX_DOUBLET_MAX_K is SRX_E_ARG: at r = 2 this allows k <= 21, and scanpy's default k exceeds that for more than
+ *    about 1 800 cells — the caller then chooses k, or a smaller sim_ratio (t-SNE carries the same 64-neighbour limit).
+ * 4. Scores.  For each of the n + n_sim rows, k_d = its neighbours with index >= n, rho = expected_rate, se_rho = stdev_rate:
+ *      q     = (k_d + 1) / (k_adj + 2)
+ *      D     = 1 - rho - q * (1 - rho - rho / r)
+ *      Ld    = q * rho / r / D
+ *      se_q  = sqrt(q * (1 - q) / (k_adj + 3))
+ *      se_Ld = q * rho / r / (D * D) * sqrt((se_q / q * (1 - rho))^2 + (se_rho / rho * (1 - q))^2)
+ *    in f64, in the order written (products and quotients left to right), no contraction, no fast-math.  Ld of rows [0, n) are
+ *    the observed scores, those of [n, n + n_sim) the simulated ones.
+ * 5. Threshold (host code): scikit-image's threshold_minimum, which Scrublet's call_doublets applies to the simulated scores.
+ *    Histogram: 256 equal bins over [min, max], the bin of x is min(255, floor((x - min) / (max - min) * 256)), the centre of
+ *    bin b is min + (b + 0.5) * (max - min) / 256, counts held as doubles.  A smoothing round is
+ *    s'[i] = (s[i-1] + s[i] + s[i+1]) / 3 summed left to right with s[-1] = s[0], s[256] = s[255].  After each round the maxima:
+ *    walk i = 0 .. 254 with a direction that starts as rising; while rising, s[i+1] < s[i] records a maximum at i and turns to
+ *    falling; while falling, s[i+1] > s[i] turns to rising.  Stop at the first round with fewer than three maxima (at least
+ *    one round is made; the limit is SRX_DOUBLET_MAX_ROUNDS).  Exactly two maxima m0 < m1 below the limit: the threshold is the
+ *    centre of the first minimum of s on [m0, m1], found = 1.  Otherwise (fewer than two maxima, the limit reached, fewer than
+ *    2 scores, max == min, a non-finite score): threshold NaN, found = 0, nothing is predicted and the rates are NaN; this is
+ *    not an error status.  A caller's threshold > 0 replaces all of this (threshold_found and smooth_rounds are then 0).
+ *    With a threshold t: predicted[i] = Ld_obs[i] > t, z[i] = (Ld_obs[i] - t) / se_obs[i], detected_rate = mean(Ld_obs > t),
+ *    detectable_fraction = mean(Ld_sim > t), overall_rate = detected_rate / detectable_fraction.
+ * Not done: UMI subsampling of the synthetic rows (synthetic_doublet_umi_subsampling < 1); Scrublet's own gene filter and
+ *    z-scoring (the embedding is this library's pipeline); more than SRX_DOUBLET_MAX_K neighbours.
+ * The simulation's count and fill passes give a wave to a synthetic row whose parents hold up to SRX_DOUBLET_WAVE_ROW entries
+ *    together and a workgroup to a longer one; the result does not depend on which.
+ * Refused with SRX_E_ARG and a message, nothing launched (*out is left untouched): a NULL argument (info, parents and
+ *    parents_out may be NULL); counts in CSC storage (convert with srx_matrix_to_csr); a context with more than one rank; fitted
+ *    without a PCA result; cell or gene counts of the two matrices that differ; n == 0; n_sim == 0 in srx_doublets_result;
+ *    n + n_sim >= 2^32; sim_ratio negative or non-finite; expected_rate outside (0, 1); stdev_rate negative or NaN; bad
+ *    transform bits; k negative; k_adj outside 1 .. SRX_DOUBLET_MAX_K or above n + n_sim - 1; n_dims above the scores'
+ *    components; in the list form k_adj == 0, n_obs == 0 or an index >= n_obs + n_sim.  SRX_E_BOUNDS: a given parent >= n.
+ *    srx_doublets_simulate with n_sim == 0 gives an empty matrix of n_cols columns. */
+#define SRX_DOUBLET_MAX_K 64
+#define SRX_DOUBLET_MAX_ROUNDS 10000
+#define SRX_DOUBLET_WAVE_ROW 8192
+typedef struct srx_doublets srx_doublets;   /* owns the point block, the list, the parents and the scores; free it before its context */
+typedef struct srx_doublet_opts {
+    double   sim_ratio;             /* 0 = 2.0 */
+    double   expected_rate;         /* 0 = 0.05 */
+    double   stdev_rate;            /* 0 = 0.02 */
+    double   target_sum;            /* of the transform applied to `fitted` (SRX_BACKED_NORMALIZE) */
+    double   threshold;             /* 0 = automatic */
+    uint64_t seed;
+    int32_t  k;                     /* 0 = round(0.5 * sqrt(n)) */
+    int32_t  n_dims;                /* leading components used by the search, 0 = all */
+    int32_t  transform;             /* SRX_BACKED_NORMALIZE | SRX_BACKED_LOG1P: what was applied to `fitted` before its fit */
+    int32_t  reserved_;
+} srx_doublet_opts;
+typedef struct srx_doublet_info {
+    uint64_t n_obs, n_sim, nnz_sim;
+    uint32_t k, k_adj, d;           /* d: coordinates used by the search */
+    uint32_t threshold_found;       /* 1: the automatic threshold exists and is in use */
+    double   threshold;             /* in use: automatic, the caller's, or NaN */
+    uint32_t smooth_rounds;         /* smoothing rounds of the automatic threshold */
+    uint32_t reserved_;
+    uint64_t n_predicted;
+    double   detected_rate, detectable_fraction, overall_rate;
+    uint64_t rows_certified, rows_recomputed;             /* of the k-NN search (srx_knn_info) */
+    double   ms_simulate, ms_project, ms_knn, ms_score;   /* hipEvent times of the stages */
+} srx_doublet_info;
+enum { SRX_DOUBLETS_SCORES_OBS = 0 /* n f64 */, SRX_DOUBLETS_SCORES_SIM = 1 /* n_sim f64 */, SRX_DOUBLETS_SE_OBS = 2,
+       SRX_DOUBLETS_SE_SIM = 3, SRX_DOUBLETS_Z = 4 /* n f64 */, SRX_DOUBLETS_PREDICTED = 5 /* n u8 */,
+       SRX_DOUBLETS_POINTS = 6 /* (n + n_sim) x d f64 row-major: the coordinates the search used */,
+       SRX_DOUBLETS_PARENTS = 7 /* 2 n_sim u64 */, SRX_DOUBLETS_KNN = 8 /* (n + n_sim) x k_adj u32 */ };
+/* Section 1 alone.  counts: CSR; parents: 2 n_sim host entries (row s: parents[2 s], parents[2 s + 1]) or NULL = hashed from
+ * seed; parents_out (room for 2 n_sim, may be NULL) receives the parents used.  *out is an srx_mat the caller frees. */
+int32_t srx_doublets_simulate(srx_mat* counts, uint64_t n_sim, uint64_t seed, const uint64_t* parents, srx_mat** out,
+                              uint64_t* parents_out);
+/* Section 4 alone, on a caller's neighbour list (host, (n_obs + n_sim) x k_adj row-major; any k_adj >= 1): the scoring kernel
+ * applied to it.  score_out / se_out: n_obs + n_sim f64 each, either may be NULL. */
+int32_t srx_doublet_scores_knn(srx_ctx* ctx, const uint32_t* indices, uint64_t n_obs, uint64_t n_sim, uint32_t k_adj,
+                               double expected_rate, double stdev_rate, double* score_out, double* se_out);
+/* Section 5's automatic threshold alone: pure host code, no context, no device.  Any output may be NULL. */
+int32_t srx_doublets_threshold(const double* sim_scores, uint64_t n, double* threshold_out, int32_t* found_out,
+                               uint32_t* rounds_out);
+/* The whole chain with every intermediate in HBM; only the simulated scores come to the host, for the threshold.  opts NULL =
+ * all defaults (no transform).  The synthetic matrix is freed before the call returns.  *out is written on success only. */
+int32_t srx_doublets_result(srx_mat* fitted, srx_mat* counts, const srx_doublet_opts* opts, srx_doublets** out,
+                            srx_doublet_info* info);
+/* Scrublet's call_doublets(threshold = ...) on the resident scores: threshold 0 = the automatic one again.  Negative or NaN:
+ * SRX_E_ARG. */
+int32_t srx_doublets_call(srx_doublets* h, double threshold, srx_doublet_info* info);
+/* One table (the enum above names each one's type and shape). */
+int32_t srx_doublets_fetch(srx_doublets* h, int32_t which, void* out);
+int32_t srx_doublets_info_get(const srx_doublets* h, srx_doublet_info* info);
+void    srx_doublets_free(srx_doublets* h);
+
 /* The raw operators the PCA is built from, for a caller-supplied 64-column panel (k x 64
  * row-major): y_out (n_rows x 64) = X[:, sel] * panel, t_out (k x 64) = X[:, sel]^T * y, and
  * gram_out (k x k) = X[:, sel]^T X[:, sel] (panel not needed).  `sel` must be strictly

@@ -22,6 +22,9 @@ pub const SRX_DIFFMAP_MAX_NCV: i32 = 129;
 pub const SRX_HARMONY_MAX_CLUSTERS: i32 = 256;
 pub const SRX_HARMONY_MAX_BATCHES: i32 = 256;
 pub const SRX_HARMONY_MAX_ROUNDS: i32 = 64;
+pub const SRX_DOUBLET_MAX_K: i32 = 64;
+pub const SRX_DOUBLET_MAX_ROUNDS: i32 = 10000;
+pub const SRX_DOUBLET_WAVE_ROW: i32 = 8192;
 pub const SRX_OK: i32 = 0;
 pub const SRX_E_ARG: i32 = -1;
 pub const SRX_E_DTYPE: i32 = -2;
@@ -79,6 +82,15 @@ pub const SRX_HARMONY_R: i32 = 1;
 pub const SRX_HARMONY_CENTROIDS: i32 = 2;
 pub const SRX_HARMONY_OBSERVED: i32 = 3;
 pub const SRX_HARMONY_EXPECTED: i32 = 4;
+pub const SRX_DOUBLETS_SCORES_OBS: i32 = 0;
+pub const SRX_DOUBLETS_SCORES_SIM: i32 = 1;
+pub const SRX_DOUBLETS_SE_OBS: i32 = 2;
+pub const SRX_DOUBLETS_SE_SIM: i32 = 3;
+pub const SRX_DOUBLETS_Z: i32 = 4;
+pub const SRX_DOUBLETS_PREDICTED: i32 = 5;
+pub const SRX_DOUBLETS_POINTS: i32 = 6;
+pub const SRX_DOUBLETS_PARENTS: i32 = 7;
+pub const SRX_DOUBLETS_KNN: i32 = 8;
 pub const SRX_BACKED_NORMALIZE: i32 = 1;
 pub const SRX_BACKED_LOG1P: i32 = 2;
 pub const SRX_K_NORMALIZE: i32 = 0;
@@ -103,6 +115,7 @@ pub const SRX_K_COUNT_: i32 = 13;
 #[repr(C)] pub struct SrxMarkers { _private: [u8; 0] }      // opaque `srx_markers`
 #[repr(C)] pub struct SrxTsne { _private: [u8; 0] }      // opaque `srx_tsne`
 #[repr(C)] pub struct SrxHarmony { _private: [u8; 0] }      // opaque `srx_harmony`
+#[repr(C)] pub struct SrxDoublets { _private: [u8; 0] }      // opaque `srx_doublets`
 #[repr(C)] pub struct SrxBacked { _private: [u8; 0] }      // opaque `srx_backed`
 
 #[repr(C)]
@@ -431,6 +444,46 @@ pub struct SrxHarmonyInfo {      // `srx_harmony_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxDoubletOpts {      // `srx_doublet_opts`
+    pub sim_ratio: f64,
+    pub expected_rate: f64,
+    pub stdev_rate: f64,
+    pub target_sum: f64,
+    pub threshold: f64,
+    pub seed: u64,
+    pub k: i32,
+    pub n_dims: i32,
+    pub transform: i32,
+    pub reserved: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxDoubletInfo {      // `srx_doublet_info`
+    pub n_obs: u64,
+    pub n_sim: u64,
+    pub nnz_sim: u64,
+    pub k: u32,
+    pub k_adj: u32,
+    pub d: u32,
+    pub threshold_found: u32,
+    pub threshold: f64,
+    pub smooth_rounds: u32,
+    pub reserved: u32,
+    pub n_predicted: u64,
+    pub detected_rate: f64,
+    pub detectable_fraction: f64,
+    pub overall_rate: f64,
+    pub rows_certified: u64,
+    pub rows_recomputed: u64,
+    pub ms_simulate: f64,
+    pub ms_project: f64,
+    pub ms_knn: f64,
+    pub ms_score: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPipelineResult {      // `srx_pipeline_result`
     pub pca: SrxPcaInfo,
     pub ms_normalize: f64,
@@ -582,6 +635,18 @@ extern "C" {
     pub fn srx_neighbors_harmony(h: *mut SrxHarmony, opts: *const SrxKnnOpts, knn_info: *mut SrxKnnInfo,
                                  out: *mut *mut SrxGraph) -> i32;
     pub fn srx_harmony_free(h: *mut SrxHarmony);
+    pub fn srx_doublets_simulate(counts: *mut SrxMat, n_sim: u64, seed: u64, parents: *const u64,
+                                 out: *mut *mut SrxMat, parents_out: *mut u64) -> i32;
+    pub fn srx_doublet_scores_knn(ctx: *mut SrxCtx, indices: *const u32, n_obs: u64, n_sim: u64, k_adj: u32,
+                                  expected_rate: f64, stdev_rate: f64, score_out: *mut f64, se_out: *mut f64) -> i32;
+    pub fn srx_doublets_threshold(sim_scores: *const f64, n: u64, threshold_out: *mut f64, found_out: *mut i32,
+                                  rounds_out: *mut u32) -> i32;
+    pub fn srx_doublets_result(fitted: *mut SrxMat, counts: *mut SrxMat, opts: *const SrxDoubletOpts,
+                               out: *mut *mut SrxDoublets, info: *mut SrxDoubletInfo) -> i32;
+    pub fn srx_doublets_call(h: *mut SrxDoublets, threshold: f64, info: *mut SrxDoubletInfo) -> i32;
+    pub fn srx_doublets_fetch(h: *mut SrxDoublets, which: i32, out: *mut c_void) -> i32;
+    pub fn srx_doublets_info_get(h: *const SrxDoublets, info: *mut SrxDoubletInfo) -> i32;
+    pub fn srx_doublets_free(h: *mut SrxDoublets);
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,

@@ -23,6 +23,9 @@ DIFFMAP_MAX_NCV = 129
 HARMONY_MAX_CLUSTERS = 256
 HARMONY_MAX_BATCHES = 256
 HARMONY_MAX_ROUNDS = 64
+DOUBLET_MAX_K = 64
+DOUBLET_MAX_ROUNDS = 10000
+DOUBLET_WAVE_ROW = 8192
 SYNTH_MAX_TYPES = 128
 OK = 0
 E_ARG = -1
@@ -81,6 +84,15 @@ HARMONY_R = 1
 HARMONY_CENTROIDS = 2
 HARMONY_OBSERVED = 3
 HARMONY_EXPECTED = 4
+DOUBLETS_SCORES_OBS = 0
+DOUBLETS_SCORES_SIM = 1
+DOUBLETS_SE_OBS = 2
+DOUBLETS_SE_SIM = 3
+DOUBLETS_Z = 4
+DOUBLETS_PREDICTED = 5
+DOUBLETS_POINTS = 6
+DOUBLETS_PARENTS = 7
+DOUBLETS_KNN = 8
 BACKED_NORMALIZE = 1
 BACKED_LOG1P = 2
 K_NORMALIZE = 0
@@ -241,6 +253,21 @@ class HarmonyInfo(C.Structure):      # srx_harmony_info
                 ("ms", C.c_double)]
 
 
+class DoubletOpts(C.Structure):      # srx_doublet_opts
+    _fields_ = [("sim_ratio", C.c_double), ("expected_rate", C.c_double), ("stdev_rate", C.c_double),
+                ("target_sum", C.c_double), ("threshold", C.c_double), ("seed", C.c_uint64), ("k", C.c_int32),
+                ("n_dims", C.c_int32), ("transform", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class DoubletInfo(C.Structure):      # srx_doublet_info
+    _fields_ = [("n_obs", C.c_uint64), ("n_sim", C.c_uint64), ("nnz_sim", C.c_uint64), ("k", C.c_uint32),
+                ("k_adj", C.c_uint32), ("d", C.c_uint32), ("threshold_found", C.c_uint32), ("threshold", C.c_double),
+                ("smooth_rounds", C.c_uint32), ("reserved_", C.c_uint32), ("n_predicted", C.c_uint64),
+                ("detected_rate", C.c_double), ("detectable_fraction", C.c_double), ("overall_rate", C.c_double),
+                ("rows_certified", C.c_uint64), ("rows_recomputed", C.c_uint64), ("ms_simulate", C.c_double),
+                ("ms_project", C.c_double), ("ms_knn", C.c_double), ("ms_score", C.c_double)]
+
+
 class PipelineResult(C.Structure):      # srx_pipeline_result
     _fields_ = [("pca", PcaInfo), ("ms_normalize", C.c_double), ("ms_moments", C.c_double), ("ms_select", C.c_double),
                 ("ms_compact", C.c_double), ("ms_pca", C.c_double)]
@@ -359,6 +386,14 @@ SIGNATURES = {
     "srx_knn_harmony": (C.c_int32, [P, C.POINTER(KnnOpts), P, P, C.POINTER(KnnInfo)]),
     "srx_neighbors_harmony": (C.c_int32, [P, C.POINTER(KnnOpts), C.POINTER(KnnInfo), C.POINTER(P)]),
     "srx_harmony_free": (None, [P]),
+    "srx_doublets_simulate": (C.c_int32, [P, C.c_uint64, C.c_uint64, P, C.POINTER(P), P]),
+    "srx_doublet_scores_knn": (C.c_int32, [P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, C.c_double, P, P]),
+    "srx_doublets_threshold": (C.c_int32, [P, C.c_uint64, P, P, P]),
+    "srx_doublets_result": (C.c_int32, [P, P, C.POINTER(DoubletOpts), C.POINTER(P), C.POINTER(DoubletInfo)]),
+    "srx_doublets_call": (C.c_int32, [P, C.c_double, C.POINTER(DoubletInfo)]),
+    "srx_doublets_fetch": (C.c_int32, [P, C.c_int32, P]),
+    "srx_doublets_info_get": (C.c_int32, [P, C.POINTER(DoubletInfo)]),
+    "srx_doublets_free": (None, [P]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),

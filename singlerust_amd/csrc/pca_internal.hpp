@@ -202,6 +202,8 @@ inline size_t gram_packed_count(int k) { return (size_t)k * (size_t)(k + 1) / 2;
 // ---- pca_solve.hip: products, iteration, solver ------------------------------------------------------
 int32_t build_row_order(srx_ctx* ctx, RowMajor& r);
 int scores_ld(int n_pc);
+// pca_model.inl: srx_pca_transform with feat == NULL, row r of the query written to d_out + r * ld on the device (doublets.hip)
+int32_t pca_transform_device(srx_pca_model* p, srx_mat* q, double target_sum, int32_t transform, double* d_out, size_t ld);
 void result_layout(uint64_t n_rows, int k, int n_pc, int dim, size_t& score_bytes, size_t& small_doubles,
                    std::vector<int>* plan_a_out = nullptr, std::vector<int>* plan_b_out = nullptr);
 int32_t ensure_result_capacity(srx_ctx* ctx, srx_pca_state& st, size_t need);

@@ -140,22 +140,36 @@ static int32_t model_sel(srx_pca_model* p) {
     return SRX_OK;
 }
 
-// Scores of the CSR matrix `m` (the query, or its transpose / transformed copy) into the dense host matrix `out`.
+// Where a transform leaves its scores: the dense host matrix `host` (n_rows x n_pc), or — `dev` non-null — rows of `ld`
+// doubles on the device (the forward product writes them where they lie: no staging copy, no host round trip).
+struct ScoreDest {
+    double* host = nullptr;
+    double* dev = nullptr;
+    size_t ld = 0;
+};
+
+// Scores of the CSR matrix `m` (the query, or its transpose / transformed copy) into `dst`.
 template <typename VT>
 static int32_t model_scores(srx_pca_model* p, srx_mat* m, const std::vector<uint64_t>& genes /* ascending */,
-                            const std::vector<int32_t>& row_of_slot, RowXf xf, double* out) {
+                            const std::vector<int32_t>& row_of_slot, RowXf xf, ScoreDest dst) {
     using PT = VT;
     srx_ctx* ctx = p->ctx;
     const uint64_t N = m->n_rows;
-    const int kp = (int)genes.size(), ns = p->n_slices, n_pc = (int)p->n_pc, ld = scores_ld(n_pc);
-    double* scores;
-    SRX_TRY(scratch(ctx, "pcat_scores", (N ? N : 1) * (size_t)ld * sizeof(double), (void**)&scores));
+    const int kp = (int)genes.size(), ns = p->n_slices, n_pc = (int)p->n_pc, ld = dst.dev ? (int)dst.ld : scores_ld(n_pc);
+    double* scores = dst.dev;
+    if (!scores) SRX_TRY(scratch(ctx, "pcat_scores", (N ? N : 1) * (size_t)ld * sizeof(double), (void**)&scores));
     if (kp == 0) {
         // no model gene is in the query: every row is -cvec (at the product's precision)
         std::vector<double> cv((size_t)ns * L);
         SRX_TRY(d2h(ctx, cv.data(), p->d_cvec, cv.size() * sizeof(double)));
+        if (dst.dev) {
+            std::vector<double> rows(N * (size_t)ld, 0.0);
+            for (uint64_t r = 0; r < N; ++r)
+                for (int j = 0; j < n_pc; ++j) rows[r * ld + j] = -(double)(PT)cv[j];
+            return h2d(ctx, dst.dev, rows.data(), rows.size() * sizeof(double));
+        }
         for (uint64_t r = 0; r < N; ++r)
-            for (int j = 0; j < n_pc; ++j) out[r * n_pc + j] = -(double)(PT)cv[j];
+            for (int j = 0; j < n_pc; ++j) dst.host[r * n_pc + j] = -(double)(PT)cv[j];
         return SRX_OK;
     }
     // selection bits of the present genes and their prefix counts (the compacted column of a gene is its rank among them)
@@ -185,7 +199,80 @@ static int32_t model_scores(srx_pca_model* p, srx_mat* m, const std::vector<uint
         SRX_TRY((launch_fwd_rows<VT, PT>(ctx, rm, Ps, Ps + (size_t)kp * L, std::min(L, n_pc - s * L), scores + (size_t)s * L,
                                          (PT*)nullptr, ld)));
     }
-    return d2h_rows(ctx, out, scores, N, (size_t)n_pc * 8, (size_t)ld * 8);
+    if (dst.dev) return SRX_OK;
+    return d2h_rows(ctx, dst.host, scores, N, (size_t)n_pc * 8, (size_t)ld * 8);
+}
+
+// The body of srx_pca_transform, for either destination.
+static int32_t pca_transform_into(srx_pca_model* p, srx_mat* q, const uint64_t* feat, double target_sum, int32_t transform,
+                                  ScoreDest dst) {
+    if (!p || !q) return fail(p ? p->ctx : q ? q->ctx : nullptr, SRX_E_ARG, "srx_pca_transform: null model or query");
+    srx_ctx* ctx = q->ctx;
+    if (p->ctx != ctx) return fail(ctx, SRX_E_ARG, "srx_pca_transform: model and query live on different contexts");
+    if (transform & ~(SRX_BACKED_NORMALIZE | SRX_BACKED_LOG1P)) return fail(ctx, SRX_E_ARG, "srx_pca_transform: bad transform bits %d", transform);
+    SRX_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t k = p->k;
+    const uint64_t n_cells = q->csc ? q->n_cols : q->n_rows, n_genes = q->csc ? q->n_rows : q->n_cols;
+    if (!feat) {
+        if (!p->has_sel) return fail(ctx, SRX_E_ARG, "srx_pca_transform: feat == NULL needs a model that knows its feature ids");
+        SRX_TRY(model_sel(p));
+    }
+    const uint64_t* fm = feat ? feat : p->sel.data();
+    // the present genes in ascending query order (the compacted columns' order) and the model row of each
+    std::vector<std::pair<uint64_t, int32_t>> present;
+    present.reserve(k);
+    for (uint64_t i = 0; i < k; ++i) {
+        if (fm[i] == UINT64_MAX) continue;
+        if (fm[i] >= n_genes) return fail(ctx, SRX_E_BOUNDS, "srx_pca_transform: feat[%llu] = %llu out of bounds (%llu genes)",
+                                          (unsigned long long)i, (unsigned long long)fm[i], (unsigned long long)n_genes);
+        present.emplace_back(fm[i], (int32_t)i);
+    }
+    std::sort(present.begin(), present.end());
+    for (size_t s = 1; s < present.size(); ++s)
+        if (present[s].first == present[s - 1].first)
+            return fail(ctx, SRX_E_ARG, "srx_pca_transform: query column %llu named twice in feat", (unsigned long long)present[s].first);
+    if (!dst.host && !dst.dev && n_cells) return fail(ctx, SRX_E_ARG, "srx_pca_transform: null scores_out");
+    if (n_cells == 0) return SRX_OK;
+    std::vector<uint64_t> genes(present.size());
+    std::vector<int32_t> row_of_slot(present.size());
+    for (size_t s = 0; s < present.size(); ++s) {
+        genes[s] = present[s].first;
+        row_of_slot[s] = present[s].second;
+    }
+    // the matrix the compaction reads: the query itself, the CSR of a CSC query (device transpose, as srx_pca), or — one of the
+    // two transform bits alone — a copy transformed in place by the separate calls; both bits are applied on the fly
+    const bool do_norm = (transform & SRX_BACKED_NORMALIZE) != 0, do_log = (transform & SRX_BACKED_LOG1P) != 0;
+    srx_mat* own = nullptr;
+    int32_t rc = SRX_OK;
+    if (q->csc) rc = transpose_device(q, &own);
+    else if (do_norm != do_log) rc = srx_matrix_clone(q, &own);
+    srx_mat* m = own ? own : q;
+    RowXf xf;
+    if (rc == SRX_OK && do_norm && do_log) {
+        double* rs = nullptr;
+        rc = scratch(ctx, "pcat_rowsum", (m->n_rows ? m->n_rows : 1) * sizeof(double), (void**)&rs);
+        if (rc == SRX_OK) rc = launch_row_sums(m, rs);
+        xf.row_sum = rs;
+        xf.target = target_sum;
+    } else if (rc == SRX_OK && do_norm) {
+        rc = srx_normalize_total_inplace(m, target_sum, SRX_ROW);
+    } else if (rc == SRX_OK && do_log) {
+        rc = srx_log1p_inplace(m);
+    }
+    if (rc == SRX_OK) {
+        Range r_("srx:pca_transform");
+        rc = is_f32(m) ? model_scores<float>(p, m, genes, row_of_slot, xf, dst)
+                       : model_scores<double>(p, m, genes, row_of_slot, xf, dst);
+    }
+    if (own) srx_matrix_free(own);
+    return rc;
+}
+
+// srx_pca_transform with feat == NULL whose scores stay on the device: row r of the query goes to d_out + r * ld (ld >= n_pc
+// doubles; the columns from n_pc on are left as they are).  Same checks, same arithmetic, same bits as the host entry point.
+int32_t pca_transform_device(srx_pca_model* p, srx_mat* q, double target_sum, int32_t transform, double* d_out, size_t ld) {
+    if (!d_out || !p || ld < p->n_pc) return fail(p ? p->ctx : nullptr, SRX_E_ARG, "pca_transform_device: no room for the scores");
+    return pca_transform_into(p, q, nullptr, target_sum, transform, ScoreDest{nullptr, d_out, ld});
 }
 
 }  // namespace srx
@@ -290,66 +377,7 @@ void srx_pca_model_free(srx_pca_model* p) {
 
 int32_t srx_pca_transform(srx_pca_model* p, srx_mat* q, const uint64_t* feat, double target_sum, int32_t transform,
                           double* scores_out) {
-    if (!p || !q) return fail(p ? p->ctx : q ? q->ctx : nullptr, SRX_E_ARG, "srx_pca_transform: null model or query");
-    srx_ctx* ctx = q->ctx;
-    if (p->ctx != ctx) return fail(ctx, SRX_E_ARG, "srx_pca_transform: model and query live on different contexts");
-    if (transform & ~(SRX_BACKED_NORMALIZE | SRX_BACKED_LOG1P)) return fail(ctx, SRX_E_ARG, "srx_pca_transform: bad transform bits %d", transform);
-    SRX_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t k = p->k;
-    const uint64_t n_cells = q->csc ? q->n_cols : q->n_rows, n_genes = q->csc ? q->n_rows : q->n_cols;
-    if (!feat) {
-        if (!p->has_sel) return fail(ctx, SRX_E_ARG, "srx_pca_transform: feat == NULL needs a model that knows its feature ids");
-        SRX_TRY(model_sel(p));
-    }
-    const uint64_t* fm = feat ? feat : p->sel.data();
-    // the present genes in ascending query order (the compacted columns' order) and the model row of each
-    std::vector<std::pair<uint64_t, int32_t>> present;
-    present.reserve(k);
-    for (uint64_t i = 0; i < k; ++i) {
-        if (fm[i] == UINT64_MAX) continue;
-        if (fm[i] >= n_genes) return fail(ctx, SRX_E_BOUNDS, "srx_pca_transform: feat[%llu] = %llu out of bounds (%llu genes)",
-                                          (unsigned long long)i, (unsigned long long)fm[i], (unsigned long long)n_genes);
-        present.emplace_back(fm[i], (int32_t)i);
-    }
-    std::sort(present.begin(), present.end());
-    for (size_t s = 1; s < present.size(); ++s)
-        if (present[s].first == present[s - 1].first)
-            return fail(ctx, SRX_E_ARG, "srx_pca_transform: query column %llu named twice in feat", (unsigned long long)present[s].first);
-    if (!scores_out && n_cells) return fail(ctx, SRX_E_ARG, "srx_pca_transform: null scores_out");
-    if (n_cells == 0) return SRX_OK;
-    std::vector<uint64_t> genes(present.size());
-    std::vector<int32_t> row_of_slot(present.size());
-    for (size_t s = 0; s < present.size(); ++s) {
-        genes[s] = present[s].first;
-        row_of_slot[s] = present[s].second;
-    }
-    // the matrix the compaction reads: the query itself, the CSR of a CSC query (device transpose, as srx_pca), or — one of the
-    // two transform bits alone — a copy transformed in place by the separate calls; both bits are applied on the fly
-    const bool do_norm = (transform & SRX_BACKED_NORMALIZE) != 0, do_log = (transform & SRX_BACKED_LOG1P) != 0;
-    srx_mat* own = nullptr;
-    int32_t rc = SRX_OK;
-    if (q->csc) rc = transpose_device(q, &own);
-    else if (do_norm != do_log) rc = srx_matrix_clone(q, &own);
-    srx_mat* m = own ? own : q;
-    RowXf xf;
-    if (rc == SRX_OK && do_norm && do_log) {
-        double* rs = nullptr;
-        rc = scratch(ctx, "pcat_rowsum", (m->n_rows ? m->n_rows : 1) * sizeof(double), (void**)&rs);
-        if (rc == SRX_OK) rc = launch_row_sums(m, rs);
-        xf.row_sum = rs;
-        xf.target = target_sum;
-    } else if (rc == SRX_OK && do_norm) {
-        rc = srx_normalize_total_inplace(m, target_sum, SRX_ROW);
-    } else if (rc == SRX_OK && do_log) {
-        rc = srx_log1p_inplace(m);
-    }
-    if (rc == SRX_OK) {
-        Range r_("srx:pca_transform");
-        rc = is_f32(m) ? model_scores<float>(p, m, genes, row_of_slot, xf, scores_out)
-                       : model_scores<double>(p, m, genes, row_of_slot, xf, scores_out);
-    }
-    if (own) srx_matrix_free(own);
-    return rc;
+    return pca_transform_into(p, q, feat, target_sum, transform, ScoreDest{scores_out, nullptr, 0});
 }
 
 }  // extern "C"

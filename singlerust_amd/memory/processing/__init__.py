@@ -9,6 +9,7 @@ from ... import _ffi as F
 from ...anndata import DeviceCsr, Direction, FlexValue, IMAnnData
 from . import dim_red
 from .diffmap import diffmap, diffmap_csr, dpt, dpt_from, graph_diffmap, graph_transitions
+from .doublets import Doublets, doublet_scores_knn, doublets_threshold, scrublet, simulate_doublets
 from .harmony import Harmony, encode_batches, harmony_integrate, harmony_points
 from .louvain import graph_labels, louvain, louvain_csr
 from .markers import group_moments, rank_genes_groups
