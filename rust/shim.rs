@@ -790,6 +790,75 @@ pub mod processing_free {
             Ok((Array2::from_shape_vec((n_q, n_neighbors), idx)?, Array2::from_shape_vec((n_q, n_neighbors), dist)?))
         }
 
+        /// Approximate k-NN of the cells through an inverted-file index over the resident scores (srx_knn_index_result, then
+        /// srx_knn_index_search in the self form without self): the k nearest among the members of the `n_probe` nearest
+        /// of `n_lists` lists, exact within them.  0 for `n_lists` / `n_probe` takes the defaults (round(4 sqrt(n)), 20);
+        /// `n_pcs` = 0 uses every component.  Returns what `neighbors` returns.
+        pub fn neighbors_approx(adata: &IMAnnData, n_neighbors: usize, n_pcs: usize, n_lists: usize, n_probe: usize)
+                                -> anyhow::Result<(Array2<u32>, Array2<f64>)> {
+            let (n, k) = (adata.n_obs(), n_neighbors);
+            let iopts = SrxIvfOpts { n_lists: n_lists as i32, train_iters: 10, seed: 0, max_train_points: 0 };
+            let opts = SrxKnnOpts { k: k as i32, n_dims: 0, include_self: 0, reserved: 0 };
+            let mut idx = vec![0u32; n * k];
+            let mut dist = vec![0.0f64; n * k];
+            with_resident(adata, |x| {
+                let mut ix: *mut SrxKnnIndex = null_mut();
+                x.ctx.check(unsafe { srx_knn_index_result(x.mat, n_pcs as i32, &iopts, &mut ix) })?;
+                let rc = unsafe {
+                    srx_knn_index_search(ix, std::ptr::null(), 0, &opts, n_probe as i32,
+                                         if idx.is_empty() { null_mut() } else { idx.as_mut_ptr() },
+                                         if dist.is_empty() { null_mut() } else { dist.as_mut_ptr() }, null_mut())
+                };
+                unsafe { srx_knn_index_free(ix) };
+                x.ctx.check(rc)
+            })?;
+            Ok((Array2::from_shape_vec((n, k), idx)?, Array2::from_shape_vec((n, k), dist)?))
+        }
+        /// The weighted graph of that approximate list (srx_neighbors_index): the list never leaves the device.
+        pub fn neighbors_approx_graph(adata: &IMAnnData, n_neighbors: usize, n_pcs: usize, n_lists: usize, n_probe: usize)
+                                      -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>)> {
+            let iopts = SrxIvfOpts { n_lists: n_lists as i32, train_iters: 10, seed: 0, max_train_points: 0 };
+            let opts = SrxKnnOpts { k: n_neighbors as i32, n_dims: 0, include_self: 0, reserved: 0 };
+            with_resident(adata, |x| {
+                let mut ix: *mut SrxKnnIndex = null_mut();
+                x.ctx.check(unsafe { srx_knn_index_result(x.mat, n_pcs as i32, &iopts, &mut ix) })?;
+                let mut g: *mut SrxGraph = null_mut();
+                let rc = unsafe { srx_neighbors_index(ix, &opts, n_probe as i32, null_mut(), &mut g) };
+                unsafe { srx_knn_index_free(ix) };
+                x.ctx.check(rc)?;
+                let out = graph_to_host(x.ctx, g);
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        /// The index over caller-supplied points (srx_knn_index_points; `centroids` None: trained): its centroids, list
+        /// offsets and list members (srx_knn_index_fetch) with the counters of srx_knn_index_info_get.
+        pub fn knn_index_of(points: &Array2<f64>, centroids: Option<&Array2<f64>>, n_lists: usize)
+                            -> anyhow::Result<(Array2<f64>, Vec<u64>, Vec<u32>, SrxIvfInfo)> {
+            let (n, d) = points.dim();
+            let p: Vec<f64> = points.iter().copied().collect();                    // row-major
+            let c: Option<Vec<f64>> = centroids.map(|c| c.iter().copied().collect());
+            let n_lists = centroids.map_or(n_lists, |c| c.dim().0);
+            let iopts = SrxIvfOpts { n_lists: n_lists as i32, train_iters: 10, seed: 0, max_train_points: 0 };
+            with_ctx(|ctx| {
+                let mut ix: *mut SrxKnnIndex = null_mut();
+                ctx.check(unsafe {
+                    srx_knn_index_points(ctx.0, p.as_ptr(), n as u64, d as u64, &iopts,
+                                         c.as_ref().map_or(std::ptr::null(), |v| v.as_ptr()), &mut ix)
+                })?;
+                let mut info: SrxIvfInfo = unsafe { std::mem::zeroed() };
+                let mut rc = unsafe { srx_knn_index_info_get(ix, &mut info) };
+                let l = info.n_lists as usize;
+                let (mut cent, mut off, mut mem) = (vec![0.0f64; l * d], vec![0u64; l + 1], vec![0u32; n]);
+                if rc == 0 {
+                    rc = unsafe { srx_knn_index_fetch(ix, cent.as_mut_ptr(), off.as_mut_ptr(), mem.as_mut_ptr()) };
+                }
+                unsafe { srx_knn_index_free(ix) };
+                ctx.check(rc)?;
+                Ok((Array2::from_shape_vec((l, d), cent)?, off, mem, info))
+            })
+        }
+
         /// The weighted neighbour graph of the cells (srx_neighbors_result): exact k-NN over the resident scores, then
         /// scanpy's `pp.neighbors` weights (umap-learn's fuzzy_simplicial_set restated for rows without self; not compared
         /// with either package) — all on the device.  Returns (distances, connectivities), both n_obs x n_obs CSR.

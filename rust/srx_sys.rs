@@ -112,6 +112,7 @@ pub const SRX_K_COUNT_: i32 = 13;
 #[repr(C)] pub struct SrxMat { _private: [u8; 0] }      // opaque `srx_mat`
 #[repr(C)] pub struct SrxPcaModel { _private: [u8; 0] }      // opaque `srx_pca_model`
 #[repr(C)] pub struct SrxGraph { _private: [u8; 0] }      // opaque `srx_graph`
+#[repr(C)] pub struct SrxKnnIndex { _private: [u8; 0] }      // opaque `srx_knn_index`
 #[repr(C)] pub struct SrxMarkers { _private: [u8; 0] }      // opaque `srx_markers`
 #[repr(C)] pub struct SrxTsne { _private: [u8; 0] }      // opaque `srx_tsne`
 #[repr(C)] pub struct SrxHarmony { _private: [u8; 0] }      // opaque `srx_harmony`
@@ -214,6 +215,47 @@ pub struct SrxGraphInfo {      // `srx_graph_info`
     pub rows_all_zero: u64,
     pub entries_dropped: u64,
     pub max_row_nnz: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxIvfOpts {      // `srx_ivf_opts`
+    pub n_lists: i32,
+    pub train_iters: i32,
+    pub seed: u64,
+    pub max_train_points: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxIvfInfo {      // `srx_ivf_info`
+    pub n_ref: u64,
+    pub n_train: u64,
+    pub d: u32,
+    pub n_lists: u32,
+    pub train_iters: u32,
+    pub reserved: u32,
+    pub min_list: u64,
+    pub max_list: u64,
+    pub empty_lists: u64,
+    pub inertia: f64,
+    pub ms_train: f64,
+    pub ms_assign: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxIvfSearchInfo {      // `srx_ivf_search_info`
+    pub n_query: u64,
+    pub k: u32,
+    pub n_probe: u32,
+    pub n_candidates: u32,
+    pub reserved: u32,
+    pub rows_certified: u64,
+    pub rows_rescanned: u64,
+    pub rows_exhaustive: u64,
+    pub pairs: u64,
+    pub points_scanned: u64,
 }
 
 #[repr(C)]
@@ -573,6 +615,18 @@ extern "C" {
     pub fn srx_graph_fetch(g: *mut SrxGraph, which: i32, indptr: *mut u64, indices: *mut u32, data: *mut f64) -> i32;
     pub fn srx_graph_fetch_scales(g: *mut SrxGraph, rho: *mut f64, sigma: *mut f64) -> i32;
     pub fn srx_graph_free(g: *mut SrxGraph);
+    pub fn srx_knn_index_result(m: *mut SrxMat, n_dims: i32, opts: *const SrxIvfOpts, out: *mut *mut SrxKnnIndex) -> i32;
+    pub fn srx_knn_index_points(ctx: *mut SrxCtx, ref_: *const f64, n_ref: u64, d: u64, opts: *const SrxIvfOpts,
+                                centroids: *const f64, out: *mut *mut SrxKnnIndex) -> i32;
+    pub fn srx_knn_index_info_get(ix: *const SrxKnnIndex, info: *mut SrxIvfInfo) -> i32;
+    pub fn srx_knn_index_fetch(ix: *mut SrxKnnIndex, centroids: *mut f64, list_offsets: *mut u64,
+                               list_members: *mut u32) -> i32;
+    pub fn srx_knn_index_search(ix: *mut SrxKnnIndex, query: *const f64, n_query: u64, opts: *const SrxKnnOpts,
+                                n_probe: i32, indices_out: *mut u32, distances_out: *mut f64,
+                                info: *mut SrxIvfSearchInfo) -> i32;
+    pub fn srx_neighbors_index(ix: *mut SrxKnnIndex, opts: *const SrxKnnOpts, n_probe: i32,
+                               info: *mut SrxIvfSearchInfo, out: *mut *mut SrxGraph) -> i32;
+    pub fn srx_knn_index_free(ix: *mut SrxKnnIndex);
     pub fn srx_louvain(g: *mut SrxGraph, opts: *const SrxLouvainOpts, labels_out: *mut u32,
                        info: *mut SrxLouvainInfo) -> i32;
     pub fn srx_louvain_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,

@@ -158,6 +158,24 @@ class GraphInfo(C.Structure):      # srx_graph_info
                 ("max_row_nnz", C.c_uint64)]
 
 
+class IvfOpts(C.Structure):      # srx_ivf_opts
+    _fields_ = [("n_lists", C.c_int32), ("train_iters", C.c_int32), ("seed", C.c_uint64),
+                ("max_train_points", C.c_uint64)]
+
+
+class IvfInfo(C.Structure):      # srx_ivf_info
+    _fields_ = [("n_ref", C.c_uint64), ("n_train", C.c_uint64), ("d", C.c_uint32), ("n_lists", C.c_uint32),
+                ("train_iters", C.c_uint32), ("reserved_", C.c_uint32), ("min_list", C.c_uint64),
+                ("max_list", C.c_uint64), ("empty_lists", C.c_uint64), ("inertia", C.c_double),
+                ("ms_train", C.c_double), ("ms_assign", C.c_double)]
+
+
+class IvfSearchInfo(C.Structure):      # srx_ivf_search_info
+    _fields_ = [("n_query", C.c_uint64), ("k", C.c_uint32), ("n_probe", C.c_uint32), ("n_candidates", C.c_uint32),
+                ("reserved_", C.c_uint32), ("rows_certified", C.c_uint64), ("rows_rescanned", C.c_uint64),
+                ("rows_exhaustive", C.c_uint64), ("pairs", C.c_uint64), ("points_scanned", C.c_uint64)]
+
+
 class LouvainOpts(C.Structure):      # srx_louvain_opts
     _fields_ = [("resolution", C.c_double), ("min_gain", C.c_double), ("max_levels", C.c_int32),
                 ("max_sweeps", C.c_int32)]
@@ -345,6 +363,14 @@ SIGNATURES = {
     "srx_graph_fetch": (C.c_int32, [P, C.c_int32, P, P, P]),
     "srx_graph_fetch_scales": (C.c_int32, [P, P, P]),
     "srx_graph_free": (None, [P]),
+    "srx_knn_index_result": (C.c_int32, [P, C.c_int32, C.POINTER(IvfOpts), C.POINTER(P)]),
+    "srx_knn_index_points": (C.c_int32, [P, P, C.c_uint64, C.c_uint64, C.POINTER(IvfOpts), P, C.POINTER(P)]),
+    "srx_knn_index_info_get": (C.c_int32, [P, C.POINTER(IvfInfo)]),
+    "srx_knn_index_fetch": (C.c_int32, [P, P, P, P]),
+    "srx_knn_index_search": (C.c_int32, [P, P, C.c_uint64, C.POINTER(KnnOpts), C.c_int32, P, P,
+                                         C.POINTER(IvfSearchInfo)]),
+    "srx_neighbors_index": (C.c_int32, [P, C.POINTER(KnnOpts), C.c_int32, C.POINTER(IvfSearchInfo), C.POINTER(P)]),
+    "srx_knn_index_free": (None, [P]),
     "srx_louvain": (C.c_int32, [P, C.POINTER(LouvainOpts), P, C.POINTER(LouvainInfo)]),
     "srx_louvain_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(LouvainOpts), P, C.POINTER(LouvainInfo)]),
     "srx_graph_labels_fetch": (C.c_int32, [P, P]),

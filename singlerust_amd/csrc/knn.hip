@@ -26,29 +26,13 @@
 //     t_k + eps_row < tau,      t_k = (k-th exact squared distance) - |q|^2:
 // strictly, and by a margin of at least 0.01 eps_row, so no point left out can tie with the k-th one even in rounded f64.
 #include "common.hpp"
+#include "knn_internal.hpp"
 #include "pca_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace srx {
-
-constexpr int kKnnSlack = 8;         // K' = k + 8 (profiles/knn.md: share of recomputed rows)
-constexpr int kKnnMaxK = 64;
-constexpr int kKnnQB = 128;          // queries of a workgroup: 4 waves x 32 columns of the 32x32 MFMA tile
-constexpr int kKnnPad = 64;          // points are padded to whole reference tiles (the largest RT)
-constexpr int kKnnCapMax = 120;      // kept + pending entries per query in LDS (two per lane in a merge)
-constexpr uint32_t kKnnNone = 0xFFFFFFFFu;
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-// f32 -> u32 with the same order (negative scores occur: t = dist^2 - |q|^2)
-__device__ __forceinline__ uint32_t f32_key(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // ---- centre, finiteness ------------------------------------------------------------------------------------------------
 // grid.x blocks of 256 threads; thread t owns column t % dpow (dpow = d rounded up to a power of two <= 256) and walks the rows
@@ -110,33 +94,7 @@ __global__ void __launch_bounds__(256) k_knn_prepare(const double* __restrict__ 
     if (rmax2_bits && p < n) atomicMax(rmax2_bits, (unsigned long long)__double_as_longlong(nrm));
 }
 
-// ---- candidate pass ----------------------------------------------------------------------------------------------------
-// One query's entries in LDS: u64 keys (ordered score bits << 32 | reference index), so (score, index) order is one compare.
-// Merge of the n <= 120 entries of query slot `qs` by one wave: every lane ranks its (up to) two entries against all,
-// the KP lowest go to their rank (sorted), the count falls to min(n, KP); returns the score that is now the bound.
-__device__ __forceinline__ void knn_merge(unsigned long long* __restrict__ keys, int* __restrict__ cnt, float* __restrict__ tau,
-                                          int qs, int CAP, int KP) {
-    const int lane = lane_id();
-    unsigned long long* e = keys + (size_t)qs * CAP;
-    const int n = cnt[qs];
-    const unsigned long long e0 = lane < n ? e[lane] : ~0ull, e1 = lane + 64 < n ? e[lane + 64] : ~0ull;
-    int r0 = 0, r1 = 0;
-    for (int m = 0; m < n; ++m) {
-        const unsigned long long o = e[m];      // all lanes read the same word: a broadcast
-        r0 += o < e0;
-        r1 += o < e1;
-    }
-    wave_lds_sync();
-    if (lane < n && r0 < KP) e[r0] = e0;         // keys are distinct (distinct indices): ranks are a permutation
-    if (lane + 64 < n && r1 < KP) e[r1] = e1;
-    if (n > KP) {
-        if (lane < n && r0 == KP - 1) tau[qs] = key_f32((uint32_t)(e0 >> 32));
-        if (lane + 64 < n && r1 == KP - 1) tau[qs] = key_f32((uint32_t)(e1 >> 32));
-        if (lane == 0) cnt[qs] = KP;
-    }
-    wave_lds_sync();
-}
-
+// ---- candidate pass (the keys of one query in LDS and their merge: knn_internal.hpp) -------------------------------------
 // K: padded coordinates (even, > d); RT: references per tile.  Dynamic LDS: 2 tiles | keys 128 x CAP | cnt 128 | tau 128.
 // self_skip: query i is reference i and may not list itself.
 template <int K, int RT>
@@ -248,18 +206,7 @@ __global__ void __launch_bounds__(256) k_knn_candidates(const float* __restrict_
     }
 }
 
-// ---- f64 selection -----------------------------------------------------------------------------------------------------
-// The reported squared distance: the differences of the ORIGINAL coordinates, summed in coordinate order.
-__device__ __forceinline__ double knn_dist2(const double* __restrict__ a, const double* __restrict__ b, int d) {
-    double s = 0.0;
-    for (int c = 0; c < d; ++c) {
-        const double t = a[c] - b[c];
-        s += t * t;
-    }
-    return s;
-}
-__device__ __forceinline__ bool knn_less(double da, uint32_t ia, double db, uint32_t ib) { return da < db || (da == db && ia < ib); }
-
+// ---- f64 selection (knn_dist2, knn_less: knn_internal.hpp) -------------------------------------------------------------
 // One wave per query row.  ALL = false: the row's KP candidates; ALL = true: row rows[..] against every reference.
 // The wave keeps at most k + 64 entries in LDS: 64 references at a time, those below the k-th kept one are appended, the
 // list is ranked by (distance, index) and cut back to k.  ALL = false also evaluates the certificate and lists the rows
@@ -340,14 +287,6 @@ __global__ void __launch_bounds__(256) k_knn_exact(const double* __restrict__ re
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-struct KnnArgs {
-    const double *d_ref, *d_qry;     // device, row-major with pitches ld_r / ld_q (doubles); d_qry == d_ref for a self graph
-    uint64_t n_ref, n_query;
-    size_t ld_r, ld_q;
-    int d;
-    bool self;
-};
-
 template <int K, int RT>
 static int32_t launch_candidates(srx_ctx* ctx, const float* ref_t, uint64_t n_ref_pad, const float* qry_t, uint64_t n_query,
                                  uint64_t n_query_pad, int d, int KP, int CAP, int self_skip, uint32_t* cand, float* tau) {
@@ -360,15 +299,26 @@ static int32_t launch_candidates(srx_ctx* ctx, const float* ref_t, uint64_t n_re
     return SRX_OK;
 }
 
-static int32_t knn_device(srx_ctx* ctx, const KnnArgs& a, const srx_knn_opts* opts, uint32_t* indices_out, double* distances_out,
-                          srx_knn_info* info) {
+int32_t knn_exact_rows(srx_ctx* ctx, const KnnArgs& a, int k, int self_skip, const uint32_t* d_rows, uint64_t n_rows,
+                       uint32_t* d_idx, double* d_dist) {
+    if (n_rows == 0) return SRX_OK;
+    hipLaunchKernelGGL(k_knn_exact<true>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, ctx->stream, a.d_ref, a.n_ref, a.ld_r,
+                       a.d_qry, a.n_query, a.ld_q, a.d, k, 0, self_skip, (const uint32_t*)nullptr, (const float*)nullptr,
+                       (const double*)nullptr, (const unsigned long long*)nullptr, 0, d_rows, n_rows, d_idx, d_dist,
+                       (uint32_t*)nullptr, (unsigned int*)nullptr);
+    SRX_HIP(ctx, hipGetLastError());
+    return SRX_OK;
+}
+
+int32_t knn_device(srx_ctx* ctx, const KnnArgs& a, const srx_knn_opts* opts, uint32_t* indices_out, double* distances_out,
+                   srx_knn_info* info) {
     const int k = opts->k, d = a.d;
     const uint64_t admissible = a.n_ref - ((a.self && !opts->include_self) ? 1 : 0);
     const int self_skip = a.self && !opts->include_self;
     const int KP = (int)std::min<uint64_t>((uint64_t)k + kKnnSlack, std::max<uint64_t>(admissible, 1));
     const int CAP = std::min(2 * KP + 32, kKnnCapMax);
     // padded coordinate count: d + 1 (the norm) rounded up to the next instantiated width
-    const int K = d < 8 ? 8 : d < 20 ? 20 : d < 36 ? 36 : d < 52 ? 52 : d < 68 ? 68 : 132;
+    const int K = knn_padded_width(d);
     const uint64_t n_ref_pad = (a.n_ref + kKnnPad - 1) / kKnnPad * kKnnPad, n_query_pad = (a.n_query + kKnnPad - 1) / kKnnPad * kKnnPad;
     const int n_part = (int)std::min<uint64_t>(1024, (a.n_ref + 255) / 256);
     int dpow = 1;
@@ -436,13 +386,7 @@ static int32_t knn_device(srx_ctx* ctx, const KnnArgs& a, const srx_knn_opts* op
                            d_fail, d_fail_n);
         SRX_HIP(ctx, hipGetLastError());
         SRX_TRY(d2h(ctx, &n_fail, d_fail_n, 4));
-        if (n_fail) {
-            hipLaunchKernelGGL(k_knn_exact<true>, dim3((n_fail + 3) / 4), dim3(256), 0, st, a.d_ref, a.n_ref, a.ld_r, a.d_qry,
-                               a.n_query, a.ld_q, d, k, KP, self_skip, (const uint32_t*)nullptr, (const float*)nullptr,
-                               (const double*)nullptr, (const unsigned long long*)nullptr, K, d_fail, (uint64_t)n_fail, d_idx,
-                               d_dist, (uint32_t*)nullptr, (unsigned int*)nullptr);
-            SRX_HIP(ctx, hipGetLastError());
-        }
+        SRX_TRY(knn_exact_rows(ctx, a, k, self_skip, d_fail, n_fail, d_idx, d_dist));
     }
     if (indices_out) SRX_TRY(d2h(ctx, indices_out, d_idx, a.n_query * (size_t)k * 4));
     if (distances_out) SRX_TRY(d2h(ctx, distances_out, d_dist, a.n_query * (size_t)k * 8));
@@ -461,8 +405,8 @@ static int32_t knn_device(srx_ctx* ctx, const KnnArgs& a, const srx_knn_opts* op
 }
 
 // argument checks shared by both entry points; d_full: coordinates per point, d: those used
-static int32_t knn_check(srx_ctx* ctx, const srx_knn_opts* opts, uint64_t n_ref, uint64_t n_query, uint64_t d_full, bool self,
-                         int* d_out) {
+int32_t knn_check(srx_ctx* ctx, const srx_knn_opts* opts, uint64_t n_ref, uint64_t n_query, uint64_t d_full, bool self,
+                  int* d_out) {
     if (!opts) return fail(ctx, SRX_E_ARG, "knn: null options");
     if (ctx->n_ranks > 1) return fail(ctx, SRX_E_ARG, "knn: rows are sharded; neighbours need all cells");
     if (opts->k < 1 || opts->k > kKnnMaxK) return fail(ctx, SRX_E_ARG, "knn: k = %d outside 1..%d", opts->k, kKnnMaxK);

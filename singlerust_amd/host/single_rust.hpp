@@ -514,6 +514,74 @@ inline KnnGraph knn_points(Context& ctx, const std::vector<double>& ref, const s
     return g;
 }
 
+// Approximate k-NN: an owning wrapper of an srx_knn_index (inverted-file index: centroids, lists, its own copy of the points).
+// search() is exact within the n_probe nearest lists; n_probe == n_lists returns what knn_points returns.
+class KnnIndex {
+public:
+    // over the scores the last PCA on `a` left on the device (srx_knn_index_result); trained centroids
+    static KnnIndex of(const IMAnnData& a, int n_pcs = 0, const srx_ivf_opts& opts = srx_ivf_opts{0, 10, 0, 0}) {
+        KnnIndex ix(a.ctx());
+        a.ctx().check(srx_knn_index_result(a.x(), n_pcs, &opts, &ix.h_));
+        return ix;
+    }
+    // over caller-supplied points (row-major n x d); centroids empty: trained, else opts.n_lists x d taken as they are
+    static KnnIndex of_points(Context& ctx, const std::vector<double>& ref, std::size_t d, const std::vector<double>& centroids = {},
+                              srx_ivf_opts opts = srx_ivf_opts{0, 10, 0, 0}) {
+        if (d == 0 || ref.size() % d || centroids.size() % d) throw Error(SRX_E_ARG, "KnnIndex: sizes are not multiples of d");
+        if (!centroids.empty()) opts.n_lists = static_cast<std::int32_t>(centroids.size() / d);
+        KnnIndex ix(ctx);
+        ctx.check(srx_knn_index_points(ctx.handle(), ref.data(), ref.size() / d, d, &opts,
+                                       centroids.empty() ? nullptr : centroids.data(), &ix.h_));
+        return ix;
+    }
+    KnnIndex(KnnIndex&& o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    KnnIndex& operator=(KnnIndex&& o) noexcept {
+        std::swap(ctx_, o.ctx_);
+        std::swap(h_, o.h_);
+        return *this;
+    }
+    KnnIndex(const KnnIndex&) = delete;
+    KnnIndex& operator=(const KnnIndex&) = delete;
+    ~KnnIndex() { srx_knn_index_free(h_); }
+
+    srx_ivf_info info() const {
+        srx_ivf_info i{};
+        ctx_->check(srx_knn_index_info_get(h_, &i));
+        return i;
+    }
+    // an empty query: the self form.  n_probe 0: min(20, n_lists).
+    KnnGraph search(const std::vector<double>& query = {}, int k = 15, int n_probe = 0, bool include_self = false,
+                    srx_ivf_search_info* sinfo = nullptr) const {
+        const srx_ivf_info i = info();
+        if (query.size() % i.d) throw Error(SRX_E_ARG, "KnnIndex::search: the query is not a multiple of d");
+        KnnGraph g;
+        g.n_query = query.empty() ? i.n_ref : query.size() / i.d;
+        g.k = k > 0 ? static_cast<std::size_t>(k) : 0;
+        g.indices.resize(g.n_query * g.k);
+        g.distances.resize(g.n_query * g.k);
+        const srx_knn_opts o{k, 0, include_self ? 1 : 0, 0};
+        ctx_->check(srx_knn_index_search(h_, query.empty() ? nullptr : query.data(), g.n_query, &o, n_probe,
+                                         g.indices.empty() ? nullptr : g.indices.data(),
+                                         g.distances.empty() ? nullptr : g.distances.data(), sinfo));
+        return g;
+    }
+    // (centroids n_lists x d, list offsets n_lists + 1, list members n_ref)
+    void fetch(std::vector<double>& centroids, std::vector<std::uint64_t>& offsets, std::vector<std::uint32_t>& members) const {
+        const srx_ivf_info i = info();
+        centroids.resize(static_cast<std::size_t>(i.n_lists) * i.d);
+        offsets.resize(static_cast<std::size_t>(i.n_lists) + 1);
+        members.resize(i.n_ref);
+        ctx_->check(srx_knn_index_fetch(h_, centroids.data(), offsets.data(), members.data()));
+    }
+    srx_knn_index* handle() const { return h_; }
+    Context& ctx() const { return *ctx_; }
+
+private:
+    explicit KnnIndex(Context& ctx) : ctx_(&ctx) {}
+    Context* ctx_;
+    srx_knn_index* h_ = nullptr;
+};
+
 // The weighted neighbour graph (obsp["distances"], obsp["connectivities"]): an owning wrapper of an srx_graph.  Both matrices
 // stay on the device as CSR for the consumers of the graph; csr() copies one to the host.
 struct GraphCsr {
@@ -534,6 +602,13 @@ public:
         Graph g(a.ctx());
         const srx_knn_opts o{n_neighbors, n_pcs, 0, 0};
         a.ctx().check(srx_neighbors_result(a.x(), &o, &g.knn_info_, &g.h_));
+        return g;
+    }
+    // the self search of an inverted-file index, then the graph of that list (srx_neighbors_index); knn_info() stays zero
+    static Graph of_index(const KnnIndex& ix, int n_neighbors = 15, int n_probe = 0, srx_ivf_search_info* sinfo = nullptr) {
+        Graph g(ix.ctx());
+        const srx_knn_opts o{n_neighbors, 0, 0, 0};
+        ix.ctx().check(srx_neighbors_index(ix.handle(), &o, n_probe, sinfo, &g.h_));
         return g;
     }
     // the graph of a k-NN list (n x k row-major; no row names itself): srx_neighbors_from_knn

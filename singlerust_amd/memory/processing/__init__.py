@@ -13,7 +13,7 @@ from .doublets import Doublets, doublet_scores_knn, doublets_threshold, scrublet
 from .harmony import Harmony, encode_batches, harmony_integrate, harmony_points
 from .louvain import graph_labels, louvain, louvain_csr
 from .markers import group_moments, rank_genes_groups
-from .neighbors import connectivities_from_knn, knn_points, neighbors
+from .neighbors import KnnIndex, connectivities_from_knn, knn_index, knn_index_points, knn_points, neighbors, neighbors_approx
 from .tsne import Tsne, tsne, tsne_affinities, tsne_affinities_graph, tsne_embedding, tsne_forces, tsne_run
 from .umap import fit_ab, graph_embedding, umap, umap_csr
 

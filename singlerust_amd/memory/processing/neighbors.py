@@ -153,6 +153,126 @@ def neighbors(adata: IMAnnData, n_neighbors: int = 15, n_pcs=None, include_self:
     return adata.uns["neighbors"]
 
 
+class KnnIndex(OwnedHandle):
+    """Owning wrapper of an ``srx_knn_index``: the inverted-file index of the approximate search (centroids, lists, the
+    index's own copy of the points), all on the device."""
+
+    _free = "srx_knn_index_free"
+
+    def info(self) -> dict:
+        i = F.IvfInfo()
+        F.check(F.lib().srx_knn_index_info_get(self._h, C.byref(i)), self.ctx.handle)
+        return flat_info(i)
+
+    def fetch(self):
+        """(centroids f64 n_lists x d, list offsets uint64 n_lists + 1, list members uint32 n_ref)."""
+        i = self.info()
+        cent = np.zeros((i["n_lists"], i["d"]), dtype=np.float64)
+        off = np.zeros(i["n_lists"] + 1, dtype=np.uint64)
+        mem = np.zeros(i["n_ref"], dtype=np.uint32)
+        F.check(F.lib().srx_knn_index_fetch(self._h, F.ptr(cent), F.ptr(off), F.ptr(mem)), self.ctx.handle)
+        return cent, off, mem
+
+    def search(self, query=None, k: int = 15, n_probe: int = 0, include_self: bool = False, n_dims=None):
+        """Neighbours of every row of ``query`` (None: the self form) among the indexed points, from the ``n_probe`` nearest
+        lists (0: min(20, n_lists)).  Returns (indices uint32 n_query x k, distances f64, the ``srx_ivf_search_info`` dict)."""
+        i = self.info()
+        if query is not None:
+            query = np.ascontiguousarray(query, dtype=np.float64)
+            if query.ndim != 2 or query.shape[1] != i["d"]:
+                raise ValueError("query must be n_query x d with the d of the index")
+        nq = i["n_ref"] if query is None else query.shape[0]
+        k = int(k)
+        opts = F.KnnOpts(k, int(n_dims or 0), int(bool(include_self)), 0)
+        info = F.IvfSearchInfo()
+        idx = np.zeros((nq, max(k, 0)), dtype=np.uint32)
+        dist = np.zeros((nq, max(k, 0)), dtype=np.float64)
+        F.check(F.lib().srx_knn_index_search(self._h, None if query is None else C.c_void_p(query.ctypes.data or 1), nq,
+                                             C.byref(opts), int(n_probe), F.ptr(idx) if idx.size else None,
+                                             F.ptr(dist) if dist.size else None, C.byref(info)), self.ctx.handle)
+        return idx, dist, flat_info(info)
+
+    def graph(self, k: int = 15, n_probe: int = 0):
+        """The weighted graph of the self search (``srx_neighbors_index``): (``Graph``, search info dict)."""
+        opts = F.KnnOpts(int(k), 0, 0, 0)
+        info = F.IvfSearchInfo()
+        h = C.c_void_p()
+        F.check(F.lib().srx_neighbors_index(self._h, C.byref(opts), int(n_probe), C.byref(info), C.byref(h)), self.ctx.handle)
+        return Graph(self.ctx, h), flat_info(info)
+
+
+def _ivf_opts(n_lists, train_iters, seed, max_train_points):
+    return F.IvfOpts(int(n_lists), int(train_iters), int(seed), int(max_train_points))
+
+
+def knn_index_points(ctx, ref, centroids=None, n_lists: int = 0, train_iters: int = 10, seed: int = 0,
+                     max_train_points: int = 0) -> KnnIndex:
+    """The index over the rows of ``ref`` (n x d f64).  ``centroids`` (n_lists x d): taken as they are; None: trained
+    (``srx_knn_index_points``)."""
+    ref = np.ascontiguousarray(ref, dtype=np.float64)
+    if ref.ndim != 2:
+        raise ValueError("ref must be n x d")
+    if centroids is not None:
+        centroids = np.ascontiguousarray(centroids, dtype=np.float64)
+        if centroids.ndim != 2 or centroids.shape[1] != ref.shape[1]:
+            raise ValueError("centroids must be n_lists x d with the d of ref")
+        n_lists = centroids.shape[0]
+    opts = _ivf_opts(n_lists, train_iters, seed, max_train_points)
+    h = C.c_void_p()
+    F.check(F.lib().srx_knn_index_points(ctx.handle, F.ptr(ref) if ref.size else None, ref.shape[0], ref.shape[1], C.byref(opts),
+                                         None if centroids is None else C.c_void_p(centroids.ctypes.data or 1), C.byref(h)),
+            ctx.handle)
+    return KnnIndex(ctx, h)
+
+
+def knn_index(adata: IMAnnData, n_pcs=None, n_lists: int = 0, train_iters: int = 10, seed: int = 0,
+              max_train_points: int = 0) -> KnnIndex:
+    """The index over the scores the last ``pca_inplace`` left on the device (``srx_knn_index_result``)."""
+    opts = _ivf_opts(n_lists, train_iters, seed, max_train_points)
+    h = C.c_void_p()
+    ctx = adata.x().ctx
+    F.check(F.lib().srx_knn_index_result(adata.x().handle, int(n_pcs or 0), C.byref(opts), C.byref(h)), ctx.handle)
+    return KnnIndex(ctx, h)
+
+
+def neighbors_approx(adata: IMAnnData, n_neighbors: int = 15, n_pcs=None, n_lists: int = 0, n_probe: int = 0,
+                     connectivities: bool = False, knn_lists: bool = False, train_iters: int = 10, seed: int = 0,
+                     max_train_points: int = 0) -> dict:
+    """``neighbors`` through an inverted-file index of the scores (``srx_knn_index_result`` + ``srx_knn_index_search`` /
+    ``srx_neighbors_index``): the k nearest among the members of the ``n_probe`` nearest of ``n_lists`` lists, exact within
+    them.  Fills the keys ``neighbors`` fills, with ``"method": "ivf"`` and the index and search counters in
+    ``uns["neighbors"]``; the index is freed before returning."""
+    k = int(n_neighbors)
+    ix = knn_index(adata, n_pcs, n_lists, train_iters, seed, max_train_points)
+    try:
+        params = {"n_neighbors": k, "n_pcs": None if n_pcs is None else int(n_pcs), "include_self": False,
+                  "metric": "euclidean", "method": "ivf", "n_lists": ix.info()["n_lists"]}
+        if connectivities:
+            g, info = ix.graph(k, n_probe)
+            old = getattr(adata, "_graph", None)
+            if old is not None:
+                old.free()
+            adata._graph = g
+            adata.obsp["distances"] = g.matrix(F.GRAPH_DISTANCES)
+            adata.obsp["connectivities"] = g.matrix(F.GRAPH_CONNECTIVITIES)
+            if knn_lists:
+                _, indices, data = g.fetch(F.GRAPH_DISTANCES)
+                idx, dist = indices.reshape(-1, k), data.reshape(-1, k)
+                order = np.lexsort((idx, dist), axis=1)
+                adata.obsm["knn_indices"] = np.take_along_axis(idx, order, axis=1)
+                adata.obsm["knn_distances"] = np.take_along_axis(dist, order, axis=1)
+            adata.uns["neighbors"] = {"params": params, "info": info, "index": ix.info(), "graph": g.info()}
+        else:
+            idx, dist, info = ix.search(None, k, n_probe)
+            adata.obsm["knn_indices"] = idx
+            adata.obsm["knn_distances"] = dist
+            adata.uns["neighbors"] = {"params": params, "info": info, "index": ix.info()}
+        params["n_probe"] = info["n_probe"]
+    finally:
+        ix.free()
+    return adata.uns["neighbors"]
+
+
 def knn_points(ctx, ref, query=None, k: int = 15, n_dims=None, include_self: bool = False):
     """Neighbours of every row of ``query`` among the rows of ``ref`` (n x d f64 arrays; ``query`` None: the self graph of
     ``ref``).  Returns (indices uint32 n_query x k, distances f64, info dict)."""
