@@ -39,7 +39,8 @@ extern "C" {
                                   (kernel class 12) and srx_louvain / srx_louvain_csr / srx_graph_labels_fetch (no class of
                                   their own: the time is in srx_louvain_info.ms) and srx_group_moments / srx_rank_genes_groups[_graph] /
                                   srx_markers_* (no class either: srx_markers_info.ms) and srx_diffmap[_csr] /
-                                  srx_graph_diffmap_fetch / srx_graph_transitions_fetch / srx_dpt[_from] (srx_diffmap_info.ms) */
+                                  srx_graph_diffmap_fetch / srx_graph_transitions_fetch / srx_dpt[_from] (srx_diffmap_info.ms) and
+                                  srx_iterate_op (the dense solver's kernels one at a time: tests and diagnostics) */
 
 typedef struct srx_ctx srx_ctx;   /* one GPU + stream + (optional) RCCL communicator      */
 typedef struct srx_mat srx_mat;   /* device-resident CSR (the `X` of an IMAnnData)        */
@@ -1227,6 +1228,54 @@ void    srx_doublets_free(srx_doublets* h);
  * ascending; any output may be NULL. */
 int32_t srx_spmm(srx_mat* m, const uint64_t* sel, uint64_t k, const double* panel, double* y_out,
                  double* t_out, double* gram_out);
+
+/* ONE operation of the dense k x 64 subspace iteration on caller-supplied host arrays (f64, row-major): a test and diagnostics
+ * entry with NO stability promise (additive: detected by symbol, the ABI version stays).  The arrays are uploaded into fresh
+ * device buffers of exactly their sizes, the kernel(s) are launched as the solver launches them, the stream is drained and the
+ * buffers come back into the same arrays.  Every k x 64 block is allocated with 8 more rows that hold a sentinel; `tail_touched`
+ * says whether any of them changed.  Slots an operation does not name may be NULL.
+ *
+ *   op       variant                            reads                                        writes
+ *   APPLY    -                                  c (k x k), blk[0] = W, blk[1] = Wp           blk[1] (Wp += C^T W)
+ *   GRAM1    -                                  blk[0] = A, blk[1] = B, sm[0] = H            sm[0] (H += A^T B)
+ *   GRAM2    -                                  blk[0] = A, blk[1] = B                       sm[0] = A^T B, sm[1] = B^T B
+ *   CHOL     0 plain, 1 shifted, 2 mfma         sm[0] = G, n                                 sm[1] = R, vec[0] = dinv, xi (mfma), sm[0], status[0]
+ *   TRSM     0 rows, 1 mfma                     blk[0] = source, sm[1] = R, vec[0] / xi      blk[1] = W, blk[2..4] = z0..z2
+ *   EIG      -                                  sm[0] = H, n, off_tol2, n_want               sm[1] = U, vec[0] = theta, sm[0], status[0..1]
+ *   RITZ     -                                  blk[0] = W, blk[1] = Wp, sm[1] = U, vec[0]   blk[2] = A1, blk[3] = A2, blk[1], vec[1] = rho,
+ *                                               = theta, n_pc, l_act                         vec[2] = colmax, out[0..5]
+ *   CHEB     0 first  (blk: A1, A2)             vec[0] = theta, l_act, d (scale)             the blocks
+ *            1 first2 (blk: Z, W, cur, prev)
+ *            2 step   (blk: Z, cur, prev)
+ *            3 scale  (blk: Y)
+ * With SRX_IT_ALIAS_B, GRAM1 / GRAM2 pass the device copy of blk[0] as B too.  TRSM passes z_i when SRX_IT_Z0 << i is set (blk[2 + i]
+ * is then uploaded and comes back), the SOURCE itself as z0 with SRX_IT_Z0_IS_SRC, and the source as the destination with
+ * SRX_IT_SRC_IS_W (the result still comes back in blk[1]).  RITZ passes zero_wp = 1 with SRX_IT_ZERO_WP.
+ * SRX_E_ARG (the context stays usable): a null context, argument block or named slot, k < 1, n or l_act outside 1..64, n_pc outside
+ * 1..l_act, an unknown op or variant. */
+typedef enum srx_iterate_opcode {
+    SRX_IT_APPLY = 0, SRX_IT_GRAM1 = 1, SRX_IT_GRAM2 = 2, SRX_IT_CHOL = 3, SRX_IT_TRSM = 4, SRX_IT_EIG = 5, SRX_IT_RITZ = 6,
+    SRX_IT_CHEB = 7
+} srx_iterate_opcode;
+#define SRX_IT_ALIAS_B 1
+#define SRX_IT_ZERO_WP 1
+#define SRX_IT_Z0 1             /* SRX_IT_Z0 << i: pass z_i, i = 0 .. 2 */
+#define SRX_IT_Z0_IS_SRC 8
+#define SRX_IT_SRC_IS_W 16
+typedef struct srx_iterate_args {
+    int32_t k, n, l_act, n_pc, n_want, d, variant, flags;
+    double off_tol2;
+    double* c;              /* k x k */
+    double* blk[5];         /* k x 64 each */
+    double* sm[2];          /* 64 x 64 each */
+    double* vec[3];         /* 64 each */
+    double* xi;             /* 4 x 16 x 16 */
+    double out[8];          /* RITZ: k_resid_final's scalars */
+    int32_t status[2];      /* the solver's status word and the eigen-solve's sweep count, as the kernels left them */
+    int32_t tail_touched;   /* 1: a sentinel row behind a k x 64 block was written */
+    int32_t reserved;
+} srx_iterate_args;
+int32_t srx_iterate_op(srx_ctx* ctx, int32_t op, srx_iterate_args* args);
 
 /* ---- fused pipeline: normalize_total_inplace(target, Row) -> log1p_transform_inplace ->
  * pca_inplace(n_pc, center, scale, .., HighlyVariable(n_hvg)) with every intermediate

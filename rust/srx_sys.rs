@@ -25,6 +25,11 @@ pub const SRX_HARMONY_MAX_ROUNDS: i32 = 64;
 pub const SRX_DOUBLET_MAX_K: i32 = 64;
 pub const SRX_DOUBLET_MAX_ROUNDS: i32 = 10000;
 pub const SRX_DOUBLET_WAVE_ROW: i32 = 8192;
+pub const SRX_IT_ALIAS_B: i32 = 1;
+pub const SRX_IT_ZERO_WP: i32 = 1;
+pub const SRX_IT_Z0: i32 = 1;
+pub const SRX_IT_Z0_IS_SRC: i32 = 8;
+pub const SRX_IT_SRC_IS_W: i32 = 16;
 pub const SRX_OK: i32 = 0;
 pub const SRX_E_ARG: i32 = -1;
 pub const SRX_E_DTYPE: i32 = -2;
@@ -91,6 +96,14 @@ pub const SRX_DOUBLETS_PREDICTED: i32 = 5;
 pub const SRX_DOUBLETS_POINTS: i32 = 6;
 pub const SRX_DOUBLETS_PARENTS: i32 = 7;
 pub const SRX_DOUBLETS_KNN: i32 = 8;
+pub const SRX_IT_APPLY: i32 = 0;
+pub const SRX_IT_GRAM1: i32 = 1;
+pub const SRX_IT_GRAM2: i32 = 2;
+pub const SRX_IT_CHOL: i32 = 3;
+pub const SRX_IT_TRSM: i32 = 4;
+pub const SRX_IT_EIG: i32 = 5;
+pub const SRX_IT_RITZ: i32 = 6;
+pub const SRX_IT_CHEB: i32 = 7;
 pub const SRX_BACKED_NORMALIZE: i32 = 1;
 pub const SRX_BACKED_LOG1P: i32 = 2;
 pub const SRX_K_NORMALIZE: i32 = 0;
@@ -526,6 +539,29 @@ pub struct SrxDoubletInfo {      // `srx_doublet_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxIterateArgs {      // `srx_iterate_args`
+    pub k: i32,
+    pub n: i32,
+    pub l_act: i32,
+    pub n_pc: i32,
+    pub n_want: i32,
+    pub d: i32,
+    pub variant: i32,
+    pub flags: i32,
+    pub off_tol2: f64,
+    pub c: *mut f64,
+    pub blk: [*mut f64; 5 as usize],
+    pub sm: [*mut f64; 2 as usize],
+    pub vec: [*mut f64; 3 as usize],
+    pub xi: *mut f64,
+    pub out: [f64; 8 as usize],
+    pub status: [i32; 2 as usize],
+    pub tail_touched: i32,
+    pub reserved: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPipelineResult {      // `srx_pipeline_result`
     pub pca: SrxPcaInfo,
     pub ms_normalize: f64,
@@ -703,6 +739,7 @@ extern "C" {
     pub fn srx_doublets_free(h: *mut SrxDoublets);
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
+    pub fn srx_iterate_op(ctx: *mut SrxCtx, op: i32, args: *mut SrxIterateArgs) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,
                         res: *mut SrxPipelineResult) -> i32;
     pub fn srx_result_fetch(m: *mut SrxMat, scores: *mut f64, components: *mut f64, evr: *mut f64, mean: *mut f64,

@@ -26,6 +26,11 @@ HARMONY_MAX_ROUNDS = 64
 DOUBLET_MAX_K = 64
 DOUBLET_MAX_ROUNDS = 10000
 DOUBLET_WAVE_ROW = 8192
+IT_ALIAS_B = 1
+IT_ZERO_WP = 1
+IT_Z0 = 1
+IT_Z0_IS_SRC = 8
+IT_SRC_IS_W = 16
 SYNTH_MAX_TYPES = 128
 OK = 0
 E_ARG = -1
@@ -93,6 +98,14 @@ DOUBLETS_PREDICTED = 5
 DOUBLETS_POINTS = 6
 DOUBLETS_PARENTS = 7
 DOUBLETS_KNN = 8
+IT_APPLY = 0
+IT_GRAM1 = 1
+IT_GRAM2 = 2
+IT_CHOL = 3
+IT_TRSM = 4
+IT_EIG = 5
+IT_RITZ = 6
+IT_CHEB = 7
 BACKED_NORMALIZE = 1
 BACKED_LOG1P = 2
 K_NORMALIZE = 0
@@ -286,6 +299,13 @@ class DoubletInfo(C.Structure):      # srx_doublet_info
                 ("ms_project", C.c_double), ("ms_knn", C.c_double), ("ms_score", C.c_double)]
 
 
+class IterateArgs(C.Structure):      # srx_iterate_args
+    _fields_ = [("k", C.c_int32), ("n", C.c_int32), ("l_act", C.c_int32), ("n_pc", C.c_int32), ("n_want", C.c_int32),
+                ("d", C.c_int32), ("variant", C.c_int32), ("flags", C.c_int32), ("off_tol2", C.c_double), ("c", P),
+                ("blk", P * 5), ("sm", P * 2), ("vec", P * 3), ("xi", P), ("out", C.c_double * 8),
+                ("status", C.c_int32 * 2), ("tail_touched", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PipelineResult(C.Structure):      # srx_pipeline_result
     _fields_ = [("pca", PcaInfo), ("ms_normalize", C.c_double), ("ms_moments", C.c_double), ("ms_select", C.c_double),
                 ("ms_compact", C.c_double), ("ms_pca", C.c_double)]
@@ -421,6 +441,7 @@ SIGNATURES = {
     "srx_doublets_info_get": (C.c_int32, [P, C.POINTER(DoubletInfo)]),
     "srx_doublets_free": (None, [P]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
+    "srx_iterate_op": (C.c_int32, [P, C.c_int32, C.POINTER(IterateArgs)]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),
     "srx_backed_create": (C.c_int32, [P, C.c_uint64, C.c_int32, C.POINTER(P)]),

@@ -429,7 +429,8 @@ __global__ __launch_bounds__(1024) void k_chol_factor(const double* __restrict__
         if (!drop && !(d > 0.0)) bad = true;
         const double inv = drop ? 0.0 : rsqrt(d), inv2 = inv * inv;
         if (tid < L) {
-            Rout[(size_t)j * L + tid] = (tid >= j && tid < n) ? (drop ? (tid == j ? 1.0 : 0.0) : A[j][tid] * inv) : 0.0;
+            // (the diagonal from the pivot as USED: a lifted pivot gives R[j][j] = sqrt(floor) = 1 / dinv[j], the factor of the shifted G)
+            Rout[(size_t)j * L + tid] = (tid >= j && tid < n) ? (drop ? (tid == j ? 1.0 : 0.0) : (tid == j ? d : A[j][tid]) * inv) : 0.0;
             if (tid == j) dinv[j] = inv;
         }
 #pragma unroll

@@ -21,7 +21,8 @@
 //    every register index is static; the wave's only LDS traffic are 32 broadcast 16-byte reads per round.
 //
 // Outputs: U (L x L row-major) receives eigenvector c in COLUMN c, eigenvalues
-// descending in theta; rows / columns >= n are 0, theta[c >= n] = 0; kStatEig on non-convergence after 30 sweeps.
+// descending in theta; rows / columns >= n are 0, theta[c >= n] = 0; kStatEig on non-convergence after 30 sweeps.  A NaN in the
+// leading block: every theta is NaN (the Ritz tail's residual is then NaN, which is what the driver looks at), U is unspecified.
 // `off_tol2`: the sweep loop stops when sum_{i<j} a_ij^2 <= off_tol2 * sum_i a_ii^2, measured before a sweep's first round;
 // the solve leaves after that round (the state is one round better than measured; players are back in their own slots).
 // `n_want` (round 5): the sum on the left runs over the pairs with at least one WANTED index — the n_want largest diagonal
@@ -143,8 +144,13 @@ __device__ __forceinline__ void j2_rotation(double app, double aqq, double apq, 
     const double ab = ((d >= 0.0) == (b >= 0.0)) ? fabs(b) : -fabs(b);
     const double tt = ab * j2_rcp(u);
     const double cc = u * j2_rsqrt(__builtin_fma(u, u, b * b));
+    // t^2 < 2^-53: the cosine rounds to 1.  u * rsqrt(u^2 + b^2) does not return it — the corrected seed is within an ulp, not
+    // correctly rounded, and next to 1 the f64 grid is twice as fine below as above, so the product lands on 1 - 2^-53 far more
+    // often than on 1 + 2^-52: a bias of ~ -3e-17 per rotation that every column of U collected 63 times a sweep (the columns'
+    // norms drifted to 1 - 4e-14 in 16 sweeps; tests/test_iterate_gpu.py).  (Beside the reciprocal square root, not behind it.)
+    const bool unit = b * b < 0x1p-53 * (u * u);
     t = live ? tt : 0.0;
-    c = live ? cc : 1.0;
+    c = live && !unit ? cc : 1.0;
     dp = __builtin_fma(-t, apq, app);
     dq = __builtin_fma(t, apq, aqq);
 }
@@ -364,7 +370,9 @@ __global__ __launch_bounds__(kJ2Threads) void k_jacobi_eig2(double* __restrict__
                     double dg = dv * dv;
                     off = wave_sum(off);
                     dg = wave_sum(dg);
-                    if (lane == 0) S.flag = !(off > off_tol2 * dg) ? 1 : (sweep >= 30 ? 2 : 0);
+                    // (a NaN anywhere in the matrix shows in one of the two sums at the first measurement: flag 3, and every Ritz value is
+                    //  returned as NaN below — "converged" on a failed comparison left theta to the races of a NaN's rank)
+                    if (lane == 0) S.flag = (off != off || dg != dg) ? 3 : !(off > off_tol2 * dg) ? 1 : (sweep >= 30 ? 2 : 0);
                     // (diagnostics, SRX_PCA_TRACE: the measured off-diagonal norm over the diagonal's, per sweep, as float bits)
                     if (lane == 0 && sweep < 32) status[16 + sweep] = __float_as_int((float)sqrt(off / dg));
                     // who is wanted at the NEXT sweep's measurement: rank of this slot's diagonal entry among the 64
@@ -404,8 +412,9 @@ __global__ __launch_bounds__(kJ2Threads) void k_jacobi_eig2(double* __restrict__
                 else before = (j < n) && (other > mine || (other == mine && j < tid));
                 rk += before ? 1 : 0;
             }
-            S.rank[tid] = rk;
-            theta[rk] = tid < n ? mine : 0.0;
+            const bool nan_in = S.flag == 3;
+            S.rank[tid] = nan_in ? tid : rk;
+            theta[nan_in ? tid : rk] = nan_in ? __builtin_nan("") : (tid < n ? mine : 0.0);
         }
         j2_barrier();
     } else {

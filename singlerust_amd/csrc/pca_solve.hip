@@ -186,6 +186,67 @@ static int32_t gram2(srx_ctx* ctx, const Work& w, const double* A, const double*
     return SRX_OK;
 }
 
+// The launch of every kernel of the iteration: grid, block, dynamic LDS.  subspace_iterate's segments and srx_iterate_op (the
+// kernel-level entry) both go through these, so that what the tests launch is what the solver launches.  They only enqueue
+// on ctx->stream: the caller reads hipGetLastError.
+static int32_t attr_dense_apply(srx_ctx* ctx) {
+    SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_dense_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDenseLds));
+    return SRX_OK;
+}
+static int32_t attr_jacobi(srx_ctx* ctx) {
+    SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_jacobi_eig2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(J2Lds)));
+    return SRX_OK;
+}
+static void launch_dense_apply(srx_ctx* ctx, const double* C, const double* Win, int k, double* Wout) {
+    hipLaunchKernelGGL(k_dense_apply, dim3((k + 31) / 32, kDenseSplit), dim3(kDenseWaves * 64), kDenseLds, ctx->stream, C, Win, k, Wout);
+}
+static void launch_gram1(srx_ctx* ctx, const double* A, const double* B, int k, double* H) {
+    int nb = (k + 31) / 32;
+    if (nb > kGram1Blocks) nb = kGram1Blocks;
+    hipLaunchKernelGGL(k_gram1_part, dim3(nb), dim3(1024), 0, ctx->stream, A, B, k, H);
+}
+static void launch_chol(srx_ctx* ctx, const double* G, int n, double* R, double* dinv, int* status, int shifted) {
+    hipLaunchKernelGGL(k_chol_factor, dim3(1), dim3(1024), 0, ctx->stream, G, n, R, dinv, status, shifted);
+}
+static void launch_chol_mfma(srx_ctx* ctx, double* G, int n, double* R, double* dinv, double* Xi, int* status) {
+    hipLaunchKernelGGL(k_chol_factor_mfma, dim3(1), dim3(1024), 0, ctx->stream, G, n, R, dinv, Xi, status);
+}
+static void launch_trsm_rows(srx_ctx* ctx, const double* src, const double* R, const double* dinv, int k, double* W, double* z0,
+                             double* z1, double* z2) {
+    hipLaunchKernelGGL(k_trsm_rows, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, src, R, dinv, k, W, z0, z1, z2);
+}
+static void launch_trsm_mfma(srx_ctx* ctx, const double* src, const double* R, const double* Xi, int k, double* W, double* z0,
+                             double* z1, double* z2) {
+    hipLaunchKernelGGL(k_trsm_mfma, dim3((k + 16 * kTrsmTiles - 1) / (16 * kTrsmTiles)), dim3(kTrsmTiles * 64), 0, ctx->stream, src,
+                       R, Xi, k, W, z0, z1, z2);
+}
+static void launch_jacobi(srx_ctx* ctx, double* H, int n, double* U, double* theta, int* status, double off_tol2, int n_want) {
+    hipLaunchKernelGGL(k_jacobi_eig2, dim3(1), dim3(kJ2Threads), sizeof(J2Lds), ctx->stream, H, n, U, theta, status, off_tol2, n_want);
+}
+static void launch_ritz_post(srx_ctx* ctx, const double* W, double* Wp, const double* U, const double* theta, int k, double* A1,
+                             double* A2, double* part, int zero_wp) {
+    hipLaunchKernelGGL(k_ritz_post, dim3(kRitzBlocks), dim3(256), 0, ctx->stream, W, Wp, U, theta, k, A1, A2, part, zero_wp);
+}
+static void launch_resid_final(srx_ctx* ctx, const double* part, const double* theta, int n_pc, int l_act, const int* status,
+                               const int* status_sel, double* rho, double* colmax, double* out) {
+    hipLaunchKernelGGL(k_resid_final, dim3(1), dim3(1024), 0, ctx->stream, part, kRitzBlocks, theta, n_pc, l_act, status, status_sel,
+                       rho, colmax, out);
+}
+static unsigned cheb_grid_of(size_t kl) { return (unsigned)((kl + 255) / 256); }
+static void launch_cheb_first(srx_ctx* ctx, double* A1, const double* A2, const double* theta, int l_act, size_t kl) {
+    hipLaunchKernelGGL(k_cheb_first, dim3(cheb_grid_of(kl)), dim3(256), 0, ctx->stream, A1, A2, theta, l_act, kl);
+}
+static void launch_cheb_first2(srx_ctx* ctx, double* Z, const double* W, double* cur, double* prev, const double* theta, int l_act,
+                               size_t kl) {
+    hipLaunchKernelGGL(k_cheb_first2, dim3(cheb_grid_of(kl)), dim3(256), 0, ctx->stream, Z, W, cur, prev, theta, l_act, kl);
+}
+static void launch_cheb_step(srx_ctx* ctx, double* Z, const double* cur, double* prev, const double* theta, int l_act, size_t kl) {
+    hipLaunchKernelGGL(k_cheb_step, dim3(cheb_grid_of(kl)), dim3(256), 0, ctx->stream, Z, cur, prev, theta, l_act, kl);
+}
+static void launch_cheb_scale(srx_ctx* ctx, double* Y, const double* theta, int l_act, int d, size_t kl) {
+    hipLaunchKernelGGL(k_cheb_scale, dim3(cheb_grid_of(kl)), dim3(256), 0, ctx->stream, Y, theta, l_act, d, kl);
+}
+
 // Run `enqueue` (kernel launches / async memsets and copies on ctx->stream, no host synchronisation, no
 // allocation) through a cached hipGraph: captured the first time a key is seen, one hipGraphLaunch afterwards.
 // The key must name everything the launches depend on (shapes, schedule, device pointers).  Any failure of the
@@ -259,7 +320,7 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
     SRX_TRY(scratch(ctx, "pca_res", kSlots * kSlotDoubles * sizeof(double), (void**)&d_res));
     double* d_ritz;
     SRX_TRY(scratch(ctx, "pca_ritzpart", (size_t)kRitzBlocks * 3 * L * sizeof(double), (void**)&d_ritz));
-    SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_jacobi_eig2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(J2Lds)));
+    SRX_TRY(attr_jacobi(ctx));
     // what a captured segment depends on besides its own schedule: shapes, options, every buffer it touches
     char key0[320];
     snprintf(key0, sizeof key0, "k%d l%d p%d w%d r%d n%d s%llu t%a|%p %p %p %p %p %p %p %p %p %p", k, l_act, o.power, o.warm,
@@ -275,35 +336,31 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
     // orthonormalise src -> W  (CholeskyQR: G = src^T src = R^T R, W = src R^-1; src == W is fine: every
     // thread of the substitution owns one row); G lands in dHG + L*L
     auto gram1 = [&](const double* A, const double* B) -> int32_t {       // A^T B summed into d_h1 (zero between uses)
-        int nb = (k + 31) / 32;
-        if (nb > kGram1Blocks) nb = kGram1Blocks;
-        hipLaunchKernelGGL(k_gram1_part, dim3(nb), dim3(1024), 0, ctx->stream, A, B, k, d_h1);
+        launch_gram1(ctx, A, B, k, d_h1);
         SRX_HIP(ctx, hipGetLastError());
         return 1;
     };
     auto orth = [&](const double* src) -> int32_t {
         if (o.robust) {
             SRX_TRY(gram2(ctx, w, src, src, k));
-            hipLaunchKernelGGL(k_chol_factor, dim3(1), dim3(1024), 0, ctx->stream, w.dHG + L * L, l_act, w.dM, w.dDinv, d_status, 1);
+            launch_chol(ctx, w.dHG + L * L, l_act, w.dM, w.dDinv, d_status, 1);
         } else {
             const int32_t nb = gram1(src, src);
             if (nb < 0) return nb;
-            hipLaunchKernelGGL(k_chol_factor_mfma, dim3(1), dim3(1024), 0, ctx->stream, d_h1, l_act, w.dM, w.dDinv, w.dXi, d_status);
+            launch_chol_mfma(ctx, d_h1, l_act, w.dM, w.dDinv, w.dXi, d_status);
         }
         double* const zT = acc_apply ? w.T : nullptr;           // (the matrix-free solver's apply overwrites its destination and uses T itself)
         double* const zWp = acc_apply ? w.Wp : nullptr;
         double* const zA1 = acc_apply ? w.A1 : nullptr;
         if (o.robust)
-            hipLaunchKernelGGL(k_trsm_rows, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, src, (const double*)w.dM, (const double*)w.dDinv, k, w.W, zWp, zA1, zT);
+            launch_trsm_rows(ctx, src, w.dM, w.dDinv, k, w.W, zWp, zA1, zT);
         else
-            hipLaunchKernelGGL(k_trsm_mfma, dim3((k + 16 * kTrsmTiles - 1) / (16 * kTrsmTiles)), dim3(kTrsmTiles * 64), 0, ctx->stream, src,
-                               (const double*)w.dM, (const double*)w.dXi, k, w.W, zWp, zA1, zT);
+            launch_trsm_mfma(ctx, src, w.dM, w.dXi, k, w.W, zWp, zA1, zT);
         SRX_HIP(ctx, hipGetLastError());
         if (o.robust) {                         // second pass: the first one may have run on a shifted Gram matrix
             SRX_TRY(gram2(ctx, w, w.W, w.W, k));
-            hipLaunchKernelGGL(k_chol_factor, dim3(1), dim3(1024), 0, ctx->stream, w.dHG + L * L, l_act, w.dM, w.dDinv, d_status, 1);
-            hipLaunchKernelGGL(k_trsm_rows, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, (const double*)w.W, (const double*)w.dM, (const double*)w.dDinv, k, w.W,
-                               (double*)nullptr, (double*)nullptr, (double*)nullptr);
+            launch_chol(ctx, w.dHG + L * L, l_act, w.dM, w.dDinv, d_status, 1);
+            launch_trsm_rows(ctx, w.W, w.dM, w.dDinv, k, w.W, nullptr, nullptr, nullptr);
             SRX_HIP(ctx, hipGetLastError());
         }
         return SRX_OK;
@@ -350,13 +407,10 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
             // over theta_npc, i.e. sqrt(tol2) x (theta_1 / theta_npc) x a few — 1e-4 of the residual tolerance keeps it two
             // orders below what the step is judged on (tol 1e-7: 1e-22, one sweep of the quadratic tail less than 1e-30)
             const double exact_tol2 = std::max(1e-30, (o.tol * 1e-4) * (o.tol * 1e-4));
-            hipLaunchKernelGGL(k_jacobi_eig2, dim3(1), dim3(kJ2Threads), sizeof(J2Lds), ctx->stream, d_h1, l_act,
-                               w.dM2, w.dTheta, d_status, loose ? loose_tol2 : exact_tol2,
-                               o.direct ? l_act : std::min(l_act, o.n_pc + 4));      // (the guard columns' block need not be diagonal: jacobi.inl)
-            hipLaunchKernelGGL(k_ritz_post, dim3(kRitzBlocks), dim3(256), 0, ctx->stream, (const double*)w.W, w.Wp,
-                               (const double*)w.dM2, (const double*)w.dTheta, k, w.A1, w.A2, d_ritz, acc_apply ? 1 : 0);
-            hipLaunchKernelGGL(k_resid_final, dim3(1), dim3(1024), 0, ctx->stream, (const double*)d_ritz, kRitzBlocks,
-                               (const double*)w.dTheta, o.n_pc, l_act, d_status, d_status_sel, w.dRho, w.dColmax,
+            launch_jacobi(ctx, d_h1, l_act, w.dM2, w.dTheta, d_status, loose ? loose_tol2 : exact_tol2,
+                          o.direct ? l_act : std::min(l_act, o.n_pc + 4));      // (the guard columns' block need not be diagonal: jacobi.inl)
+            launch_ritz_post(ctx, w.W, w.Wp, w.dM2, w.dTheta, k, w.A1, w.A2, d_ritz, acc_apply ? 1 : 0);
+            launch_resid_final(ctx, d_ritz, w.dTheta, o.n_pc, l_act, d_status, d_status_sel, w.dRho, w.dColmax,
                                d_res + kSlotDoubles * slot);
         }
         SRX_HIP(ctx, hipGetLastError());
@@ -430,10 +484,8 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
     };
     // Chebyshev filter after the first Ritz step (Gram solver: w.T is free and `apply` has no collective).
     // Speculative part: Y1 and Z = C Y1 (needed whatever the degree turns out to be, d >= 2).
-    const unsigned cheb_grid = (unsigned)((kl + 255) / 256);
     auto cheb_spec = [&]() -> int32_t {
-        hipLaunchKernelGGL(k_cheb_first, dim3(cheb_grid), dim3(256), 0, ctx->stream, w.A1, (const double*)w.A2,
-                           (const double*)w.dTheta, l_act, kl);
+        launch_cheb_first(ctx, w.A1, w.A2, w.dTheta, l_act, kl);
         SRX_HIP(ctx, hipGetLastError());
         return apply(w.A1, w.Wp, acc_apply);          // (Gram solver: the Ritz tail left Wp zeroed)
     };
@@ -442,13 +494,12 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
         double *cur = w.A1, *prev = w.A2;
         for (int j = 1; j < d; ++j) {
             if (j > 1) SRX_TRY(apply(cur, w.Wp, true));          // (the step before left Wp zeroed)
-            hipLaunchKernelGGL(k_cheb_step, dim3(cheb_grid), dim3(256), 0, ctx->stream, w.Wp,
-                               (const double*)cur, prev, (const double*)w.dTheta, l_act, kl);
+            launch_cheb_step(ctx, w.Wp, cur, prev, w.dTheta, l_act, kl);
             double* t = cur;
             cur = prev;
             prev = t;
         }
-        hipLaunchKernelGGL(k_cheb_scale, dim3(cheb_grid), dim3(256), 0, ctx->stream, cur, (const double*)w.dTheta, l_act, d, kl);
+        launch_cheb_scale(ctx, cur, w.dTheta, l_act, d, kl);
         SRX_HIP(ctx, hipGetLastError());
         return orth(cur);
     };
@@ -462,8 +513,7 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
         SRX_TRY(cheb_filter(d));
         if (d2 > 0) {
             SRX_TRY(apply(w.W, w.Wp, acc_apply));                // (Gram solver: the CholeskyQR left Wp, A1, T zeroed)
-            hipLaunchKernelGGL(k_cheb_first2, dim3(cheb_grid), dim3(256), 0, ctx->stream, w.Wp, (const double*)w.W, w.A1, w.A2,
-                               (const double*)w.dTheta, l_act, kl);
+            launch_cheb_first2(ctx, w.Wp, w.W, w.A1, w.A2, w.dTheta, l_act, kl);
             SRX_HIP(ctx, hipGetLastError());
             SRX_TRY(apply(w.A1, w.Wp, true));
             SRX_TRY(cheb_filter(d2));
@@ -486,8 +536,7 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
     int sweeps_since = 0;
     if (bailed_first) *bailed_first = false;
     if (resume) {
-        hipLaunchKernelGGL(k_resid_final, dim3(1), dim3(1024), 0, ctx->stream, (const double*)d_ritz, kRitzBlocks,
-                           (const double*)w.dTheta, o.n_pc, l_act, d_status, d_status_sel, w.dRho, w.dColmax, d_res + kSlotDoubles * slot);
+        launch_resid_final(ctx, d_ritz, w.dTheta, o.n_pc, l_act, d_status, d_status_sel, w.dRho, w.dColmax, d_res + kSlotDoubles * slot);
         SRX_HIP(ctx, hipGetLastError());
     } else {
         SRX_TRY(graphed(ctx, use_graph, key_base + "|start", seg_start));
@@ -867,7 +916,7 @@ static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const T
         auto apply = [&](const double* Win, double* Wout, bool out_zeroed) -> int32_t {
             ProfScope ps(ctx, SRX_K_DENSE, (double)k * k * 8.0 + 2.0 * k * L * 8.0);
             if (!out_zeroed) SRX_HIP(ctx, hipMemsetAsync(Wout, 0, kl * 8, ctx->stream));
-            hipLaunchKernelGGL(k_dense_apply, dim3((k + 31) / 32, kDenseSplit), dim3(kDenseWaves * 64), kDenseLds, ctx->stream, C, Win, k, Wout);
+            launch_dense_apply(ctx, C, Win, k, Wout);
             SRX_HIP(ctx, hipGetLastError());
             return SRX_OK;
         };
@@ -878,7 +927,7 @@ static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const T
             return SRX_OK;
         };
         Range r_("srx:iterate");
-        SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_dense_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDenseLds));
+        SRX_TRY(attr_dense_apply(ctx));
         SRX_TRY(solve(apply, C, true, reset, deflate));
     } else {
         if (n_parts != 1 || !t256p) return fail(ctx, SRX_E_ARG, "pca: the SpMM solver needs the matrix resident in one piece");
@@ -1098,6 +1147,165 @@ int32_t srx_spmm(srx_mat* m, const uint64_t* sel, uint64_t k64, const double* pa
         return SRX_OK;
     };
     return is_f32(m) ? run(float{}, float{}) : run(double{}, double{});
+}
+
+// Kernel-level entry point of the dense iteration (test and diagnostics: no stability promise): one operation of
+// subspace_iterate on host arrays, through the solver's own launch_* functions, in fresh device buffers of exactly the stated
+// sizes (a k x 64 block: k + 8 rows, the last 8 a sentinel that must come back untouched).
+namespace {
+constexpr int kItTail = 8;
+constexpr double kItSentinel = -7.25e77;
+struct ItBufs {                                    // the device buffers of one call, freed when it returns
+    std::vector<void*> p;
+    ~ItBufs() {
+        for (void* q : p) (void)hipFree(q);
+    }
+};
+}  // namespace
+
+static int32_t it_alloc(srx_ctx* ctx, ItBufs& bufs, size_t bytes, void** out) {
+    SRX_HIP(ctx, hipMalloc(out, bytes));
+    bufs.p.push_back(*out);
+    return SRX_OK;
+}
+// a host array -> a fresh device buffer of `n` doubles (+ the sentinel rows of a k x 64 block)
+static int32_t it_up(srx_ctx* ctx, ItBufs& bufs, const double* host, size_t n, bool block, double** dev) {
+    const size_t tail = block ? (size_t)kItTail * L : 0;
+    SRX_TRY(it_alloc(ctx, bufs, (n + tail) * 8, (void**)dev));
+    std::vector<double> h(n + tail, kItSentinel);
+    if (host) memcpy(h.data(), host, n * 8);
+    else std::fill(h.begin(), h.begin() + n, 0.0);
+    return h2d(ctx, *dev, h.data(), h.size() * 8);
+}
+static int32_t it_down(srx_ctx* ctx, double* host, const double* dev, size_t n, bool block, int32_t* touched) {
+    const size_t tail = block ? (size_t)kItTail * L : 0;
+    std::vector<double> h(n + tail);
+    SRX_TRY(d2h(ctx, h.data(), dev, h.size() * 8));
+    if (host) memcpy(host, h.data(), n * 8);
+    for (size_t e = n; e < n + tail; ++e)
+        if (h[e] != kItSentinel) *touched = 1;
+    return SRX_OK;
+}
+
+int32_t srx_iterate_op(srx_ctx* ctx, int32_t op, srx_iterate_args* a) {
+    if (!ctx || !a) return fail(ctx, SRX_E_ARG, "srx_iterate_op: null argument");
+    if (a->k < 1) return fail(ctx, SRX_E_ARG, "srx_iterate_op: k must be >= 1");
+    const bool needs_n = op == SRX_IT_CHOL || op == SRX_IT_EIG;
+    const bool needs_l = op == SRX_IT_RITZ || op == SRX_IT_CHEB;
+    if (needs_n && (a->n < 1 || a->n > L)) return fail(ctx, SRX_E_ARG, "srx_iterate_op: n must be in 1..%d", L);
+    if (needs_l && (a->l_act < 1 || a->l_act > L)) return fail(ctx, SRX_E_ARG, "srx_iterate_op: l_act must be in 1..%d", L);
+    if (op == SRX_IT_RITZ && (a->n_pc < 1 || a->n_pc > a->l_act)) return fail(ctx, SRX_E_ARG, "srx_iterate_op: n_pc must be in 1..l_act");
+    int n_blk = 0, n_sm = 0, n_vec = 0;            // the slots the operation names: all must be given
+    bool need_c = false, need_xi = false;
+    switch (op) {
+        case SRX_IT_APPLY: n_blk = 2; need_c = true; break;
+        case SRX_IT_GRAM1: n_blk = (a->flags & SRX_IT_ALIAS_B) ? 1 : 2; n_sm = 1; break;
+        case SRX_IT_GRAM2: n_blk = (a->flags & SRX_IT_ALIAS_B) ? 1 : 2; n_sm = 2; break;
+        case SRX_IT_CHOL:
+            if (a->variant < 0 || a->variant > 2) return fail(ctx, SRX_E_ARG, "srx_iterate_op: chol variant must be 0, 1 or 2");
+            n_sm = 2; n_vec = 1; need_xi = a->variant == 2; break;
+        case SRX_IT_TRSM:
+            if (a->variant < 0 || a->variant > 1) return fail(ctx, SRX_E_ARG, "srx_iterate_op: trsm variant must be 0 or 1");
+            n_blk = 2; n_sm = 2; n_vec = a->variant == 0 ? 1 : 0; need_xi = a->variant == 1;
+            for (int i = 0; i < 3; ++i)
+                if ((a->flags & (SRX_IT_Z0 << i)) && !a->blk[2 + i]) return fail(ctx, SRX_E_ARG, "srx_iterate_op: null z block");
+            break;
+        case SRX_IT_EIG: n_sm = 2; n_vec = 1; break;
+        case SRX_IT_RITZ: n_blk = 4; n_sm = 2; n_vec = 3; break;
+        case SRX_IT_CHEB:
+            if (a->variant < 0 || a->variant > 3) return fail(ctx, SRX_E_ARG, "srx_iterate_op: cheb variant must be 0..3");
+            n_blk = a->variant == 0 ? 2 : a->variant == 1 ? 4 : a->variant == 2 ? 3 : 1; n_vec = 1; break;
+        default: return fail(ctx, SRX_E_ARG, "srx_iterate_op: unknown op %d", op);
+    }
+    for (int i = 0; i < n_blk; ++i)
+        if (!a->blk[i]) return fail(ctx, SRX_E_ARG, "srx_iterate_op: null block %d", i);
+    for (int i = (op == SRX_IT_TRSM || op == SRX_IT_RITZ ? 1 : 0); i < n_sm; ++i)      // (these two read sm[1] alone)
+        if (!a->sm[i]) return fail(ctx, SRX_E_ARG, "srx_iterate_op: null matrix %d", i);
+    for (int i = 0; i < n_vec; ++i)
+        if (!a->vec[i]) return fail(ctx, SRX_E_ARG, "srx_iterate_op: null vector %d", i);
+    if ((need_c && !a->c) || (need_xi && !a->xi)) return fail(ctx, SRX_E_ARG, "srx_iterate_op: null argument");
+    SRX_HIP(ctx, hipSetDevice(ctx->device));
+
+    const int k = a->k;
+    const size_t kl = (size_t)k * L, ll = (size_t)L * L;
+    ItBufs bufs;
+    double *blk[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *sm[2] = {nullptr, nullptr}, *vec[3] = {nullptr, nullptr, nullptr};
+    double *c = nullptr, *xi = nullptr, *out = nullptr;
+    int *status = nullptr, *status_sel = nullptr;
+    a->tail_touched = 0;
+    for (int i = 0; i < 5; ++i)
+        if (a->blk[i]) SRX_TRY(it_up(ctx, bufs, a->blk[i], kl, true, &blk[i]));
+    for (int i = 0; i < 2; ++i) SRX_TRY(it_up(ctx, bufs, a->sm[i], ll, false, &sm[i]));
+    for (int i = 0; i < 3; ++i) SRX_TRY(it_up(ctx, bufs, a->vec[i], L, false, &vec[i]));
+    SRX_TRY(it_up(ctx, bufs, a->xi, 4 * 16 * 16, false, &xi));
+    SRX_TRY(it_up(ctx, bufs, nullptr, 8, false, &out));
+    if (a->c) SRX_TRY(it_up(ctx, bufs, a->c, (size_t)k * k, false, &c));
+    SRX_TRY(it_alloc(ctx, bufs, 512, (void**)&status));         // (the solver's 256-byte status block, and the selection's word)
+    SRX_HIP(ctx, hipMemsetAsync(status, 0, 512, ctx->stream));
+    status_sel = status + 64;
+
+    switch (op) {
+        case SRX_IT_APPLY:
+            SRX_TRY(attr_dense_apply(ctx));
+            launch_dense_apply(ctx, c, blk[0], k, blk[1]);
+            break;
+        case SRX_IT_GRAM1:
+            launch_gram1(ctx, blk[0], (a->flags & SRX_IT_ALIAS_B) ? blk[0] : blk[1], k, sm[0]);
+            break;
+        case SRX_IT_GRAM2: {
+            Work w{};
+            double* hg;
+            SRX_TRY(it_alloc(ctx, bufs, (size_t)kGram2Blocks * 2 * ll * 8, (void**)&w.gpart));
+            SRX_TRY(it_alloc(ctx, bufs, 2 * ll * 8, (void**)&hg));
+            w.dHG = hg;
+            SRX_TRY(gram2(ctx, w, blk[0], (a->flags & SRX_IT_ALIAS_B) ? blk[0] : blk[1], k));
+            SRX_HIP(ctx, hipMemcpyAsync(sm[0], hg, ll * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            SRX_HIP(ctx, hipMemcpyAsync(sm[1], hg + ll, ll * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            break;
+        }
+        case SRX_IT_CHOL:
+            if (a->variant == 2) launch_chol_mfma(ctx, sm[0], a->n, sm[1], vec[0], xi, status);
+            else launch_chol(ctx, sm[0], a->n, sm[1], vec[0], status, a->variant);
+            break;
+        case SRX_IT_TRSM: {
+            double* const src = blk[0];
+            double* const W = (a->flags & SRX_IT_SRC_IS_W) ? src : blk[1];
+            double* z[3];
+            for (int i = 0; i < 3; ++i) z[i] = (a->flags & (SRX_IT_Z0 << i)) ? blk[2 + i] : nullptr;
+            if (a->flags & SRX_IT_Z0_IS_SRC) z[0] = src;
+            if (a->variant == 0) launch_trsm_rows(ctx, src, sm[1], vec[0], k, W, z[0], z[1], z[2]);
+            else launch_trsm_mfma(ctx, src, sm[1], xi, k, W, z[0], z[1], z[2]);
+            if (W != blk[1]) SRX_HIP(ctx, hipMemcpyAsync(blk[1], W, kl * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            break;
+        }
+        case SRX_IT_EIG:
+            SRX_TRY(attr_jacobi(ctx));
+            launch_jacobi(ctx, sm[0], a->n, sm[1], vec[0], status, a->off_tol2, a->n_want);
+            break;
+        case SRX_IT_RITZ: {
+            double* part;
+            SRX_TRY(it_alloc(ctx, bufs, (size_t)kRitzBlocks * 3 * L * 8, (void**)&part));
+            launch_ritz_post(ctx, blk[0], blk[1], sm[1], vec[0], k, blk[2], blk[3], part, (a->flags & SRX_IT_ZERO_WP) ? 1 : 0);
+            launch_resid_final(ctx, part, vec[0], a->n_pc, a->l_act, status, status_sel, vec[1], vec[2], out);
+            break;
+        }
+        case SRX_IT_CHEB:
+            if (a->variant == 0) launch_cheb_first(ctx, blk[0], blk[1], vec[0], a->l_act, kl);
+            else if (a->variant == 1) launch_cheb_first2(ctx, blk[0], blk[1], blk[2], blk[3], vec[0], a->l_act, kl);
+            else if (a->variant == 2) launch_cheb_step(ctx, blk[0], blk[1], blk[2], vec[0], a->l_act, kl);
+            else launch_cheb_scale(ctx, blk[0], vec[0], a->l_act, a->d, kl);
+            break;
+    }
+    SRX_HIP(ctx, hipGetLastError());
+    SRX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 5; ++i)
+        if (blk[i]) SRX_TRY(it_down(ctx, a->blk[i], blk[i], kl, true, &a->tail_touched));
+    for (int i = 0; i < 2; ++i) SRX_TRY(it_down(ctx, a->sm[i], sm[i], ll, false, nullptr));
+    for (int i = 0; i < 3; ++i) SRX_TRY(it_down(ctx, a->vec[i], vec[i], L, false, nullptr));
+    SRX_TRY(it_down(ctx, a->xi, xi, 4 * 16 * 16, false, nullptr));
+    SRX_TRY(it_down(ctx, a->out, out, 8, false, nullptr));
+    SRX_TRY(d2h(ctx, a->status, status, sizeof a->status));
+    return SRX_OK;
 }
 
 }  // extern "C"
