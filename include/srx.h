@@ -272,6 +272,61 @@ int32_t srx_normalize_log1p_inplace(srx_mat* m, double target_sum, double* row_s
  * gene indices IN RANK ORDER.  idx_out has room for min(n, n_cols) entries. */
 int32_t srx_select_hvg(srx_mat* m, uint64_t n, uint64_t* idx_out, uint64_t* n_out);
 
+/* ---- highly variable genes by analytic Pearson residuals (not in the reference) ---------------------------------------------
+ * scanpy's experimental.pp.highly_variable_genes(flavor = "pearson_residuals") and normalize_pearson_residuals (Lause,
+ * Berens & Kobak 2021) on RAW counts, before srx_normalize_log1p_inplace; additive, detected by symbol, no profiling class of
+ * its own (the times are in srx_pearson_info).
+ *
+ * Definition.  X is n x G with non-negative entries, r_i its row sums (cells), g_j its column sums (genes), T = sum_i r_i (a
+ * fixed-order f64 sum).  theta > 0 (+inf: Poisson) and the clip c >= 0 are the options.  For every pair (i, j), in f64, in this
+ * order, without contraction and without fast-math:
+ *      mu   = (r_i * g_j) / T
+ *      s    = sqrt(mu + (mu * mu) / theta)          (theta = +inf: sqrt(mu))
+ *      z_ij = min(max((x_ij - mu) / s, -c), c)      (mu == 0: z_ij = 0)
+ *   v_j = (sum_i z_ij^2) / n - ((sum_i z_ij) / n)^2: the population variance over ALL n cells, zeros included (np.var).
+ *   A gene with g_j = 0 has v_j = 0.0 exactly and is never selected; a cell with r_i = 0 has z = 0 for every gene and counts in
+ *   n.  T = 0: every v_j is 0 and nothing is selected; that is no error.
+ *   Selection: the first n genes with g_j > 0 by descending v_j, equal variances in ascending gene index, in rank order (the
+ *   order of srx_select_hvg for any key array: the same ranking kernel).
+ *   Defaults are scanpy's: theta == 0 in the option struct means 100, clip == 0 means sqrt(n_rows); clip = +inf: no clipping.
+ * How v_j is summed.  A CSC handle (genes are its stored rows) evaluates z_ij of every pair of a gene as defined, zeros
+ *   included, and sums z and z^2 over the cells in one fixed order, in f64 (sum_quantum = sq_quantum = 0).  A CSR handle makes
+ *   S1_j = sum_i z_ij and S2_j = sum_i z_ij^2 each as the sum of a DENSE part over all n cells of the residual of a zero
+ *   entry, f = -min(mu' / sqrt(mu' (1 + mu' / theta)), c) with mu' = r_i * (g_j / T), f^2 its square (cells in chunks, the
+ *   chunks' partial sums added in ascending order), and a SPARSE correction over the stored entries of z - f and z^2 - f^2 (z
+ *   as defined above), kept in 64-bit fixed point (integer atomics: exact in any order) with
+ *      b = min(c, sqrt(T)),   sum_quantum = 2^(ceil(log2(2 n b)) - 61),   sq_quantum = 2^(ceil(log2(n b b)) - 61)
+ *   (|z| <= b for non-negative X: x <= r_i and x <= g_j give mu >= x^2 / T), each no finer than 2^-200; every stored entry adds
+ *   at most half a quantum of error to its gene's sum.  No floating-point atomics: results are bit-identical from call to call,
+ *   and two identical columns get bit-identical variances wherever they sit.
+ * Departures from scanpy: scanpy yields NaN for an empty cell (here 0) and leaves ties to an unstable argsort (here: gene
+ *   index); batch_key (median rank over batches) and normalize_pearson_residuals followed by a PCA of the dense residuals are
+ *   out of scope (the PCA here is sparse; the selection enters it as an explicit list).
+ * All three calls accept CSR and CSC handles at either value storage and any dtype, leave the handle as it was (values,
+ *   logical dtype; the moments cache is filled with the moments of the current values if it was empty) and compute on the
+ *   device only.  Non-integer values are accepted.
+ * Refused with SRX_E_ARG and a message, nothing written: a NULL handle or output (opts, info and the var_out of
+ *   srx_select_hvg_pearson may be NULL); theta negative or NaN; clip negative or NaN; a gene index >= n_cols; a negative, NaN
+ *   or infinite stored value (found on the device by the pass that reads the values first); a context with more than one rank;
+ *   a context with an open backed session (sharded and out-of-core forms are out of scope). */
+typedef struct srx_pearson_opts { double theta; double clip; } srx_pearson_opts;          /* NULL = {0, 0} */
+typedef struct srx_pearson_info {
+    uint64_t n_cells, n_genes, n_expressed /* g_j > 0 */, n_empty_cells;
+    double   total, theta, clip;           /* T and the values actually used */
+    double   sum_quantum, sq_quantum;      /* 0 unless the sparse sums are kept in fixed point: their resolution */
+    double   ms_dense, ms_sparse, ms_rank;
+} srx_pearson_info;
+/* v_j of every gene (var_out: n_cols f64, host). */
+int32_t srx_pearson_gene_variance(srx_mat* m, const srx_pearson_opts* opts, double* var_out /* n_cols */, srx_pearson_info* info);
+/* The selection: idx_out has room for min(n, n_cols) entries, *n_out = min(n, n_expressed) of them are written. */
+int32_t srx_select_hvg_pearson(srx_mat* m, uint64_t n, const srx_pearson_opts* opts, uint64_t* idx_out, uint64_t* n_out,
+                               double* var_out /* n_cols, may be NULL */, srx_pearson_info* info);
+/* The clipped residuals z_ij of the listed genes (any order, repeats allowed), all cells, zeros included: scanpy's
+ * normalize_pearson_residuals restricted to a gene list.  Made on the device in chunks of rows of at most 1 GiB.  The timing
+ * and quantum fields of info are 0. */
+int32_t srx_pearson_residuals(srx_mat* m, const uint64_t* genes, uint64_t k, const srx_pearson_opts* opts,
+                              double* out /* host, n_rows x k row-major */, srx_pearson_info* info);
+
 /* ---- PCA: dim_red::pca_inplace (dim_red/mod.rs:24-94); arithmetic spec
  * src/shared/processing/pca/mod.rs:74-215.  Computed by randomized block subspace
  * iteration on the implicit standardised matrix Z = (X[:, sel] - 1 mu^T) D^-1 with a

@@ -227,6 +227,36 @@ impl<'c> DeviceX<'c> {
         }
     }
 
+    /// Not in the reference: scanpy's `highly_variable_genes(flavor = "pearson_residuals")` on the RAW counts (srx.h states the
+    /// definition).  Returns (the selected genes in rank order, the residual variance of every gene, the info block); `theta`
+    /// `None` = 100, `clip` `None` = sqrt(n_obs).  Hand the list to `pca_with_selection` after normalize / log1p.
+    pub fn highly_variable_genes_pearson(&self, n_top_genes: usize, theta: Option<f64>, clip: Option<f64>)
+                                         -> Result<(Vec<u64>, Vec<f64>, SrxPearsonInfo)> {
+        let opts = SrxPearsonOpts { theta: theta.unwrap_or(0.0), clip: clip.unwrap_or(0.0) };
+        let mut idx = vec![0u64; n_top_genes.min(self.n_vars).max(1)];
+        let mut var = vec![0f64; self.n_vars.max(1)];
+        let mut n_out = 0u64;
+        let mut info: SrxPearsonInfo = unsafe { std::mem::zeroed() };
+        self.ctx.check(unsafe {
+            srx_select_hvg_pearson(self.mat, n_top_genes as u64, &opts, idx.as_mut_ptr(), &mut n_out, var.as_mut_ptr(), &mut info)
+        })?;
+        idx.truncate(n_out as usize);
+        var.truncate(self.n_vars);
+        Ok((idx, var, info))
+    }
+
+    /// scanpy's `normalize_pearson_residuals` restricted to a gene list: n_obs x genes.len() clipped residuals, row-major,
+    /// zeros included; genes in any order, repeats allowed.
+    pub fn pearson_residuals(&self, genes: &[u64], theta: Option<f64>, clip: Option<f64>) -> Result<Vec<f64>> {
+        let opts = SrxPearsonOpts { theta: theta.unwrap_or(0.0), clip: clip.unwrap_or(0.0) };
+        let mut out = vec![0f64; (self.n_obs * genes.len()).max(1)];
+        self.ctx.check(unsafe {
+            srx_pearson_residuals(self.mat, genes.as_ptr(), genes.len() as u64, &opts, out.as_mut_ptr(), null_mut())
+        })?;
+        out.truncate(self.n_obs * genes.len());
+        Ok(out)
+    }
+
     /// dim_red/mod.rs:24-94 without the dense N x k matrix: returns (scores N x n_pc row-major, explained variance
     /// ratio, selected features) — exactly what `attach_pca_results` (:96-121) takes; `n_threads` is accepted and ignored,
     /// the `svd_mode` marker has no counterpart.

@@ -166,6 +166,30 @@ pub struct SrxFlex {      // `srx_flex`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxPearsonOpts {      // `srx_pearson_opts`
+    pub theta: f64,
+    pub clip: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxPearsonInfo {      // `srx_pearson_info`
+    pub n_cells: u64,
+    pub n_genes: u64,
+    pub n_expressed: u64,
+    pub n_empty_cells: u64,
+    pub total: f64,
+    pub theta: f64,
+    pub clip: f64,
+    pub sum_quantum: f64,
+    pub sq_quantum: f64,
+    pub ms_dense: f64,
+    pub ms_sparse: f64,
+    pub ms_rank: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPcaOpts {      // `srx_pca_opts`
     pub n_components: i32,
     pub center: i32,
@@ -626,6 +650,12 @@ extern "C" {
     pub fn srx_log1p_inplace(m: *mut SrxMat) -> i32;
     pub fn srx_normalize_log1p_inplace(m: *mut SrxMat, target_sum: f64, row_sums_out: *mut f64) -> i32;
     pub fn srx_select_hvg(m: *mut SrxMat, n: u64, idx_out: *mut u64, n_out: *mut u64) -> i32;
+    pub fn srx_pearson_gene_variance(m: *mut SrxMat, opts: *const SrxPearsonOpts, var_out: *mut f64,
+                                     info: *mut SrxPearsonInfo) -> i32;
+    pub fn srx_select_hvg_pearson(m: *mut SrxMat, n: u64, opts: *const SrxPearsonOpts, idx_out: *mut u64,
+                                  n_out: *mut u64, var_out: *mut f64, info: *mut SrxPearsonInfo) -> i32;
+    pub fn srx_pearson_residuals(m: *mut SrxMat, genes: *const u64, k: u64, opts: *const SrxPearsonOpts,
+                                 out: *mut f64, info: *mut SrxPearsonInfo) -> i32;
     pub fn srx_pca(m: *mut SrxMat, sel: *const u64, k: u64, opts: *const SrxPcaOpts, scores: *mut f64,
                    components: *mut f64, evr: *mut f64, mean: *mut f64, std: *mut f64, info: *mut SrxPcaInfo) -> i32;
     pub fn srx_pca_loadings(components: *const f64, std: *const f64, sel: *const u64, k: u64, n_pc: u64,

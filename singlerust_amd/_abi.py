@@ -142,6 +142,17 @@ class Flex(C.Structure):      # srx_flex
     _fields_ = [("kind", C.c_int32), ("absolute", C.c_uint32), ("relative", C.c_double)]
 
 
+class PearsonOpts(C.Structure):      # srx_pearson_opts
+    _fields_ = [("theta", C.c_double), ("clip", C.c_double)]
+
+
+class PearsonInfo(C.Structure):      # srx_pearson_info
+    _fields_ = [("n_cells", C.c_uint64), ("n_genes", C.c_uint64), ("n_expressed", C.c_uint64),
+                ("n_empty_cells", C.c_uint64), ("total", C.c_double), ("theta", C.c_double), ("clip", C.c_double),
+                ("sum_quantum", C.c_double), ("sq_quantum", C.c_double), ("ms_dense", C.c_double),
+                ("ms_sparse", C.c_double), ("ms_rank", C.c_double)]
+
+
 class PcaOpts(C.Structure):      # srx_pca_opts
     _fields_ = [("n_components", C.c_int32), ("center", C.c_int32), ("scale", C.c_int32), ("n_threads", C.c_int32),
                 ("block", C.c_int32), ("max_iter", C.c_int32), ("solver", C.c_int32), ("tol", C.c_double),
@@ -367,6 +378,9 @@ SIGNATURES = {
     "srx_log1p_inplace": (C.c_int32, [P]),
     "srx_normalize_log1p_inplace": (C.c_int32, [P, C.c_double, P]),
     "srx_select_hvg": (C.c_int32, [P, C.c_uint64, P, P]),
+    "srx_pearson_gene_variance": (C.c_int32, [P, C.POINTER(PearsonOpts), P, C.POINTER(PearsonInfo)]),
+    "srx_select_hvg_pearson": (C.c_int32, [P, C.c_uint64, C.POINTER(PearsonOpts), P, P, P, C.POINTER(PearsonInfo)]),
+    "srx_pearson_residuals": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PearsonOpts), P, C.POINTER(PearsonInfo)]),
     "srx_pca": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PcaOpts), P, P, P, P, P, C.POINTER(PcaInfo)]),
     "srx_pca_loadings": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint64, C.c_uint64, P]),
     "srx_pca_model_from_result": (C.c_int32, [P, C.POINTER(P)]),

@@ -378,6 +378,16 @@ int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, SelDev&
     return launch_sel_finish(m, d_rank, d_var, true, center, scale, out);
 }
 
+// The ranking alone, for any key array (pearson.hip): d_rank[j] += the number of genes before j under (key desc, index asc);
+// the caller has zeroed d_rank.  The full ranking: a key array has no sampled threshold to trust.
+int32_t rank_keys_device(srx_ctx* ctx, const double* d_key, uint64_t G, uint32_t* d_rank) {
+    if (G == 0) return SRX_OK;
+    hipLaunchKernelGGL(k_hvg_rank, dim3((unsigned)((G + 255) / 256), (unsigned)((G + kRankTile - 1) / kRankTile)), dim3(256), 0, ctx->stream,
+                       d_key, (uint32_t)G, d_rank);
+    SRX_HIP(ctx, hipGetLastError());
+    return SRX_OK;
+}
+
 // An explicit list: its rank table is the position of every gene in the list, so that the selection comes out in the
 // caller's order (1.2 MB to upload at 300 000 columns).  Needs the global moments of `m` where `vectors`.
 int32_t select_list(srx_mat* m, const uint64_t* genes, uint64_t k, int center, int scale, SelDev& out, bool vectors) {

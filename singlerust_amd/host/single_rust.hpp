@@ -324,6 +324,40 @@ inline IMAnnData filter_genes(const IMAnnData& a, const FlexValue& lo, const Fle
 inline void filter_cells_inplace(IMAnnData& a, const FlexValue& lo, const FlexValue& hi) { a = filter_impl(a, lo, hi, false); }
 inline void filter_genes_inplace(IMAnnData& a, const FlexValue& lo, const FlexValue& hi) { a = filter_impl(a, lo, hi, true); }
 
+// Not in the reference: scanpy's highly_variable_genes(flavor = "pearson_residuals") on the RAW counts (srx.h states the
+// definition).  The selected genes in rank order; var_bool()["highly_variable"] receives the mask that
+// FeatureSelection::HighlyVariableCol("highly_variable") reads.  theta 0 = 100, clip 0 = sqrt(n_obs).
+struct PearsonHvg {
+    std::vector<std::uint64_t> selected;                          // rank order
+    std::vector<double> residual_variances;                       // n_vars
+    srx_pearson_info info{};
+};
+inline PearsonHvg highly_variable_genes_pearson(IMAnnData& a, std::size_t n_top_genes = 2000, double theta = 100.0, double clip = 0.0) {
+    PearsonHvg r;
+    const srx_pearson_opts opts{theta, clip};
+    r.selected.resize(std::max<std::size_t>(std::min<std::size_t>(n_top_genes, a.n_vars()), 1));
+    r.residual_variances.resize(std::max<std::size_t>(a.n_vars(), 1));
+    std::uint64_t n_out = 0;
+    a.ctx().check(srx_select_hvg_pearson(a.x(), n_top_genes, &opts, r.selected.data(), &n_out, r.residual_variances.data(), &r.info));
+    r.selected.resize(n_out);
+    r.residual_variances.resize(a.n_vars());
+    std::vector<bool> mask(a.n_vars(), false);
+    for (std::uint64_t g : r.selected) mask[g] = true;
+    a.var_bool()["highly_variable"] = std::move(mask);
+    return r;
+}
+// scanpy's normalize_pearson_residuals restricted to a gene list: n_obs x genes.size() clipped residuals, zeros included.
+inline Array2 pearson_residuals(const IMAnnData& a, const std::vector<std::uint64_t>& genes, double theta = 100.0, double clip = 0.0) {
+    const srx_pearson_opts opts{theta, clip};
+    Array2 out;
+    out.nrows = a.n_obs();
+    out.ncols = genes.size();
+    out.data.assign(std::max<std::size_t>(out.nrows * out.ncols, 1), 0.0);
+    a.ctx().check(srx_pearson_residuals(a.x(), genes.data(), genes.size(), &opts, out.data.data(), nullptr));
+    out.data.resize(out.nrows * out.ncols);
+    return out;
+}
+
 namespace dim_red {                                              // src/memory/processing/dim_red/mod.rs
 inline std::vector<std::uint64_t> select_features(const IMAnnData& a, const FeatureSelection& fs) {   // :123-156
     switch (fs.kind) {
