@@ -300,8 +300,7 @@ int32_t srx_select_hvg(srx_mat* m, uint64_t n, uint64_t* idx_out, uint64_t* n_ou
  *   at most half a quantum of error to its gene's sum.  No floating-point atomics: results are bit-identical from call to call,
  *   and two identical columns get bit-identical variances wherever they sit.
  * Departures from scanpy: scanpy yields NaN for an empty cell (here 0) and leaves ties to an unstable argsort (here: gene
- *   index); batch_key (median rank over batches) and normalize_pearson_residuals followed by a PCA of the dense residuals are
- *   out of scope (the PCA here is sparse; the selection enters it as an explicit list).
+ *   index); batch_key (median rank over batches) is out of scope.
  * All three calls accept CSR and CSC handles at either value storage and any dtype, leave the handle as it was (values,
  *   logical dtype; the moments cache is filled with the moments of the current values if it was empty) and compute on the
  *   device only.  Non-integer values are accepted.
@@ -395,6 +394,75 @@ int32_t srx_pca(srx_mat* m, const uint64_t* sel, uint64_t k, const srx_pca_opts*
  * loadings row i = components[i,:] * std[i] (pca/mod.rs:204-215), other rows 0. */
 int32_t srx_pca_loadings(const double* components, const double* std_, const uint64_t* sel,
                          uint64_t k, uint64_t n_pc, uint64_t n_vars, double* out);
+
+/* ---- PCA of the Pearson residuals (not in the reference) ----------------------------------------------------------------------
+ * scanpy's experimental.pp.normalize_pearson_residuals_pca, the second half of recipe_pearson_residuals: the clipped residuals of
+ * a gene list, then their PCA, on RAW counts; additive, detected by symbol, no profiling class of its own (the times are in
+ * srx_pearson_pca_info).  The scores stay resident as the handle's PCA result: everything that reads "the resident scores of the
+ * handle" (neighbours, Harmony, the graph, clustering, the layouts) follows without a host round trip.  What goes through a
+ * fitted MODEL does not: srx_pca_model_from_result, and with it srx_doublets_result, which projects its simulated cells with
+ * srx_pca_transform, are refused on such a result (below).
+ *
+ * Definition.  m holds raw counts (CSR or CSC), genes lists k DISTINCT gene indices.  Z is the n x k matrix of the clipped
+ *   residuals z_ij exactly as the section above defines them (the same order of operations, in f64, no contraction; mu == 0
+ *   gives 0; an empty cell is a row of zeros, a listed gene with g_j = 0 a column of zeros), with the sums taken per `totals`:
+ *      SRX_PEARSON_TOTALS_ALL       r_i, g_j and T of the whole matrix: what srx_pearson_residuals does;
+ *      SRX_PEARSON_TOTALS_SELECTED  r_i and T are sums over the listed genes only (g_j is the same either way): what scanpy's
+ *                                   normalize_pearson_residuals_pca does, which subsets before it normalises.  r_i is summed
+ *                                   over the stored entries of the cell in one fixed order, T over the r_i as above.
+ *   The default clip stays sqrt(n_rows) either way.  Then
+ *      m_j    = (sum_i z_ij) / n                                       (center false: m = 0)
+ *      C      = (Z^T Z - n m m^T) / (n - 1)                            (no scaling)
+ *      the n_pc algebraically largest eigenpairs of C are the explained variances and the components V (k x n_pc)
+ *      evr_p  = eigenvalue_p / trace(C)
+ *      scores = (Z - 1 m^T) V
+ *   with the sign rule of srx_pca (the largest-|.| entry of each component is positive) and the components' rows in the
+ *   caller's gene order.  The solver works on (n - 1) C and on its trace, like srx_pca: the ratio is the same.
+ * How it is computed.  Z is dense and not low-rank once the clip is active: Z^T Z is a product of n x k doubles.  Z is made in
+ *   chunks of cells from the definition (chunk_cells rows; 0: what a quarter of the last-level cache holds, 64 MiB), each chunk
+ *   read back by an f64 matrix-core product: G += Z_c^T Z_c (upper triangle, 64 x 64 tiles) with the column sums of Z_c, the
+ *   Gram solver of srx_pca on C (plans, deflation rounds, robust mode and result block are shared), then the chunks again for
+ *   scores = Z_c V - 1 (m^T V).  No floating-point atomics; the chunks, and the slabs a chunk may be cut into, are added in
+ *   ascending order: two calls give bit-identical results, and the Gram matrix is symmetric bit for bit.
+ * The result block of the handle: mean = m, std = ones, the selection = the list; srx_result_fetch, srx_knn_result and every
+ *   other reader of the resident SCORES work as after srx_pca.  srx_pca_model_from_result is refused (SRX_E_ARG):
+ *   srx_pca_transform would apply normalise / log1p arithmetic to a residual model, and projecting new cells onto a residual
+ *   PCA is out of scope; srx_doublets_result on such a handle is refused for the same reason, with a message that says so.
+ * Options: `center` < 0 or 1: true, 0: false (pca.center is not read); pca.n_components, max_iter, tol, seed, solver (AUTO or
+ *   GRAM) as for srx_pca; opts == NULL: Pearson defaults, totals ALL, centred, 2 components.
+ * Departures from scanpy: scanpy yields NaN for an empty cell (here a row of zeros); the sign rule is this library's; scanpy is
+ *   not part of the test environment, nothing is compared with it.  batch_key stays out of scope.
+ * Refused, in this order: what the section above refuses without a pass over the matrix (a NULL handle or list, several ranks,
+ *   a backed session, theta, clip), an empty list, totals outside {0, 1}, k > 16384, a gene index >= n_cols, a repeated gene,
+ *   pca.scale > 0, pca.solver == SRX_SOLVER_SPMM (all SRX_E_ARG); k < 2 or n < 5 (SRX_E_SHAPE, as srx_pca; srx_pca_pearson
+ *   only); a negative, NaN or infinite stored value (SRX_E_ARG, found on the device). */
+typedef enum srx_pearson_totals {
+    SRX_PEARSON_TOTALS_ALL = 0,
+    SRX_PEARSON_TOTALS_SELECTED = 1
+} srx_pearson_totals;
+typedef struct srx_pearson_pca_opts {
+    srx_pearson_opts pearson;
+    int32_t  totals;        /* srx_pearson_totals                                          */
+    int32_t  center;        /* < 0 or 1: true, 0: false                                    */
+    uint64_t chunk_cells;   /* cells per chunk of Z; 0: auto                               */
+    srx_pca_opts pca;
+} srx_pearson_pca_opts;
+typedef struct srx_pearson_pca_info {
+    uint64_t n_cells, n_genes, n_expressed /* g_j > 0, whole matrix */, n_empty_cells /* r_i == 0 under `totals` */;
+    double   total, theta, clip;           /* T under `totals` and the values actually used */
+    srx_pca_info pca;                      /* nnz_selected is 0: the residuals are dense   */
+    double   ms_gram, ms_solve, ms_scores; /* chunks + SYRK; the eigen-solve; chunks + score product */
+    uint64_t n_chunks, chunk_cells, chunk_bytes;   /* chunk_bytes: one chunk of Z as stored (rows padded to 64 columns) */
+} srx_pearson_pca_info;
+/* Host outputs, each may be NULL: scores n_rows x n_pc, components k x n_pc (rows in the caller's gene order), evr n_pc,
+ * mean k (m, the caller's order).  SRX_E_NOCONV as for srx_pca. */
+int32_t srx_pca_pearson(srx_mat* m, const uint64_t* genes, uint64_t k, const srx_pearson_pca_opts* opts, double* scores,
+                        double* components, double* evr, double* mean, srx_pearson_pca_info* info);
+/* Kernel-level entry (as srx_spmm for the sparse kernels): Z^T Z (k x k, both triangles, the caller's gene order) and the
+ * column sums of Z, so that the SYRK can be checked alone.  opts->center and opts->pca are not read; one of the two outputs
+ * may be NULL; k >= 1 (an empty list is SRX_E_ARG) and any n. */
+int32_t srx_pearson_gram(srx_mat* m, const uint64_t* genes, uint64_t k, const srx_pearson_pca_opts* opts,
+                         double* gram_out /* k x k, host */, double* colsum_out /* k, host */, srx_pearson_pca_info* info);
 
 /* ---- a fitted PCA applied to other cells: Pca::transform (src/shared/processing/pca/mod.rs:156-185)
  * A model is k feature rows (V: k x n_pc, mu, sd, flags center / scale) held on the device.  For a query
@@ -1217,7 +1285,7 @@ void    srx_harmony_free(srx_harmony* h);
  *    together and a workgroup to a longer one; the result does not depend on which.
  * Refused with SRX_E_ARG and a message, nothing launched (*out is left untouched): a NULL argument (info, parents and
  *    parents_out may be NULL); counts in CSC storage (convert with srx_matrix_to_csr); a context with more than one rank; fitted
- *    without a PCA result; cell or gene counts of the two matrices that differ; n == 0; n_sim == 0 in srx_doublets_result;
+ *    without a PCA result, or with the PCA of Pearson residuals (srx_pca_pearson: no model to project with); cell or gene counts of the two matrices that differ; n == 0; n_sim == 0 in srx_doublets_result;
  *    n + n_sim >= 2^32; sim_ratio negative or non-finite; expected_rate outside (0, 1); stdev_rate negative or NaN; bad
  *    transform bits; k negative; k_adj outside 1 .. SRX_DOUBLET_MAX_K or above n + n_sim - 1; n_dims above the scores'
  *    components; in the list form k_adj == 0, n_obs == 0 or an index >= n_obs + n_sim.  SRX_E_BOUNDS: a given parent >= n.

@@ -257,6 +257,33 @@ impl<'c> DeviceX<'c> {
         Ok(out)
     }
 
+    /// scanpy's `normalize_pearson_residuals_pca` on the RAW counts: PCA of the clipped residuals of `genes` (srx.h states the
+    /// definition).  Returns (scores n_obs x n_pc row-major, components genes.len() x n_pc, explained variance ratio, the info
+    /// block); the scores also stay resident as the handle's PCA result.  `selected_totals`: the cell sums and the total over
+    /// the listed genes (scanpy) instead of the whole matrix.
+    pub fn pca_pearson_residuals(&self, genes: &[u64], n_components: usize, theta: Option<f64>, clip: Option<f64>,
+                                 selected_totals: bool, center: bool) -> Result<(Vec<f64>, Vec<f64>, Vec<f64>, SrxPearsonPcaInfo)> {
+        let mut opts: SrxPearsonPcaOpts = unsafe { std::mem::zeroed() };
+        opts.pearson = SrxPearsonOpts { theta: theta.unwrap_or(0.0), clip: clip.unwrap_or(0.0) };
+        opts.totals = if selected_totals { 1 } else { 0 };
+        opts.center = if center { 1 } else { 0 };
+        opts.pca.n_components = n_components as i32;
+        opts.pca.center = -1;
+        let n_pc = n_components.min(genes.len());
+        let mut scores = vec![0f64; (self.n_obs * n_pc).max(1)];
+        let mut comps = vec![0f64; (genes.len() * n_pc).max(1)];
+        let mut evr = vec![0f64; n_pc.max(1)];
+        let mut info: SrxPearsonPcaInfo = unsafe { std::mem::zeroed() };
+        self.ctx.check(unsafe {
+            srx_pca_pearson(self.mat, genes.as_ptr(), genes.len() as u64, &opts, scores.as_mut_ptr(), comps.as_mut_ptr(),
+                            evr.as_mut_ptr(), null_mut(), &mut info)
+        })?;
+        scores.truncate(self.n_obs * n_pc);
+        comps.truncate(genes.len() * n_pc);
+        evr.truncate(n_pc);
+        Ok((scores, comps, evr, info))
+    }
+
     /// dim_red/mod.rs:24-94 without the dense N x k matrix: returns (scores N x n_pc row-major, explained variance
     /// ratio, selected features) — exactly what `attach_pca_results` (:96-121) takes; `n_threads` is accepted and ignored,
     /// the `svd_mode` marker has no counterpart.

@@ -62,6 +62,8 @@ pub const SRX_FLEX_RELATIVE: i32 = 2;
 pub const SRX_SOLVER_AUTO: i32 = 0;
 pub const SRX_SOLVER_GRAM: i32 = 1;
 pub const SRX_SOLVER_SPMM: i32 = 2;
+pub const SRX_PEARSON_TOTALS_ALL: i32 = 0;
+pub const SRX_PEARSON_TOTALS_SELECTED: i32 = 1;
 pub const SRX_GRAPH_DISTANCES: i32 = 0;
 pub const SRX_GRAPH_CONNECTIVITIES: i32 = 1;
 pub const SRX_MARKERS_CNT: i32 = 0;
@@ -214,6 +216,35 @@ pub struct SrxPcaInfo {      // `srx_pca_info`
     pub nnz_selected: u64,
     pub solver: u32,
     pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxPearsonPcaOpts {      // `srx_pearson_pca_opts`
+    pub pearson: SrxPearsonOpts,
+    pub totals: i32,
+    pub center: i32,
+    pub chunk_cells: u64,
+    pub pca: SrxPcaOpts,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxPearsonPcaInfo {      // `srx_pearson_pca_info`
+    pub n_cells: u64,
+    pub n_genes: u64,
+    pub n_expressed: u64,
+    pub n_empty_cells: u64,
+    pub total: f64,
+    pub theta: f64,
+    pub clip: f64,
+    pub pca: SrxPcaInfo,
+    pub ms_gram: f64,
+    pub ms_solve: f64,
+    pub ms_scores: f64,
+    pub n_chunks: u64,
+    pub chunk_cells: u64,
+    pub chunk_bytes: u64,
 }
 
 #[repr(C)]
@@ -660,6 +691,11 @@ extern "C" {
                    components: *mut f64, evr: *mut f64, mean: *mut f64, std: *mut f64, info: *mut SrxPcaInfo) -> i32;
     pub fn srx_pca_loadings(components: *const f64, std: *const f64, sel: *const u64, k: u64, n_pc: u64,
                             n_vars: u64, out: *mut f64) -> i32;
+    pub fn srx_pca_pearson(m: *mut SrxMat, genes: *const u64, k: u64, opts: *const SrxPearsonPcaOpts,
+                           scores: *mut f64, components: *mut f64, evr: *mut f64, mean: *mut f64,
+                           info: *mut SrxPearsonPcaInfo) -> i32;
+    pub fn srx_pearson_gram(m: *mut SrxMat, genes: *const u64, k: u64, opts: *const SrxPearsonPcaOpts,
+                            gram_out: *mut f64, colsum_out: *mut f64, info: *mut SrxPearsonPcaInfo) -> i32;
     pub fn srx_pca_model_from_result(m: *mut SrxMat, out: *mut *mut SrxPcaModel) -> i32;
     pub fn srx_pca_model_create(ctx: *mut SrxCtx, k: u64, n_pc: u64, components: *const f64, mean: *const f64,
                                 std: *const f64, sel: *const u64, center: i32, scale: i32,

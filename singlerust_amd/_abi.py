@@ -64,6 +64,8 @@ FLEX_RELATIVE = 2
 SOLVER_AUTO = 0
 SOLVER_GRAM = 1
 SOLVER_SPMM = 2
+PEARSON_TOTALS_ALL = 0
+PEARSON_TOTALS_SELECTED = 1
 GRAPH_DISTANCES = 0
 GRAPH_CONNECTIVITIES = 1
 MARKERS_CNT = 0
@@ -163,6 +165,18 @@ class PcaInfo(C.Structure):      # srx_pca_info
     _fields_ = [("n_cells_global", C.c_uint64), ("k", C.c_uint32), ("n_pc", C.c_uint32), ("block", C.c_uint32),
                 ("n_iter", C.c_uint32), ("residual", C.c_double), ("nnz_selected", C.c_uint64),
                 ("solver", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class PearsonPcaOpts(C.Structure):      # srx_pearson_pca_opts
+    _fields_ = [("pearson", PearsonOpts), ("totals", C.c_int32), ("center", C.c_int32), ("chunk_cells", C.c_uint64),
+                ("pca", PcaOpts)]
+
+
+class PearsonPcaInfo(C.Structure):      # srx_pearson_pca_info
+    _fields_ = [("n_cells", C.c_uint64), ("n_genes", C.c_uint64), ("n_expressed", C.c_uint64),
+                ("n_empty_cells", C.c_uint64), ("total", C.c_double), ("theta", C.c_double), ("clip", C.c_double),
+                ("pca", PcaInfo), ("ms_gram", C.c_double), ("ms_solve", C.c_double), ("ms_scores", C.c_double),
+                ("n_chunks", C.c_uint64), ("chunk_cells", C.c_uint64), ("chunk_bytes", C.c_uint64)]
 
 
 class KnnOpts(C.Structure):      # srx_knn_opts
@@ -383,6 +397,8 @@ SIGNATURES = {
     "srx_pearson_residuals": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PearsonOpts), P, C.POINTER(PearsonInfo)]),
     "srx_pca": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PcaOpts), P, P, P, P, P, C.POINTER(PcaInfo)]),
     "srx_pca_loadings": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint64, C.c_uint64, P]),
+    "srx_pca_pearson": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PearsonPcaOpts), P, P, P, P, C.POINTER(PearsonPcaInfo)]),
+    "srx_pearson_gram": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PearsonPcaOpts), P, P, C.POINTER(PearsonPcaInfo)]),
     "srx_pca_model_from_result": (C.c_int32, [P, C.POINTER(P)]),
     "srx_pca_model_create": (C.c_int32, [P, C.c_uint64, C.c_uint64, P, P, P, P, C.c_int32, C.c_int32, C.POINTER(P)]),
     "srx_pca_model_info": (C.c_int32, [P, P, P, P]),

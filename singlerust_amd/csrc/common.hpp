@@ -150,6 +150,7 @@ struct srx_pca_state {           // what the last srx_pca / srx_pipeline left in
     bool valid = false;
     uint32_t k = 0, n_pc = 0;
     int center = 1, scale = 1;       // the flags the solve ran with (srx_pca_model_from_result)
+    bool residual = false;           // the result is a PCA of Pearson residuals (srx_pca_pearson): no model can be made of it
     std::vector<int> round_counts;   // components resolved by each deflation round (sums to n_pc); set by run_pca with its plan
     double* d_scores = nullptr;      // n_rows x n_pc, row-major f64
     size_t scores_cap = 0;

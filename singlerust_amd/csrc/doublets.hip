@@ -556,6 +556,9 @@ int32_t srx_doublets_result(srx_mat* fitted, srx_mat* counts, const srx_doublet_
     }
     SRX_TRY(rates_check(ctx, o.rho, o.se_rho));
     if (!fitted->pca.valid || !fitted->pca.d_small) return fail(ctx, SRX_E_ARG, "doublets: no PCA result on the fitted matrix");
+    if (fitted->pca.residual)
+        return fail(ctx, SRX_E_ARG, "doublets: the fitted result is a PCA of Pearson residuals (srx_pca_pearson); the simulated cells are "
+                                    "projected by srx_pca_transform, which has no residual model");
     if (counts->csc) return fail(ctx, SRX_E_ARG, "doublets: counts are in CSC storage; convert with srx_matrix_to_csr");
     const uint64_t n = counts->n_rows;
     const uint64_t fit_cells = fitted->csc ? fitted->n_cols : fitted->n_rows, fit_genes = fitted->csc ? fitted->n_rows : fitted->n_cols;

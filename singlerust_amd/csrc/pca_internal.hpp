@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <numeric>
 #include <string>
 #include <type_traits>
@@ -214,7 +215,16 @@ inline PcaResultLayout result_block(const srx_pca_state& st) { return PcaResultL
 // solver only): st.info, the solve at the precisions of (f32 storage, o.solver), and the small results moved from the context's
 // scratch into the matrix's own result block (host copies: pca_materialize).  A solve that broke down before it had a block
 // returns its code with st.valid false.
+// A second source of the Gram solver (pearson_pca.hip): `parts` null, `gram_packed` the ready packed upper triangle of Z^T Z of a
+// DENSE n_rows x k matrix in f64 that never exists as a whole, sel.d_mu its column means.  The round hands its panel to
+// `write_scores`, which writes columns [col0, col0 + n_r) of the scores, Z P - 1 cvec^T, at the stride `ld`.
+struct DenseSource {
+    int k = 0;
+    uint64_t n_rows = 0;
+    std::function<int32_t(const double* panel, const double* cvec, int col0, int n_r, double* scores, int ld)> write_scores;
+};
 int32_t solve_and_stash(srx_ctx* ctx, bool f32, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed,
-                        const Resolved& o, const SelDev& sel, int l_act, uint64_t n_cells, uint64_t nnz_selected, srx_pca_state& st);
+                        const Resolved& o, const SelDev& sel, int l_act, uint64_t n_cells, uint64_t nnz_selected, srx_pca_state& st,
+                        const DenseSource* dense = nullptr);
 
 }  // namespace srx

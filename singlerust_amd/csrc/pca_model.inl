@@ -284,6 +284,9 @@ int32_t srx_pca_model_from_result(srx_mat* m, srx_pca_model** out) {
     srx_ctx* ctx = m->ctx;
     const srx_pca_state& st = m->pca;
     if (!st.valid || !st.d_small) return fail(ctx, SRX_E_ARG, "srx_pca_model_from_result: no PCA result on this matrix");
+    if (st.residual)
+        return fail(ctx, SRX_E_ARG, "srx_pca_model_from_result: the result is a PCA of Pearson residuals (srx_pca_pearson); "
+                                    "srx_pca_transform would apply normalise / log1p arithmetic to a residual model");
     SRX_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t k = st.k, n_pc = st.n_pc;
     srx_pca_model* p = nullptr;

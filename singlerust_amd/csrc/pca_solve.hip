@@ -738,10 +738,10 @@ int32_t ensure_result_capacity(srx_ctx* ctx, srx_pca_state& st, size_t need) {
 
 template <typename VT, typename PT>
 static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed,
-                       const Resolved& o, const SelDev& sel, int l_act, double n_cells, srx_pca_state& st) {
+                       const Resolved& o, const SelDev& sel, int l_act, double n_cells, srx_pca_state& st, const DenseSource* dense) {
     const RowMajor* rmp = n_parts == 1 ? &parts[0] : nullptr;
-    const int k = parts[0].k;
-    struct { uint64_t n_rows, max_rows; } cc{0, 0};
+    const int k = dense ? dense->k : parts[0].k;
+    struct { uint64_t n_rows, max_rows; } cc{dense ? dense->n_rows : 0, 0};
     for (int i = 0; i < n_parts; ++i) {
         cc.n_rows += parts[i].n_rows;
         cc.max_rows = std::max(cc.max_rows, parts[i].n_rows);
@@ -799,7 +799,10 @@ static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const T
         // at c3 against 0.84 — when its view was made: the matrix-free solver)
         uint64_t row0 = 0;
         const int ld_s = scores_ld(n_pc);
-        if (t256p) {
+        if (dense) {                            // the dense source writes its own scores from the panel
+            if constexpr (std::is_same_v<PT, double>) SRX_TRY(dense->write_scores(P, cvec, col0, n_r, st.d_scores, ld_s));
+            else return fail(ctx, SRX_E_ARG, "pca: a dense source is solved in f64");
+        } else if (t256p) {
             SRX_TRY((launch_fwd<VT, PT>(ctx, *t256p, P, cvec, Y, st.d_scores + col0, n_r, ld_s)));
         } else {
             for (int i = 0; i < n_parts; ++i) {
@@ -904,7 +907,7 @@ static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const T
             bool reduced = false;
             SRX_TRY(launch_gram<VT>(ctx, *rmp, Pk, &reduced, true));  // (a fresh sum: zeroed on the way; sharded rows: the exchange overlaps the second half)
             if (!reduced) SRX_TRY(allreduce_f64(ctx, Pk, n_packed));
-        } else {
+        } else if (!dense) {
             SRX_TRY(allreduce_f64(ctx, Pk, n_packed));            // the one exchange of this solver: the packed upper triangle
         }
         auto reset = [&]() -> int32_t {
@@ -930,6 +933,7 @@ static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const T
         SRX_TRY(attr_dense_apply(ctx));
         SRX_TRY(solve(apply, C, true, reset, deflate));
     } else {
+        if (dense) return fail(ctx, SRX_E_ARG, "pca: a dense source needs the Gram solver");
         if (n_parts != 1 || !t256p) return fail(ctx, SRX_E_ARG, "pca: the SpMM solver needs the matrix resident in one piece");
         const Tiled& t256 = *t256p;
         // matrix-free: Z^T (Z W) by a forward and a transposed SpMM; resolved eigenpairs are deflated IMPLICITLY,
@@ -1057,9 +1061,11 @@ static int32_t stash_results(srx_ctx* ctx, srx_pca_state& st, int k, int n_pc, c
 }
 
 int32_t solve_and_stash(srx_ctx* ctx, bool f32, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed,
-                        const Resolved& o, const SelDev& sel, int l_act, uint64_t n_cells, uint64_t nnz_selected, srx_pca_state& st) {
-    const int k = parts[0].k;
+                        const Resolved& o, const SelDev& sel, int l_act, uint64_t n_cells, uint64_t nnz_selected, srx_pca_state& st,
+                        const DenseSource* dense) {
+    const int k = dense ? dense->k : parts[0].k;
     st.valid = false;
+    st.residual = dense != nullptr;
     st.info = srx_pca_info{};
     st.info.n_cells_global = n_cells;
     st.info.k = (uint32_t)k;
@@ -1071,7 +1077,7 @@ int32_t solve_and_stash(srx_ctx* ctx, bool f32, const RowMajor* parts, int n_par
     // panels in f64 (f32 products of Z W level the residuals of the small components off at ~1e-7 theta_1 / theta_i:
     // 6.6e-5 at k = 9000 on a flat-tailed matrix, however many sweeps)
     const auto run = !f32 ? run_pca<double, double> : o.solver == 2 ? run_pca<float, double> : run_pca<float, float>;
-    const int32_t rc = run(ctx, parts, n_parts, t256p, gram_packed, o, sel, l_act, (double)n_cells, st);
+    const int32_t rc = run(ctx, parts, n_parts, t256p, gram_packed, o, sel, l_act, (double)n_cells, st, dense);
     if ((rc != SRX_OK && rc != SRX_E_NOCONV) || !st.d_small) return rc;      // d_small unset: the solve broke down early
     SRX_TRY(stash_results(ctx, st, k, o.n_pc, sel));
     return rc;

@@ -9,7 +9,7 @@
 // cells with the stored entries merged in and evaluates every pair as defined (k_pr_gene_direct).  The order of every sum is
 // fixed: cell chunks in ascending order, a CSC gene's cells by lane and butterfly.  The ranking is select.hip's
 // (rank_keys_device).
-#include "common.hpp"
+#include "pearson_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -33,22 +33,6 @@ constexpr int kPrSparseMinRows = 64;         // ... of at least this many rows
 constexpr int kPrBlockTile = 256;            // outputs per workgroup of the block kernel
 constexpr uint64_t kPrBlockBytes = 1ull << 30;
 
-struct PrArgs {
-    double total;          // T
-    double theta;          // the value in use (+inf: Poisson)
-    double inv_theta;      // 1 / theta (0: Poisson), the dense form's factor
-    double clip;           // the value in use (+inf: none)
-    int poisson;
-};
-
-// z of srx.h for one pair, in the order written there.  T == 0 makes mu NaN, which fails the test like mu == 0.
-__device__ __forceinline__ double pr_resid(double x, double r, double g, const PrArgs& a) {
-    const double mu = (r * g) / a.total;
-    if (!(mu > 0.0)) return 0.0;
-    const double s = a.poisson ? sqrt(mu) : sqrt(mu + (mu * mu) / a.theta);
-    const double z = (x - mu) / s;
-    return fmin(fmax(z, -a.clip), a.clip);
-}
 // The residual of a zero entry in the dense pass's form: f = -min(mu / sqrt(mu (1 + mu / theta)), c) from mu = r_i * (g_j / T),
 // and its square.  One division and one root; the dense pass and the corrections call THIS function, so that what a stored
 // entry takes off again is bit for bit what the dense pass put in.
@@ -310,16 +294,7 @@ __global__ __launch_bounds__(kPrBlockTile) void k_pr_block(const int64_t* __rest
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-struct PrPrep {
-    uint64_t n = 0, G = 0;               // cells, genes of X
-    const double* d_cell = nullptr;      // r_i
-    const double* d_gene = nullptr;      // g_j
-    double* d_gene_a = nullptr;          // g_j / T
-    uint64_t n_expressed = 0, n_empty = 0;
-    PrArgs a{};
-};
-
-static int32_t pr_check_args(srx_mat* m, const srx_pearson_opts* opts, const char* who, PrArgs& a, uint64_t n_cells) {
+int32_t pr_check_args(srx_mat* m, const srx_pearson_opts* opts, const char* who, PrArgs& a, uint64_t n_cells) {
     srx_ctx* ctx = m->ctx;
     if (ctx->n_ranks > 1) return fail(ctx, SRX_E_ARG, "%s: a context with more than one rank (the sharded form is out of scope)", who);
     if (ctx->pool_on > 0) return fail(ctx, SRX_E_ARG, "%s: a backed session is open on this context (the out-of-core form is out of scope)", who);
@@ -334,7 +309,7 @@ static int32_t pr_check_args(srx_mat* m, const srx_pearson_opts* opts, const cha
 }
 
 // Everything the three calls share: the arguments, the value check, r, g, T and the counts.  One small read-back.
-static int32_t pr_prepare(srx_mat* m, const srx_pearson_opts* opts, const char* who, PrPrep& p) {
+int32_t pr_prepare(srx_mat* m, const srx_pearson_opts* opts, const char* who, PrPrep& p) {
     srx_ctx* ctx = m->ctx;
     p.n = m->csc ? m->n_cols : m->n_rows;
     p.G = m->csc ? m->n_rows : m->n_cols;
@@ -380,7 +355,7 @@ static int32_t pr_prepare(srx_mat* m, const srx_pearson_opts* opts, const char* 
     return SRX_OK;
 }
 
-static void pr_info(const PrPrep& p, srx_pearson_info* info) {
+void pr_info(const PrPrep& p, srx_pearson_info* info) {
     if (!info) return;
     memset(info, 0, sizeof *info);
     info->n_cells = p.n;
@@ -390,6 +365,22 @@ static void pr_info(const PrPrep& p, srx_pearson_info* info) {
     info->total = p.a.total;
     info->theta = p.a.theta;
     info->clip = p.a.clip;
+}
+
+// T and the empty cells of another set of per-cell sums (pearson_pca.hip: the sums over the listed genes), by the kernel and in
+// the order of pr_prepare
+int32_t pr_totals(srx_ctx* ctx, const double* d_cell, uint64_t n, const double* d_gene, uint64_t G, double* total, uint64_t* n_empty) {
+    char* d_small;
+    SRX_TRY(scratch(ctx, "pearson_small2", 256, (void**)&d_small));
+    SRX_HIP(ctx, hipMemsetAsync(d_small, 0, 256, ctx->stream));
+    hipLaunchKernelGGL(k_pr_totals, dim3(1), dim3(1024), 0, ctx->stream, d_cell, n, d_gene, G, reinterpret_cast<double*>(d_small),
+                       reinterpret_cast<uint64_t*>(d_small + 8));
+    SRX_HIP(ctx, hipGetLastError());
+    unsigned char host[24];
+    SRX_TRY(d2h(ctx, host, d_small, sizeof host));
+    memcpy(total, host, 8);
+    memcpy(n_empty, host + 16, 8);
+    return SRX_OK;
 }
 
 // 2^shift with 2^(61 - shift) >= bound: the fixed-point scale of a sum whose magnitude stays below `bound`

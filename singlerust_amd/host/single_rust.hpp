@@ -358,6 +358,43 @@ inline Array2 pearson_residuals(const IMAnnData& a, const std::vector<std::uint6
     return out;
 }
 
+// scanpy's normalize_pearson_residuals_pca on the RAW counts: PCA of the clipped residuals of `genes` (srx.h states the
+// definition).  The scores stay resident as the handle's PCA result (neighbours, Harmony, ... read them there) and are stored as
+// obsm["X_pca"]; selected_totals: the cell sums and the total over the listed genes (scanpy) instead of the whole matrix.
+struct PearsonPca {
+    Array2 scores, components;                                    // n_obs x n_pc, genes.size() x n_pc
+    std::vector<double> explained_variance_ratio, mean;
+    srx_pearson_pca_info info{};
+};
+inline PearsonPca pca_pearson_residuals(IMAnnData& a, const std::vector<std::uint64_t>& genes, int n_components = 50, double theta = 100.0,
+                                        double clip = 0.0, bool selected_totals = true, bool center = true) {
+    srx_pearson_pca_opts opts{};
+    opts.pearson = srx_pearson_opts{theta, clip};
+    opts.totals = selected_totals ? SRX_PEARSON_TOTALS_SELECTED : SRX_PEARSON_TOTALS_ALL;
+    opts.center = center ? 1 : 0;
+    opts.pca.n_components = n_components;
+    opts.pca.center = -1;
+    PearsonPca r;
+    const std::size_t k = genes.size();
+    const std::size_t n_pc = std::min<std::size_t>(n_components < 0 ? 2 : (std::size_t)n_components, k);
+    r.scores.nrows = a.n_obs();
+    r.scores.ncols = n_pc;
+    r.components.nrows = k;
+    r.components.ncols = n_pc;
+    r.scores.data.assign(std::max<std::size_t>(a.n_obs() * n_pc, 1), 0.0);
+    r.components.data.assign(std::max<std::size_t>(k * n_pc, 1), 0.0);
+    r.explained_variance_ratio.assign(std::max<std::size_t>(n_pc, 1), 0.0);
+    r.mean.assign(std::max<std::size_t>(k, 1), 0.0);
+    a.ctx().check(srx_pca_pearson(a.x(), genes.data(), k, &opts, r.scores.data.data(), r.components.data.data(),
+                                  r.explained_variance_ratio.data(), r.mean.data(), &r.info));
+    r.scores.data.resize(a.n_obs() * n_pc);
+    r.components.data.resize(k * n_pc);
+    r.explained_variance_ratio.resize(n_pc);
+    r.mean.resize(k);
+    a.obsm()["X_pca"] = r.scores;
+    return r;
+}
+
 namespace dim_red {                                              // src/memory/processing/dim_red/mod.rs
 inline std::vector<std::uint64_t> select_features(const IMAnnData& a, const FeatureSelection& fs) {   // :123-156
     switch (fs.kind) {

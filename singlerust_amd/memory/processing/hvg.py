@@ -1,6 +1,7 @@
 """Highly variable genes by analytic Pearson residuals over libsrx_hip (``srx_select_hvg_pearson``, ``srx_pearson_residuals``):
 what ``sc.experimental.pp.highly_variable_genes(flavor="pearson_residuals")`` and ``normalize_pearson_residuals`` give, on
-the RAW counts, before ``normalize_total`` / ``log1p``.
+the RAW counts, before ``normalize_total`` / ``log1p``; and the PCA of the residuals of the chosen genes
+(``srx_pca_pearson``: ``sc.experimental.pp.normalize_pearson_residuals_pca``), whose scores stay on the device.
 
 Not in the reference.  The definition (include/srx.h) is scanpy's closed form; every residual is evaluated on the device, the
 matrix never leaves it.  Departures from scanpy: an empty cell has residual 0 (scanpy: NaN), equal variances are ordered by gene
@@ -82,3 +83,60 @@ def pearson_residuals(adata, genes, theta=100.0, clip=None) -> np.ndarray:
     dst = out if out.size else np.zeros(1)           # (the C call refuses a NULL output also where nothing is written)
     F.check(F.lib().srx_pearson_residuals(m.handle, F.ptr(g) if g.size else None, g.size, C.byref(o), F.ptr(dst), None), m.ctx.handle)
     return out
+
+
+TOTALS = {"all": F.PEARSON_TOTALS_ALL, "selected": F.PEARSON_TOTALS_SELECTED}
+
+
+def _pca_opts(theta, clip, totals, center, chunk_cells, n_components, max_iter=0, tol=0.0, seed=0, solver=0) -> F.PearsonPcaOpts:
+    if totals not in TOTALS:
+        raise ValueError("totals must be 'all' or 'selected', not %r" % (totals,))
+    pca = F.PcaOpts(int(n_components), -1, 0, -1, 0, int(max_iter), int(solver), float(tol), int(seed))
+    return F.PearsonPcaOpts(_opts(theta, clip), TOTALS[totals], int(bool(center)), int(chunk_cells), pca)
+
+
+def _pca_info(i) -> dict:
+    out = {n: getattr(i, n) for n, _ in i._fields_ if n != "pca"}
+    out.update(flat_info(i.pca))
+    return out
+
+
+def pearson_gram(adata, genes, theta=100.0, clip=None, totals="selected", chunk_cells=0):
+    """(Z^T Z (k x k), column sums of Z (k), info dict) of the clipped residuals Z of the listed genes: ``srx_pearson_gram``,
+    the kernel-level entry of ``pca_pearson_residuals``.  An empty list is refused (``SrxError``, ``E_ARG``)."""
+    m = _matrix(adata)
+    g = np.ascontiguousarray(genes, dtype=np.uint64).ravel()
+    gram, colsum = np.zeros((g.size, g.size), dtype=np.float64), np.zeros(g.size, dtype=np.float64)
+    o, i = _pca_opts(theta, clip, totals, True, chunk_cells, -1), F.PearsonPcaInfo()
+    F.check(F.lib().srx_pearson_gram(m.handle, F.ptr(g) if g.size else None, g.size, C.byref(o), F.ptr(gram), F.ptr(colsum), C.byref(i)),
+            m.ctx.handle)
+    return gram, colsum, _pca_info(i)
+
+
+def pca_pearson_residuals(adata, genes=None, n_top_genes=2000, n_components=50, theta=100.0, clip=None, totals="selected",
+                          center=True, chunk_cells=0, max_iter=0, tol=0.0, seed=0, solver=0) -> dict:
+    """PCA of the clipped Pearson residuals of ``genes`` on the RAW counts (``srx_pca_pearson``).  ``genes`` None: the
+    ``n_top_genes`` of ``highly_variable_genes_pearson`` (same theta and clip) are selected first.  ``totals``: "selected" takes the
+    cell sums and the total over the listed genes (scanpy, which subsets before it normalises), "all" over the whole matrix
+    (``pearson_residuals``).  The scores stay resident as the handle's PCA result (``neighbors``, ``harmony_integrate``, ... read
+    them there); an ``IMAnnData`` also receives ``obsm["X_pca"]`` and ``uns["pca"]`` (``std`` is ones: no scaling).  Returns the
+    info dict.  No ``PcaModel`` can be made of this result."""
+    m = _matrix(adata)
+    if genes is None:
+        genes = highly_variable_genes_pearson(adata, n_top_genes, theta, clip)
+    g = np.ascontiguousarray(genes, dtype=np.uint64).ravel()
+    k, n = g.size, int(m.info().n_rows)
+    n_pc = max(min(2 if int(n_components) < 0 else int(n_components), k), 0)
+    scores, comps = np.zeros((n, n_pc), dtype=np.float64), np.zeros((k, n_pc), dtype=np.float64)
+    evr, mean = np.zeros(n_pc, dtype=np.float64), np.zeros(k, dtype=np.float64)
+    o, i = _pca_opts(theta, clip, totals, center, chunk_cells, n_components, max_iter, tol, seed, solver), F.PearsonPcaInfo()
+    F.check(F.lib().srx_pca_pearson(m.handle, F.ptr(g) if k else None, k, C.byref(o), F.ptr(scores) if scores.size else None,
+                                    F.ptr(comps) if comps.size else None, F.ptr(evr) if n_pc else None, F.ptr(mean) if k else None,
+                                    C.byref(i)), m.ctx.handle)
+    info = _pca_info(i)
+    if isinstance(adata, IMAnnData):
+        adata.obsm["X_pca"] = scores
+        adata.uns["pca"] = {"components": comps, "explained_variance_ratio": evr, "mean": mean, "std": np.ones(k),
+                            "selected_features": g, "n_iter": info["n_iter"], "residual": info["residual"], "solver": info["solver"],
+                            "center": bool(center), "scale": False, "residuals": "pearson", "totals": totals}
+    return dict(info, scores=scores, components=comps, explained_variance_ratio=evr, mean=mean, selected_features=g)
