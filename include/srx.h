@@ -40,7 +40,8 @@ extern "C" {
                                   their own: the time is in srx_louvain_info.ms) and srx_group_moments / srx_rank_genes_groups[_graph] /
                                   srx_markers_* (no class either: srx_markers_info.ms) and srx_diffmap[_csr] /
                                   srx_graph_diffmap_fetch / srx_graph_transitions_fetch / srx_dpt[_from] (srx_diffmap_info.ms) and
-                                  srx_iterate_op (the dense solver's kernels one at a time: tests and diagnostics) */
+                                  srx_iterate_op (the dense solver's kernels one at a time: tests and diagnostics) and
+                                  srx_select_op (the feature selection on host arrays, every route: tests and diagnostics) */
 
 typedef struct srx_ctx srx_ctx;   /* one GPU + stream + (optional) RCCL communicator      */
 typedef struct srx_mat srx_mat;   /* device-resident CSR (the `X` of an IMAnnData)        */
@@ -1399,6 +1400,55 @@ typedef struct srx_iterate_args {
     int32_t reserved;
 } srx_iterate_args;
 int32_t srx_iterate_op(srx_ctx* ctx, int32_t op, srx_iterate_args* args);
+
+/* The feature selection of the PCA on caller-supplied host arrays: a test and diagnostics entry with NO stability promise
+ * (additive: detected by symbol, the ABI version stays).  The arrays are uploaded into fresh device buffers of exactly their
+ * sizes, each followed by 8 sentinel elements; the kernels are launched by the function the pipeline launches them through
+ * (select.hip: k_gene_var, k_hvg_candidates, k_rank_selected / k_hvg_rank, k_sel_finish), the stream is drained and everything
+ * comes back.  k = min(take, G) genes are selected; n_words = ceil(G / 32).
+ *
+ *   op    reads                                                         writes
+ *   HVG   cnt, sum, sq (G each: the per-gene nonzero count, sum and     var[G], rank[G] (as k_sel_finish reads it), counter,
+ *         sum of squares), n_cells, center, scale, route                sel_rank[k], bits[n_words], prefix[n_words], mu[k],
+ *                                                                       sd[k], dinv[k], trace, status
+ *   LIST  genes (take distinct indices below G, the caller's order),    rank[G] (the position of every gene in the list),
+ *         sum, sq, n_cells, center, scale                               sel_rank .. status as above; var and counter are not
+ *
+ * route (HVG): 0 as the pipeline decides (the candidate route from G = 512), 1 every gene ranked, 2 the threshold nothing
+ * reaches (the decision on the device falls back to the full ranking).  counter: the number of candidates M, 0xffffffff where
+ * the device fell back, SRX_SEL_COUNTER_UNUSED where the full ranking was launched directly (route 1, G < 512) or op is LIST.
+ * LIST with SRX_SEL_NO_VECTORS: the selection alone; sum and sq are not read and may be NULL, mu / sd / dinv / trace come back
+ * as they went in.  There is no NaN test on an explicit list: status stays 0.
+ * tail_touched: bit i set when a sentinel behind buffer i changed, i = 0 cnt, 1 sum, 2 sq, 3 var, 4 rank, 5 candidate list,
+ * 6 counter, 7 sel_rank, 8 bits, 9 prefix, 10 mu, 11 sd, 12 dinv, 13 trace, 14 status.
+ * SRX_E_ARG (the context stays usable, no output is written): a null context, argument block or named array (outputs mu, sd,
+ * dinv may be NULL with SRX_SEL_NO_VECTORS); G == 0 or take == 0; an unknown op or route; HVG outside the device ranking's
+ * envelope (G > 65536, min(take, G) > 8192); LIST with G >= 2^31 or a repeated index.  SRX_E_BOUNDS: LIST with an index >= G. */
+typedef enum srx_select_opcode { SRX_SEL_HVG = 0, SRX_SEL_LIST = 1 } srx_select_opcode;
+#define SRX_SEL_NO_VECTORS 1
+#define SRX_SEL_COUNTER_UNUSED 2147483646 /* 0x7ffffffe: no candidate count (at most 65536) reaches it, and it fits an int */
+typedef struct srx_select_args {
+    uint64_t G, take, n_cells;
+    int32_t op, route, center, scale, flags, reserved;
+    const uint64_t* cnt;    /* G */
+    const double* sum;      /* G */
+    const double* sq;       /* G */
+    const uint64_t* genes;  /* LIST: take */
+    double* var;            /* G (HVG) */
+    uint32_t* rank;         /* G */
+    int32_t* sel_rank;      /* k */
+    uint32_t* bits;         /* n_words */
+    uint32_t* prefix;       /* n_words */
+    double* mu;             /* k */
+    double* sd;             /* k */
+    double* dinv;           /* k */
+    double trace;
+    uint32_t counter;
+    int32_t status;         /* k_sel_finish's status word: bit 0 = a NaN variance */
+    int32_t tail_touched;
+    int32_t reserved2;
+} srx_select_args;
+int32_t srx_select_op(srx_ctx* ctx, srx_select_args* args);
 
 /* ---- fused pipeline: normalize_total_inplace(target, Row) -> log1p_transform_inplace ->
  * pca_inplace(n_pc, center, scale, .., HighlyVariable(n_hvg)) with every intermediate

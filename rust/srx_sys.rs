@@ -30,6 +30,8 @@ pub const SRX_IT_ZERO_WP: i32 = 1;
 pub const SRX_IT_Z0: i32 = 1;
 pub const SRX_IT_Z0_IS_SRC: i32 = 8;
 pub const SRX_IT_SRC_IS_W: i32 = 16;
+pub const SRX_SEL_NO_VECTORS: i32 = 1;
+pub const SRX_SEL_COUNTER_UNUSED: i32 = 2147483646;
 pub const SRX_OK: i32 = 0;
 pub const SRX_E_ARG: i32 = -1;
 pub const SRX_E_DTYPE: i32 = -2;
@@ -106,6 +108,8 @@ pub const SRX_IT_TRSM: i32 = 4;
 pub const SRX_IT_EIG: i32 = 5;
 pub const SRX_IT_RITZ: i32 = 6;
 pub const SRX_IT_CHEB: i32 = 7;
+pub const SRX_SEL_HVG: i32 = 0;
+pub const SRX_SEL_LIST: i32 = 1;
 pub const SRX_BACKED_NORMALIZE: i32 = 1;
 pub const SRX_BACKED_LOG1P: i32 = 2;
 pub const SRX_K_NORMALIZE: i32 = 0;
@@ -617,6 +621,37 @@ pub struct SrxIterateArgs {      // `srx_iterate_args`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxSelectArgs {      // `srx_select_args`
+    pub G: u64,
+    pub take: u64,
+    pub n_cells: u64,
+    pub op: i32,
+    pub route: i32,
+    pub center: i32,
+    pub scale: i32,
+    pub flags: i32,
+    pub reserved: i32,
+    pub cnt: *const u64,
+    pub sum: *const f64,
+    pub sq: *const f64,
+    pub genes: *const u64,
+    pub var: *mut f64,
+    pub rank: *mut u32,
+    pub sel_rank: *mut i32,
+    pub bits: *mut u32,
+    pub prefix: *mut u32,
+    pub mu: *mut f64,
+    pub sd: *mut f64,
+    pub dinv: *mut f64,
+    pub trace: f64,
+    pub counter: u32,
+    pub status: i32,
+    pub tail_touched: i32,
+    pub reserved2: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxPipelineResult {      // `srx_pipeline_result`
     pub pca: SrxPcaInfo,
     pub ms_normalize: f64,
@@ -806,6 +841,7 @@ extern "C" {
     pub fn srx_spmm(m: *mut SrxMat, sel: *const u64, k: u64, panel: *const f64, y_out: *mut f64, t_out: *mut f64,
                     gram_out: *mut f64) -> i32;
     pub fn srx_iterate_op(ctx: *mut SrxCtx, op: i32, args: *mut SrxIterateArgs) -> i32;
+    pub fn srx_select_op(ctx: *mut SrxCtx, args: *mut SrxSelectArgs) -> i32;
     pub fn srx_pipeline(m: *mut SrxMat, target_sum: f64, n_hvg: u64, opts: *const SrxPcaOpts,
                         res: *mut SrxPipelineResult) -> i32;
     pub fn srx_result_fetch(m: *mut SrxMat, scores: *mut f64, components: *mut f64, evr: *mut f64, mean: *mut f64,

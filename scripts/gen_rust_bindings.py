@@ -78,6 +78,8 @@ def render() -> str:
     o.append("")
     for k, v in h.consts:
         t = "usize" if k in ("SRX_UNIQUE_ID_BYTES",) else "i32"
+        # rustc denies an out-of-range literal (overflowing_literals): one such constant and the whole module fails to compile
+        assert t != "i32" or -2**31 <= v < 2**31, f"{k} = {v} does not fit the i32 it is rendered as"
         o.append(f"pub const {k}: {t} = {v};")
     o.append("")
     for name in h.opaque:

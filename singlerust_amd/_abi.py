@@ -31,6 +31,8 @@ IT_ZERO_WP = 1
 IT_Z0 = 1
 IT_Z0_IS_SRC = 8
 IT_SRC_IS_W = 16
+SEL_NO_VECTORS = 1
+SEL_COUNTER_UNUSED = 2147483646
 SYNTH_MAX_TYPES = 128
 OK = 0
 E_ARG = -1
@@ -108,6 +110,8 @@ IT_TRSM = 4
 IT_EIG = 5
 IT_RITZ = 6
 IT_CHEB = 7
+SEL_HVG = 0
+SEL_LIST = 1
 BACKED_NORMALIZE = 1
 BACKED_LOG1P = 2
 K_NORMALIZE = 0
@@ -331,6 +335,14 @@ class IterateArgs(C.Structure):      # srx_iterate_args
                 ("status", C.c_int32 * 2), ("tail_touched", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SelectArgs(C.Structure):      # srx_select_args
+    _fields_ = [("G", C.c_uint64), ("take", C.c_uint64), ("n_cells", C.c_uint64), ("op", C.c_int32),
+                ("route", C.c_int32), ("center", C.c_int32), ("scale", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32), ("cnt", P), ("sum", P), ("sq", P), ("genes", P), ("var", P), ("rank", P),
+                ("sel_rank", P), ("bits", P), ("prefix", P), ("mu", P), ("sd", P), ("dinv", P), ("trace", C.c_double),
+                ("counter", C.c_uint32), ("status", C.c_int32), ("tail_touched", C.c_int32), ("reserved2", C.c_int32)]
+
+
 class PipelineResult(C.Structure):      # srx_pipeline_result
     _fields_ = [("pca", PcaInfo), ("ms_normalize", C.c_double), ("ms_moments", C.c_double), ("ms_select", C.c_double),
                 ("ms_compact", C.c_double), ("ms_pca", C.c_double)]
@@ -472,6 +484,7 @@ SIGNATURES = {
     "srx_doublets_free": (None, [P]),
     "srx_spmm": (C.c_int32, [P, P, C.c_uint64, P, P, P, P]),
     "srx_iterate_op": (C.c_int32, [P, C.c_int32, C.POINTER(IterateArgs)]),
+    "srx_select_op": (C.c_int32, [P, C.POINTER(SelectArgs)]),
     "srx_pipeline": (C.c_int32, [P, C.c_double, C.c_uint64, C.POINTER(PcaOpts), C.POINTER(PipelineResult)]),
     "srx_result_fetch": (C.c_int32, [P, P, P, P, P, P, P]),
     "srx_backed_create": (C.c_int32, [P, C.c_uint64, C.c_int32, C.POINTER(P)]),

@@ -32,7 +32,7 @@ static int32_t select_hvg_host(srx_ctx* ctx, const std::vector<double>& var, uin
 
 // ---- FeatureSelection::HighlyVariable(n) on the device (the pipeline's route: no host round trip) ----
 // Same semantics as select_hvg_host / dim_red/mod.rs:135-140: nz-only population variance in the reference's
-// operation order (csr.rs:179-185: no FMA contraction — explicit _rn intrinsics), stable descending order
+// operation order (csr.rs:179-185: no FMA contraction — this file's operators under the pragma), stable descending order
 // (ties keep the ascending gene index), NaN -> status bit 1 (the reference panics).
 __global__ void k_gene_var(const uint64_t* __restrict__ cnt, const double* __restrict__ sum, const double* __restrict__ sq,
                            uint64_t G, double* __restrict__ var, uint32_t* __restrict__ rank, uint32_t rank_init) {
@@ -41,8 +41,11 @@ __global__ void k_gene_var(const uint64_t* __restrict__ cnt, const double* __res
     double v = 0.0;
     if (cnt[j] > 0) {
         const double c = (double)(uint32_t)cnt[j];
-        const double mean = __ddiv_rn(sum[j], c);
-        v = __dsub_rn(__ddiv_rn(sq[j], c), __dmul_rn(mean, mean));
+        // plain operators: the pragma above covers them.  (The runtime's __dmul_rn / __dsub_rn are operators of a header read
+        // before the pragma: their results stayed contractable, and sq / c - mean * mean was ONE v_fma_f64.)
+        const double mean = sum[j] / c;
+        const double mm = mean * mean;
+        v = sq[j] / c - mm;
     }
     var[j] = v;
     rank[j] = rank_init;          // (candidate route: 0xffffffff = not a candidate; full ranking: the partial ranks start at 0)
@@ -307,7 +310,7 @@ __global__ __launch_bounds__(1024) void k_sel_finish(const uint32_t* __restrict_
         __syncthreads();
     }
     if (t == 0) {
-        *trace = s_tr[0];
+        if (sum) *trace = s_tr[0];                      // (`sum` null: no vectors — the trace is one of them)
         *status = s_nan;
     }
 }
@@ -331,13 +334,13 @@ static int32_t sel_buffers(srx_ctx* ctx, uint64_t G, uint64_t take, SelDev& out,
     return SRX_OK;
 }
 
-static int32_t launch_sel_finish(srx_mat* m, const uint32_t* d_rank, const double* d_var, bool vectors, int center, int scale,
-                                 const SelDev& out) {
-    srx_ctx* ctx = m->ctx;
+// `d_prefix`: the n_words prefix counts (the pipeline keeps them behind the bits: out.d_bits + out.n_words)
+static int32_t launch_sel_finish(srx_ctx* ctx, const uint32_t* d_rank, const double* d_var, const double* d_sum, const double* d_sq, uint64_t G,
+                                 double n_cells, int center, int scale, const SelDev& out, uint32_t* d_prefix) {
     auto kern = out.n_words <= kSelLdsWords ? k_sel_finish<true> : k_sel_finish<false>;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, d_rank, d_var, vectors ? m->d_sum : nullptr, m->d_sq,
-                       (uint32_t)m->n_cols, (uint32_t)out.k, out.n_words, (double)m->n_rows_global, center, scale, out.d_sel_rank,
-                       out.d_status, out.d_bits, out.d_bits + out.n_words, out.d_mu, out.d_sd, out.d_dinv, out.d_trace);
+    hipLaunchKernelGGL(kern, dim3(1), dim3(1024), 0, ctx->stream, d_rank, d_var, d_sum, d_sq, (uint32_t)G, (uint32_t)out.k, out.n_words,
+                       n_cells, center, scale, out.d_sel_rank, out.d_status, out.d_bits, d_prefix, out.d_mu, out.d_sd, out.d_dinv,
+                       out.d_trace);
     SRX_HIP(ctx, hipGetLastError());
     return SRX_OK;
 }
@@ -347,35 +350,53 @@ bool hvg_on_device(uint64_t n, uint64_t n_cols) {
     return n > 0 && std::min(n, n_cols) <= kDevSelMaxK && n_cols <= 65536;
 }
 
+// The work buffers of the device ranking beside the SelDev: G variances, the G-entry rank table, the candidate list (G entries)
+// and its counter word, the prefix counts.
+struct SelWork {
+    double* d_var = nullptr;
+    uint32_t *d_rank = nullptr, *d_cand = nullptr, *d_counter = nullptr, *d_prefix = nullptr;
+};
+enum { kRouteAuto = 0, kRouteFull = 1, kRouteMiss = 2 };      // (srx_select_args.route)
+// Device-side HighlyVariable(n) on device pointers: the four launches: variances; threshold + candidate list + the decision;
+// the ranks; mask, vectors, status.  `take` = min(n, G); `route`: kRouteFull ranks every gene, kRouteMiss gives
+// k_hvg_candidates a threshold nothing reaches (the device-side fallback).  d_cand / d_counter are read on the candidate route only.
+static int32_t hvg_launches(srx_ctx* ctx, const uint64_t* d_cnt, const double* d_sum, const double* d_sq, uint64_t G, uint64_t take,
+                            double n_cells, int center, int scale, int route, const SelWork& w, const SelDev& out) {
+    const unsigned gb = (unsigned)at_least_one((G + 255) / 256);
+    const unsigned gy = (unsigned)at_least_one((G + kRankTile - 1) / kRankTile);
+    const bool all = route == kRouteFull || take == 0 || G < (uint64_t)kRankSample;
+    hipLaunchKernelGGL(k_gene_var, dim3(gb), dim3(256), 0, ctx->stream, d_cnt, d_sum, d_sq, G, w.d_var, w.d_rank, all ? 0u : 0xffffffffu);
+    if (all) {
+        hipLaunchKernelGGL(k_hvg_rank, dim3(gb, gy), dim3(256), 0, ctx->stream, w.d_var, (uint32_t)G, w.d_rank);
+    } else {
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(G, std::max<uint64_t>(4 * take, 4096));
+        hipLaunchKernelGGL(k_hvg_candidates, dim3(1), dim3(kSelThreads), 0, ctx->stream, w.d_var, (uint32_t)G, (uint32_t)take, cap, w.d_counter,
+                           w.d_cand, w.d_rank, route == kRouteMiss ? 1 : 0);
+        hipLaunchKernelGGL(k_rank_selected, dim3((cap + 255) / 256, (cap + kCandTile - 1) / kCandTile), dim3(256), 0, ctx->stream, w.d_var,
+                           (uint32_t)G, w.d_counter, w.d_cand, w.d_rank);
+    }
+    return launch_sel_finish(ctx, w.d_rank, w.d_var, d_sum, d_sq, G, n_cells, center, scale, out, w.d_prefix);
+}
+
 // Device-side HighlyVariable(n): fills the scratch buffers named in sel_buffers; nothing is read back.
 int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, SelDev& out) {
     srx_ctx* ctx = m->ctx;
     const uint64_t G = m->n_cols;
     const uint64_t take = n < G ? n : G;
-    double* d_var;
-    uint32_t* d_rank;
-    SRX_TRY(scratch(ctx, "hvg_var", at_least_one(G) * sizeof(double), (void**)&d_var));
-    SRX_TRY(sel_buffers(ctx, G, take, out, &d_rank));
-    const unsigned gb = (unsigned)at_least_one((G + 255) / 256);
-    const unsigned gy = (unsigned)at_least_one((G + kRankTile - 1) / kRankTile);
+    SelWork w;
+    SRX_TRY(scratch(ctx, "hvg_var", at_least_one(G) * sizeof(double), (void**)&w.d_var));
+    SRX_TRY(sel_buffers(ctx, G, take, out, &w.d_rank));
+    w.d_prefix = out.d_bits + out.n_words;
     static const bool full_rank = getenv("SRX_HVG_FULL_RANK") != nullptr;       // A/B switch: rank every gene
-    const bool all = full_rank || take == 0 || G < (uint64_t)kRankSample;
-    // four launches (round 4: eleven): variances; threshold + candidate list + the decision; the ranks; mask, vectors, status
-    hipLaunchKernelGGL(k_gene_var, dim3(gb), dim3(256), 0, ctx->stream, m->d_cnt, m->d_sum, m->d_sq, G, d_var, d_rank, all ? 0u : 0xffffffffu);
-    if (all) {
-        hipLaunchKernelGGL(k_hvg_rank, dim3(gb, gy), dim3(256), 0, ctx->stream, d_var, (uint32_t)G, d_rank);
-    } else {
-        uint32_t* d_cand;
-        SRX_TRY(scratch(ctx, "hvg_cand", (at_least_one(G) + 8) * sizeof(uint32_t), (void**)&d_cand));
-        uint32_t* d_counter = d_cand + G + 4;
-        static const int force_miss = getenv("SRX_HVG_FORCE_MISS") ? 1 : 0;       // exercises the device-side fallback
-        const uint32_t cap = (uint32_t)std::min<uint64_t>(G, std::max<uint64_t>(4 * take, 4096));
-        hipLaunchKernelGGL(k_hvg_candidates, dim3(1), dim3(kSelThreads), 0, ctx->stream, d_var, (uint32_t)G, (uint32_t)take, cap, d_counter, d_cand,
-                           d_rank, force_miss);
-        hipLaunchKernelGGL(k_rank_selected, dim3((cap + 255) / 256, (cap + kCandTile - 1) / kCandTile), dim3(256), 0, ctx->stream, d_var,
-                           (uint32_t)G, d_counter, d_cand, d_rank);
+    static const int force_miss = getenv("SRX_HVG_FORCE_MISS") ? 1 : 0;         // exercises the device-side fallback
+    // every buffer is asked for before the first launch: where scratch() grows one (hipFree + hipMalloc, which wait for the
+    // device), it does so ahead of k_gene_var, not between it and k_hvg_candidates
+    if (!(full_rank || take == 0 || G < (uint64_t)kRankSample)) {
+        SRX_TRY(scratch(ctx, "hvg_cand", (at_least_one(G) + 8) * sizeof(uint32_t), (void**)&w.d_cand));
+        w.d_counter = w.d_cand + G + 4;
     }
-    return launch_sel_finish(m, d_rank, d_var, true, center, scale, out);
+    return hvg_launches(ctx, m->d_cnt, m->d_sum, m->d_sq, G, take, (double)m->n_rows_global, center, scale,
+                        full_rank ? kRouteFull : force_miss ? kRouteMiss : kRouteAuto, w, out);
 }
 
 // The ranking alone, for any key array (pearson.hip): d_rank[j] += the number of genes before j under (key desc, index asc);
@@ -390,10 +411,8 @@ int32_t rank_keys_device(srx_ctx* ctx, const double* d_key, uint64_t G, uint32_t
 
 // An explicit list: its rank table is the position of every gene in the list, so that the selection comes out in the
 // caller's order (1.2 MB to upload at 300 000 columns).  Needs the global moments of `m` where `vectors`.
-int32_t select_list(srx_mat* m, const uint64_t* genes, uint64_t k, int center, int scale, SelDev& out, bool vectors) {
-    srx_ctx* ctx = m->ctx;
-    const uint64_t G = m->n_cols;
-    std::vector<uint32_t> rank(G, 0xffffffffu);
+static int32_t list_rank_table(srx_ctx* ctx, const uint64_t* genes, uint64_t k, uint64_t G, std::vector<uint32_t>& rank) {
+    rank.assign(G, 0xffffffffu);
     for (uint64_t s = 0; s < k; ++s) {
         const uint64_t g = genes ? genes[s] : s;
         if (g >= G) return fail(ctx, SRX_E_BOUNDS, "selected feature index %llu out of bounds (n_vars = %llu)",
@@ -401,10 +420,18 @@ int32_t select_list(srx_mat* m, const uint64_t* genes, uint64_t k, int center, i
         if (rank[g] != 0xffffffffu) return fail(ctx, SRX_E_ARG, "selected feature index %llu appears twice", (unsigned long long)g);
         rank[g] = (uint32_t)s;
     }
+    return SRX_OK;
+}
+int32_t select_list(srx_mat* m, const uint64_t* genes, uint64_t k, int center, int scale, SelDev& out, bool vectors) {
+    srx_ctx* ctx = m->ctx;
+    const uint64_t G = m->n_cols;
+    std::vector<uint32_t> rank;
+    SRX_TRY(list_rank_table(ctx, genes, k, G, rank));
     uint32_t* d_rank;
     SRX_TRY(sel_buffers(ctx, G, k, out, &d_rank));
     SRX_TRY(h2d(ctx, d_rank, rank.data(), G * sizeof(uint32_t)));
-    return launch_sel_finish(m, d_rank, nullptr, vectors, center, scale, out);
+    return launch_sel_finish(ctx, d_rank, nullptr, vectors ? m->d_sum : nullptr, m->d_sq, G, (double)m->n_rows_global, center, scale, out,
+                             out.d_bits + out.n_words);
 }
 
 int32_t hvg_list_host(srx_mat* m, uint64_t n, std::vector<uint64_t>& out) {
@@ -431,6 +458,112 @@ int32_t srx_select_hvg(srx_mat* m, uint64_t n, uint64_t* idx_out, uint64_t* n_ou
     SRX_TRY(hvg_list_host(m, n, sel));
     if (idx_out) memcpy(idx_out, sel.data(), sel.size() * sizeof(uint64_t));
     *n_out = sel.size();
+    return SRX_OK;
+}
+
+// Kernel-level entry point of the selection (test and diagnostics: no stability promise): hvg_launches / select_list's table and
+// k_sel_finish on host arrays, in fresh device buffers of exactly the stated sizes, each followed by kSelTail sentinel elements
+// that must come back untouched.
+namespace {
+constexpr size_t kSelTail = 8;
+constexpr unsigned char kSelSentinelByte = 0xa5;
+struct SelBufs {                                   // the device buffers of one call, freed when it returns
+    std::vector<void*> p;
+    ~SelBufs() {
+        for (void* q : p) (void)hipFree(q);
+    }
+};
+// `n` elements of `elem` bytes from `host` (null: sentinel bytes there too) + the tail
+int32_t sel_up(srx_ctx* ctx, SelBufs& bufs, const void* host, size_t n, size_t elem, void** dev) {
+    SRX_HIP(ctx, hipMalloc(dev, (n + kSelTail) * elem));
+    bufs.p.push_back(*dev);
+    std::vector<unsigned char> h((n + kSelTail) * elem, kSelSentinelByte);
+    if (host) memcpy(h.data(), host, n * elem);
+    return h2d(ctx, *dev, h.data(), h.size());
+}
+int32_t sel_down(srx_ctx* ctx, void* host, const void* dev, size_t n, size_t elem, int bit, int32_t* touched) {
+    std::vector<unsigned char> h((n + kSelTail) * elem);
+    SRX_TRY(d2h(ctx, h.data(), dev, h.size()));
+    if (host) memcpy(host, h.data(), n * elem);
+    for (size_t e = n * elem; e < h.size(); ++e)
+        if (h[e] != kSelSentinelByte) *touched |= 1 << bit;
+    return SRX_OK;
+}
+}  // namespace
+
+int32_t srx_select_op(srx_ctx* ctx, srx_select_args* a) {
+    if (!ctx || !a) return fail(ctx, SRX_E_ARG, "srx_select_op: null argument");
+    const bool list = a->op == SRX_SEL_LIST;
+    if (a->op != SRX_SEL_HVG && !list) return fail(ctx, SRX_E_ARG, "srx_select_op: unknown op %d", a->op);
+    const bool vectors = !(list && (a->flags & SRX_SEL_NO_VECTORS));
+    const uint64_t G = a->G;
+    if (G == 0 || a->take == 0) return fail(ctx, SRX_E_ARG, "srx_select_op: G and take must be >= 1");
+    if (!a->rank || !a->sel_rank || !a->bits || !a->prefix || (vectors && (!a->sum || !a->sq || !a->mu || !a->sd || !a->dinv)))
+        return fail(ctx, SRX_E_ARG, "srx_select_op: null array");
+    std::vector<uint32_t> table;
+    if (list) {
+        if (!a->genes) return fail(ctx, SRX_E_ARG, "srx_select_op: null gene list");
+        // a matrix has fewer than 2^31 columns (upload_on): the rank table, n_words and the kernel's G are sized by that
+        if (G >= (1ull << 31)) return fail(ctx, SRX_E_ARG, "srx_select_op: G %llu exceeds int32 device indices", (unsigned long long)G);
+        SRX_TRY(list_rank_table(ctx, a->genes, a->take, G, table));
+    } else {
+        if (!a->cnt || !a->var) return fail(ctx, SRX_E_ARG, "srx_select_op: null array");
+        if (a->route < kRouteAuto || a->route > kRouteMiss) return fail(ctx, SRX_E_ARG, "srx_select_op: route must be 0, 1 or 2");
+        if (!hvg_on_device(a->take, G))
+            return fail(ctx, SRX_E_ARG, "srx_select_op: outside the device ranking's envelope (G <= 65536, min(take, G) <= %llu)",
+                        (unsigned long long)kDevSelMaxK);
+    }
+    SRX_HIP(ctx, hipSetDevice(ctx->device));
+
+    const uint64_t k = std::min<uint64_t>(a->take, G);
+    const int n_words = (int)((G + 31) / 32);
+    SelBufs bufs;
+    uint64_t* d_cnt = nullptr;
+    double *d_sum = nullptr, *d_sq = nullptr;
+    SelWork w;
+    SelDev out;
+    out.k = (int)k;
+    out.n_words = n_words;
+    uint32_t unused = (uint32_t)SRX_SEL_COUNTER_UNUSED;
+    if (a->cnt) SRX_TRY(sel_up(ctx, bufs, a->cnt, G, 8, (void**)&d_cnt));
+    if (a->sum && vectors) SRX_TRY(sel_up(ctx, bufs, a->sum, G, 8, (void**)&d_sum));
+    if (a->sq && vectors) SRX_TRY(sel_up(ctx, bufs, a->sq, G, 8, (void**)&d_sq));
+    SRX_TRY(sel_up(ctx, bufs, a->var, G, 8, (void**)&w.d_var));
+    SRX_TRY(sel_up(ctx, bufs, list ? table.data() : a->rank, G, 4, (void**)&w.d_rank));
+    SRX_TRY(sel_up(ctx, bufs, nullptr, G, 4, (void**)&w.d_cand));
+    SRX_TRY(sel_up(ctx, bufs, &unused, 1, 4, (void**)&w.d_counter));
+    SRX_TRY(sel_up(ctx, bufs, a->sel_rank, k, 4, (void**)&out.d_sel_rank));
+    SRX_TRY(sel_up(ctx, bufs, a->bits, n_words, 4, (void**)&out.d_bits));
+    SRX_TRY(sel_up(ctx, bufs, a->prefix, n_words, 4, (void**)&w.d_prefix));
+    SRX_TRY(sel_up(ctx, bufs, a->mu, k, 8, (void**)&out.d_mu));
+    SRX_TRY(sel_up(ctx, bufs, a->sd, k, 8, (void**)&out.d_sd));
+    SRX_TRY(sel_up(ctx, bufs, a->dinv, k, 8, (void**)&out.d_dinv));
+    SRX_TRY(sel_up(ctx, bufs, &a->trace, 1, 8, (void**)&out.d_trace));
+    SRX_TRY(sel_up(ctx, bufs, &a->status, 1, 4, (void**)&out.d_status));
+
+    if (list)
+        SRX_TRY(launch_sel_finish(ctx, w.d_rank, nullptr, d_sum, d_sq, G, (double)a->n_cells, a->center, a->scale, out, w.d_prefix));
+    else
+        SRX_TRY(hvg_launches(ctx, d_cnt, d_sum, d_sq, G, k, (double)a->n_cells, a->center, a->scale, a->route, w, out));
+    SRX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+
+    int32_t touched = 0;
+    if (d_cnt) SRX_TRY(sel_down(ctx, nullptr, d_cnt, G, 8, 0, &touched));
+    if (d_sum) SRX_TRY(sel_down(ctx, nullptr, d_sum, G, 8, 1, &touched));
+    if (d_sq) SRX_TRY(sel_down(ctx, nullptr, d_sq, G, 8, 2, &touched));
+    SRX_TRY(sel_down(ctx, list ? nullptr : a->var, w.d_var, G, 8, 3, &touched));
+    SRX_TRY(sel_down(ctx, a->rank, w.d_rank, G, 4, 4, &touched));
+    SRX_TRY(sel_down(ctx, nullptr, w.d_cand, G, 4, 5, &touched));
+    SRX_TRY(sel_down(ctx, &a->counter, w.d_counter, 1, 4, 6, &touched));
+    SRX_TRY(sel_down(ctx, a->sel_rank, out.d_sel_rank, k, 4, 7, &touched));
+    SRX_TRY(sel_down(ctx, a->bits, out.d_bits, n_words, 4, 8, &touched));
+    SRX_TRY(sel_down(ctx, a->prefix, w.d_prefix, n_words, 4, 9, &touched));
+    SRX_TRY(sel_down(ctx, a->mu, out.d_mu, k, 8, 10, &touched));
+    SRX_TRY(sel_down(ctx, a->sd, out.d_sd, k, 8, 11, &touched));
+    SRX_TRY(sel_down(ctx, a->dinv, out.d_dinv, k, 8, 12, &touched));
+    SRX_TRY(sel_down(ctx, &a->trace, out.d_trace, 1, 8, 13, &touched));
+    SRX_TRY(sel_down(ctx, &a->status, out.d_status, 1, 4, 14, &touched));
+    a->tail_touched = touched;
     return SRX_OK;
 }
 
