@@ -301,7 +301,7 @@ int32_t srx_select_hvg(srx_mat* m, uint64_t n, uint64_t* idx_out, uint64_t* n_ou
  *   at most half a quantum of error to its gene's sum.  No floating-point atomics: results are bit-identical from call to call,
  *   and two identical columns get bit-identical variances wherever they sit.
  * Departures from scanpy: scanpy yields NaN for an empty cell (here 0) and leaves ties to an unstable argsort (here: gene
- *   index); batch_key (median rank over batches) is out of scope.
+ *   index); batch_key (median rank over batches) is not built for this flavour (srx_select_hvg_seurat_v3 below has it).
  * All three calls accept CSR and CSC handles at either value storage and any dtype, leave the handle as it was (values,
  *   logical dtype; the moments cache is filled with the moments of the current values if it was empty) and compute on the
  *   device only.  Non-integer values are accepted.
@@ -855,6 +855,109 @@ int32_t srx_rank_genes_wilcoxon_graph(srx_mat* m, srx_graph* g, const srx_wilcox
 int32_t srx_markers_fetch_ties(srx_markers* mk, uint64_t* out);
 /* SRX_E_ARG on a handle of the t-test. */
 int32_t srx_markers_wilcoxon_info_get(const srx_markers* mk, srx_wilcoxon_info* info);
+
+/* ---- highly variable genes as Seurat v3 chooses them, with batches (not in the reference) --------------------------------------
+ * scanpy's pp.highly_variable_genes(flavor = "seurat_v3" / "seurat_v3_paper", batch_key = ..) on RAW counts, beside the
+ * Pearson-residual selection above; it stands here because it is built on the grouped moments of this section (a batch is
+ * a group).  Additive, detected by symbol, no profiling class of its own (the times are in srx_seurat_v3_info).  The
+ * definition here is what is tested; the output has NOT been compared with scanpy or skmisc (neither is installed where this
+ * was built).
+ *
+ * Input: the raw counts of a CSR handle (N cells x G genes, non-negative stored values, non-integers accepted) and optionally
+ * one batch label < n_batches per cell (NULL: one batch).  Everything below is f64, without FMA contraction, in the order
+ * written.
+ * Step 1, batch moments.  For batch b with N_b cells: S, Q = the per-gene sum and sum of squares over the batch's stored
+ *   entries, in the fixed point of srx_group_moments (its scales: integer counts give exact moments);
+ *      mean = S / N_b,     var = (Q / N_b - mean * mean) * (N_b / (N_b - 1))        (not clamped)
+ *   a gene is NOT CONSTANT in b when var > 0.
+ * Step 2, trend.  Over the m not-constant genes of b: x = log10(mean), y = log10(var), and e_j = the value at x_j of a DIRECT
+ *   loess fit: local quadratic, tricube weights, family gaussian, no robustness iterations:
+ *      q = min(m, max(1, floor(span * m + 1e-5))),    h = the q-th smallest |x_i - x_j| (the point itself included),
+ *      t_i = (x_i - x_j) / h,   u = |t_i|,   w_i = (1 - (u * u) * u)^3 formed as c = 1 - (u * u) * u, w = (c * c) * c,
+ *      for the points with |x_i - x_j| < h (every other point has weight 0);  h == 0: the points with x_i == x_j, t = 0, w = 1.
+ *   Moments over the weighted points: M_k = sum w t^k (k = 0 .. 4, each term formed as ((w t) t) ..), B_k = sum ((w t^k) y)
+ *   (k = 0 .. 2).  The fitted value is the intercept of the weighted least-squares polynomial in t, by Cramer's rule:
+ *      c00 = M2 M4 - M3 M3,  c01 = M1 M4 - M2 M3,  c02 = M1 M3 - M2 M2,  det = (M0 c00 - M1 c01) + M2 c02,  d2 = M0 M2 - M1 M1
+ *      det > 2^-33 ((M0 M2) M4):  e = ((B0 c00 - M1 (B1 M4 - B2 M3)) + M2 (B1 M3 - B2 M2)) / det        (degree 2)
+ *      else d2 > 2^-33 (M0 M2):   e = (B0 M2 - B1 M1) / d2                                              (degree 1)
+ *      else                       e = B0 / M0                                                           (degree 0)
+ *   This is the degree rule: fewer than three distinct weighted abscissae make det vanish, fewer than two make d2 vanish
+ *   (one abscissa, h == 0 included, gives M1 = M2 = 0 exactly); each is bounded by the product it is compared with, so
+ *   rounding leaves it some 2^-50 of that product and the test at 2^-33 decides the degree from the weighted moments alone,
+ *   without a sort.  A window whose three abscissae are that close to two is fitted as a line.  The test reference
+ *   (tests/hvg_seurat_ref.py) states the same rule.
+ *   The moment sums run over the weighted points in one fixed order that depends on the value x_j alone (sorted by (x, gene
+ *   index); lane l of a wave takes the points first + l, first + l + 64, ..; one butterfly), so two genes with bit-identical
+ *   (mean, var) get bit-identical e wherever they sit, and results are bit-identical from call to call.  A constant gene has
+ *   e = 0.
+ * Step 3, clip and normalised variance.  reg_var = 10^e (pow: the one operation here that is not correctly rounded; clip and
+ *   nv are formed from the value the tables report as reg_var), reg_std = sqrt(reg_var), clip = reg_std * sqrt(N_b) + mean;
+ *   S_c, Q_c = the per-gene sums of min(x, clip) and of its square over the batch's stored entries, in the same fixed point
+ *   and at the same two scales as step 1 (round(c 2^sum_scale_log2), round((c * c) 2^sq_scale_log2) with c = min(x, clip),
+ *   ties to even, integer atomics, order-free);
+ *      nv = ((N_b * (mean * mean) + Q_c) - (2 * S_c) * mean) / ((N_b - 1) * reg_var)
+ * Step 4, ranks.  rank_b(j) = the number of genes before j under (nv descending, gene index ascending); nbatches_j = the number
+ *   of batches with rank_b(j) < min(n_top, G); median_j = the median of those ranks (the mean of the two middle ones for an
+ *   even count; NaN when nbatches_j == 0).
+ * Step 5, selection.  The first min(n_top, G) genes, in rank order, under (median ascending with NaN last, nbatches
+ *   descending, gene index ascending) — scanpy's "seurat_v3" — or with paper_order != 0 under (nbatches descending, median
+ *   ascending, gene index ascending) — its "seurat_v3_paper".
+ * Per gene: means and variances over ALL cells from the integer totals over the batches by the formulas of step 1;
+ *   variances_norm = the mean of nv over the batches (added in ascending batch order, divided by n_batches).
+ * Departures from scanpy: the loess surface is skmisc's "direct" — scanpy calls it with the default "interpolate" (a kd-tree
+ *   and blending between its vertices), which is NOT restated; ties are broken by gene index where scanpy leaves them to an
+ *   unstable argsort; ranks are kept as integers where scanpy keeps them as float32.
+ * The handle is left as it was (values, dtype, moments cache, resident result), as srx_group_moments promises.
+ * Refused with a message, nothing written.  SRX_E_ARG: a NULL handle, idx_out or n_out; n_top == 0; span NaN or outside (0, 1];
+ *   n_batches outside 1 .. SRX_GROUPS_MAX; NULL labels with n_batches != 1; a label >= n_batches (found on the device); a batch
+ *   with fewer than 2 cells; a negative stored value; a CSC handle; a context with more than one rank; an open backed session.
+ *   SRX_E_NAN: a stored value is NaN or Inf. */
+typedef struct srx_seurat_v3_opts {
+    double  span;          /* 0 = 0.3 */
+    int32_t paper_order;   /* != 0: the order of "seurat_v3_paper" */
+    int32_t reserved_;
+} srx_seurat_v3_opts;      /* NULL = {0, 0, 0} */
+/* Host buffers, each may be NULL.  The first five hold one entry per gene, the others n_batches x G, row-major. */
+typedef struct srx_seurat_v3_tables {
+    double*   means;
+    double*   variances;
+    double*   variances_norm;
+    double*   median;
+    uint32_t* nbatches;
+    double*   mean;
+    double*   var;
+    double*   fitted;      /* e */
+    double*   reg_var;     /* 10^e as the device's pow gave it: the one operation that is not correctly rounded */
+    double*   clip;
+    double*   clip_sum;    /* S_c as f64(integer) 2^-sum_scale_log2 */
+    double*   clip_sumsq;
+    double*   nv;
+    uint32_t* rank;
+} srx_seurat_v3_tables;
+typedef struct srx_seurat_v3_info {
+    uint64_t n_cells, n_genes;
+    uint32_t n_batches;
+    int32_t  sum_scale_log2, sq_scale_log2;
+    uint32_t reserved_;
+    double   max_abs;
+    uint64_t min_batch_cells;     /* the smallest N_b */
+    double   span;                /* the value used */
+    double   ms_moments, ms_loess, ms_clip, ms_rank;      /* hipEvent times of the four stages */
+} srx_seurat_v3_info;
+/* idx_out has room for min(n_top, n_cols) entries; *n_out = that many are written. */
+int32_t srx_select_hvg_seurat_v3(srx_mat* m, uint64_t n_top, const uint32_t* batch /* n_rows, NULL: one batch */, uint32_t n_batches,
+                                 const srx_seurat_v3_opts* opts, uint64_t* idx_out, uint64_t* n_out, srx_seurat_v3_tables* tables,
+                                 srx_seurat_v3_info* info);
+/* Step 2 alone on host arrays (x, y, fitted_out: m f64; x in any order): how the kernel is tested on its own; no stability
+ * promise beyond the definition.  SRX_E_ARG: a NULL context or array, span NaN or outside (0, 1]; SRX_E_NAN: a point that is
+ * NaN or Inf.  m == 0 writes nothing. */
+int32_t srx_loess_direct(srx_ctx* ctx, const double* x, const double* y, uint64_t m, double span, double* fitted_out);
+/* Step 3's pass alone for any clip table (clip: n_groups x n_cols f64 on the host, every entry >= 0, +inf allowed): the sums
+ * of min(x, clip) and of its square per (group, gene), as srx_group_moments gives SUM and SUMSQ, with its refusals and its
+ * scales (info; may be NULL) — with every clip +inf the tables equal srx_group_moments's bit for bit.  Also SRX_E_ARG: a NULL
+ * clip table, a clip that is negative or NaN, an open backed session. */
+int32_t srx_clipped_group_moments(srx_mat* m, const uint32_t* labels, uint32_t n_groups, const double* clip, double* sum_out,
+                                  double* sumsq_out, srx_markers_info* info);
 
 /* ---- UMAP layout of a symmetric weighted graph in 2 or 3 dimensions: what sc.tl.umap gives obsm["X_umap"] -----------------
  * Not in the reference (it stops at plot_pca and a commented-out tsne).  This is umap-learn's optimize_layout_euclidean

@@ -84,6 +84,18 @@ macro_rules! csc_descriptor {
     };
 }
 
+/// What `DeviceX::highly_variable_genes_seurat_v3` returns: the selection in rank order and the per-gene columns under scanpy's
+/// names (`highly_variable_rank` is NaN where no batch ranks the gene within `n_top_genes`).
+pub struct SeuratV3Hvg {
+    pub selected: Vec<u64>,
+    pub means: Vec<f64>,
+    pub variances: Vec<f64>,
+    pub variances_norm: Vec<f64>,
+    pub highly_variable_rank: Vec<f64>,
+    pub highly_variable_nbatches: Vec<u32>,
+    pub info: SrxSeuratV3Info,
+}
+
 impl<'c> DeviceX<'c> {
     /// Takes the same read guard the reference takes (statistics/mod.rs:11-13) for the duration of the copy.
     pub fn upload(ctx: &'c Ctx, adata: &IMAnnData) -> Result<Self> {
@@ -243,6 +255,38 @@ impl<'c> DeviceX<'c> {
         idx.truncate(n_out as usize);
         var.truncate(self.n_vars);
         Ok((idx, var, info))
+    }
+
+    /// Not in the reference: scanpy's `highly_variable_genes(flavor = "seurat_v3", batch_key = ..)` on the RAW counts (srx.h
+    /// states the definition: a direct loess surface).  `batch`: one code below `n_batches` per cell, `None` = one batch;
+    /// `span` `None` = 0.3; `paper_order`: the order of "seurat_v3_paper".  Returns the selected genes in rank order and the
+    /// per-gene columns under scanpy's names.
+    pub fn highly_variable_genes_seurat_v3(&self, n_top_genes: usize, batch: Option<&[u32]>, n_batches: u32, span: Option<f64>,
+                                           paper_order: bool) -> Result<SeuratV3Hvg> {
+        if let Some(b) = batch {
+            if b.len() != self.n_obs { bail!("highly_variable_genes_seurat_v3: {} batch labels for {} cells", b.len(), self.n_obs); }
+        }
+        let opts = SrxSeuratV3Opts { span: span.unwrap_or(0.0), paper_order: paper_order as i32, reserved: 0 };
+        let g = self.n_vars.max(1);
+        let mut r = SeuratV3Hvg { selected: vec![0u64; n_top_genes.min(self.n_vars).max(1)], means: vec![0f64; g], variances: vec![0f64; g],
+                                  variances_norm: vec![0f64; g], highly_variable_rank: vec![0f64; g],
+                                  highly_variable_nbatches: vec![0u32; g], info: unsafe { std::mem::zeroed() } };
+        let mut t: SrxSeuratV3Tables = unsafe { std::mem::zeroed() };
+        t.means = r.means.as_mut_ptr();
+        t.variances = r.variances.as_mut_ptr();
+        t.variances_norm = r.variances_norm.as_mut_ptr();
+        t.median = r.highly_variable_rank.as_mut_ptr();
+        t.nbatches = r.highly_variable_nbatches.as_mut_ptr();
+        let mut n_out = 0u64;
+        self.ctx.check(unsafe {
+            srx_select_hvg_seurat_v3(self.mat, n_top_genes as u64, batch.map_or(std::ptr::null(), |b| b.as_ptr()),
+                                     if batch.is_some() { n_batches } else { 1 }, &opts, r.selected.as_mut_ptr(), &mut n_out, &mut t,
+                                     &mut r.info)
+        })?;
+        r.selected.truncate(n_out as usize);
+        for v in [&mut r.means, &mut r.variances, &mut r.variances_norm, &mut r.highly_variable_rank] { v.truncate(self.n_vars); }
+        r.highly_variable_nbatches.truncate(self.n_vars);
+        Ok(r)
     }
 
     /// scanpy's `normalize_pearson_residuals` restricted to a gene list: n_obs x genes.len() clipped residuals, row-major,

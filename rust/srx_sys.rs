@@ -402,6 +402,51 @@ pub struct SrxWilcoxonInfo {      // `srx_wilcoxon_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxSeuratV3Opts {      // `srx_seurat_v3_opts`
+    pub span: f64,
+    pub paper_order: i32,
+    pub reserved: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxSeuratV3Tables {      // `srx_seurat_v3_tables`
+    pub means: *mut f64,
+    pub variances: *mut f64,
+    pub variances_norm: *mut f64,
+    pub median: *mut f64,
+    pub nbatches: *mut u32,
+    pub mean: *mut f64,
+    pub var: *mut f64,
+    pub fitted: *mut f64,
+    pub reg_var: *mut f64,
+    pub clip: *mut f64,
+    pub clip_sum: *mut f64,
+    pub clip_sumsq: *mut f64,
+    pub nv: *mut f64,
+    pub rank: *mut u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxSeuratV3Info {      // `srx_seurat_v3_info`
+    pub n_cells: u64,
+    pub n_genes: u64,
+    pub n_batches: u32,
+    pub sum_scale_log2: i32,
+    pub sq_scale_log2: i32,
+    pub reserved: u32,
+    pub max_abs: f64,
+    pub min_batch_cells: u64,
+    pub span: f64,
+    pub ms_moments: f64,
+    pub ms_loess: f64,
+    pub ms_clip: f64,
+    pub ms_rank: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxUmapOpts {      // `srx_umap_opts`
     pub a: f64,
     pub b: f64,
@@ -786,6 +831,12 @@ extern "C" {
                                          out: *mut *mut SrxMarkers) -> i32;
     pub fn srx_markers_fetch_ties(mk: *mut SrxMarkers, out: *mut u64) -> i32;
     pub fn srx_markers_wilcoxon_info_get(mk: *const SrxMarkers, info: *mut SrxWilcoxonInfo) -> i32;
+    pub fn srx_select_hvg_seurat_v3(m: *mut SrxMat, n_top: u64, batch: *const u32, n_batches: u32,
+                                    opts: *const SrxSeuratV3Opts, idx_out: *mut u64, n_out: *mut u64,
+                                    tables: *mut SrxSeuratV3Tables, info: *mut SrxSeuratV3Info) -> i32;
+    pub fn srx_loess_direct(ctx: *mut SrxCtx, x: *const f64, y: *const f64, m: u64, span: f64, fitted_out: *mut f64) -> i32;
+    pub fn srx_clipped_group_moments(m: *mut SrxMat, labels: *const u32, n_groups: u32, clip: *const f64,
+                                     sum_out: *mut f64, sumsq_out: *mut f64, info: *mut SrxMarkersInfo) -> i32;
     pub fn srx_umap(g: *mut SrxGraph, m: *mut SrxMat, opts: *const SrxUmapOpts, init: *const f64,
                     embedding_out: *mut f64, info: *mut SrxUmapInfo) -> i32;
     pub fn srx_umap_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,

@@ -250,6 +250,23 @@ class WilcoxonInfo(C.Structure):      # srx_wilcoxon_info
                 ("ms_stage", C.c_double), ("ms_sort", C.c_double), ("ms_ranks", C.c_double)]
 
 
+class SeuratV3Opts(C.Structure):      # srx_seurat_v3_opts
+    _fields_ = [("span", C.c_double), ("paper_order", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class SeuratV3Tables(C.Structure):      # srx_seurat_v3_tables
+    _fields_ = [("means", P), ("variances", P), ("variances_norm", P), ("median", P), ("nbatches", P), ("mean", P),
+                ("var", P), ("fitted", P), ("reg_var", P), ("clip", P), ("clip_sum", P), ("clip_sumsq", P), ("nv", P),
+                ("rank", P)]
+
+
+class SeuratV3Info(C.Structure):      # srx_seurat_v3_info
+    _fields_ = [("n_cells", C.c_uint64), ("n_genes", C.c_uint64), ("n_batches", C.c_uint32),
+                ("sum_scale_log2", C.c_int32), ("sq_scale_log2", C.c_int32), ("reserved_", C.c_uint32),
+                ("max_abs", C.c_double), ("min_batch_cells", C.c_uint64), ("span", C.c_double),
+                ("ms_moments", C.c_double), ("ms_loess", C.c_double), ("ms_clip", C.c_double), ("ms_rank", C.c_double)]
+
+
 class UmapOpts(C.Structure):      # srx_umap_opts
     _fields_ = [("a", C.c_double), ("b", C.c_double), ("min_dist", C.c_double), ("spread", C.c_double),
                 ("gamma", C.c_double), ("alpha0", C.c_double), ("seed", C.c_uint64), ("n_epochs", C.c_int32),
@@ -448,6 +465,10 @@ SIGNATURES = {
     "srx_rank_genes_wilcoxon_graph": (C.c_int32, [P, P, C.POINTER(WilcoxonOpts), C.POINTER(P)]),
     "srx_markers_fetch_ties": (C.c_int32, [P, P]),
     "srx_markers_wilcoxon_info_get": (C.c_int32, [P, C.POINTER(WilcoxonInfo)]),
+    "srx_select_hvg_seurat_v3": (C.c_int32, [P, C.c_uint64, P, C.c_uint32, C.POINTER(SeuratV3Opts), P, P,
+                                             C.POINTER(SeuratV3Tables), C.POINTER(SeuratV3Info)]),
+    "srx_loess_direct": (C.c_int32, [P, P, P, C.c_uint64, C.c_double, P]),
+    "srx_clipped_group_moments": (C.c_int32, [P, P, C.c_uint32, P, P, P, C.POINTER(MarkersInfo)]),
     "srx_umap": (C.c_int32, [P, P, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
     "srx_umap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
     "srx_graph_embedding_fetch": (C.c_int32, [P, P, P]),

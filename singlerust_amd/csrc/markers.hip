@@ -12,6 +12,7 @@
 // one block per group and tile: 1.8 GB at 4096 groups x 28k genes, read back once more.)
 // The counts take a pass of their own over the indices alone (as k_gene_count): 10000 genes x (16 + 4) B exceed the LDS.
 #include "graph_handle.hpp"
+#include "markers_internal.hpp"
 #include "scan.hpp"
 
 #include <algorithm>
@@ -24,28 +25,6 @@
 // it, so their results stay contractable and `__dsub_rn(a, __dmul_rn(b, b))` becomes one v_fma_f64; the statistics therefore
 // use the operators of this file (mk_mul, mk_sub, mk_add below), which the pragma does cover.
 #pragma clang fp contract(off)
-
-struct srx_markers {
-    srx_ctx* ctx = nullptr;
-    uint64_t n_rows = 0, n_cols = 0;
-    uint32_t n_groups = 0, n_top = 0;
-    int logged = 1;
-    // one allocation: the fixed-point tables S, Q (n_groups x G i64), the counts C (n_groups x G u32), the totals over the
-    // groups (G each), the group sizes, and the top lists (n_groups x n_top)
-    void* d_block = nullptr;
-    long long *d_S = nullptr, *d_Q = nullptr, *d_totS = nullptr, *d_totQ = nullptr;
-    uint32_t *d_C = nullptr, *d_totC = nullptr;
-    uint64_t* d_sizes = nullptr;
-    uint32_t* d_top_gene = nullptr;
-    double *d_top_score = nullptr, *d_top_lfc = nullptr;
-    srx_markers_info info{};
-    // the rank-sum route (wilcoxon.inl): an allocation of its own with the doubled rank sums R2 (n_groups x G u64) and the tie
-    // terms T (G u64); null on a handle of the t-test
-    bool wilcoxon = false;
-    void* d_wx = nullptr;
-    uint64_t *d_R2 = nullptr, *d_T = nullptr;
-    srx_wilcoxon_info winfo{};
-};
 
 namespace srx {
 
@@ -144,21 +123,20 @@ __global__ void k_mk_sizes(const int64_t* __restrict__ first, uint32_t n_groups,
 }
 
 // ---- the walk: one workgroup = (gene tile, block of permuted rows of one group) -------------------------------------------
-struct MkBlock {
-    uint32_t p0, p1;      // places of the permutation
-    uint32_t group, pad_;
-};
 // COUNT: 32-bit counters per gene of the tile, the indices alone are read; else {S, Q} side by side per gene, 64-bit fixed
 // point.  A wave takes two rows at a time; a lane takes 4 consecutive entries from the 4-entry boundary at or before the
 // segment start (one 8- or 16-byte load of the indices, 16 or 2 x 16 bytes of values; entries outside [lo, hi) are masked —
 // the arrays of a matrix are padded by 16 entries).
-template <typename T, typename I, bool COUNT>
+// CLIP (hvg_seurat.hip's second pass): min(x, clip[group][gene]) takes the place of x; the group's clip row is read where it lies
+// (the accumulators fill the LDS, and the blocks of one group and tile share the row's slice in L2).
+template <typename T, typename I, bool COUNT, bool CLIP = false>
 __global__ __launch_bounds__(kMkThreads) void k_mk_walk(const int64_t* __restrict__ indptr, const int64_t* __restrict__ tp,
                                                         const I* __restrict__ idx, const T* __restrict__ vals, uint64_t n_rows,
                                                         uint64_t n_cols, int n_tiles, int tile_genes,
                                                         const uint32_t* __restrict__ perm, const MkBlock* __restrict__ blocks,
                                                         double fx_sum, double fx_sq, unsigned long long* __restrict__ out_S,
-                                                        unsigned long long* __restrict__ out_Q, uint32_t* __restrict__ out_C) {
+                                                        unsigned long long* __restrict__ out_Q, uint32_t* __restrict__ out_C,
+                                                        const double* __restrict__ clip) {
     extern __shared__ double lds[];
     unsigned long long* s_acc = reinterpret_cast<unsigned long long*>(lds);
     uint32_t* s_cnt = reinterpret_cast<uint32_t*>(lds);
@@ -166,11 +144,35 @@ __global__ __launch_bounds__(kMkThreads) void k_mk_walk(const int64_t* __restric
         for (int g = threadIdx.x; g < tile_genes; g += kMkThreads) s_cnt[g] = 0u;
     } else {
         for (int g = threadIdx.x; g < 2 * tile_genes; g += kMkThreads) s_acc[g] = 0ull;
+        // CLIP: one more word behind the accumulators, in the dynamic region (a static variable would shift its base)
+        if constexpr (CLIP) {
+            if (threadIdx.x == 0) s_acc[2 * tile_genes] = ~0ull;
+        }
     }
     __syncthreads();
     const int tile = blockIdx.x % n_tiles;
     const MkBlock blk = blocks[blockIdx.x / n_tiles];
     const int32_t gbase = tile * tile_genes;
+    // CLIP: the smallest clip of the group's row within this tile.  A value below it is below its own gene's clip too and skips
+    // the gather from the table (8 bytes from a line of its own per entry: the walk is then bound by the gather rate, not by
+    // bandwidth); min(x, clip) is the same bits either way.  Non-negative doubles order as their bit patterns.
+    const double* const clip_row = CLIP ? clip + (uint64_t)blk.group * n_cols : nullptr;
+    double clip_min = 0.0;
+    if constexpr (CLIP) {
+        unsigned long long* const s_clip_min = s_acc + 2 * tile_genes;       // (set to ~0 before the barrier above)
+        unsigned long long mn = ~0ull;
+        for (int g = threadIdx.x; g < tile_genes; g += kMkThreads) {
+            const uint64_t gene = (uint64_t)gbase + g;
+            if (gene < n_cols) {
+                const unsigned long long b = (unsigned long long)__double_as_longlong(clip_row[gene]);
+                mn = b < mn ? b : mn;
+            }
+        }
+        mn = wave_min(mn);
+        if (lane_id() == 0) atomicMin(s_clip_min, mn);
+        __syncthreads();
+        clip_min = __longlong_as_double((long long)*s_clip_min);
+    }
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     constexpr int kWaves = kMkThreads / kWave;
@@ -208,7 +210,13 @@ __global__ __launch_bounds__(kMkThreads) void k_mk_walk(const int64_t* __restric
                     __hip_atomic_fetch_add(&s_cnt[g0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 } else {
                     // round-to-nearest-even integers of x 2^s and (x x) 2^q: |.| < 2^62 by the choice of the scales (srx.h)
-                    const double x = (double)c.v[j];
+                    double x = (double)c.v[j];
+                    if constexpr (CLIP) {
+                        if (!(x < clip_min)) {
+                            const double cl = clip_row[c.g[j]];
+                            x = x < cl ? x : cl;
+                        }
+                    }
                     const long long is = (long long)__builtin_rint(mk_mul(x, fx_sum));
                     const long long iq = (long long)__builtin_rint(mk_mul(mk_mul(x, x), fx_sq));
                     __hip_atomic_fetch_add(&s_acc[2 * g0], (unsigned long long)is, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -400,7 +408,7 @@ static MkTables mk_tables(const srx_markers* mk) {
     return t;
 }
 
-static void mk_free(srx_markers* mk) {
+void mk_free(srx_markers* mk) {
     if (!mk) return;
     if (mk->d_block) {
         (void)hipSetDevice(mk->ctx->device);
@@ -429,10 +437,38 @@ static uint32_t mk_chunk_groups(const srx_markers* mk) {
 
 #include "wilcoxon.inl"
 
+// The walk's launches: every (gene tile, block) pair, by value storage and index form.  d_clip null: S, Q and, unless d_C is
+// null, the counts C (a second launch over the indices alone); else the clipped sums alone.
+static int32_t mk_walk(srx_mat* m, const uint32_t* d_perm, const MkBlock* d_blocks, size_t n_blocks, double fx_sum, double fx_sq,
+                       const double* d_clip, unsigned long long* d_S, unsigned long long* d_Q, uint32_t* d_C) {
+    srx_ctx* ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    const dim3 grid((unsigned)(n_blocks * (size_t)m->n_tiles));
+    auto launch = [&](auto kern, size_t lds, const auto* idxp, const auto* valp) -> int32_t {
+        SRX_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, grid, dim3(kMkThreads), lds, st, (const int64_t*)m->d_indptr, (const int64_t*)m->d_tile_ptr, idxp, valp, m->n_rows,
+                           m->n_cols, m->n_tiles, m->tile_genes, d_perm, d_blocks, fx_sum, fx_sq, d_S, d_Q, d_C, d_clip);
+        SRX_HIP(ctx, hipGetLastError());
+        return SRX_OK;
+    };
+    auto both = [&](const auto* idxp, const auto* valp) -> int32_t {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(valp)>>;
+        using I = std::remove_cv_t<std::remove_pointer_t<decltype(idxp)>>;
+        if (d_clip) return launch(k_mk_walk<T, I, false, true>, (size_t)m->tile_genes * 16 + 16, idxp, valp);      // (+ the smallest clip)
+        SRX_TRY(launch(k_mk_walk<T, I, false>, (size_t)m->tile_genes * 16, idxp, valp));
+        if (!d_C) return SRX_OK;                   // (a caller that reads no counts: hvg_seurat.hip)
+        return launch(k_mk_walk<float, I, true>, (size_t)m->tile_genes * 4, idxp, (const float*)nullptr);      // (the indices alone)
+    };
+    auto by_idx = [&](const auto* valp) -> int32_t {
+        return m->d_idx16 ? both((const uint16_t*)m->d_idx16, valp) : both((const int32_t*)m->d_indices, valp);
+    };
+    return is_f32(m) ? by_idx((const float*)m->d_values) : by_idx((const double*)m->d_values);
+}
+
 // The whole call.  d_labels: n_rows u32 on the device (n_groups known: every label is validated against it).  want_rank false:
 // the moments alone (srx_group_moments).  wx: the rank-sum route (its scores are ranked in place of Welch's t).
 static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_groups, const srx_rank_genes_opts* opts, bool want_rank,
-                           srx_markers** out, const WxOpts* wx = nullptr) {
+                           srx_markers** out, const WxOpts* wx = nullptr, MkPlan* plan = nullptr, bool want_counts = true) {
     srx_ctx* ctx = m->ctx;
     const uint64_t N = m->n_rows, G = m->n_cols;
     uint32_t n_top = 0;
@@ -541,30 +577,21 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
     SRX_HIP(ctx, hipEventRecord(ev.e[1], st));
 
     // -- stage 2: the grouped moments and counts, the totals
+    MkBlock* d_blocks = nullptr;
+    const double fx_sum = std::ldexp(1.0, info.sum_scale_log2), fx_sq = std::ldexp(1.0, info.sq_scale_log2);
     if (!blocks.empty() && m->nnz && G) {
-        MkBlock* d_blocks;
         SRX_TRY(scratch(ctx, "mk_blocks", blocks.size() * sizeof(MkBlock), (void**)&d_blocks));
         SRX_TRY(h2d(ctx, d_blocks, blocks.data(), blocks.size() * sizeof(MkBlock)));
-        const double fx_sum = std::ldexp(1.0, info.sum_scale_log2), fx_sq = std::ldexp(1.0, info.sq_scale_log2);
-        const dim3 grid((unsigned)(blocks.size() * (size_t)m->n_tiles));
-        auto launch = [&](auto kern, size_t lds, const auto* idxp, const auto* valp) -> int32_t {
-            SRX_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, grid, dim3(kMkThreads), lds, st, (const int64_t*)m->d_indptr, (const int64_t*)m->d_tile_ptr, idxp, valp, N, G,
-                               m->n_tiles, m->tile_genes, (const uint32_t*)d_perm, (const MkBlock*)d_blocks, fx_sum, fx_sq,
-                               (unsigned long long*)mk->d_S, (unsigned long long*)mk->d_Q, mk->d_C);
-            SRX_HIP(ctx, hipGetLastError());
-            return SRX_OK;
-        };
-        auto both = [&](const auto* idxp, const auto* valp) -> int32_t {
-            using T = std::remove_cv_t<std::remove_pointer_t<decltype(valp)>>;
-            using I = std::remove_cv_t<std::remove_pointer_t<decltype(idxp)>>;
-            SRX_TRY(launch(k_mk_walk<T, I, false>, (size_t)m->tile_genes * 16, idxp, valp));
-            return launch(k_mk_walk<float, I, true>, (size_t)m->tile_genes * 4, idxp, (const float*)nullptr);      // (the indices alone)
-        };
-        auto by_idx = [&](const auto* valp) -> int32_t {
-            return m->d_idx16 ? both((const uint16_t*)m->d_idx16, valp) : both((const int32_t*)m->d_indices, valp);
-        };
-        SRX_TRY(is_f32(m) ? by_idx((const float*)m->d_values) : by_idx((const double*)m->d_values));
+        SRX_TRY(mk_walk(m, d_perm, d_blocks, blocks.size(), fx_sum, fx_sq, nullptr, (unsigned long long*)mk->d_S, (unsigned long long*)mk->d_Q,
+                        want_counts ? mk->d_C : nullptr));
+    }
+    if (plan) {
+        plan->d_perm = d_perm;
+        plan->d_blocks = d_blocks;
+        plan->n_blocks = d_blocks ? blocks.size() : 0;
+        plan->fx_sum = fx_sum;
+        plan->fx_sq = fx_sq;
+        plan->sizes = sizes;
     }
     if (G) hipLaunchKernelGGL(k_mk_totals, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, (const long long*)mk->d_S, (const long long*)mk->d_Q,
                               (const uint32_t*)mk->d_C, n_groups, G, mk->d_totS, mk->d_totQ, mk->d_totC);
@@ -648,7 +675,16 @@ static int32_t markers_fetch_table(srx_markers* mk, int32_t which, void* out) {
     return SRX_OK;
 }
 
-static int32_t markers_check(srx_mat* m, const char* what) {
+int32_t markers_moments(srx_mat* m, const uint32_t* d_labels, uint32_t n_groups, bool want_counts, srx_markers** out, MkPlan* plan) {
+    return markers_run(m, d_labels, n_groups, nullptr, false, out, nullptr, plan, want_counts);
+}
+
+int32_t markers_clipped_walk(srx_mat* m, const MkPlan& plan, const double* d_clip, unsigned long long* d_S, unsigned long long* d_Q) {
+    if (!plan.n_blocks) return SRX_OK;
+    return mk_walk(m, plan.d_perm, plan.d_blocks, plan.n_blocks, plan.fx_sum, plan.fx_sq, d_clip, d_S, d_Q, nullptr);
+}
+
+int32_t markers_check(srx_mat* m, const char* what) {
     if (!m) return fail(nullptr, SRX_E_ARG, "%s: null matrix", what);
     srx_ctx* ctx = m->ctx;
     if (m->csc) return fail(ctx, SRX_E_ARG, "%s walks cells: convert the CSC matrix with srx_matrix_to_csr", what);
@@ -658,7 +694,7 @@ static int32_t markers_check(srx_mat* m, const char* what) {
     return SRX_OK;
 }
 
-static int32_t markers_host_labels(srx_mat* m, const uint32_t* labels, uint32_t n_groups, const char* what, uint32_t** d_labels) {
+int32_t markers_host_labels(srx_mat* m, const uint32_t* labels, uint32_t n_groups, const char* what, uint32_t** d_labels) {
     srx_ctx* ctx = m->ctx;
     if (n_groups < 1 || n_groups > SRX_GROUPS_MAX) return fail(ctx, SRX_E_ARG, "%s: n_groups = %u is outside 1 .. %d", what, n_groups, SRX_GROUPS_MAX);
     if (m->n_rows && !labels) return fail(ctx, SRX_E_ARG, "%s: null labels", what);

@@ -346,6 +346,38 @@ inline PearsonHvg highly_variable_genes_pearson(IMAnnData& a, std::size_t n_top_
     a.var_bool()["highly_variable"] = std::move(mask);
     return r;
 }
+// Not in the reference: scanpy's highly_variable_genes(flavor = "seurat_v3", batch_key = ..) on the RAW counts (srx.h states the
+// definition: a direct loess surface).  `batch`: one code below n_batches per cell, or empty for one batch; paper_order: the
+// order of "seurat_v3_paper".  The per-gene columns carry scanpy's names; var_bool()["highly_variable"] receives the mask.
+struct SeuratV3Hvg {
+    std::vector<std::uint64_t> selected;                          // rank order
+    std::vector<double> means, variances, variances_norm, highly_variable_rank;      // n_vars each; the rank is NaN where no batch ranks the gene
+    std::vector<std::uint32_t> highly_variable_nbatches;
+    srx_seurat_v3_info info{};
+};
+inline SeuratV3Hvg highly_variable_genes_seurat_v3(IMAnnData& a, std::size_t n_top_genes = 2000, const std::vector<std::uint32_t>& batch = {},
+                                                   std::uint32_t n_batches = 1, double span = 0.3, bool paper_order = false) {
+    SeuratV3Hvg r;
+    const std::size_t g = std::max<std::size_t>(a.n_vars(), 1);
+    const srx_seurat_v3_opts opts{span, paper_order ? 1 : 0, 0};
+    if (!batch.empty() && batch.size() != a.n_obs()) throw std::invalid_argument("highly_variable_genes_seurat_v3: one batch label per cell");
+    r.selected.resize(std::max<std::size_t>(std::min<std::size_t>(n_top_genes, a.n_vars()), 1));
+    r.means.resize(g); r.variances.resize(g); r.variances_norm.resize(g); r.highly_variable_rank.resize(g);
+    r.highly_variable_nbatches.resize(g);
+    srx_seurat_v3_tables t{};
+    t.means = r.means.data(); t.variances = r.variances.data(); t.variances_norm = r.variances_norm.data();
+    t.median = r.highly_variable_rank.data(); t.nbatches = r.highly_variable_nbatches.data();
+    std::uint64_t n_out = 0;
+    a.ctx().check(srx_select_hvg_seurat_v3(a.x(), n_top_genes, batch.empty() ? nullptr : batch.data(), batch.empty() ? 1u : n_batches, &opts,
+                                           r.selected.data(), &n_out, &t, &r.info));
+    r.selected.resize(n_out);
+    for (auto* v : {&r.means, &r.variances, &r.variances_norm, &r.highly_variable_rank}) v->resize(a.n_vars());
+    r.highly_variable_nbatches.resize(a.n_vars());
+    std::vector<bool> mask(a.n_vars(), false);
+    for (std::uint64_t j : r.selected) mask[j] = true;
+    a.var_bool()["highly_variable"] = std::move(mask);
+    return r;
+}
 // scanpy's normalize_pearson_residuals restricted to a gene list: n_obs x genes.size() clipped residuals, zeros included.
 inline Array2 pearson_residuals(const IMAnnData& a, const std::vector<std::uint64_t>& genes, double theta = 100.0, double clip = 0.0) {
     const srx_pearson_opts opts{theta, clip};

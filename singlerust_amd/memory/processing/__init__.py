@@ -11,7 +11,8 @@ from . import dim_red
 from .diffmap import diffmap, diffmap_csr, dpt, dpt_from, graph_diffmap, graph_transitions
 from .doublets import Doublets, doublet_scores_knn, doublets_threshold, scrublet, simulate_doublets
 from .harmony import Harmony, encode_batches, harmony_integrate, harmony_points
-from .hvg import highly_variable_genes_pearson, pca_pearson_residuals, pearson_gene_variance, pearson_gram, pearson_residuals
+from .hvg import (highly_variable_genes_pearson, highly_variable_genes_seurat_v3, pca_pearson_residuals, pearson_gene_variance, pearson_gram,
+                  pearson_residuals, seurat_v3_tables)
 from .louvain import graph_labels, louvain, louvain_csr
 from .markers import group_moments, rank_genes_groups
 from .neighbors import KnnIndex, connectivities_from_knn, knn_index, knn_index_points, knn_points, neighbors, neighbors_approx

@@ -6,6 +6,11 @@ the RAW counts, before ``normalize_total`` / ``log1p``; and the PCA of the resid
 Not in the reference.  The definition (include/srx.h) is scanpy's closed form; every residual is evaluated on the device, the
 matrix never leaves it.  Departures from scanpy: an empty cell has residual 0 (scanpy: NaN), equal variances are ordered by gene
 index (scanpy: an unstable argsort), no ``batch_key``.
+
+Also here: ``highly_variable_genes_seurat_v3`` (``srx_select_hvg_seurat_v3``), scanpy's ``flavor="seurat_v3"`` with
+``batch_key`` on the raw counts: per batch a direct loess fit of the mean / variance trend and the variance of the clipped
+counts, then median ranks over the batches.  Departures: skmisc's "direct" surface in place of the interpolated default, ties by
+gene index, integer ranks.
 """
 from __future__ import annotations
 
@@ -140,3 +145,59 @@ def pca_pearson_residuals(adata, genes=None, n_top_genes=2000, n_components=50, 
                             "selected_features": g, "n_iter": info["n_iter"], "residual": info["residual"], "solver": info["solver"],
                             "center": bool(center), "scale": False, "residuals": "pearson", "totals": totals}
     return dict(info, scores=scores, components=comps, explained_variance_ratio=evr, mean=mean, selected_features=g)
+
+
+# ---- Seurat v3 ----------------------------------------------------------------------------------------------------------------------
+_SEURAT_GENE = ("means", "variances", "variances_norm", "median", "nbatches")
+_SEURAT_BATCH = ("mean", "var", "fitted", "reg_var", "clip", "clip_sum", "clip_sumsq", "nv", "rank")
+_SEURAT_FLAVORS = {"seurat_v3": 0, "seurat_v3_paper": 1}
+
+
+def seurat_v3_tables(adata, n_top_genes=2000, batch=None, n_batches=None, span=0.3, flavor="seurat_v3"):
+    """(selection uint64 in rank order, dict of every table of ``srx_seurat_v3_tables``, info dict):
+    ``srx_select_hvg_seurat_v3`` with everything fetched.  ``batch``: uint32 codes below ``n_batches`` (None: one batch)."""
+    if flavor not in _SEURAT_FLAVORS:
+        raise ValueError("flavor must be 'seurat_v3' or 'seurat_v3_paper', not %r" % (flavor,))
+    m = _matrix(adata)
+    mi = m.info()
+    n_vars, n_obs = int(mi.n_cols), int(mi.n_rows)
+    codes = None
+    if batch is not None:
+        codes = np.ascontiguousarray(batch, dtype=np.uint32).ravel()
+        if codes.size != n_obs:
+            raise ValueError("batch holds %d labels for %d cells" % (codes.size, n_obs))
+        if n_batches is None:
+            n_batches = int(codes.max()) + 1 if codes.size else 1
+    nb = 1 if n_batches is None else int(n_batches)
+    T = {k: np.zeros(n_vars, dtype=np.uint32 if k == "nbatches" else np.float64) for k in _SEURAT_GENE}
+    T.update({k: np.zeros((nb, n_vars), dtype=np.uint32 if k == "rank" else np.float64) for k in _SEURAT_BATCH})
+    tables = F.SeuratV3Tables(*[F.ptr(T[k]) if T[k].size else None for k in _SEURAT_GENE + _SEURAT_BATCH])
+    idx = np.zeros(max(min(int(n_top_genes), n_vars), 1), dtype=np.uint64)
+    n_out = C.c_uint64(0)
+    o, i = F.SeuratV3Opts(float(span), _SEURAT_FLAVORS[flavor], 0), F.SeuratV3Info()
+    F.check(F.lib().srx_select_hvg_seurat_v3(m.handle, int(n_top_genes), F.ptr(codes) if codes is not None else None, nb, C.byref(o),
+                                             F.ptr(idx), C.byref(n_out), C.byref(tables), C.byref(i)), m.ctx.handle)
+    return idx[:int(n_out.value)].copy(), T, flat_info(i)
+
+
+def highly_variable_genes_seurat_v3(adata, n_top_genes=2000, batch=None, span=0.3, flavor="seurat_v3"):
+    """``sc.pp.highly_variable_genes(flavor="seurat_v3", batch_key=...)`` on the RAW counts, on the device
+    (``srx_select_hvg_seurat_v3``; the definition is in include/srx.h, with a direct loess surface where scanpy's is
+    interpolated).  ``batch``: one label per cell of any type (None: one batch); ``flavor="seurat_v3_paper"`` orders by the number
+    of batches first.  Returns (the selection in rank order, uint64; a dict of the per-gene columns under scanpy's names:
+    ``means``, ``variances``, ``variances_norm``, ``highly_variable_rank`` (the median rank, NaN where the gene is in no batch's
+    top), ``highly_variable_nbatches``, ``highly_variable``).  An ``IMAnnData`` receives the columns in ``var`` and ``uns["hvg"]``."""
+    codes, cats = (None, None)
+    if batch is not None:
+        cats, inv = np.unique(np.asarray(batch), return_inverse=True)
+        codes = np.ascontiguousarray(inv, dtype=np.uint32)
+    sel, T, info = seurat_v3_tables(adata, n_top_genes, codes, None if cats is None else max(int(cats.size), 1), span, flavor)
+    mask = np.zeros(T["means"].size, dtype=bool)
+    mask[sel.astype(np.int64)] = True
+    cols = {"means": T["means"], "variances": T["variances"], "variances_norm": T["variances_norm"],
+            "highly_variable_rank": T["median"], "highly_variable_nbatches": T["nbatches"], "highly_variable": mask}
+    if isinstance(adata, IMAnnData):
+        for k, v in cols.items():
+            adata.var[k] = v
+        adata.uns["hvg"] = dict(info, flavor=flavor, n_top_genes=int(n_top_genes))
+    return sel, cols
