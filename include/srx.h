@@ -465,6 +465,92 @@ int32_t srx_pca_pearson(srx_mat* m, const uint64_t* genes, uint64_t k, const srx
 int32_t srx_pearson_gram(srx_mat* m, const uint64_t* genes, uint64_t k, const srx_pearson_pca_opts* opts,
                          double* gram_out /* k x k, host */, double* colsum_out /* k, host */, srx_pearson_pca_info* info);
 
+/* ---- regress out covariates, scale, clip; PCA of the result (not in the reference) --------------------------------------------
+ * scanpy's sc.pp.regress_out(adata, keys) -> sc.pp.scale(adata, max_value) -> sc.tl.pca(adata), Seurat's
+ * ScaleData(vars.to.regress = ...) -> RunPCA, for continuous covariates, on a gene list; additive, detected by symbol, no
+ * profiling class of its own (the times are in srx_regress_info).  The scores of srx_pca_regress stay resident as the handle's PCA
+ * result, exactly as after srx_pca_pearson: the readers of "the resident scores of the handle" follow, the readers of a fitted
+ * MODEL (srx_pca_model_from_result, srx_doublets_result) refuse, naming this call.
+ *
+ * Definition.  m is a CSR or CSC handle with n cells and G genes; its values are read as stored (typically after
+ *   srx_normalize_log1p_inplace; f32 storage is read as (double)x).  genes lists k DISTINCT gene indices.  cov is a host array,
+ *   n x p row-major f64, 0 <= p <= 16; p = 0 is plain scale + clip.  Everything is f64, in the order written, without
+ *   contraction, fast-math or floating-point atomics; every sum over the cells is taken in one fixed order (below).
+ *   1. Covariates.  cbar_q = (sum_i c_iq) / n;  ct_iq = c_iq - cbar_q;  A = Ct^T Ct (p x p).  An intercept is always part of the
+ *      model: centring the covariates is how it is fitted, and it keeps A from inheriting the scale of a covariate such as a
+ *      library size of 1e4.  A is factored as the Cholesky factor of D^-1/2 A D^-1/2, D = diag A.  A covariate with A_qq == 0
+ *      (constant) is refused with SRX_E_ARG, naming q; so is one whose pivot (1 - R^2 of that covariate on the earlier ones)
+ *      is below 1e-10: there the normal equations have lost ten of sixteen digits.  statsmodels would silently take a
+ *      pseudo-inverse: a stated departure.
+ *   2. Fit, per listed gene j.  xbar_j = srx_compute_sum(m, Column)[j] / n, the library's own column sum, bit for bit;
+ *      w_qj = sum_i ct_iq x_ij;  bt_j solves A bt_j = w_j by that factor (forward and back substitution on the scaled system).
+ *   3. Residual.  r_ij = (x_ij - xbar_j) - sum_q ct_iq bt_qj, q ascending, the sum started at ct_i0 bt_0j.  A gene whose n values
+ *      are all equal (no non-zero entry at all, or n stored entries of one value; found from srx_compute_number and
+ *      srx_compute_min_max) has r_ij = 0 for every cell, as scanpy's regress_out returns zeros there.
+ *   4. Scale (`scale`, default on).  v_j = (sum_i r_ij^2) / (n - 1), the sum over the residuals themselves;  s_j = sqrt(v_j),
+ *      s_j = 1 where v_j == 0.  The mean of r_.j is zero by construction; scanpy subtracts its rounding error, here it is not
+ *      subtracted.  Flag off: s_j = 1.
+ *   5. Clip.  z_ij = r_ij / s_j;  with max_value > 0, z_ij = min(max(z_ij, -max_value), max_value) (both sides, as current
+ *      scanpy does when it centres);  max_value == 0: no clip.
+ *   6. PCA of Z, exactly the second half of the srx_pca_pearson section: m_j = (sum_i z_ij) / n (not zero once the clip is
+ *      active), C = (Z^T Z - n m m^T) / (n - 1), the n_pc largest eigenpairs, evr = eigenvalue / trace C,
+ *      scores = (Z - 1 m^T) V, the library's sign rule, component rows in the caller's gene order.  In the result block
+ *      mean = m, std = s (the caller's order) and the selection is the list.
+ * How it is computed.  Z is dense.  It is made in chunks of cells (chunk_cells; 0: as srx_pca_pearson) by ONE pair of chunk
+ *   kernels that evaluate one element function in three modes (x, r or z), and is read by four passes over the chunks: W (a
+ *   weighted column sum: per column and slab of 64-row groups the rows in ascending order, the slabs, then the chunks, added in
+ *   ascending order), sum r^2 (the same kernel with the column's own value as weight), then the Gram + column-sum pass and the
+ *   score pass of srx_pca_pearson, the same kernels on the f64 matrix cores.  cbar is summed on the host in ascending cell
+ *   order, A by the weighted column-sum kernel over Ct itself; the p x p factor and the k solves run on the host in f64.
+ *   n_clipped (the pairs with |r_ij / s_j| > max_value) is an integer count made with the chunks of the Gram pass.  Two calls
+ *   give bit-identical results.
+ * All calls leave the handle's values and dtype as they were (the moments cache is filled with the
+ *   moments of the current values if it was empty); srx_pca_regress replaces the handle's PCA result.
+ * Departures from scanpy: scanpy regresses with statsmodels' GLM and scales with a mean subtraction of rounding size; neither
+ *   package is part of the test environment and nothing is compared with them.  Out of scope: a categorical regressor
+ *   (scanpy's per-category means), zero_center = False, sharded and backed contexts, projecting new cells onto such a PCA
+ *   (srx_pca_model_from_result refuses, as for the Pearson result), and the sparse-plus-low-rank Gram that would avoid the dense
+ *   product when nothing is clipped.
+ * Refused with SRX_E_ARG and a message, nothing written, in this order: (1) a NULL handle or list, or cov == NULL with p > 0
+ *   (and a call with no output at all); (2) several ranks; (3) an open backed session; (4) max_value negative or NaN; (5) p > 16;
+ *   (6) k == 0, k > 16384, a gene index >= n_cols, a repeated gene; (7) pca.scale > 0 (scaling is this call's own flag) or
+ *   pca.solver == SRX_SOLVER_SPMM; then SRX_E_SHAPE: n < p + 2, and for srx_pca_regress k < 2 or n < 5 as srx_pca; then again
+ *   SRX_E_ARG: (8) a non-finite covariate; (9) a constant or collinear covariate, as above; (10) a non-finite stored value, found
+ *   on the device. */
+typedef struct srx_regress_opts {
+    int32_t  scale;        /* < 0 or 1: true, 0: false                                     */
+    int32_t  reserved;
+    double   max_value;    /* 0: no clip                                                   */
+    uint64_t chunk_cells;  /* cells per chunk of Z; 0: auto, as srx_pca_pearson            */
+    srx_pca_opts pca;      /* n_components, max_iter, tol, seed, solver (AUTO or GRAM)     */
+} srx_regress_opts;        /* NULL: scale on, no clip, auto chunks, 2 components           */
+typedef struct srx_regress_info {
+    uint64_t n_cells, n_genes /* k */, n_cov, n_constant_genes;
+    uint64_t n_clipped;                    /* pairs with |r / s| > max_value (0 from srx_regress_fit / _sums) */
+    double   min_pivot;                    /* the smallest Cholesky pivot of the scaled A (1 with p = 0) */
+    double   ms_fit, ms_scale, ms_gram, ms_solve, ms_scores;   /* covariates + W pass + solves; the r^2 pass; as srx_pearson_pca_info */
+    uint64_t n_chunks, chunk_cells, chunk_bytes;
+    srx_pca_info pca;
+} srx_regress_info;
+/* Kernel-level entries, so that each stage can be checked alone (as srx_pearson_residuals and srx_pearson_gram).  Host
+ * outputs in the caller's gene order; each output of srx_regress_fit may be NULL (not all), beta_out is p x k row-major. */
+int32_t srx_regress_fit(srx_mat* m, const uint64_t* genes, uint64_t k, const double* cov, uint64_t p, const srx_regress_opts* opts,
+                        double* beta_out /* p x k */, double* xbar_out /* k */, double* sd_out /* k: s */, srx_regress_info* info);
+/* The sums the fit is made of, so that each can be held against its dot-product bound: cbar (p), A (p x p) and W (p x k, the
+ * caller's gene order); each output may be NULL (not all).  Needs p >= 1. */
+int32_t srx_regress_sums(srx_mat* m, const uint64_t* genes, uint64_t k, const double* cov, uint64_t p, const srx_regress_opts* opts,
+                         double* cbar_out /* p */, double* a_out /* p x p */, double* w_out /* p x k */, srx_regress_info* info);
+/* z (n x k row-major), made by the chunk kernels the Gram and score passes read. */
+int32_t srx_regress_residuals(srx_mat* m, const uint64_t* genes, uint64_t k, const double* cov, uint64_t p,
+                              const srx_regress_opts* opts, double* out /* host n x k */, srx_regress_info* info);
+/* Z^T Z (k x k, both triangles) and the column sums of Z; one of the two may be NULL. */
+int32_t srx_regress_gram(srx_mat* m, const uint64_t* genes, uint64_t k, const double* cov, uint64_t p, const srx_regress_opts* opts,
+                         double* gram_out /* k x k */, double* colsum_out /* k */, srx_regress_info* info);
+/* Host outputs, each may be NULL: scores n x n_pc, components k x n_pc, evr n_pc, mean k (m), sd k (s).  SRX_E_NOCONV as
+ * for srx_pca. */
+int32_t srx_pca_regress(srx_mat* m, const uint64_t* genes, uint64_t k, const double* cov, uint64_t p, const srx_regress_opts* opts,
+                        double* scores, double* components, double* evr, double* mean, double* sd, srx_regress_info* info);
+
 /* ---- a fitted PCA applied to other cells: Pca::transform (src/shared/processing/pca/mod.rs:156-185)
  * A model is k feature rows (V: k x n_pc, mu, sd, flags center / scale) held on the device.  For a query
  * matrix Xq (cells x its own genes) and a feature map feat (k entries: the query column of model row i,
@@ -1389,7 +1475,7 @@ void    srx_harmony_free(srx_harmony* h);
  *    together and a workgroup to a longer one; the result does not depend on which.
  * Refused with SRX_E_ARG and a message, nothing launched (*out is left untouched): a NULL argument (info, parents and
  *    parents_out may be NULL); counts in CSC storage (convert with srx_matrix_to_csr); a context with more than one rank; fitted
- *    without a PCA result, or with the PCA of Pearson residuals (srx_pca_pearson: no model to project with); cell or gene counts of the two matrices that differ; n == 0; n_sim == 0 in srx_doublets_result;
+ *    without a PCA result, or with the PCA of a dense residual matrix (srx_pca_pearson, srx_pca_regress: no model to project with); cell or gene counts of the two matrices that differ; n == 0; n_sim == 0 in srx_doublets_result;
  *    n + n_sim >= 2^32; sim_ratio negative or non-finite; expected_rate outside (0, 1); stdev_rate negative or NaN; bad
  *    transform bits; k negative; k_adj outside 1 .. SRX_DOUBLET_MAX_K or above n + n_sim - 1; n_dims above the scores'
  *    components; in the list form k_adj == 0, n_obs == 0 or an index >= n_obs + n_sim.  SRX_E_BOUNDS: a given parent >= n.

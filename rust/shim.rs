@@ -328,6 +328,49 @@ impl<'c> DeviceX<'c> {
         Ok((scores, comps, evr, info))
     }
 
+    /// scanpy's `regress_out` -> `scale(max_value)` -> `pca` on the values as stored: `covariates` (n_obs x n_cov row-major; empty:
+    /// plain scale + clip) regressed out of `genes`, the residuals scaled and clipped (`max_value` None: no clip), then their PCA
+    /// (srx.h states the definition).  Returns (scores, components, explained variance ratio, the info block); the scores also
+    /// stay resident as the handle's PCA result.
+    pub fn pca_regress_scale(&self, genes: &[u64], covariates: &[f64], n_cov: usize, n_components: usize, scale: bool,
+                             max_value: Option<f64>) -> Result<(Vec<f64>, Vec<f64>, Vec<f64>, SrxRegressInfo)> {
+        assert_eq!(covariates.len(), self.n_obs * n_cov);
+        let mut opts: SrxRegressOpts = unsafe { std::mem::zeroed() };
+        opts.scale = if scale { 1 } else { 0 };
+        opts.max_value = max_value.unwrap_or(0.0);
+        opts.pca.n_components = n_components as i32;
+        opts.pca.center = -1;
+        let n_pc = n_components.min(genes.len());
+        let mut scores = vec![0f64; (self.n_obs * n_pc).max(1)];
+        let mut comps = vec![0f64; (genes.len() * n_pc).max(1)];
+        let mut evr = vec![0f64; n_pc.max(1)];
+        let mut info: SrxRegressInfo = unsafe { std::mem::zeroed() };
+        let cov = if n_cov > 0 { covariates.as_ptr() } else { std::ptr::null() };
+        self.ctx.check(unsafe {
+            srx_pca_regress(self.mat, genes.as_ptr(), genes.len() as u64, cov, n_cov as u64, &opts, scores.as_mut_ptr(),
+                            comps.as_mut_ptr(), evr.as_mut_ptr(), null_mut(), null_mut(), &mut info)
+        })?;
+        scores.truncate(self.n_obs * n_pc);
+        comps.truncate(genes.len() * n_pc);
+        evr.truncate(n_pc);
+        Ok((scores, comps, evr, info))
+    }
+
+    /// The regressed, scaled and clipped values of `genes` (n_obs x genes.len() row-major): `srx_regress_residuals`.
+    pub fn regress_out(&self, genes: &[u64], covariates: &[f64], n_cov: usize, scale: bool, max_value: Option<f64>) -> Result<Vec<f64>> {
+        assert_eq!(covariates.len(), self.n_obs * n_cov);
+        let mut opts: SrxRegressOpts = unsafe { std::mem::zeroed() };
+        opts.scale = if scale { 1 } else { 0 };
+        opts.max_value = max_value.unwrap_or(0.0);
+        let mut out = vec![0f64; (self.n_obs * genes.len()).max(1)];
+        let cov = if n_cov > 0 { covariates.as_ptr() } else { std::ptr::null() };
+        self.ctx.check(unsafe {
+            srx_regress_residuals(self.mat, genes.as_ptr(), genes.len() as u64, cov, n_cov as u64, &opts, out.as_mut_ptr(), null_mut())
+        })?;
+        out.truncate(self.n_obs * genes.len());
+        Ok(out)
+    }
+
     /// dim_red/mod.rs:24-94 without the dense N x k matrix: returns (scores N x n_pc row-major, explained variance
     /// ratio, selected features) — exactly what `attach_pca_results` (:96-121) takes; `n_threads` is accepted and ignored,
     /// the `svd_mode` marker has no counterpart.

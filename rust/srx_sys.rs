@@ -253,6 +253,36 @@ pub struct SrxPearsonPcaInfo {      // `srx_pearson_pca_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxRegressOpts {      // `srx_regress_opts`
+    pub scale: i32,
+    pub reserved: i32,
+    pub max_value: f64,
+    pub chunk_cells: u64,
+    pub pca: SrxPcaOpts,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxRegressInfo {      // `srx_regress_info`
+    pub n_cells: u64,
+    pub n_genes: u64,
+    pub n_cov: u64,
+    pub n_constant_genes: u64,
+    pub n_clipped: u64,
+    pub min_pivot: f64,
+    pub ms_fit: f64,
+    pub ms_scale: f64,
+    pub ms_gram: f64,
+    pub ms_solve: f64,
+    pub ms_scores: f64,
+    pub n_chunks: u64,
+    pub chunk_cells: u64,
+    pub chunk_bytes: u64,
+    pub pca: SrxPcaInfo,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxKnnOpts {      // `srx_knn_opts`
     pub k: i32,
     pub n_dims: i32,
@@ -776,6 +806,20 @@ extern "C" {
                            info: *mut SrxPearsonPcaInfo) -> i32;
     pub fn srx_pearson_gram(m: *mut SrxMat, genes: *const u64, k: u64, opts: *const SrxPearsonPcaOpts,
                             gram_out: *mut f64, colsum_out: *mut f64, info: *mut SrxPearsonPcaInfo) -> i32;
+    pub fn srx_regress_fit(m: *mut SrxMat, genes: *const u64, k: u64, cov: *const f64, p: u64,
+                           opts: *const SrxRegressOpts, beta_out: *mut f64, xbar_out: *mut f64, sd_out: *mut f64,
+                           info: *mut SrxRegressInfo) -> i32;
+    pub fn srx_regress_sums(m: *mut SrxMat, genes: *const u64, k: u64, cov: *const f64, p: u64,
+                            opts: *const SrxRegressOpts, cbar_out: *mut f64, a_out: *mut f64, w_out: *mut f64,
+                            info: *mut SrxRegressInfo) -> i32;
+    pub fn srx_regress_residuals(m: *mut SrxMat, genes: *const u64, k: u64, cov: *const f64, p: u64,
+                                 opts: *const SrxRegressOpts, out: *mut f64, info: *mut SrxRegressInfo) -> i32;
+    pub fn srx_regress_gram(m: *mut SrxMat, genes: *const u64, k: u64, cov: *const f64, p: u64,
+                            opts: *const SrxRegressOpts, gram_out: *mut f64, colsum_out: *mut f64,
+                            info: *mut SrxRegressInfo) -> i32;
+    pub fn srx_pca_regress(m: *mut SrxMat, genes: *const u64, k: u64, cov: *const f64, p: u64,
+                           opts: *const SrxRegressOpts, scores: *mut f64, components: *mut f64, evr: *mut f64,
+                           mean: *mut f64, sd: *mut f64, info: *mut SrxRegressInfo) -> i32;
     pub fn srx_pca_model_from_result(m: *mut SrxMat, out: *mut *mut SrxPcaModel) -> i32;
     pub fn srx_pca_model_create(ctx: *mut SrxCtx, k: u64, n_pc: u64, components: *const f64, mean: *const f64,
                                 std: *const f64, sel: *const u64, center: i32, scale: i32,

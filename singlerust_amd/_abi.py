@@ -183,6 +183,19 @@ class PearsonPcaInfo(C.Structure):      # srx_pearson_pca_info
                 ("n_chunks", C.c_uint64), ("chunk_cells", C.c_uint64), ("chunk_bytes", C.c_uint64)]
 
 
+class RegressOpts(C.Structure):      # srx_regress_opts
+    _fields_ = [("scale", C.c_int32), ("reserved", C.c_int32), ("max_value", C.c_double), ("chunk_cells", C.c_uint64),
+                ("pca", PcaOpts)]
+
+
+class RegressInfo(C.Structure):      # srx_regress_info
+    _fields_ = [("n_cells", C.c_uint64), ("n_genes", C.c_uint64), ("n_cov", C.c_uint64),
+                ("n_constant_genes", C.c_uint64), ("n_clipped", C.c_uint64), ("min_pivot", C.c_double),
+                ("ms_fit", C.c_double), ("ms_scale", C.c_double), ("ms_gram", C.c_double), ("ms_solve", C.c_double),
+                ("ms_scores", C.c_double), ("n_chunks", C.c_uint64), ("chunk_cells", C.c_uint64),
+                ("chunk_bytes", C.c_uint64), ("pca", PcaInfo)]
+
+
 class KnnOpts(C.Structure):      # srx_knn_opts
     _fields_ = [("k", C.c_int32), ("n_dims", C.c_int32), ("include_self", C.c_int32), ("reserved_", C.c_int32)]
 
@@ -428,6 +441,16 @@ SIGNATURES = {
     "srx_pca_loadings": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint64, C.c_uint64, P]),
     "srx_pca_pearson": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PearsonPcaOpts), P, P, P, P, C.POINTER(PearsonPcaInfo)]),
     "srx_pearson_gram": (C.c_int32, [P, P, C.c_uint64, C.POINTER(PearsonPcaOpts), P, P, C.POINTER(PearsonPcaInfo)]),
+    "srx_regress_fit": (C.c_int32, [P, P, C.c_uint64, P, C.c_uint64, C.POINTER(RegressOpts), P, P, P,
+                                    C.POINTER(RegressInfo)]),
+    "srx_regress_sums": (C.c_int32, [P, P, C.c_uint64, P, C.c_uint64, C.POINTER(RegressOpts), P, P, P,
+                                     C.POINTER(RegressInfo)]),
+    "srx_regress_residuals": (C.c_int32, [P, P, C.c_uint64, P, C.c_uint64, C.POINTER(RegressOpts), P,
+                                          C.POINTER(RegressInfo)]),
+    "srx_regress_gram": (C.c_int32, [P, P, C.c_uint64, P, C.c_uint64, C.POINTER(RegressOpts), P, P,
+                                     C.POINTER(RegressInfo)]),
+    "srx_pca_regress": (C.c_int32, [P, P, C.c_uint64, P, C.c_uint64, C.POINTER(RegressOpts), P, P, P, P, P,
+                                    C.POINTER(RegressInfo)]),
     "srx_pca_model_from_result": (C.c_int32, [P, C.POINTER(P)]),
     "srx_pca_model_create": (C.c_int32, [P, C.c_uint64, C.c_uint64, P, P, P, P, C.c_int32, C.c_int32, C.POINTER(P)]),
     "srx_pca_model_info": (C.c_int32, [P, P, P, P]),

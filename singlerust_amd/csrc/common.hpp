@@ -150,7 +150,8 @@ struct srx_pca_state {           // what the last srx_pca / srx_pipeline left in
     bool valid = false;
     uint32_t k = 0, n_pc = 0;
     int center = 1, scale = 1;       // the flags the solve ran with (srx_pca_model_from_result)
-    bool residual = false;           // the result is a PCA of Pearson residuals (srx_pca_pearson): no model can be made of it
+    int residual = 0;                // kResidual*: the result is a PCA of a dense residual matrix (srx_pca_pearson, srx_pca_regress): no
+                                     // model can be made of it; the value says which call made it
     std::vector<int> round_counts;   // components resolved by each deflation round (sums to n_pc); set by run_pca with its plan
     double* d_scores = nullptr;      // n_rows x n_pc, row-major f64
     size_t scores_cap = 0;
@@ -204,6 +205,8 @@ struct srx_mat {
 };
 
 namespace srx {
+
+enum { kResidualNone = 0, kResidualPearson = 1, kResidualRegress = 2 };   // srx_pca_state::residual
 
 // ---- error plumbing ------------------------------------------------------------------------
 extern thread_local std::string g_tls_err;

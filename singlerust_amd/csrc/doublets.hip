@@ -556,6 +556,9 @@ int32_t srx_doublets_result(srx_mat* fitted, srx_mat* counts, const srx_doublet_
     }
     SRX_TRY(rates_check(ctx, o.rho, o.se_rho));
     if (!fitted->pca.valid || !fitted->pca.d_small) return fail(ctx, SRX_E_ARG, "doublets: no PCA result on the fitted matrix");
+    if (fitted->pca.residual == kResidualRegress)
+        return fail(ctx, SRX_E_ARG, "doublets: the fitted result is a PCA of regressed, scaled and clipped values (srx_pca_regress); the "
+                                    "simulated cells are projected by srx_pca_transform, which has no covariates to regress out of them");
     if (fitted->pca.residual)
         return fail(ctx, SRX_E_ARG, "doublets: the fitted result is a PCA of Pearson residuals (srx_pca_pearson); the simulated cells are "
                                     "projected by srx_pca_transform, which has no residual model");

@@ -220,6 +220,7 @@ inline PcaResultLayout result_block(const srx_pca_state& st) { return PcaResultL
 // `write_scores`, which writes columns [col0, col0 + n_r) of the scores, Z P - 1 cvec^T, at the stride `ld`.
 struct DenseSource {
     int k = 0;
+    int route = kResidualPearson;    // what srx_pca_state::residual says of the result
     uint64_t n_rows = 0;
     std::function<int32_t(const double* panel, const double* cvec, int col0, int n_r, double* scores, int ld)> write_scores;
 };

@@ -284,6 +284,9 @@ int32_t srx_pca_model_from_result(srx_mat* m, srx_pca_model** out) {
     srx_ctx* ctx = m->ctx;
     const srx_pca_state& st = m->pca;
     if (!st.valid || !st.d_small) return fail(ctx, SRX_E_ARG, "srx_pca_model_from_result: no PCA result on this matrix");
+    if (st.residual == kResidualRegress)
+        return fail(ctx, SRX_E_ARG, "srx_pca_model_from_result: the result is a PCA of regressed, scaled and clipped values (srx_pca_regress); "
+                                    "srx_pca_transform has no covariates to regress out of new cells");
     if (st.residual)
         return fail(ctx, SRX_E_ARG, "srx_pca_model_from_result: the result is a PCA of Pearson residuals (srx_pca_pearson); "
                                     "srx_pca_transform would apply normalise / log1p arithmetic to a residual model");

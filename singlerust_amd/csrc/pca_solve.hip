@@ -1065,7 +1065,7 @@ int32_t solve_and_stash(srx_ctx* ctx, bool f32, const RowMajor* parts, int n_par
                         const DenseSource* dense) {
     const int k = dense ? dense->k : parts[0].k;
     st.valid = false;
-    st.residual = dense != nullptr;
+    st.residual = dense ? dense->route : kResidualNone;
     st.info = srx_pca_info{};
     st.info.n_cells_global = n_cells;
     st.info.k = (uint32_t)k;

@@ -11,10 +11,11 @@
 // Between the two the Gram solver of pca_solve.hip runs unchanged on C = G - n m m^T (DenseSource): plans A / B, deflation, the
 // robust mode and the result block are shared with srx_pca.  The chunk is made twice, once for each product: keeping n x k
 // doubles (20.8 GB at 1.3 M x 2000) is what this route exists to avoid.
+// The two products and their host loops are shared with regress.hip (dense_pca_internal.hpp): a caller hands in what makes a chunk.
 // No floating-point atomics: a tile of G has one owner per launch, the launches of the chunks follow each other on the stream
 // (ascending chunk order), and where a chunk is cut into slabs their partial tiles are added in ascending slab order.
 #include "pearson_internal.hpp"
-#include "pca_internal.hpp"
+#include "dense_pca_internal.hpp"
 
 // the chunk kernels evaluate the definition and the sums of this file are stated in one order
 #pragma clang fp contract(off)
@@ -23,12 +24,12 @@ namespace srx {
 
 typedef double dvec4 __attribute__((ext_vector_type(4)));
 
-constexpr int kPpTile = 64;                     // a tile of G: 64 x 64, four waves of 32 x 32 (2 x 2 MFMA tiles each)
+constexpr int kPpTile = kDenseTile;             // a tile of G: 64 x 64, four waves of 32 x 32 (2 x 2 MFMA tiles each)
 constexpr int kPpThreads = 256;
 constexpr int kPpKU = 4;                        // MFMA K-steps (of 4 cells) whose loads are in flight together
 constexpr int kPpMaxSlabs = 64;
 constexpr uint64_t kPpChunkBytes = 64ull << 20; // a chunk of Z: a quarter of the 256 MB last-level cache
-constexpr int kPpMaxK = 16384;                  // the Gram solver's bound
+constexpr int kPpMaxK = kDenseMaxK;
 
 // ---- per-cell sums over the listed genes (totals = SELECTED): one pass over the stored entries ------------------------------------
 // A wave per row; lane l adds the entries l, l + 64, .. in that order, the 64 partial sums meet in a butterfly.
@@ -258,22 +259,8 @@ __global__ __launch_bounds__(kPpScoreWaves * 64) void k_pp_scores(const double* 
     }
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-struct PpRun {                       // everything between the arguments and the two products
-    PrPrep p;
-    int k = 0;
-    uint32_t ldz = 0;
-    uint64_t chunk = 0, n_chunks = 0;
-    std::vector<uint32_t> sorted;    // the list in ascending gene order: slot s of the solver is gene sorted[s]
-    std::vector<int> slot_of_pos;    // caller's position -> slot
-    uint32_t* d_genes = nullptr;
-    int32_t* d_slot_of = nullptr;
-    double* d_Z = nullptr;
-};
-
-int32_t pp_check_list(srx_ctx* ctx, const char* who, const uint64_t* genes, uint64_t k, uint64_t G) {
+// ---- host side: the passes of dense_pca_internal.hpp ------------------------------------------------------------------------------------
+int32_t dense_check_list(srx_ctx* ctx, const char* who, const uint64_t* genes, uint64_t k, uint64_t G) {
     if (k > (uint64_t)kPpMaxK) return fail(ctx, SRX_E_ARG, "%s: %llu listed genes (the k x k f64 Gram matrix is built up to k = %d)", who,
                                            (unsigned long long)k, kPpMaxK);
     std::vector<uint64_t> s(genes, genes + k);
@@ -286,6 +273,98 @@ int32_t pp_check_list(srx_ctx* ctx, const char* who, const uint64_t* genes, uint
     return SRX_OK;
 }
 
+int32_t dense_chunks_setup(srx_ctx* ctx, uint64_t n, uint64_t k64, uint64_t chunk_cells, DenseChunks& g) {
+    g.n = n;
+    g.k = (int)k64;
+    g.ldz = (uint32_t)((k64 + kPpTile - 1) / kPpTile * kPpTile);
+    // a chunk: what the last-level cache keeps between the kernel that makes it and the product that reads it, whole 64-row
+    // groups; never more rows than a 32-bit row index and the fill kernel's grid hold
+    const uint64_t row_bytes = (uint64_t)g.ldz * sizeof(double);
+    uint64_t chunk = chunk_cells ? chunk_cells : std::max<uint64_t>(64, kPpChunkBytes / row_bytes / 64 * 64);
+    chunk = std::min<uint64_t>(chunk, (1ull << 31) / g.ldz);
+    chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, at_least_one(n)));
+    g.chunk = chunk;
+    g.n_chunks = (n + chunk - 1) / chunk;
+    SRX_TRY(scratch(ctx, "pp_chunk", chunk * row_bytes, (void**)&g.d_Z));
+    return SRX_OK;
+}
+
+// Gp (packed upper triangle, slot order) and colsum over all chunks; both zeroed here
+int32_t dense_gram_pass(srx_ctx* ctx, const DenseChunks& g, const DenseChunkFn& make, double* Gp, double* colsum, double* ms) {
+    const int k = g.k, n_t = (int)(g.ldz / kPpTile), n_pairs = n_t * (n_t + 1) / 2;
+    // slabs: enough workgroups for two per CU where the tile pairs alone are fewer, each slab whole groups of 64 rows
+    const uint64_t groups = (g.chunk + 63) / 64;
+    const int want = std::max(1, (2 * ctx->n_cus + n_pairs - 1) / n_pairs);
+    const int n_slabs_max = (int)std::min<uint64_t>(std::min<uint64_t>(groups, (uint64_t)want), kPpMaxSlabs);
+    const int cs_slabs_max = (int)std::min<uint64_t>(groups, kPpMaxSlabs);
+    double *part = nullptr, *cs_part;
+    SRX_TRY(scratch(ctx, "pp_part", (size_t)n_slabs_max * n_pairs * kPpTile * kPpTile * sizeof(double), (void**)&part));
+    SRX_TRY(scratch(ctx, "pp_cs_part", (size_t)cs_slabs_max * at_least_one(k) * sizeof(double), (void**)&cs_part));
+    StreamTimer timer(ctx, ctx->stream);
+    SRX_TRY(timer.start());
+    SRX_HIP(ctx, hipMemsetAsync(Gp, 0, gram_packed_count(k) * sizeof(double), ctx->stream));
+    SRX_HIP(ctx, hipMemsetAsync(colsum, 0, (size_t)k * sizeof(double), ctx->stream));
+    for (uint64_t row0 = 0; row0 < g.n; row0 += g.chunk) {
+        const uint64_t rows = std::min(g.chunk, g.n - row0);
+        SRX_TRY(make(row0, rows, g.d_Z));
+        const uint64_t gr = (rows + 63) / 64;
+        const uint32_t n_slabs = (uint32_t)std::min<uint64_t>(gr, (uint64_t)n_slabs_max);
+        const uint32_t slab_rows = (uint32_t)((gr + n_slabs - 1) / n_slabs * 64);
+        const uint32_t ns = (uint32_t)((rows + slab_rows - 1) / slab_rows);
+        hipLaunchKernelGGL(k_pp_syrk, dim3((unsigned)n_pairs, ns), dim3(kPpThreads), 0, ctx->stream, (const double*)g.d_Z, g.ldz, (uint32_t)rows,
+                           slab_rows, n_t, k, Gp, part);
+        if (ns > 1)
+            hipLaunchKernelGGL(k_pp_syrk_reduce, dim3((unsigned)n_pairs * 16), dim3(256), 0, ctx->stream, (const double*)part, n_pairs, (int)ns,
+                               n_t, k, Gp);
+        const uint32_t cs_n = (uint32_t)std::min<uint64_t>(gr, (uint64_t)cs_slabs_max);
+        const uint32_t cs_rows = (uint32_t)((gr + cs_n - 1) / cs_n * 64);
+        const uint32_t cs_ns = (uint32_t)((rows + cs_rows - 1) / cs_rows);
+        hipLaunchKernelGGL(k_pp_colsum, dim3(grid256(k), cs_ns), dim3(256), 0, ctx->stream, (const double*)g.d_Z, g.ldz, (uint32_t)rows, cs_rows,
+                           (uint32_t)k, cs_part);
+        hipLaunchKernelGGL(k_pp_colsum_reduce, dim3(grid256(k)), dim3(256), 0, ctx->stream, (const double*)cs_part, cs_ns, (uint32_t)k, colsum);
+        SRX_HIP(ctx, hipGetLastError());
+    }
+    SRX_TRY(timer.stop(ms));
+    return SRX_OK;
+}
+
+int32_t dense_score_pass(srx_ctx* ctx, const DenseChunks& g, const DenseChunkFn& make, const double* P, const double* cvec, int n_r,
+                         double* out, int ld, double* ms_acc) {
+    StreamTimer timer(ctx, ctx->stream);
+    SRX_TRY(timer.start());
+    for (uint64_t row0 = 0; row0 < g.n; row0 += g.chunk) {
+        const uint64_t rows = std::min(g.chunk, g.n - row0);
+        SRX_TRY(make(row0, rows, g.d_Z));
+        hipLaunchKernelGGL(k_pp_scores, dim3((unsigned)((rows + 15) / 16)), dim3(kPpScoreWaves * 64), 0, ctx->stream, (const double*)g.d_Z, g.ldz,
+                           (uint32_t)rows, (uint32_t)g.k, P, cvec, n_r, out + row0 * (size_t)ld, ld);
+        SRX_HIP(ctx, hipGetLastError());
+    }
+    double ms = 0.0;
+    SRX_TRY(timer.stop(&ms));
+    *ms_acc += ms;
+    return SRX_OK;
+}
+
+int32_t dense_finish(srx_ctx* ctx, const double* Gp, const double* colsum, int k, uint64_t n, int center, const SelDev& sd) {
+    hipLaunchKernelGGL(k_pp_finish, dim3(1), dim3(1024), 0, ctx->stream, Gp, colsum, k, (double)n, center, sd.d_mu, sd.d_sd, sd.d_dinv,
+                       sd.d_trace);
+    SRX_HIP(ctx, hipGetLastError());
+    return SRX_OK;
+}
+
+// ---- host side: the Pearson calls ----------------------------------------------------------------------------------------------------------
+namespace {
+
+struct PpRun {                       // everything between the arguments and the two products
+    PrPrep p;
+    int k = 0;
+    DenseChunks g;                   // the chunk geometry and the chunk buffer
+    std::vector<uint32_t> sorted;    // the list in ascending gene order: slot s of the solver is gene sorted[s]
+    std::vector<int> slot_of_pos;    // caller's position -> slot
+    uint32_t* d_genes = nullptr;
+    int32_t* d_slot_of = nullptr;
+};
+
 // `m` is a CSR handle.  The preparation of every Pearson call, the sums over the listed genes where asked, the list and its
 // slot table on the device, the chunk size and the chunk buffer.
 int32_t pp_setup(srx_mat* m, const uint64_t* genes, uint64_t k64, const srx_pearson_opts* popts, int totals, uint64_t chunk_cells,
@@ -294,7 +373,6 @@ int32_t pp_setup(srx_mat* m, const uint64_t* genes, uint64_t k64, const srx_pear
     SRX_TRY(pr_prepare(m, popts, who, R.p));
     const uint64_t n = R.p.n, G = R.p.G;
     R.k = (int)k64;
-    R.ldz = (uint32_t)((k64 + kPpTile - 1) / kPpTile * kPpTile);
     std::vector<uint32_t> order(k64);
     std::iota(order.begin(), order.end(), 0u);
     std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return genes[a] < genes[b]; });
@@ -324,71 +402,23 @@ int32_t pp_setup(srx_mat* m, const uint64_t* genes, uint64_t k64, const srx_pear
         R.p.d_cell = d_rsel;
         SRX_TRY(pr_totals(ctx, d_rsel, n, R.p.d_gene, G, &R.p.a.total, &R.p.n_empty));
     }
-    // a chunk: what the last-level cache keeps between the kernel that makes it and the product that reads it, whole 64-row
-    // groups; never more rows than a 32-bit row index and the fill kernel's grid hold
-    const uint64_t row_bytes = (uint64_t)R.ldz * sizeof(double);
-    uint64_t chunk = chunk_cells ? chunk_cells : std::max<uint64_t>(64, kPpChunkBytes / row_bytes / 64 * 64);
-    chunk = std::min<uint64_t>(chunk, (1ull << 31) / R.ldz);
-    chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, at_least_one(n)));
-    R.chunk = chunk;
-    R.n_chunks = (n + chunk - 1) / chunk;
-    SRX_TRY(scratch(ctx, "pp_chunk", chunk * row_bytes, (void**)&R.d_Z));
+    SRX_TRY(dense_chunks_setup(ctx, n, k64, chunk_cells, R.g));
     return SRX_OK;
 }
 
 // rows [row0, row0 + rows) of Z into the chunk buffer
-int32_t pp_make_chunk(srx_mat* m, const PpRun& R, uint64_t row0, uint64_t rows) {
+int32_t pp_make_chunk(srx_mat* m, const PpRun& R, uint64_t row0, uint64_t rows, double* Z) {
     srx_ctx* ctx = m->ctx;
-    hipLaunchKernelGGL(k_pp_fill, dim3((unsigned)((rows * R.ldz + 255) / 256)), dim3(256), 0, ctx->stream, R.p.d_cell, R.p.d_gene,
-                       (const uint32_t*)R.d_genes, (uint32_t)R.k, R.ldz, row0, rows, R.p.a, R.d_Z);
+    hipLaunchKernelGGL(k_pp_fill, dim3((unsigned)((rows * R.g.ldz + 255) / 256)), dim3(256), 0, ctx->stream, R.p.d_cell, R.p.d_gene,
+                       (const uint32_t*)R.d_genes, (uint32_t)R.k, R.g.ldz, row0, rows, R.p.a, Z);
     const unsigned grid = (unsigned)((rows + 3) / 4);
     if (is_f32(m))
         hipLaunchKernelGGL(k_pp_stored<float>, dim3(grid), dim3(256), 0, ctx->stream, m->d_indptr, m->d_indices, (const float*)m->d_values,
-                           R.p.d_cell, R.p.d_gene, (const int32_t*)R.d_slot_of, R.ldz, row0, rows, R.p.a, R.d_Z);
+                           R.p.d_cell, R.p.d_gene, (const int32_t*)R.d_slot_of, R.g.ldz, row0, rows, R.p.a, Z);
     else
         hipLaunchKernelGGL(k_pp_stored<double>, dim3(grid), dim3(256), 0, ctx->stream, m->d_indptr, m->d_indices, (const double*)m->d_values,
-                           R.p.d_cell, R.p.d_gene, (const int32_t*)R.d_slot_of, R.ldz, row0, rows, R.p.a, R.d_Z);
+                           R.p.d_cell, R.p.d_gene, (const int32_t*)R.d_slot_of, R.g.ldz, row0, rows, R.p.a, Z);
     SRX_HIP(ctx, hipGetLastError());
-    return SRX_OK;
-}
-
-// Gp (packed upper triangle, slot order) and colsum over all chunks; both zeroed here
-int32_t pp_gram(srx_mat* m, const PpRun& R, double* Gp, double* colsum, double* ms) {
-    srx_ctx* ctx = m->ctx;
-    const int k = R.k, n_t = (int)(R.ldz / kPpTile), n_pairs = n_t * (n_t + 1) / 2;
-    // slabs: enough workgroups for two per CU where the tile pairs alone are fewer, each slab whole groups of 64 rows
-    const uint64_t groups = (R.chunk + 63) / 64;
-    const int want = std::max(1, (2 * ctx->n_cus + n_pairs - 1) / n_pairs);
-    const int n_slabs_max = (int)std::min<uint64_t>(std::min<uint64_t>(groups, (uint64_t)want), kPpMaxSlabs);
-    const int cs_slabs_max = (int)std::min<uint64_t>(groups, kPpMaxSlabs);
-    double *part = nullptr, *cs_part;
-    SRX_TRY(scratch(ctx, "pp_part", (size_t)n_slabs_max * n_pairs * kPpTile * kPpTile * sizeof(double), (void**)&part));
-    SRX_TRY(scratch(ctx, "pp_cs_part", (size_t)cs_slabs_max * at_least_one(k) * sizeof(double), (void**)&cs_part));
-    StreamTimer timer(ctx, ctx->stream);
-    SRX_TRY(timer.start());
-    SRX_HIP(ctx, hipMemsetAsync(Gp, 0, gram_packed_count(k) * sizeof(double), ctx->stream));
-    SRX_HIP(ctx, hipMemsetAsync(colsum, 0, (size_t)k * sizeof(double), ctx->stream));
-    for (uint64_t row0 = 0; row0 < R.p.n; row0 += R.chunk) {
-        const uint64_t rows = std::min(R.chunk, R.p.n - row0);
-        SRX_TRY(pp_make_chunk(m, R, row0, rows));
-        const uint64_t g = (rows + 63) / 64;
-        const uint32_t n_slabs = (uint32_t)std::min<uint64_t>(g, (uint64_t)n_slabs_max);
-        const uint32_t slab_rows = (uint32_t)((g + n_slabs - 1) / n_slabs * 64);
-        const uint32_t ns = (uint32_t)((rows + slab_rows - 1) / slab_rows);
-        hipLaunchKernelGGL(k_pp_syrk, dim3((unsigned)n_pairs, ns), dim3(kPpThreads), 0, ctx->stream, (const double*)R.d_Z, R.ldz, (uint32_t)rows,
-                           slab_rows, n_t, k, Gp, part);
-        if (ns > 1)
-            hipLaunchKernelGGL(k_pp_syrk_reduce, dim3((unsigned)n_pairs * 16), dim3(256), 0, ctx->stream, (const double*)part, n_pairs, (int)ns,
-                               n_t, k, Gp);
-        const uint32_t cs_n = (uint32_t)std::min<uint64_t>(g, (uint64_t)cs_slabs_max);
-        const uint32_t cs_rows = (uint32_t)((g + cs_n - 1) / cs_n * 64);
-        const uint32_t cs_ns = (uint32_t)((rows + cs_rows - 1) / cs_rows);
-        hipLaunchKernelGGL(k_pp_colsum, dim3(grid256(k), cs_ns), dim3(256), 0, ctx->stream, (const double*)R.d_Z, R.ldz, (uint32_t)rows, cs_rows,
-                           (uint32_t)k, cs_part);
-        hipLaunchKernelGGL(k_pp_colsum_reduce, dim3(grid256(k)), dim3(256), 0, ctx->stream, (const double*)cs_part, cs_ns, (uint32_t)k, colsum);
-        SRX_HIP(ctx, hipGetLastError());
-    }
-    SRX_TRY(timer.stop(ms));
     return SRX_OK;
 }
 
@@ -402,9 +432,9 @@ void pp_info(const PpRun& R, srx_pearson_pca_info* info) {
     info->total = R.p.a.total;
     info->theta = R.p.a.theta;
     info->clip = R.p.a.clip;
-    info->n_chunks = R.n_chunks;
-    info->chunk_cells = R.chunk;
-    info->chunk_bytes = R.chunk * (uint64_t)R.ldz * sizeof(double);
+    info->n_chunks = R.g.n_chunks;
+    info->chunk_cells = R.g.chunk;
+    info->chunk_bytes = R.g.chunk * (uint64_t)R.g.ldz * sizeof(double);
 }
 
 int32_t pp_check_common(srx_mat* m, const uint64_t* genes, uint64_t k, const srx_pearson_pca_opts* opts, const char* who) {
@@ -415,7 +445,7 @@ int32_t pp_check_common(srx_mat* m, const uint64_t* genes, uint64_t k, const srx
     if (k == 0) return fail(ctx, SRX_E_ARG, "%s: an empty gene list (k >= 1)", who);
     if (opts && opts->totals != SRX_PEARSON_TOTALS_ALL && opts->totals != SRX_PEARSON_TOTALS_SELECTED)
         return fail(ctx, SRX_E_ARG, "%s: totals = %d (0: the whole matrix, 1: the listed genes)", who, opts->totals);
-    return pp_check_list(ctx, who, genes, k, m->csc ? m->n_rows : m->n_cols);
+    return dense_check_list(ctx, who, genes, k, m->csc ? m->n_rows : m->n_cols);
 }
 
 int32_t pp_gram_entry(srx_mat* m, const uint64_t* genes, uint64_t k, const srx_pearson_pca_opts* opts, double* gram_out, double* colsum_out,
@@ -431,12 +461,13 @@ int32_t pp_gram_entry(srx_mat* m, const uint64_t* genes, uint64_t k, const srx_p
     }
     PpRun R;
     SRX_TRY(pp_setup(m, genes, k, opts ? &opts->pearson : nullptr, opts ? opts->totals : 0, opts ? opts->chunk_cells : 0, "pearson_gram", R));
+    const DenseChunkFn make = [&](uint64_t row0, uint64_t rows, double* Z) { return pp_make_chunk(m, R, row0, rows, Z); };
     srx_pearson_pca_info inf;
     pp_info(R, &inf);
     double *Gp, *colsum;
     SRX_TRY(scratch(ctx, "pp_gpacked", gram_packed_count((int)k) * sizeof(double), (void**)&Gp));
     SRX_TRY(scratch(ctx, "pp_colsum", k * sizeof(double), (void**)&colsum));
-    SRX_TRY(pp_gram(m, R, Gp, colsum, &inf.ms_gram));
+    SRX_TRY(dense_gram_pass(ctx, R.g, make, Gp, colsum, &inf.ms_gram));
     std::vector<double> hp(gram_packed_count((int)k)), hc(k);
     SRX_TRY(d2h(ctx, hp.data(), Gp, hp.size() * sizeof(double)));
     SRX_TRY(d2h(ctx, hc.data(), colsum, hc.size() * sizeof(double)));
@@ -477,6 +508,7 @@ int32_t pp_pca(srx_mat* m, const uint64_t* genes, uint64_t k64, const srx_pearso
     SRX_TRY(resolve_opts(ctx, &po, k, m->n_rows, false, o, l_act));
     PpRun R;
     SRX_TRY(pp_setup(m, genes, k64, opts ? &opts->pearson : nullptr, opts ? opts->totals : 0, opts ? opts->chunk_cells : 0, "pca_pearson", R));
+    const DenseChunkFn make = [&](uint64_t row0, uint64_t rows, double* Z) { return pp_make_chunk(m, R, row0, rows, Z); };
     srx_pearson_pca_info inf;
     pp_info(R, &inf);
     const uint64_t n = R.p.n;
@@ -502,29 +534,15 @@ int32_t pp_pca(srx_mat* m, const uint64_t* genes, uint64_t k64, const srx_pearso
     SRX_TRY(h2d(ctx, sd.d_sel_rank, list.data(), (size_t)k * sizeof(int32_t)));
     SRX_HIP(ctx, hipMemsetAsync(sd.d_status, 0, 256, ctx->stream));
 
-    SRX_TRY(pp_gram(m, R, Gp, colsum, &inf.ms_gram));
-    hipLaunchKernelGGL(k_pp_finish, dim3(1), dim3(1024), 0, ctx->stream, (const double*)Gp, (const double*)colsum, k, (double)n, o.center,
-                       sd.d_mu, sd.d_sd, sd.d_dinv, sd.d_trace);
-    SRX_HIP(ctx, hipGetLastError());
+    SRX_TRY(dense_gram_pass(ctx, R.g, make, Gp, colsum, &inf.ms_gram));
+    SRX_TRY(dense_finish(ctx, Gp, colsum, k, n, o.center, sd));
 
     double ms_scores = 0.0;
     DenseSource src;
     src.k = k;
     src.n_rows = n;
     src.write_scores = [&](const double* P, const double* cvec, int col0, int n_r, double* scores, int ld) -> int32_t {
-        StreamTimer timer(ctx, ctx->stream);
-        SRX_TRY(timer.start());
-        for (uint64_t row0 = 0; row0 < n; row0 += R.chunk) {
-            const uint64_t rows = std::min(R.chunk, n - row0);
-            SRX_TRY(pp_make_chunk(m, R, row0, rows));
-            hipLaunchKernelGGL(k_pp_scores, dim3((unsigned)((rows + 15) / 16)), dim3(kPpScoreWaves * 64), 0, ctx->stream, (const double*)R.d_Z, R.ldz,
-                               (uint32_t)rows, (uint32_t)k, P, cvec, n_r, scores + row0 * (size_t)ld + col0, ld);
-            SRX_HIP(ctx, hipGetLastError());
-        }
-        double ms = 0.0;
-        SRX_TRY(timer.stop(&ms));
-        ms_scores += ms;
-        return SRX_OK;
+        return dense_score_pass(ctx, R.g, make, P, cvec, n_r, scores + col0, ld, &ms_scores);
     };
     StreamTimer timer(ctx, ctx->stream);
     SRX_TRY(timer.start());

@@ -427,6 +427,61 @@ inline PearsonPca pca_pearson_residuals(IMAnnData& a, const std::vector<std::uin
     return r;
 }
 
+// scanpy's regress_out -> scale(max_value) -> pca on the values as stored (after normalise + log1p): the covariates (n_obs x
+// n_cov row-major; empty: plain scale + clip) regressed out of `genes`, the residuals scaled to unit variance and clipped, then
+// their PCA (srx.h states the definition).  The scores stay resident as the handle's PCA result and are stored as obsm["X_pca"].
+struct RegressPca {
+    Array2 scores, components;                                    // n_obs x n_pc, genes.size() x n_pc
+    std::vector<double> explained_variance_ratio, mean, std_;     // mean of the clipped values, the scale s
+    srx_regress_info info{};
+};
+inline RegressPca pca_regress_scale(IMAnnData& a, const std::vector<std::uint64_t>& genes, const std::vector<double>& covariates,
+                                    std::size_t n_cov, int n_components = 50, bool scale = true, double max_value = 10.0) {
+    srx_regress_opts opts{};
+    opts.scale = scale ? 1 : 0;
+    opts.max_value = max_value;
+    opts.pca.n_components = n_components;
+    opts.pca.center = -1;
+    RegressPca r;
+    const std::size_t k = genes.size();
+    const std::size_t n_pc = std::min<std::size_t>(n_components < 0 ? 2 : (std::size_t)n_components, k);
+    if (covariates.size() != a.n_obs() * n_cov) throw std::invalid_argument("pca_regress_scale: covariates must hold n_obs x n_cov values");
+    r.scores.nrows = a.n_obs();
+    r.scores.ncols = n_pc;
+    r.components.nrows = k;
+    r.components.ncols = n_pc;
+    r.scores.data.assign(std::max<std::size_t>(a.n_obs() * n_pc, 1), 0.0);
+    r.components.data.assign(std::max<std::size_t>(k * n_pc, 1), 0.0);
+    r.explained_variance_ratio.assign(std::max<std::size_t>(n_pc, 1), 0.0);
+    r.mean.assign(std::max<std::size_t>(k, 1), 0.0);
+    r.std_.assign(std::max<std::size_t>(k, 1), 0.0);
+    a.ctx().check(srx_pca_regress(a.x(), genes.data(), k, n_cov ? covariates.data() : nullptr, n_cov, &opts, r.scores.data.data(),
+                                  r.components.data.data(), r.explained_variance_ratio.data(), r.mean.data(), r.std_.data(), &r.info));
+    r.scores.data.resize(a.n_obs() * n_pc);
+    r.components.data.resize(k * n_pc);
+    r.explained_variance_ratio.resize(n_pc);
+    r.mean.resize(k);
+    r.std_.resize(k);
+    a.obsm()["X_pca"] = r.scores;
+    return r;
+}
+// the regressed, scaled and clipped values themselves (n_obs x genes.size()): srx_regress_residuals
+inline Array2 regress_out(const IMAnnData& a, const std::vector<std::uint64_t>& genes, const std::vector<double>& covariates,
+                          std::size_t n_cov, bool scale = false, double max_value = 0.0) {
+    srx_regress_opts opts{};
+    opts.scale = scale ? 1 : 0;
+    opts.max_value = max_value;
+    if (covariates.size() != a.n_obs() * n_cov) throw std::invalid_argument("regress_out: covariates must hold n_obs x n_cov values");
+    Array2 out;
+    out.nrows = a.n_obs();
+    out.ncols = genes.size();
+    out.data.assign(std::max<std::size_t>(out.nrows * out.ncols, 1), 0.0);
+    a.ctx().check(srx_regress_residuals(a.x(), genes.data(), genes.size(), n_cov ? covariates.data() : nullptr, n_cov, &opts,
+                                        out.data.data(), nullptr));
+    out.data.resize(out.nrows * out.ncols);
+    return out;
+}
+
 namespace dim_red {                                              // src/memory/processing/dim_red/mod.rs
 inline std::vector<std::uint64_t> select_features(const IMAnnData& a, const FeatureSelection& fs) {   // :123-156
     switch (fs.kind) {

@@ -16,6 +16,7 @@ from .hvg import (highly_variable_genes_pearson, highly_variable_genes_seurat_v3
 from .louvain import graph_labels, louvain, louvain_csr
 from .markers import group_moments, rank_genes_groups
 from .neighbors import KnnIndex, connectivities_from_knn, knn_index, knn_index_points, knn_points, neighbors, neighbors_approx
+from .regress import pca_regress_scale, regress_fit, regress_gram, regress_out, scale
 from .tsne import Tsne, tsne, tsne_affinities, tsne_affinities_graph, tsne_embedding, tsne_forces, tsne_run
 from .umap import fit_ab, graph_embedding, umap, umap_csr
 
