@@ -551,6 +551,105 @@ int32_t srx_regress_gram(srx_mat* m, const uint64_t* genes, uint64_t k, const do
 int32_t srx_pca_regress(srx_mat* m, const uint64_t* genes, uint64_t k, const double* cov, uint64_t p, const srx_regress_opts* opts,
                         double* scores, double* components, double* evr, double* mean, double* sd, srx_regress_info* info);
 
+/* ---- sums over gene lists per cell; the gene-set score built on them (not in the reference) ----------------------------------
+ * What sc.tl.score_genes and sc.tl.score_genes_cell_cycle give obs["score"], obs["S_score"], obs["G2M_score"] (the usual
+ * covariates of the regress section above), and what calculate_qc_metrics(qc_vars=...) gives per gene subset
+ * (total_counts_mt, pct_counts_mt).  Additive, detected by symbol, no profiling class of its own (the times are in the info
+ * structs).  The definition here is what is tested.  NOTHING has been compared with scanpy, which is not installed where this
+ * was built; the control genes are chosen by a hash where scanpy samples with numpy's or pandas's generator (a stated
+ * departure, below), so the scores of one dataset differ from scanpy's by the choice of controls.
+ *
+ * 1. Sums over gene lists (srx_gene_list_sums).  m is a CSR handle with N cells and G genes, read as stored (f32 storage is
+ *   read as (double)x).  List t holds DISTINCT gene indices < G: list_genes[list_ptr[t] .. list_ptr[t + 1]); a gene may be in
+ *   any number of lists.  Per (cell i, list t) over the STORED entries of row i whose column is in list t (a stored 0 counts):
+ *     c[i][t] = their number,   S[i][t] = their sum,
+ *   S accumulated as a 64-bit fixed-point integer round(x 2^sum_scale_log2), ties to even.  The scale rule is that of
+ *   srx_group_moments with one change:
+ *     max_abs = the largest |x| over ALL stored values (one reduction pass, which also refuses NaN / Inf: SRX_E_NAN),
+ *     e = the smallest integer with max_abs < 2^e (0 when max_abs == 0), taken no lower than -30,
+ *     L = ceil(log2(max(longest list of the call, 1)))    (not from N: rows are canonical CSR, so a sum has at most as many
+ *         terms as its list has genes),
+ *     sum_scale_log2 = 62 - e - L.
+ *   SUM = f64(S_int) 2^-sum_scale_log2.  Consequences: every |S_int| stays below 2^62; the sums are independent of the order in
+ *   which the entries are met and bit-identical from call to call; they are exact (equal to the integer sums) for integer counts
+ *   while sum_scale_log2 >= 0; otherwise |S_int 2^-sum_scale_log2 - exact| <= c 2^-(sum_scale_log2 + 1), and SUM, the f64 of an
+ *   integer that may exceed 2^53, lies within another half ulp of SUM of that.  The scale belongs to the CALL (its longest
+ *   list): the same list summed beside a list of another power-of-two size class may differ within that bound.
+ *   How: more than 64 lists are ceil(n_lists / 64) walks over the column indices (the 16-bit mirror where the handle has one,
+ *   else the 32-bit indices); each index is tested against a 1-bit "in any list of this walk" bitmap (in LDS up to 524288 genes,
+ *   read from global memory above); only a hit loads its value and the gene's 64-bit membership mask from a G x 8 B table and
+ *   adds into the per-list integer accumulators of its row's wave in LDS.  No floating-point atomic, no contraction.
+ *   The handle is left exactly as it was: values, dtype, version, moments cache, resident PCA result.
+ *   Refused with a message, nothing written, in this order.  SRX_E_ARG: (1) a NULL handle, list_ptr or list_genes, or both outputs
+ *   NULL; (2) n_lists 0 or above SRX_GENE_LISTS_MAX; (3) a CSC handle; (4) a context with more than one rank; (5) an open backed
+ *   session; (6) 2^32 rows or more; (7) a list_ptr that does not start at 0 or that decreases; (8) an empty list; (9) a gene index
+ *   >= n_cols; (10) a gene repeated within a list.  Then SRX_E_NAN: a stored value is NaN or Inf.  SRX_E_OOM: the N x n_lists
+ *   tables do not fit on the device.
+ *
+ * 2. Control genes (srx_score_genes_controls): pure host code, no context, no device.  gene_mean holds G means; `pool` lists the
+ *   P genes controls may come from (NULL, 0: every gene, P = G).  These are scanpy's lines, restated:
+ *     n_items = rint(P / (n_bins - 1)), ties to even (np.round);   rank_j = 1 + the number of pool genes with a strictly smaller
+ *     mean (pandas rank(method="min"); -0.0 == 0.0);   cut_j = rank_j / n_items, integer division.
+ *   For set s and every distinct cut c among its genes the candidates are the pool genes with cut == c — as they are with
+ *   ctrl_as_ref, without the set's own genes otherwise.  More than ctrl_size candidates: the ctrl_size that come first under
+ *   (key_j ascending, j ascending) are kept, key_j = mix(seed + 0x9E3779B97F4A7C15 (j + 1)) mod 2^64, mix() being splitmix64's
+ *   finaliser as in the UMAP section.  The control list of s is the union over its cuts minus the set's own genes, in ascending
+ *   gene order.  Property: the key depends on neither the set nor the cut, so scoring several sets in one call equals scoring
+ *   each alone, bit for bit.
+ *   Worked example: means [0, 0, 1, 2, 3, 5, 8, 13], n_bins = 5: n_items = 2; ranks 1, 1, 3, 4, 5, 6, 7, 8; cuts 0, 0, 1, 2, 2,
+ *   3, 3, 4.  P = 10, n_bins = 5: n_items = rint(2.5) = 2.
+ *   Stated departure: scanpy draws the ctrl_size genes of a bin with numpy's / pandas's generator; here the hash decides.
+ *   Capacity: set s needs at most ctrl_size * min(|s|, P / n_items + 1) entries of ctrl_genes_out; `capacity` is their sum.
+ *   Refused with SRX_E_ARG and a message, nothing written, in this order: (1) a NULL array (gene_mean, set_ptr, set_genes,
+ *   ctrl_ptr_out, ctrl_genes_out; pool NULL with n_pool > 0); n_sets == 0; (2) n_bins < 2; (3) a pool gene >= n_genes or repeated;
+ *   (4) n_items == 0; (5) a non-finite mean of a pool gene; (6) a set_ptr that does not start at 0 or that decreases, an empty
+ *   set; (7) a set gene >= n_genes, repeated within its set, or not in the pool; (8) a set whose control list comes out empty,
+ *   naming the set; (9) a capacity smaller than the lists need.
+ *
+ * 3. The score (srx_score_genes).  gene_mean_j = srx_compute_sum(m, Column)[j] / N, the library's own column sum, bit for bit
+ *   (as the regress section); controls from 2.; sums from 1. over 2 n_sets lists — the sets, then their controls — in one call,
+ *   so one walk up to 32 sets;  score[i][s] = SUM_set / |set| - SUM_ctrl / |ctrl|, f64, in that order, no contraction, on the
+ *   device.  Refusals, in this order: 1.(1)-(6) with n_sets in place of n_lists (1 .. SRX_GENE_LISTS_MAX / 2; score_out may not
+ *   be NULL; the control outputs may, both or neither), SRX_E_NAN, then 2.(2)-(9), where `capacity` is only checked when the
+ *   control outputs are given.  The moments cache is filled with the moments of the current values if it was empty (that is
+ *   srx_compute_sum); everything else about the handle stays.
+ * Out of scope: CSC handles, sharded contexts and backed sessions; use_raw and layers (the values are read as stored); scanpy's
+ *   random sampling; weighted signatures. */
+#define SRX_GENE_LISTS_MAX 4096
+typedef struct srx_gene_list_info {
+    uint64_t n_rows, n_cols, n_lists, longest_list;
+    int32_t  sum_scale_log2;
+    uint32_t n_walks;
+    double   max_abs;
+    double   ms_scan, ms_walk;   /* hipEvent times: the reduction over the values; the walks with their table uploads */
+} srx_gene_list_info;
+typedef struct srx_score_genes_opts {
+    uint32_t ctrl_size;    /* 0: 50                          */
+    uint32_t n_bins;       /* 0: 25                          */
+    uint64_t seed;
+    int32_t  ctrl_as_ref;  /* < 0 or 1: true, 0: false       */
+    int32_t  reserved;
+} srx_score_genes_opts;    /* NULL: {50, 25, 0, true}        */
+typedef struct srx_score_genes_info {
+    uint64_t n_rows, n_cols, n_sets, n_pool, n_ctrl_total /* sum of |ctrl| */, n_items, longest_list;
+    int32_t  sum_scale_log2;
+    uint32_t n_walks;
+    double   max_abs;
+    double   ms_mean, ms_ctrl, ms_walk;   /* hipEvent times: scan + column means; the control genes (host); walks + score */
+} srx_score_genes_info;
+/* sum_out (f64), cnt_out (u32): host, n_rows x n_lists row-major; either may be NULL, not both. */
+int32_t srx_gene_list_sums(srx_mat* m, const uint64_t* list_ptr /* n_lists + 1 */, const uint64_t* list_genes, uint64_t n_lists,
+                           double* sum_out, uint32_t* cnt_out, srx_gene_list_info* info);
+/* cut_out: G entries, UINT32_MAX outside the pool; may be NULL. */
+int32_t srx_score_genes_controls(const double* gene_mean /* n_genes */, uint64_t n_genes, const uint64_t* pool, uint64_t n_pool,
+                                 const uint64_t* set_ptr /* n_sets + 1 */, const uint64_t* set_genes, uint64_t n_sets,
+                                 const srx_score_genes_opts* opts, uint64_t* ctrl_ptr_out /* n_sets + 1 */, uint64_t* ctrl_genes_out,
+                                 uint64_t capacity, uint32_t* cut_out);
+/* score_out: host, n_rows x n_sets row-major. */
+int32_t srx_score_genes(srx_mat* m, const uint64_t* set_ptr, const uint64_t* set_genes, uint64_t n_sets, const uint64_t* pool,
+                        uint64_t n_pool, const srx_score_genes_opts* opts, double* score_out, uint64_t* ctrl_ptr_out,
+                        uint64_t* ctrl_genes_out, uint64_t capacity, srx_score_genes_info* info);
+
 /* ---- a fitted PCA applied to other cells: Pca::transform (src/shared/processing/pca/mod.rs:156-185)
  * A model is k feature rows (V: k x n_pc, mu, sd, flags center / scale) held on the device.  For a query
  * matrix Xq (cells x its own genes) and a feature map feat (k entries: the query column of model row i,

@@ -54,6 +54,15 @@ fn last_error(ctx: *const SrxCtx) -> String {
     unsafe { CStr::from_ptr(srx_last_error(ctx)) }.to_string_lossy().into_owned()
 }
 
+/// Gene lists as the C ABI takes them: (ptr with lists.len() + 1 entries, the genes of every list one after another; never empty).
+fn pack_lists(lists: &[Vec<u64>]) -> (Vec<u64>, Vec<u64>) {
+    let mut ptr = vec![0u64; lists.len() + 1];
+    for (t, l) in lists.iter().enumerate() { ptr[t + 1] = ptr[t] + l.len() as u64; }
+    let mut flat: Vec<u64> = lists.iter().flatten().copied().collect();
+    if flat.is_empty() { flat.push(0); }
+    (ptr, flat)
+}
+
 /// Device-resident X of one IMAnnData.  Upload once; every call of the path then works on the handle.
 pub struct DeviceX<'c> { ctx: &'c Ctx, mat: *mut SrxMat, n_obs: usize, n_vars: usize }
 
@@ -369,6 +378,70 @@ impl<'c> DeviceX<'c> {
         })?;
         out.truncate(self.n_obs * genes.len());
         Ok(out)
+    }
+
+    /// Per cell and gene list the sum and the number of the stored entries whose gene is in the list (n_obs x lists.len()
+    /// row-major each; a stored 0 counts): `srx_gene_list_sums`, one walk over the column indices per 64 lists.
+    pub fn gene_list_sums(&self, lists: &[Vec<u64>]) -> Result<(Vec<f64>, Vec<u32>, SrxGeneListInfo)> {
+        let (ptr, flat) = pack_lists(lists);
+        let mut sum = vec![0f64; (self.n_obs * lists.len()).max(1)];
+        let mut cnt = vec![0u32; (self.n_obs * lists.len()).max(1)];
+        let mut info: SrxGeneListInfo = unsafe { std::mem::zeroed() };
+        self.ctx.check(unsafe {
+            srx_gene_list_sums(self.mat, ptr.as_ptr(), flat.as_ptr(), lists.len() as u64, sum.as_mut_ptr(), cnt.as_mut_ptr(), &mut info)
+        })?;
+        sum.truncate(self.n_obs * lists.len());
+        cnt.truncate(self.n_obs * lists.len());
+        Ok((sum, cnt, info))
+    }
+
+    /// scanpy's `score_genes` on the values as stored, every set of `sets` in one call: per cell the mean over the set minus
+    /// the mean over its control genes (srx.h states the definition; the controls of a bin are chosen by a hash of `seed` and
+    /// the gene, not by numpy's generator).  Returns (scores n_obs x sets.len() row-major, the control list of every set, the
+    /// info block).  `ctrl_size` 0 = 50, `n_bins` 0 = 25, `gene_pool` None = every gene.
+    pub fn score_genes(&self, sets: &[Vec<u64>], ctrl_size: u32, n_bins: u32, gene_pool: Option<&[u64]>, seed: u64,
+                       ctrl_as_ref: bool) -> Result<(Vec<f64>, Vec<Vec<u64>>, SrxScoreGenesInfo)> {
+        let (ptr, flat) = pack_lists(sets);
+        let opts = SrxScoreGenesOpts { ctrl_size, n_bins, seed, ctrl_as_ref: if ctrl_as_ref { 1 } else { 0 }, reserved: 0 };
+        let n_pool = gene_pool.map_or(self.n_vars, |p| p.len());
+        // the bound of srx.h: per set ctrl_size * min(|set|, P / n_items + 1)
+        let size = if ctrl_size == 0 { 50 } else { ctrl_size as usize };
+        let bins = if n_bins == 0 { 25 } else { n_bins as usize };
+        let n_items = ((n_pool as f64 / (bins.max(2) - 1) as f64).round_ties_even() as usize).max(1);
+        let capacity: usize = sets.iter().map(|s| size * s.len().min(n_pool / n_items + 1)).sum::<usize>().max(1);
+        let mut score = vec![0f64; (self.n_obs * sets.len()).max(1)];
+        let mut ctrl_ptr = vec![0u64; sets.len() + 1];
+        let mut ctrl = vec![0u64; capacity];
+        let mut info: SrxScoreGenesInfo = unsafe { std::mem::zeroed() };
+        let (pool, pool_len) = gene_pool.map_or((std::ptr::null(), 0u64), |p| (p.as_ptr(), p.len() as u64));
+        self.ctx.check(unsafe {
+            srx_score_genes(self.mat, ptr.as_ptr(), flat.as_ptr(), sets.len() as u64, pool, pool_len, &opts, score.as_mut_ptr(),
+                            ctrl_ptr.as_mut_ptr(), ctrl.as_mut_ptr(), capacity as u64, &mut info)
+        })?;
+        score.truncate(self.n_obs * sets.len());
+        let lists = (0..sets.len()).map(|s| ctrl[ctrl_ptr[s] as usize..ctrl_ptr[s + 1] as usize].to_vec()).collect();
+        Ok((score, lists, info))
+    }
+
+    /// scanpy's `score_genes_cell_cycle`: both sets in one call with `ctrl_size = min(|s|, |g2m|)`, then the phase on the
+    /// host — "S" by default, "G2M" where G2M > S, "G1" where both are < 0.  Returns (S_score, G2M_score, phase).
+    pub fn score_genes_cell_cycle(&self, s_genes: &[u64], g2m_genes: &[u64]) -> Result<(Vec<f64>, Vec<f64>, Vec<&'static str>)> {
+        let ctrl_size = s_genes.len().min(g2m_genes.len()) as u32;
+        let (score, _, _) = self.score_genes(&[s_genes.to_vec(), g2m_genes.to_vec()], ctrl_size, 25, None, 0, true)?;
+        let s: Vec<f64> = score.iter().step_by(2).copied().collect();
+        let g: Vec<f64> = score.iter().skip(1).step_by(2).copied().collect();
+        let phase = s.iter().zip(&g).map(|(&s, &g)| if s < 0.0 && g < 0.0 { "G1" } else if g > s { "G2M" } else { "S" }).collect();
+        Ok((s, g, phase))
+    }
+
+    /// The `qc_vars` part of scanpy's `calculate_qc_metrics`: per subset (total_counts, pct_counts = 100 * total / the cell's
+    /// sum with 0 / 0 kept as NaN, n_genes_by_counts = the cell's STORED entries in the subset, an explicit 0 included), each
+    /// n_obs x subsets.len() row-major.
+    pub fn qc_gene_fractions(&self, subsets: &[Vec<u64>]) -> Result<(Vec<f64>, Vec<f64>, Vec<u32>)> {
+        let (sum, cnt, _) = self.gene_list_sums(subsets)?;
+        let total = self.compute_sum(Direction::Row)?;
+        let pct = sum.iter().enumerate().map(|(e, &s)| 100.0 * s / total[e / subsets.len()]).collect();
+        Ok((sum, pct, cnt))
     }
 
     /// dim_red/mod.rs:24-94 without the dense N x k matrix: returns (scores N x n_pc row-major, explained variance

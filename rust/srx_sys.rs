@@ -7,6 +7,7 @@ use std::os::raw::{c_char, c_void};
 
 pub const SRX_ABI_VERSION: i32 = 6;
 pub const SRX_UNIQUE_ID_BYTES: usize = 128;
+pub const SRX_GENE_LISTS_MAX: i32 = 4096;
 pub const SRX_KNN_MAX_DIMS: i32 = 128;
 pub const SRX_LOUVAIN_MAX_LEVELS: i32 = 32;
 pub const SRX_GROUPS_MAX: i32 = 4096;
@@ -279,6 +280,48 @@ pub struct SrxRegressInfo {      // `srx_regress_info`
     pub chunk_cells: u64,
     pub chunk_bytes: u64,
     pub pca: SrxPcaInfo,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxGeneListInfo {      // `srx_gene_list_info`
+    pub n_rows: u64,
+    pub n_cols: u64,
+    pub n_lists: u64,
+    pub longest_list: u64,
+    pub sum_scale_log2: i32,
+    pub n_walks: u32,
+    pub max_abs: f64,
+    pub ms_scan: f64,
+    pub ms_walk: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxScoreGenesOpts {      // `srx_score_genes_opts`
+    pub ctrl_size: u32,
+    pub n_bins: u32,
+    pub seed: u64,
+    pub ctrl_as_ref: i32,
+    pub reserved: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxScoreGenesInfo {      // `srx_score_genes_info`
+    pub n_rows: u64,
+    pub n_cols: u64,
+    pub n_sets: u64,
+    pub n_pool: u64,
+    pub n_ctrl_total: u64,
+    pub n_items: u64,
+    pub longest_list: u64,
+    pub sum_scale_log2: i32,
+    pub n_walks: u32,
+    pub max_abs: f64,
+    pub ms_mean: f64,
+    pub ms_ctrl: f64,
+    pub ms_walk: f64,
 }
 
 #[repr(C)]
@@ -820,6 +863,16 @@ extern "C" {
     pub fn srx_pca_regress(m: *mut SrxMat, genes: *const u64, k: u64, cov: *const f64, p: u64,
                            opts: *const SrxRegressOpts, scores: *mut f64, components: *mut f64, evr: *mut f64,
                            mean: *mut f64, sd: *mut f64, info: *mut SrxRegressInfo) -> i32;
+    pub fn srx_gene_list_sums(m: *mut SrxMat, list_ptr: *const u64, list_genes: *const u64, n_lists: u64,
+                              sum_out: *mut f64, cnt_out: *mut u32, info: *mut SrxGeneListInfo) -> i32;
+    pub fn srx_score_genes_controls(gene_mean: *const f64, n_genes: u64, pool: *const u64, n_pool: u64,
+                                    set_ptr: *const u64, set_genes: *const u64, n_sets: u64,
+                                    opts: *const SrxScoreGenesOpts, ctrl_ptr_out: *mut u64,
+                                    ctrl_genes_out: *mut u64, capacity: u64, cut_out: *mut u32) -> i32;
+    pub fn srx_score_genes(m: *mut SrxMat, set_ptr: *const u64, set_genes: *const u64, n_sets: u64,
+                           pool: *const u64, n_pool: u64, opts: *const SrxScoreGenesOpts, score_out: *mut f64,
+                           ctrl_ptr_out: *mut u64, ctrl_genes_out: *mut u64, capacity: u64,
+                           info: *mut SrxScoreGenesInfo) -> i32;
     pub fn srx_pca_model_from_result(m: *mut SrxMat, out: *mut *mut SrxPcaModel) -> i32;
     pub fn srx_pca_model_create(ctx: *mut SrxCtx, k: u64, n_pc: u64, components: *const f64, mean: *const f64,
                                 std: *const f64, sel: *const u64, center: i32, scale: i32,

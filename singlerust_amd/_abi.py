@@ -8,6 +8,7 @@ P = C.c_void_p
 
 ABI_VERSION = 6
 UNIQUE_ID_BYTES = 128
+GENE_LISTS_MAX = 4096
 KNN_MAX_DIMS = 128
 LOUVAIN_MAX_LEVELS = 32
 GROUPS_MAX = 4096
@@ -194,6 +195,24 @@ class RegressInfo(C.Structure):      # srx_regress_info
                 ("ms_fit", C.c_double), ("ms_scale", C.c_double), ("ms_gram", C.c_double), ("ms_solve", C.c_double),
                 ("ms_scores", C.c_double), ("n_chunks", C.c_uint64), ("chunk_cells", C.c_uint64),
                 ("chunk_bytes", C.c_uint64), ("pca", PcaInfo)]
+
+
+class GeneListInfo(C.Structure):      # srx_gene_list_info
+    _fields_ = [("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("n_lists", C.c_uint64), ("longest_list", C.c_uint64),
+                ("sum_scale_log2", C.c_int32), ("n_walks", C.c_uint32), ("max_abs", C.c_double),
+                ("ms_scan", C.c_double), ("ms_walk", C.c_double)]
+
+
+class ScoreGenesOpts(C.Structure):      # srx_score_genes_opts
+    _fields_ = [("ctrl_size", C.c_uint32), ("n_bins", C.c_uint32), ("seed", C.c_uint64), ("ctrl_as_ref", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class ScoreGenesInfo(C.Structure):      # srx_score_genes_info
+    _fields_ = [("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("n_sets", C.c_uint64), ("n_pool", C.c_uint64),
+                ("n_ctrl_total", C.c_uint64), ("n_items", C.c_uint64), ("longest_list", C.c_uint64),
+                ("sum_scale_log2", C.c_int32), ("n_walks", C.c_uint32), ("max_abs", C.c_double),
+                ("ms_mean", C.c_double), ("ms_ctrl", C.c_double), ("ms_walk", C.c_double)]
 
 
 class KnnOpts(C.Structure):      # srx_knn_opts
@@ -451,6 +470,11 @@ SIGNATURES = {
                                      C.POINTER(RegressInfo)]),
     "srx_pca_regress": (C.c_int32, [P, P, C.c_uint64, P, C.c_uint64, C.POINTER(RegressOpts), P, P, P, P, P,
                                     C.POINTER(RegressInfo)]),
+    "srx_gene_list_sums": (C.c_int32, [P, P, P, C.c_uint64, P, P, C.POINTER(GeneListInfo)]),
+    "srx_score_genes_controls": (C.c_int32, [P, C.c_uint64, P, C.c_uint64, P, P, C.c_uint64,
+                                             C.POINTER(ScoreGenesOpts), P, P, C.c_uint64, P]),
+    "srx_score_genes": (C.c_int32, [P, P, P, C.c_uint64, P, C.c_uint64, C.POINTER(ScoreGenesOpts), P, P, P,
+                                    C.c_uint64, C.POINTER(ScoreGenesInfo)]),
     "srx_pca_model_from_result": (C.c_int32, [P, C.POINTER(P)]),
     "srx_pca_model_create": (C.c_int32, [P, C.c_uint64, C.c_uint64, P, P, P, P, C.c_int32, C.c_int32, C.POINTER(P)]),
     "srx_pca_model_info": (C.c_int32, [P, P, P, P]),

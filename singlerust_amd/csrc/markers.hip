@@ -32,9 +32,6 @@ constexpr int kMkThreads = 1024;          // one workgroup per CU: its accumulat
 constexpr int kMkSortRows = 1024;         // rows per workgroup of the counting sort
 constexpr uint64_t kMkMinRows = 64;       // rows_per_block = max(kMkMinRows, ceil(N / max(1, kMkBlocks / n_tiles)))
 constexpr uint64_t kMkBlocks = 1024;      // ... four workgroups per CU of the 256 when one group holds every row
-// d_small: the few words the host reads back
-enum { MK_MAXABS = 0, MK_FLAGS = 1, MK_MAXLABEL = 2, MK_WORDS = 4 };
-constexpr unsigned long long kMkNonFinite = 1, kMkBadLabel = 2;
 
 inline uint64_t mk_rows_per_block(uint64_t n_rows, int n_tiles) {
     const uint64_t want = std::max<uint64_t>(1, kMkBlocks / (uint64_t)std::max(n_tiles, 1));
@@ -520,11 +517,7 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
     unsigned long long* d_small;
     SRX_TRY(scratch(ctx, "mk_small", MK_WORDS * 8, (void**)&d_small));
     SRX_HIP(ctx, hipMemsetAsync(d_small, 0, MK_WORDS * 8, st));
-    if (m->nnz) {
-        const unsigned grid = (unsigned)std::min<uint64_t>((m->nnz + 255) / 256, (uint64_t)ctx->n_cus * 16);
-        if (is_f32(m)) hipLaunchKernelGGL(k_mk_value_scan<float>, dim3(grid), dim3(256), 0, st, (const float*)m->d_values, m->nnz, d_small);
-        else hipLaunchKernelGGL(k_mk_value_scan<double>, dim3(grid), dim3(256), 0, st, (const double*)m->d_values, m->nnz, d_small);
-    }
+    markers_value_scan(m, d_small);
     const uint64_t n_blk = at_least_one((N + kMkSortRows - 1) / kMkSortRows);
     const uint64_t n_tab = (uint64_t)n_groups * n_blk;
     int64_t *d_table, *d_first;
@@ -551,9 +544,7 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
     // the scales (srx.h): e from max_abs, no lower than -30; L = ceil(log2(max(N, 1)))
     double max_abs;
     memcpy(&max_abs, &small[MK_MAXABS], 8);
-    int e = 0;
-    (void)std::frexp(max_abs, &e);                // max_abs = f 2^e, 0.5 <= f < 1: the smallest e with max_abs < 2^e (0 for 0)
-    e = std::max(e, -30);
+    const int e = fx_exponent(max_abs);
     int L = 0;
     while ((1ull << L) < at_least_one(N)) ++L;
     srx_markers_info& info = mk->info;
@@ -682,6 +673,13 @@ int32_t markers_moments(srx_mat* m, const uint32_t* d_labels, uint32_t n_groups,
 int32_t markers_clipped_walk(srx_mat* m, const MkPlan& plan, const double* d_clip, unsigned long long* d_S, unsigned long long* d_Q) {
     if (!plan.n_blocks) return SRX_OK;
     return mk_walk(m, plan.d_perm, plan.d_blocks, plan.n_blocks, plan.fx_sum, plan.fx_sq, d_clip, d_S, d_Q, nullptr);
+}
+
+void markers_value_scan(srx_mat* m, unsigned long long* d_small) {
+    if (!m->nnz) return;
+    const unsigned grid = (unsigned)std::min<uint64_t>((m->nnz + 255) / 256, (uint64_t)m->ctx->n_cus * 16);
+    if (is_f32(m)) hipLaunchKernelGGL(k_mk_value_scan<float>, dim3(grid), dim3(256), 0, m->ctx->stream, (const float*)m->d_values, m->nnz, d_small);
+    else hipLaunchKernelGGL(k_mk_value_scan<double>, dim3(grid), dim3(256), 0, m->ctx->stream, (const double*)m->d_values, m->nnz, d_small);
 }
 
 int32_t markers_check(srx_mat* m, const char* what) {

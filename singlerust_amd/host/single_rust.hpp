@@ -17,6 +17,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <optional>
@@ -482,7 +483,106 @@ inline Array2 regress_out(const IMAnnData& a, const std::vector<std::uint64_t>& 
     return out;
 }
 
-namespace dim_red {                                              // src/memory/processing/dim_red/mod.rs
+// ---- sums over gene lists per cell, gene-set scores (srx.h states the definitions; scanpy's sc.tl.score_genes,
+// score_genes_cell_cycle and the qc_vars of calculate_qc_metrics; the control genes of a bin are chosen by a hash, not by numpy's
+// generator, and nothing is compared with scanpy)
+struct GeneListSums {
+    Array2 sum;                                // n_obs x n_lists
+    std::vector<std::uint32_t> cnt;            // the same shape, row-major: stored entries, an explicit 0 included
+    srx_gene_list_info info{};
+};
+inline std::pair<std::vector<std::uint64_t>, std::vector<std::uint64_t>> pack_lists(const std::vector<std::vector<std::uint64_t>>& lists) {
+    std::vector<std::uint64_t> ptr(lists.size() + 1, 0), flat;
+    for (std::size_t t = 0; t < lists.size(); ++t) {
+        ptr[t + 1] = ptr[t] + lists[t].size();
+        flat.insert(flat.end(), lists[t].begin(), lists[t].end());
+    }
+    if (flat.empty()) flat.push_back(0);
+    return {ptr, flat};
+}
+inline GeneListSums gene_list_sums(const IMAnnData& a, const std::vector<std::vector<std::uint64_t>>& lists) {
+    const auto packed = pack_lists(lists);
+    GeneListSums r;
+    r.sum.nrows = a.n_obs();
+    r.sum.ncols = lists.size();
+    r.sum.data.assign(std::max<std::size_t>(a.n_obs() * lists.size(), 1), 0.0);
+    r.cnt.assign(std::max<std::size_t>(a.n_obs() * lists.size(), 1), 0u);
+    a.ctx().check(srx_gene_list_sums(a.x(), packed.first.data(), packed.second.data(), lists.size(), r.sum.data.data(), r.cnt.data(), &r.info));
+    r.sum.data.resize(a.n_obs() * lists.size());
+    r.cnt.resize(a.n_obs() * lists.size());
+    return r;
+}
+struct GeneScores {
+    Array2 score;                                          // n_obs x n_sets
+    std::vector<std::vector<std::uint64_t>> controls;      // per set, ascending
+    srx_score_genes_info info{};
+};
+inline GeneScores score_genes(const IMAnnData& a, const std::vector<std::vector<std::uint64_t>>& sets, std::uint32_t ctrl_size = 50,
+                              std::uint32_t n_bins = 25, const std::vector<std::uint64_t>* gene_pool = nullptr, std::uint64_t seed = 0,
+                              bool ctrl_as_ref = true) {
+    const auto packed = pack_lists(sets);
+    srx_score_genes_opts opts{};
+    opts.ctrl_size = ctrl_size;
+    opts.n_bins = n_bins;
+    opts.seed = seed;
+    opts.ctrl_as_ref = ctrl_as_ref ? 1 : 0;
+    // the bound of srx.h: per set ctrl_size * min(|set|, P / n_items + 1)
+    const std::size_t P = gene_pool ? gene_pool->size() : a.n_vars(), size = ctrl_size ? ctrl_size : 50, bins = n_bins ? n_bins : 25;
+    const std::size_t n_items = std::max<std::size_t>((std::size_t)std::nearbyint((double)P / (double)(std::max<std::size_t>(bins, 2) - 1)), 1);
+    std::size_t capacity = 0;
+    for (const auto& s : sets) capacity += size * std::min<std::size_t>(s.size(), P / n_items + 1);
+    GeneScores r;
+    r.score.nrows = a.n_obs();
+    r.score.ncols = sets.size();
+    r.score.data.assign(std::max<std::size_t>(a.n_obs() * sets.size(), 1), 0.0);
+    std::vector<std::uint64_t> ctrl_ptr(sets.size() + 1, 0), ctrl(std::max<std::size_t>(capacity, 1), 0);
+    a.ctx().check(srx_score_genes(a.x(), packed.first.data(), packed.second.data(), sets.size(), gene_pool ? gene_pool->data() : nullptr,
+                                  gene_pool ? gene_pool->size() : 0, &opts, r.score.data.data(), ctrl_ptr.data(), ctrl.data(), ctrl.size(), &r.info));
+    r.score.data.resize(a.n_obs() * sets.size());
+    for (std::size_t s = 0; s < sets.size(); ++s) r.controls.emplace_back(ctrl.begin() + ctrl_ptr[s], ctrl.begin() + ctrl_ptr[s + 1]);
+    return r;
+}
+struct CellCycle {
+    std::vector<double> s_score, g2m_score;
+    std::vector<std::string> phase;            // "S" by default, "G2M" where G2M > S, "G1" where both are < 0 (scanpy's rule and order)
+};
+inline CellCycle score_genes_cell_cycle(IMAnnData& a, const std::vector<std::uint64_t>& s_genes, const std::vector<std::uint64_t>& g2m_genes) {
+    const GeneScores g = score_genes(a, {s_genes, g2m_genes}, (std::uint32_t)std::min(s_genes.size(), g2m_genes.size()));
+    CellCycle r;
+    for (std::size_t i = 0; i < a.n_obs(); ++i) {
+        const double s = g.score.data[2 * i], m = g.score.data[2 * i + 1];
+        r.s_score.push_back(s);
+        r.g2m_score.push_back(m);
+        r.phase.push_back(s < 0.0 && m < 0.0 ? "G1" : m > s ? "G2M" : "S");
+    }
+    a.obs_columns()["S_score"] = r.s_score;
+    a.obs_columns()["G2M_score"] = r.g2m_score;
+    return r;
+}
+// per subset k: total_counts_<k>, pct_counts_<k> = 100 * total / the cell's sum (0 / 0 stays NaN), n_genes_by_counts_<k> = the
+// cell's STORED entries in the subset (an explicit 0 included: the one difference from scanpy's count of values > 0)
+inline std::map<std::string, std::vector<double>> qc_gene_fractions(IMAnnData& a, const std::map<std::string, std::vector<std::uint64_t>>& subsets) {
+    std::vector<std::vector<std::uint64_t>> lists;
+    for (const auto& kv : subsets) lists.push_back(kv.second);
+    const GeneListSums g = gene_list_sums(a, lists);
+    const std::vector<double> total = statistics::compute_sum(a, Direction::Row);
+    std::map<std::string, std::vector<double>> out;
+    std::size_t t = 0;
+    for (const auto& kv : subsets) {
+        std::vector<double>&tc = out["total_counts_" + kv.first], &pc = out["pct_counts_" + kv.first], &ng = out["n_genes_by_counts_" + kv.first];
+        for (std::size_t i = 0; i < a.n_obs(); ++i) {
+            const double s = g.sum.data[i * lists.size() + t];
+            tc.push_back(s);
+            pc.push_back(100.0 * s / total[i]);
+            ng.push_back((double)g.cnt[i * lists.size() + t]);
+        }
+        ++t;
+    }
+    for (const auto& kv : out) a.obs_columns()[kv.first] = kv.second;
+    return out;
+}
+
+namespace dim_red {                                            // src/memory/processing/dim_red/mod.rs
 inline std::vector<std::uint64_t> select_features(const IMAnnData& a, const FeatureSelection& fs) {   // :123-156
     switch (fs.kind) {
         case FeatureSelection::HighlyVariableK: {

@@ -17,6 +17,7 @@ from .louvain import graph_labels, louvain, louvain_csr
 from .markers import group_moments, rank_genes_groups
 from .neighbors import KnnIndex, connectivities_from_knn, knn_index, knn_index_points, knn_points, neighbors, neighbors_approx
 from .regress import pca_regress_scale, regress_fit, regress_gram, regress_out, scale
+from .score import cell_cycle_phase, gene_list_sums, qc_gene_fractions, score_genes, score_genes_cell_cycle, score_genes_controls
 from .tsne import Tsne, tsne, tsne_affinities, tsne_affinities_graph, tsne_embedding, tsne_forces, tsne_run
 from .umap import fit_ab, graph_embedding, umap, umap_csr
 
