@@ -345,6 +345,24 @@ inline bool is_f32(const srx_mat* m) { return m->store == SRX_STORE_F32; }
 // direction as the STORED matrix sees it: a CSC matrix is the CSR of the transpose
 inline int32_t eff_dir(const srx_mat* m, int32_t d) { return (m->csc && (d == SRX_ROW || d == SRX_COLUMN)) ? 1 - d : d; }
 int32_t transpose_device(srx_mat* m, srx_mat** out);      // csc.hip: CSR of the transpose of the stored matrix
+// run(x) on the CSR of the cells' rows: x is `m` itself, or for a CSC handle its device transpose, freed afterwards; with
+// hand_back_pca the PCA result the run left on the transpose becomes m's
+template <typename F>
+int32_t on_cells_csr(srx_mat* m, bool hand_back_pca, F&& run) {
+    if (!m->csc) return run(m);
+    srx_mat* t = nullptr;
+    SRX_TRY(transpose_device(m, &t));
+    const int32_t rc = run(t);
+    if (hand_back_pca) std::swap(m->pca, t->pca);
+    srx_matrix_free(t);
+    return rc;
+}
 inline size_t val_bytes(const srx_mat* m) { return is_f32(m) ? 4 : 8; }
+// matrix.hip: the one reduction over the stored values, queued on the context's stream.  d_small (VS_WORDS words, zeroed by the
+// caller) receives the bit pattern of the largest finite |x| in word VS_MAXABS and, in word VS_FLAGS, kValNonFinite where a
+// value is NaN or Inf and kValNegative where a finite value is below zero.  The flag bits from kValOwnFlag up are the caller's.
+enum { VS_MAXABS = 0, VS_FLAGS = 1, VS_WORDS = 2 };
+constexpr unsigned long long kValNonFinite = 1, kValNegative = 2, kValOwnFlag = 4;
+void value_scan(srx_mat* m, unsigned long long* d_small);
 
 }  // namespace srx

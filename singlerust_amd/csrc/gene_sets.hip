@@ -171,14 +171,14 @@ int32_t gs_check_lists(srx_ctx* ctx, const char* who, const char* what, const ui
 int32_t gs_value_scan(srx_mat* m, const char* who, double* max_abs) {
     srx_ctx* ctx = m->ctx;
     unsigned long long* d_small;
-    SRX_TRY(scratch(ctx, "gs_small", MK_WORDS * 8, (void**)&d_small));
-    SRX_HIP(ctx, hipMemsetAsync(d_small, 0, MK_WORDS * 8, ctx->stream));
-    markers_value_scan(m, d_small);
+    SRX_TRY(scratch(ctx, "gs_small", VS_WORDS * 8, (void**)&d_small));
+    SRX_HIP(ctx, hipMemsetAsync(d_small, 0, VS_WORDS * 8, ctx->stream));
+    value_scan(m, d_small);
     SRX_HIP(ctx, hipGetLastError());
-    unsigned long long small[MK_WORDS];
+    unsigned long long small[VS_WORDS];
     SRX_TRY(d2h(ctx, small, d_small, sizeof small));
-    if (small[MK_FLAGS] & kMkNonFinite) return fail(ctx, SRX_E_NAN, "%s: a stored value is NaN or Inf", who);
-    memcpy(max_abs, &small[MK_MAXABS], 8);
+    if (small[VS_FLAGS] & kValNonFinite) return fail(ctx, SRX_E_NAN, "%s: a stored value is NaN or Inf", who);
+    memcpy(max_abs, &small[VS_MAXABS], 8);
     return SRX_OK;
 }
 

@@ -8,6 +8,7 @@
 // Every floating-point sum has one fixed order (a fit's moments: lanes counted from the first weighted point, one butterfly);
 // the sums over the stored entries are 64-bit fixed point with integer atomics.  No floating-point atomics.
 #include "markers_internal.hpp"
+#include "pca_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -19,8 +20,6 @@
 
 namespace srx {
 
-int32_t rank_keys_device(srx_ctx* ctx, const double* d_key, uint64_t G, uint32_t* d_rank);      // select.hip
-
 constexpr int kSvLoessThreads = 256;                       // four fit points per workgroup, a wave each
 constexpr int kSvLoessWaves = kSvLoessThreads / kWave;
 constexpr double kSvRankTol = 0x1p-33;                     // the degree rule of srx.h
@@ -29,17 +28,6 @@ __device__ __forceinline__ double sv_mul(double a, double b) { return a * b; }
 __device__ __forceinline__ double sv_sub(double a, double b) { return a - b; }
 __device__ __forceinline__ double sv_add(double a, double b) { return a + b; }
 __device__ __forceinline__ double sv_div(double a, double b) { return a / b; }
-
-// ---- a negative stored value (NaN and Inf are the moments pass's to refuse) -------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void k_sv_negative(const T* __restrict__ vals, uint64_t nnz, uint32_t* __restrict__ bad) {
-    bool b = false;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += (uint64_t)gridDim.x * blockDim.x) {
-        const double v = (double)vals[e];
-        b |= v < 0.0 && v >= -kDblMax;
-    }
-    if (__ballot(b) != 0ull && lane_id() == 0) atomicOr(bad, 1u);
-}
 
 // ---- step 1: mean, var of every (batch, gene); the trend's abscissa and ordinate; the sort key of the abscissa ------------------
 // key = -x for a gene that varies (rank_keys_device orders by key descending, index ascending: x ascending), -inf otherwise,
@@ -267,10 +255,6 @@ __global__ __launch_bounds__(256) void k_sv_combine(const uint32_t* __restrict__
     key[j] = k;
     final_rank[j] = 0u;
 }
-__global__ __launch_bounds__(256) void k_sv_pick(const uint32_t* __restrict__ rank, uint64_t G, uint32_t take, uint64_t* __restrict__ sel) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < G && rank[j] < take) sel[rank[j]] = j;
-}
 // f64(fixed-point integer) x 2^-scale, a whole table
 __global__ __launch_bounds__(256) void k_sv_unfix(const long long* __restrict__ in, uint64_t n, double inv, double* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -339,16 +323,14 @@ static int32_t sv_begin(srx_mat* m, const char* who) {
 static int32_t sv_refuse_negative(srx_mat* m, const char* who) {
     srx_ctx* ctx = m->ctx;
     if (!m->nnz) return SRX_OK;
-    uint32_t* d_bad;
-    SRX_TRY(scratch(ctx, "seurat_bad", 256, (void**)&d_bad));
-    SRX_HIP(ctx, hipMemsetAsync(d_bad, 0, 256, ctx->stream));
-    const unsigned grid = (unsigned)std::min<uint64_t>((m->nnz + 255) / 256, (uint64_t)(8 * ctx->n_cus));
-    if (is_f32(m)) hipLaunchKernelGGL(k_sv_negative<float>, dim3(grid), dim3(256), 0, ctx->stream, (const float*)m->d_values, m->nnz, d_bad);
-    else hipLaunchKernelGGL(k_sv_negative<double>, dim3(grid), dim3(256), 0, ctx->stream, (const double*)m->d_values, m->nnz, d_bad);
+    unsigned long long* d_small;
+    SRX_TRY(scratch(ctx, "seurat_bad", 256, (void**)&d_small));
+    SRX_HIP(ctx, hipMemsetAsync(d_small, 0, 256, ctx->stream));
+    value_scan(m, d_small);
     SRX_HIP(ctx, hipGetLastError());
-    uint32_t bad = 0;
-    SRX_TRY(d2h(ctx, &bad, d_bad, 4));
-    if (bad) return fail(ctx, SRX_E_ARG, "%s: the matrix holds a negative value (raw counts are expected)", who);
+    unsigned long long flags = 0;
+    SRX_TRY(d2h(ctx, &flags, d_small + VS_FLAGS, sizeof flags));
+    if (flags & kValNegative) return fail(ctx, SRX_E_ARG, "%s: the matrix holds a negative value (raw counts are expected)", who);
     return SRX_OK;
 }
 
@@ -535,8 +517,7 @@ int32_t srx_select_hvg_seurat_v3(srx_mat* m, uint64_t n_top, const uint32_t* bat
                            f64(o_means), f64(o_vars), f64(o_vn), f64(o_med), u32(o_nb), f64(o_fkey), u32(o_frank));
         SRX_HIP(ctx, hipGetLastError());
         SRX_TRY(rank_keys_device(ctx, f64(o_fkey), G, u32(o_frank)));
-        hipLaunchKernelGGL(k_sv_pick, dim3(grid256(G)), dim3(256), 0, st, (const uint32_t*)u32(o_frank), G, (uint32_t)take, d_sel);
-        SRX_HIP(ctx, hipGetLastError());
+        SRX_TRY(pick_top(ctx, u32(o_frank), G, take, d_sel));
     }
     SRX_TRY(t_rank.stop(&info.ms_rank));
 

@@ -45,29 +45,6 @@ __device__ __forceinline__ double mk_sub(double a, double b) { return a - b; }
 __device__ __forceinline__ double mk_add(double a, double b) { return a + b; }
 __device__ __forceinline__ double mk_div(double a, double b) { return a / b; }
 
-// ---- one reduction over the stored values: the largest |x| (the bit patterns of non-negative doubles order as integers)
-// and whether any value is NaN or Inf
-template <typename T>
-__global__ __launch_bounds__(256) void k_mk_value_scan(const T* __restrict__ vals, uint64_t nnz, unsigned long long* __restrict__ small) {
-    unsigned long long mx = 0, bad = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += stride) {
-        const double a = fabs((double)vals[i]);
-        if (a < INFINITY) {
-            const unsigned long long b = (unsigned long long)__double_as_longlong(a);
-            mx = b > mx ? b : mx;
-        } else {
-            bad = 1;
-        }
-    }
-    mx = wave_max(mx);
-    bad = wave_max(bad);
-    if (lane_id() == 0) {
-        if (mx) atomicMax(&small[MK_MAXABS], mx);
-        if (bad) atomicOr(&small[MK_FLAGS], kMkNonFinite);
-    }
-}
-
 __global__ __launch_bounds__(256) void k_mk_label_max(const uint32_t* __restrict__ labels, uint64_t n, unsigned long long* __restrict__ small) {
     unsigned long long mx = 0;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -517,7 +494,7 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
     unsigned long long* d_small;
     SRX_TRY(scratch(ctx, "mk_small", MK_WORDS * 8, (void**)&d_small));
     SRX_HIP(ctx, hipMemsetAsync(d_small, 0, MK_WORDS * 8, st));
-    markers_value_scan(m, d_small);
+    value_scan(m, d_small);
     const uint64_t n_blk = at_least_one((N + kMkSortRows - 1) / kMkSortRows);
     const uint64_t n_tab = (uint64_t)n_groups * n_blk;
     int64_t *d_table, *d_first;
@@ -535,7 +512,7 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
     unsigned long long small[MK_WORDS];
     SRX_TRY(d2h(ctx, small, d_small, sizeof small));
     if (small[MK_FLAGS] & kMkBadLabel) return fail(ctx, SRX_E_ARG, "markers: a label is not below n_groups = %u", n_groups);
-    if (small[MK_FLAGS] & kMkNonFinite) return fail(ctx, SRX_E_NAN, "markers: a stored value is NaN or Inf");
+    if (small[MK_FLAGS] & kValNonFinite) return fail(ctx, SRX_E_NAN, "markers: a stored value is NaN or Inf");
     std::vector<uint64_t> sizes(n_groups);
     SRX_TRY(d2h(ctx, sizes.data(), mk->d_sizes, (size_t)n_groups * 8));
     if (N) hipLaunchKernelGGL(k_mk_place, dim3((unsigned)n_blk), dim3(kMkSortRows), 0, st, d_labels, (const uint16_t*)d_rank, (const int64_t*)d_first, N, n_blk, d_perm);
@@ -673,13 +650,6 @@ int32_t markers_moments(srx_mat* m, const uint32_t* d_labels, uint32_t n_groups,
 int32_t markers_clipped_walk(srx_mat* m, const MkPlan& plan, const double* d_clip, unsigned long long* d_S, unsigned long long* d_Q) {
     if (!plan.n_blocks) return SRX_OK;
     return mk_walk(m, plan.d_perm, plan.d_blocks, plan.n_blocks, plan.fx_sum, plan.fx_sq, d_clip, d_S, d_Q, nullptr);
-}
-
-void markers_value_scan(srx_mat* m, unsigned long long* d_small) {
-    if (!m->nnz) return;
-    const unsigned grid = (unsigned)std::min<uint64_t>((m->nnz + 255) / 256, (uint64_t)m->ctx->n_cus * 16);
-    if (is_f32(m)) hipLaunchKernelGGL(k_mk_value_scan<float>, dim3(grid), dim3(256), 0, m->ctx->stream, (const float*)m->d_values, m->nnz, d_small);
-    else hipLaunchKernelGGL(k_mk_value_scan<double>, dim3(grid), dim3(256), 0, m->ctx->stream, (const double*)m->d_values, m->nnz, d_small);
 }
 
 int32_t markers_check(srx_mat* m, const char* what) {

@@ -47,9 +47,9 @@ struct MkPlan {
     std::vector<uint64_t> sizes;           // cells per group
 };
 
-// d_small: the few words the host reads back from the passes over the values and the labels
-enum { MK_MAXABS = 0, MK_FLAGS = 1, MK_MAXLABEL = 2, MK_WORDS = 4 };
-constexpr unsigned long long kMkNonFinite = 1, kMkBadLabel = 2;
+// d_small: the few words the host reads back from the passes over the values (common.hpp: value_scan's two) and the labels
+enum { MK_MAXABS = VS_MAXABS, MK_FLAGS = VS_FLAGS, MK_MAXLABEL = 2, MK_WORDS = 4 };
+constexpr unsigned long long kMkBadLabel = kValOwnFlag;
 // the e of srx.h's fixed-point scales: max_abs = f 2^e, 0.5 <= f < 1, so e is the smallest integer with max_abs < 2^e (0 for 0),
 // taken no lower than -30
 inline int fx_exponent(double max_abs) {
@@ -59,9 +59,6 @@ inline int fx_exponent(double max_abs) {
 }
 
 void mk_free(srx_markers* mk);
-// the one reduction over the stored values, queued on the context's stream: d_small (MK_WORDS words, zeroed by the caller) receives
-// the bit pattern of the largest |x| in word MK_MAXABS and kMkNonFinite in word MK_FLAGS where a value is NaN or Inf
-void markers_value_scan(srx_mat* m, unsigned long long* d_small);
 // the refusals that need no pass over the matrix (NULL, CSC, several ranks, 2^32 - 1 rows or more); sets the device
 int32_t markers_check(srx_mat* m, const char* what);
 // n_groups checked, the labels uploaded into the scratch buffer "mk_labels"

@@ -44,17 +44,9 @@ namespace srx {
 static int32_t pca_device(srx_mat* m, const uint64_t* sel, uint64_t k64, const srx_pca_opts* opts, uint64_t hvg_n = 0) {
     srx_ctx* ctx = m->ctx;
     SRX_HIP(ctx, hipSetDevice(ctx->device));
-    if (m->csc) {
-        // compaction, Gram and SpMM walk cells: solve on the CSR of X (device transpose, csc.hip) and hand the
-        // result to the CSC handle (convert_to_array_f64_csc_selected, src/shared/mod.rs:261-290, builds the same
-        // dense matrix from either storage)
-        srx_mat* t = nullptr;
-        SRX_TRY(transpose_device(m, &t));
-        const int32_t rc = pca_device(t, sel, k64, opts, hvg_n);
-        std::swap(m->pca, t->pca);
-        srx_matrix_free(t);
-        return rc;
-    }
+    // compaction, Gram and SpMM walk cells: solve on the CSR of X (device transpose, csc.hip) and hand the result to the CSC
+    // handle (convert_to_array_f64_csc_selected, src/shared/mod.rs:261-290, builds the same dense matrix from either storage)
+    if (m->csc) return on_cells_csr(m, true, [&](srx_mat* t) { return pca_device(t, sel, k64, opts, hvg_n); });
     srx_pca_state& st = m->pca;
     st.valid = false;
     const uint64_t G = m->n_cols;

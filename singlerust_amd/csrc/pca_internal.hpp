@@ -179,6 +179,10 @@ int32_t select_hvg_device(srx_mat* m, uint64_t n, int center, int scale, SelDev&
 // an explicit list (`genes`: k distinct features below n_cols in the caller's order; null: every feature, k = n_cols),
 // validated; `vectors` false: the selection alone, the moments of `m` are not read
 int32_t select_list(srx_mat* m, const uint64_t* genes, uint64_t k, int center, int scale, SelDev& out, bool vectors = true);
+// the ranking alone, for any key array: d_rank[j] += the number of genes before j under (key desc, index asc); the caller has
+// zeroed d_rank.  pick_top: d_sel[r] = the gene of rank r, for r < take
+int32_t rank_keys_device(srx_ctx* ctx, const double* d_key, uint64_t G, uint32_t* d_rank);
+int32_t pick_top(srx_ctx* ctx, const uint32_t* d_rank, uint64_t G, uint64_t take, uint64_t* d_sel);
 // genes.hip.  E: int32_t column indices or GramPk<VT> records
 template <typename E>
 int32_t launch_tile_ptr(srx_ctx* ctx, const int64_t* indptr, const E* idx, uint64_t n_rows, int n_tiles, int tile_genes,

@@ -10,6 +10,7 @@
 // fixed: cell chunks in ascending order, a CSC gene's cells by lane and butterfly.  The ranking is select.hip's
 // (rank_keys_device).
 #include "pearson_internal.hpp"
+#include "pca_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -19,8 +20,6 @@
 #pragma clang fp contract(off)
 
 namespace srx {
-
-int32_t rank_keys_device(srx_ctx* ctx, const double* d_key, uint64_t G, uint32_t* d_rank);      // select.hip
 
 // The sizes the tests walk round (tests/test_pearson_gpu.py names the same numbers).
 constexpr int kPrDenseThreads = 256;
@@ -42,17 +41,6 @@ __device__ __forceinline__ void pr_zero(double mu, double inv_theta, double clip
     a = fmin(a, clip);
     f = -a;
     f2 = a * a;
-}
-
-// ---- the first pass over the values: anything negative, NaN or infinite ------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void k_pr_check(const T* __restrict__ vals, uint64_t nnz, uint32_t* __restrict__ bad) {
-    bool b = false;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += (uint64_t)gridDim.x * blockDim.x) {
-        const double v = (double)vals[e];
-        b |= !(v >= 0.0 && v <= kDblMax);
-    }
-    if (__ballot(b) != 0ull && lane_id() == 0) atomicOr(bad, 1u);
 }
 
 // ---- totals: T = sum r_i in one fixed order, the expressed genes, the empty cells (one workgroup) ----------------------------
@@ -264,10 +252,6 @@ __global__ __launch_bounds__(256) void k_pr_finish(const double* __restrict__ pa
     key[j] = expressed ? v : -INFINITY;
     rank[j] = 0u;
 }
-__global__ __launch_bounds__(256) void k_pr_pick(const uint32_t* __restrict__ rank, uint64_t G, uint32_t take, uint64_t* __restrict__ sel) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < G && rank[j] < take) sel[rank[j]] = j;
-}
 
 // ---- block kernel: the residuals of listed genes, a chunk of cells --------------------------------------------------------------
 // One thread per output: a binary search of the column in the stored row (CSR: cell i's row for the gene; CSC: the gene's row
@@ -319,16 +303,10 @@ int32_t pr_prepare(srx_mat* m, const srx_pearson_opts* opts, const char* who, Pr
     SRX_TRY(scratch(ctx, "pearson_small", 256, (void**)&d_small));
     double* d_total = reinterpret_cast<double*>(d_small);
     uint64_t* d_counts = reinterpret_cast<uint64_t*>(d_small + 8);
-    uint32_t* d_bad = reinterpret_cast<uint32_t*>(d_small + 24);
+    unsigned long long* d_scan = reinterpret_cast<unsigned long long*>(d_small + 24);      // the value scan's VS_WORDS words
     SRX_HIP(ctx, hipMemsetAsync(d_small, 0, 256, ctx->stream));
-    if (m->nnz) {
-        const unsigned grid = (unsigned)std::min<uint64_t>((m->nnz + 255) / 256, (uint64_t)(8 * ctx->n_cus));
-        if (is_f32(m))
-            hipLaunchKernelGGL(k_pr_check<float>, dim3(grid), dim3(256), 0, ctx->stream, (const float*)m->d_values, m->nnz, d_bad);
-        else
-            hipLaunchKernelGGL(k_pr_check<double>, dim3(grid), dim3(256), 0, ctx->stream, (const double*)m->d_values, m->nnz, d_bad);
-        SRX_HIP(ctx, hipGetLastError());
-    }
+    value_scan(m, d_scan);
+    SRX_HIP(ctx, hipGetLastError());
     // the sums over the stored rows go to a buffer of this call (the handle's d_row_sum is the normalise pass's), those over the
     // stored columns are the handle's cached raw moments
     double *d_rows, *d_gene_a;
@@ -342,14 +320,14 @@ int32_t pr_prepare(srx_mat* m, const srx_pearson_opts* opts, const char* who, Pr
     hipLaunchKernelGGL(k_pr_totals, dim3(1), dim3(1024), 0, ctx->stream, p.d_cell, p.n, p.d_gene, p.G, d_total, d_counts);
     hipLaunchKernelGGL(k_pr_gene_factor, dim3(grid256(p.G)), dim3(256), 0, ctx->stream, p.d_gene, p.G, (const double*)d_total, d_gene_a);
     SRX_HIP(ctx, hipGetLastError());
-    unsigned char host[32];
+    unsigned char host[24 + 8 * VS_WORDS];
     SRX_TRY(d2h(ctx, host, d_small, sizeof host));
-    uint32_t bad;
+    unsigned long long scan[VS_WORDS];
     uint64_t counts[2];
     memcpy(&p.a.total, host, 8);
     memcpy(counts, host + 8, 16);
-    memcpy(&bad, host + 24, 4);
-    if (bad) return fail(ctx, SRX_E_ARG, "%s: the matrix holds a negative, NaN or infinite value", who);
+    memcpy(scan, host + 24, sizeof scan);
+    if (scan[VS_FLAGS] & (kValNegative | kValNonFinite)) return fail(ctx, SRX_E_ARG, "%s: the matrix holds a negative, NaN or infinite value", who);
     p.n_expressed = counts[0];
     p.n_empty = counts[1];
     return SRX_OK;
@@ -484,8 +462,7 @@ static int32_t pr_variance(srx_mat* m, const srx_pearson_opts* opts, const char*
     if (take) {
         SRX_TRY(scratch(ctx, "pearson_sel", take * sizeof(uint64_t), (void**)&d_sel));
         SRX_TRY(rank_keys_device(ctx, d_key, G, d_rank));
-        hipLaunchKernelGGL(k_pr_pick, dim3(grid256(G)), dim3(256), 0, ctx->stream, (const uint32_t*)d_rank, G, (uint32_t)take, d_sel);
-        SRX_HIP(ctx, hipGetLastError());
+        SRX_TRY(pick_top(ctx, d_rank, G, take, d_sel));
     }
     SRX_TRY(timer_r.stop(&info.ms_rank));
     SRX_TRY(d2h(ctx, var.data(), d_var, G * sizeof(double)));

@@ -1,17 +1,16 @@
 // regress.hip — covariates regressed out of listed genes, the residuals scaled and clipped, and the PCA of the result (srx.h:
 // srx_regress_fit, srx_regress_residuals, srx_regress_gram, srx_pca_regress): scanpy's regress_out -> scale -> pca on the device.
 //
-// Z (n x k) is dense and is never held as a whole.  As in pearson_pca.hip it is made a CHUNK of cells at a time from ONE element
-// function (rg_value): every pair gets the value of a zero entry (k_rg_fill), then the stored entries of the chunk's rows
-// overwrite theirs (k_rg_stored).  A mode says what the chunk holds: the stored x (for W = Ct^T X), the residual r (for
-// sum r^2), or z = clip(r / s) (for the products and the block).  Four passes over the chunks:
+// Z (n x k) is dense and is never held as a whole: this is a caller of the dense route (dense_pca.hip, dense_pca_internal.hpp),
+// which makes Z a CHUNK of cells at a time from ONE element function (rg_value).  A mode says what the chunk holds: the stored x
+// (for W = Ct^T X), the residual r (for sum r^2), or z = clip(r / s) (for the products and the block).  Four passes over the chunks:
 //   W       a weighted column sum (k_rg_wsum): per column and slab the rows in ascending order, up to 16 weight vectors at once;
 //   sum r^2 the same kernel with the column's own value as weight;
-//   Gram    Z^T Z and the column sums   } the passes of dense_pca_internal.hpp: the kernels of pearson_pca.hip on the f64
-//   scores  Z P - 1 c^T                 } matrix cores, handed this file's chunk producer.
+//   Gram    Z^T Z and the column sums   } the dense route's products on the f64 matrix cores, handed this file's element
+//   scores  Z P - 1 c^T                 } function.
 // The p x p factor (p <= 16) and the k solves run on the host in f64.
 // No floating-point atomics: a partial sum has one owner, slabs and chunks are added in ascending order.  The only atomics count
-// clipped pairs (integers: exact in any order).
+// clipped pairs in the chunk kernels (integers: exact in any order).
 #include "dense_pca_internal.hpp"
 
 // the chunk kernels evaluate the definition and the sums of this file are stated in one order (host code included)
@@ -21,7 +20,7 @@ namespace srx {
 
 enum { kRgRaw = 0, kRgResid = 1, kRgZ = 2 };    // what a chunk holds
 constexpr int kRgMaxCov = 16;
-constexpr int kRgMaxSlabs = 64;                 // slabs of a chunk (k_pp_colsum's bound)
+constexpr int kRgMaxSlabs = 64;                 // slabs of a chunk (k_dense_colsum's bound)
 constexpr int kRgCovSlabs = 1024;               // slabs of the covariate matrix, which is summed as one chunk of n rows
 constexpr double kRgMinPivot = 1e-10;
 
@@ -34,6 +33,7 @@ struct RgArgs {
     double max_value;      // 0: no clip
     uint32_t k;
     int p, mode;
+    __device__ __forceinline__ double at(double x, uint64_t row, uint32_t slot, bool* clipped) const;   // the dense route's element: rg_value
 };
 
 // The element (i, j) of the chunk for the stored value x, in the order srx.h states.  *clipped: |r / s| > max_value.
@@ -56,54 +56,12 @@ __device__ __forceinline__ double rg_value(double x, uint64_t i, uint32_t j, con
     return fmin(fmax(z, -a.max_value), a.max_value);
 }
 
-// ---- a chunk: rows [row0, row0 + rows) x ldz columns, columns >= k zero --------------------------------------------------------------
-// cnt (may be null): [0] += the clipped pairs of this kernel (every pair as a zero entry)
-__global__ __launch_bounds__(256) void k_rg_fill(uint32_t ldz, uint64_t row0, uint64_t rows, RgArgs a, double* __restrict__ Z,
-                                                 unsigned long long* __restrict__ cnt) {
-    const uint64_t o = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (o >= rows * ldz) return;
-    const uint64_t i = o / ldz;
-    const uint32_t c = (uint32_t)(o - i * ldz);
-    bool cl = false;
-    Z[o] = c < a.k ? rg_value(0.0, row0 + i, c, a, &cl) : 0.0;
-    if (cnt) {
-        const unsigned long long b = __ballot(cl);
-        if (cl && lane_id() == __ffsll(b) - 1) atomicAdd(cnt, (unsigned long long)__popcll(b));
-    }
-}
-// the stored entries of the chunk's rows: a wave per row, the listed ones overwrite the value of a zero entry.
-// cnt (may be null): [1] += the clipped ones among them, [2] += those whose overwritten zero-entry value was counted by k_rg_fill
-template <typename T>
-__global__ __launch_bounds__(256) void k_rg_stored(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
-                                                   const T* __restrict__ vals, const int32_t* __restrict__ slot_of, uint32_t ldz,
-                                                   uint64_t row0, uint64_t rows, RgArgs a, double* __restrict__ Z,
-                                                   unsigned long long* __restrict__ cnt) {
-    const uint64_t i = global_wave_id();
-    if (i >= rows) return;
-    const uint64_t r = row0 + i;
-    const int64_t hi = indptr[r + 1];
-    unsigned int n_new = 0, n_old = 0;
-    for (int64_t e = indptr[r] + lane_id(); e < hi; e += kWave) {
-        const int32_t s = slot_of[idx[e]];
-        if (s < 0) continue;
-        bool cl, cl0 = false;
-        Z[i * ldz + (uint32_t)s] = rg_value((double)vals[e], r, (uint32_t)s, a, &cl);
-        if (cnt) (void)rg_value(0.0, r, (uint32_t)s, a, &cl0);
-        n_new += cl ? 1u : 0u;
-        n_old += cl0 ? 1u : 0u;
-    }
-    if (cnt) {
-        n_new = wave_sum(n_new);
-        n_old = wave_sum(n_old);
-        if (lane_id() == 0) {
-            if (n_new) atomicAdd(cnt + 1, (unsigned long long)n_new);
-            if (n_old) atomicAdd(cnt + 2, (unsigned long long)n_old);
-        }
-    }
+__device__ __forceinline__ double RgArgs::at(double x, uint64_t row, uint32_t slot, bool* clipped) const {
+    return rg_value(x, row, slot, *this, clipped);
 }
 
 // ---- weighted column sums of a chunk ---------------------------------------------------------------------------------------------------
-// A thread per column and slab walks the slab's rows in ascending order (k_pp_colsum's scheme) and adds w[r][q] * Z[r][c] for the
+// A thread per column and slab walks the slab's rows in ascending order (k_dense_colsum's scheme) and adds w[r][q] * Z[r][c] for the
 // nw <= 16 weight vectors q at once (w: row r of the chunk at w + r * ldw); sq: one sum, the weight is Z[r][c] itself.
 // part[(slab * nw + q) * k + c].
 __global__ __launch_bounds__(256) void k_rg_wsum(const double* __restrict__ Z, uint32_t ldz, uint32_t rows, uint32_t slab_rows, uint32_t k,
@@ -141,14 +99,6 @@ __global__ __launch_bounds__(256) void k_rg_wsum_reduce(const double* __restrict
     out[o] += s;
 }
 
-// a stored value that is not finite sets *bad (every writer stores the same word)
-template <typename T>
-__global__ __launch_bounds__(256) void k_rg_check(const T* __restrict__ vals, uint64_t nnz, uint32_t* __restrict__ bad) {
-    bool any = false;
-    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (uint64_t)gridDim.x * 256) any |= !is_finite((double)vals[e]);
-    if (any) *bad = 1u;
-}
-
 // ---- host side --------------------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -178,8 +128,7 @@ struct RgPrep {                      // what is made before the rows are walked:
 
 struct RgRun {
     DenseChunks g;
-    std::vector<int> slot_of_pos;    // caller's position -> slot (ascending gene)
-    int32_t* d_slot_of = nullptr;
+    DenseSlots sl;                   // slots: ascending gene, as the solver and the chunk's columns are ordered
     double *d_ct = nullptr, *d_beta = nullptr, *d_xbar = nullptr, *d_s = nullptr;
     uint8_t* d_cst = nullptr;
     unsigned long long* d_cnt = nullptr;
@@ -284,16 +233,14 @@ int32_t rg_prepare(srx_mat* m, const uint64_t* genes, uint64_t k, const double* 
     }
     // the stored values
     if (m->nnz) {
-        uint32_t* d_bad;
-        SRX_TRY(scratch(ctx, "rg_small", 256, (void**)&d_bad));
-        SRX_HIP(ctx, hipMemsetAsync(d_bad, 0, 256, ctx->stream));
-        const unsigned grid = (unsigned)std::min<uint64_t>((m->nnz + 255) / 256, (uint64_t)(8 * ctx->n_cus));
-        if (is_f32(m)) hipLaunchKernelGGL(k_rg_check<float>, dim3(grid), dim3(256), 0, ctx->stream, (const float*)m->d_values, m->nnz, d_bad);
-        else hipLaunchKernelGGL(k_rg_check<double>, dim3(grid), dim3(256), 0, ctx->stream, (const double*)m->d_values, m->nnz, d_bad);
+        unsigned long long* d_small;
+        SRX_TRY(scratch(ctx, "rg_small", 256, (void**)&d_small));
+        SRX_HIP(ctx, hipMemsetAsync(d_small, 0, 256, ctx->stream));
+        value_scan(m, d_small);
         SRX_HIP(ctx, hipGetLastError());
-        uint32_t bad = 0;
-        SRX_TRY(d2h(ctx, &bad, d_bad, sizeof bad));
-        if (bad) return fail(ctx, SRX_E_ARG, "%s: the matrix holds a NaN or infinite value", who);
+        unsigned long long flags = 0;
+        SRX_TRY(d2h(ctx, &flags, d_small + VS_FLAGS, sizeof flags));
+        if (flags & kValNonFinite) return fail(ctx, SRX_E_ARG, "%s: the matrix holds a NaN or infinite value", who);
     }
     // xbar from the library's own column sums; the genes whose n values are all equal from its counts and extremes
     std::vector<double> sum(at_least_one(G)), mn(at_least_one(G)), mx(at_least_one(G));
@@ -315,30 +262,11 @@ int32_t rg_prepare(srx_mat* m, const uint64_t* genes, uint64_t k, const double* 
     return SRX_OK;
 }
 
-// rows [row0, row0 + rows) of the chunk in `mode`
-int32_t rg_make_chunk(srx_mat* m, const RgRun& R, const RgPrep& P, int mode, bool count, uint64_t row0, uint64_t rows, double* Z) {
-    srx_ctx* ctx = m->ctx;
-    RgArgs a;
-    a.ct = R.d_ct;
-    a.beta = R.d_beta;
-    a.xbar = R.d_xbar;
-    a.s = R.d_s;
-    a.cst = R.d_cst;
-    a.max_value = P.max_value;
-    a.k = (uint32_t)P.k;
-    a.p = P.p;
-    a.mode = mode;
-    unsigned long long* cnt = count ? R.d_cnt : nullptr;
-    hipLaunchKernelGGL(k_rg_fill, dim3((unsigned)((rows * R.g.ldz + 255) / 256)), dim3(256), 0, ctx->stream, R.g.ldz, row0, rows, a, Z, cnt);
-    const unsigned grid = (unsigned)((rows + 3) / 4);
-    if (is_f32(m))
-        hipLaunchKernelGGL(k_rg_stored<float>, dim3(grid), dim3(256), 0, ctx->stream, m->d_indptr, m->d_indices, (const float*)m->d_values,
-                           (const int32_t*)R.d_slot_of, R.g.ldz, row0, rows, a, Z, cnt);
-    else
-        hipLaunchKernelGGL(k_rg_stored<double>, dim3(grid), dim3(256), 0, ctx->stream, m->d_indptr, m->d_indices, (const double*)m->d_values,
-                           (const int32_t*)R.d_slot_of, R.g.ldz, row0, rows, a, Z, cnt);
-    SRX_HIP(ctx, hipGetLastError());
-    return SRX_OK;
+// what makes rows [row0, row0 + rows) of the chunk in `mode`; COUNT: the clipped pairs are counted into R.d_cnt
+template <bool COUNT>
+DenseChunkFn rg_maker(srx_mat* m, const RgRun& R, const RgPrep& P, int mode) {
+    const RgArgs a{R.d_ct, R.d_beta, R.d_xbar, R.d_s, R.d_cst, P.max_value, (uint32_t)P.k, P.p, mode};
+    return [m, &R, a](uint64_t row0, uint64_t rows, double* Z) { return dense_make_chunk<RgArgs, COUNT>(m, R.sl, R.g, a, row0, rows, Z, R.d_cnt); };
 }
 
 int32_t rg_clipped(srx_ctx* ctx, const RgRun& R, uint64_t* n_clipped) {
@@ -362,32 +290,24 @@ int32_t rg_run(srx_mat* m, const uint64_t* genes, const srx_regress_opts* opts, 
     inf.n_constant_genes = P.n_const;
     inf.min_pivot = P.min_pivot;
 
-    // slots: ascending gene, as the solver and the chunk's columns are ordered
     RgRun R;
-    std::vector<uint32_t> order(k);
-    std::iota(order.begin(), order.end(), 0u);
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return genes[a] < genes[b]; });
-    R.slot_of_pos.resize(k);
-    std::vector<int32_t> slot_of(at_least_one(G), -1);
+    SRX_TRY(dense_slots_setup(ctx, genes, (uint64_t)k, G, R.sl));
+    const std::vector<int>& slot_of_pos = R.sl.slot_of_pos;
     std::vector<double> xbar(k);
     std::vector<uint8_t> cst(k);
-    for (int s = 0; s < k; ++s) {
-        R.slot_of_pos[order[s]] = s;
-        slot_of[genes[order[s]]] = (int32_t)s;
-        xbar[s] = P.xbar[order[s]];
-        cst[s] = P.cst[order[s]];
+    for (int a = 0; a < k; ++a) {
+        xbar[slot_of_pos[a]] = P.xbar[a];
+        cst[slot_of_pos[a]] = P.cst[a];
     }
     R.beta.assign((size_t)std::max(p, 1) * k, 0.0);
     R.s.assign(k, 1.0);
     const size_t beta_bytes = (size_t)std::max(p, 1) * k * sizeof(double);
-    SRX_TRY(scratch(ctx, "rg_slot_of", at_least_one(G) * sizeof(int32_t), (void**)&R.d_slot_of));
     SRX_TRY(scratch(ctx, "rg_ct", at_least_one((uint64_t)n * p) * sizeof(double), (void**)&R.d_ct));
     SRX_TRY(scratch(ctx, "rg_beta", beta_bytes, (void**)&R.d_beta));
     SRX_TRY(scratch(ctx, "rg_xbar", (size_t)k * sizeof(double), (void**)&R.d_xbar));
     SRX_TRY(scratch(ctx, "rg_s", (size_t)k * sizeof(double), (void**)&R.d_s));
     SRX_TRY(scratch(ctx, "rg_cst", (size_t)k, (void**)&R.d_cst));
     SRX_TRY(scratch(ctx, "rg_cnt", 256, (void**)&R.d_cnt));
-    SRX_TRY(h2d(ctx, R.d_slot_of, slot_of.data(), at_least_one(G) * sizeof(int32_t)));
     if (p > 0) SRX_TRY(h2d(ctx, R.d_ct, P.ct.data(), (size_t)n * p * sizeof(double)));      // (a CSC call: the transpose ran in between)
     SRX_TRY(h2d(ctx, R.d_beta, R.beta.data(), beta_bytes));
     SRX_TRY(h2d(ctx, R.d_xbar, xbar.data(), (size_t)k * sizeof(double)));
@@ -411,9 +331,10 @@ int32_t rg_run(srx_mat* m, const uint64_t* genes, const srx_regress_opts* opts, 
         StreamTimer timer(ctx, ctx->stream);
         SRX_TRY(timer.start());
         SRX_HIP(ctx, hipMemsetAsync(d_sums, 0, (size_t)p * k * sizeof(double), ctx->stream));
+        const DenseChunkFn make_x = rg_maker<false>(m, R, P, kRgRaw);
         for (uint64_t row0 = 0; row0 < n; row0 += R.g.chunk) {
             const uint64_t rows = std::min(R.g.chunk, n - row0);
-            SRX_TRY(rg_make_chunk(m, R, P, kRgRaw, false, row0, rows, R.g.d_Z));
+            SRX_TRY(make_x(row0, rows, R.g.d_Z));
             SRX_TRY(rg_wsum(ctx, R.g.d_Z, R.g.ldz, rows, (uint32_t)k, R.d_ct + row0 * (size_t)p, (uint32_t)p, p, 0, slabs_max, d_part, d_sums));
         }
         double ms = 0.0;
@@ -425,7 +346,7 @@ int32_t rg_run(srx_mat* m, const uint64_t* genes, const srx_regress_opts* opts, 
             for (int q = 0; q < p; ++q) {
                 if (out.cbar) out.cbar[q] = P.cbar[q];
                 for (int t = 0; out.A && t < p; ++t) out.A[(size_t)q * p + t] = P.A[(size_t)q * p + t];
-                for (int a = 0; out.W && a < k; ++a) out.W[(size_t)q * k + a] = W[(size_t)q * k + R.slot_of_pos[a]];
+                for (int a = 0; out.W && a < k; ++a) out.W[(size_t)q * k + a] = W[(size_t)q * k + slot_of_pos[a]];
             }
             if (info) *info = inf;
             return SRX_OK;
@@ -453,9 +374,10 @@ int32_t rg_run(srx_mat* m, const uint64_t* genes, const srx_regress_opts* opts, 
         StreamTimer timer(ctx, ctx->stream);
         SRX_TRY(timer.start());
         SRX_HIP(ctx, hipMemsetAsync(d_sums, 0, (size_t)k * sizeof(double), ctx->stream));
+        const DenseChunkFn make_r = rg_maker<false>(m, R, P, kRgResid);
         for (uint64_t row0 = 0; row0 < n; row0 += R.g.chunk) {
             const uint64_t rows = std::min(R.g.chunk, n - row0);
-            SRX_TRY(rg_make_chunk(m, R, P, kRgResid, false, row0, rows, R.g.d_Z));
+            SRX_TRY(make_r(row0, rows, R.g.d_Z));
             SRX_TRY(rg_wsum(ctx, R.g.d_Z, R.g.ldz, rows, (uint32_t)k, nullptr, 0, 1, 1, slabs_max, d_part, d_sums));
         }
         SRX_TRY(timer.stop(&inf.ms_scale));
@@ -468,12 +390,11 @@ int32_t rg_run(srx_mat* m, const uint64_t* genes, const srx_regress_opts* opts, 
         SRX_TRY(h2d(ctx, R.d_s, R.s.data(), (size_t)k * sizeof(double)));
     }
 
-    const DenseChunkFn make_z = [&](uint64_t row0, uint64_t rows, double* Z) { return rg_make_chunk(m, R, P, kRgZ, false, row0, rows, Z); };
-    const DenseChunkFn make_z_counted = [&](uint64_t row0, uint64_t rows, double* Z) { return rg_make_chunk(m, R, P, kRgZ, true, row0, rows, Z); };
+    const DenseChunkFn make_z = rg_maker<false>(m, R, P, kRgZ), make_z_counted = rg_maker<true>(m, R, P, kRgZ);
 
     if (stage == kStageFit) {
         for (int a = 0; a < k; ++a) {
-            const int s = R.slot_of_pos[a];
+            const int s = slot_of_pos[a];
             if (out.xbar) out.xbar[a] = P.xbar[a];
             if (out.sd) out.sd[a] = R.s[s];
             for (int q = 0; out.beta && q < p; ++q) out.beta[(size_t)q * k + a] = R.beta[(size_t)q * k + s];
@@ -485,29 +406,16 @@ int32_t rg_run(srx_mat* m, const uint64_t* genes, const srx_regress_opts* opts, 
             SRX_TRY(make_z_counted(row0, rows, R.g.d_Z));
             SRX_TRY(d2h(ctx, h.data(), R.g.d_Z, (size_t)rows * R.g.ldz * sizeof(double)));
             for (uint64_t i = 0; i < rows; ++i)
-                for (int a = 0; a < k; ++a) out.block[(row0 + i) * (uint64_t)k + a] = h[i * R.g.ldz + R.slot_of_pos[a]];
+                for (int a = 0; a < k; ++a) out.block[(row0 + i) * (uint64_t)k + a] = h[i * R.g.ldz + slot_of_pos[a]];
         }
         SRX_TRY(rg_clipped(ctx, R, &inf.n_clipped));
     } else if (stage == kStageGram) {
         double *Gp, *colsum;
-        SRX_TRY(scratch(ctx, "pp_gpacked", gram_packed_count(k) * sizeof(double), (void**)&Gp));
-        SRX_TRY(scratch(ctx, "pp_colsum", (size_t)k * sizeof(double), (void**)&colsum));
-        SRX_TRY(dense_gram_pass(ctx, R.g, make_z_counted, Gp, colsum, &inf.ms_gram));
-        std::vector<double> hp(gram_packed_count(k)), hc(k);
-        SRX_TRY(d2h(ctx, hp.data(), Gp, hp.size() * sizeof(double)));
-        SRX_TRY(d2h(ctx, hc.data(), colsum, hc.size() * sizeof(double)));
+        SRX_TRY(dense_gram_pass(ctx, R.g, make_z_counted, &Gp, &colsum, &inf.ms_gram));
+        SRX_TRY(dense_gram_fetch(ctx, R.sl, Gp, colsum, out.gram, out.colsum));
         SRX_TRY(rg_clipped(ctx, R, &inf.n_clipped));
-        for (int a = 0; a < k; ++a) {             // the caller's order; (a, b) and (b, a) copy the same entry
-            const int sa = R.slot_of_pos[a];
-            if (out.colsum) out.colsum[a] = hc[sa];
-            for (int b = 0; out.gram && b < k; ++b) {
-                const int sb = R.slot_of_pos[b];
-                out.gram[(size_t)a * k + b] = hp[tri_index(std::min(sa, sb), std::max(sa, sb), k)];
-            }
-        }
     } else {
-        srx_pca_state& st = m->pca;
-        st.valid = false;
+        m->pca.valid = false;
         srx_pca_opts po{};
         if (opts) po = opts->pca;
         else po.n_components = -1;
@@ -516,48 +424,15 @@ int32_t rg_run(srx_mat* m, const uint64_t* genes, const srx_regress_opts* opts, 
         Resolved o;
         int l_act = 0;
         SRX_TRY(resolve_opts(ctx, &po, k, m->n_rows, false, o, l_act));
-        st.center = 1;
-        st.scale = 0;
-        // the selection as the solver reads it: vectors in slot order, the list in the caller's order
-        SelDev sd;
-        double *d_f, *Gp, *colsum;
-        SRX_TRY(scratch(ctx, "pp_sel_f", (3 * (size_t)k + 8) * sizeof(double), (void**)&d_f));
-        SRX_TRY(scratch(ctx, "pp_sel_rank", (size_t)k * sizeof(int32_t), (void**)&sd.d_sel_rank));
-        SRX_TRY(scratch(ctx, "pp_status", 256, (void**)&sd.d_status));
-        SRX_TRY(scratch(ctx, "pp_gpacked", gram_packed_count(k) * sizeof(double), (void**)&Gp));
-        SRX_TRY(scratch(ctx, "pp_colsum", (size_t)k * sizeof(double), (void**)&colsum));
-        sd.k = k;
-        sd.d_mu = d_f;
-        sd.d_sd = d_f + k;
-        sd.d_dinv = d_f + 2 * (size_t)k;
-        sd.d_trace = d_f + 3 * (size_t)k;
-        std::vector<int32_t> list(k);
-        for (int s = 0; s < k; ++s) list[s] = (int32_t)genes[s];
-        SRX_TRY(h2d(ctx, sd.d_sel_rank, list.data(), (size_t)k * sizeof(int32_t)));
-        SRX_HIP(ctx, hipMemsetAsync(sd.d_status, 0, 256, ctx->stream));
-
-        SRX_TRY(dense_gram_pass(ctx, R.g, make_z_counted, Gp, colsum, &inf.ms_gram));
-        SRX_TRY(dense_finish(ctx, Gp, colsum, k, n, 1, sd));
-        // Z is scaled where it is made: the solver's factor stays 1, the result block's std is s
-        SRX_HIP(ctx, hipMemcpyAsync(sd.d_sd, R.d_s, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        // clips are counted in the Gram pass only; Z is scaled where it is made, so the result block's std is s
+        DenseSolved sv;
+        const int32_t rc = dense_pca_solve(m, o, l_act, genes, R.g, make_z_counted, make_z, kResidualRegress, 1, R.d_s, sv);
+        if (!sv.solved) return rc;
         SRX_TRY(rg_clipped(ctx, R, &inf.n_clipped));
-
-        double ms_scores = 0.0;
-        DenseSource src;
-        src.k = k;
-        src.n_rows = n;
-        src.route = kResidualRegress;
-        src.write_scores = [&](const double* Pn, const double* cvec, int col0, int n_r, double* scores, int ld) -> int32_t {
-            return dense_score_pass(ctx, R.g, make_z, Pn, cvec, n_r, scores + col0, ld, &ms_scores);
-        };
-        StreamTimer timer(ctx, ctx->stream);
-        SRX_TRY(timer.start());
-        const int32_t rc = solve_and_stash(ctx, false, nullptr, 0, nullptr, Gp, o, sd, l_act, n, 0, st, &src);
-        double ms_all = 0.0;
-        SRX_TRY(timer.stop(&ms_all));
-        inf.ms_scores = ms_scores;
-        inf.ms_solve = ms_all - ms_scores;
-        inf.pca = st.info;
+        inf.ms_gram = sv.ms_gram;
+        inf.ms_solve = sv.ms_solve;
+        inf.ms_scores = sv.ms_scores;
+        inf.pca = sv.pca;
         if (info) *info = inf;
         return rc;
     }
@@ -570,13 +445,8 @@ int32_t rg_entry(srx_mat* m, const uint64_t* genes, uint64_t k, const double* co
     SRX_TRY(rg_check(m, genes, k, cov, p, opts, who, stage == kStagePca));
     RgPrep P;
     SRX_TRY(rg_prepare(m, genes, k, cov, p, opts, who, P));
-    if (!m->csc) return rg_run(m, genes, opts, P, stage, out, info);
-    srx_mat* t = nullptr;                      // the chunks are made from the cells' rows: on the CSR of X (device transpose, csc.hip)
-    SRX_TRY(transpose_device(m, &t));
-    const int32_t rc = rg_run(t, genes, opts, P, stage, out, info);
-    if (stage == kStagePca) std::swap(m->pca, t->pca);
-    srx_matrix_free(t);
-    return rc;
+    // the chunks are made from the cells' rows
+    return on_cells_csr(m, stage == kStagePca, [&](srx_mat* x) { return rg_run(x, genes, opts, P, stage, out, info); });
 }
 
 }  // namespace

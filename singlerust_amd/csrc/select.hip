@@ -409,6 +409,17 @@ int32_t rank_keys_device(srx_ctx* ctx, const double* d_key, uint64_t G, uint32_t
     return SRX_OK;
 }
 
+// The first `take` of a full ranking: d_sel[rank] = gene for every gene with rank < take
+__global__ __launch_bounds__(256) void k_pick_top(const uint32_t* __restrict__ rank, uint64_t G, uint32_t take, uint64_t* __restrict__ sel) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < G && rank[j] < take) sel[rank[j]] = j;
+}
+int32_t pick_top(srx_ctx* ctx, const uint32_t* d_rank, uint64_t G, uint64_t take, uint64_t* d_sel) {
+    hipLaunchKernelGGL(k_pick_top, dim3(grid256(G)), dim3(256), 0, ctx->stream, d_rank, G, (uint32_t)take, d_sel);
+    SRX_HIP(ctx, hipGetLastError());
+    return SRX_OK;
+}
+
 // An explicit list: its rank table is the position of every gene in the list, so that the selection comes out in the
 // caller's order (1.2 MB to upload at 300 000 columns).  Needs the global moments of `m` where `vectors`.
 static int32_t list_rank_table(srx_ctx* ctx, const uint64_t* genes, uint64_t k, uint64_t G, std::vector<uint32_t>& rank) {

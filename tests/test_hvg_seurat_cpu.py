@@ -16,7 +16,7 @@ import hvg_seurat_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("srx_select_hvg_seurat_v3", "srx_loess_direct", "srx_clipped_group_moments")
-KERNELS = ("k_sv_negative", "k_sv_stats", "k_sv_scatter", "k_sv_loess", "k_sv_clip", "k_sv_nv", "k_sv_combine", "k_sv_pick", "k_sv_unfix",
+KERNELS = ("k_sv_stats", "k_sv_scatter", "k_sv_loess", "k_sv_clip", "k_sv_nv", "k_sv_combine", "k_sv_unfix",
            "k_sv_negate")
 
 
@@ -153,7 +153,8 @@ def test_seurat_symbols_are_exported_and_bound():
     # the walk is markers.hip's, shared and not copied; the ranking is select.hip's; no floating-point atomic
     assert "k_mk_walk" not in src and "markers_clipped_walk(" in src and "markers_moments(" in src
     assert len(re.findall(r"__global__[^;{]*\bk_mk_walk\b", markers)) == 1 and '#include "markers_internal.hpp"' in markers
-    assert "rank_keys_device(ctx" in src
+    assert "rank_keys_device(ctx" in src and "pick_top(ctx" in src and "value_scan(m, " in src
+    assert "rank_keys_device(srx_ctx*" not in src                             # declared once, in pca_internal.hpp
     assert not re.search(r"atomicAdd\([^;]*\(double\)|unsafeAtomicAdd|atomicAdd_f|__hip_atomic_fetch_add", src)
     # the definition names its departures
     block = header[header.index("as Seurat v3 chooses them"):header.index("srx_seurat_v3_opts")]
@@ -224,7 +225,7 @@ def test_seurat_kernels_do_not_spill_registers(tmp_path):
     found = _kernel_meta(tmp_path, "hvg_seurat.hip", "k_sv_")
     seen = {k for k in KERNELS if any(re.search(r"\d%s(I|E|\b)" % k, name) for name in found)}
     assert seen == set(KERNELS), set(KERNELS) - seen
-    assert len(found) == len(KERNELS) + 1                                             # k_sv_negative: f32 and f64 storage
+    assert len(found) == len(KERNELS)          # none is a template; the value check and the pick are matrix.hip's and select.hip's
     walks = _kernel_meta(tmp_path, "markers.hip", "k_mk_walk")
     # f32 / f64 values x 16-bit mirror / 32-bit indices, unclipped and clipped; the counting pass per index form
     assert len(walks) == 4 + 4 + 2, walks

@@ -15,9 +15,10 @@ import pearson_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("srx_pearson_gene_variance", "srx_select_hvg_pearson", "srx_pearson_residuals")
-KERNELS = ("k_pr_check", "k_pr_totals", "k_pr_gene_factor", "k_pr_dense", "k_pr_sparse_csr", "k_pr_gene_direct", "k_pr_finish",
-           "k_pr_pick", "k_pr_block")
-INSTANCES = 13          # four of the nine are templates over the value storage (f32 / f64)
+KERNELS = ("k_pr_totals", "k_pr_gene_factor", "k_pr_dense", "k_pr_sparse_csr", "k_pr_gene_direct", "k_pr_finish", "k_pr_block")
+INSTANCES = 10          # three of the seven are templates over the value storage (f32 / f64)
+# the kernels this file shares with other calls: the value check (matrix.hip, f32 / f64) and the pick of the first ranks (select.hip)
+SHARED = {"matrix.hip": ("k_value_scan", 2), "select.hip": ("k_pick_top", 1)}
 
 
 def kat():
@@ -125,7 +126,8 @@ def test_pearson_symbols_are_exported_and_bound():
     assert "fp contract(off)" in src and not any("fast-math" in f for f in build.FLAGS)
     # no floating-point atomic (the fixed-point sums add 64-bit integers); the ranking is select.hip's kernel
     assert not re.search(r"atomicAdd\([^;]*\(double\)|unsafeAtomicAdd|atomicAdd_f|__hip_atomic_fetch_add", src)
-    assert "rank_keys_device(ctx, d_key" in src
+    assert "rank_keys_device(ctx, d_key" in src and "pick_top(ctx, d_rank" in src and "value_scan(m, " in src
+    assert "rank_keys_device(srx_ctx*" not in src                             # declared once, in pca_internal.hpp
     select = open(os.path.join(ROOT, "singlerust_amd", "csrc", "select.hip")).read()
     assert re.search(r"int32_t rank_keys_device\(.*?k_hvg_rank", select, flags=re.S)
 
@@ -188,3 +190,12 @@ def test_pearson_kernels_do_not_spill_registers(tmp_path):
         seen |= {k for k in KERNELS if re.search(r"\d%s(I|E|\b)" % k, m.group(1))}
     assert seen == set(KERNELS), set(KERNELS) - seen
     assert n_kernels == INSTANCES
+    for source, (kernel, instances) in SHARED.items():
+        out = str(tmp_path / (source + ".s"))
+        subprocess.check_call([build._hipcc(), *[f for f in build.FLAGS if f != "-Wall"], "-w", "-S", "--cuda-device-only", "-o", out,
+                               os.path.join(ROOT, "singlerust_amd", "csrc", source)], stderr=subprocess.DEVNULL)
+        bodies = re.findall(r"\.name:\s+\S*\d%s(?:I\S*|E\S*)?\n(.*?)\.wavefront_size" % kernel, open(out).read(), flags=re.S)
+        assert len(bodies) == instances, (kernel, len(bodies))
+        for body in bodies:
+            for field in ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"):
+                assert int(re.search(r"\.%s:\s+(\d+)" % field, body).group(1)) == 0, (kernel, field)

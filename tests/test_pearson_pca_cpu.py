@@ -1,7 +1,8 @@
 """PCA of the Pearson residuals without a GPU: the numpy restatement (pearson_pca_ref.py) against a `decimal` evaluation of the
 covariance of a 5 x 3 count matrix under both totals, the planted input's eigenvalue gaps, the new symbols bound in every layer
 with the struct layout gcc gives them, NULL arguments refused with nothing written, and the gfx950 listings of the kernels of
-pearson_pca.hip free of register spills and scratch, with the two products on the f64 matrix cores."""
+pearson_pca.hip and of the dense route it calls (dense_pca.hip) free of register spills and scratch, with the two products on the
+f64 matrix cores."""
 import ctypes as C
 import decimal
 import os
@@ -15,9 +16,14 @@ import pearson_pca_ref as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("srx_pca_pearson", "srx_pearson_gram")
-KERNELS = ("k_pp_row_sums", "k_pp_fill", "k_pp_stored", "k_pp_syrk", "k_pp_syrk_reduce", "k_pp_colsum", "k_pp_colsum_reduce",
-           "k_pp_finish", "k_pp_scores")
-MFMA_KERNELS = ("k_pp_syrk", "k_pp_scores")
+# per translation unit; the two chunk kernels are templates on the caller's element and are compiled with the caller
+KERNELS = {"pearson_pca.hip": ("k_pp_row_sums", "k_pp_gene_sums", "k_dense_fill", "k_dense_stored"),
+           "dense_pca.hip": ("k_dense_syrk", "k_dense_syrk_reduce", "k_dense_colsum", "k_dense_colsum_reduce", "k_dense_finish",
+                             "k_dense_scores")}
+# the instantiations of pearson_pca.hip: the row sums and the stored pass per value storage, no counting form
+INSTANCES = {"k_pp_row_sums": 2, "k_pp_gene_sums": 1, "k_dense_fill": 1, "k_dense_stored": 2}
+MFMA_KERNELS = ("k_dense_syrk", "k_dense_scores")
+PRODUCTS = r"k_dense_(syrk|colsum|finish|scores)"
 
 X53 = np.array([[3, 0, 1], [0, 2, 5], [7, 1, 0], [1, 1, 1], [0, 4, 2]], dtype=np.int64)
 
@@ -114,11 +120,22 @@ def test_pearson_pca_symbols_are_exported_and_bound():
     # additive: the ABI version and the number of profiling classes stay
     assert re.search(r"#define\s+SRX_ABI_VERSION\s+6\b", header) and lib.srx_abi_version() == 6
     assert re.search(r"SRX_K_COUNT_ = 13\b", header)
-    assert "pearson_pca.hip" in build.SOURCES
-    src = open(os.path.join(ROOT, "singlerust_amd", "csrc", "pearson_pca.hip")).read()
-    shared = open(os.path.join(ROOT, "singlerust_amd", "csrc", "pearson_internal.hpp")).read()
-    assert "fp contract(off)" in shared and '#include "pearson_internal.hpp"' in src
-    assert not re.search(r"atomicAdd|unsafeAtomicAdd|__hip_atomic", src)              # no atomics at all: every sum has one owner
+    assert "pearson_pca.hip" in build.SOURCES and "dense_pca.hip" in build.SOURCES
+    read = lambda name: open(os.path.join(ROOT, "singlerust_amd", "csrc", name)).read()
+    src, dense, route, shared = read("pearson_pca.hip"), read("dense_pca.hip"), read("dense_pca_internal.hpp"), read("pearson_internal.hpp")
+    assert "fp contract(off)" in shared and '#include "pearson_internal.hpp"' in src and '#include "dense_pca_internal.hpp"' in src
+    assert "fp contract(off)" in src and "fp contract(off)" in dense
+    for text in (src, dense):
+        assert not re.search(r"atomicAdd|unsafeAtomicAdd|__hip_atomic", text)         # no atomics at all: every sum has one owner
+    # the chunk templates: only the counts of clipped pairs, integers, cast where they are added; Pearson instantiates neither
+    assert not re.search(r"unsafeAtomicAdd|__hip_atomic|atomicExch|atomicCAS|atomicMax|atomicMin", route)
+    adds = re.findall(r"atomicAdd\(([^;]*);", route)
+    assert len(adds) == 3 and all("(unsigned long long)" in a for a in adds), adds
+    assert not re.search(r"\b(double|float)\s*\*\s*(__restrict__\s*)?cnt\b", route)
+    assert "dense_make_chunk<PpElem, false>" in src and "dense_make_chunk<PpElem, true>" not in src
+    # the products are dense_pca.hip's, once: this caller neither defines nor launches one
+    assert not re.search(r"__global__[^;{]*\b" + PRODUCTS, src) and not re.search(r"hipLaunchKernelGGL\(\(?" + PRODUCTS, src)
+    assert len(re.findall(r"__global__[^;{]*\b" + PRODUCTS, dense)) == 6
     assert "residuals followed by a PCA" not in header and "batch_key" in header
 
 
@@ -154,22 +171,28 @@ def test_null_arguments_are_refused_and_nothing_is_written():
 
 
 def test_pearson_pca_kernels_do_not_spill_registers(tmp_path):
-    """The gfx950 code-object metadata of every kernel of pearson_pca.hip shows no VGPR / SGPR spill and no scratch, and the
-    two products issue v_mfma_f64_16x16x4."""
+    """The gfx950 code-object metadata of every kernel of pearson_pca.hip (its instantiations of the two chunk kernels included)
+    and of dense_pca.hip shows no VGPR / SGPR spill and no scratch, and the two products issue v_mfma_f64_16x16x4."""
     from singlerust_amd import build
-    out = str(tmp_path / "pearson_pca.s")
-    subprocess.check_call([build._hipcc(), *[f for f in build.FLAGS if f != "-Wall"], "-w", "-S", "--cuda-device-only", "-o", out,
-                           os.path.join(ROOT, "singlerust_amd", "csrc", "pearson_pca.hip")], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    seen = set()
-    for m in re.finditer(r"\.name:\s+(\S*k_pp_\S*)\n(.*?)\.wavefront_size", text, flags=re.S):
-        body = m.group(2)
-        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", body).group(1))
-        sspill = int(re.search(r"\.sgpr_spill_count:\s+(\d+)", body).group(1))
-        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
-        assert spill == 0 and sspill == 0 and scratch == 0, f"{m.group(1)}: {spill} / {sspill} spilled V/SGPRs, {scratch} B of scratch"
-        seen |= {k for k in KERNELS if re.search(r"\d%s(I|E|\b)" % k, m.group(1))}
-    assert seen == set(KERNELS), set(KERNELS) - seen
-    for k in MFMA_KERNELS:
-        body = re.search(r"^_ZN3srx\d+%sE\w*:[^\n]*\n(.*?)^\.Lfunc_end" % k, text, flags=re.S | re.M).group(1)
-        assert body.count("v_mfma_f64_16x16x4") >= 4, k
+    for source, kernels in KERNELS.items():
+        out = str(tmp_path / (source + ".s"))
+        subprocess.check_call([build._hipcc(), *[f for f in build.FLAGS if f != "-Wall"], "-w", "-S", "--cuda-device-only", "-o", out,
+                               os.path.join(ROOT, "singlerust_amd", "csrc", source)], stderr=subprocess.DEVNULL)
+        text = open(out).read()
+        count = {k: 0 for k in kernels}
+        for m in re.finditer(r"\.name:\s+(\S*k_(?:pp|dense)_\S*)\n(.*?)\.wavefront_size", text, flags=re.S):
+            body = m.group(2)
+            spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", body).group(1))
+            sspill = int(re.search(r"\.sgpr_spill_count:\s+(\d+)", body).group(1))
+            scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
+            assert spill == 0 and sspill == 0 and scratch == 0, f"{m.group(1)}: {spill} / {sspill} spilled V/SGPRs, {scratch} B of scratch"
+            hit = [k for k in kernels if re.search(r"\d%s(I|E|\b)" % k, m.group(1))]
+            assert len(hit) == 1, m.group(1)                                          # no kernel of the route is outside the lists
+            count[hit[0]] += 1
+        if source == "pearson_pca.hip":
+            assert count == INSTANCES, count
+        else:
+            assert all(c == 1 for c in count.values()), count
+            for k in MFMA_KERNELS:
+                body = re.search(r"^_ZN3srx\d+%sE\w*:[^\n]*\n(.*?)^\.Lfunc_end" % k, text, flags=re.S | re.M).group(1)
+                assert body.count("v_mfma_f64_16x16x4") >= 4, k

@@ -18,7 +18,11 @@ import regress_ref as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("srx_regress_fit", "srx_regress_sums", "srx_regress_residuals", "srx_regress_gram", "srx_pca_regress")
-KERNELS = ("k_rg_fill", "k_rg_stored", "k_rg_wsum", "k_rg_wsum_reduce", "k_rg_check")
+# the two chunk kernels are the dense route's templates (dense_pca_internal.hpp), compiled here with regress's element
+KERNELS = ("k_dense_fill", "k_dense_stored", "k_rg_wsum", "k_rg_wsum_reduce")
+# the instantiations: the fill with and without the clip counters, the stored pass also per value storage
+INSTANCES = {"k_dense_fill": 2, "k_dense_stored": 4, "k_rg_wsum": 1, "k_rg_wsum_reduce": 1}
+PRODUCTS = r"k_dense_(syrk|colsum|finish|scores)"
 LD_EPS = float(np.finfo(np.longdouble).eps)
 
 
@@ -121,19 +125,25 @@ def test_regress_symbols_are_exported_and_bound():
     # additive: the ABI version and the number of profiling classes stay
     assert re.search(r"#define\s+SRX_ABI_VERSION\s+6\b", header) and lib.srx_abi_version() == 6
     assert re.search(r"SRX_K_COUNT_ = 13\b", header)
-    assert "regress.hip" in build.SOURCES
+    assert "regress.hip" in build.SOURCES and "dense_pca.hip" in build.SOURCES
     assert re.search(r"regress", header, flags=re.I) and "max_value" in header
 
 
 def test_regress_source_has_no_floating_point_atomic_and_no_contraction():
-    src = open(os.path.join(ROOT, "singlerust_amd", "csrc", "regress.hip")).read()
+    read = lambda name: open(os.path.join(ROOT, "singlerust_amd", "csrc", name)).read()
+    src, route, dense = read("regress.hip"), read("dense_pca_internal.hpp"), read("dense_pca.hip")
     assert "fp contract(off)" in src and '#include "dense_pca_internal.hpp"' in src
-    assert not re.search(r"unsafeAtomicAdd|__hip_atomic|atomicExch|atomicCAS|atomicMax|atomicMin", src)
-    for m in re.finditer(r"atomicAdd\(([^;]*);", src):                       # the counts of clipped pairs: integers, cast where they are added
-        assert "(unsigned long long)" in m.group(1), m.group(0)
-    assert not re.search(r"\b(double|float)\s*\*\s*(__restrict__\s*)?cnt\b", src)
-    # the products are pearson_pca.hip's, once: the kernels are not defined a second time
-    assert not re.search(r"__global__[^;{]*\bk_pp_", src) and "hipLaunchKernelGGL(k_pp_" not in src
+    # the counts of clipped pairs are the only atomics of the route: in the chunk templates, integers, cast where they are added
+    assert "atomicAdd" not in src and "atomicAdd" not in dense
+    for text in (src, route, dense):
+        assert not re.search(r"unsafeAtomicAdd|__hip_atomic|atomicExch|atomicCAS|atomicMax|atomicMin", text)
+        assert not re.search(r"\b(double|float)\s*\*\s*(__restrict__\s*)?cnt\b", text)
+    adds = re.findall(r"atomicAdd\(([^;]*);", route)
+    assert len(adds) == 3 and all("(unsigned long long)" in a for a in adds), adds
+    assert "dense_make_chunk<RgArgs, COUNT>" in src and "rg_maker<true>" in src and "rg_maker<false>" in src
+    # the products are dense_pca.hip's, once: this caller neither defines nor launches one
+    assert not re.search(r"__global__[^;{]*\b" + PRODUCTS, src) and not re.search(r"hipLaunchKernelGGL\(\(?" + PRODUCTS, src)
+    assert len(re.findall(r"__global__[^;{]*\b" + PRODUCTS, dense)) == 6
 
 
 @pytest.mark.parametrize("cname,struct,size", [("srx_regress_opts", "RegressOpts", 72), ("srx_regress_info", "RegressInfo", 160)])
@@ -173,20 +183,23 @@ def test_null_arguments_are_refused_and_nothing_is_written():
 
 
 def test_regress_kernels_do_not_spill_registers(tmp_path):
-    """The gfx950 code-object metadata of every kernel of regress.hip shows no VGPR / SGPR spill and no scratch."""
+    """The gfx950 code-object metadata of every kernel of regress.hip, its instantiations of the two chunk kernels included,
+    shows no VGPR / SGPR spill and no scratch."""
     from singlerust_amd import build
     out = str(tmp_path / "regress.s")
     subprocess.check_call([build._hipcc(), *[f for f in build.FLAGS if f != "-Wall"], "-w", "-S", "--cuda-device-only", "-o", out,
                            os.path.join(ROOT, "singlerust_amd", "csrc", "regress.hip")], stderr=subprocess.DEVNULL)
     text = open(out).read()
-    seen = set()
-    for m in re.finditer(r"\.name:\s+(\S*k_rg_\S*)\n(.*?)\.wavefront_size", text, flags=re.S):
+    count = {k: 0 for k in KERNELS}
+    for m in re.finditer(r"\.name:\s+(\S*k_(?:rg|dense)_\S*)\n(.*?)\.wavefront_size", text, flags=re.S):
         body = m.group(2)
         spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", body).group(1))
         sspill = int(re.search(r"\.sgpr_spill_count:\s+(\d+)", body).group(1))
         scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
         assert spill == 0 and sspill == 0 and scratch == 0, f"{m.group(1)}: {spill} / {sspill} spilled V/SGPRs, {scratch} B of scratch"
-        seen |= {k for k in KERNELS if re.search(r"\d%s(I|E|\b)" % k, m.group(1))}
-    assert seen == set(KERNELS), set(KERNELS) - seen
+        hit = [k for k in KERNELS if re.search(r"\d%s(I|E|\b)" % k, m.group(1))]
+        assert len(hit) == 1, m.group(1)
+        count[hit[0]] += 1
+    assert count == INSTANCES, count
     body = re.search(r"^_ZN3srx\d+k_rg_wsumE\w*:[^\n]*\n(.*?)^\.Lfunc_end", text, flags=re.S | re.M).group(1)
     assert "v_fma_f64" not in body and "v_mul_f64" in body and "v_add_f64" in body           # no contraction in the sums
