@@ -152,7 +152,7 @@ struct srx_pca_state {           // what the last srx_pca / srx_pipeline left in
     int center = 1, scale = 1;       // the flags the solve ran with (srx_pca_model_from_result)
     int residual = 0;                // kResidual*: the result is a PCA of a dense residual matrix (srx_pca_pearson, srx_pca_regress): no
                                      // model can be made of it; the value says which call made it
-    std::vector<int> round_counts;   // components resolved by each deflation round (sums to n_pc); set by run_pca with its plan
+    std::vector<int> round_counts;   // components resolved by each deflation round (sums to n_pc); set by run_plan (pca_solve.hip) with the plan it runs (pca_plans, pca_schedule.hpp)
     double* d_scores = nullptr;      // n_rows x n_pc, row-major f64
     size_t scores_cap = 0;
     std::vector<double> components;  // k x n_pc (host copy; small)

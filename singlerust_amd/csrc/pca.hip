@@ -22,8 +22,8 @@
 // A is the HVG-COMPACTED matrix (compact.inl): row-major (column, value) records — what the Gram kernel and the forward
 // product read — and, for the matrix-free solver, a tile-major view; everything of size k x 64 is replicated per rank and
 // kept in f64.  Three translation units share pca_internal.hpp: pca_form.hip (compaction, owner records, G = A^T A and its
-// exchange across row shards), pca_solve.hip (the sparse products, the k x 64 iteration, the solver driver run_pca,
-// srx_spmm) and this file: feature selection plumbing, the per-matrix driver pca_device, the host copies of the results, the
+// exchange across row shards), pca_solve.hip (the sparse products, the k x 64 iteration (struct Iteration), the operators and the solver driver
+// run_pca, srx_spmm; the schedule of a solve as plain host functions: pca_schedule.hpp) and this file: feature selection plumbing, the per-matrix driver pca_device, the host copies of the results, the
 // out-of-core sessions (backed.inl) and the C entry points srx_pca / srx_pipeline / srx_result_fetch.
 //
 // Measured on MI355X (profiles/r01_*): LDS f32 float atomics (ds_add_f32) run ~10x slower than

@@ -1,7 +1,7 @@
 // pca_internal.hpp — what the three translation units of the PCA path share (pca_form.hip: compaction + Gram formation;
 // pca_solve.hip: the sparse products, the k x 64 subspace iteration and the solver driver; pca.hip: selection, the per-matrix
 // driver, backed sessions and the C entry points).  Constants, the entry / record formats, small device helpers, the
-// descriptors of the compacted matrix, and the functions that cross a translation-unit boundary.
+// descriptors of the compacted matrix, and the functions that cross a translation-unit boundary.  Resolved (the options of a solve) is in pca_schedule.hpp.
 #pragma once
 
 #include <algorithm>
@@ -14,6 +14,7 @@
 
 #include "common.hpp"
 #include "pca_result.hpp"
+#include "pca_schedule.hpp"
 
 namespace srx {
 
@@ -143,20 +144,6 @@ struct RowMajor {
     int64_t n_recs = -1;       // >= 0: the Gram kernel's record counts were made with the compaction (scratch pca_brtot / pca_brbase
                                // hold them): launch_gram starts at the bucket pass, one host wait less per step
 };
-struct Resolved {
-    int n_pc, center, scale, max_iter, solver;
-    double bail_ratio = 0.0; // > 0: give the round up after its first Ritz step when theta_l / theta_npc exceeds this (the
-                             // caller has a plan with more guard columns per round)
-    bool direct = false;     // k <= 64 with the explicit matrix: the block is the identity, one exact eigen-solve of C
-    bool robust = false;     // last resort after a breakdown: CholeskyQR after every application of C, shifted
-                             // CholeskyQR3, plain sweeps instead of Chebyshev filters
-    int power = 1;           // applications of C per Rayleigh–Ritz step
-    int warm = 0;            // leading sweeps of `power` applications + CholeskyQR WITHOUT a Rayleigh–Ritz step
-    double tol;
-    uint64_t seed;
-};
-
-
 // ---- select.hip (and, from genes.hip, the two things it needs beyond common.hpp) ---------------------
 // FeatureSelection::HighlyVariable(n) ranked on the host (the CSC variance for a CSC matrix): the route of srx_select_hvg, and of
 // the PCA drivers outside hvg_on_device's envelope, which pass the list on
@@ -210,7 +197,7 @@ int scores_ld(int n_pc);
 // pca_model.inl: srx_pca_transform with feat == NULL, row r of the query written to d_out + r * ld on the device (doublets.hip)
 int32_t pca_transform_device(srx_pca_model* p, srx_mat* q, double target_sum, int32_t transform, double* d_out, size_t ld);
 void result_layout(uint64_t n_rows, int k, int n_pc, int dim, size_t& score_bytes, size_t& small_doubles,
-                   std::vector<int>* plan_a_out = nullptr, std::vector<int>* plan_b_out = nullptr);
+                   PcaPlans* plans_out = nullptr);
 int32_t ensure_result_capacity(srx_ctx* ctx, srx_pca_state& st, size_t need);
 int32_t resolve_opts(srx_ctx* ctx, const srx_pca_opts* opts, int k, uint64_t Ng, bool f32, Resolved& o, int& l_act);
 inline PcaResultLayout result_block(const srx_pca_state& st) { return PcaResultLayout(st.k, L, st.round_counts); }

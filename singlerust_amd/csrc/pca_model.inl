@@ -1,5 +1,5 @@
 // pca_model.inl — a fitted PCA applied to other cells: Pca::transform (src/shared/processing/pca/mod.rs:156-185), included by
-// pca_solve.hip after run_pca.  A model folds V, mu, sd' and the flags once into what the forward product consumes: f64 panels
+// pca_solve.hip after the solver (run_pca, srx_spmm, srx_iterate_op).  A model folds V, mu, sd' and the flags once into what the forward product consumes: f64 panels
 // P = D^-1 V (slices of 64 columns, model rows in the fit's selection order) and cvec = c mu^T P.  A transform builds the
 // selection bits of the genes the query has, compacts the query (the raw-value XF form under normalise + log1p), gathers
 // the panel rows into the compacted columns' order (ascending query gene) and runs the fit's forward kernel per slice.

@@ -1,7 +1,7 @@
 // pca_solve.hip — the solver half of dim_red::pca_inplace on the GPU (pca.hip has the overview): the sparse products with a
 // k x 64 panel (spmm.inl), the k x 64 subspace iteration on the device (iterate.inl, jacobi.inl: dense apply on the f64 matrix
-// cores, CholeskyQR, Jacobi eigen-solve, Chebyshev filter, residuals; replayed from hipGraphs), the solver driver run_pca
-// (deflation rounds, plans A / B, the transform), srx_spmm (the raw operators, for kernel-level parity tests) and the PCA model
+// cores, CholeskyQR, Jacobi eigen-solve, Chebyshev filter, residuals; replayed from hipGraphs: struct Iteration), the operators and the
+// solver driver (run_pca: deflation rounds, plans A / B, the transform; every host decision: pca_schedule.hpp), srx_spmm (the raw operators, for kernel-level parity tests) and the PCA model
 // of srx_pca_transform (pca_model.inl).
 #include "pca_internal.hpp"
 #include "hash.hpp"
@@ -186,7 +186,7 @@ static int32_t gram2(srx_ctx* ctx, const Work& w, const double* A, const double*
     return SRX_OK;
 }
 
-// The launch of every kernel of the iteration: grid, block, dynamic LDS.  subspace_iterate's segments and srx_iterate_op (the
+// The launch of every kernel of the iteration: grid, block, dynamic LDS.  Iteration's segments and srx_iterate_op (the
 // kernel-level entry) both go through these, so that what the tests launch is what the solver launches.  They only enqueue
 // on ctx->stream: the caller reads hipGetLastError.
 static int32_t attr_dense_apply(srx_ctx* ctx) {
@@ -285,106 +285,113 @@ static int32_t graphed(srx_ctx* ctx, bool enable, const std::string& key, Fn&& e
     return SRX_OK;
 }
 
-// Block subspace iteration with Rayleigh–Ritz on span(W); `apply(W, Wp)` computes Wp = C W.
-// On return w.A2 = W U holds the Ritz vectors (k x 64, leading n_pc columns meaningful),
-// theta their Ritz values, w.dColmax the largest-|.| entry of each Ritz vector.
-template <typename Apply>
-static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, const Resolved& o, Apply&& apply,
-                                const void* apply_id, bool graphable, const int* d_status_sel, double& resid, int& iters,
-                                bool& converged, bool acc_apply, bool resume = false, bool* bailed_first = nullptr) {
-    // `resume`: the block is the one a one-round plan just left at its FIRST Ritz step (flat tail: `*bailed_first`), with the
-    // speculative first filter step already queued behind it — W, A2 = Ritz vectors, theta, A1 = Y1, Wp = C Y1, the Ritz tail's
-    // partial sums: everything this round's own start segment (start block, warm-up sweeps, first Ritz step: ~0.45 ms at k =
-    // 1000) would recompute, for the same 64-column block.  Only the step's scalars are re-made for this round's n_pc.
-    // `acc_apply` (the Gram solver): `apply` ACCUMULATES into a zeroed destination and w.T is free.  The applications of a sweep
-    // then rotate through three scratch blocks (Wp, A1, T), and the kernels that are the last to read a block leave it zeroed
-    // (the CholeskyQR's substitution: all three; the Ritz tail: Wp; the filter step: its Z) — the eight memset launches a solve
-    // used to queue in front of its applications are gone (~40 us of a 1 ms iteration).  Invariants: after `orth` Wp, A1 and T
-    // are zero; after a Ritz step Wp and T are zero, A1 = (C W) U, A2 = W U.
-    const size_t kl = (size_t)k * L;
-    const bool use_graph = graphable && !getenv("SRX_NO_GRAPH");
-    const bool use_cheb = l_act > o.n_pc && !o.robust && !o.direct;      // both solvers: the filter only needs `apply`
-    constexpr int kSlots = srx_ctx::kAsyncSlots, kSlotDoubles = 8;
-    if (!ctx->pin_async) {
-        SRX_HIP(ctx, hipHostMalloc((void**)&ctx->pin_async, kSlots * kSlotDoubles * sizeof(double), hipHostMallocDefault));
-        for (auto& e : ctx->async_ev) SRX_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    int* d_status;
-    double* d_res;
+// The switches of a solve, read from the environment once.
+struct SolveEnv {
+    const bool trace = getenv("SRX_PCA_TRACE"), no_graph = getenv("SRX_NO_GRAPH"), robust = getenv("SRX_PCA_ROBUST");
+};
+struct IterResult {
+    double resid = INFINITY;
+    int iters = 0;                      // sweeps after the warm-up
+    bool converged = false;
+    bool bailed_first = false;          // left at the first Ritz step for its flat tail, the block and the queued first filter step intact
+};
+
+// Block subspace iteration with Rayleigh–Ritz on span(W); `op.apply(W, Wp, zeroed)` computes Wp = C W.  After run(), w.A2 = W U
+// holds the Ritz vectors (k x 64, leading n_pc columns meaningful), theta their Ritz values, w.dColmax the largest-|.| entry
+// of each Ritz vector.
+// Every member but run(), collect() and trace_step() only ENQUEUES work: the l x l factorisations run on the device, and the
+// one number the host needs per Rayleigh–Ritz step (the residual) comes back through a pinned slot and an event, read one step
+// late so that the stream never drains.  run() is the host loop: collect, decide (pca_schedule.hpp), enqueue the named segment
+// through `graphed`, read back.
+// An operator that ACCUMULATES (the Gram solver) adds into a zeroed destination and leaves w.T free.  The applications of a
+// sweep then rotate through three scratch blocks (Wp, A1, T), and the kernels that are the last to read a block leave it zeroed
+// (the CholeskyQR's substitution: all three; the Ritz tail: Wp; the filter step: its Z) — the eight memset launches a solve
+// used to queue in front of its applications are gone (~40 us of a 1 ms iteration).  INVARIANTS: after `orth` Wp, A1 and T
+// are zero; after a Ritz step Wp and T are zero, A1 = (C W) U, A2 = W U.
+template <typename Op>
+struct Iteration {
+    static constexpr int kSlots = srx_ctx::kAsyncSlots, kSlotDoubles = 8;
     // the status words and, behind them, the ONE 64 x 64 matrix the partial products of a block pair are summed into (k_gram1_part:
     // global f64 atomics; its single consumer — the Cholesky factorisation or the eigen-solve — reads it once and leaves it zeroed;
     // the memset that clears the status words at the start of a solve clears it too)
-    constexpr size_t kStatusBytes = 256;
-    SRX_TRY(scratch(ctx, "pca_status", kStatusBytes + (size_t)L * L * sizeof(double), (void**)&d_status));
-    double* const d_h1 = reinterpret_cast<double*>(reinterpret_cast<char*>(d_status) + kStatusBytes);
-    SRX_TRY(scratch(ctx, "pca_res", kSlots * kSlotDoubles * sizeof(double), (void**)&d_res));
-    double* d_ritz;
-    SRX_TRY(scratch(ctx, "pca_ritzpart", (size_t)kRitzBlocks * 3 * L * sizeof(double), (void**)&d_ritz));
-    SRX_TRY(attr_jacobi(ctx));
-    // what a captured segment depends on besides its own schedule: shapes, options, every buffer it touches
-    char key0[320];
-    snprintf(key0, sizeof key0, "k%d l%d p%d w%d r%d n%d s%llu t%a|%p %p %p %p %p %p %p %p %p %p", k, l_act, o.power, o.warm,
-             (o.robust ? 1 : 0) + (o.direct ? 2 : 0) + (acc_apply ? 4 : 0), o.n_pc,
-             (unsigned long long)o.seed, o.tol, apply_id, (void*)w.W, (void*)w.Wp, (void*)w.A1, (void*)w.A2, (void*)w.small,
-             (void*)w.gpart, (void*)d_status, (void*)d_status_sel, (void*)w.T);       // (d_ritz, d_res: allocated with d_status, never regrown)
-    const std::string key_base(key0);
+    static constexpr size_t kStatusBytes = 256, kStatusAndH1 = kStatusBytes + (size_t)L * L * sizeof(double);
+    static constexpr bool acc = Op::accumulates;
+    srx_ctx* const ctx;
+    const Work& w;
+    const int k, l_act;
+    const Resolved& o;                 // the round's options
+    Op& op;
+    const int* const d_status_sel;
+    const SolveEnv& env;
+    const size_t kl = (size_t)k * L;
+    const bool use_graph = Op::graphable && !env.no_graph;
+    int* d_status = nullptr;
+    double *d_h1 = nullptr, *d_res = nullptr, *d_ritz = nullptr;
+    std::string key_base;              // what a captured segment depends on besides its own schedule: shapes, options, every buffer it touches
+    double spread = 1.0;               // theta_1 / theta_l of the last collected Ritz step
 
-    // Everything below only ENQUEUES work: the l x l factorisations run on the device, and the one
-    // number the host needs per Rayleigh–Ritz step (the residual) comes back through a pinned slot
-    // and an event, read one step late so that the stream never drains.
+    int32_t prepare() {
+        if (!ctx->pin_async) {
+            SRX_HIP(ctx, hipHostMalloc((void**)&ctx->pin_async, kSlots * kSlotDoubles * sizeof(double), hipHostMallocDefault));
+            for (auto& e : ctx->async_ev) SRX_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        SRX_TRY(scratch(ctx, "pca_status", kStatusAndH1, (void**)&d_status));
+        d_h1 = reinterpret_cast<double*>(reinterpret_cast<char*>(d_status) + kStatusBytes);
+        SRX_TRY(scratch(ctx, "pca_res", kSlots * kSlotDoubles * sizeof(double), (void**)&d_res));
+        SRX_TRY(scratch(ctx, "pca_ritzpart", (size_t)kRitzBlocks * 3 * L * sizeof(double), (void**)&d_ritz));
+        SRX_TRY(attr_jacobi(ctx));
+        char key0[320];
+        snprintf(key0, sizeof key0, "k%d l%d p%d w%d r%d n%d s%llu t%a|%p %p %p %p %p %p %p %p %p %p", k, l_act, o.power, o.warm,
+                 (o.robust ? 1 : 0) + (o.direct ? 2 : 0) + (acc ? 4 : 0), o.n_pc,
+                 (unsigned long long)o.seed, o.tol, op.key(), (void*)w.W, (void*)w.Wp, (void*)w.A1, (void*)w.A2, (void*)w.small,
+                 (void*)w.gpart, (void*)d_status, (void*)d_status_sel, (void*)w.T);       // (d_ritz, d_res: allocated with d_status, never regrown)
+        key_base = key0;
+        return SRX_OK;
+    }
+    template <typename Fn>
+    int32_t segment(const char* name, Fn&& enqueue) { return graphed(ctx, use_graph, key_base + name, enqueue); }
 
     // orthonormalise src -> W  (CholeskyQR: G = src^T src = R^T R, W = src R^-1; src == W is fine: every
-    // thread of the substitution owns one row); G lands in dHG + L*L
-    auto gram1 = [&](const double* A, const double* B) -> int32_t {       // A^T B summed into d_h1 (zero between uses)
-        launch_gram1(ctx, A, B, k, d_h1);
-        SRX_HIP(ctx, hipGetLastError());
-        return 1;
-    };
-    auto orth = [&](const double* src) -> int32_t {
-        if (o.robust) {
+    // thread of the substitution owns one row); the substitution leaves an accumulating operator's three blocks zeroed
+    // (the matrix-free solver's apply overwrites its destination and uses T itself)
+    int32_t orth(const double* src) {
+        double *const zWp = acc ? w.Wp : nullptr, *const zA1 = acc ? w.A1 : nullptr, *const zT = acc ? w.T : nullptr;
+        if (!o.robust) {
+            launch_gram1(ctx, src, src, k, d_h1);           // src^T src summed into d_h1 (zero between uses)
+            launch_chol_mfma(ctx, d_h1, l_act, w.dM, w.dDinv, w.dXi, d_status);
+            launch_trsm_mfma(ctx, src, w.dM, w.dXi, k, w.W, zWp, zA1, zT);
+        } else {                                // shifted CholeskyQR, G in dHG + L*L, and a second pass: the first one may have run on a shifted Gram matrix
             SRX_TRY(gram2(ctx, w, src, src, k));
             launch_chol(ctx, w.dHG + L * L, l_act, w.dM, w.dDinv, d_status, 1);
-        } else {
-            const int32_t nb = gram1(src, src);
-            if (nb < 0) return nb;
-            launch_chol_mfma(ctx, d_h1, l_act, w.dM, w.dDinv, w.dXi, d_status);
-        }
-        double* const zT = acc_apply ? w.T : nullptr;           // (the matrix-free solver's apply overwrites its destination and uses T itself)
-        double* const zWp = acc_apply ? w.Wp : nullptr;
-        double* const zA1 = acc_apply ? w.A1 : nullptr;
-        if (o.robust)
             launch_trsm_rows(ctx, src, w.dM, w.dDinv, k, w.W, zWp, zA1, zT);
-        else
-            launch_trsm_mfma(ctx, src, w.dM, w.dXi, k, w.W, zWp, zA1, zT);
-        SRX_HIP(ctx, hipGetLastError());
-        if (o.robust) {                         // second pass: the first one may have run on a shifted Gram matrix
+            SRX_HIP(ctx, hipGetLastError());
             SRX_TRY(gram2(ctx, w, w.W, w.W, k));
             launch_chol(ctx, w.dHG + L * L, l_act, w.dM, w.dDinv, d_status, 1);
             launch_trsm_rows(ctx, w.W, w.dM, w.dDinv, k, w.W, nullptr, nullptr, nullptr);
-            SRX_HIP(ctx, hipGetLastError());
         }
+        SRX_HIP(ctx, hipGetLastError());
         return SRX_OK;
-    };
+    }
     // `n` applications of C starting from `src`, ping-ponging between Wp and A1 (no copies); returns where
     // the result is
     // (`after_orth`: Wp, A1 and T are zero; otherwise — after a Ritz step — Wp and T are)
-    auto apply_n = [&](const double* src, int n, bool after_orth, const double** out) -> int32_t {
+    int32_t apply_n(const double* src, int n, bool after_orth, const double** out) {
         const double* cur = src;
-        double* const cand[3] = {w.Wp, w.A1, acc_apply ? w.T : nullptr};
-        bool zero[3] = {acc_apply, acc_apply && after_orth, acc_apply};
+        double* const cand[3] = {w.Wp, w.A1, acc ? w.T : nullptr};
+        bool zero[3] = {acc, acc && after_orth, acc};
         for (int t = 0; t < n; ++t) {
             int pick = -1;
             for (int c = 0; c < 3 && pick < 0; ++c)
                 if (cand[c] && cand[c] != cur && zero[c]) pick = c;
             for (int c = 0; c < 3 && pick < 0; ++c)
                 if (cand[c] && cand[c] != cur) pick = c;
-            SRX_TRY(apply(cur, cand[pick], zero[pick]));
+            SRX_TRY(op.apply(cur, cand[pick], zero[pick]));
             zero[pick] = false;
             cur = cand[pick];
         }
         *out = cur;
         return SRX_OK;
-    };
+    }
     // one Rayleigh–Ritz step on span(W): Wp = C W, H = W^T Wp = U diag(theta) U^T, Ritz vectors
     // A2 = W U, residuals || C v_i - theta_i v_i || in f64; slot <- (residual, status)
     // `loose`: the step after the warm-up.  Its residuals are O(1e-2) whatever the eigen-solver does (it only feeds the
@@ -392,75 +399,78 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
     // the cyclic Jacobi two slow sweeps: it may stop at an off-diagonal norm of 1e-5 of the diagonal (7 -> 5 sweeps).  The
     // residuals are measured on the vectors actually formed, so a loosely rotated basis is judged as what it is: at the
     // default tolerances (1e-7 / 1e-9) such a step is never accepted as converged — the next, exact one decides.
-    auto ritz_kernels = [&](int slot, bool loose = false, bool wp_zero = false) -> int32_t {
-        SRX_TRY(apply(w.W, w.Wp, wp_zero || acc_apply));          // (Gram solver: Wp is zero after every CholeskyQR / filter step)
-        {
-            // H = W^T (C W) as partial sums -> eigen-solve (adds them on load) -> Ritz vectors, C x Ritz vectors, residual and
-            // largest-entry partials in one pass -> the step's scalars: 4 launches (9 on the old route)
-            const int32_t nb = gram1(w.W, w.Wp);
-            if (nb < 0) return nb;
-            // the step after the warm-up only feeds the filter's bounds and the rotated start (any invertible U spans the same
-            // block): off-diagonal norm 1e-3 of the diagonal is enough — the Ritz residual it reports, 1.63e-3 at c3, is the same
-            // to three digits as with 1e-5 (1.62e-3), one Jacobi sweep less; at 1e-2 it reads 1.7e-2 and the filter takes a degree more
-            constexpr double loose_tol2 = 1e-6;
-            // an exact step: the off-diagonal norm the solver leaves behind shows up in the Ritz residuals as at most that norm
-            // over theta_npc, i.e. sqrt(tol2) x (theta_1 / theta_npc) x a few — 1e-4 of the residual tolerance keeps it two
-            // orders below what the step is judged on (tol 1e-7: 1e-22, one sweep of the quadratic tail less than 1e-30)
-            const double exact_tol2 = std::max(1e-30, (o.tol * 1e-4) * (o.tol * 1e-4));
-            launch_jacobi(ctx, d_h1, l_act, w.dM2, w.dTheta, d_status, loose ? loose_tol2 : exact_tol2,
-                          o.direct ? l_act : std::min(l_act, o.n_pc + 4));      // (the guard columns' block need not be diagonal: jacobi.inl)
-            launch_ritz_post(ctx, w.W, w.Wp, w.dM2, w.dTheta, k, w.A1, w.A2, d_ritz, acc_apply ? 1 : 0);
-            launch_resid_final(ctx, d_ritz, w.dTheta, o.n_pc, l_act, d_status, d_status_sel, w.dRho, w.dColmax,
-                               d_res + kSlotDoubles * slot);
-        }
+    int32_t ritz_kernels(int slot, bool loose = false, bool wp_zero = false) {
+        SRX_TRY(op.apply(w.W, w.Wp, wp_zero || acc));          // (Gram solver: Wp is zero after every CholeskyQR / filter step)
+        // H = W^T (C W) as partial sums -> eigen-solve (adds them on load) -> Ritz vectors, C x Ritz vectors, residual and
+        // largest-entry partials in one pass -> the step's scalars: 4 launches (9 on the old route)
+        launch_gram1(ctx, w.W, w.Wp, k, d_h1);
+        launch_jacobi(ctx, d_h1, l_act, w.dM2, w.dTheta, d_status, jacobi_tol2(loose, o.tol), wanted_pairs(o.direct, l_act, o.n_pc));
+        launch_ritz_post(ctx, w.W, w.Wp, w.dM2, w.dTheta, k, w.A1, w.A2, d_ritz, acc ? 1 : 0);
+        return resid_final(slot);
+    }
+    int32_t resid_final(int slot) {             // the step's scalars for this round's n_pc
+        launch_resid_final(ctx, d_ritz, w.dTheta, o.n_pc, l_act, d_status, d_status_sel, w.dRho, w.dColmax, d_res + kSlotDoubles * slot);
         SRX_HIP(ctx, hipGetLastError());
         return SRX_OK;
-    };
+    }
     // the read-back of a Ritz step (pinned slot + event): always a plain stream operation, never captured
-    auto ritz_readback = [&](int slot) -> int32_t {
+    int32_t ritz_readback(int slot) {
         SRX_HIP(ctx, hipMemcpyAsync(ctx->pin_async + kSlotDoubles * slot, d_res + kSlotDoubles * slot,
                                     kSlotDoubles * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         SRX_HIP(ctx, hipEventRecord(ctx->async_ev[slot], ctx->stream));
         return SRX_OK;
-    };
+    }
+    int32_t collect(int slot, double& r, double& ratio) {
+        SRX_HIP(ctx, hipEventSynchronize(ctx->async_ev[slot]));
+        const double* const pin = ctx->pin_async + kSlotDoubles * slot;
+        r = pin[0];
+        const int st = (int)pin[1];
+        ratio = pin[2];
+        spread = pin[4];
+        if ((int)pin[3] & 1) return fail(ctx, SRX_E_NAN, "%s", kNanVarianceMsg);
+        if (st & kStatChol) return fail(ctx, SRX_E_NOCONV, "pca: block lost rank (Cholesky pivot <= 0)");
+        if (st & kStatEig) return fail(ctx, SRX_E_NOCONV, "pca: l x l eigen-solver did not converge");
+        if (r != r) return fail(ctx, SRX_E_NOCONV, "pca: NaN in the Ritz residual");
+        return SRX_OK;
+    }
+    void trace_step(int sweep, int n_ritz, int slot, double r, double ratio) {
+        const int n_jacobi = (int)ctx->pin_async[kSlotDoubles * slot + 5];
+        fprintf(stderr, "[srx pca] sweep %d (ritz step %d): residual %.3e, theta_l/theta_npc %.3e, %d Jacobi sweeps\n", sweep, n_ritz, r,
+                ratio, n_jacobi);
+        // the eigen-solve's off-diagonal norm (wanted pairs) over the diagonal's at every sweep's measurement (a drain: trace only)
+        int st[64];
+        if (d2h(ctx, st, d_status, sizeof st) != SRX_OK) return;
+        fprintf(stderr, "[srx pca]   Jacobi off / diag per sweep:");
+        for (int q = 0; q <= n_jacobi && q < 32; ++q) {
+            float f;
+            memcpy(&f, &st[16 + q], 4);
+            fprintf(stderr, " %.2e", (double)f);
+        }
+        fprintf(stderr, "\n");
+    }
     // the extra applications of C between two Rayleigh–Ritz steps (cheap dense products only; the
     // block stays well conditioned: kappa ~ (theta_1/theta_l)^power) and the next CholeskyQR
-    auto advance = [&]() -> int32_t {
+    int32_t advance() {
         // continue from the ROTATED block A1 = (C W) U (same span): its columns are close to eigenvectors,
         // so the next projected matrix is close to diagonal and its Jacobi solve takes 2-3 sweeps, not 8
         const double* res;
         SRX_TRY(apply_n(w.A1, o.power - 1, false, &res));
         return orth(res);
-    };
-    double spread = 1.0;               // theta_1 / theta_l of the last collected Ritz step
-    auto collect = [&](int slot, double& r, double& ratio) -> int32_t {
-        SRX_HIP(ctx, hipEventSynchronize(ctx->async_ev[slot]));
-        r = ctx->pin_async[kSlotDoubles * slot];
-        const int st = (int)ctx->pin_async[kSlotDoubles * slot + 1];
-        ratio = ctx->pin_async[kSlotDoubles * slot + 2];
-        spread = ctx->pin_async[kSlotDoubles * slot + 4];
-        if ((int)ctx->pin_async[kSlotDoubles * slot + 3] & 1)
-            return fail(ctx, SRX_E_NAN, "%s", kNanVarianceMsg);
-        if (st & kStatChol) return fail(ctx, SRX_E_NOCONV, "pca: block lost rank (Cholesky pivot <= 0)");
-        if (st & kStatEig) return fail(ctx, SRX_E_NOCONV, "pca: l x l eigen-solver did not converge");
-        if (r != r) return fail(ctx, SRX_E_NOCONV, "pca: NaN in the Ritz residual");
-        return SRX_OK;
-    };
+    }
     // one sweep WITHOUT a Rayleigh–Ritz step: `power` applications of C, then CholeskyQR
-    auto plain_sweep = [&]() -> int32_t {
+    int32_t plain_sweep() {
         const double* res;
         SRX_TRY(apply_n(w.W, o.power, true, &res));
         return orth(res);
-    };
-
+    }
     // segment "start": random block, CholeskyQR2, warm-up sweeps (the first Ritz residuals are O(1) whatever
     // happens — no Rayleigh–Ritz step to learn that), first Ritz step
-    auto seg_start = [&]() -> int32_t {
+    int32_t seg_start() {
         if (o.direct) {                    // W = I (k x k, k = l_act): H = C itself, Ritz pairs = eigenpairs whatever the rank
-            SRX_HIP(ctx, hipMemsetAsync(d_status, 0, kStatusBytes + (size_t)L * L * sizeof(double), ctx->stream));
+            SRX_HIP(ctx, hipMemsetAsync(d_status, 0, kStatusAndH1, ctx->stream));
             hipLaunchKernelGGL(k_identity_block, dim3((unsigned)((kl + 255) / 256)), dim3(256), 0, ctx->stream, k, w.W);
             SRX_HIP(ctx, hipGetLastError());
-            if (acc_apply) SRX_HIP(ctx, hipMemsetAsync(w.Wp, 0, kl * 8, ctx->stream));      // (no start block, no CholeskyQR: nothing has zeroed it)
+            if (acc) SRX_HIP(ctx, hipMemsetAsync(w.Wp, 0, kl * 8, ctx->stream));      // (no start block, no CholeskyQR: nothing has zeroed it)
             return ritz_kernels(0, false);
         }
         // With a warm-up sweep the random block goes straight into C^power: the CholeskyQR that ends the sweep is the first
@@ -472,206 +482,125 @@ static int32_t subspace_iterate(srx_ctx* ctx, const Work& w, int k, int l_act, c
         //  into Wp, and the CholeskyQR that follows leaves the three zeroed)
         // (the status words and the 64 x 64 projected matrix behind them start from zero: the start block's kernel does it)
         hipLaunchKernelGGL(k_init_block, dim3((unsigned)((kl + 255) / 256)), dim3(256), 0, ctx->stream, o.seed, k, l_act,
-                           start_orth ? w.Wp : w.W, acc_apply && !start_orth ? w.Wp : (double*)nullptr,
-                           acc_apply ? w.A1 : (double*)nullptr, acc_apply ? w.T : (double*)nullptr, reinterpret_cast<uint32_t*>(d_status),
-                           (int)((kStatusBytes + (size_t)L * L * sizeof(double)) / 4));
+                           start_orth ? w.Wp : w.W, acc && !start_orth ? w.Wp : (double*)nullptr,
+                           acc ? w.A1 : (double*)nullptr, acc ? w.T : (double*)nullptr, reinterpret_cast<uint32_t*>(d_status),
+                           (int)(kStatusAndH1 / 4));
         if (start_orth) {
             SRX_TRY(orth(w.Wp));
             SRX_TRY(orth(w.W));
         }
         for (int sweep = 0; sweep < o.warm; ++sweep) SRX_TRY(plain_sweep());
         return ritz_kernels(0, true);
-    };
+    }
     // Chebyshev filter after the first Ritz step (Gram solver: w.T is free and `apply` has no collective).
     // Speculative part: Y1 and Z = C Y1 (needed whatever the degree turns out to be, d >= 2).
-    auto cheb_spec = [&]() -> int32_t {
+    int32_t cheb_spec() {
         launch_cheb_first(ctx, w.A1, w.A2, w.dTheta, l_act, kl);
         SRX_HIP(ctx, hipGetLastError());
-        return apply(w.A1, w.Wp, acc_apply);          // (Gram solver: the Ritz tail left Wp zeroed)
-    };
+        return op.apply(w.A1, w.Wp, acc);          // (Gram solver: the Ritz tail left Wp zeroed)
+    }
     // the rest of a degree-d filter (Z = C Y1 is in Wp, cur = A1, prev = A2) and the CholeskyQR behind it
-    auto cheb_filter = [&](int d) -> int32_t {
+    int32_t cheb_filter(int d) {
         double *cur = w.A1, *prev = w.A2;
         for (int j = 1; j < d; ++j) {
-            if (j > 1) SRX_TRY(apply(cur, w.Wp, true));          // (the step before left Wp zeroed)
+            if (j > 1) SRX_TRY(op.apply(cur, w.Wp, true));          // (the step before left Wp zeroed)
             launch_cheb_step(ctx, w.Wp, cur, prev, w.dTheta, l_act, kl);
-            double* t = cur;
-            cur = prev;
-            prev = t;
+            std::swap(cur, prev);
         }
         launch_cheb_scale(ctx, cur, w.dTheta, l_act, d, kl);
         SRX_HIP(ctx, hipGetLastError());
         return orth(cur);
-    };
+    }
     // ... then, where ONE filter of the degree the block can take will not reach the tolerance anyway (flat tails: theta_l / theta_npc
     // = 0.97 gains 10x per degree-10 filter), a SECOND filter straight behind the CholeskyQR — C W, Y1 = a C W - W, C Y1, the
     // recurrence, the CholeskyQR — and only then the Ritz step: the projected Gram product, the eigen-solve, the Ritz tail and a
     // host decision less per pair of filters.  The bounds and the column scales are the last Ritz step's (the block still is that
     // step's Ritz vectors, filtered and re-orthonormalised); the CholeskyQR between the two takes the leading directions out of
     // the guard columns as a Ritz step would.
-    auto cheb_rest = [&](int d, int d2, int slot) -> int32_t {
+    int32_t cheb_rest(int d, int d2, int slot) {
         SRX_TRY(cheb_filter(d));
         if (d2 > 0) {
-            SRX_TRY(apply(w.W, w.Wp, acc_apply));                // (Gram solver: the CholeskyQR left Wp, A1, T zeroed)
+            SRX_TRY(op.apply(w.W, w.Wp, acc));                // (Gram solver: the CholeskyQR left Wp, A1, T zeroed)
             launch_cheb_first2(ctx, w.Wp, w.W, w.A1, w.A2, w.dTheta, l_act, kl);
             SRX_HIP(ctx, hipGetLastError());
-            SRX_TRY(apply(w.A1, w.Wp, true));
+            SRX_TRY(op.apply(w.A1, w.Wp, true));
             SRX_TRY(cheb_filter(d2));
         }
         return ritz_kernels(slot, false, true);          // (Wp: zeroed by the last filter step, untouched by the CholeskyQR)
-    };
+    }
     // segment "next": [advance] + (m - 1) plain sweeps + a Ritz step into `slot`
-    auto seg_next = [&](bool with_advance, int m, int slot) -> int32_t {
+    int32_t seg_next(bool with_advance, int m, int slot) {
         if (with_advance) SRX_TRY(advance());
         for (int sI = 1; sI < m; ++sI) SRX_TRY(plain_sweep());
         return ritz_kernels(slot);
-    };
-
-    resid = INFINITY;
-    converged = false;
-    iters = 0;                         // sweeps after the warm-up
-    int n_ritz = 0, slot = 0;
-    int q_applied = o.warm * o.power + 1;          // applications of C the block has seen (warm-up + first Ritz step)
-    double r_last = INFINITY, rate_meas = 0.0;
-    int sweeps_since = 0;
-    if (bailed_first) *bailed_first = false;
-    if (resume) {
-        launch_resid_final(ctx, d_ritz, w.dTheta, o.n_pc, l_act, d_status, d_status_sel, w.dRho, w.dColmax, d_res + kSlotDoubles * slot);
-        SRX_HIP(ctx, hipGetLastError());
-    } else {
-        SRX_TRY(graphed(ctx, use_graph, key_base + "|start", seg_start));
     }
-    SRX_TRY(ritz_readback(slot));
-    for (;;) {
-        ++iters;
-        ++n_ritz;
-        const bool first = n_ritz == 1;
-        const bool cheb = use_cheb;
-        if (cheb && first) {
-            if (!resume) SRX_TRY(graphed(ctx, use_graph, key_base + "|cheb0", cheb_spec));   // speculative: Y1, C Y1 (resume: already there)
-        } else if (first && !o.direct) SRX_TRY(graphed(ctx, use_graph, key_base + "|adv", advance));   // speculative: completes this sweep
-        double r, ratio;
-        SRX_TRY(collect(slot, r, ratio));
-        resid = r;
-        if (getenv("SRX_PCA_TRACE")) {
-            fprintf(stderr, "[srx pca] sweep %d (ritz step %d): residual %.3e, theta_l/theta_npc %.3e, %d Jacobi sweeps\n", iters + o.warm,
-                    n_ritz, r, ratio, (int)ctx->pin_async[kSlotDoubles * slot + 5]);
-            // the eigen-solve's off-diagonal norm (wanted pairs) over the diagonal's at every sweep's measurement (a drain: trace only)
-            int st[64];
-            if (d2h(ctx, st, d_status, sizeof st) == SRX_OK) {
-                fprintf(stderr, "[srx pca]   Jacobi off / diag per sweep:");
-                for (int q = 0; q <= (int)ctx->pin_async[kSlotDoubles * slot + 5] && q < 32; ++q) {
-                    float f;
-                    memcpy(&f, &st[16 + q], 4);
-                    fprintf(stderr, " %.2e", (double)f);
-                }
-                fprintf(stderr, "\n");
-            }
-        }
-        if (r <= o.tol) {
-            converged = true;
-            break;
-        }
-        if (iters >= o.max_iter) break;
-        if (first && o.bail_ratio > 0.0 && ratio > o.bail_ratio) {
-            if (getenv("SRX_PCA_TRACE")) fprintf(stderr, "[srx pca] flat tail (theta_l / theta_npc = %.3f): leaving the round to the safe plan\n", ratio);
-            if (bailed_first) *bailed_first = cheb;         // (the block and the queued first filter step are the next plan's to continue from)
-            break;                                 // converged stays false
-        }
-        if (cheb) {
-            // degree: T_d(t_a) >= 4 r / tol with t_a = (2 theta_npc - b) / b = 2 / ratio - 1
-            const double ta = ratio > 0 && ratio < 1 ? 2.0 / ratio - 1.0 : 1.0;
-            int d = 3;
-            if (ta > 1.0) d = (int)std::ceil(std::acosh(std::max(4.0 * r / o.tol, 1.0)) / std::acosh(ta) - 1e-9);
-            // The block captures eigenvector j up to an error ~ (b / lambda_j)^q after q applications of C, and a
-            // degree-d filter multiplies that error (relative to the column's own component) by ~ (lambda_j / b)^d:
-            // with d <= q the leading eigenvectors cannot swamp the other columns.  A degree-12 filter on a block
-            // that had seen ONE application (SpMM solver, no warm-up) collapsed it ("block lost rank").
-            if (d > q_applied) d = q_applied;
-            if (d > 12) d = 12;                // T_12 of the largest t stays far inside f64; harder spectra take more rounds
-            // The filter multiplies the component of every column along the leading eigenvector by T_d(t_1), t_1 =
-            // 2 theta_1 / theta_l - 1, and the guard columns' own components by ~1: whatever rounding-level trace of v_1
-            // a guard column carries (1e-16) must stay small against the column itself, or the block collapses onto the
-            // leading directions and the next CholeskyQR finds a pivot <= 0.  T_d(t_1) <= 1e14 <=> d <= 32.9 / acosh(t_1):
-            // no limit in practice when the block's spectrum spans less than 5x, 6 at 30x, 5 at 100x.
-            {
-                const double t1 = 2.0 * (spread > 1.0 ? spread : 1.0) - 1.0;
-                const int d_safe = t1 > 1.0 + 1e-9 ? (int)std::floor(32.9 / std::acosh(t1)) : 12;
-                if (d > d_safe) d = d_safe;
-            }
-            if (d < 2) d = 2;
-            // the degree the tolerance asks for against the degree this filter may have: a second one behind it when one cannot do
-            int d2 = 0;
-            if (ta > 1.0) {
-                const int d_need = (int)std::ceil(std::acosh(std::max(4.0 * r / o.tol, 1.0)) / std::acosh(ta) - 1e-9);
-                if (d_need > d + 1) {
-                    const double t1 = 2.0 * (spread > 1.0 ? spread : 1.0) - 1.0;
-                    const int d_safe = t1 > 1.0 + 1e-9 ? (int)std::floor(32.9 / std::acosh(t1)) : 12;
-                    d2 = std::min(std::min(d_need - d, 12), std::min(d_safe, q_applied + d));
-                    if (d2 < 2) d2 = 0;
-                }
-            }
-            q_applied += d + d2;               // d - 1 (+ d2) applications in the filter(s) + the one of the Ritz step
-            iters += (d + d2 + o.power - 1) / o.power;      // counted in sweep equivalents (max_iter bounds applications of C)
-            slot = (slot + 1) % kSlots;
-            char kn[64];
-            snprintf(kn, sizeof kn, "|cheb f%d d%d e%d s%d", first ? 1 : 0, d, d2, slot);
-            SRX_TRY(graphed(ctx, use_graph, key_base + kn, [&]() -> int32_t {
-                if (!first) SRX_TRY(cheb_spec());      // later rounds: nothing was queued speculatively
-                return cheb_rest(d, d2, slot);
-            }));
-            SRX_TRY(ritz_readback(slot));
-            if (getenv("SRX_PCA_TRACE")) {
-                if (d2) fprintf(stderr, "[srx pca] Chebyshev filters of degree %d and %d, a CholeskyQR between them (t_a = %.3f)\n", d, d2, ta);
-                else fprintf(stderr, "[srx pca] Chebyshev filter of degree %d (t_a = %.3f)\n", d, ta);
-            }
-            r_last = INFINITY;                 // the filter's gain says nothing about the rate of plain sweeps
-            sweeps_since = 0;
-            continue;
-        }
-        if (r_last < INFINITY && sweeps_since > 0 && r < r_last) rate_meas = std::pow(r / r_last, 1.0 / sweeps_since);
-        double rate = rate_meas > 0.0 ? rate_meas : std::pow(ratio < 1.0 ? ratio : 1.0, (double)o.power);
-        if (!(rate > 1e-8)) rate = 1e-8;
-        if (rate > 0.9) rate = 0.9;
-        int m = (int)std::ceil(std::log(o.tol / r) / std::log(rate) - 1e-9);
-        if (m < 1) m = 1;
-        if (m > 6) m = 6;
-        if (iters + m > o.max_iter) m = o.max_iter - iters;
-        iters += m - 1;
-        slot = (slot + 1) % kSlots;
-        {
-            const bool with_adv = !first;      // the first step's half-sweep was queued speculatively
-            char kn[64];
-            snprintf(kn, sizeof kn, "|next a%d m%d s%d", with_adv ? 1 : 0, m, slot);
-            SRX_TRY(graphed(ctx, use_graph, key_base + kn, [&]() { return seg_next(with_adv, m, slot); }));
-        }
+
+    // `resume`: the block is the one a one-round plan just left at its FIRST Ritz step (flat tail: bailed_first), with the
+    // speculative first filter step already queued behind it — W, A2 = Ritz vectors, theta, A1 = Y1, Wp = C Y1, the Ritz tail's
+    // partial sums: everything this round's own start segment (start block, warm-up sweeps, first Ritz step: ~0.45 ms at k =
+    // 1000) would recompute, for the same 64-column block.  Only the step's scalars are re-made for this round's n_pc.
+    int32_t run(bool resume, IterResult& res) {
+        const bool cheb = l_act > o.n_pc && !o.robust && !o.direct;      // both solvers: the filter only needs `apply`
+        res = IterResult{};
+        int n_ritz = 0, slot = 0;
+        int q_applied = o.warm * o.power + 1;          // applications of C the block has seen (warm-up + first Ritz step)
+        double r_last = INFINITY, rate_meas = 0.0;
+        int sweeps_since = 0;
+        if (resume) SRX_TRY(resid_final(slot));
+        else SRX_TRY(segment("|start", [&] { return seg_start(); }));
         SRX_TRY(ritz_readback(slot));
-        r_last = r;
-        sweeps_since = m;
+        for (;;) {
+            ++res.iters;
+            const bool first = ++n_ritz == 1;
+            if (cheb && first) {
+                if (!resume) SRX_TRY(segment("|cheb0", [&] { return cheb_spec(); }));   // speculative: Y1, C Y1 (resume: already there)
+            } else if (first && !o.direct) SRX_TRY(segment("|adv", [&] { return advance(); }));   // speculative: completes this sweep
+            double r, ratio;
+            SRX_TRY(collect(slot, r, ratio));
+            res.resid = r;
+            if (env.trace) trace_step(res.iters + o.warm, n_ritz, slot, r, ratio);
+            if (r <= o.tol) {
+                res.converged = true;
+                break;
+            }
+            if (res.iters >= o.max_iter) break;
+            if (step_bails(first, o.bail_ratio, ratio)) {
+                if (env.trace) fprintf(stderr, "[srx pca] flat tail (theta_l / theta_npc = %.3f): leaving the round to the safe plan\n", ratio);
+                res.bailed_first = cheb;           // (the block and the queued first filter step are the next plan's to continue from)
+                break;                             // converged stays false
+            }
+            char kn[64];
+            if (cheb) {
+                const ChebDegrees c = cheb_degrees(r, o.tol, ratio, spread, q_applied);
+                count_filter(c.d, c.d2, o.power, q_applied, res.iters);
+                slot = (slot + 1) % kSlots;
+                snprintf(kn, sizeof kn, "|cheb f%d d%d e%d s%d", first ? 1 : 0, c.d, c.d2, slot);
+                SRX_TRY(segment(kn, [&]() -> int32_t {
+                    if (!first) SRX_TRY(cheb_spec());      // later rounds: nothing was queued speculatively
+                    return cheb_rest(c.d, c.d2, slot);
+                }));
+                SRX_TRY(ritz_readback(slot));
+                if (env.trace && c.d2)
+                    fprintf(stderr, "[srx pca] Chebyshev filters of degree %d and %d, a CholeskyQR between them (t_a = %.3f)\n", c.d, c.d2, c.ta);
+                else if (env.trace) fprintf(stderr, "[srx pca] Chebyshev filter of degree %d (t_a = %.3f)\n", c.d, c.ta);
+                r_last = INFINITY;                 // the filter's gain says nothing about the rate of plain sweeps
+                sweeps_since = 0;
+                continue;
+            }
+            if (const double rm = measured_rate(r, r_last, sweeps_since); rm >= 0.0) rate_meas = rm;
+            const int m = plain_sweeps(r, o.tol, ratio, o.power, rate_meas, res.iters, o.max_iter);
+            res.iters += m - 1;
+            slot = (slot + 1) % kSlots;
+            const bool with_adv = !first;          // the first step's half-sweep was queued speculatively
+            snprintf(kn, sizeof kn, "|next a%d m%d s%d", with_adv ? 1 : 0, m, slot);
+            SRX_TRY(segment(kn, [&] { return seg_next(with_adv, m, slot); }));
+            SRX_TRY(ritz_readback(slot));
+            r_last = r;
+            sweeps_since = m;
+        }
+        return SRX_OK;
     }
-    return SRX_OK;
-}
-
-// Components per deflation round when more than L - 8 are asked of a k > L problem (the block keeps 16 guard
-// columns), and the number of rounds; the last round takes everything that is left once <= L dimensions remain.
-constexpr int kPcaPerRound = 48;
-constexpr int kPcaPerRoundSafe = 32;       // the fallback plan: >= 32 guard columns per round (c2, 1000 HVGs, 50 components:
-                                           // 12 -> 19.6 ms, 16 -> 16.3, 24 -> 15.5, 32 -> 10.7)
-// Components per round when at most `per` are asked of one round.
-static std::vector<int> plan_rounds(int k /* dimension of the operator's range */, int n_pc, int per) {
-    std::vector<int> counts;
-    if (k <= L) {                            // the block spans the whole range: one exact round
-        counts.push_back(n_pc);
-        return counts;
-    }
-    int done = 0;
-    while (done < n_pc) {
-        const int take = (k - done <= L) ? n_pc - done : std::min(per, n_pc - done);
-        counts.push_back(take);
-        done += take;
-    }
-    return counts;
-}
+};
 
 // M (64 x 64, row-major) <- diag(s) M: row r scaled by s[r]
 __global__ void k_scale_rows(double* __restrict__ M, const double* __restrict__ s) {
@@ -715,15 +644,11 @@ __global__ void k_deflate(double* __restrict__ C, int k, const double* __restric
 int scores_ld(int n_pc) {
     return (n_pc + 15) / 16 * 16;            // (c3, n_pc = 50: the forward SpMM 0.640 -> 0.616 ms against the dense layout)
 }
-void result_layout(uint64_t n_rows, int k, int n_pc, int dim, size_t& score_bytes, size_t& small_doubles,
-                   std::vector<int>* plan_a_out, std::vector<int>* plan_b_out) {
-    const std::vector<int> pa = plan_rounds(dim, n_pc, n_pc <= L - 8 ? n_pc : kPcaPerRound);
-    const int n_b = (n_pc + kPcaPerRoundSafe - 1) / kPcaPerRoundSafe;
-    const std::vector<int> pb = plan_rounds(dim, n_pc, (n_pc + n_b - 1) / n_b);
+void result_layout(uint64_t n_rows, int k, int n_pc, int dim, size_t& score_bytes, size_t& small_doubles, PcaPlans* plans_out) {
+    const PcaPlans plans = pca_plans(dim, n_pc, L);
     score_bytes = (n_rows ? n_rows : 1) * (size_t)scores_ld(n_pc) * 8;
-    small_doubles = PcaResultLayout(k, L, std::max(pa.size(), pb.size())).total_doubles();
-    if (plan_a_out) *plan_a_out = pa;
-    if (plan_b_out) *plan_b_out = pb;
+    small_doubles = PcaResultLayout(k, L, plans.max_rounds()).total_doubles();
+    if (plans_out) *plans_out = plans;
 }
 int32_t ensure_result_capacity(srx_ctx* ctx, srx_pca_state& st, size_t need) {
     if (st.scores_cap < need) {
@@ -736,6 +661,186 @@ int32_t ensure_result_capacity(srx_ctx* ctx, srx_pca_state& st, size_t need) {
     return SRX_OK;
 }
 
+// ---- the operator C of the iteration ------------------------------------------------------------------
+// reset() restores the undeflated operator, apply(Win, Wout, out_zeroed) enqueues Wout = C Win, deflate(n_r) removes the
+// eigenpairs a round has resolved (w.A2 / w.dTheta, leading n_r columns); key() names the operator in the graph cache.
+
+// explicit Gram: G = A^T A once (all-reduced, the packed triangle Pk), C = D (G - c N mu mu^T) D dense
+struct GramOperator {
+    static constexpr bool graphable = true;
+    static constexpr bool accumulates = true;       // the dense application accumulates into a zeroed block; w.T is free
+    srx_ctx* ctx;
+    const Work& w;                                  // (w.d, w.mu: the scaling and centring vectors)
+    int k, center;
+    double n_cells;
+    const double* Pk;
+    double* C;
+    const void* key() const { return C; }
+    int32_t reset() {
+        hipLaunchKernelGGL(k_gram_expand, dim3((unsigned)(((size_t)k * k + 255) / 256)), dim3(256), 0, ctx->stream, Pk,
+                           k, (const double*)w.d, (const double*)w.mu, center, n_cells, C);
+        SRX_HIP(ctx, hipGetLastError());
+        return SRX_OK;
+    }
+    int32_t apply(const double* Win, double* Wout, bool out_zeroed) {
+        ProfScope ps(ctx, SRX_K_DENSE, (double)k * k * 8.0 + 2.0 * k * L * 8.0);
+        if (!out_zeroed) SRX_HIP(ctx, hipMemsetAsync(Wout, 0, (size_t)k * L * 8, ctx->stream));
+        launch_dense_apply(ctx, C, Win, k, Wout);
+        SRX_HIP(ctx, hipGetLastError());
+        return SRX_OK;
+    }
+    int32_t deflate(int n_r) {                      // C -= V diag(theta) V^T
+        hipLaunchKernelGGL(k_deflate, dim3((unsigned)(((size_t)k * k + 255) / 256)), dim3(256), 0, ctx->stream, C, k,
+                           (const double*)w.A2, (const double*)w.dTheta, n_r);
+        SRX_HIP(ctx, hipGetLastError());
+        return SRX_OK;
+    }
+};
+
+// matrix-free: Z^T (Z W) by a forward and a transposed SpMM; resolved eigenpairs are deflated IMPLICITLY,
+// W' -= V_lock (theta_lock * (V_lock^T W)) with the locked vectors in a k x 64 block (plan B locks <= 48)
+template <typename VT, typename PT>
+struct MatrixFreeOperator {
+    static constexpr bool graphable = false;        // (the exchange of apply is a collective)
+    static constexpr bool accumulates = false;      // apply overwrites its destination and uses w.T itself
+    srx_ctx* ctx;
+    const Work& w;
+    int k, center;
+    const Tiled& t256;
+    const RowMajor& rows;
+    PT *P, *cvec, *Y;
+    double *v_lock, *th_lock;
+    int n_lock = 0;
+    const void* key() const { return nullptr; }
+    int32_t reset() {
+        n_lock = 0;
+        SRX_HIP(ctx, hipMemsetAsync(v_lock, 0, ((size_t)k * L + L) * 8, ctx->stream));
+        return SRX_OK;
+    }
+    int32_t apply(const double* Win, double* Wout, bool) {
+        const size_t kl = (size_t)k * L;
+        hipLaunchKernelGGL((k_make_panel<PT>), dim3(1), dim3(1024), 0, ctx->stream, Win, w.d, w.mu,
+                           (const double*)nullptr, k, center, P, cvec);
+        SRX_HIP(ctx, hipGetLastError());
+        // forward product: the row-major batch-stream kernel where its widest slice (8 f64 columns of all k genes: k <= 2559)
+        // fits the LDS — 8 passes over the records, 1.48 against 2.45 ms per application at c3 for the tile-major kernel,
+        // which reads the matrix once whatever k is and stays the route beyond (narrower slices mean 16+ passes)
+        if (rows.pk && fwd_rows_q<PT>(k) >= 2)
+            SRX_TRY((launch_fwd_rows<VT, PT>(ctx, rows, P, cvec, L, (double*)nullptr, Y, L)));
+        else SRX_TRY((launch_fwd<VT, PT>(ctx, t256, P, cvec, Y)));
+        SRX_TRY((launch_t<VT, PT>(ctx, t256, Y, w.T)));
+        SRX_TRY(allreduce_f64(ctx, w.T, kl + L));             // the one exchange per iteration
+        hipLaunchKernelGGL(k_finish_t, dim3((unsigned)((kl + 255) / 256)), dim3(256), 0, ctx->stream, w.T, w.d, w.mu,
+                           k, center, Wout);
+        SRX_HIP(ctx, hipGetLastError());
+        if (n_lock > 0) {
+            SRX_TRY(gram2(ctx, w, v_lock, Win, k));                               // dHG <- V_lock^T W (64 x 64)
+            hipLaunchKernelGGL(k_scale_rows, dim3((L * L + 255) / 256), dim3(256), 0, ctx->stream, w.dHG, (const double*)th_lock);
+            hipLaunchKernelGGL(k_right_mul, dim3(128), dim3(256), 0, ctx->stream, (const double*)v_lock, (const double*)w.dHG, k, w.T);
+            hipLaunchKernelGGL(k_sub_inplace, dim3((unsigned)((kl + 255) / 256)), dim3(256), 0, ctx->stream, Wout, (const double*)w.T, kl);
+            SRX_HIP(ctx, hipGetLastError());
+        }
+        return SRX_OK;
+    }
+    int32_t deflate(int n_r) {                      // the round's vectors join the locked block
+        if (n_lock + n_r > L) return fail(ctx, SRX_E_ARG, "pca: more than %d locked vectors in the matrix-free solver", L);
+        hipLaunchKernelGGL(k_lock_columns, dim3((unsigned)(((size_t)k * n_r + 255) / 256)), dim3(256), 0, ctx->stream, v_lock,
+                           th_lock, (const double*)w.A2, (const double*)w.dTheta, k, n_lock, n_r);
+        SRX_HIP(ctx, hipGetLastError());
+        n_lock += n_r;
+        return SRX_OK;
+    }
+};
+
+// ---- the solver driver: DEFLATION ROUNDS.  A round resolves the next eigenpairs with the 64-column block, writes their scores,
+// and removes them from the operator, so that the next round's dominant subspace is the one after them.
+struct Solve {                              // what the rounds of a solve share, and its running result
+    srx_ctx* ctx;
+    const Work& w;
+    int k, l_act, dim;                      // dim: dimension of the operator's range
+    const Resolved& o;
+    const int* d_status_sel;
+    srx_pca_state& st;
+    const SolveEnv env{};
+    double resid = INFINITY;
+    int iters = 0;
+    bool converged = false;
+    bool bailed_first = false;              // the last plan was left at its first Ritz step (flat tail) with its block intact
+};
+
+// Runs a plan of deflation rounds on the operator.  SRX_E_NOCONV (breakdown) or converged == false (budget spent) leave the
+// decision to the caller.
+template <typename Op, typename Finish>
+static int32_t run_plan(Solve& s, Op& op, const Finish& finish_round, const std::vector<int>& plan, int budget, bool robust,
+                        double bail = 0.0, bool resume = false) {
+    if (!resume) SRX_TRY(op.reset());     // (resume: nothing was deflated, C is as expanded)
+    s.st.round_counts = plan;             // the layout of the result block, for finish_round and every reader
+    s.resid = 0.0;
+    s.converged = true;
+    s.iters = 0;
+    int done = 0;
+    const int rounds = (int)plan.size();
+    for (int r = 0; r < rounds; ++r) {
+        const Resolved o_r = round_options(s.o, plan[r], r, budget, bail, robust);
+        const int l_r = round_width(rounds, s.l_act, L, s.dim, done);
+        IterResult res;
+        s.bailed_first = false;
+        {
+            ProfScope ps_it(s.ctx, SRX_K_ITERATE, (double)s.k * s.k * 8.0);
+            Iteration<Op> it{s.ctx, s.w, s.k, l_r, o_r, op, s.d_status_sel, s.env};
+            SRX_TRY(it.prepare());
+            SRX_TRY(it.run(resume && r == 0 && l_r == s.l_act, res));
+        }
+        s.bailed_first = res.bailed_first;
+        s.resid = std::max(s.resid, res.resid);
+        s.iters += res.iters + s.o.warm;
+        if (!res.converged) {
+            s.converged = false;
+            return SRX_OK;
+        }
+        SRX_TRY(finish_round(r, done, o_r.n_pc));
+        if (r + 1 < rounds) SRX_TRY(op.deflate(o_r.n_pc));
+        done += o_r.n_pc;
+    }
+    return SRX_OK;
+}
+
+// plan A, then plan B if it stalled or broke down, then robust mode (the policy: PcaPlans, pca_schedule.hpp)
+template <typename Op, typename Finish>
+static int32_t solve(Solve& s, Op& op, const Finish& finish_round, const PcaPlans& plans) {
+    const Resolved& o = s.o;
+    if (s.env.robust) {                                           // test switch: the last-resort mode from the start
+        SRX_TRY(run_plan(s, op, finish_round, plans.safest(), o.max_iter, true));
+        s.iters -= o.warm;
+        return SRX_OK;
+    }
+    int32_t rc = run_plan(s, op, finish_round, plans.a, plans.budget_a(o.max_iter), false, plans.bail_a());
+    if (plans.have_b() && (rc == SRX_E_NOCONV || (rc == SRX_OK && !s.converged))) {
+        if (s.env.trace)
+            fprintf(stderr, "[srx pca] plan A (%zu round(s)) %s at residual %.3e: rounds of <= %d components instead\n",
+                    plans.a.size(), rc == SRX_OK ? "stalled" : "broke down", s.resid, plans.b[0]);
+        const int spent = s.iters;
+        // (left at the first Ritz step for its flat tail: the safe plan's first round continues from that block — the same 64
+        //  columns, the same warm-up and Ritz step it would redo from a new random start)
+        const bool resume = rc == SRX_OK && s.bailed_first && plans.a.size() == 1;
+        rc = run_plan(s, op, finish_round, plans.b, o.max_iter, false, 0.0, resume);
+        s.iters += resume ? 0 : spent;
+    }
+    if (rc == SRX_E_NOCONV) {
+        // last resort: a block whose spectrum spans more than ~1e8 between two CholeskyQRs (small exact-rank
+        // problems: k = 10 features of 6 cells have theta_1 / theta_5 ~ 1e3 and a sweep is three applications)
+        if (s.env.trace) fprintf(stderr, "[srx pca] breakdown again: robust mode (CholeskyQR3 after every application)\n");
+        const int spent = s.iters;
+        rc = run_plan(s, op, finish_round, plans.safest(), o.max_iter, true);
+        s.iters += spent;
+    }
+    SRX_TRY(rc);
+    s.iters -= o.warm;                                            // st.info adds it back once
+    return SRX_OK;
+}
+
+// The solve of one matrix at the precisions <VT, PT> of its records and panels: work blocks, plans and the result allocation,
+// the operator of o.solver, the plans' rounds, st.info.
 template <typename VT, typename PT>
 static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const Tiled* t256p, double* gram_packed,
                        const Resolved& o, const SelDev& sel, int l_act, double n_cells, srx_pca_state& st, const DenseSource* dense) {
@@ -760,34 +865,19 @@ static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const T
     cvec = P + kl;
     SRX_TRY(scratch(ctx, "pca_Y", (cc.max_rows ? cc.max_rows : 1) * (size_t)L * sizeof(PT), (void**)&Y));
 
-    double resid = INFINITY;
-    int iters = 0;
-    bool converged = false;
-    // DEFLATION ROUNDS on the explicit C (Gram solver).  A round resolves the next eigenpairs with the 64-column block,
-    // writes their scores, and removes them from C (C -= V diag(theta) V^T), so that the next round's dominant
-    // subspace is the one after them.
-    //   plan A: everything in one round up to 56 components (48 per round beyond) — two Ritz steps when the spectrum
-    //           decays across the block, the normal case;
-    //   plan B: rounds of <= 32 components with 32+ guard columns each.  Taken when plan A breaks down or stalls: a flat
-    //           tail (theta_64 / theta_50 -> 1) needs Chebyshev filters of high total degree, and with the dominant
-    //           eigenvalues still in the operator (theta_1 / theta_64 ~ 20-100) a degree-12 filter amplifies the leading
-    //           directions by T_12(t_1) ~ 1e20 over the guard columns — the block collapses onto them ("Cholesky pivot
-    //           <= 0").  Once a round has deflated the leading eigenpairs the remaining spectrum is narrow and the same
-    //           filters are harmless.
-    const int n_pc = o.n_pc;
     // dimension of the operator's range: min(k, N - 1) (N when not centred); a block as wide as that is exact
     const int dim = o.direct ? k : (int)std::min<double>((double)k, n_cells - (o.center ? 1.0 : 0.0));
-    std::vector<int> plan_a, plan_b;
+    PcaPlans plans;
     size_t score_bytes, small_doubles;
-    result_layout(cc.n_rows, k, n_pc, dim, score_bytes, small_doubles, &plan_a, &plan_b);
+    result_layout(cc.n_rows, k, o.n_pc, dim, score_bytes, small_doubles, &plans);
     // one allocation: the scores, then the block of small results (srx_matrix_reserve_results makes it ahead of time)
     SRX_TRY(ensure_result_capacity(ctx, st, score_bytes + small_doubles * 8));
     double* const d_small = st.d_scores + score_bytes / 8;
-    // A2 = W U are the Ritz vectors (ascending-gene row order); sign: largest-|.| entry positive.
-    // scores = Z V (transform, pca/mod.rs:156-185): one forward SpMM per row tile with the panel D V, the f64 scores
-    // written by the SpMM itself.  The Ritz vectors, values and signs move out of the (per-context) scratch into
-    // the matrix's own block; their host copies are made by the first fetch (pca_materialize).
-    auto finish_round = [&](int r, int col0, int n_r) -> int32_t {
+    // The end of round r, which resolved components [col0, col0 + n_r).  A2 = W U are the Ritz vectors (ascending-gene row order);
+    // sign: largest-|.| entry positive.  scores = Z V (transform, pca/mod.rs:156-185): one forward SpMM per row tile with the panel
+    // D V, the f64 scores written by the SpMM itself.  The Ritz vectors, values and signs move out of the (per-context) scratch
+    // into the matrix's own block; their host copies are made by the first fetch (pca_materialize).
+    const auto finish_round = [&](int r, int col0, int n_r) -> int32_t {
         // signs, panel, centring partials and the copy of (Ritz vectors, values, signs) into the result block: one pass
         const PcaResultLayout lay(k, L, st.round_counts);
         hipLaunchKernelGGL((k_make_panel_mb<PT>), dim3(kPanelBlocks), dim3(1024), 0, ctx->stream, (const double*)w.A2, (const double*)w.d,
@@ -798,7 +888,7 @@ static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const T
         // scores = Z V: the transform from the row-major records, one launch per row tile (the tile-major kernel — 1.22 ms
         // at c3 against 0.84 — when its view was made: the matrix-free solver)
         uint64_t row0 = 0;
-        const int ld_s = scores_ld(n_pc);
+        const int ld_s = scores_ld(o.n_pc);
         if (dense) {                            // the dense source writes its own scores from the panel
             if constexpr (std::is_same_v<PT, double>) SRX_TRY(dense->write_scores(P, cvec, col0, n_r, st.d_scores, ld_s));
             else return fail(ctx, SRX_E_ARG, "pca: a dense source is solved in f64");
@@ -812,91 +902,8 @@ static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const T
         }
         return SRX_OK;
     };
-    // Runs a plan of deflation rounds with the solver's `apply`; `reset` restores the undeflated operator, `deflate`
-    // removes the eigenpairs a round has resolved (w.A2 / w.dTheta, leading n columns).  SRX_E_NOCONV (breakdown) or
-    // converged == false (budget spent) leave the decision to the caller.
-    const bool acc_apply = o.solver == 1;            // the dense application accumulates into a zeroed block; w.T is free
-    bool bailed_first = false;               // the last plan was left at its first Ritz step (flat tail) with its block intact
-    auto run_plan = [&](const std::vector<int>& plan, int budget, bool robust, auto& apply, const void* apply_id, bool graphable,
-                        auto& reset, auto& deflate, double bail = 0.0, bool resume = false) -> int32_t {
-        if (!resume) SRX_TRY(reset());      // (resume: nothing was deflated, C is as expanded)
-        st.round_counts = plan;             // the layout of the result block, for finish_round and every reader
-        resid = 0.0;
-        converged = true;
-        iters = 0;
-        int done = 0;
-        const int rounds = (int)plan.size();
-        for (int r = 0; r < rounds; ++r) {
-            Resolved o_r = o;
-            o_r.n_pc = plan[r];
-            o_r.max_iter = budget;
-            o_r.seed = o.seed + (uint64_t)r;
-            o_r.bail_ratio = bail;
-            if (robust) {                       // CholeskyQR after every application, the same number of applications up front
-                o_r.robust = true;
-                o_r.warm = o.warm * o.power;
-                o_r.power = 1;
-                o_r.max_iter = budget * o.power;
-            }
-            const int l_r = rounds == 1 ? l_act : std::min(L, dim - done);        // dim - done: what is still in the operator
-            double resid_r = INFINITY;
-            int iters_r = 0;
-            bool conv_r = false;
-            {
-                ProfScope ps_it(ctx, SRX_K_ITERATE, (double)k * k * 8.0);
-                SRX_TRY(subspace_iterate(ctx, w, k, l_r, o_r, apply, apply_id, graphable, sel.d_status, resid_r,
-                                         iters_r, conv_r, acc_apply, resume && r == 0 && l_r == l_act, &bailed_first));
-            }
-            resid = std::max(resid, resid_r);
-            iters += iters_r + o.warm;
-            if (!conv_r) {
-                converged = false;
-                return SRX_OK;
-            }
-            SRX_TRY(finish_round(r, done, o_r.n_pc));
-            if (r + 1 < rounds) SRX_TRY(deflate(done, o_r.n_pc));
-            done += o_r.n_pc;
-        }
-        return SRX_OK;
-    };
-    // plan A, then plan B if it stalled or broke down.  One round for everything gets a short budget before the safe
-    // plan takes over; a plan A that already deflates (n_pc > 56) keeps the full one.
-    auto solve = [&](auto& apply, const void* apply_id, bool graphable, auto& reset, auto& deflate) -> int32_t {
-        const bool have_b = plan_b.size() > plan_a.size();
-        if (getenv("SRX_PCA_ROBUST")) {                               // test switch: the last-resort mode from the start
-            SRX_TRY(run_plan(have_b ? plan_b : plan_a, o.max_iter, true, apply, apply_id, graphable, reset, deflate));
-            iters -= o.warm;
-            return SRX_OK;
-        }
-        // (a one-round plan A is also given up at once when its first Ritz step shows a flat tail, theta_64 / theta_npc >
-        //  0.93: such a round needs a total filter degree of 45+ and plan B gets there sooner)
-        int32_t rc = run_plan(plan_a, have_b && plan_a.size() == 1 ? std::min(o.max_iter, 40) : o.max_iter, false, apply, apply_id,
-                              graphable, reset, deflate, have_b && plan_a.size() == 1 ? 0.93 : 0.0);
-        if (have_b && (rc == SRX_E_NOCONV || (rc == SRX_OK && !converged))) {
-            if (getenv("SRX_PCA_TRACE"))
-                fprintf(stderr, "[srx pca] plan A (%zu round(s)) %s at residual %.3e: rounds of <= %d components instead\n",
-                        plan_a.size(), rc == SRX_OK ? "stalled" : "broke down", resid, plan_b[0]);
-            const int spent = iters;
-            // (left at the first Ritz step for its flat tail: the safe plan's first round continues from that block — the same 64
-            //  columns, the same warm-up and Ritz step it would redo from a new random start)
-            const bool resume = rc == SRX_OK && bailed_first && plan_a.size() == 1;
-            rc = run_plan(plan_b, o.max_iter, false, apply, apply_id, graphable, reset, deflate, 0.0, resume);
-            iters += resume ? 0 : spent;
-        }
-        if (rc == SRX_E_NOCONV) {
-            // last resort: a block whose spectrum spans more than ~1e8 between two CholeskyQRs (small exact-rank
-            // problems: k = 10 features of 6 cells have theta_1 / theta_5 ~ 1e3 and a sweep is three applications)
-            if (getenv("SRX_PCA_TRACE")) fprintf(stderr, "[srx pca] breakdown again: robust mode (CholeskyQR3 after every application)\n");
-            const int spent = iters;
-            rc = run_plan(have_b ? plan_b : plan_a, o.max_iter, true, apply, apply_id, graphable, reset, deflate);
-            iters += spent;
-        }
-        SRX_TRY(rc);
-        iters -= o.warm;                                              // st.info adds it back once below
-        return SRX_OK;
-    };
+    Solve s{ctx, w, k, l_act, dim, o, sel.d_status, st};
     if (o.solver == 1) {
-        // explicit Gram: G = A^T A once (all-reduced), C = D (G - c N mu mu^T) D dense
         double* C;
         SRX_TRY(scratch(ctx, "pca_C", (size_t)k * k * 8, (void**)&C));
         double* Pk = gram_packed;
@@ -910,83 +917,24 @@ static int32_t run_pca(srx_ctx* ctx, const RowMajor* parts, int n_parts, const T
         } else if (!dense) {
             SRX_TRY(allreduce_f64(ctx, Pk, n_packed));            // the one exchange of this solver: the packed upper triangle
         }
-        auto reset = [&]() -> int32_t {
-            hipLaunchKernelGGL(k_gram_expand, dim3((unsigned)(((size_t)k * k + 255) / 256)), dim3(256), 0, ctx->stream, Pk,
-                               k, (const double*)w.d, (const double*)w.mu, o.center, n_cells, C);
-            SRX_HIP(ctx, hipGetLastError());
-            return SRX_OK;
-        };
-        auto apply = [&](const double* Win, double* Wout, bool out_zeroed) -> int32_t {
-            ProfScope ps(ctx, SRX_K_DENSE, (double)k * k * 8.0 + 2.0 * k * L * 8.0);
-            if (!out_zeroed) SRX_HIP(ctx, hipMemsetAsync(Wout, 0, kl * 8, ctx->stream));
-            launch_dense_apply(ctx, C, Win, k, Wout);
-            SRX_HIP(ctx, hipGetLastError());
-            return SRX_OK;
-        };
-        auto deflate = [&](int, int n_r) -> int32_t {                  // C -= V diag(theta) V^T
-            hipLaunchKernelGGL(k_deflate, dim3((unsigned)(((size_t)k * k + 255) / 256)), dim3(256), 0, ctx->stream, C, k,
-                               (const double*)w.A2, (const double*)w.dTheta, n_r);
-            SRX_HIP(ctx, hipGetLastError());
-            return SRX_OK;
-        };
+        GramOperator op{ctx, w, k, o.center, n_cells, Pk, C};
         Range r_("srx:iterate");
         SRX_TRY(attr_dense_apply(ctx));
-        SRX_TRY(solve(apply, C, true, reset, deflate));
+        SRX_TRY(solve(s, op, finish_round, plans));
     } else {
         if (dense) return fail(ctx, SRX_E_ARG, "pca: a dense source needs the Gram solver");
         if (n_parts != 1 || !t256p) return fail(ctx, SRX_E_ARG, "pca: the SpMM solver needs the matrix resident in one piece");
-        const Tiled& t256 = *t256p;
-        // matrix-free: Z^T (Z W) by a forward and a transposed SpMM; resolved eigenpairs are deflated IMPLICITLY,
-        // W' -= V_lock (theta_lock * (V_lock^T W)) with the locked vectors in a k x 64 block (plan B locks <= 48)
         double* v_lock;
         SRX_TRY(scratch(ctx, "pca_lock", (kl + L) * 8, (void**)&v_lock));
-        double* th_lock = v_lock + kl;
-        int n_lock = 0;
-        auto reset = [&]() -> int32_t {
-            n_lock = 0;
-            SRX_HIP(ctx, hipMemsetAsync(v_lock, 0, (kl + L) * 8, ctx->stream));
-            return SRX_OK;
-        };
-        auto apply = [&](const double* Win, double* Wout, bool) -> int32_t {
-            hipLaunchKernelGGL((k_make_panel<PT>), dim3(1), dim3(1024), 0, ctx->stream, Win, w.d, w.mu,
-                               (const double*)nullptr, k, o.center, P, cvec);
-            SRX_HIP(ctx, hipGetLastError());
-            // forward product: the row-major batch-stream kernel where its widest slice (8 f64 columns of all k genes: k <= 2559)
-            // fits the LDS — 8 passes over the records, 1.48 against 2.45 ms per application at c3 for the tile-major kernel,
-            // which reads the matrix once whatever k is and stays the route beyond (narrower slices mean 16+ passes)
-            if (parts[0].pk && fwd_rows_q<PT>(k) >= 2)
-                SRX_TRY((launch_fwd_rows<VT, PT>(ctx, parts[0], P, cvec, L, (double*)nullptr, Y, L)));
-            else SRX_TRY((launch_fwd<VT, PT>(ctx, t256, P, cvec, Y)));
-            SRX_TRY((launch_t<VT, PT>(ctx, t256, Y, w.T)));
-            SRX_TRY(allreduce_f64(ctx, w.T, kl + L));             // the one exchange per iteration
-            hipLaunchKernelGGL(k_finish_t, dim3((unsigned)((kl + 255) / 256)), dim3(256), 0, ctx->stream, w.T, w.d, w.mu,
-                               k, o.center, Wout);
-            SRX_HIP(ctx, hipGetLastError());
-            if (n_lock > 0) {
-                SRX_TRY(gram2(ctx, w, v_lock, Win, k));                               // dHG <- V_lock^T W (64 x 64)
-                hipLaunchKernelGGL(k_scale_rows, dim3((L * L + 255) / 256), dim3(256), 0, ctx->stream, w.dHG, (const double*)th_lock);
-                hipLaunchKernelGGL(k_right_mul, dim3(128), dim3(256), 0, ctx->stream, (const double*)v_lock, (const double*)w.dHG, k, w.T);
-                hipLaunchKernelGGL(k_sub_inplace, dim3((unsigned)((kl + 255) / 256)), dim3(256), 0, ctx->stream, Wout, (const double*)w.T, kl);
-                SRX_HIP(ctx, hipGetLastError());
-            }
-            return SRX_OK;
-        };
-        auto deflate = [&](int, int n_r) -> int32_t {                  // the round's vectors join the locked block
-            if (n_lock + n_r > L) return fail(ctx, SRX_E_ARG, "pca: more than %d locked vectors in the matrix-free solver", L);
-            hipLaunchKernelGGL(k_lock_columns, dim3((unsigned)(((size_t)k * n_r + 255) / 256)), dim3(256), 0, ctx->stream, v_lock,
-                               th_lock, (const double*)w.A2, (const double*)w.dTheta, k, n_lock, n_r);
-            SRX_HIP(ctx, hipGetLastError());
-            n_lock += n_r;
-            return SRX_OK;
-        };
-        SRX_TRY(solve(apply, nullptr, false, reset, deflate));
+        MatrixFreeOperator<VT, PT> op{ctx, w, k, o.center, *t256p, parts[0], P, cvec, Y, v_lock, v_lock + kl};
+        SRX_TRY(solve(s, op, finish_round, plans));
     }
     st.d_small = d_small;
-    st.info.n_iter = (uint32_t)(iters + o.warm);
-    st.info.residual = resid;
-    if (!converged)
+    st.info.n_iter = (uint32_t)(s.iters + o.warm);
+    st.info.residual = s.resid;
+    if (!s.converged)
         return fail(ctx, SRX_E_NOCONV, "pca: subspace iteration stopped at max_iter=%d with residual %.3e > tol %.3e",
-                    o.max_iter, resid, o.tol);
+                    o.max_iter, s.resid, o.tol);
     return SRX_OK;
 }
 
@@ -1156,7 +1104,7 @@ int32_t srx_spmm(srx_mat* m, const uint64_t* sel, uint64_t k64, const double* pa
 }
 
 // Kernel-level entry point of the dense iteration (test and diagnostics: no stability promise): one operation of
-// subspace_iterate on host arrays, through the solver's own launch_* functions, in fresh device buffers of exactly the stated
+// Iteration on host arrays, through the solver's own launch_* functions, in fresh device buffers of exactly the stated
 // sizes (a k x 64 block: k + 8 rows, the last 8 a sentinel that must come back untouched).
 namespace {
 constexpr int kItTail = 8;
