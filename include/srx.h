@@ -1429,6 +1429,77 @@ int32_t srx_dpt(srx_graph* g, uint64_t root, double cap, double* pseudotime_out)
 int32_t srx_dpt_from(srx_ctx* ctx, const double* evals, const double* evecs, uint64_t n, uint32_t m, uint64_t root, double cap,
                      double* pseudotime_out);
 
+/* ---- PAGA: the neighbour graph coarse-grained over the groups; what sc.tl.paga gives uns["paga"] -----------------------------
+ * Not in the reference.  This is scanpy's model="v1.2" (_compute_connectivities_v1_2, _get_connectivities_tree_v1_2) RESTATED
+ * below so that the result is exact and bit-identical from call to call.  The definition here is what is tested.  The output
+ * has NOT been compared with scanpy (scanpy is not installed where this was built).
+ *
+ * Input: a directed pattern P as CSR (u64 indptr of n + 1, u32 indices, n < 2^32) and one label < n_groups per row,
+ *   1 <= n_groups <= SRX_GROUPS_MAX.  For a handle P is D: n k entries, no diagonal.  Every stored entry (i, j) counts once,
+ *   whatever its value and however often the pair is stored; a diagonal entry is an edge inside its group; rows need not be
+ *   sorted.  A row holds fewer than 2^22 entries (a workgroup counts its rows' targets in 32-bit counters).
+ * Counts, all integers in u64:
+ *   n_g = the number of rows with label g,  N = n;
+ *   E[g][h] = the number of stored entries with label_i = g and label_j = h, the diagonal g = h included;
+ *   es_g = sum over h of E[g][h];   V[g][h] = E[g][h] + E[h][g] for g != h,  V[g][g] = 0.
+ * Null model and connectivity, only where V[g][h] > 0 (every other entry of both tables is +0.0):
+ *   num = es_g n_h + es_h n_g, formed exactly as an integer (128 bits: it can need 73);
+ *   expected[g][h] = (double)num / (double)(N - 1)          (one rounding per conversion, one for the quotient)
+ *   r = (double)V[g][h] / expected[g][h];   conn[g][h] = r > 1 ? 1.0 : r.
+ *   Both tables are symmetric in the same bits.  V > 0 implies two non-empty groups, hence N >= 2.
+ * Tree: the spanning forest that Kruskal's algorithm builds from the unordered pairs g < h with conn > 0, taken in the order
+ *   (conn descending, g ascending, h ascending).  tree[g][h] = conn[g][h] for the chosen pairs, stored at g < h only; every
+ *   other entry is 0.  (Clipping makes conn == 1.0 common, so the tie rule decides much of the tree.)
+ * n == 0 gives all-zero tables with components = n_groups.
+ * Start positions (scanpy's get_init_pos_from_paga with a hash in place of numpy's generator).  pos is n_groups x dim f64, the
+ * caller's coarse layout, dim 2 or 3.  Per group g: nb(g) = the h with the largest conn[g][h] > 0, ties to the lowest h;
+ *   dist_c = pos[g][c] - pos[nb][c].  For cell i of group g and coordinate c:
+ *   u = (mix(seed + 0x9E3779B97F4A7C15 * (i * dim + c + 1)) >> 11) * 2^-53          (mix: the UMAP section's)
+ *   y = (pos[g][c] - 0.5 * dist_c) + (u - 0.5) * dist_c        (f64, every operation rounded once, no FMA contraction)
+ *   A group without a neighbour puts its cells exactly on pos[g].  The result is what srx_umap takes as SRX_UMAP_INIT_GIVEN.
+ * Refusals, each SRX_E_ARG with a message and nothing written: a NULL handle or context where one is needed; n_groups outside
+ *   1 .. SRX_GROUPS_MAX; a label >= n_groups (found on the device); labels == NULL on a handle that holds none; an index >= n;
+ *   an indptr that does not start at 0 or that decreases; a row of 2^22 entries or more; n >= 2^32; a context with more than
+ *   one rank; for srx_paga_from_counts NULL counts or sizes, or a non-zero count in a row or column of a group of size 0; for
+ *   srx_paga_init_positions dim not 2 or 3, a NaN or Inf in pos or connectivities, NULL out with n > 0, n other than the
+ *   handle's.
+ * Out of scope: model="v1.0", RNA-velocity transitions, the coarse layout itself (scanpy's pl.paga), sharded contexts. */
+typedef struct srx_paga_info {
+    uint64_t n, nnz;
+    uint32_t n_groups, groups_empty;
+    uint64_t edges_inner, edges_inter;      /* the sum of E's diagonal, and the rest: the two sum to nnz               */
+    uint64_t pairs_connected;               /* unordered pairs g < h with V > 0                                        */
+    uint64_t pairs_clipped;                 /* ... of them, those with r > 1                                           */
+    uint32_t tree_edges;
+    uint32_t components;                    /* of the graph conn > 0 over all n_groups vertices: an empty group is one of
+                                               its own; tree_edges = n_groups - components                             */
+    double   ms;                            /* hipEvent time of the device work (0 from srx_paga_from_counts)          */
+} srx_paga_info;
+typedef struct srx_paga_tables {   /* host buffers, each may be NULL */
+    uint64_t* sizes;          /* n_groups                 */
+    uint64_t* out_edges;      /* n_groups: es             */
+    uint64_t* counts;         /* n_groups x n_groups: E   */
+    double*   connectivities; /* n_groups x n_groups, row-major, like the two below */
+    double*   expected;
+    double*   tree;
+} srx_paga_tables;
+/* The handle's D, read where it lies: the handle, its C, labels, embedding and diffusion map stay untouched.  labels == NULL:
+ * the labels the last srx_louvain left on g, read on the device (n_groups is then srx_louvain_info.n_communities or more);
+ * else n host u32, uploaded and checked on the device.  t and info may be NULL. */
+int32_t srx_paga(srx_graph* g, const uint32_t* labels, uint32_t n_groups, srx_paga_tables* t, srx_paga_info* info);
+/* The same on any pattern. */
+int32_t srx_paga_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* indices, uint64_t n, const uint32_t* labels,
+                     uint32_t n_groups, srx_paga_tables* t, srx_paga_info* info);
+/* Everything after the counts, from E (n_groups x n_groups) and the sizes: out_edges, the three f64 tables, the tree and the
+ * counters; n is the sum of the sizes and nnz the sum of counts.  Host only: it needs no GPU, and the two calls above end in
+ * it.  t->sizes and t->counts receive copies of the input. */
+int32_t srx_paga_from_counts(const uint64_t* counts, const uint64_t* sizes, uint32_t n_groups, srx_paga_tables* t,
+                             srx_paga_info* info);
+/* The start positions (n x dim f64, row-major, host).  g != NULL && labels == NULL: the handle's labels; ctx may be NULL with a
+ * handle (its context is used).  connectivities: n_groups x n_groups as srx_paga gives them. */
+int32_t srx_paga_init_positions(srx_graph* g, srx_ctx* ctx, const uint32_t* labels, uint64_t n, uint32_t n_groups,
+                                const double* connectivities, const double* pos, uint32_t dim, uint64_t seed, double* out);
+
 /* ---- Harmony: batch integration of the PCA scores, what sc.external.pp.harmony_integrate gives obsm["X_pca_harmony"] --------
  * Not in the reference.  This is Harmony (Korsunsky et al. 2019) as harmonypy runs it for ONE batch covariate, RESTATED below
  * with its random choices replaced by hashes so that the result is bit-identical from call to call.  The definition here is

@@ -1154,6 +1154,91 @@ pub mod processing_free {
             c.check(unsafe { srx_graph_labels_fetch(g, labels.as_mut_ptr()) })?;
             Ok(labels)
         }
+        /// What PAGA gives `uns["paga"]`: the tables are `n_groups x n_groups`, row-major; `tree` holds its edges at g < h.
+        pub struct Paga {
+            pub n_groups: usize,
+            pub sizes: Vec<u64>,
+            pub out_edges: Vec<u64>,
+            pub counts: Vec<u64>,
+            pub connectivities: Vec<f64>,
+            pub expected: Vec<f64>,
+            pub tree: Vec<f64>,
+            pub info: SrxPagaInfo,
+        }
+        /// The buffers of one call: `run` receives the `SrxPagaTables` that points at them and the info to fill.
+        fn paga_call(n_groups: usize, run: impl FnOnce(*mut SrxPagaTables, *mut SrxPagaInfo) -> anyhow::Result<()>)
+                     -> anyhow::Result<Paga> {
+            let gg = n_groups * n_groups;
+            let mut p = Paga { n_groups, sizes: vec![0; n_groups], out_edges: vec![0; n_groups], counts: vec![0; gg],
+                               connectivities: vec![0.0; gg], expected: vec![0.0; gg], tree: vec![0.0; gg],
+                               info: unsafe { std::mem::zeroed() } };
+            let mut t = SrxPagaTables { sizes: p.sizes.as_mut_ptr(), out_edges: p.out_edges.as_mut_ptr(), counts: p.counts.as_mut_ptr(),
+                                        connectivities: p.connectivities.as_mut_ptr(), expected: p.expected.as_mut_ptr(),
+                                        tree: p.tree.as_mut_ptr() };
+            run(&mut t, &mut p.info)?;
+            Ok(p)
+        }
+        /// PAGA of the cells' k-NN graph over the communities Louvain finds on it (srx_neighbors_result, srx_louvain, then
+        /// srx_paga with the labels where they lie): nothing but the `n_groups x n_groups` tables and the labels comes back.
+        pub fn paga(adata: &IMAnnData, resolution: f64, n_neighbors: usize, n_pcs: usize) -> anyhow::Result<(Vec<u32>, Paga)> {
+            let kopts = SrxKnnOpts { k: n_neighbors as i32, n_dims: n_pcs as i32, include_self: 0, reserved: 0 };
+            let lopts = SrxLouvainOpts { resolution, min_gain: 0.0, max_levels: 0, max_sweeps: 0 };
+            with_resident(adata, |x| {
+                let mut g: *mut SrxGraph = null_mut();
+                x.ctx.check(unsafe { srx_neighbors_result(x.mat, &kopts, null_mut(), &mut g) })?;
+                let mut ginfo: SrxGraphInfo = unsafe { std::mem::zeroed() };
+                let mut linfo: SrxLouvainInfo = unsafe { std::mem::zeroed() };
+                let out = x.ctx.check(unsafe { srx_graph_info_get(g, &mut ginfo) }).and_then(|_| {
+                    let mut labels = vec![0u32; ginfo.n as usize];
+                    x.ctx.check(unsafe { srx_louvain(g, &lopts, labels.as_mut_ptr(), &mut linfo) })?;
+                    let n_groups = (linfo.n_communities as usize).max(1);
+                    let p = paga_call(n_groups, |t, info| x.ctx.check(unsafe { srx_paga(g, std::ptr::null(), n_groups as u32, t, info) }))?;
+                    Ok((labels, p))
+                });
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        /// PAGA of any directed pattern the caller holds, one label below `n_groups` per row (srx_paga_csr).
+        pub fn paga_csr(pattern: &CsrMatrix<f64>, labels: &[u32], n_groups: usize) -> anyhow::Result<Paga> {
+            let n = pattern.nrows();
+            if labels.len() != n {
+                bail!("paga_csr: {} labels for {n} rows", labels.len());
+            }
+            let indptr: Vec<u64> = pattern.row_offsets().iter().map(|&v| v as u64).collect();
+            let indices: Vec<u32> = pattern.col_indices().iter().map(|&v| v as u32).collect();
+            with_ctx(|c| paga_call(n_groups, |t, info| {
+                c.check(unsafe { srx_paga_csr(c.0, indptr.as_ptr(), indices.as_ptr(), n as u64, labels.as_ptr(), n_groups as u32, t, info) })
+            }))
+        }
+        /// Everything after the counts (host code in the library: no device): `counts` is `n_groups x n_groups`, row-major.
+        pub fn paga_from_counts(counts: &[u64], sizes: &[u64]) -> anyhow::Result<Paga> {
+            let n_groups = sizes.len();
+            if counts.len() != n_groups * n_groups {
+                bail!("paga_from_counts: {} counts for {n_groups} groups", counts.len());
+            }
+            paga_call(n_groups, |t, info| {
+                match unsafe { srx_paga_from_counts(counts.as_ptr(), sizes.as_ptr(), n_groups as u32, t, info) } {
+                    SRX_OK => Ok(()),
+                    rc => Err(anyhow!("srx_paga_from_counts: status {rc}")),
+                }
+            })
+        }
+        /// Start positions for a layout from PAGA (srx_paga_init_positions): `pos` is the coarse layout, `n_groups x dim`;
+        /// returns `n x dim`, what `umap` takes as a given start.
+        pub fn paga_init_positions(labels: &[u32], p: &Paga, pos: &Array2<f64>, seed: u64) -> anyhow::Result<Array2<f64>> {
+            let (rows, dim) = pos.dim();
+            if rows != p.n_groups {
+                bail!("paga_init_positions: pos has {rows} rows for {} groups", p.n_groups);
+            }
+            let flat: Vec<f64> = pos.iter().copied().collect();                    // row-major
+            let mut out = vec![0.0f64; labels.len() * dim];
+            with_ctx(|c| c.check(unsafe {
+                srx_paga_init_positions(null_mut(), c.0, labels.as_ptr(), labels.len() as u64, p.n_groups as u32,
+                                        p.connectivities.as_ptr(), flat.as_ptr(), dim as u32, seed, out.as_mut_ptr())
+            }))?;
+            Array2::from_shape_vec((labels.len(), dim), out).map_err(|e| anyhow!("paga_init_positions: {e}"))
+        }
         fn graph_to_host(c: &Ctx, g: *mut SrxGraph) -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>)> {
             let mut info: SrxGraphInfo = unsafe { std::mem::zeroed() };
             c.check(unsafe { srx_graph_info_get(g, &mut info) })?;

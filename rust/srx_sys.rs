@@ -643,6 +643,33 @@ pub struct SrxDiffmapInfo {      // `srx_diffmap_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxPagaInfo {      // `srx_paga_info`
+    pub n: u64,
+    pub nnz: u64,
+    pub n_groups: u32,
+    pub groups_empty: u32,
+    pub edges_inner: u64,
+    pub edges_inter: u64,
+    pub pairs_connected: u64,
+    pub pairs_clipped: u64,
+    pub tree_edges: u32,
+    pub components: u32,
+    pub ms: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxPagaTables {      // `srx_paga_tables`
+    pub sizes: *mut u64,
+    pub out_edges: *mut u64,
+    pub counts: *mut u64,
+    pub connectivities: *mut f64,
+    pub expected: *mut f64,
+    pub tree: *mut f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxHarmonyOpts {      // `srx_harmony_opts`
     pub theta: f64,
     pub sigma: f64,
@@ -962,6 +989,14 @@ extern "C" {
     pub fn srx_dpt(g: *mut SrxGraph, root: u64, cap: f64, pseudotime_out: *mut f64) -> i32;
     pub fn srx_dpt_from(ctx: *mut SrxCtx, evals: *const f64, evecs: *const f64, n: u64, m: u32, root: u64,
                         cap: f64, pseudotime_out: *mut f64) -> i32;
+    pub fn srx_paga(g: *mut SrxGraph, labels: *const u32, n_groups: u32, t: *mut SrxPagaTables,
+                    info: *mut SrxPagaInfo) -> i32;
+    pub fn srx_paga_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, n: u64, labels: *const u32,
+                        n_groups: u32, t: *mut SrxPagaTables, info: *mut SrxPagaInfo) -> i32;
+    pub fn srx_paga_from_counts(counts: *const u64, sizes: *const u64, n_groups: u32, t: *mut SrxPagaTables,
+                                info: *mut SrxPagaInfo) -> i32;
+    pub fn srx_paga_init_positions(g: *mut SrxGraph, ctx: *mut SrxCtx, labels: *const u32, n: u64, n_groups: u32,
+                                   connectivities: *const f64, pos: *const f64, dim: u32, seed: u64, out: *mut f64) -> i32;
     pub fn srx_harmony_result(m: *mut SrxMat, batch: *const u32, n_batches: u32, opts: *const SrxHarmonyOpts,
                               out: *mut *mut SrxHarmony, info: *mut SrxHarmonyInfo) -> i32;
     pub fn srx_harmony_points(ctx: *mut SrxCtx, points: *const f64, n: u64, d: u64, batch: *const u32,

@@ -348,6 +348,17 @@ class DiffmapInfo(C.Structure):      # srx_diffmap_info
                 ("reserved_", C.c_uint32), ("max_residual", C.c_double), ("max_ortho", C.c_double), ("ms", C.c_double)]
 
 
+class PagaInfo(C.Structure):      # srx_paga_info
+    _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("n_groups", C.c_uint32), ("groups_empty", C.c_uint32),
+                ("edges_inner", C.c_uint64), ("edges_inter", C.c_uint64), ("pairs_connected", C.c_uint64),
+                ("pairs_clipped", C.c_uint64), ("tree_edges", C.c_uint32), ("components", C.c_uint32),
+                ("ms", C.c_double)]
+
+
+class PagaTables(C.Structure):      # srx_paga_tables
+    _fields_ = [("sizes", P), ("out_edges", P), ("counts", P), ("connectivities", P), ("expected", P), ("tree", P)]
+
+
 class HarmonyOpts(C.Structure):      # srx_harmony_opts
     _fields_ = [("theta", C.c_double), ("sigma", C.c_double), ("lambda_", C.c_double),
                 ("epsilon_cluster", C.c_double), ("epsilon_harmony", C.c_double), ("seed", C.c_uint64),
@@ -534,6 +545,10 @@ SIGNATURES = {
     "srx_graph_transitions_fetch": (C.c_int32, [P, P]),
     "srx_dpt": (C.c_int32, [P, C.c_uint64, C.c_double, P]),
     "srx_dpt_from": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_double, P]),
+    "srx_paga": (C.c_int32, [P, P, C.c_uint32, C.POINTER(PagaTables), C.POINTER(PagaInfo)]),
+    "srx_paga_csr": (C.c_int32, [P, P, P, C.c_uint64, P, C.c_uint32, C.POINTER(PagaTables), C.POINTER(PagaInfo)]),
+    "srx_paga_from_counts": (C.c_int32, [P, P, C.c_uint32, C.POINTER(PagaTables), C.POINTER(PagaInfo)]),
+    "srx_paga_init_positions": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, P, P, C.c_uint32, C.c_uint64, P]),
     "srx_harmony_result": (C.c_int32, [P, P, C.c_uint32, C.POINTER(HarmonyOpts), C.POINTER(P), C.POINTER(HarmonyInfo)]),
     "srx_harmony_points": (C.c_int32, [P, P, C.c_uint64, C.c_uint64, P, C.c_uint32, C.POINTER(HarmonyOpts),
                                        C.POINTER(P), C.POINTER(HarmonyInfo)]),

@@ -411,6 +411,44 @@ static uint32_t mk_chunk_groups(const srx_markers* mk) {
 
 #include "wilcoxon.inl"
 
+// ---- the counting sort as the walks over label-sorted rows call it (markers_internal.hpp) -----------------------------------
+int32_t label_sort_count(srx_ctx* ctx, const uint32_t* d_labels, uint64_t N, uint32_t n_groups, unsigned long long* d_small, uint64_t* d_sizes,
+                         LabelSort* s) {
+    hipStream_t st = ctx->stream;
+    const uint64_t n_blk = at_least_one((N + kMkSortRows - 1) / kMkSortRows);
+    const uint64_t n_tab = (uint64_t)n_groups * n_blk;
+    int64_t *d_table, *d_first;
+    uint16_t* d_rank;
+    uint32_t* d_perm;
+    SRX_TRY(scratch(ctx, "mk_table_cnt", n_tab * 8, (void**)&d_table));
+    SRX_TRY(scratch(ctx, "mk_table_first", (n_tab + 1) * 8, (void**)&d_first));
+    SRX_TRY(scratch(ctx, "mk_rank", at_least_one(N) * 2, (void**)&d_rank));
+    SRX_TRY(scratch(ctx, "mk_perm", at_least_one(N) * 4, (void**)&d_perm));
+    hipLaunchKernelGGL(k_mk_label_count, dim3((unsigned)n_blk), dim3(kMkSortRows), 0, st, d_labels, N, n_groups, n_blk, d_table, d_rank, d_small);
+    SRX_HIP(ctx, hipGetLastError());
+    SRX_TRY(scan_exclusive(ctx, d_table, n_tab, d_first, nullptr));
+    hipLaunchKernelGGL(k_mk_sizes, dim3((n_groups + 255) / 256), dim3(256), 0, st, (const int64_t*)d_first, n_groups, n_blk, d_sizes);
+    SRX_HIP(ctx, hipGetLastError());
+    *s = LabelSort{d_perm, d_first, d_rank, N, n_blk};
+    return SRX_OK;
+}
+int32_t label_sort_place(srx_ctx* ctx, const uint32_t* d_labels, const LabelSort& s) {
+    if (s.n) hipLaunchKernelGGL(k_mk_place, dim3((unsigned)s.n_blk), dim3(kMkSortRows), 0, ctx->stream, d_labels, (const uint16_t*)s.d_rank,
+                                (const int64_t*)s.d_first, s.n, s.n_blk, s.d_perm);
+    SRX_HIP(ctx, hipGetLastError());
+    return SRX_OK;
+}
+std::vector<MkBlock> label_blocks(const std::vector<uint64_t>& sizes, uint64_t rows_per_block) {
+    std::vector<MkBlock> blocks;
+    uint64_t at = 0;
+    for (uint32_t g = 0; g < (uint32_t)sizes.size(); ++g) {
+        for (uint64_t p = 0; p < sizes[g]; p += rows_per_block)
+            blocks.push_back(MkBlock{(uint32_t)(at + p), (uint32_t)(at + std::min(p + rows_per_block, sizes[g])), g, 0u});
+        at += sizes[g];
+    }
+    return blocks;
+}
+
 // The walk's launches: every (gene tile, block) pair, by value storage and index form.  d_clip null: S, Q and, unless d_C is
 // null, the counts C (a second launch over the indices alone); else the clipped sums alone.
 static int32_t mk_walk(srx_mat* m, const uint32_t* d_perm, const MkBlock* d_blocks, size_t n_blocks, double fx_sum, double fx_sq,
@@ -495,28 +533,16 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
     SRX_TRY(scratch(ctx, "mk_small", MK_WORDS * 8, (void**)&d_small));
     SRX_HIP(ctx, hipMemsetAsync(d_small, 0, MK_WORDS * 8, st));
     value_scan(m, d_small);
-    const uint64_t n_blk = at_least_one((N + kMkSortRows - 1) / kMkSortRows);
-    const uint64_t n_tab = (uint64_t)n_groups * n_blk;
-    int64_t *d_table, *d_first;
-    uint16_t* d_rank;
-    uint32_t* d_perm;
-    SRX_TRY(scratch(ctx, "mk_table_cnt", n_tab * 8, (void**)&d_table));
-    SRX_TRY(scratch(ctx, "mk_table_first", (n_tab + 1) * 8, (void**)&d_first));
-    SRX_TRY(scratch(ctx, "mk_rank", at_least_one(N) * 2, (void**)&d_rank));
-    SRX_TRY(scratch(ctx, "mk_perm", at_least_one(N) * 4, (void**)&d_perm));
-    hipLaunchKernelGGL(k_mk_label_count, dim3((unsigned)n_blk), dim3(kMkSortRows), 0, st, d_labels, N, n_groups, n_blk, d_table, d_rank, d_small);
-    SRX_HIP(ctx, hipGetLastError());
-    SRX_TRY(scan_exclusive(ctx, d_table, n_tab, d_first, nullptr));
-    hipLaunchKernelGGL(k_mk_sizes, dim3((n_groups + 255) / 256), dim3(256), 0, st, (const int64_t*)d_first, n_groups, n_blk, mk->d_sizes);
-    SRX_HIP(ctx, hipGetLastError());
+    LabelSort sort;
+    SRX_TRY(label_sort_count(ctx, d_labels, N, n_groups, d_small, mk->d_sizes, &sort));
     unsigned long long small[MK_WORDS];
     SRX_TRY(d2h(ctx, small, d_small, sizeof small));
     if (small[MK_FLAGS] & kMkBadLabel) return fail(ctx, SRX_E_ARG, "markers: a label is not below n_groups = %u", n_groups);
     if (small[MK_FLAGS] & kValNonFinite) return fail(ctx, SRX_E_NAN, "markers: a stored value is NaN or Inf");
     std::vector<uint64_t> sizes(n_groups);
     SRX_TRY(d2h(ctx, sizes.data(), mk->d_sizes, (size_t)n_groups * 8));
-    if (N) hipLaunchKernelGGL(k_mk_place, dim3((unsigned)n_blk), dim3(kMkSortRows), 0, st, d_labels, (const uint16_t*)d_rank, (const int64_t*)d_first, N, n_blk, d_perm);
-    SRX_HIP(ctx, hipGetLastError());
+    SRX_TRY(label_sort_place(ctx, d_labels, sort));
+    const uint32_t* d_perm = sort.d_perm;
 
     // the scales (srx.h): e from max_abs, no lower than -30; L = ceil(log2(max(N, 1)))
     double max_abs;
@@ -533,15 +559,7 @@ static int32_t markers_run(srx_mat* m, const uint32_t* d_labels, uint32_t n_grou
 
     // the blocks: at most rows_per_block consecutive places of ONE group each
     const uint64_t rpb = mk_rows_per_block(N, m->n_tiles);
-    std::vector<MkBlock> blocks;
-    {
-        uint64_t at = 0;
-        for (uint32_t g = 0; g < n_groups; ++g) {
-            for (uint64_t p = 0; p < sizes[g]; p += rpb)
-                blocks.push_back(MkBlock{(uint32_t)(at + p), (uint32_t)(at + std::min(p + rpb, sizes[g])), g, 0u});
-            at += sizes[g];
-        }
-    }
+    const std::vector<MkBlock> blocks = label_blocks(sizes, rpb);
     SRX_HIP(ctx, hipEventRecord(ev.e[1], st));
 
     // -- stage 2: the grouped moments and counts, the totals
@@ -662,12 +680,27 @@ int32_t markers_check(srx_mat* m, const char* what) {
     return SRX_OK;
 }
 
-int32_t markers_host_labels(srx_mat* m, const uint32_t* labels, uint32_t n_groups, const char* what, uint32_t** d_labels) {
-    srx_ctx* ctx = m->ctx;
+int32_t host_labels(srx_ctx* ctx, uint64_t n, const uint32_t* labels, uint32_t n_groups, const char* what, uint32_t** d_labels) {
     if (n_groups < 1 || n_groups > SRX_GROUPS_MAX) return fail(ctx, SRX_E_ARG, "%s: n_groups = %u is outside 1 .. %d", what, n_groups, SRX_GROUPS_MAX);
-    if (m->n_rows && !labels) return fail(ctx, SRX_E_ARG, "%s: null labels", what);
-    SRX_TRY(scratch(ctx, "mk_labels", at_least_one(m->n_rows) * 4, (void**)d_labels));
-    return h2d(ctx, *d_labels, labels, m->n_rows * 4);
+    if (n && !labels) return fail(ctx, SRX_E_ARG, "%s: null labels", what);
+    SRX_TRY(scratch(ctx, "mk_labels", at_least_one(n) * 4, (void**)d_labels));
+    return h2d(ctx, *d_labels, labels, n * 4);
+}
+int32_t markers_host_labels(srx_mat* m, const uint32_t* labels, uint32_t n_groups, const char* what, uint32_t** d_labels) {
+    return host_labels(m->ctx, m->n_rows, labels, n_groups, what, d_labels);
+}
+
+int32_t label_max(srx_ctx* ctx, const uint32_t* d_labels, uint64_t n, uint64_t* mx_out) {
+    unsigned long long* d_small;
+    SRX_TRY(scratch(ctx, "mk_small", MK_WORDS * 8, (void**)&d_small));
+    SRX_HIP(ctx, hipMemsetAsync(d_small, 0, MK_WORDS * 8, ctx->stream));
+    const unsigned grid = (unsigned)std::min<uint64_t>((at_least_one(n) + 255) / 256, (uint64_t)ctx->n_cus * 4);
+    hipLaunchKernelGGL(k_mk_label_max, dim3(grid), dim3(256), 0, ctx->stream, d_labels, n, d_small);
+    SRX_HIP(ctx, hipGetLastError());
+    unsigned long long mx = 0;
+    SRX_TRY(d2h(ctx, &mx, d_small + MK_MAXLABEL, 8));
+    *mx_out = mx;
+    return SRX_OK;
 }
 
 // the labels the last srx_louvain left on g: the handle checked against m, n_groups = the largest label + 1
@@ -679,15 +712,9 @@ static int32_t markers_graph_labels(srx_mat* m, srx_graph* g, const char* what, 
     if (g->n != m->n_rows)
         return fail(ctx, SRX_E_ARG, "%s: the graph has %llu cells, the matrix %llu rows", what, (unsigned long long)g->n, (unsigned long long)m->n_rows);
     if (!g->n) return fail(ctx, SRX_E_ARG, "%s: no cells, hence no groups", what);
-    unsigned long long* d_small;
-    SRX_TRY(scratch(ctx, "mk_small", MK_WORDS * 8, (void**)&d_small));
-    SRX_HIP(ctx, hipMemsetAsync(d_small, 0, MK_WORDS * 8, ctx->stream));
-    const unsigned grid = (unsigned)std::min<uint64_t>((g->n + 255) / 256, (uint64_t)ctx->n_cus * 4);
-    hipLaunchKernelGGL(k_mk_label_max, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t*)g->d_labels, g->n, d_small);
-    SRX_HIP(ctx, hipGetLastError());
-    unsigned long long mx = 0;
-    SRX_TRY(d2h(ctx, &mx, d_small + MK_MAXLABEL, 8));
-    if (mx >= SRX_GROUPS_MAX) return fail(ctx, SRX_E_ARG, "%s: %llu communities, more than %d groups", what, mx + 1, SRX_GROUPS_MAX);
+    uint64_t mx = 0;
+    SRX_TRY(label_max(ctx, g->d_labels, g->n, &mx));
+    if (mx >= SRX_GROUPS_MAX) return fail(ctx, SRX_E_ARG, "%s: %llu communities, more than %d groups", what, (unsigned long long)(mx + 1), SRX_GROUPS_MAX);
     *n_groups = (uint32_t)mx + 1;
     return SRX_OK;
 }

@@ -58,6 +58,27 @@ inline int fx_exponent(double max_abs) {
     return e > -30 ? e : -30;
 }
 
+// ---- rows planned by label, for every walk over label-sorted rows (markers.hip's own, hvg_seurat.hip's through the plan above,
+// paga.hip's over a graph's rows).  The stable counting sort comes in two halves, so that the caller reads d_small (MK_WORDS
+// words it zeroed; a label >= n_groups raises kMkBadLabel in word MK_FLAGS) and the sizes between them: `count` queues the
+// histograms, their scan and the group sizes (d_sizes: n_groups u64 on the device), `place` writes the permutation.  The
+// buffers are the context's scratch ("mk_perm", ...): valid until the next sort on this context.
+struct LabelSort {
+    uint32_t* d_perm = nullptr;
+    int64_t* d_first = nullptr;
+    uint16_t* d_rank = nullptr;
+    uint64_t n = 0, n_blk = 0;
+};
+int32_t label_sort_count(srx_ctx* ctx, const uint32_t* d_labels, uint64_t n, uint32_t n_groups, unsigned long long* d_small, uint64_t* d_sizes,
+                         LabelSort* s);
+int32_t label_sort_place(srx_ctx* ctx, const uint32_t* d_labels, const LabelSort& s);
+// the workgroups of a walk: at most rows_per_block consecutive places of ONE group each, groups ascending
+std::vector<MkBlock> label_blocks(const std::vector<uint64_t>& sizes, uint64_t rows_per_block);
+// n_groups checked, n host labels uploaded into the scratch buffer "mk_labels" (not yet compared with n_groups: the sort does)
+int32_t host_labels(srx_ctx* ctx, uint64_t n, const uint32_t* labels, uint32_t n_groups, const char* what, uint32_t** d_labels);
+// the largest of n labels on the device (0 for none); drains the stream
+int32_t label_max(srx_ctx* ctx, const uint32_t* d_labels, uint64_t n, uint64_t* mx);
+
 void mk_free(srx_markers* mk);
 // the refusals that need no pass over the matrix (NULL, CSC, several ranks, 2^32 - 1 rows or more); sets the device
 int32_t markers_check(srx_mat* m, const char* what);

@@ -853,6 +853,20 @@ struct Diffmap {
     std::uint32_t n_comps = 0;
     std::vector<double> evals, evecs;
 };
+// What PAGA gives uns["paga"]: the tables are n_groups x n_groups, row-major; `tree` holds its edges at g < h
+struct Paga {
+    std::uint32_t n_groups = 0;
+    std::vector<std::uint64_t> sizes, out_edges, counts;
+    std::vector<double> connectivities, expected, tree;
+    srx_paga_info info{};
+    explicit Paga(std::uint32_t G = 0)
+        : n_groups(G), sizes(G), out_edges(G), counts(static_cast<std::size_t>(G) * G), connectivities(counts.size()),
+          expected(counts.size()), tree(counts.size()) {}
+    // the buffers as the C calls take them (the vectors must not be resized while it is in use)
+    srx_paga_tables tables() {
+        return srx_paga_tables{sizes.data(), out_edges.data(), counts.data(), connectivities.data(), expected.data(), tree.data()};
+    }
+};
 class Graph {
 public:
     // k-NN over the scores the last PCA on `a` left on the device, then the graph of it (srx_neighbors_result)
@@ -931,6 +945,24 @@ public:
         ctx_->check(srx_graph_labels_fetch(h_, labels.empty() ? nullptr : labels.data()));
         return labels;
     }
+    // PAGA of the graph's D over the groups, read where it lies (srx_paga).  `labels` null: those the last louvain() left
+    // on the device, n_groups = its n_communities or more; else one host label below n_groups per cell
+    Paga paga(std::uint32_t n_groups, const std::vector<std::uint32_t>* labels = nullptr) const {
+        if (labels && labels->size() != info_n()) throw Error(SRX_E_ARG, "paga: one label per cell expected");
+        Paga p(n_groups);
+        srx_paga_tables t = p.tables();
+        ctx_->check(srx_paga(h_, labels && !labels->empty() ? labels->data() : nullptr, n_groups, &t, &p.info));
+        return p;
+    }
+    // start positions for umap() from a PAGA result and a coarse layout `pos` (n_groups x dim, row-major): n x dim
+    // (srx_paga_init_positions with the labels on the device)
+    std::vector<double> paga_init_positions(const Paga& p, const std::vector<double>& pos, std::uint32_t dim, std::uint64_t seed = 0) const {
+        if (pos.size() != static_cast<std::size_t>(p.n_groups) * dim) throw Error(SRX_E_ARG, "paga_init_positions: pos is n_groups x dim");
+        std::vector<double> out(info_n() * dim);
+        ctx_->check(srx_paga_init_positions(h_, nullptr, nullptr, info_n(), p.n_groups, p.connectivities.data(), pos.data(), dim, seed,
+                                            out.empty() ? nullptr : out.data()));
+        return out;
+    }
     // Diffusion map of the connectivities, read where they lie (srx_diffmap): the n_comps algebraically largest eigenpairs of
     // the transition operator, descending; `opts` null: the defaults; `info` (may be null) receives the call's srx_diffmap_info
     Diffmap diffmap(const srx_diffmap_opts* opts = nullptr, srx_diffmap_info* info = nullptr) const {
@@ -979,6 +1011,27 @@ inline std::vector<std::uint32_t> louvain_csr(Context& ctx, const std::vector<st
     ctx.check(srx_louvain_csr(ctx.handle(), indptr.data(), indices.empty() ? nullptr : indices.data(),
                               weights.empty() ? nullptr : weights.data(), labels.size(), &o, labels.empty() ? nullptr : labels.data(), info));
     return labels;
+}
+// PAGA of any directed pattern (CSR; every stored entry counts once) with one label below n_groups per row: srx_paga_csr
+inline Paga paga_csr(Context& ctx, const std::vector<std::uint64_t>& indptr, const std::vector<std::uint32_t>& indices,
+                     const std::vector<std::uint32_t>& labels, std::uint32_t n_groups) {
+    if (indptr.empty() || indptr.back() != indices.size() || labels.size() != indptr.size() - 1)
+        throw Error(SRX_E_ARG, "paga_csr: indptr (n + 1), indices (indptr[n]) and labels (n) expected");
+    Paga p(n_groups);
+    srx_paga_tables t = p.tables();
+    ctx.check(srx_paga_csr(ctx.handle(), indptr.data(), indices.empty() ? nullptr : indices.data(), labels.size(),
+                           labels.empty() ? nullptr : labels.data(), n_groups, &t, &p.info));
+    return p;
+}
+// everything after the counts (host code in the library: no device): counts is n_groups x n_groups, row-major
+inline Paga paga_from_counts(const std::vector<std::uint64_t>& counts, const std::vector<std::uint64_t>& sizes) {
+    const std::uint32_t G = static_cast<std::uint32_t>(sizes.size());
+    if (counts.size() != sizes.size() * sizes.size()) throw Error(SRX_E_ARG, "paga_from_counts: counts is n_groups x n_groups");
+    Paga p(G);
+    srx_paga_tables t = p.tables();
+    const std::int32_t rc = srx_paga_from_counts(counts.data(), sizes.data(), G, &t, &p.info);
+    if (rc != SRX_OK) throw Error(rc, srx_last_error(nullptr));
+    return p;
 }
 // Diffusion map of any symmetric weighted graph without empty rows (srx_diffmap_csr), and the pseudotime of such a result
 inline Diffmap diffmap_csr(Context& ctx, const std::vector<std::uint64_t>& indptr, const std::vector<std::uint32_t>& indices,
