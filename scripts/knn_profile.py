@@ -24,7 +24,7 @@ from singlerust_amd.memory.processing import neighbors              # noqa: E402
 
 
 def padded_k(d):
-    return next(w for w in (8, 20, 36, 52, 68, 132) if d < w)       # knn.hip: d + 1 up to the next instantiated width
+    return next(w for w in (8, 20, 36, 52, 68, 132) if d < w)       # restates knn_padded_width over kKnnInstances (knn_internal.hpp)
 
 
 def main():

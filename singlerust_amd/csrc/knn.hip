@@ -4,12 +4,17 @@
 // N x N is never formed.  An f32 pass on the matrix cores PROPOSES K' = k + kKnnSlack candidates per query, f64 decides:
 //
 //   k_knn_colsum / _finish   column means of the reference in a fixed order (the centre c), finiteness of every point
-//   k_knn_prepare            f32 copy of x - c in MFMA fragment order with |x - c|^2 as one more coordinate; max |x - c|^2
+//   k_knn_fragments          f32 copy of x - c in MFMA fragment order with |x - c|^2 as one more coordinate; max |x - c|^2.
+//                            Behind knn_prepare, which knn_ivf.hip calls too (through an index array, for its list-major copy)
 //   k_knn_candidates<K, RT>  s(q, r) = |r|^2 - 2 q.r on v_mfma_f32_32x32x2_f32 for a block of 128 queries against every
 //                            reference tile; the K' smallest per query kept in LDS; out: their indices and the bound tau
 //   k_knn_exact<false>       f64 distances (difference form) of the K' candidates, sorted by (distance, index), the first
 //                            k written; the certificate below decides whether the row is proven
 //   k_knn_exact<true>        the rows the certificate refused: the same f64 selection over ALL references
+// What the inverted-file index shares with this file is in knn_internal.hpp, stated there once: the keys and their merge,
+// the keep step of the f64 selection (knn_take), eps_row of the certificate (knn_certificate), and on the host the (K, RT)
+// instance table with its dispatch, the dynamic LDS and the candidate counts K' and CAP.  The tile loop of k_knn_candidates
+// is stated a second time in k_ivf_candidates (see the note there).
 //
 // Certificate.  With centred points q, r in f64 the pass approximates t(q, r) = |r|^2 - 2 q.r = dist^2 - |q|^2, which orders
 // the references of one query exactly as the distance does.  What it computes is an f32 fmaf chain over K = padded d + 1
@@ -74,24 +79,35 @@ __global__ void k_knn_colsum_finish(const double* __restrict__ part, int n_part,
 // ---- f32 copy in fragment order ----------------------------------------------------------------------------------------
 // Points are grouped in blocks of 32; block b holds K floats per point as [s = kk / 2][h = kk & 1][i = point % 32], so that
 // lane l of a wave reads word s * 64 + l for step s of v_mfma_f32_32x32x2_f32 (operand element [i = l & 31][k = l >> 5]):
-// consecutive words, no bank conflict, and a reference tile is one contiguous piece of memory.
-// kk < d: x - c; kk == d: |x - c|^2 (+inf for the padding points: never below any threshold); above: 0.
-__global__ void __launch_bounds__(256) k_knn_prepare(const double* __restrict__ x, uint64_t n, uint64_t n_pad, int d, size_t ld,
-                                                     int K, const double* __restrict__ centre, float* __restrict__ out,
-                                                     unsigned long long* __restrict__ rmax2_bits) {
+// consecutive words, no bank conflict, and a reference tile is one contiguous piece of memory.  Position p is point ids[p]
+// (ids null: p itself below n), and what each coordinate holds is stated at knn_prepare (knn_internal.hpp), the launcher
+// both searches call.
+__global__ void __launch_bounds__(256) k_knn_fragments(const double* __restrict__ x, size_t ld, const uint32_t* __restrict__ ids,
+                                                       uint64_t n, uint64_t n_pad, int d, int K, const double* __restrict__ centre,
+                                                       float* __restrict__ out, unsigned long long* __restrict__ rmax2_bits) {
     const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n_pad) return;
+    const uint32_t src = ids ? ids[p] : (p < n ? (uint32_t)p : kKnnNone);
+    const bool real = src != kKnnNone;
     float* o = out + (p >> 5) * (size_t)(32 * K) + (p & 31);
     double nrm = 0.0;
     for (int kk = 0; kk < d; ++kk) {
-        const double v = p < n ? x[p * ld + kk] - centre[kk] : 0.0;
+        const double v = real ? x[(size_t)src * ld + kk] - centre[kk] : 0.0;
         nrm += v * v;
         o[(kk >> 1) * 64 + (kk & 1) * 32] = (float)v;
     }
-    o[(d >> 1) * 64 + (d & 1) * 32] = p < n ? (float)nrm : __builtin_inff();
+    o[(d >> 1) * 64 + (d & 1) * 32] = real ? (float)nrm : __builtin_inff();
     for (int kk = d + 1; kk < K; ++kk) o[(kk >> 1) * 64 + (kk & 1) * 32] = 0.f;
     // non-negative doubles order as their bit patterns: an order-free maximum
-    if (rmax2_bits && p < n) atomicMax(rmax2_bits, (unsigned long long)__double_as_longlong(nrm));
+    if (rmax2_bits && real) atomicMax(rmax2_bits, (unsigned long long)__double_as_longlong(nrm));
+}
+
+int32_t knn_prepare(srx_ctx* ctx, const double* d_x, size_t ld, const uint32_t* d_ids, uint64_t n, uint64_t n_pad, int d, int K,
+                    const double* d_centre, float* d_out, unsigned long long* d_rmax2_bits) {
+    hipLaunchKernelGGL(k_knn_fragments, dim3(grid256(n_pad)), dim3(256), 0, ctx->stream, d_x, ld, d_ids, n, n_pad, d, K, d_centre,
+                       d_out, d_rmax2_bits);
+    SRX_HIP(ctx, hipGetLastError());
+    return SRX_OK;
 }
 
 // ---- candidate pass (the keys of one query in LDS and their merge: knn_internal.hpp) -------------------------------------
@@ -206,11 +222,10 @@ __global__ void __launch_bounds__(256) k_knn_candidates(const float* __restrict_
     }
 }
 
-// ---- f64 selection (knn_dist2, knn_less: knn_internal.hpp) -------------------------------------------------------------
+// ---- f64 selection (knn_dist2, knn_less, knn_take, knn_certificate: knn_internal.hpp) ----------------------------------
 // One wave per query row.  ALL = false: the row's KP candidates; ALL = true: row rows[..] against every reference.
-// The wave keeps at most k + 64 entries in LDS: 64 references at a time, those below the k-th kept one are appended, the
-// list is ranked by (distance, index) and cut back to k.  ALL = false also evaluates the certificate and lists the rows
-// that fail it in `fail_rows` (count in fail_n).
+// The wave keeps at most k + 64 entries in LDS: 64 references at a time, those below the k-th kept one go through the keep
+// step.  ALL = false also evaluates the certificate and lists the rows that fail it in `fail_rows` (count in fail_n).
 template <bool ALL>
 __global__ void __launch_bounds__(256) k_knn_exact(const double* __restrict__ ref, uint64_t n_ref, size_t ld_r,
                                                    const double* __restrict__ qry, uint64_t n_query, size_t ld_q, int d, int k,
@@ -240,43 +255,13 @@ __global__ void __launch_bounds__(256) k_knn_exact(const double* __restrict__ re
             dd = knn_dist2(qp, ref + (size_t)idx * ld_r, d);
             if (n == k) ok = knn_less(dd, idx, D[k - 1], I[k - 1]);
         }
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
-        if (m == 0ull) continue;
-        if (ok) {
-            const int pos = n + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-            D[pos] = dd;
-            I[pos] = idx;
-        }
-        n += __builtin_popcountll(m);
-        wave_lds_sync();
-        // rank the n <= k + 64 <= 128 entries, keep the first k in order
-        const double d0 = lane < n ? D[lane] : 0.0, d1 = lane + 64 < n ? D[lane + 64] : 0.0;
-        const uint32_t i0 = lane < n ? I[lane] : 0u, i1 = lane + 64 < n ? I[lane + 64] : 0u;
-        int r0 = 0, r1 = 0;
-        for (int e = 0; e < n; ++e) {
-            const double de = D[e];
-            const uint32_t ie = I[e];
-            r0 += knn_less(de, ie, d0, i0);
-            r1 += knn_less(de, ie, d1, i1);
-        }
-        wave_lds_sync();
-        if (lane < n && r0 < k) { D[r0] = d0; I[r0] = i0; }
-        if (lane + 64 < n && r1 < k) { D[r1] = d1; I[r1] = i1; }
-        n = n < k ? n : k;
-        wave_lds_sync();
+        n = knn_take(D, I, n, k, ok, dd, idx);
     }
     // (the caller guarantees k admissible references, and K' >= k candidates exist whenever that many references do)
     bool proven = true;
     if (!ALL) {
-        double qn = 0.0;
-        for (int c = 0; c < d; ++c) {
-            const double v = qp[c] - centre[c];
-            qn += v * v;
-        }
-        const double R2 = __longlong_as_double((long long)*rmax2_bits), R = sqrt(R2);
-        double eps = 1.01 * (double)(Kpad + 4) * 5.9604644775390625e-08 * (2.0 * sqrt(qn) * R + R2);
-        if (!(R >= 9.094947017729282e-13 && R <= 1.152921504606847e18)) eps = (double)__builtin_inff();      // 2^-40 .. 2^60
-        proven = n == k && (D[k - 1] - qn) + eps < (double)tau[q];
+        const KnnBound b = knn_certificate(qp, centre, d, Kpad, rmax2_bits);
+        proven = n == k && (D[k - 1] - b.qn) + b.eps_row < (double)tau[q];
         if (!proven && lane == 0) fail_rows[atomicAdd(fail_n, 1u)] = (uint32_t)q;
     }
     if (proven)
@@ -287,18 +272,6 @@ __global__ void __launch_bounds__(256) k_knn_exact(const double* __restrict__ re
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-template <int K, int RT>
-static int32_t launch_candidates(srx_ctx* ctx, const float* ref_t, uint64_t n_ref_pad, const float* qry_t, uint64_t n_query,
-                                 uint64_t n_query_pad, int d, int KP, int CAP, int self_skip, uint32_t* cand, float* tau) {
-    const size_t lds = (size_t)2 * RT * K * 4 + (size_t)kKnnQB * CAP * 8 + (size_t)kKnnQB * 8;
-    SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_knn_candidates<K, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned grid = (unsigned)((n_query + kKnnQB - 1) / kKnnQB);
-    hipLaunchKernelGGL((k_knn_candidates<K, RT>), dim3(grid), dim3(256), lds, ctx->stream, ref_t, n_ref_pad, qry_t, n_query,
-                       n_query_pad, d, KP, CAP, self_skip, cand, tau);
-    SRX_HIP(ctx, hipGetLastError());
-    return SRX_OK;
-}
-
 int32_t knn_exact_rows(srx_ctx* ctx, const KnnArgs& a, int k, int self_skip, const uint32_t* d_rows, uint64_t n_rows,
                        uint32_t* d_idx, double* d_dist) {
     if (n_rows == 0) return SRX_OK;
@@ -315,9 +288,8 @@ int32_t knn_device(srx_ctx* ctx, const KnnArgs& a, const srx_knn_opts* opts, uin
     const int k = opts->k, d = a.d;
     const uint64_t admissible = a.n_ref - ((a.self && !opts->include_self) ? 1 : 0);
     const int self_skip = a.self && !opts->include_self;
-    const int KP = (int)std::min<uint64_t>((uint64_t)k + kKnnSlack, std::max<uint64_t>(admissible, 1));
-    const int CAP = std::min(2 * KP + 32, kKnnCapMax);
-    // padded coordinate count: d + 1 (the norm) rounded up to the next instantiated width
+    const KnnCounts counts = knn_candidate_counts(k, admissible);
+    const int KP = counts.KP, CAP = counts.CAP;
     const int K = knn_padded_width(d);
     const uint64_t n_ref_pad = (a.n_ref + kKnnPad - 1) / kKnnPad * kKnnPad, n_query_pad = (a.n_query + kKnnPad - 1) / kKnnPad * kKnnPad;
     const int n_part = (int)std::min<uint64_t>(1024, (a.n_ref + 255) / 256);
@@ -360,26 +332,18 @@ int32_t knn_device(srx_ctx* ctx, const KnnArgs& a, const srx_knn_opts* opts, uin
         SRX_TRY(d2h(ctx, &bad, d_bad, 4));
         if (bad) return fail(ctx, SRX_E_ARG, "knn: the points hold NaN or Inf");
 
-        hipLaunchKernelGGL(k_knn_prepare, dim3((unsigned)(n_ref_pad / 256 + 1)), dim3(256), 0, st, a.d_ref, a.n_ref, n_ref_pad, d,
-                           a.ld_r, K, d_centre, d_ref_t, d_rmax2);
-        if (!a.self)
-            hipLaunchKernelGGL(k_knn_prepare, dim3((unsigned)(n_query_pad / 256 + 1)), dim3(256), 0, st, a.d_qry, a.n_query,
-                               n_query_pad, d, a.ld_q, K, d_centre, d_qry_t, (unsigned long long*)nullptr);
-        SRX_HIP(ctx, hipGetLastError());
-#define SRX_KNN_CASE(KK, RT)                                                                                                    \
-    case KK:                                                                                                                    \
-        SRX_TRY((launch_candidates<KK, RT>(ctx, d_ref_t, n_ref_pad, d_qry_t, a.n_query, n_query_pad, d, KP, CAP, self_skip,    \
-                                           d_cand, d_tau)));                                                                   \
-        break;
-        switch (K) {
-            SRX_KNN_CASE(8, 64)
-            SRX_KNN_CASE(20, 64)
-            SRX_KNN_CASE(36, 64)
-            SRX_KNN_CASE(52, 64)
-            SRX_KNN_CASE(68, 64)
-            SRX_KNN_CASE(132, 32)
-        }
-#undef SRX_KNN_CASE
+        SRX_TRY(knn_prepare(ctx, a.d_ref, a.ld_r, nullptr, a.n_ref, n_ref_pad, d, K, d_centre, d_ref_t, d_rmax2));
+        if (!a.self) SRX_TRY(knn_prepare(ctx, a.d_qry, a.ld_q, nullptr, a.n_query, n_query_pad, d, K, d_centre, d_qry_t, nullptr));
+        SRX_TRY(knn_dispatch(K, [&](auto Kc, auto RTc) -> int32_t {
+            constexpr int KK = decltype(Kc)::value, RT = decltype(RTc)::value;
+            const size_t lds = knn_candidates_lds(KK, RT, CAP);
+            SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_knn_candidates<KK, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            const unsigned grid = (unsigned)((a.n_query + kKnnQB - 1) / kKnnQB);
+            hipLaunchKernelGGL((k_knn_candidates<KK, RT>), dim3(grid), dim3(256), lds, st, (const float*)d_ref_t, n_ref_pad,
+                               (const float*)d_qry_t, a.n_query, n_query_pad, d, KP, CAP, self_skip, d_cand, d_tau);
+            SRX_HIP(ctx, hipGetLastError());
+            return SRX_OK;
+        }));
         const unsigned wg = (unsigned)((a.n_query + 3) / 4);
         hipLaunchKernelGGL(k_knn_exact<false>, dim3(wg), dim3(256), 0, st, a.d_ref, a.n_ref, a.ld_r, a.d_qry, a.n_query, a.ld_q, d, k,
                            KP, self_skip, d_cand, d_tau, d_centre, d_rmax2, K, (const uint32_t*)nullptr, (uint64_t)0, d_idx, d_dist,

@@ -11,14 +11,15 @@
 //   k_ivf_offsets             list offsets from the sorted keys
 //   k_ivf_segsum              one workgroup per segment of rows: a fixed-order f64 column sum or mean (centroid means over the
 //                             sorted sample, the global centre, the inertia)
-//   k_ivf_place / _prepare    the list-major f32 copy in MFMA fragment order (k_knn_prepare's layout, centre and norm
-//                             coordinate), every list padded to whole tiles with +inf norms, the original index beside it
+//   k_ivf_place               a member's place in the list-major f32 copy: every list padded to whole tiles, the original
+//                             index beside it.  The copy itself is knn.hip's (knn_prepare through the index array: the same
+//                             layout, global centre and norm coordinate, +inf norms at the padding)
 //   k_ivf_candidates<K, RT>   THE HOT PATH: one workgroup per (list, block of <= 128 of the queries that probe it).  It is
 //                             k_knn_candidates with the query fragments gathered through an index array, the reference tiles
 //                             the list's own range of the copy, and K' = k + 8 candidates and a bound tau per (query, probe)
-//   k_ivf_select<false>       one wave per query: the K' best of its n_probe x K' candidates by f32 score, their f64 re-rank,
-//                             knn.hip's certificate with tau = the minimum of the K'-th score and the row's pairs' bounds;
-//                             lists the rows that fail and the rows that are short
+//   k_ivf_select<false>       one wave per query: the K' best of its n_probe x K' candidates by f32 score, their f64 re-rank
+//                             (knn_take), knn.hip's certificate (knn_certificate) with tau = the minimum of the K'-th score
+//                             and the row's pairs' bounds; lists the rows that fail and the rows that are short
 //   k_ivf_select<true>        the rows that failed: the f64 selection over the members of their probed lists
 // Rows whose probed lists hold fewer than k admissible points go through k_knn_exact<true> (knn_exact_rows).
 //
@@ -184,26 +185,6 @@ __global__ void __launch_bounds__(256) k_ivf_place(const uint32_t* __restrict__ 
     ids[q] = m;
     pos[m] = q;
 }
-// k_knn_prepare's layout and values for position p = point ids[p] (ids null: p itself below n); a padding position has zero
-// coordinates and a +inf norm
-__global__ void __launch_bounds__(256) k_ivf_prepare(const double* __restrict__ x, size_t ld, const uint32_t* __restrict__ ids,
-                                                     uint64_t n, uint64_t n_pad, int d, int K, const double* __restrict__ centre,
-                                                     float* __restrict__ out, unsigned long long* __restrict__ rmax2_bits) {
-    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= n_pad) return;
-    const uint32_t src = ids ? ids[p] : (p < n ? (uint32_t)p : kKnnNone);
-    const bool real = src != kKnnNone;
-    float* o = out + (p >> 5) * (size_t)(32 * K) + (p & 31);
-    double nrm = 0.0;
-    for (int kk = 0; kk < d; ++kk) {
-        const double v = real ? x[(size_t)src * ld + kk] - centre[kk] : 0.0;
-        nrm += v * v;
-        o[(kk >> 1) * 64 + (kk & 1) * 32] = (float)v;
-    }
-    o[(d >> 1) * 64 + (d & 1) * 32] = real ? (float)nrm : __builtin_inff();
-    for (int kk = d + 1; kk < K; ++kk) o[(kk >> 1) * 64 + (kk & 1) * 32] = 0.f;
-    if (rmax2_bits && real) atomicMax(rmax2_bits, (unsigned long long)__double_as_longlong(nrm));
-}
 
 // ---- candidate pass, list-major ------------------------------------------------------------------------------------------
 // items[w] = (list, first sorted pair, pairs <= 128, -).  pairs[]: the chunk's (query, probe slot) pairs sorted by list, as
@@ -211,6 +192,11 @@ __global__ void __launch_bounds__(256) k_ivf_prepare(const double* __restrict__ 
 // the position inside the list (ascending with the point index, as the members are); the self-skip and the output translate it
 // through ids.  Dynamic LDS: 2 tiles | keys 128 x CAP | cnt 128 | tau 128.  Out: cand[pair x KP] as keys (ordered score bits
 // << 32 | point index; ~0: none), tau_out[pair].
+// The tile loop below (LDS carve-up, staging, MFMA chain, minimum tree and ballot, C/D row map, append, merge-on-full) is
+// k_knn_candidates' loop, which is the case "every slot live, one list = all references".  Stated once as a forceinline
+// template it compiled to the same loop instructions at the same occupancy, yet the searches at 1.3 M cells measured 0.2 to
+// 0.5 % slower than the two copies (profiles/knn.md, profiles/knn_ivf.md), so the copies stay: a change to one is a change
+// to both.
 template <int K, int RT>
 __global__ void __launch_bounds__(256) k_ivf_candidates(const float* __restrict__ ref_t, const uint32_t* __restrict__ ids,
                                                         const int64_t* __restrict__ poff, const float* __restrict__ qry_t,
@@ -338,36 +324,6 @@ __global__ void __launch_bounds__(256) k_ivf_candidates(const float* __restrict_
 }
 
 // ---- f64 selection ---------------------------------------------------------------------------------------------------------
-// k_knn_exact's step: the lanes with ok append (dd, idx) to the wave's n sorted entries, the list is ranked by (distance, index)
-// and cut back to k.  Returns the new n.
-__device__ __forceinline__ int ivf_take(double* __restrict__ D, uint32_t* __restrict__ I, int n, int k, bool ok, double dd,
-                                        uint32_t idx) {
-    const int lane = lane_id();
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
-    if (m == 0ull) return n;
-    if (ok) {
-        const int pos = n + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-        D[pos] = dd;
-        I[pos] = idx;
-    }
-    n += __builtin_popcountll(m);
-    wave_lds_sync();
-    const double d0 = lane < n ? D[lane] : 0.0, d1 = lane + 64 < n ? D[lane + 64] : 0.0;
-    const uint32_t i0 = lane < n ? I[lane] : 0u, i1 = lane + 64 < n ? I[lane + 64] : 0u;
-    int r0 = 0, r1 = 0;
-    for (int e = 0; e < n; ++e) {
-        const double de = D[e];
-        const uint32_t ie = I[e];
-        r0 += knn_less(de, ie, d0, i0);
-        r1 += knn_less(de, ie, d1, i1);
-    }
-    wave_lds_sync();
-    if (lane < n && r0 < k) { D[r0] = d0; I[r0] = i0; }
-    if (lane + 64 < n && r1 < k) { D[r1] = d1; I[r1] = i1; }
-    wave_lds_sync();
-    return n < k ? n : k;
-}
-
 // One wave per query row.  LISTS = false: row q0 + w of the chunk, over its n_probe x KP candidates; the certificate decides
 // whether it is written, listed in fail_rows (count[0]) or — fewer than k admissible members in its probed lists — in
 // short_rows (count[1]).  LISTS = true: row rows[w] over all members of its probed lists, always written.
@@ -440,7 +396,7 @@ __global__ void __launch_bounds__(256) k_ivf_select(const double* __restrict__ r
                 dd = knn_dist2(qp, ref + (size_t)idx * d, d);
                 if (n == k) ok = knn_less(dd, idx, D[k - 1], I[k - 1]);
             }
-            n = ivf_take(D, I, n, k, ok, dd, idx);
+            n = knn_take(D, I, n, k, ok, dd, idx);
         }
     }
     bool write = true;
@@ -454,16 +410,9 @@ __global__ void __launch_bounds__(256) k_ivf_select(const double* __restrict__ r
         const long long avail = wave_sum(len) - (self_skip ? 1 : 0);      // (in the self form a point's own list is probed)
         float tau_min = wave_min(tq);
         if (n_valid > KP) tau_min = fminf(tau_min, key_f32((uint32_t)(Kk[KP - 1] >> 32)));
-        double qn = 0.0;
-        for (int c = 0; c < d; ++c) {
-            const double v = qp[c] - centre[c];
-            qn += v * v;
-        }
-        const double R2 = __longlong_as_double((long long)*rmax2_bits), R = sqrt(R2);
-        double eps = 1.01 * (double)(Kpad + 4) * 5.9604644775390625e-08 * (2.0 * sqrt(qn) * R + R2);
-        if (!(R >= 9.094947017729282e-13 && R <= 1.152921504606847e18)) eps = (double)__builtin_inff();      // 2^-40 .. 2^60
+        const KnnBound b = knn_certificate(qp, centre, d, Kpad, rmax2_bits);
         const bool is_short = avail < (long long)k;
-        write = !is_short && n == k && (D[k - 1] - qn) + eps < (double)tau_min;
+        write = !is_short && n == k && (D[k - 1] - b.qn) + b.eps_row < (double)tau_min;
         if (!write && lane == 0) {
             if (is_short) short_rows[atomicAdd(count + 1, 1u)] = (uint32_t)q;
             else fail_rows[atomicAdd(count, 1u)] = (uint32_t)q;
@@ -668,9 +617,7 @@ static int32_t ivf_build(srx_ctx* ctx, const double* d_src, size_t ld, uint64_t 
         hipLaunchKernelGGL(k_ivf_place, dim3(grid256(n_ref)), dim3(256), 0, st, (const uint32_t*)d_keys, (const uint32_t*)ix->d_members,
                            n_ref, (const int64_t*)ix->d_off, (const int64_t*)ix->d_poff, ix->d_ids, ix->d_pos);
         SRX_TRY(ivf_colsum(ctx, ix->d_pts, (size_t)d, n_ref, d, (double)n_ref, ix->d_centre));
-        hipLaunchKernelGGL(k_ivf_prepare, dim3(grid256(ix->n_pad)), dim3(256), 0, st, (const double*)ix->d_pts, (size_t)d,
-                           (const uint32_t*)ix->d_ids, n_ref, ix->n_pad, d, ix->K, (const double*)ix->d_centre, ix->d_ref_t, ix->d_rmax2);
-        SRX_HIP(ctx, hipGetLastError());
+        SRX_TRY(knn_prepare(ctx, ix->d_pts, (size_t)d, ix->d_ids, n_ref, ix->n_pad, d, ix->K, ix->d_centre, ix->d_ref_t, ix->d_rmax2));
     }
     SRX_TRY(t_assign.stop(&ms_assign));
 
@@ -705,19 +652,6 @@ static int32_t ivf_opts_check(srx_ctx* ctx, const srx_ivf_opts* opts, uint64_t n
     return SRX_OK;
 }
 
-template <int K, int RT>
-static int32_t launch_ivf_candidates(srx_ctx* ctx, const srx_knn_index* ix, const float* qry_t, const uint32_t* qpos,
-                                     const uint32_t* pairs, const uint4* items, unsigned n_items, uint64_t q0, int n_probe, int KP,
-                                     int CAP, int self_skip, unsigned long long* cand, float* tau) {
-    const size_t lds = (size_t)2 * RT * K * 4 + (size_t)kKnnQB * CAP * 8 + (size_t)kKnnQB * 8;
-    SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_ivf_candidates<K, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_ivf_candidates<K, RT>), dim3(n_items), dim3(256), lds, ctx->stream, (const float*)ix->d_ref_t,
-                       (const uint32_t*)ix->d_ids, (const int64_t*)ix->d_poff, qry_t, qpos, pairs, items, q0, n_probe, ix->d, KP, CAP,
-                       self_skip, cand, tau);
-    SRX_HIP(ctx, hipGetLastError());
-    return SRX_OK;
-}
-
 // The search of n_query rows at d_qry (device, pitch ld_q; the index's own points for the self form).  The list is left in the
 // "knn_idx" / "knn_dist" scratch slots, as knn_device leaves it.
 static int32_t ivf_search_device(srx_knn_index* ix, const double* d_qry, size_t ld_q, uint64_t n_query, bool self, int k,
@@ -728,8 +662,8 @@ static int32_t ivf_search_device(srx_knn_index* ix, const double* d_qry, size_t 
     const uint32_t L = ix->n_lists;
     const int self_skip = self && !include_self;
     const uint64_t admissible = ix->n_ref - (self_skip ? 1 : 0);
-    const int KP = (int)std::min<uint64_t>((uint64_t)k + kKnnSlack, std::max<uint64_t>(admissible, 1));
-    const int CAP = std::min(2 * KP + 32, kKnnCapMax);
+    const KnnCounts counts = knn_candidate_counts(k, admissible);
+    const int KP = counts.KP, CAP = counts.CAP;
 
     // probe sets: the exact n_probe nearest centroids of every query
     const srx_knn_opts po{n_probe, 0, 0, 0};
@@ -758,9 +692,7 @@ static int32_t ivf_search_device(srx_knn_index* ix, const double* d_qry, size_t 
         float* t;
         SRX_TRY(scratch(ctx, "ivf_qry_f32", nq_pad * (size_t)K * 4, (void**)&t));
         ProfScope ps(ctx, SRX_K_KNN, (double)n_query * d * 12.0);
-        hipLaunchKernelGGL(k_ivf_prepare, dim3(grid256(nq_pad)), dim3(256), 0, st, d_qry, ld_q, (const uint32_t*)nullptr, n_query, nq_pad,
-                           d, K, (const double*)ix->d_centre, t, (unsigned long long*)nullptr);
-        SRX_HIP(ctx, hipGetLastError());
+        SRX_TRY(knn_prepare(ctx, d_qry, ld_q, nullptr, n_query, nq_pad, d, K, ix->d_centre, t, nullptr));
         d_qry_t = t;
         d_qpos = nullptr;
     }
@@ -804,20 +736,17 @@ static int32_t ivf_search_device(srx_knn_index* ix, const double* d_qry, size_t 
             ProfScope ps(ctx, SRX_K_KNN, (double)nq * d * 8.0 + (double)nq * k * 12.0);
             const unsigned n_items = (unsigned)h_items.size();
             if (n_items) {
-#define SRX_IVF_CASE(KK, RT)                                                                                                    \
-    case KK:                                                                                                                    \
-        SRX_TRY((launch_ivf_candidates<KK, RT>(ctx, ix, d_qry_t, d_qpos, d_pairs, d_items, n_items, q0, n_probe, KP, CAP,       \
-                                               self_skip, d_cand, d_tau)));                                                    \
-        break;
-                switch (K) {
-                    SRX_IVF_CASE(8, 64)
-                    SRX_IVF_CASE(20, 64)
-                    SRX_IVF_CASE(36, 64)
-                    SRX_IVF_CASE(52, 64)
-                    SRX_IVF_CASE(68, 64)
-                    SRX_IVF_CASE(132, 32)
-                }
-#undef SRX_IVF_CASE
+                SRX_TRY(knn_dispatch(K, [&](auto Kc, auto RTc) -> int32_t {
+                    constexpr int KK = decltype(Kc)::value, RT = decltype(RTc)::value;
+                    const size_t lds = knn_candidates_lds(KK, RT, CAP);
+                    SRX_HIP(ctx, hipFuncSetAttribute((const void*)k_ivf_candidates<KK, RT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     (int)lds));
+                    hipLaunchKernelGGL((k_ivf_candidates<KK, RT>), dim3(n_items), dim3(256), lds, st, (const float*)ix->d_ref_t,
+                                       (const uint32_t*)ix->d_ids, (const int64_t*)ix->d_poff, d_qry_t, d_qpos, (const uint32_t*)d_pairs,
+                                       (const uint4*)d_items, q0, n_probe, d, KP, CAP, self_skip, d_cand, d_tau);
+                    SRX_HIP(ctx, hipGetLastError());
+                    return SRX_OK;
+                }));
             }
             hipLaunchKernelGGL(k_ivf_select<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, (const double*)ix->d_pts, d_qry, ld_q,
                                q0, nq, d, k, KP, n_probe, self_skip, (const unsigned long long*)d_cand, (const float*)d_tau,

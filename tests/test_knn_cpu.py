@@ -74,18 +74,19 @@ def test_knn_fails_loudly_without_a_device():
 
 def test_knn_kernels_do_not_spill_registers(tmp_path):
     """The same method as test_hot_kernels_do_not_spill_registers: the gfx950 code-object metadata of every instance of the
-    candidate kernel (and of the f64 selection) shows no VGPR spill and no scratch."""
+    candidate kernel (and of the f64 selection, and of the f32 copy both searches use) shows no VGPR spill and no scratch."""
     from singlerust_amd import build
     out = str(tmp_path / "knn.s")
     subprocess.check_call([build._hipcc(), *[f for f in build.FLAGS if f != "-Wall"], "-w", "-S", "--cuda-device-only", "-o", out,
                            os.path.join(ROOT, "singlerust_amd", "csrc", "knn.hip")], stderr=subprocess.DEVNULL)
     meta = open(out).read()
     assert "v_mfma_f32_32x32x2_f32" in meta or "v_mfma_f32_32x32x2f32" in meta
-    seen = 0
-    for m in re.finditer(r"\.name:\s+(\S*(?:k_knn_candidates|k_knn_exact)\S*)\n(.*?)\.wavefront_size", meta, flags=re.S):
+    seen = copies = 0
+    for m in re.finditer(r"\.name:\s+(\S*(?:k_knn_candidates|k_knn_exact|k_knn_fragments)\S*)\n(.*?)\.wavefront_size", meta, flags=re.S):
         body = m.group(2)
         spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", body).group(1))
         scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
         assert spill == 0 and scratch == 0, f"{m.group(1)}: {spill} spilled VGPRs, {scratch} B of scratch"
         seen += "k_knn_candidates" in m.group(1)
-    assert seen == 6, seen
+        copies += "k_knn_fragments" in m.group(1)
+    assert seen == 6 and copies == 1, (seen, copies)

@@ -16,8 +16,8 @@ import knn_ivf_ref as R
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("srx_knn_index_result", "srx_knn_index_points", "srx_knn_index_info_get", "srx_knn_index_fetch", "srx_knn_index_search",
        "srx_neighbors_index", "srx_knn_index_free")
-KERNELS = ("k_ivf_sort_pass", "k_ivf_offsets", "k_ivf_segsum", "k_ivf_gather", "k_ivf_dist2", "k_ivf_place", "k_ivf_prepare",
-           "k_ivf_candidates", "k_ivf_select")
+KERNELS = ("k_ivf_sort_pass", "k_ivf_offsets", "k_ivf_segsum", "k_ivf_gather", "k_ivf_dist2", "k_ivf_place", "k_ivf_candidates",
+           "k_ivf_select")                   # (the f32 copy is knn.hip's k_knn_fragments: test_knn_cpu.py)
 
 
 # ---- the layers ---------------------------------------------------------------------------------------------------------------

@@ -67,6 +67,69 @@ def test_exhaustive_probe_equals_exact_search(ctx, n, d):
             ix.free()
 
 
+# ---- 1b. every instance of the list-major candidate pass --------------------------------------------------------------------
+# One d per instantiated width (knn_ref.WIDTHS); below 128 it is the largest d of its width, so the norm sits in the last
+# coordinate slot.  Two explicit centroids and n_probe = n_lists: every list is probed by all 300 rows of the self form (work
+# items of 128, 128 and 44 pairs: full blocks, and a partial one with two dead waves) or by the 130 separate queries (128 and
+# 2: three dead waves).  Coordinates are integers times 2^-16, so knn_ref's int64 distances are exact and the expectation
+# needs no near-tie allowance.
+WIDTH_D = (7, 19, 35, 51, 67, 128)
+WIDTH_N, WIDTH_NQ, WIDTH_K, WIDTH_EXP = 300, 130, 15, -16
+
+
+@pytest.fixture(scope="module", params=WIDTH_D)
+def width_case(request):
+    import knn_ref as KR
+    d = request.param
+    assert KR.width(d) == KR.WIDTHS[WIDTH_D.index(d)] and (d == 128 or KR.width(d + 1) > KR.width(d))
+    rng = np.random.default_rng(7000 + d)
+    scale = np.linspace(4, 0.5, d) * 2.0 ** -WIDTH_EXP
+    units = np.rint(rng.standard_normal((WIDTH_N, d)) * scale).astype(np.int64)
+    qry = np.concatenate([np.rint(rng.standard_normal((WIDTH_NQ - 40, d)) * 2 * scale).astype(np.int64), units[::7][:40]])
+    assert len(qry) == WIDTH_NQ
+    forms = {"self": KR.Case(f"ivf_width_d{d}", units, exp=WIDTH_EXP),
+             "query": KR.Case(f"ivf_width_d{d}_query", units, exp=WIDTH_EXP, query=qry)}
+    for case in forms.values():                  # no exact tie at rank k: the k-th and the next distance differ in every row
+        _, d2, _ = case.expected()
+        assert (d2[:, WIDTH_K - 1] < d2[:, WIDTH_K]).all(), case.name
+    cent = np.zeros((3, d))
+    cent[0, 0], cent[1, 0] = -1.0, 1.0           # the two halves along the widest axis
+    cent[2] = 1e4                                # and a centroid no point is nearest to
+    return d, forms, cent
+
+
+def check_width_forms(ctx, ix, forms, n_lists):
+    for form, case in forms.items():
+        ref, qry = case.points()
+        idx, dist, info = ix.search(qry, k=WIDTH_K, n_probe=n_lists)
+        wi, wd, _ = P().knn_points(ctx, ref, qry, k=WIDTH_K)
+        assert np.array_equal(idx, wi), case.name
+        assert np.array_equal(dist.view(np.uint64), wd.view(np.uint64)), case.name
+        ei, ed = case.expected_k(WIDTH_K)
+        assert np.array_equal(idx.astype(np.int64), ei) and np.array_equal(dist.view(np.uint64), ed.view(np.uint64)), case.name
+        counters_sum(info)
+        assert info["pairs"] == len(idx) * n_lists and info["points_scanned"] == len(idx) * WIDTH_N, (case.name, info)
+
+
+def test_exhaustive_probe_equals_exact_search_at_every_width(ctx, width_case):
+    d, forms, cent = width_case
+    ix = P().knn_index_points(ctx, forms["self"].points()[0], centroids=cent[:2])
+    i = ix.info()
+    assert i["n_lists"] == 2 and i["d"] == d and i["empty_lists"] == 0 and i["min_list"] > 64, i
+    check_width_forms(ctx, ix, forms, 2)
+    ix.free()
+
+
+def test_an_empty_list_changes_nothing(ctx, width_case):
+    d, forms, cent = width_case
+    ix = P().knn_index_points(ctx, forms["self"].points()[0], centroids=cent)
+    i = ix.info()
+    assert i["n_lists"] == 3 and i["empty_lists"] == 1 and i["min_list"] == 0, i
+    assert np.diff(ix.fetch()[1].astype(np.int64))[2] == 0
+    check_width_forms(ctx, ix, forms, 3)
+    ix.free()
+
+
 # ---- 2. supplied integer centroids against the restatement ------------------------------------------------------------------
 def check_against_ref(ctx, ix, ref_u, cent_u, qry_u, k, n_probe, include_self, exp, label):
     want = R.search(ref_u, cent_u, k, n_probe, qry_u, include_self)
