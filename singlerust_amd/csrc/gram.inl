@@ -25,8 +25,16 @@ __device__ __forceinline__ double gram_product(double a, double b) { return a * 
 // whatever the LDS atomics make it — the Gram sums are order-dependent in their last bits anyway).
 // boff[rb][w] .. boff[rb][w + 1]: records of owner w, relative to the block's first record (rec_base[rb]).
 constexpr int kBucketThreads = 1024;
-constexpr int kBucketGroup = 8;           // consecutive rows a wave walks as one flat run
-constexpr int kBucketUnroll = 8;          // 64-entry chunks of the run in flight
+constexpr int kBucketWaves = kBucketThreads / kWave;
+// 64-entry chunks of a wave's span that stay in registers from the count phase to the scatter phase: 2 registers per f32 entry,
+// 4 per f64 entry (the 16-byte load's destination), 80 of the 128 a wave of a 1024-thread workgroup may have — no scratch.
+// c3: a wave's 32 rows hold 36 chunks.
+// (Two workgroups per CU need 64 registers: 16 resident chunks, or 12 without a forced bound — the other 20 of c3's 36 re-read behind
+//  the scatter phase's stores: both measured at the old walk's time, profiles/gram_records.md.  One workgroup per CU, the span whole.)
+template <typename VT> constexpr int kBucketResident = sizeof(VT) == 4 ? 40 : 20;
+constexpr int kBucketTail = 8;            // chunks per load round of the part of a span behind the resident one
+// 64-counter pieces of the owner counters: n_wg <= 10240 owners (gram_plan: SR (k + SR) doubles within 160 KiB of LDS)
+constexpr int kBucketMaxPieces = 160;
 
 // per-block record totals (k_bucket's layout needs their prefix sums before it runs)
 __global__ __launch_bounds__(256) void k_rec_count(const int64_t* __restrict__ rm_ptr, uint64_t n_rows, uint32_t rblk,
@@ -124,6 +132,27 @@ __global__ void k_gstat_decode(const double* __restrict__ bins, uint32_t* __rest
     gstat[2] = bins[2 * NB] != 0.0 ? 1u : 0u;
 }
 
+// entry i of a wave's span (`rs`: a buffer over exactly the span); past its end: zeros, nothing fetched, no branch around the load
+__device__ __forceinline__ void bucket_load(__amdgpu_buffer_rsrc_t rs, uint32_t i, uint32_t& j, float& v) {
+    const auto x = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(i * 8u), 0, 0);
+    j = (uint32_t)x[0];
+    v = __builtin_bit_cast(float, (unsigned)x[1]);
+}
+__device__ __forceinline__ void bucket_load(__amdgpu_buffer_rsrc_t rs, uint32_t i, uint32_t& j, double& v) {
+    const auto x = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(i * 16u), 0, 0);
+    j = (uint32_t)x[0];
+    v = __builtin_bit_cast(double, ((unsigned long long)(unsigned)x[3] << 32) | (unsigned)x[2]);
+}
+
+// Wave v takes rows [v R, (v + 1) R) of the block, R = ceil(rblk / 16): their entries are ONE flat span of the row-major matrix.
+// The wave issues the loads of the whole span — 64-entry chunks, lane l taking entry 64 u + l of chunk u — before it uses the first,
+// and keeps the first kBucketResident chunks in registers through both phases: COUNT (records per owner, value statistics), the scan
+// of the owner counters, SCATTER (records written).  A lane's entries come in increasing position, so the row of an entry — the
+// suffix length needs the row's end — is a per-lane cursor into `rptr` that only moves forward; the count phase leaves the suffix
+// length in the upper half of the entry's column word (both below 2^16: k <= 20480, gram_plan), so that the scatter phase of the
+// resident part is LDS atomics and record stores alone: no global load stands in front of a store (vmcnt retires in order: a load
+// behind 64 scattered 12-byte stores waits for every acknowledgement).  A span longer than the resident part (dense rows, skewed
+// gene densities) walks the rest kBucketTail chunks at a time in both phases, reading it twice.
 template <typename VT>
 __global__ __launch_bounds__(kBucketThreads) void k_bucket(const int64_t* __restrict__ rm_ptr, const GramPk<VT>* __restrict__ rm,
                                                            uint64_t n_rows, uint32_t rblk, int k, int sr_shift, int n_wg, int n_stripes,
@@ -132,6 +161,7 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket(const int64_t* __rest
                                                            int64_t n_recs, double* __restrict__ zero_g, uint64_t n_zero_g) {
     extern __shared__ double lds_raw[];
     __shared__ uint32_t s_stat[3];
+    __shared__ uint32_t s_piece[kBucketMaxPieces];                // totals of the 64-counter pieces of `hist`
     // side jobs that used to be memset launches in front of this kernel (4-5 us each on the step's critical path): the
     // kGramUnroll records behind the last one (the stripe kernel's batches read past the end) and, for a fresh sum, the packed
     // triangle the stripe kernel adds into
@@ -148,55 +178,91 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket(const int64_t* __rest
     const uint64_t r0 = rb * rblk;
     const uint64_t r1 = r0 + rblk < n_rows ? r0 + rblk : n_rows;
     const int nr = (int)(r1 - r0);
-    const int lane = lane_id(), wave = threadIdx.x / kWave;
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    const int n_pc = (n_wg + kWave - 1) / kWave;
+    if (n_pc > kBucketMaxPieces) __builtin_trap();                // (gram_plan's LDS bound rules it out)
     const int64_t base = rm_ptr[r0];
     for (int e = threadIdx.x; e <= n_wg; e += kBucketThreads) hist[e] = 0u;
-    for (int e = threadIdx.x; e <= nr + kBucketGroup; e += kBucketThreads)
-        rptr[e] = (uint32_t)(rm_ptr[r0 + (e < nr ? e : nr)] - base);          // padded by a group of empty rows
+    for (int e = threadIdx.x; e <= nr; e += kBucketThreads) rptr[e] = (uint32_t)(rm_ptr[r0 + e] - base);
     __syncthreads();
-    const GramPk<VT>* rmb = rm + base;
-    // A wave takes kBucketGroup consecutive rows at a time: their entries are one contiguous run, walked flat 64 at a time
-    // (coalesced), and the row of an entry is found by comparing with the group's three inner row starts — the suffix
-    // length of an entry (its record count) needs the row's end.  `visit(p, j, v, row_end)` for every entry of the block.
-    auto walk = [&](auto visit) {
-        for (int g0 = wave * kBucketGroup; g0 < nr; g0 += (kBucketThreads / kWave) * kBucketGroup) {
-            uint32_t b[kBucketGroup + 1];
+    constexpr int K = kBucketResident<VT>;
+    const int R = (int)((rblk + kBucketWaves - 1) / kBucketWaves);
+    const int rw0 = wave * R < nr ? wave * R : nr, rw1 = rw0 + R < nr ? rw0 + R : nr;
+    // the span: entries [s0, s0 + n) of the block (wave-uniform, and known to the compiler as such: the buffer's descriptor is scalar)
+    const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)rptr[rw0]);
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)rptr[rw1]) - s0;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<GramPk<VT>*>(rm + base + s0), (short)0,
+                                                                        (int)(n * (uint32_t)sizeof(GramPk<VT>)), 0x00020000);
+    uint32_t jl[K];                       // column, from the count phase on: column | suffix length << 16 (0: no entry)
+    VT val[K];
 #pragma unroll
-            for (int i = 0; i <= kBucketGroup; ++i) b[i] = rptr[g0 + i];
-            for (uint32_t p0 = b[0]; p0 < b[kBucketGroup]; p0 += kBucketUnroll * kWave) {
-                GramPk<VT> x[kBucketUnroll];
+    for (int u = 0; u < K; ++u) bucket_load(rs, (uint32_t)(u * kWave + lane), jl[u], val[u]);
+    // the row cursor: entry p of the span (s0 <= p < s0 + n) lies in the row with rptr[row] <= p < rptr[row + 1] = end
+    auto seek = [&](uint32_t p, int& row, uint32_t& end) {
+        int lo = rw0, hi = rw1;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (rptr[mid] <= p) lo = mid;
+            else hi = mid;
+        }
+        row = lo;
+        end = rptr[lo + 1];
+    };
+    auto advance = [&](uint32_t p, int& row, uint32_t& end) {
+        while (p >= end) end = rptr[++row + 1];
+    };
+    // the part of the span behind the resident chunks: `visit(p, j, v, len)` for each of its entries
+    auto tail = [&](auto visit) {
+        if (n <= (uint32_t)(K * kWave)) return;
+        int row = rw0;
+        uint32_t end = 0xffffffffu;
+        if ((uint32_t)(K * kWave + lane) < n) seek(s0 + (uint32_t)(K * kWave + lane), row, end);
+        for (uint32_t c0 = K * kWave; c0 < n; c0 += kBucketTail * kWave) {
+            uint32_t j[kBucketTail];
+            VT v[kBucketTail];
 #pragma unroll
-                for (int u = 0; u < kBucketUnroll; ++u) {
-                    const uint32_t p = p0 + u * kWave + lane;
-                    x[u].j = -1;
-                    if (p < b[kBucketGroup]) x[u] = rmb[p];
-                }
+            for (int u = 0; u < kBucketTail; ++u) bucket_load(rs, c0 + (uint32_t)(u * kWave + lane), j[u], v[u]);
 #pragma unroll
-                for (int u = 0; u < kBucketUnroll; ++u) {
-                    const uint32_t p = p0 + u * kWave + lane;
-                    if (x[u].j < 0) continue;
-                    uint32_t end = b[1];
-#pragma unroll
-                    for (int i = 1; i < kBucketGroup; ++i) end = p >= b[i] ? b[i + 1] : end;
-                    visit(p, x[u].j, x[u].v, end);
-                }
+            for (int u = 0; u < kBucketTail; ++u) {
+                const uint32_t i = c0 + (uint32_t)(u * kWave + lane);
+                if (i >= n) continue;
+                advance(s0 + i, row, end);
+                visit(s0 + i, (int)j[u], v[u], end - (s0 + i));
             }
         }
     };
+    // COUNT: records per owner, value statistics
     uint32_t vmax_b = 0u, vmin_nb = 0u, neg = 0u;
-    walk([&](uint32_t p, int j, VT v, uint32_t end) {
-        __hip_atomic_fetch_add(&hist[gram_owner(j, sr_shift, n_wg, n_stripes)], (end - p + 63u) >> 6, __ATOMIC_RELAXED,
+    auto count = [&](uint32_t, int j, VT v, uint32_t len) {
+        __hip_atomic_fetch_add(&hist[gram_owner(j, sr_shift, n_wg, n_stripes)], (len + 63u) >> 6, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_WORKGROUP);
-        {                                       // (a stored zero makes the smallest |v| zero: the range test fails, the f64 atomics run)
-            uint32_t b;                             // f64 entries: the high word (sign, exponent, 20 mantissa bits)
-            if constexpr (sizeof(VT) == 4) b = __float_as_uint(v);
-            else b = (uint32_t)((unsigned long long)__double_as_longlong(v) >> 32);
-            const uint32_t ab = b & 0x7fffffffu;
-            vmax_b = ab > vmax_b ? ab : vmax_b;
-            vmin_nb = ~ab > vmin_nb ? ~ab : vmin_nb;
-            neg |= b;
+        uint32_t b;                             // f64 entries: the high word (sign, exponent, 20 mantissa bits)
+        if constexpr (sizeof(VT) == 4) b = __float_as_uint(v);
+        else b = (uint32_t)((unsigned long long)__double_as_longlong(v) >> 32);
+        const uint32_t ab = b & 0x7fffffffu;    // (a stored zero makes the smallest |v| zero: the range test fails, the f64 atomics run)
+        vmax_b = ab > vmax_b ? ab : vmax_b;
+        vmin_nb = ~ab > vmin_nb ? ~ab : vmin_nb;
+        neg |= b;
+    };
+    {
+        int row = rw0;
+        uint32_t end = 0xffffffffu;
+        if ((uint32_t)lane < n) seek(s0 + (uint32_t)lane, row, end);
+#pragma unroll
+        for (int u = 0; u < K; ++u) {
+            if ((uint32_t)(u * kWave) >= n) break;
+            const uint32_t i = (uint32_t)(u * kWave + lane);
+            uint32_t packed = 0u;
+            if (i < n) {
+                advance(s0 + i, row, end);
+                const uint32_t len = end - (s0 + i);
+                count(s0 + i, (int)jl[u], val[u], len);
+                packed = jl[u] | len << 16;
+            }
+            jl[u] = packed;
         }
-    });
+    }
+    tail(count);
     if (vmax_b) atomicMax(&s_stat[0], vmax_b);
     if (vmin_nb) atomicMax(&s_stat[1], vmin_nb);
     if (neg >> 31) atomicOr(&s_stat[2], 1u);
@@ -205,42 +271,59 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket(const int64_t* __rest
         if (threadIdx.x == 2) atomicOr(&gstat[2], 1u);
         else atomicMax(&gstat[threadIdx.x], s_stat[threadIdx.x]);
     }
-    // exclusive scan of the n_wg counters by wave 0, 64 at a time
-    if (wave == 0) {
-        uint32_t carry = 0;
-        for (int c0 = 0; c0 < n_wg; c0 += kWave) {
-            const int i = c0 + lane;
-            const uint32_t v = i < n_wg ? hist[i] : 0u;
-            const uint32_t inc = wave_scan_inclusive(v);
-            if (i < n_wg) {
-                hist[i] = carry + inc - v;
-                boff[rb * (uint64_t)(n_wg + 1) + i] = carry + inc - v;
-            }
-            carry += __shfl(inc, kWave - 1, kWave);
-        }
-        if (lane == 0) boff[rb * (uint64_t)(n_wg + 1) + n_wg] = carry;
+    // exclusive scan of the n_wg counters, a wave per 64-counter piece: inside the pieces, then the pieces before each
+    for (int pc = wave; pc < n_pc; pc += kBucketWaves) {
+        const int i = pc * kWave + lane;
+        const uint32_t v = i < n_wg ? hist[i] : 0u;
+        const uint32_t inc = wave_scan_inclusive(v);
+        if (i < n_wg) hist[i] = inc - v;
+        if (lane == kWave - 1) s_piece[pc] = inc;
     }
     __syncthreads();
+    for (int pc = wave; pc < n_pc; pc += kBucketWaves) {
+        uint32_t before = 0u;
+        for (int q = lane; q < pc; q += kWave) before += s_piece[q];
+        before = wave_sum(before);
+        const int i = pc * kWave + lane;
+        if (i < n_wg) {
+            const uint32_t o = hist[i] + before;
+            hist[i] = o;
+            boff[rb * (uint64_t)(n_wg + 1) + i] = o;
+        }
+        if (pc == n_pc - 1 && lane == 0) boff[rb * (uint64_t)(n_wg + 1) + n_wg] = before + s_piece[pc];
+    }
+    __syncthreads();
+    // SCATTER: the records of an entry, one per 64-entry piece of its suffix, into its owner's run
     GramRec<VT>* rcb = recs + rec_base[rb];
-    walk([&](uint32_t p, int j, VT v, uint32_t end) {
-        const uint32_t len = end - p, nch = (len + 63u) >> 6;
-        uint32_t slot = __hip_atomic_fetch_add(&hist[gram_owner(j, sr_shift, n_wg, n_stripes)], nch, __ATOMIC_RELAXED,
+    auto scatter = [&](uint32_t p, int j, VT v, uint32_t len) {
+        uint32_t slot = __hip_atomic_fetch_add(&hist[gram_owner(j, sr_shift, n_wg, n_stripes)], (len + 63u) >> 6, __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_WORKGROUP);
         if constexpr (sizeof(VT) == 4) {
             // f32 entries (round 5): the record in the form the stripe kernel's scalar unit consumes it — the piece's BYTE offset in the
             // block, and n0 | n1 << 6 | row base << 12: n0 / n1 = the lanes of a HALF wave whose first / second entry lies inside the
             // piece (lane l of a half takes entries 2 l and 2 l + 1), the row's accumulators as a signed byte offset
             const uint32_t rb = (uint32_t)gram_row_base(j, k, sr_shift, n_wg, n_stripes) << 15;      // (x 8 bytes, above the 12 count bits)
+            // the 12-byte store wants the value in the third register of a triple: a COPY made here, or the register allocator keeps
+            // every resident value in a triple of its own from the load on (120 registers for 40 values: spills)
+            VT vr;
+            asm volatile("v_mov_b32 %0, %1" : "=v"(vr) : "v"(v));
             for (uint32_t o = 0; o < len; o += kWave, ++slot) {
                 const uint32_t L = len - o < (uint32_t)kWave ? len - o : (uint32_t)kWave;
-                rcb[slot] = GramRec<VT>{(p + o) * 8u, ((L + 1u) >> 1) | ((L >> 1) << 6) | rb, v};
+                rcb[slot] = GramRec<VT>{(p + o) * 8u, ((L + 1u) >> 1) | ((L >> 1) << 6) | rb, vr};
             }
         } else {
             const uint32_t rb8 = (uint32_t)gram_row_base(j, k, sr_shift, n_wg, n_stripes) << 11;      // BYTE offset of the row's accumulators (x 8, signed), above the length byte
             for (uint32_t o = 0; o < len; o += kWave, ++slot)
                 rcb[slot] = GramRec<VT>{p + o, (len - o < (uint32_t)kWave ? len - o : (uint32_t)kWave) | rb8, v};
         }
-    });
+    };
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        if ((uint32_t)(u * kWave) >= n) break;
+        const uint32_t len = jl[u] >> 16;
+        if (len) scatter(s0 + (uint32_t)(u * kWave + lane), (int)(jl[u] & 0xffffu), val[u], len);
+    }
+    tail(scatter);
 }
 
 __device__ __forceinline__ float readfirst_v(float x) {

@@ -44,6 +44,8 @@ int32_t gram_plan(srx_ctx* ctx, int k, uint64_t n_rows, GramPlan& g, double entr
     }
     g.lds_bytes = (size_t)sr * widest * 8;
     if (g.lds_bytes > 163840) return fail(ctx, SRX_E_ARG, "pca: %d selected features exceed the Gram kernel's LDS stripes", k);
+    // the bucket pass keeps an entry's column and its suffix length in 16 bits each, and scans n_wg <= 64 kBucketMaxPieces owner counters
+    static_assert(163840 / 8 < 65536 && 163840 / 16 <= 64 * kBucketMaxPieces, "the LDS bound above must imply the bucket pass's");
     g.rblk = 512u;      // (round 6, assembly core: 256 / 384 / 512 / 1024 cells: stripes 2.55 / 2.55 / 2.47 / 2.49, records 0.89 / 0.87 / 0.89 / 1.07 ms) c3: bucket pass + stripe kernel 4.89 ms with 1024-cell blocks, 4.78 with 512, 5.07 with 256
     // an owner record names its piece by a 32-bit BYTE offset from its row block's first entry (a row holds at most k entries of at
     // most 16 bytes): 512 x 16384 x 16 = 2^27 — asserted, not assumed
@@ -328,7 +330,7 @@ int32_t launch_gram(srx_ctx* ctx, const RowMajor& rm, double* Gp, bool* reduce, 
         SRX_TRY(scratch(ctx, "pca_brecs", ((size_t)n_recs + kGramUnroll) * sizeof(GramRec<VT>), (void**)&recs));
         if (ctx->prof_mask & (1u << SRX_K_BUCKET)) ctx->prof[SRX_K_BUCKET].bytes += (double)n_recs * sizeof(GramRec<VT>);
         hipLaunchKernelGGL((k_bucket<VT>), dim3((unsigned)g.n_rblk), dim3(kBucketThreads),
-                           (size_t)(g.n_wg + 1 + g.rblk + 1 + kBucketGroup) * sizeof(uint32_t), ctx->stream, rm.ptr,
+                           (size_t)(g.n_wg + 1 + g.rblk + 1) * sizeof(uint32_t), ctx->stream, rm.ptr,
                            (const GramPk<VT>*)rm.pk, rm.n_rows, g.rblk, rm.k, g.sr_shift, g.n_wg, g.n_stripes, rec_base, boff, recs,
                            reinterpret_cast<uint32_t*>(rec_base + g.n_rblk + 2), n_recs, zero_first ? Gp : (double*)nullptr,
                            (uint64_t)rm.k * (rm.k + 1) / 2);
