@@ -1500,6 +1500,113 @@ int32_t srx_paga_from_counts(const uint64_t* counts, const uint64_t* sizes, uint
 int32_t srx_paga_init_positions(srx_graph* g, srx_ctx* ctx, const uint32_t* labels, uint64_t n, uint32_t n_groups,
                                 const double* connectivities, const double* pos, uint32_t dim, uint64_t seed, double* out);
 
+/* ---- spatial autocorrelation per gene on a neighbour graph: Moran's I and Geary's C ------------------------------------------
+ * What sc.metrics.morans_i / sc.metrics.gearys_c give over obsp["connectivities"], and squidpy's gr.spatial_autocorr over a
+ * spatial graph with symmetric weights, with the z-scores PySAL's esda reports under the normality assumption.  Not in the
+ * reference; the definition here is what is tested.  NOT compared: scanpy, squidpy, esda (not installed where this was built).
+ *
+ * Input: the current stored values x of a CSR matrix (N = n_rows cells x G = n_cols genes, f32 or f64 storage) and a symmetric
+ *   weighted graph w on the same N cells with zero diagonal: the connectivities C of a graph handle, read where they lie, or
+ *   a caller-supplied CSR with exactly the contract of srx_louvain_csr.  nnz = the stored entries of the graph.
+ * Five integer tables per gene g, all over STORED entries only (the implicit zeros enter by arithmetic, below); rint is
+ *   round-to-nearest-even, every product is rounded to f64 once, in the order the brackets give, no FMA contraction:
+ *   S_g = sum_i rint(x_ig 2^s_S)                 Q_g = sum_i rint((x_ig x_ig) 2^s_Q)       (srx_group_moments with one group,
+ *                                                                                           bit for bit)
+ *   dq_i = sum_j rint(w_ij 2^s_w), an integer;   W = sum_i dq_i;   d_i = f64(dq_i) 2^-s_w  (converted once)
+ *   A_g = sum_i rint((d_i x_ig) 2^s_A)           B_g = sum_i rint((d_i (x_ig x_ig)) 2^s_B)
+ *   P_g = sum over the stored entries (i, j) of the graph with j > i, both cells storing gene g, of
+ *         rint((w_ij (x_ig x_jg)) 2^s_P)         (the strict upper triangle: a pair is visited once; the full double sum is 2 P)
+ *   and from the graph alone  S1 = sum_ij rint((w_ij w_ij) 2^s_1),  S2 = sum_i rint((d_i d_i) 2^s_2).
+ * Scales.  e(v) = the smallest integer with v < 2^e (0 for v = 0), taken no lower than -30, as for srx_group_moments;
+ *   e_x = e(max |x|), e_w = e(max w), e_d = e(max d_i);  L_N = ceil(log2 N), L_E = ceil(log2 nnz):
+ *   s_S = 62 - e_x - L_N          s_Q = 62 - 2 e_x - L_N          s_w = 62 - e_w - L_E          s_1 = 62 - 2 e_w - L_E
+ *   s_A = 62 - e_d - e_x - L_N    s_B = 62 - e_d - 2 e_x - L_N    s_P = 62 - e_w - 2 e_x - L_E  s_2 = 62 - 2 e_d - L_N
+ *   Every term is at most 2^(62 - L) in magnitude and there are at most 2^L of them, so no total can pass 2^62 and every sum
+ *   fits a signed 64-bit integer; the tables do not depend on the order of the rows or of the edges and are bit-identical
+ *   from call to call; integer counts with dyadic weights give exact tables while the scales are not negative; otherwise
+ *   |table - exact| <= (number of terms) 2^-(scale + 1) (for A and B: relative to the d_i above, which are themselves within
+ *   (row length) 2^-(s_w + 1) of the exact row sums).  A scale may be negative; none is capped.  Admitted range: max |x|,
+ *   max w and max d_i below 2^255 (refused beyond: x x, d (x x) and w (x x) must stay finite and every 2^scale a normal
+ *   double; the smallest scale is then about -830).
+ * Statistics: host code on the tables, in x87 extended precision (long double, 64-bit significand: every table converts
+ *   exactly).  With S, Q, A, B, P, W the tables times 2^-scale (exact), N as a long double, every operation rounded once in
+ *   the order written:
+ *   den: in integers.  a = N Q_int and b = S_int^2 are formed exactly in 128 bits; sh = 2 s_S - s_Q = 62 - L_N;
+ *        D = a - (b >> sh) (exact), r = b mod 2^sh.  N den 2^(2 s_S) = D 2^sh - r exactly, so den > 0 exactly when D >= 1.
+ *        den = ((ld(D) 2^sh - ld(r)) 2^(-2 s_S)) / N                                  relative error at most 2^-61
+ *   A gene whose den is not > 0 is constant (all-zero genes included): its I, C and both z are NaN, as in scanpy, and it is
+ *   counted in info.genes_constant.  (The decision is exact where the tables are; a constant gene of values whose squares
+ *   are not representable can land either side of 0.)
+ *   t1 = 2 P;  t2 = (2 (S A)) / N;  t3 = (((S S) W) / N) / N;  num_I = (t1 - t2) + t3
+ *   I = ((N num_I) / W) / den                  |I - I(tables)| <= 2^-52 |I| + 2^-60 (N / (W den)) (|t1| + |t2| + |t3|)
+ *   num_C = B - 2 P;  C = (((N - 1) num_C) / W) / den                                 |C - C(tables)| <= 2^-52 |C|
+ *   (num_I cancels heavily when I is near 0: its bound is absolute in the terms; everything else is relative.)
+ *   These are the textbook double sums with z = x - m over ALL cells, m = S / N, the implicit zeros included:
+ *   sum_ij w_ij z_i z_j = 2P - 2 m A + m^2 W,   sum_ij w_ij (x_i - x_j)^2 = 2B - 4P,   sum_i z_i^2 = Q - N m^2 = den,
+ *   I = (N / W) sum_ij w_ij z_i z_j / den,      C = (N - 1) sum_ij w_ij (x_i - x_j)^2 / (2 W den).
+ * z-scores under normality (Cliff & Ord; esda's formulas).  s0 = W, s1 = 2 S1 2^-s_1, s2 = 4 S2 2^-s_2 (exact in long double):
+ *   E[I] = -1 / (N - 1)         Var[I] = (N^2 s1 - N s2 + 3 s0^2) / ((N^2 - 1) s0^2) - E[I]^2
+ *   E[C] = 1                    Var[C] = ((2 s1 + s2)(N - 1) - 4 s0^2) / (2 (N + 1) s0^2)
+ *   z = (stat - E) / sqrt(Var), from the long double stat; NaN where Var is not > 0.
+ * Refusals, each with a message.  SRX_E_ARG: a NULL handle, a CSC handle, more than one rank, 2^32 - 1 rows or more, a graph
+ *   whose n differs from n_rows, handles of different contexts, N < 2, a graph without stored entries (W = 0), max |x|, max w
+ *   or max d_i not below 2^255, everything srx_louvain_csr refuses.  SRX_E_NAN: a stored value is NaN or Inf.  SRX_E_OOM: the
+ *   tables do not fit.  m is never modified: its values, version, moments cache and resident PCA result stay as they were
+ *   (the pattern-only gene tiles of srx_matrix_prepare are built if the handle has none yet); the graph handle is only read.
+ * Out of scope: row-standardised or otherwise asymmetric weights (squidpy's default transformation; the directed distances D
+ *   are not accepted either), dense values such as obsm columns, permutation p-values, multiple-testing correction, sharded
+ *   contexts. */
+typedef struct srx_autocorr_opts {
+    uint32_t rows_per_block;   /* rows a workgroup of the walk takes; 0 = chosen from N and the gene tiles.  The tables do not
+                                  depend on it.  NULL opts = {0}                                                            */
+    uint32_t reserved_;
+} srx_autocorr_opts;
+typedef struct srx_autocorr_out {   /* host buffers of n_cols entries, each may be NULL */
+    double*  morans_i;
+    double*  gearys_c;
+    double*  z_i;
+    double*  z_c;
+    double*  sum;          /* f64(table) 2^-scale: S, Q, A, B, P */
+    double*  sumsq;
+    double*  dsum;
+    double*  dsumsq;
+    double*  cross;
+    int64_t* sum_int;      /* the tables themselves */
+    int64_t* sumsq_int;
+    int64_t* dsum_int;
+    int64_t* dsumsq_int;
+    int64_t* cross_int;
+} srx_autocorr_out;
+typedef struct srx_autocorr_info {
+    uint64_t n, n_genes, nnz;                 /* N, G, stored entries of the graph                                        */
+    int32_t  s_sum, s_sumsq, s_dsum, s_dsumsq, s_cross, s_w, s_1, s_2;     /* the scales s_S, s_Q, s_A, s_B, s_P, s_w, s_1, s_2 */
+    double   max_abs, max_weight, max_degree; /* max |x|, max w, max d_i                                                  */
+    int64_t  w_int, s1_int, s2_int;           /* W, S1, S2 as integers                                                    */
+    double   w, s1, s2;                       /* s0 = W, s1, s2 rounded to f64                                            */
+    double   e_i, var_i, e_c, var_c;
+    uint64_t genes_constant;
+    double   ms;                              /* hipEvent time of the device work: the three parts below                  */
+    double   ms_graph, ms_moments, ms_walk;   /* the graph sums with their read-backs | S, Q, A, B | the walk for P       */
+    double   ms_wmax, ms_degrees, ms_s2;      /* per kernel, within ms_graph: k_ac_wmax, k_ac_degrees, k_ac_s2            */
+    double   ms_sum_sumsq, ms_dsum_dsumsq;    /* per kernel, within ms_moments: the {S, Q} launch, the {A, B} launch      */
+} srx_autocorr_info;
+/* The handle's C, read where it lies.  opts, out and info may be NULL. */
+int32_t srx_autocorr(srx_mat* m, srx_graph* g, const srx_autocorr_opts* opts, srx_autocorr_out* out, srx_autocorr_info* info);
+/* The same on a caller-supplied symmetric graph of n vertices, validated on the device as srx_louvain_csr validates its input. */
+int32_t srx_autocorr_csr(srx_mat* m, const uint64_t* indptr, const uint32_t* indices, const double* weights, uint64_t n,
+                         const srx_autocorr_opts* opts, srx_autocorr_out* out, srx_autocorr_info* info);
+/* The scale rule alone, host code: info goes in with n, nnz, max_abs, max_weight and max_degree set and comes back with the
+ * eight scales; the device calls use exactly this.  SRX_E_ARG: NULL, n < 2 or n >= 2^32 - 1, nnz == 0, a maximum that is
+ * negative, NaN or not below 2^255. */
+int32_t srx_autocorr_scales(srx_autocorr_info* info);
+/* The statistics from five tables of n_genes integers each: host code, no GPU; the two calls above end in it.  info goes in
+ * with n, the eight scales and w_int, s1_int, s2_int set, and comes back with n_genes, w, s1, s2, both E and Var and
+ * genes_constant filled as well; every other field is left as it was.  out: its *_int pointers are ignored, the f64 tables
+ * are written from the input.  SRX_E_ARG: a NULL table or info, n < 2 or n >= 2^32 - 1, w_int <= 0, 2 s_sum - s_sumsq outside
+ * 0 .. 62. */
+int32_t srx_autocorr_from_tables(const int64_t* sum_int, const int64_t* sumsq_int, const int64_t* dsum_int, const int64_t* dsumsq_int,
+                                 const int64_t* cross_int, uint64_t n_genes, srx_autocorr_info* info, srx_autocorr_out* out);
+
 /* ---- Harmony: batch integration of the PCA scores, what sc.external.pp.harmony_integrate gives obsm["X_pca_harmony"] --------
  * Not in the reference.  This is Harmony (Korsunsky et al. 2019) as harmonypy runs it for ONE batch covariate, RESTATED below
  * with its random choices replaced by hashes so that the result is bit-identical from call to call.  The definition here is

@@ -1239,6 +1239,76 @@ pub mod processing_free {
             }))?;
             Array2::from_shape_vec((labels.len(), dim), out).map_err(|e| anyhow!("paga_init_positions: {e}"))
         }
+        /// Moran's I and Geary's C per gene with their z-scores under normality; a constant gene has NaN statistics.
+        pub struct Autocorr {
+            pub morans_i: Vec<f64>,
+            pub gearys_c: Vec<f64>,
+            pub z_i: Vec<f64>,
+            pub z_c: Vec<f64>,
+            pub info: SrxAutocorrInfo,
+        }
+        /// The buffers of one call: `run` receives the `SrxAutocorrOut` that points at them (the tables are not asked for).
+        fn autocorr_call(n_genes: usize, run: impl FnOnce(*mut SrxAutocorrOut, *mut SrxAutocorrInfo) -> anyhow::Result<()>)
+                         -> anyhow::Result<Autocorr> {
+            let mut r = Autocorr { morans_i: vec![0.0; n_genes], gearys_c: vec![0.0; n_genes], z_i: vec![0.0; n_genes],
+                                   z_c: vec![0.0; n_genes], info: unsafe { std::mem::zeroed() } };
+            let mut o: SrxAutocorrOut = unsafe { std::mem::zeroed() };
+            o.morans_i = r.morans_i.as_mut_ptr();
+            o.gearys_c = r.gearys_c.as_mut_ptr();
+            o.z_i = r.z_i.as_mut_ptr();
+            o.z_c = r.z_c.as_mut_ptr();
+            run(&mut o, &mut r.info)?;
+            Ok(r)
+        }
+        /// Which genes vary smoothly along the cells' k-NN graph (srx_neighbors_result, then srx_autocorr with the
+        /// connectivities where they lie): four numbers per gene come back, nothing per cell.
+        pub fn gene_autocorr(adata: &IMAnnData, n_neighbors: usize, n_pcs: usize) -> anyhow::Result<Autocorr> {
+            let kopts = SrxKnnOpts { k: n_neighbors as i32, n_dims: n_pcs as i32, include_self: 0, reserved: 0 };
+            let n_genes = adata.n_vars();
+            with_resident(adata, |x| {
+                let mut g: *mut SrxGraph = null_mut();
+                x.ctx.check(unsafe { srx_neighbors_result(x.mat, &kopts, null_mut(), &mut g) })?;
+                let out = autocorr_call(n_genes, |o, info| x.ctx.check(unsafe { srx_autocorr(x.mat, g, std::ptr::null(), o, info) }));
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        /// The same on any symmetric weighted graph over the cells the caller holds (srx_autocorr_csr).
+        pub fn autocorr_csr(adata: &IMAnnData, graph: &CsrMatrix<f64>) -> anyhow::Result<Autocorr> {
+            let n = graph.nrows();
+            let n_genes = adata.n_vars();
+            let indptr: Vec<u64> = graph.row_offsets().iter().map(|&v| v as u64).collect();
+            let indices: Vec<u32> = graph.col_indices().iter().map(|&v| v as u32).collect();
+            with_resident(adata, |x| autocorr_call(n_genes, |o, info| {
+                x.ctx.check(unsafe { srx_autocorr_csr(x.mat, indptr.as_ptr(), indices.as_ptr(), graph.values().as_ptr(), n as u64,
+                                                      std::ptr::null(), o, info) })
+            }))
+        }
+        /// The eight fixed-point scales from `info`'s n, nnz, max_abs, max_weight and max_degree (srx_autocorr_scales: host code).
+        pub fn autocorr_scales(mut info: SrxAutocorrInfo) -> anyhow::Result<SrxAutocorrInfo> {
+            match unsafe { srx_autocorr_scales(&mut info) } {
+                SRX_OK => Ok(info),
+                rc => Err(anyhow!("srx_autocorr_scales: status {rc}")),
+            }
+        }
+        /// The statistics from the five integer tables (host code in the library: no device); `info` carries n, the scales and
+        /// the graph's integer sums.
+        pub fn autocorr_from_tables(tables: [&[i64]; 5], info: SrxAutocorrInfo) -> anyhow::Result<Autocorr> {
+            let n_genes = tables[0].len();
+            if tables.iter().any(|t| t.len() != n_genes) {
+                bail!("autocorr_from_tables: five tables of one length expected");
+            }
+            let mut filled = info;
+            let mut r = autocorr_call(n_genes, |o, _| {
+                match unsafe { srx_autocorr_from_tables(tables[0].as_ptr(), tables[1].as_ptr(), tables[2].as_ptr(), tables[3].as_ptr(),
+                                                        tables[4].as_ptr(), n_genes as u64, &mut filled, o) } {
+                    SRX_OK => Ok(()),
+                    rc => Err(anyhow!("srx_autocorr_from_tables: status {rc}")),
+                }
+            })?;
+            r.info = filled;                                              // w, s1, s2, E, Var, genes_constant as the library filled them
+            Ok(r)
+        }
         fn graph_to_host(c: &Ctx, g: *mut SrxGraph) -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>)> {
             let mut info: SrxGraphInfo = unsafe { std::mem::zeroed() };
             c.check(unsafe { srx_graph_info_get(g, &mut info) })?;

@@ -670,6 +670,71 @@ pub struct SrxPagaTables {      // `srx_paga_tables`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxAutocorrOpts {      // `srx_autocorr_opts`
+    pub rows_per_block: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxAutocorrOut {      // `srx_autocorr_out`
+    pub morans_i: *mut f64,
+    pub gearys_c: *mut f64,
+    pub z_i: *mut f64,
+    pub z_c: *mut f64,
+    pub sum: *mut f64,
+    pub sumsq: *mut f64,
+    pub dsum: *mut f64,
+    pub dsumsq: *mut f64,
+    pub cross: *mut f64,
+    pub sum_int: *mut i64,
+    pub sumsq_int: *mut i64,
+    pub dsum_int: *mut i64,
+    pub dsumsq_int: *mut i64,
+    pub cross_int: *mut i64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxAutocorrInfo {      // `srx_autocorr_info`
+    pub n: u64,
+    pub n_genes: u64,
+    pub nnz: u64,
+    pub s_sum: i32,
+    pub s_sumsq: i32,
+    pub s_dsum: i32,
+    pub s_dsumsq: i32,
+    pub s_cross: i32,
+    pub s_w: i32,
+    pub s_1: i32,
+    pub s_2: i32,
+    pub max_abs: f64,
+    pub max_weight: f64,
+    pub max_degree: f64,
+    pub w_int: i64,
+    pub s1_int: i64,
+    pub s2_int: i64,
+    pub w: f64,
+    pub s1: f64,
+    pub s2: f64,
+    pub e_i: f64,
+    pub var_i: f64,
+    pub e_c: f64,
+    pub var_c: f64,
+    pub genes_constant: u64,
+    pub ms: f64,
+    pub ms_graph: f64,
+    pub ms_moments: f64,
+    pub ms_walk: f64,
+    pub ms_wmax: f64,
+    pub ms_degrees: f64,
+    pub ms_s2: f64,
+    pub ms_sum_sumsq: f64,
+    pub ms_dsum_dsumsq: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxHarmonyOpts {      // `srx_harmony_opts`
     pub theta: f64,
     pub sigma: f64,
@@ -997,6 +1062,14 @@ extern "C" {
                                 info: *mut SrxPagaInfo) -> i32;
     pub fn srx_paga_init_positions(g: *mut SrxGraph, ctx: *mut SrxCtx, labels: *const u32, n: u64, n_groups: u32,
                                    connectivities: *const f64, pos: *const f64, dim: u32, seed: u64, out: *mut f64) -> i32;
+    pub fn srx_autocorr(m: *mut SrxMat, g: *mut SrxGraph, opts: *const SrxAutocorrOpts, out: *mut SrxAutocorrOut,
+                        info: *mut SrxAutocorrInfo) -> i32;
+    pub fn srx_autocorr_csr(m: *mut SrxMat, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,
+                            opts: *const SrxAutocorrOpts, out: *mut SrxAutocorrOut, info: *mut SrxAutocorrInfo) -> i32;
+    pub fn srx_autocorr_scales(info: *mut SrxAutocorrInfo) -> i32;
+    pub fn srx_autocorr_from_tables(sum_int: *const i64, sumsq_int: *const i64, dsum_int: *const i64,
+                                    dsumsq_int: *const i64, cross_int: *const i64, n_genes: u64,
+                                    info: *mut SrxAutocorrInfo, out: *mut SrxAutocorrOut) -> i32;
     pub fn srx_harmony_result(m: *mut SrxMat, batch: *const u32, n_batches: u32, opts: *const SrxHarmonyOpts,
                               out: *mut *mut SrxHarmony, info: *mut SrxHarmonyInfo) -> i32;
     pub fn srx_harmony_points(ctx: *mut SrxCtx, points: *const f64, n: u64, d: u64, batch: *const u32,

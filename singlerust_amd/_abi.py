@@ -359,6 +359,28 @@ class PagaTables(C.Structure):      # srx_paga_tables
     _fields_ = [("sizes", P), ("out_edges", P), ("counts", P), ("connectivities", P), ("expected", P), ("tree", P)]
 
 
+class AutocorrOpts(C.Structure):      # srx_autocorr_opts
+    _fields_ = [("rows_per_block", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class AutocorrOut(C.Structure):      # srx_autocorr_out
+    _fields_ = [("morans_i", P), ("gearys_c", P), ("z_i", P), ("z_c", P), ("sum", P), ("sumsq", P), ("dsum", P),
+                ("dsumsq", P), ("cross", P), ("sum_int", P), ("sumsq_int", P), ("dsum_int", P), ("dsumsq_int", P),
+                ("cross_int", P)]
+
+
+class AutocorrInfo(C.Structure):      # srx_autocorr_info
+    _fields_ = [("n", C.c_uint64), ("n_genes", C.c_uint64), ("nnz", C.c_uint64), ("s_sum", C.c_int32),
+                ("s_sumsq", C.c_int32), ("s_dsum", C.c_int32), ("s_dsumsq", C.c_int32), ("s_cross", C.c_int32),
+                ("s_w", C.c_int32), ("s_1", C.c_int32), ("s_2", C.c_int32), ("max_abs", C.c_double),
+                ("max_weight", C.c_double), ("max_degree", C.c_double), ("w_int", C.c_int64), ("s1_int", C.c_int64),
+                ("s2_int", C.c_int64), ("w", C.c_double), ("s1", C.c_double), ("s2", C.c_double), ("e_i", C.c_double),
+                ("var_i", C.c_double), ("e_c", C.c_double), ("var_c", C.c_double), ("genes_constant", C.c_uint64),
+                ("ms", C.c_double), ("ms_graph", C.c_double), ("ms_moments", C.c_double), ("ms_walk", C.c_double),
+                ("ms_wmax", C.c_double), ("ms_degrees", C.c_double), ("ms_s2", C.c_double),
+                ("ms_sum_sumsq", C.c_double), ("ms_dsum_dsumsq", C.c_double)]
+
+
 class HarmonyOpts(C.Structure):      # srx_harmony_opts
     _fields_ = [("theta", C.c_double), ("sigma", C.c_double), ("lambda_", C.c_double),
                 ("epsilon_cluster", C.c_double), ("epsilon_harmony", C.c_double), ("seed", C.c_uint64),
@@ -549,6 +571,12 @@ SIGNATURES = {
     "srx_paga_csr": (C.c_int32, [P, P, P, C.c_uint64, P, C.c_uint32, C.POINTER(PagaTables), C.POINTER(PagaInfo)]),
     "srx_paga_from_counts": (C.c_int32, [P, P, C.c_uint32, C.POINTER(PagaTables), C.POINTER(PagaInfo)]),
     "srx_paga_init_positions": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, P, P, C.c_uint32, C.c_uint64, P]),
+    "srx_autocorr": (C.c_int32, [P, P, C.POINTER(AutocorrOpts), C.POINTER(AutocorrOut), C.POINTER(AutocorrInfo)]),
+    "srx_autocorr_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(AutocorrOpts), C.POINTER(AutocorrOut),
+                                     C.POINTER(AutocorrInfo)]),
+    "srx_autocorr_scales": (C.c_int32, [C.POINTER(AutocorrInfo)]),
+    "srx_autocorr_from_tables": (C.c_int32, [P, P, P, P, P, C.c_uint64, C.POINTER(AutocorrInfo),
+                                             C.POINTER(AutocorrOut)]),
     "srx_harmony_result": (C.c_int32, [P, P, C.c_uint32, C.POINTER(HarmonyOpts), C.POINTER(P), C.POINTER(HarmonyInfo)]),
     "srx_harmony_points": (C.c_int32, [P, P, C.c_uint64, C.c_uint64, P, C.c_uint32, C.POINTER(HarmonyOpts),
                                        C.POINTER(P), C.POINTER(HarmonyInfo)]),

@@ -867,6 +867,22 @@ struct Paga {
         return srx_paga_tables{sizes.data(), out_edges.data(), counts.data(), connectivities.data(), expected.data(), tree.data()};
     }
 };
+// Moran's I and Geary's C per gene with their z-scores under normality, the five tables as f64 and as the integers themselves
+// (srx_autocorr / srx_autocorr_csr); a constant gene has NaN statistics and is counted in info.genes_constant
+struct Autocorr {
+    std::vector<double> morans_i, gearys_c, z_i, z_c, sum, sumsq, dsum, dsumsq, cross;
+    std::vector<std::int64_t> sum_int, sumsq_int, dsum_int, dsumsq_int, cross_int;
+    srx_autocorr_info info{};
+    explicit Autocorr(std::size_t G = 0)
+        : morans_i(G), gearys_c(G), z_i(G), z_c(G), sum(G), sumsq(G), dsum(G), dsumsq(G), cross(G), sum_int(G), sumsq_int(G),
+          dsum_int(G), dsumsq_int(G), cross_int(G) {}
+    // the buffers as the C calls take them (the vectors must not be resized while it is in use)
+    srx_autocorr_out out() {
+        return srx_autocorr_out{morans_i.data(), gearys_c.data(), z_i.data(), z_c.data(), sum.data(), sumsq.data(), dsum.data(),
+                                dsumsq.data(), cross.data(), sum_int.data(), sumsq_int.data(), dsum_int.data(), dsumsq_int.data(),
+                                cross_int.data()};
+    }
+};
 class Graph {
 public:
     // k-NN over the scores the last PCA on `a` left on the device, then the graph of it (srx_neighbors_result)
@@ -963,6 +979,13 @@ public:
                                             out.empty() ? nullptr : out.data()));
         return out;
     }
+    // Moran's I and Geary's C of every gene of `a` on the connectivities, read where they lie (srx_autocorr)
+    Autocorr autocorr(const IMAnnData& a) const {
+        Autocorr r(a.n_vars());
+        srx_autocorr_out o = r.out();
+        ctx_->check(srx_autocorr(a.x(), h_, nullptr, &o, &r.info));
+        return r;
+    }
     // Diffusion map of the connectivities, read where they lie (srx_diffmap): the n_comps algebraically largest eigenpairs of
     // the transition operator, descending; `opts` null: the defaults; `info` (may be null) receives the call's srx_diffmap_info
     Diffmap diffmap(const srx_diffmap_opts* opts = nullptr, srx_diffmap_info* info = nullptr) const {
@@ -1032,6 +1055,35 @@ inline Paga paga_from_counts(const std::vector<std::uint64_t>& counts, const std
     const std::int32_t rc = srx_paga_from_counts(counts.data(), sizes.data(), G, &t, &p.info);
     if (rc != SRX_OK) throw Error(rc, srx_last_error(nullptr));
     return p;
+}
+// Moran's I and Geary's C on any symmetric weighted graph over the cells of `a` (CSR, ascending columns, weights > 0, no
+// diagonal): srx_autocorr_csr
+inline Autocorr autocorr_csr(const IMAnnData& a, const std::vector<std::uint64_t>& indptr, const std::vector<std::uint32_t>& indices,
+                             const std::vector<double>& weights) {
+    if (indptr.empty() || indices.size() != weights.size() || indptr.back() != indices.size())
+        throw Error(SRX_E_ARG, "autocorr_csr: indptr (n + 1), indices and weights (indptr[n] each) expected");
+    Autocorr r(a.n_vars());
+    srx_autocorr_out o = r.out();
+    a.ctx().check(srx_autocorr_csr(a.x(), indptr.data(), indices.empty() ? nullptr : indices.data(),
+                                   weights.empty() ? nullptr : weights.data(), indptr.size() - 1, nullptr, &o, &r.info));
+    return r;
+}
+// the eight fixed-point scales from info's n, nnz, max_abs, max_weight and max_degree (srx_autocorr_scales: host code)
+inline srx_autocorr_info autocorr_scales(srx_autocorr_info info) {
+    const std::int32_t rc = srx_autocorr_scales(&info);
+    if (rc != SRX_OK) throw Error(rc, srx_last_error(nullptr));
+    return info;
+}
+// the statistics from the five integer tables (host code in the library: no device); `info` carries n, the scales and the
+// graph's integer sums
+inline Autocorr autocorr_from_tables(const Autocorr& tables, const srx_autocorr_info& info) {
+    Autocorr r = tables;
+    r.info = info;
+    srx_autocorr_out o = r.out();
+    const std::int32_t rc = srx_autocorr_from_tables(tables.sum_int.data(), tables.sumsq_int.data(), tables.dsum_int.data(),
+                                                     tables.dsumsq_int.data(), tables.cross_int.data(), tables.sum_int.size(), &r.info, &o);
+    if (rc != SRX_OK) throw Error(rc, srx_last_error(nullptr));
+    return r;
 }
 // Diffusion map of any symmetric weighted graph without empty rows (srx_diffmap_csr), and the pseudotime of such a result
 inline Diffmap diffmap_csr(Context& ctx, const std::vector<std::uint64_t>& indptr, const std::vector<std::uint32_t>& indices,

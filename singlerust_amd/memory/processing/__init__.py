@@ -8,6 +8,7 @@ import numpy as np
 from ... import _ffi as F
 from ...anndata import DeviceCsr, Direction, FlexValue, IMAnnData
 from . import dim_red
+from .autocorr import autocorr_csr, autocorr_from_tables, autocorr_scales, gearys_c, gene_autocorr, morans_i
 from .diffmap import diffmap, diffmap_csr, dpt, dpt_from, graph_diffmap, graph_transitions
 from .doublets import Doublets, doublet_scores_knn, doublets_threshold, scrublet, simulate_doublets
 from .harmony import Harmony, encode_batches, harmony_integrate, harmony_points
