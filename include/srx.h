@@ -1188,7 +1188,7 @@ int32_t srx_clipped_group_moments(srx_mat* m, const uint32_t* labels, uint32_t n
  *   Levenberg-Marquardt from (1, 1).  opts.a == opts.b == 0 means "fit from min_dist, spread".
  * Defaults (NULL opts): min_dist 0.5, spread 1.0 (scanpy's), gamma 1, alpha0 1, R 5, dim 2, seed 0, the PCA start;
  *   n_epochs == 0 means 500 for n <= 10 000, else 200.
- * Out of scope: spectral initialisation, transforming new points, densMAP, supervised and non-Euclidean outputs.
+ * Out of scope: spectral initialisation, densMAP, supervised and non-Euclidean outputs (new points: the next section).
  * Refused with SRX_E_ARG and a message, nothing written: dim not 2 or 3; R outside 0..32; a, b (unless both 0), gamma,
  *   alpha0 or spread not finite or <= 0; min_dist < 0 or > spread (or NaN); n_epochs < 0 or > 2^20; stop_after < 0 or
  *   > n_epochs; an unknown start; a NaN or Inf start; the PCA start without a usable result (none, or fewer than dim
@@ -1224,6 +1224,104 @@ int32_t srx_umap_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* indic
 int32_t srx_graph_embedding_fetch(srx_graph* g, double* out, uint32_t* dim_out);
 /* Host only.  SRX_E_ARG: spread or min_dist not finite, spread <= 0, min_dist < 0 or > spread, a null output. */
 int32_t srx_umap_fit_ab(double spread, double min_dist, double* a, double* b);
+
+/* ---- new cells on a fitted data set: the label vote and the UMAP transform; what sc.tl.ingest gives obs[...] and
+ * obsm["X_umap"] of the query ------------------------------------------------------------------------------------------------
+ * Not in the reference.  The transform is umap-learn's UMAP.transform RESTATED so that the result is bit-identical from call
+ * to call; the vote is pandas' mode as scanpy's ingest.map_labels takes it.  The definition here is what is tested.
+ * NOT compared: umap-learn, scanpy (not installed).  Projecting the new cells (srx_pca_transform) and finding their
+ * neighbours among the fitted ones (srx_knn_points / srx_knn_index_search) are the sections above.
+ *
+ * Input: a k-NN list of n_query rows x kq entries, u32 indices into n_ref reference points and f64 distances, finite and
+ *   >= 0; 3 <= kq <= 64, kq <= n_ref < 2^32; a row never names one reference twice; rows need not be sorted.  Reference
+ *   positions Yref: n_ref x dim f64, finite, dim 2 or 3.  Everything below is stated on the row in ASCENDING REFERENCE INDEX
+ *   order, slot s = 0..kq-1 (the order k_graph_rows makes), so the result does not depend on the order of the entries
+ *   within an input row; j_s and d_s are the index and distance of slot s.
+ * Membership of row i (umap-learn's smooth_knn_dist with rho_i = 0).  The row's NEAREST entry, the minimum by (distance,
+ *   index), is left out of the sum S and still gets a weight: smooth_knn_dist starts at column 1 in a transform as in a fit,
+ *   where column 0 is the point itself.  Over the other m = kq - 1 entries, with T = log2(kq):
+ *   c_i      = those with d = 0;   S_i(s) = c_i + sum over {d > 0} of exp(-d / s).
+ *   sigma*_i = the root of S_i(s) = T when c_i < T, solved to |S_i - T| <= 1e-9 by the rule of the graph section's kernel:
+ *              from lo = hi = the largest d, double hi while S(hi) < T (or halve lo while S(lo) >= T), then halve the bracket
+ *              — mid = lo + 0.5 (hi - lo); S(mid) < T moves lo, else hi — until it is one ulp wide or |S(mid) - T| <= 1e-13;
+ *              sigma* is the upper end.  Else 0 (rows_no_root).
+ *   sigma_i  = max(sigma*_i, 1e-3 * (sum_s d_s) / kq), the sum over all kq entries (rows_clamped: the floor is the larger).
+ *              A departure: umap-learn's floor uses the mean distance of the whole batch; the row's own mean keeps a row's
+ *              weights independent of which other cells are mapped with it.
+ *   A row whose kq distances are all 0 has sigma_i = 0 and every weight 1 (rows_all_zero; it counts in rows_no_root too).
+ *   w_is     = 1 when d_s = 0, else exp(-d_s / sigma_i), in f64, for all kq slots.
+ *   As in the graph section the formulas are evaluated literally: a row whose sum_s d_s overflows has floor = sigma_i = +inf,
+ *   every weight 1, and counts in rows_clamped (unless the doubling of hi overflowed as well: then sigma* = +inf itself and
+ *   the floor is not the larger); the 1e-9 holds for distances in the normal range.
+ * Start.  W_i = sum_s w_is;  y_i^0 = sum_s (w_is / W_i) * Yref[j_s] per coordinate (one division, one product per term).
+ *   Both sums are the 64-lane butterfly over the slots: v_s for s < kq, 0 for s = kq..63, then for off = 32, 16, 8, 4, 2, 1
+ *   every v_s becomes v_s + v_(s xor off).  W_i == 0: y_i^0 = the position of the nearest entry (rows_start_nearest).
+ * Schedule, negatives, epoch: srx_umap's rules on the bipartite entries e = i * kq + s, nnz = n_query * kq.  w_max = the
+ *   largest weight of the whole call; r_e, c_e(t), the sampling rule and entries_active as there.  The hash as there with
+ *   target = ((z >> 32) * n_ref) >> 32: a target is a reference point, so NO target is skipped.  Epoch t reads y_i^{t-1} and
+ *   Yref only; alpha_t = alpha0 * (1 - (t - 1) / E).  Attraction of a sampled entry (i, j_s): q and g as there with
+ *   y_j = Yref[j_s], delta_i += alpha_t * g (the head move alone, factor 1: the reference does not move).  Repulsion from
+ *   each of its R targets as there.  d2 == 0 adds nothing.  y_i^t = y_i^{t-1} + delta_i.  Lane u of the SRX_UMAP_GROUP lanes
+ *   of a query sums the entries u, u + SRX_UMAP_GROUP, ... of its row in that order (an entry's attraction, then its targets
+ *   p = 0..R-1), and the lanes meet in srx_umap's butterfly.  f64, no FMA contraction, ocml's pow.  Query rows do not
+ *   interact: a row's result does not depend on the other rows except through w_max and, through e and nnz, its place.
+ * Defaults (NULL opts; umap-learn's): alpha0 0.25 (a quarter of the fit's 1), n_epochs == 0 means 100 for n_query <= 10 000,
+ *   else 30 (a third of the fit's, rounded as umap-learn does); gamma 1, R 5, seed 0, min_dist 0.5, spread 1.0; a = b = 0
+ *   means fitted by srx_umap_fit_ab.  stop_after = s (0 = E) runs epochs 1..s of the E-epoch schedule.
+ * How: one launch holds up to chunk_epochs (0 = SRX_UMAP_TRANSFORM_CHUNK, else 1..that) epochs, a query's position staying
+ *   in registers between them; the launches run back to back on the context's stream and hand on the positions alone, so
+ *   the result is the same bits for every chunk length.
+ * Label vote.  A k-NN list n_query x k (1 <= k <= 64 and k <= n_ref, no reference twice in a row; distances are not read)
+ *   and ref_labels[n_ref] < n_groups.  label_i = the label that occurs most often among the row's k references, ties to the
+ *   LOWEST label; count_i = its number of occurrences (count / k is the confidence the Python layer reports).  Integers.
+ * Refused with SRX_E_ARG and a message, nothing written: kq outside 3..64 or > n_ref; k outside 1..64 or > n_ref (vote); an
+ *   index >= n_ref; a reference twice in a row; a negative, NaN or Inf distance; a NaN or Inf reference position; dim
+ *   not 2 or 3, or not the resident embedding's (_graph transform); a label >= n_groups; R outside 0..32; a, b (unless both 0), gamma, alpha0 or spread not finite or <= 0;
+ *   min_dist outside 0..spread; n_epochs < 0 or > SRX_UMAP_MAX_EPOCHS; stop_after outside 0..n_epochs; chunk_epochs outside
+ *   0..SRX_UMAP_TRANSFORM_CHUNK; a graph handle without an embedding (_graph transform) or without labels (_graph vote);
+ *   n_ref >= 2^32; a NULL list, position or label array where one is needed; a context with more than one rank.
+ * n_query == 0 writes nothing but info and succeeds. */
+#define SRX_UMAP_TRANSFORM_CHUNK 64   /* epochs per launch at the most: a launch stays short whatever n_epochs is */
+typedef struct srx_umap_transform_opts {
+    double   a, b;                  /* both 0: fitted from min_dist, spread */
+    double   min_dist, spread, gamma, alpha0;
+    uint64_t seed;
+    int32_t  n_epochs;              /* 0 = 100 for n_query <= 10 000, else 30 */
+    int32_t  stop_after;            /* 0 = n_epochs */
+    int32_t  negative_sample_rate;
+    int32_t  chunk_epochs;          /* 0 = SRX_UMAP_TRANSFORM_CHUNK */
+} srx_umap_transform_opts;
+typedef struct srx_umap_transform_out {   /* host buffers, each may be NULL */
+    double*   embedding;            /* n_query x dim: y after the epochs run                 */
+    double*   start;                /* n_query x dim: y^0                                    */
+    double*   weights;              /* n_query x kq, in slot order                           */
+    uint32_t* columns;              /* n_query x kq: the row's indices ascending (the slots) */
+    double*   sigma;                /* n_query                                               */
+} srx_umap_transform_out;
+typedef struct srx_umap_transform_info {
+    uint64_t n_query, n_ref, entries_active, samples, negatives;
+    uint64_t rows_no_root, rows_clamped, rows_all_zero, rows_start_nearest;
+    uint32_t kq, dim, n_epochs, epochs_run;
+    double   a, b, w_max;
+    double   ms;                    /* hipEvent time of the device work: membership_ms + the epochs */
+    double   membership_ms;         /* the membership and start kernel alone                        */
+} srx_umap_transform_info;
+/* Everything from host pointers: indices / distances n_query x kq row-major, ref_embedding n_ref x dim row-major.  opts, out,
+ * any pointer of out, and info may be NULL. */
+int32_t srx_umap_transform_knn(srx_ctx* ctx, const uint32_t* indices, const double* distances, uint64_t n_query, uint32_t kq,
+                               const double* ref_embedding, uint64_t n_ref, uint32_t dim, const srx_umap_transform_opts* opts,
+                               srx_umap_transform_out* out, srx_umap_transform_info* info);
+/* The same against the embedding the last srx_umap left on the handle, read where it lies (n_ref = the graph's n); the handle
+ * is left as it was.  dim: what the caller's buffers are sized for; SRX_E_ARG unless it is the embedding's. */
+int32_t srx_umap_transform_graph(srx_graph* g, const uint32_t* indices, const double* distances, uint64_t n_query, uint32_t kq,
+                                 uint32_t dim, const srx_umap_transform_opts* opts, srx_umap_transform_out* out,
+                                 srx_umap_transform_info* info);
+/* The label vote; labels_out and counts_out (n_query u32 each) may be NULL. */
+int32_t srx_knn_vote(srx_ctx* ctx, const uint32_t* indices, uint64_t n_query, uint32_t k, const uint32_t* ref_labels,
+                     uint64_t n_ref, uint32_t n_groups, uint32_t* labels_out, uint32_t* counts_out);
+/* The same under the labels the last srx_louvain left on the handle, read where they lie (n_ref = the graph's n). */
+int32_t srx_knn_vote_graph(srx_graph* g, const uint32_t* indices, uint64_t n_query, uint32_t k, uint32_t* labels_out,
+                           uint32_t* counts_out);
 
 /* ---- t-SNE in 2 dimensions: perplexity affinities of a k-NN list and a Barnes-Hut layout; what sc.tl.tsne gives
  * obsm["X_tsne"] -------------------------------------------------------------------------------------------------------------

@@ -1147,6 +1147,60 @@ pub mod processing_free {
                 Ok((labels, info.modularity))
             })
         }
+        /// Labels for new cells from a fitted data set (srx_knn_vote): `indices` is the new cells' k-NN list among the
+        /// reference cells (what `neighbors_of` returns), `ref_labels` one label below `n_groups` per reference cell.  Returns
+        /// per new cell the most frequent label among its neighbours (ties to the lowest label) and its share of the k.
+        pub fn knn_vote(indices: &Array2<u32>, ref_labels: &[u32], n_groups: u32) -> anyhow::Result<(Vec<u32>, Vec<f64>)> {
+            let (n, k) = indices.dim();
+            let i: Vec<u32> = indices.iter().copied().collect();                   // row-major
+            with_ctx(|c| {
+                let (mut labels, mut counts) = (vec![0u32; n], vec![0u32; n]);
+                c.check(unsafe {
+                    srx_knn_vote(c.0, i.as_ptr(), n as u64, k as u32, ref_labels.as_ptr(), ref_labels.len() as u64, n_groups,
+                                 labels.as_mut_ptr(), counts.as_mut_ptr())
+                })?;
+                Ok((labels, counts.iter().map(|&v| v as f64 / k.max(1) as f64).collect()))
+            })
+        }
+        /// New cells placed in a fitted UMAP without refitting it (srx_umap_transform_knn, every default of include/srx.h):
+        /// `indices` / `distances` are the new cells' k-NN list among the reference cells (3 <= k <= 64), `ref_embedding` the
+        /// reference's `n_ref x dim` layout (dim 2 or 3).  Returns `n_query x dim` and the call's info.
+        pub fn umap_transform(indices: &Array2<u32>, distances: &Array2<f64>, ref_embedding: &Array2<f64>)
+                              -> anyhow::Result<(Array2<f64>, SrxUmapTransformInfo)> {
+            let ((n, k), dd, (n_ref, dim)) = (indices.dim(), distances.dim(), ref_embedding.dim());
+            if dd != (n, k) {
+                bail!("umap_transform: indices are {n} x {k}, distances {} x {}", dd.0, dd.1);
+            }
+            let i: Vec<u32> = indices.iter().copied().collect();                   // row-major
+            let d: Vec<f64> = distances.iter().copied().collect();
+            let y: Vec<f64> = ref_embedding.iter().copied().collect();
+            with_ctx(|c| {
+                let mut emb = vec![0.0f64; n * dim];
+                let mut tout: SrxUmapTransformOut = unsafe { std::mem::zeroed() };
+                tout.embedding = emb.as_mut_ptr();
+                let mut tinfo: SrxUmapTransformInfo = unsafe { std::mem::zeroed() };
+                c.check(unsafe {
+                    srx_umap_transform_knn(c.0, i.as_ptr(), d.as_ptr(), n as u64, k as u32, y.as_ptr(), n_ref as u64, dim as u32,
+                                           std::ptr::null(), &mut tout, &mut tinfo)
+                })?;
+                Ok((Array2::from_shape_vec((n, dim), emb).map_err(|e| anyhow!("umap_transform: {e}"))?, tinfo))
+            })
+        }
+        /// The two calls against what lies on the device with a graph handle: the labels of its last srx_louvain
+        /// (srx_knn_vote_graph) and the embedding of its last srx_umap (srx_umap_transform_graph, `dim` = that embedding's).
+        #[allow(dead_code)]
+        fn ingest_on_graph(c: &Ctx, g: *mut SrxGraph, indices: &[u32], distances: &[f64], n: usize, k: usize, dim: usize)
+                           -> anyhow::Result<(Vec<u32>, Vec<u32>, Vec<f64>)> {
+            let (mut labels, mut counts, mut emb) = (vec![0u32; n], vec![0u32; n], vec![0.0f64; n * dim]);
+            c.check(unsafe { srx_knn_vote_graph(g, indices.as_ptr(), n as u64, k as u32, labels.as_mut_ptr(), counts.as_mut_ptr()) })?;
+            let mut tout: SrxUmapTransformOut = unsafe { std::mem::zeroed() };
+            tout.embedding = emb.as_mut_ptr();
+            c.check(unsafe {
+                srx_umap_transform_graph(g, indices.as_ptr(), distances.as_ptr(), n as u64, k as u32, dim as u32, std::ptr::null(), &mut tout,
+                                         null_mut())
+            })?;
+            Ok((labels, counts, emb))
+        }
         /// The labels the last srx_louvain left with a graph handle (srx_graph_labels_fetch).
         #[allow(dead_code)]
         fn graph_labels(c: &Ctx, g: *mut SrxGraph, n: usize) -> anyhow::Result<Vec<u32>> {

@@ -13,6 +13,7 @@ pub const SRX_LOUVAIN_MAX_LEVELS: i32 = 32;
 pub const SRX_GROUPS_MAX: i32 = 4096;
 pub const SRX_UMAP_GROUP: i32 = 8;
 pub const SRX_UMAP_MAX_EPOCHS: i32 = 1048576;
+pub const SRX_UMAP_TRANSFORM_CHUNK: i32 = 64;
 pub const SRX_TSNE_MAX_K: i32 = 64;
 pub const SRX_TSNE_MAX_LEVELS: i32 = 12;
 pub const SRX_TSNE_GROUP: i32 = 8;
@@ -557,6 +558,55 @@ pub struct SrxUmapInfo {      // `srx_umap_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxUmapTransformOpts {      // `srx_umap_transform_opts`
+    pub a: f64,
+    pub b: f64,
+    pub min_dist: f64,
+    pub spread: f64,
+    pub gamma: f64,
+    pub alpha0: f64,
+    pub seed: u64,
+    pub n_epochs: i32,
+    pub stop_after: i32,
+    pub negative_sample_rate: i32,
+    pub chunk_epochs: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxUmapTransformOut {      // `srx_umap_transform_out`
+    pub embedding: *mut f64,
+    pub start: *mut f64,
+    pub weights: *mut f64,
+    pub columns: *mut u32,
+    pub sigma: *mut f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxUmapTransformInfo {      // `srx_umap_transform_info`
+    pub n_query: u64,
+    pub n_ref: u64,
+    pub entries_active: u64,
+    pub samples: u64,
+    pub negatives: u64,
+    pub rows_no_root: u64,
+    pub rows_clamped: u64,
+    pub rows_all_zero: u64,
+    pub rows_start_nearest: u64,
+    pub kq: u32,
+    pub dim: u32,
+    pub n_epochs: u32,
+    pub epochs_run: u32,
+    pub a: f64,
+    pub b: f64,
+    pub w_max: f64,
+    pub ms: f64,
+    pub membership_ms: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxTsneInfo {      // `srx_tsne_info`
     pub n: u64,
     pub nnz: u64,
@@ -1032,6 +1082,17 @@ extern "C" {
                         opts: *const SrxUmapOpts, init: *const f64, embedding_out: *mut f64, info: *mut SrxUmapInfo) -> i32;
     pub fn srx_graph_embedding_fetch(g: *mut SrxGraph, out: *mut f64, dim_out: *mut u32) -> i32;
     pub fn srx_umap_fit_ab(spread: f64, min_dist: f64, a: *mut f64, b: *mut f64) -> i32;
+    pub fn srx_umap_transform_knn(ctx: *mut SrxCtx, indices: *const u32, distances: *const f64, n_query: u64,
+                                  kq: u32, ref_embedding: *const f64, n_ref: u64, dim: u32,
+                                  opts: *const SrxUmapTransformOpts, out: *mut SrxUmapTransformOut,
+                                  info: *mut SrxUmapTransformInfo) -> i32;
+    pub fn srx_umap_transform_graph(g: *mut SrxGraph, indices: *const u32, distances: *const f64, n_query: u64,
+                                    kq: u32, dim: u32, opts: *const SrxUmapTransformOpts,
+                                    out: *mut SrxUmapTransformOut, info: *mut SrxUmapTransformInfo) -> i32;
+    pub fn srx_knn_vote(ctx: *mut SrxCtx, indices: *const u32, n_query: u64, k: u32, ref_labels: *const u32,
+                        n_ref: u64, n_groups: u32, labels_out: *mut u32, counts_out: *mut u32) -> i32;
+    pub fn srx_knn_vote_graph(g: *mut SrxGraph, indices: *const u32, n_query: u64, k: u32, labels_out: *mut u32,
+                              counts_out: *mut u32) -> i32;
     pub fn srx_tsne_affinities_knn(ctx: *mut SrxCtx, indices: *const u32, distances: *const f64, n: u64, k: u32,
                                    perplexity: f64, out: *mut *mut SrxTsne) -> i32;
     pub fn srx_tsne_affinities_graph(g: *mut SrxGraph, perplexity: f64, out: *mut *mut SrxTsne) -> i32;

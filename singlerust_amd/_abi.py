@@ -14,6 +14,7 @@ LOUVAIN_MAX_LEVELS = 32
 GROUPS_MAX = 4096
 UMAP_GROUP = 8
 UMAP_MAX_EPOCHS = 1048576
+UMAP_TRANSFORM_CHUNK = 64
 TSNE_MAX_K = 64
 TSNE_MAX_LEVELS = 12
 TSNE_GROUP = 8
@@ -313,6 +314,25 @@ class UmapInfo(C.Structure):      # srx_umap_info
                 ("b", C.c_double), ("w_max", C.c_double), ("ms", C.c_double)]
 
 
+class UmapTransformOpts(C.Structure):      # srx_umap_transform_opts
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("min_dist", C.c_double), ("spread", C.c_double),
+                ("gamma", C.c_double), ("alpha0", C.c_double), ("seed", C.c_uint64), ("n_epochs", C.c_int32),
+                ("stop_after", C.c_int32), ("negative_sample_rate", C.c_int32), ("chunk_epochs", C.c_int32)]
+
+
+class UmapTransformOut(C.Structure):      # srx_umap_transform_out
+    _fields_ = [("embedding", P), ("start", P), ("weights", P), ("columns", P), ("sigma", P)]
+
+
+class UmapTransformInfo(C.Structure):      # srx_umap_transform_info
+    _fields_ = [("n_query", C.c_uint64), ("n_ref", C.c_uint64), ("entries_active", C.c_uint64),
+                ("samples", C.c_uint64), ("negatives", C.c_uint64), ("rows_no_root", C.c_uint64),
+                ("rows_clamped", C.c_uint64), ("rows_all_zero", C.c_uint64), ("rows_start_nearest", C.c_uint64),
+                ("kq", C.c_uint32), ("dim", C.c_uint32), ("n_epochs", C.c_uint32), ("epochs_run", C.c_uint32),
+                ("a", C.c_double), ("b", C.c_double), ("w_max", C.c_double), ("ms", C.c_double),
+                ("membership_ms", C.c_double)]
+
+
 class TsneInfo(C.Structure):      # srx_tsne_info
     _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("n_mutual", C.c_uint64), ("rows_no_root", C.c_uint64),
                 ("entries_dropped", C.c_uint64), ("k", C.c_uint32), ("reserved_", C.c_uint32),
@@ -553,6 +573,14 @@ SIGNATURES = {
     "srx_umap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(UmapOpts), P, P, C.POINTER(UmapInfo)]),
     "srx_graph_embedding_fetch": (C.c_int32, [P, P, P]),
     "srx_umap_fit_ab": (C.c_int32, [C.c_double, C.c_double, P, P]),
+    "srx_umap_transform_knn": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, P, C.c_uint64, C.c_uint32,
+                                           C.POINTER(UmapTransformOpts), C.POINTER(UmapTransformOut),
+                                           C.POINTER(UmapTransformInfo)]),
+    "srx_umap_transform_graph": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.c_uint32,
+                                             C.POINTER(UmapTransformOpts), C.POINTER(UmapTransformOut),
+                                             C.POINTER(UmapTransformInfo)]),
+    "srx_knn_vote": (C.c_int32, [P, P, C.c_uint64, C.c_uint32, P, C.c_uint64, C.c_uint32, P, P]),
+    "srx_knn_vote_graph": (C.c_int32, [P, P, C.c_uint64, C.c_uint32, P, P]),
     "srx_tsne_affinities_knn": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.c_double, C.POINTER(P)]),
     "srx_tsne_affinities_graph": (C.c_int32, [P, C.c_double, C.POINTER(P)]),
     "srx_tsne_info_get": (C.c_int32, [P, C.POINTER(TsneInfo)]),

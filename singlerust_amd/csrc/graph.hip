@@ -15,8 +15,8 @@
 // Kernels, one wave per row unless said otherwise (k <= 64: lane p holds entry p of the row):
 //   k_graph_rows      checks the list (index range, self, duplicates, distances), puts the row in column order (rank by
 //                     counting across the lanes: this IS the row of D, and everything after it depends on the row as a SET),
-//                     rho, c, the root by bracketing and bisection in f64 (every sum a fixed-order butterfly), the floor,
-//                     the directed weights
+//                     rho, c, the root by bracketing and bisection in f64 (graph_root.hpp: every sum a fixed-order butterfly),
+//                     the floor, the directed weights
 //   k_graph_reverse   binary search of i in row j for every edge i -> j: the reverse weight b (0 when absent), the value
 //                     (a + b) - a b of the pair, whether it is stored; an edge whose reverse is absent is an IN-ONLY entry
 //                     of row j and is counted there (one global atomic per such edge)
@@ -32,6 +32,7 @@
 // result is bit-identical from call to call, and C[i, j] and C[j, i] are the same bits (fma(-a, b, a + b) is symmetric).
 #include "common.hpp"
 #include "graph_handle.hpp"
+#include "graph_root.hpp"
 #include "pca_internal.hpp"
 #include "scan.hpp"
 
@@ -52,12 +53,6 @@ __device__ __forceinline__ unsigned long long below(int p) { return p >= 64 ? ~0
 __device__ __forceinline__ double fuzzy_union(double a, double b) { return fma(-a, b, a + b); }
 // the value of a pair from its two directed weights (an absent direction is 0): symmetric in a and b for either rule
 __device__ __forceinline__ double pair_value(PairRule r, double a, double b) { return r.mean ? (a + b) / r.denom : fuzzy_union(a, b); }
-
-// S(s) of the lane's row: `one` lanes count 1, `far` lanes exp(-x / s), the others nothing.  The butterfly adds in an
-// order that does not depend on the lane, so every lane holds the same bits.
-__device__ __forceinline__ double graph_S(bool one, bool far, double x, double s) {
-    return wave_sum(one ? 1.0 : far ? exp(-x / s) : 0.0);
-}
 
 __global__ void __launch_bounds__(256) k_graph_rows(const uint32_t* __restrict__ idx_in, const double* __restrict__ dist_in,
                                                     uint64_t n, int k, uint64_t* __restrict__ dptr, uint32_t* __restrict__ dind,
@@ -110,35 +105,8 @@ __global__ void __launch_bounds__(256) k_graph_rows(const uint32_t* __restrict__
     const bool has_root = !all_zero && (double)c < T;
     double sig = 0.0;
     if (has_root) {
-        // S rises from c < T (s -> 0) to k > T (s -> inf; k = T only for k = 1, where c = 1 = T): bracket by factors of two
-        // from the largest x, then halve the bracket until it is one ulp wide or S is within 1e-13 of T
-        double lo = wave_max(x), hi = lo;
-        double S = graph_S(one, far, x, lo);
-        if (S < T) {
-            for (int it = 0; it < 2200; ++it) {
-                hi = lo * 2.0;
-                if (!(hi <= kDblMax) || graph_S(one, far, x, hi) >= T) break;
-                lo = hi;
-            }
-        } else {
-            for (int it = 0; it < 2200; ++it) {
-                lo = hi * 0.5;
-                if (lo == 0.0 || graph_S(one, far, x, lo) < T) break;
-                hi = lo;
-            }
-        }
-        for (int it = 0; it < 128; ++it) {
-            const double mid = lo + 0.5 * (hi - lo);
-            if (!(mid > lo && mid < hi)) break;
-            S = graph_S(one, far, x, mid);
-            if (fabs(S - T) <= 1e-13) {
-                hi = mid;
-                break;
-            }
-            if (S < T) lo = mid;
-            else hi = mid;
-        }
-        sig = hi;
+        // S rises from c < T (s -> 0) to k > T (s -> inf; k = T only for k = 1, where c = 1 = T)
+        sig = graph_root(one, far, x, T);
     }
     const double floor_ = 1e-3 * sum_d / (double)(k + 1);
     const bool clamped = !all_zero && floor_ > sig;

@@ -19,6 +19,7 @@
 //                        its own to the next one the schedule samples, gathers y_j and the R hashed targets, sums its terms in
 //                        f64 in that order; group_sum (scan.hpp) adds the lanes; lane 0 writes y_i once.  Rows longer than G
 //                        loop.  The counters are per-block integer sums added with integer atomics.
+// The two terms of an epoch (um_term) and the small block are in umap_internal.hpp, shared with the transform of ingest.hip.
 // x^y is ocml's pow(double, double); the file is built without -ffast-math and with FMA contraction off, so that every
 // operation of the definition is rounded once, as numpy rounds it.
 #include "common.hpp"
@@ -30,20 +31,11 @@
 
 #include <cmath>
 
-#pragma clang fp contract(off)
+#include "umap_internal.hpp"         // UmParams, um_load, um_term, the small block; FMA contraction is off from here on
 
 namespace srx {
 
-constexpr int kUmGroup = SRX_UMAP_GROUP;
 constexpr unsigned long long kUmInfBits = 0x7FF0000000000000ull;
-// the small block (8-byte words)
-enum { UM_WMAX = 0, UM_ACTIVE, UM_SAMPLES, UM_SKIPPED, UM_ABSMAX, UM_PCAMAX, UM_WORDS = 8 };
-
-struct UmParams {
-    double a, b, gamma;
-    uint64_t seed;
-    int rate;
-};
 
 __global__ void __launch_bounds__(256) k_umap_wmax(const double* __restrict__ w, uint64_t nnz, unsigned long long* __restrict__ small) {
     __shared__ unsigned long long s_wave[4];
@@ -92,41 +84,6 @@ __global__ void __launch_bounds__(256) k_umap_init_pca(const double* __restrict_
     if (c >= rows * (uint64_t)dim) return;
     const double s = 10.0 / __longlong_as_double((long long)small[UM_PCAMAX]);
     y[c] = scores[(c / dim) * ld + (c % dim)] * s;
-}
-
-template <int DIM>
-__device__ __forceinline__ void um_load(const double* __restrict__ y, uint64_t i, double (&p)[DIM]) {
-    if constexpr (DIM == 2) {            // one 16-byte load
-        const double2 v = reinterpret_cast<const double2*>(y)[i];
-        p[0] = v.x;
-        p[1] = v.y;
-    } else {
-#pragma unroll
-        for (int c = 0; c < DIM; ++c) p[c] = y[i * DIM + c];
-    }
-}
-
-// acc += scale * clip(q (y_i - y_o), -4, 4) with q from d2 = |y_i - y_o|^2; `attract`: the attraction of a sampled entry, else the
-// repulsion from a negative sample (one body for both, so that pow is expanded once per exponent).  d2 == 0 adds nothing.
-template <int DIM>
-__device__ __forceinline__ void um_term(const double (&yi)[DIM], const double* __restrict__ y, uint64_t o, const UmParams& p, bool attract,
-                                        double coef, double scale, double (&acc)[DIM]) {
-    double yo[DIM], d[DIM];
-    um_load<DIM>(y, o, yo);
-    double d2 = 0.0;
-#pragma unroll
-    for (int c = 0; c < DIM; ++c) {
-        d[c] = yi[c] - yo[c];
-        d2 = c ? d2 + d[c] * d[c] : d[c] * d[c];
-    }
-    if (!(d2 > 0.0)) return;
-    const double den = p.a * pow(d2, p.b) + 1.0;
-    const double q = attract ? coef * pow(d2, p.b - 1.0) / den : coef / ((0.001 + d2) * den);
-#pragma unroll
-    for (int c = 0; c < DIM; ++c) {
-        const double g = fmin(fmax(q * d[c], -4.0), 4.0);
-        acc[c] += scale * g;
-    }
 }
 
 template <int DIM>
@@ -272,6 +229,16 @@ static int32_t um_check_curve(srx_ctx* ctx, double spread, double min_dist) {
     return SRX_OK;
 }
 
+void umap_wmax_active(srx_ctx* ctx, const double* d_w, uint64_t nnz, double epochs, unsigned long long* d_small) {
+    hipLaunchKernelGGL(k_umap_wmax, dim3(um_stride_grid(nnz)), dim3(256), 0, ctx->stream, d_w, nnz, d_small);
+    hipLaunchKernelGGL(k_umap_active, dim3(um_stride_grid(nnz)), dim3(256), 0, ctx->stream, d_w, nnz, epochs, d_small);
+}
+
+int32_t umap_fit_curve(srx_ctx* ctx, double spread, double min_dist, double* a, double* b) {
+    SRX_TRY(um_check_curve(ctx, spread, min_dist));
+    return um_fit_ab(spread, min_dist, a, b);
+}
+
 struct UmOpts {
     srx_umap_opts o;
     uint32_t epochs, run;
@@ -340,10 +307,7 @@ static int32_t umap_run(srx_ctx* ctx, const SymCsr& g, const UmOpts& u, srx_mat*
         hipLaunchKernelGGL(k_umap_init_pca, dim3(grid256(count)), dim3(256), 0, st, m->pca.d_scores, g.n, dim, ld, d_small, d_y0);
     }
     hipLaunchKernelGGL(k_umap_absmax, dim3(um_stride_grid(count)), dim3(256), 0, st, d_y0, g.n, dim, (uint64_t)dim, d_small + UM_ABSMAX);
-    if (g.nnz) {
-        hipLaunchKernelGGL(k_umap_wmax, dim3(um_stride_grid(g.nnz)), dim3(256), 0, st, g.w, g.nnz, d_small);
-        hipLaunchKernelGGL(k_umap_active, dim3(um_stride_grid(g.nnz)), dim3(256), 0, st, g.w, g.nnz, (double)u.epochs, d_small);
-    }
+    if (g.nnz) umap_wmax_active(ctx, g.w, g.nnz, (double)u.epochs, d_small);
     SRX_HIP(ctx, hipGetLastError());
     uint64_t h[UM_WORDS];
     SRX_TRY(d2h(ctx, h, d_small, sizeof h));

@@ -961,6 +961,30 @@ public:
         ctx_->check(srx_graph_labels_fetch(h_, labels.empty() ? nullptr : labels.data()));
         return labels;
     }
+    // labels for new cells from the labels the last louvain() left on the device (srx_knn_vote_graph): `indices` is their k-NN
+    // list among this graph's cells, n_query x k row-major; per new cell the most frequent label (ties to the lowest) and how
+    // often it occurs
+    std::pair<std::vector<std::uint32_t>, std::vector<std::uint32_t>> knn_vote(const std::vector<std::uint32_t>& indices,
+                                                                               std::uint32_t k) const {
+        if (!k || indices.size() % k) throw Error(SRX_E_ARG, "knn_vote: n_query x k indices expected");
+        const std::size_t nq = indices.size() / k;
+        std::vector<std::uint32_t> labels(nq), counts(nq);
+        ctx_->check(srx_knn_vote_graph(h_, nq ? indices.data() : nullptr, nq, k, nq ? labels.data() : nullptr, nq ? counts.data() : nullptr));
+        return {labels, counts};
+    }
+    // new cells placed in the embedding a srx_umap left on this handle, read where it lies (srx_umap_transform_graph): the
+    // k-NN list as above with its distances, `dim` the embedding's; n_query x dim, row-major
+    std::vector<double> umap_transform(const std::vector<std::uint32_t>& indices, const std::vector<double>& distances, std::uint32_t kq,
+                                       std::uint32_t dim, const srx_umap_transform_opts* opts = nullptr,
+                                       srx_umap_transform_info* info = nullptr) const {
+        if (!kq || indices.size() % kq || distances.size() != indices.size())
+            throw Error(SRX_E_ARG, "umap_transform: n_query x kq indices and distances expected");
+        const std::size_t nq = indices.size() / kq;
+        std::vector<double> emb(nq * dim);
+        srx_umap_transform_out o{emb.empty() ? nullptr : emb.data(), nullptr, nullptr, nullptr, nullptr};
+        ctx_->check(srx_umap_transform_graph(h_, nq ? indices.data() : nullptr, nq ? distances.data() : nullptr, nq, kq, dim, opts, &o, info));
+        return emb;
+    }
     // PAGA of the graph's D over the groups, read where it lies (srx_paga).  `labels` null: those the last louvain() left
     // on the device, n_groups = its n_communities or more; else one host label below n_groups per cell
     Paga paga(std::uint32_t n_groups, const std::vector<std::uint32_t>* labels = nullptr) const {
@@ -1034,6 +1058,32 @@ inline std::vector<std::uint32_t> louvain_csr(Context& ctx, const std::vector<st
     ctx.check(srx_louvain_csr(ctx.handle(), indptr.data(), indices.empty() ? nullptr : indices.data(),
                               weights.empty() ? nullptr : weights.data(), labels.size(), &o, labels.empty() ? nullptr : labels.data(), info));
     return labels;
+}
+// labels for new cells from host arrays (srx_knn_vote): their k-NN list among n_ref reference cells (n_query x k row-major)
+// and one label below n_groups per reference cell; per new cell the most frequent label (ties to the lowest) and its count
+inline std::pair<std::vector<std::uint32_t>, std::vector<std::uint32_t>> knn_vote(Context& ctx, const std::vector<std::uint32_t>& indices,
+                                                                                  std::uint32_t k, const std::vector<std::uint32_t>& ref_labels,
+                                                                                  std::uint32_t n_groups) {
+    if (!k || indices.size() % k) throw Error(SRX_E_ARG, "knn_vote: n_query x k indices expected");
+    const std::size_t nq = indices.size() / k;
+    std::vector<std::uint32_t> labels(nq), counts(nq);
+    ctx.check(srx_knn_vote(ctx.handle(), nq ? indices.data() : nullptr, nq, k, ref_labels.empty() ? nullptr : ref_labels.data(),
+                           ref_labels.size(), n_groups, nq ? labels.data() : nullptr, nq ? counts.data() : nullptr));
+    return {labels, counts};
+}
+// new cells placed in a fitted UMAP from host arrays (srx_umap_transform_knn): the k-NN list with its distances and the
+// reference layout (n_ref x dim row-major, dim 2 or 3); n_query x dim, row-major
+inline std::vector<double> umap_transform_knn(Context& ctx, const std::vector<std::uint32_t>& indices, const std::vector<double>& distances,
+                                              std::uint32_t kq, const std::vector<double>& ref_embedding, std::uint32_t dim,
+                                              const srx_umap_transform_opts* opts = nullptr, srx_umap_transform_info* info = nullptr) {
+    if (!kq || indices.size() % kq || distances.size() != indices.size() || !dim || ref_embedding.size() % dim)
+        throw Error(SRX_E_ARG, "umap_transform_knn: n_query x kq indices and distances and an n_ref x dim layout expected");
+    const std::size_t nq = indices.size() / kq;
+    std::vector<double> emb(nq * dim);
+    srx_umap_transform_out o{emb.empty() ? nullptr : emb.data(), nullptr, nullptr, nullptr, nullptr};
+    ctx.check(srx_umap_transform_knn(ctx.handle(), nq ? indices.data() : nullptr, nq ? distances.data() : nullptr, nq, kq,
+                                     ref_embedding.empty() ? nullptr : ref_embedding.data(), ref_embedding.size() / dim, dim, opts, &o, info));
+    return emb;
 }
 // PAGA of any directed pattern (CSR; every stored entry counts once) with one label below n_groups per row: srx_paga_csr
 inline Paga paga_csr(Context& ctx, const std::vector<std::uint64_t>& indptr, const std::vector<std::uint32_t>& indices,

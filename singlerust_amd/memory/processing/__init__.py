@@ -14,6 +14,7 @@ from .doublets import Doublets, doublet_scores_knn, doublets_threshold, scrublet
 from .harmony import Harmony, encode_batches, harmony_integrate, harmony_points
 from .hvg import (highly_variable_genes_pearson, highly_variable_genes_seurat_v3, pca_pearson_residuals, pearson_gene_variance, pearson_gram,
                   pearson_residuals, seurat_v3_tables)
+from .ingest import ingest, knn_vote, umap_transform
 from .louvain import graph_labels, louvain, louvain_csr
 from .markers import group_moments, rank_genes_groups
 from .paga import paga, paga_csr, paga_from_counts, paga_init_positions
