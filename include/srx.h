@@ -775,6 +775,77 @@ int32_t srx_graph_fetch(srx_graph* g, int32_t which, uint64_t* indptr, uint32_t*
 int32_t srx_graph_fetch_scales(srx_graph* g, double* rho, double* sigma);   /* n each */
 void    srx_graph_free(srx_graph* g);
 
+/* ---- the shared-nearest-neighbour (SNN) graph of a k-NN list: Jaccard weights, pruned -----------------------------------
+ * What Seurat's FindNeighbors (ComputeSNN), PhenoGraph and scran's buildSNNGraph(type = "jaccard" / "number") cluster.
+ * Not in the reference.  The definition below is what is tested; Seurat, PhenoGraph and scran are NOT installed where
+ * this was built and the output has NOT been compared with any of them.
+ *
+ * Input: a k-NN list as srx_neighbors_from_knn takes it: n rows of k distinct neighbours j != i, 1 <= k <= 64,
+ *   k <= n - 1; rows need not be sorted; distances play no part in the weights.
+ * Neighbour sets: include_self = 1 (the default, Seurat's convention): N(i) = {i} u knn(i), K = k + 1;
+ *   include_self = 0: N(i) = knn(i), K = k.  For i != j the shared count is s_ij = |N(i) n N(j)|, an integer in 0 .. K.
+ * Pairs considered: SRX_SNN_PAIRS_SHARED (the default, Seurat's ComputeSNN): every pair i != j with s_ij >= 1;
+ *   SRX_SNN_PAIRS_KNN (PhenoGraph's restriction): of those, the pairs joined by the list in either direction
+ *   (j in knn(i) or i in knn(j)).
+ * Value: J_ij = (double)s_ij / (double)(2 K - s_ij), ONE IEEE f64 division of two exactly converted integers.  A
+ *   considered pair is stored if and only if J_ij >= prune (Seurat zeroes value < prune: equality keeps the pair).  J rises
+ *   with s, so this is s_ij >= min_shared with min_shared = srx_snn_min_shared(k, include_self, prune), the smallest s in
+ *   1 .. K whose J >= prune by that same expression (K + 1: none, the graph is empty).  The stored weight is J_ij for
+ *   SRX_SNN_JACCARD and (double)s_ij for SRX_SNN_NUMBER.  prune lies in [0, 1]; the default is 1/15; prune = 0 keeps
+ *   every considered pair.
+ * Result: CSR like the connectivities: u64 indptr (n + 1), u32 indices ascending within a row, f64 data.  It is exactly
+ *   symmetric (both entries of a pair are the same bits), has NO diagonal (a stated departure: Seurat stores the
+ *   diagonal as 1), does not depend on the order of the entries within an input row, and is bit-identical from call to
+ *   call: everything up to the one division is integer arithmetic, and no floating-point atomic takes part.
+ * The result is an ordinary srx_graph: its C block (SRX_GRAPH_CONNECTIVITIES) holds the SNN graph, its D block a copy
+ *   of the source list in column order with its distances (zeros when none were given); rho, sigma and the directed
+ *   weights are zero; srx_graph_info has n, k, nnz_distances, nnz_connectivities and max_row_nnz, the other counters
+ *   are 0.  Every call that takes an srx_graph (srx_louvain, srx_umap, srx_paga, srx_diffmap, srx_autocorr, ...) works
+ *   on it unchanged.
+ * Refusals, each SRX_E_ARG with a message: those of srx_neighbors_from_knn (k outside 1..64, k > n - 1, an index >= n,
+ *   a row naming itself or one neighbour twice, a negative / NaN / Inf distance where distances are given, a context
+ *   with more than one rank); prune NaN or outside [0, 1]; an unknown weight or pairs.  n == 0 gives an empty graph.
+ * Out of scope: scran's type = "rank" weighting (it needs the ranks carried in the reverse lists). */
+enum { SRX_SNN_JACCARD = 0, SRX_SNN_NUMBER = 1 };
+enum { SRX_SNN_PAIRS_SHARED = 0, SRX_SNN_PAIRS_KNN = 1 };
+typedef struct srx_snn_opts {
+    int32_t weight;            /* SRX_SNN_JACCARD | SRX_SNN_NUMBER                                         */
+    int32_t pairs;             /* SRX_SNN_PAIRS_SHARED | SRX_SNN_PAIRS_KNN                                 */
+    int32_t include_self;      /* non-zero: N(i) holds i                                                   */
+    int32_t reserved_;
+    double  prune;
+} srx_snn_opts;                /* NULL = {SRX_SNN_JACCARD, SRX_SNN_PAIRS_SHARED, 1, 0, 1.0 / 15.0}         */
+typedef struct srx_snn_info {
+    uint64_t n;
+    uint32_t k, set_size;      /* set_size = K                                                             */
+    uint32_t min_shared;       /* srx_snn_min_shared(k, include_self, prune)                               */
+    uint32_t max_shared;       /* the largest s_ij over the considered pairs (0: none)                     */
+    uint64_t pairs_considered; /* unordered pairs                                                          */
+    uint64_t pairs_kept;       /* ... of them stored: nnz / 2                                              */
+    uint64_t nnz;
+    uint64_t max_row_nnz;
+    uint64_t max_in_degree;    /* the longest reverse list R(m) = {j : m in knn(j)}                        */
+    uint64_t max_candidates;   /* the largest c_i = sum over m in N(i) of |{j : m in N(j)}| over the rows  */
+    uint64_t sum_candidates;   /* the sum of c_i over the rows: what one pass into a staging would reserve */
+    uint32_t wave_capacity;    /* c_i up to here: one wave per row, a hash table in LDS                    */
+    uint32_t short_capacity;   /* c_i up to here: one workgroup per row, a hash table in LDS               */
+    uint64_t rows_wave;        /* rows on the first route                                                  */
+    uint64_t rows_long;        /* rows beyond short_capacity: one workgroup per row over windows of the index range */
+    uint64_t rows_empty;       /* rows of the result without an entry                                      */
+    double   ms;               /* hipEvent time of the device work                                         */
+    double   ms_lists, ms_count, ms_fill;   /* of it: the reverse lists | the count pass | the fill pass   */
+} srx_snn_info;
+/* The SNN graph of a caller-supplied list (n x k row-major u32; distances n x k f64 or NULL).  opts and info may be NULL. */
+int32_t srx_snn_from_knn(srx_ctx* ctx, const uint32_t* indices, const double* distances, uint64_t n, uint32_t k,
+                         const srx_snn_opts* opts, srx_snn_info* info, srx_graph** out);
+/* The same from the list that a handle holds on the device (its D block), whichever call made the handle
+ * (srx_neighbors_result, srx_neighbors_from_knn, srx_neighbors_index, srx_neighbors_harmony, or one of the two calls
+ * here): no host round trip.  g stays untouched; *out is a new handle. */
+int32_t srx_snn_graph(srx_graph* g, const srx_snn_opts* opts, srx_snn_info* info, srx_graph** out);
+/* Host code, no GPU: the smallest s in 1 .. K with (double)s / (double)(2 K - s) >= prune, K + 1 when there is none.
+ * SRX_E_ARG: k outside 1..64, prune NaN or outside [0, 1], out == NULL. */
+int32_t srx_snn_min_shared(uint32_t k, int32_t include_self, double prune, uint32_t* out);
+
 /* ---- approximate k-NN: an inverted-file (IVF) index over dense points -----------------------------------------------
  * The exact search above costs n^2 products; this one probes a few lists of an index.  Not in the reference; it is the
  * classical IVF-flat scheme, defined here tightly enough to be tested bit for bit.  It has NOT been compared with FAISS,

@@ -1107,6 +1107,54 @@ pub mod processing_free {
                 out
             })
         }
+        /// The options of the shared-nearest-neighbour graph as Seurat's FindNeighbors has them: Jaccard weights, every pair
+        /// that shares a neighbour, the cell in its own set, pairs below `prune` dropped.
+        pub fn snn_opts(prune: f64) -> SrxSnnOpts {
+            SrxSnnOpts { weight: SRX_SNN_JACCARD as i32, pairs: SRX_SNN_PAIRS_SHARED as i32, include_self: 1, reserved: 0, prune }
+        }
+        /// The SNN graph of the cells (srx_neighbors_result, then srx_snn_graph on the list where it lies): `n_neighbors` is
+        /// Seurat's k.param, which counts the cell, so the list has n_neighbors - 1 entries.  Returns (the k-NN distances, the
+        /// SNN graph), both n_obs x n_obs CSR, and the call's counters.  Not compared with Seurat, PhenoGraph or scran.
+        pub fn neighbors_snn(adata: &IMAnnData, n_neighbors: usize, n_pcs: usize, opts: &SrxSnnOpts)
+                             -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>, SrxSnnInfo)> {
+            if n_neighbors < 2 {
+                bail!("neighbors_snn: n_neighbors counts the cell itself, so it is at least 2");
+            }
+            let kopts = SrxKnnOpts { k: (n_neighbors - 1) as i32, n_dims: n_pcs as i32, include_self: 0, reserved: 0 };
+            with_resident(adata, |x| {
+                let mut src: *mut SrxGraph = null_mut();
+                x.ctx.check(unsafe { srx_neighbors_result(x.mat, &kopts, null_mut(), &mut src) })?;
+                let mut g: *mut SrxGraph = null_mut();
+                let mut info: SrxSnnInfo = unsafe { std::mem::zeroed() };
+                let rc = unsafe { srx_snn_graph(src, opts, &mut info, &mut g) };
+                unsafe { srx_graph_free(src) };
+                x.ctx.check(rc)?;
+                let out = graph_to_host(x.ctx, g).map(|(d, c)| (d, c, info));
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        /// The SNN graph of a k-NN list the caller holds (srx_snn_from_knn); distances play no part in it.
+        pub fn snn_from_knn(indices: &Array2<u32>, opts: &SrxSnnOpts) -> anyhow::Result<(CsrMatrix<f64>, SrxSnnInfo)> {
+            let (n, k) = indices.dim();
+            let i: Vec<u32> = indices.iter().copied().collect();                   // row-major
+            with_ctx(|c| {
+                let mut g: *mut SrxGraph = null_mut();
+                let mut info: SrxSnnInfo = unsafe { std::mem::zeroed() };
+                c.check(unsafe { srx_snn_from_knn(c.0, i.as_ptr(), std::ptr::null(), n as u64, k as u32, opts, &mut info, &mut g) })?;
+                let out = graph_to_host(c, g).map(|(_, snn)| (snn, info));
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        /// The smallest shared count whose Jaccard index reaches `prune` (srx_snn_min_shared: host code, no GPU).
+        pub fn snn_min_shared(k: usize, include_self: bool, prune: f64) -> anyhow::Result<u32> {
+            let mut s = 0u32;
+            match unsafe { srx_snn_min_shared(k as u32, include_self as i32, prune, &mut s) } {
+                0 => Ok(s),
+                rc => Err(anyhow!("srx_snn_min_shared: status {rc}")),
+            }
+        }
         /// Louvain communities of the cells (srx_neighbors_result, then srx_louvain on the graph where it lies): k-NN with
         /// `n_neighbors` over the first `n_pcs` resident scores (0 = all), the connectivities, parallel Louvain at
         /// `resolution` — all on the device.  Returns one label per cell, communities numbered by descending size, and Q.

@@ -70,6 +70,10 @@ pub const SRX_PEARSON_TOTALS_ALL: i32 = 0;
 pub const SRX_PEARSON_TOTALS_SELECTED: i32 = 1;
 pub const SRX_GRAPH_DISTANCES: i32 = 0;
 pub const SRX_GRAPH_CONNECTIVITIES: i32 = 1;
+pub const SRX_SNN_JACCARD: i32 = 0;
+pub const SRX_SNN_NUMBER: i32 = 1;
+pub const SRX_SNN_PAIRS_SHARED: i32 = 0;
+pub const SRX_SNN_PAIRS_KNN: i32 = 1;
 pub const SRX_MARKERS_CNT: i32 = 0;
 pub const SRX_MARKERS_SUM: i32 = 1;
 pub const SRX_MARKERS_SUMSQ: i32 = 2;
@@ -361,6 +365,42 @@ pub struct SrxGraphInfo {      // `srx_graph_info`
     pub rows_all_zero: u64,
     pub entries_dropped: u64,
     pub max_row_nnz: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxSnnOpts {      // `srx_snn_opts`
+    pub weight: i32,
+    pub pairs: i32,
+    pub include_self: i32,
+    pub reserved: i32,
+    pub prune: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxSnnInfo {      // `srx_snn_info`
+    pub n: u64,
+    pub k: u32,
+    pub set_size: u32,
+    pub min_shared: u32,
+    pub max_shared: u32,
+    pub pairs_considered: u64,
+    pub pairs_kept: u64,
+    pub nnz: u64,
+    pub max_row_nnz: u64,
+    pub max_in_degree: u64,
+    pub max_candidates: u64,
+    pub sum_candidates: u64,
+    pub wave_capacity: u32,
+    pub short_capacity: u32,
+    pub rows_wave: u64,
+    pub rows_long: u64,
+    pub rows_empty: u64,
+    pub ms: f64,
+    pub ms_lists: f64,
+    pub ms_count: f64,
+    pub ms_fill: f64,
 }
 
 #[repr(C)]
@@ -1036,6 +1076,10 @@ extern "C" {
     pub fn srx_graph_fetch(g: *mut SrxGraph, which: i32, indptr: *mut u64, indices: *mut u32, data: *mut f64) -> i32;
     pub fn srx_graph_fetch_scales(g: *mut SrxGraph, rho: *mut f64, sigma: *mut f64) -> i32;
     pub fn srx_graph_free(g: *mut SrxGraph);
+    pub fn srx_snn_from_knn(ctx: *mut SrxCtx, indices: *const u32, distances: *const f64, n: u64, k: u32,
+                            opts: *const SrxSnnOpts, info: *mut SrxSnnInfo, out: *mut *mut SrxGraph) -> i32;
+    pub fn srx_snn_graph(g: *mut SrxGraph, opts: *const SrxSnnOpts, info: *mut SrxSnnInfo, out: *mut *mut SrxGraph) -> i32;
+    pub fn srx_snn_min_shared(k: u32, include_self: i32, prune: f64, out: *mut u32) -> i32;
     pub fn srx_knn_index_result(m: *mut SrxMat, n_dims: i32, opts: *const SrxIvfOpts, out: *mut *mut SrxKnnIndex) -> i32;
     pub fn srx_knn_index_points(ctx: *mut SrxCtx, ref_: *const f64, n_ref: u64, d: u64, opts: *const SrxIvfOpts,
                                 centroids: *const f64, out: *mut *mut SrxKnnIndex) -> i32;

@@ -72,6 +72,10 @@ PEARSON_TOTALS_ALL = 0
 PEARSON_TOTALS_SELECTED = 1
 GRAPH_DISTANCES = 0
 GRAPH_CONNECTIVITIES = 1
+SNN_JACCARD = 0
+SNN_NUMBER = 1
+SNN_PAIRS_SHARED = 0
+SNN_PAIRS_KNN = 1
 MARKERS_CNT = 0
 MARKERS_SUM = 1
 MARKERS_SUMSQ = 2
@@ -231,6 +235,21 @@ class GraphInfo(C.Structure):      # srx_graph_info
                 ("nnz_connectivities", C.c_uint64), ("n_mutual", C.c_uint64), ("rows_no_root", C.c_uint64),
                 ("rows_clamped", C.c_uint64), ("rows_all_zero", C.c_uint64), ("entries_dropped", C.c_uint64),
                 ("max_row_nnz", C.c_uint64)]
+
+
+class SnnOpts(C.Structure):      # srx_snn_opts
+    _fields_ = [("weight", C.c_int32), ("pairs", C.c_int32), ("include_self", C.c_int32), ("reserved_", C.c_int32),
+                ("prune", C.c_double)]
+
+
+class SnnInfo(C.Structure):      # srx_snn_info
+    _fields_ = [("n", C.c_uint64), ("k", C.c_uint32), ("set_size", C.c_uint32), ("min_shared", C.c_uint32),
+                ("max_shared", C.c_uint32), ("pairs_considered", C.c_uint64), ("pairs_kept", C.c_uint64),
+                ("nnz", C.c_uint64), ("max_row_nnz", C.c_uint64), ("max_in_degree", C.c_uint64),
+                ("max_candidates", C.c_uint64), ("sum_candidates", C.c_uint64), ("wave_capacity", C.c_uint32),
+                ("short_capacity", C.c_uint32), ("rows_wave", C.c_uint64), ("rows_long", C.c_uint64),
+                ("rows_empty", C.c_uint64), ("ms", C.c_double), ("ms_lists", C.c_double), ("ms_count", C.c_double),
+                ("ms_fill", C.c_double)]
 
 
 class IvfOpts(C.Structure):      # srx_ivf_opts
@@ -542,6 +561,10 @@ SIGNATURES = {
     "srx_graph_fetch": (C.c_int32, [P, C.c_int32, P, P, P]),
     "srx_graph_fetch_scales": (C.c_int32, [P, P, P]),
     "srx_graph_free": (None, [P]),
+    "srx_snn_from_knn": (C.c_int32, [P, P, P, C.c_uint64, C.c_uint32, C.POINTER(SnnOpts), C.POINTER(SnnInfo),
+                                     C.POINTER(P)]),
+    "srx_snn_graph": (C.c_int32, [P, C.POINTER(SnnOpts), C.POINTER(SnnInfo), C.POINTER(P)]),
+    "srx_snn_min_shared": (C.c_int32, [C.c_uint32, C.c_int32, C.c_double, P]),
     "srx_knn_index_result": (C.c_int32, [P, C.c_int32, C.POINTER(IvfOpts), C.POINTER(P)]),
     "srx_knn_index_points": (C.c_int32, [P, P, C.c_uint64, C.c_uint64, C.POINTER(IvfOpts), P, C.POINTER(P)]),
     "srx_knn_index_info_get": (C.c_int32, [P, C.POINTER(IvfInfo)]),

@@ -45,7 +45,7 @@ int32_t knn_result_resident(srx_mat* m, const srx_knn_opts* opts, srx_knn_info* 
                             const double** d_dist, uint64_t* n_out);      // knn.hip
 
 constexpr int kGraphMaxK = 64;
-constexpr int kShort = 512;              // in-only lists up to here are ordered by one wave in LDS
+constexpr int kShort = kInShort;         // in-only lists up to here are ordered by one wave in LDS
 constexpr int kBits = 1 << 17;           // source numbers per pass of the long-list ordering (16 KiB bitmap + 16 KiB prefix)
 
 __device__ __forceinline__ unsigned long long below(int p) { return p >= 64 ? ~0ull : (1ull << p) - 1ull; }
@@ -306,7 +306,7 @@ __global__ void __launch_bounds__(256) k_graph_merge(const uint32_t* __restrict_
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-static int32_t graph_alloc(srx_ctx* ctx, uint64_t n, uint32_t k, srx_graph** out) {
+int32_t graph_alloc(srx_ctx* ctx, uint64_t n, uint32_t k, srx_graph** out) {
     srx_graph* g = new srx_graph;
     g->ctx = ctx;
     g->n = n;
@@ -332,7 +332,7 @@ static int32_t graph_alloc(srx_ctx* ctx, uint64_t n, uint32_t k, srx_graph** out
     return SRX_OK;
 }
 
-static int32_t graph_alloc_c(srx_graph* g, uint64_t nnz) {
+int32_t graph_alloc_c(srx_graph* g, uint64_t nnz) {
     const size_t o_ind = up256((g->n + 1) * 8), o_dat = o_ind + up256(nnz * 4), total = o_dat + up256(nnz * 8);
     hipError_t e = hipMalloc(&g->d_cblock, total);
     if (e != hipSuccess)
@@ -416,6 +416,34 @@ int32_t list_flag_check(srx_ctx* ctx, const char* who, uint64_t n, const int* d_
     return SRX_OK;
 }
 
+int32_t in_lists_build(srx_ctx* ctx, const uint32_t* d_dind, const double* d_val, const unsigned char* d_flags, uint64_t n,
+                       uint32_t k, int64_t* d_indeg, InLists* out) {
+    const size_t nk = (size_t)n * k;
+    hipStream_t st = ctx->stream;
+    SRX_TRY(scratch(ctx, "graph_tptr", (n + 1) * 8, (void**)&out->tptr));
+    SRX_TRY(scratch(ctx, "graph_tsrc", nk * 4, (void**)&out->tsrc));
+    SRX_TRY(scratch(ctx, "graph_tval", nk * 8, (void**)&out->tval));
+    out->lsrc = nullptr;
+    out->lval = nullptr;
+    SRX_TRY(scan_exclusive(ctx, d_indeg, n, out->tptr, nullptr));
+    hipLaunchKernelGGL(k_graph_scatter, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, d_dind, d_val, d_flags, (uint64_t)nk, (int)k,
+                       out->tptr, reinterpret_cast<unsigned long long*>(d_indeg + n), out->tsrc, out->tval);
+    hipLaunchKernelGGL(k_graph_order, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, out->tptr, n, out->tsrc, out->tval);
+    SRX_HIP(ctx, hipGetLastError());
+    return SRX_OK;
+}
+
+int32_t in_lists_order_long(srx_ctx* ctx, uint64_t n, uint32_t k, const uint32_t* d_long, uint64_t n_long, InLists* io) {
+    if (!n_long) return SRX_OK;
+    const size_t nk = (size_t)n * k;
+    SRX_TRY(scratch(ctx, "graph_lsrc", nk * 4, (void**)&io->lsrc));
+    SRX_TRY(scratch(ctx, "graph_lval", nk * 8, (void**)&io->lval));
+    hipLaunchKernelGGL(k_graph_order_long, dim3((unsigned)n_long), dim3(256), 0, ctx->stream, io->tptr, d_long, n, io->tsrc, io->tval,
+                       io->lsrc, io->lval);
+    SRX_HIP(ctx, hipGetLastError());
+    return SRX_OK;
+}
+
 // The symmetric pattern of a k-NN list and its transpose with one value per pair (graph_handle.hpp): k_graph_reverse to
 // k_graph_merge.  d_small: the caller's zeroed block, whose row counters and flag it may have used already.
 int32_t pair_union_csr(srx_ctx* ctx, PairRule rule, const uint32_t* d_dind, const double* d_a, uint64_t n, uint32_t k,
@@ -426,41 +454,28 @@ int32_t pair_union_csr(srx_ctx* ctx, PairRule rule, const uint32_t* d_dind, cons
     unsigned long long* d_two = d_small + (size_t)kCtrSlots * kCtrN;
     double* d_cval;
     unsigned char* d_flags;
-    int64_t *d_cnt, *d_indeg, *d_len, *d_tptr;
-    unsigned long long* d_cursor;
-    uint32_t *d_long, *d_tsrc, *d_lsrc = nullptr;
-    double *d_tval, *d_lval = nullptr;
+    int64_t *d_cnt, *d_indeg, *d_len;
+    uint32_t* d_long;
     SRX_TRY(scratch(ctx, "graph_cval", nk * 8, (void**)&d_cval));
     SRX_TRY(scratch(ctx, "graph_flags", nk, (void**)&d_flags));
     SRX_TRY(scratch(ctx, "graph_cnt", n * 8, (void**)&d_cnt));
     SRX_TRY(scratch(ctx, "graph_indeg", 2 * n * 8, (void**)&d_indeg));       // in-only counts | cursors
-    d_cursor = reinterpret_cast<unsigned long long*>(d_indeg + n);
     SRX_TRY(scratch(ctx, "graph_len", n * 8, (void**)&d_len));
-    SRX_TRY(scratch(ctx, "graph_tptr", (n + 1) * 8, (void**)&d_tptr));
     SRX_TRY(scratch(ctx, "graph_long", (nk / kShort + 1) * 4, (void**)&d_long));     // lists longer than kShort: at most nk / kShort
-    SRX_TRY(scratch(ctx, "graph_tsrc", nk * 4, (void**)&d_tsrc));
-    SRX_TRY(scratch(ctx, "graph_tval", nk * 8, (void**)&d_tval));
 
-    const unsigned wg_rows = (unsigned)((n + 3) / 4), wg_thr = (unsigned)((n + 255) / 256), wg_edges = (unsigned)((nk + 255) / 256);
+    const unsigned wg_rows = (unsigned)((n + 3) / 4), wg_thr = (unsigned)((n + 255) / 256);
     SRX_HIP(ctx, hipMemsetAsync(d_indeg, 0, 2 * n * 8, st));
     hipLaunchKernelGGL(k_graph_reverse, dim3(wg_rows), dim3(256), 0, st, d_dind, d_a, n, (int)k, rule, d_cval, d_flags, d_cnt, d_indeg,
                        d_ctr);
     hipLaunchKernelGGL(k_graph_rowlen, dim3(wg_thr), dim3(256), 0, st, d_cnt, d_indeg, n, d_len, d_long, d_two);
     SRX_HIP(ctx, hipGetLastError());
-    SRX_TRY(scan_exclusive(ctx, d_indeg, n, d_tptr, nullptr));
-    hipLaunchKernelGGL(k_graph_scatter, dim3(wg_edges), dim3(256), 0, st, d_dind, d_a, d_flags, (uint64_t)nk, (int)k, d_tptr, d_cursor,
-                       d_tsrc, d_tval);
-    hipLaunchKernelGGL(k_graph_order, dim3(wg_rows), dim3(256), 0, st, d_tptr, n, d_tsrc, d_tval);
-    SRX_HIP(ctx, hipGetLastError());
+    InLists in;
+    SRX_TRY(in_lists_build(ctx, d_dind, d_a, d_flags, n, k, d_indeg, &in));
     SRX_TRY(d2h(ctx, ctr, d_small, (kPairSmallWords - 1) * 8));
-    const uint64_t n_long = ctr[kCtrSlots * kCtrN + 1];
-    if (n_long) {
-        SRX_TRY(scratch(ctx, "graph_lsrc", nk * 4, (void**)&d_lsrc));
-        SRX_TRY(scratch(ctx, "graph_lval", nk * 8, (void**)&d_lval));
-        hipLaunchKernelGGL(k_graph_order_long, dim3((unsigned)n_long), dim3(256), 0, st, d_tptr, d_long, n, d_tsrc, d_tval, d_lsrc,
-                           d_lval);
-        SRX_HIP(ctx, hipGetLastError());
-    }
+    SRX_TRY(in_lists_order_long(ctx, n, k, d_long, ctr[kCtrSlots * kCtrN + 1], &in));
+    int64_t* d_tptr = in.tptr;
+    uint32_t *d_tsrc = in.tsrc, *d_lsrc = in.lsrc;
+    double *d_tval = in.tval, *d_lval = in.lval;
     // the indptr goes to scratch first: its last entry sizes the allocation it then moves into
     int64_t* d_cptr_tmp;
     SRX_TRY(scratch(ctx, "graph_cptr", (n + 1) * 8, (void**)&d_cptr_tmp));

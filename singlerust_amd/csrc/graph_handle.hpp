@@ -45,6 +45,30 @@ inline SymCsr connectivities(const srx_graph* g) { return SymCsr{g->d_cptr, g->d
 // size) <- the `bytes` at d_src, queued on the context's stream.  The caller owns the flag that says whether *slot is valid.
 int32_t keep_on_handle(srx_ctx* ctx, double** slot, bool resized, const double* d_src, size_t bytes);
 
+// A new handle with its D block allocated (indptr, indices, data, directed weights, rho, sigma: nothing filled in), and the C
+// block of a handle once nnz is known (graph.hip).  A failed graph_alloc leaves *out alone; the caller frees g after the second.
+int32_t graph_alloc(srx_ctx* ctx, uint64_t n, uint32_t k, srx_graph** out);
+int32_t graph_alloc_c(srx_graph* g, uint64_t nnz);
+
+// ---- the in-lists of a k-NN list (graph.hip): for every cell the sources of the flagged edges that point at it, ascending ----
+// Lists of more than kInShort entries are ordered by a workgroup each (k_graph_order_long) into a second pair of arrays, at
+// the same offsets; in_list_src picks the array that holds a list.
+constexpr int kInShort = 512;
+struct InLists {
+    int64_t* tptr = nullptr;                 // n + 1 offsets
+    uint32_t *tsrc = nullptr, *lsrc = nullptr;
+    double *tval = nullptr, *lval = nullptr;
+};
+__host__ __device__ inline const uint32_t* in_list_src(const uint32_t* tsrc, const uint32_t* lsrc, int64_t lo, int64_t len) {
+    return (len > kInShort ? lsrc : tsrc) + lo;
+}
+// d_indeg: 2 n words, the list lengths (counted by the caller) | n zeroed cursors.  Edge e of row e / k is listed at its
+// target d_dind[e] when d_flags[e] & 2, with the value d_val[e].  Scans the lengths, scatters, orders the short lists.
+int32_t in_lists_build(srx_ctx* ctx, const uint32_t* d_dind, const double* d_val, const unsigned char* d_flags, uint64_t n,
+                       uint32_t k, int64_t* d_indeg, InLists* out);
+// ... and the n_long lists named in d_long (the caller's row kernel found them), once the host knows n_long.
+int32_t in_lists_order_long(srx_ctx* ctx, uint64_t n, uint32_t k, const uint32_t* d_long, uint64_t n_long, InLists* io);
+
 // ---- the union of a k-NN list with its transpose (graph.hip) -------------------------------------------------------------------
 // What a row kernel finds wrong with a list (OR-ed into a flag word), and the refusal that names it: `who` starts the message.
 enum { kBadRange = 1, kBadSelf = 2, kBadDup = 4, kBadDist = 8 };

@@ -910,6 +910,25 @@ public:
                                          static_cast<std::uint32_t>(k), &g.h_));
         return g;
     }
+    // The shared-nearest-neighbour graph (Seurat's FindNeighbors, PhenoGraph): Jaccard index of the neighbour sets, pruned; an
+    // ordinary Graph whose connectivities louvain(), umap(), paga() read.  Of a k-NN list (n x k row-major; `distances` may be
+    // empty): srx_snn_from_knn.  opts null: Jaccard weights, every sharing pair, the cell in its own set, prune 1 / 15.
+    static Graph snn_from_knn(Context& ctx, const std::vector<std::uint32_t>& indices, const std::vector<double>& distances,
+                              std::size_t k, const srx_snn_opts* opts = nullptr, srx_snn_info* info = nullptr) {
+        if (k == 0 || indices.size() % k || (!distances.empty() && indices.size() != distances.size()))
+            throw Error(SRX_E_ARG, "Graph::snn_from_knn: indices must be n x k, distances too or empty");
+        Graph g(ctx);
+        ctx.check(srx_snn_from_knn(ctx.handle(), indices.empty() ? nullptr : indices.data(),
+                                   distances.empty() ? nullptr : distances.data(), indices.size() / k,
+                                   static_cast<std::uint32_t>(k), opts, info, &g.h_));
+        return g;
+    }
+    // ... of the list this graph holds on the device, with no host round trip (srx_snn_graph): a new Graph, this one untouched
+    Graph snn(const srx_snn_opts* opts = nullptr, srx_snn_info* info = nullptr) const {
+        Graph g(*ctx_);
+        ctx_->check(srx_snn_graph(h_, opts, info, &g.h_));
+        return g;
+    }
     Graph(Graph&& o) noexcept : ctx_(o.ctx_), h_(o.h_), knn_info_(o.knn_info_) { o.h_ = nullptr; }
     Graph& operator=(Graph&& o) noexcept {
         std::swap(ctx_, o.ctx_);
@@ -1084,6 +1103,12 @@ inline std::vector<double> umap_transform_knn(Context& ctx, const std::vector<st
     ctx.check(srx_umap_transform_knn(ctx.handle(), nq ? indices.data() : nullptr, nq ? distances.data() : nullptr, nq, kq,
                                      ref_embedding.empty() ? nullptr : ref_embedding.data(), ref_embedding.size() / dim, dim, opts, &o, info));
     return emb;
+}
+// the smallest shared count whose Jaccard index s / (2K - s) reaches `prune` (srx_snn_min_shared: host code, no GPU)
+inline std::uint32_t snn_min_shared(std::uint32_t k, bool include_self = true, double prune = 1.0 / 15.0) {
+    std::uint32_t s = 0;
+    if (srx_snn_min_shared(k, include_self ? 1 : 0, prune, &s) != SRX_OK) throw Error(SRX_E_ARG, srx_last_error(nullptr));
+    return s;
 }
 // PAGA of any directed pattern (CSR; every stored entry counts once) with one label below n_groups per row: srx_paga_csr
 inline Paga paga_csr(Context& ctx, const std::vector<std::uint64_t>& indptr, const std::vector<std::uint32_t>& indices,

@@ -20,6 +20,7 @@ from .markers import group_moments, rank_genes_groups
 from .paga import paga, paga_csr, paga_from_counts, paga_init_positions
 from .neighbors import KnnIndex, connectivities_from_knn, knn_index, knn_index_points, knn_points, neighbors, neighbors_approx
 from .regress import pca_regress_scale, regress_fit, regress_gram, regress_out, scale
+from .snn import neighbors_snn, snn_graph, snn_min_shared
 from .score import cell_cycle_phase, gene_list_sums, qc_gene_fractions, score_genes, score_genes_cell_cycle, score_genes_controls
 from .tsne import Tsne, tsne, tsne_affinities, tsne_affinities_graph, tsne_embedding, tsne_forces, tsne_run
 from .umap import fit_ab, graph_embedding, umap, umap_csr
