@@ -1510,6 +1510,114 @@ int32_t srx_tsne_run(srx_tsne* h, srx_mat* m, const srx_tsne_opts* opts, const d
 int32_t srx_tsne_embedding_fetch(srx_tsne* h, double* out);
 void    srx_tsne_free(srx_tsne* h);
 
+/* ---- ForceAtlas2 layout of a symmetric weighted graph in 2 dimensions: what sc.tl.draw_graph(layout="fa") gives
+ * obsm["X_draw_graph_fa"] ----------------------------------------------------------------------------------------------------
+ * Not in the reference.  ForceAtlas2 is Jacomy, Venturini, Heymann, Bastian 2014 (PLoS ONE 9(6) e98679) with the defaults
+ * scanpy passes to the fa2 package, RESTATED here so that the result is bit-identical from call to call; this definition is
+ * what is tested.  The three force expressions are compared with networkx.forceatlas2_layout's (3.4.2) through the dense
+ * expressions of the tests; networkx's speed control differs (it accumulates swing over the iterations and measures it against
+ * positions), so its layouts are NOT compared point for point, only the quality of a layout (label purity,
+ * tests/golden/make_draw_graph_golden.py).  The fa2 package, Gephi and scanpy are NOT compared: none of them is installed
+ * where the tests are made.  All arithmetic is IEEE f64, every operation rounded once: no FMA contraction, no -ffast-math, no
+ * floating-point atomics.  sqrt is correctly rounded; log1p is the device library's (ocml).  mix() and G are those of the
+ * UMAP section.
+ *
+ * 1. Input.  A symmetric graph W with exactly the contract of srx_louvain_csr (u64 indptr, u32 indices strictly ascending in a
+ *   row, positive finite weights, no diagonal, W_ij and W_ji the same bits) and positions Y (n x 2 f64).  Only 2-D.
+ * 2. Masses.  m_i = 1 + (the number of stored entries of row i), an integer.  M_tot = n + nnz (info.total_mass) must be below
+ *   2^32 (refused otherwise): the pyramid's u64 sums of m_i U_i cannot wrap then.
+ * 3. Pyramid.  t-SNE's (section 3 above) with masses: lo, side, U, the levels, the cell of a point and the default L are the
+ *   same.  A cell holds the integer mass M = sum m_i and the u64 sums SX = sum m_i U_i0, SY = sum m_i U_i1 over its points
+ *   (order-free, exact); com_c = lo_c + (f64(S_c) / f64(M)) * (side * 2^-32).
+ * 4. Repulsion of point i, kr = scaling_ratio.  The walk of t-SNE's section 3: from the four level-1 cells, children by
+ *   ascending code 2 * ybit + xbit, a cell without points skipped.  For a visited cell d = y_i - com, d2 = d_0 d_0 + d_1 d_1:
+ *     if s_l * s_l < (theta * theta) * d2 the cell is ACCEPTED (cells_accepted; d2 > 0 follows):
+ *       rep_i += ((kr * (f64(m_i) * f64(M))) / d2) * d;
+ *     otherwise, if l == L, it is OPENED EXACTLY (cells_exact): for each member j != i in ascending j, e = y_i - y_j,
+ *       e2 = e_0 e_0 + e_1 e_1: if e2 > 0, rep_i += ((kr * (f64(m_i) * f64(m_j))) / e2) * e, else pairs_coincident += 1;
+ *       pairs_exact counts both kinds;
+ *     otherwise its four children are visited.
+ *   theta = 0 never accepts a cell: the exact O(n^2) sum.  The terms of a point are added one by one in exactly this
+ *   depth-first order, which depends on (n, the cell of every point) alone and not on which points share a wave or a workgroup.
+ * 5. Gravity, g = gravity.  r = sqrt(y_i0 y_i0 + y_i1 y_i1); if r == 0 the term is 0.  Linear: grav_i = -(((g * f64(m_i)) / r)
+ *   * y_i).  strong_gravity: grav_i = -((g * f64(m_i)) * y_i), Gephi's and networkx's form; the fa2 package multiplies by the
+ *   scaling ratio once more, which is NOT done here.
+ * 6. Attraction.  attr_i = -(sum over row i of f_ij * (y_i - y_j)) with f_ij = W_ij, or with linlog f_ij = W_ij * (log1p(d) / d)
+ *   for d = sqrt(|y_i - y_j|^2) > 0, else 0.  SRX_FA2_GROUP lanes own a vertex: lane s sums the entries lo + s,
+ *   lo + s + SRX_FA2_GROUP, ... of the row in that order (each term (f_ij * e_0, f_ij * e_1) added to the lane's sum) and
+ *   the lanes' sums meet in a butterfly (offsets SRX_FA2_GROUP / 2, ..., 1); the sum is negated once.
+ *   F_i = (rep_i + grav_i) + attr_i.
+ * 7. Iteration t = 1..T, everything read from Y^{t-1}.  Start state: Fprev = 0, speed = 1, eff = 1.
+ *   swing_i = |Fprev_i - F_i|, tract_i = 0.5 * |Fprev_i + F_i| (|v| = sqrt(v_0 v_0 + v_1 v_1)).  S = sum_i f64(m_i) * swing_i,
+ *   Tr = sum_i f64(m_i) * tract_i, the rows in index order: a workgroup of 256 lanes holds 256 / SRX_FA2_GROUP consecutive
+ *   rows (the lanes that do not own a row hold 0) and sums its lanes by butterflies, the wave sums left to right; one
+ *   workgroup adds the workgroup sums: thread u chains the sums u, u + 256, ..., then the same workgroup sum.
+ *   The speed rule (Gephi's, fa2's, networkx's estimate_factor), in this order of operations, jtol = jitter_tolerance:
+ *     opt = 0.05 * sqrt(f64(n));  jt = jtol * max(sqrt(opt), min(10, (opt * Tr) / (f64(n) * f64(n))));
+ *     if Tr > 0 and S / Tr > 2: if eff > 0.05, eff = eff * 0.5; then jt = max(jt, jtol);
+ *     target = +inf if S == 0, else ((jt * eff) * Tr) / S;
+ *     if S > jt * Tr: if eff > 0.05, eff = eff * 0.7; else if speed < 1000: eff = eff * 1.3;
+ *     speed = speed + min(target - speed, 0.5 * speed).
+ *   It runs on the device, as one thread of the kernel that finishes the sums; srx_fa2_speed is the same statement on the host.
+ *   Then y_i = y_i + F_i * (speed / (1 + sqrt(speed * (f64(m_i) * swing_i)))) and Fprev = F.
+ *   n_iter == 0 means T = 500; stop_after = s (0 = T) runs only iterations 1..s.
+ * 8. Starts.  SRX_FA2_INIT_GIVEN: `init`, n x 2 f64, finite (what srx_paga_init_positions makes, for scanpy's
+ *   init_pos="paga").  SRX_FA2_INIT_RANDOM: coordinate c = 2 i + j is (mix(seed + G * (c + 1)) >> 11) * 2^-53, in [0, 1): scanpy's
+ *   np.random.random((n, 2)) with this hash in the place of numpy's generator.
+ * Defaults of a NULL opts: theta 1.2, scaling_ratio 2, gravity 1, jitter_tolerance 1, seed 0, n_iter 500, levels auto, the
+ *   hashed start, no flags.  In a given opts the four f64 parameters are taken literally (theta = 0 is the exact sum,
+ *   gravity = 0 none); n_iter = 0 means 500 and levels = 0 auto.
+ * Refused with SRX_E_ARG and a message, nothing written: theta, scaling_ratio, gravity or jitter_tolerance negative, NaN or
+ *   Inf; levels outside 0 .. SRX_TSNE_MAX_LEVELS; n_iter negative or above SRX_FA2_MAX_ITERS, stop_after < 0 or > T; an unknown
+ *   start, a NaN or Inf start, SRX_FA2_INIT_GIVEN without init; M_tot >= 2^32; everything srx_louvain_csr refuses about a
+ *   graph; a context with more than one rank; a null handle.  n == 0 gives an empty result; n == 1 runs (gravity alone).
+ * Out of scope: 3-D; outboundAttractionDistribution; adjustSizes; edgeWeightInfluence other than 1; an adaptive tree (dense
+ *   clumps cost pairs_exact); the other igraph layouts of draw_graph (fr, drl, kk, ...); multi-rank. */
+#define SRX_FA2_GROUP 8           /* lanes that own one vertex in the attraction */
+#define SRX_FA2_MAX_ITERS 1048576
+enum { SRX_FA2_INIT_GIVEN = 0, SRX_FA2_INIT_RANDOM = 1 };
+typedef struct srx_fa2_opts {
+    double   theta;                 /* taken literally: 0 is the exact sum */
+    double   scaling_ratio, gravity, jitter_tolerance;
+    uint64_t seed;
+    int32_t  n_iter;                /* 0 = 500 */
+    int32_t  stop_after;            /* 0 = n_iter */
+    int32_t  levels;                /* 0 = from n */
+    int32_t  init;
+    int32_t  strong_gravity, linlog;   /* flags: 0 or 1 */
+} srx_fa2_opts;
+typedef struct srx_fa2_info {
+    uint64_t n, nnz, total_mass;
+    uint32_t n_iter, iters_run, levels, reserved_;
+    double   speed, speed_efficiency, swing, traction;   /* after / of the last iteration */
+    double   side;                                       /* of the last iteration's pyramid */
+    uint64_t cells_accepted, cells_exact, pairs_exact, pairs_coincident;   /* the walk of the last iteration */
+    double   ms;                    /* hipEvent time of the device work */
+} srx_fa2_info;
+typedef struct srx_fa2_force_info {
+    uint32_t levels, reserved_;
+    double   side, lo[2];
+    uint64_t total_mass, cells_accepted, cells_exact, pairs_exact, pairs_coincident;
+} srx_fa2_force_info;
+/* The layout of the connectivities C of a graph handle, read where they lie.  init: NULL unless SRX_FA2_INIT_GIVEN;
+ * layout_out (n x 2 f64, row-major) and info may be NULL.  The layout stays with the handle, in a slot of its own: labels,
+ * UMAP embedding and diffusion map of the handle are left untouched. */
+int32_t srx_draw_graph(srx_graph* g, const srx_fa2_opts* opts, const double* init, double* layout_out, srx_fa2_info* info);
+/* The same for any symmetric graph in host CSR form, validated on the device as srx_louvain_csr validates. */
+int32_t srx_draw_graph_csr(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* indices, const double* weights, uint64_t n,
+                           const srx_fa2_opts* opts, const double* init, double* layout_out, srx_fa2_info* info);
+/* The last srx_draw_graph's layout (n x 2 f64).  SRX_E_ARG when none has run on the handle. */
+int32_t srx_graph_layout_fetch(srx_graph* g, double* out);
+/* A diagnostic: sections 4 to 6's rep, grav and attr (n x 2 each) and the masses (n u32) at the given Y (n x 2 f64, host,
+ * finite), once, with the kernels the run uses.  Of opts (NULL: the defaults) theta, scaling_ratio, gravity, levels and the two
+ * flags are read.  Any output may be NULL. */
+int32_t srx_draw_graph_forces(srx_ctx* ctx, const uint64_t* indptr, const uint32_t* indices, const double* weights, uint64_t n,
+                              const double* Y, const srx_fa2_opts* opts, double* rep_out, double* grav_out, double* attr_out,
+                              uint32_t* mass_out, srx_fa2_force_info* info);
+/* Section 7's speed rule on the host (no GPU): *speed and *eff are read and updated.  Refused: n == 0, S, Tr or
+ * jitter_tolerance negative, NaN or Inf, a speed or eff that is negative or NaN, a null pointer. */
+int32_t srx_fa2_speed(uint64_t n, double S, double Tr, double jitter_tolerance, double* speed, double* eff);
+
 /* ---- Diffusion maps and pseudotime: what sc.tl.diffmap gives obsm["X_diffmap"], uns["diffmap_evals"], and sc.tl.dpt
  * (without branchings) gives obs["dpt_pseudotime"] ---------------------------------------------------------------------------
  * Not in the reference.  This is scanpy's compute_transitions with its _transitions_sym, compute_eigen and

@@ -1341,6 +1341,64 @@ pub mod processing_free {
             }))?;
             Array2::from_shape_vec((labels.len(), dim), out).map_err(|e| anyhow!("paga_init_positions: {e}"))
         }
+        /// ForceAtlas2 layout of the cells' k-NN connectivities, what `sc.tl.draw_graph(layout="fa")` gives (srx_neighbors_result,
+        /// then srx_draw_graph on the graph where it lies, every default of include/srx.h: 500 iterations, theta 1.2).  `init`:
+        /// `n x 2` start positions (what `paga_init_positions` returns), or None for the hashed start of `seed`.
+        pub fn draw_graph(adata: &IMAnnData, n_neighbors: usize, n_pcs: usize, init: Option<&Array2<f64>>, seed: u64)
+                          -> anyhow::Result<(Array2<f64>, SrxFa2Info)> {
+            let kopts = SrxKnnOpts { k: n_neighbors as i32, n_dims: n_pcs as i32, include_self: 0, reserved: 0 };
+            let start: Option<Vec<f64>> = init.map(|y| y.iter().copied().collect());    // row-major
+            let fopts = SrxFa2Opts { theta: 1.2, scaling_ratio: 2.0, gravity: 1.0, jitter_tolerance: 1.0, seed, n_iter: 500,
+                                     stop_after: 0, levels: 0, init: if start.is_some() { 0 } else { 1 }, strong_gravity: 0, linlog: 0 };
+            with_resident(adata, |x| {
+                let mut g: *mut SrxGraph = null_mut();
+                x.ctx.check(unsafe { srx_neighbors_result(x.mat, &kopts, null_mut(), &mut g) })?;
+                let mut ginfo: SrxGraphInfo = unsafe { std::mem::zeroed() };
+                let mut info: SrxFa2Info = unsafe { std::mem::zeroed() };
+                let out = x.ctx.check(unsafe { srx_graph_info_get(g, &mut ginfo) }).and_then(|_| {
+                    let n = ginfo.n as usize;
+                    if let Some(s) = &start {
+                        if s.len() != n * 2 {
+                            bail!("draw_graph: the start has {} values for {n} x 2", s.len());
+                        }
+                    }
+                    let mut y = vec![0.0f64; n * 2];
+                    x.ctx.check(unsafe {
+                        srx_draw_graph(g, &fopts, start.as_ref().map_or(std::ptr::null(), |s| s.as_ptr()), y.as_mut_ptr(), &mut info)
+                    })?;
+                    Ok((Array2::from_shape_vec((n, 2), y).map_err(|e| anyhow!("draw_graph: {e}"))?, info))
+                });
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        /// The same for a symmetric weighted graph the caller holds (srx_draw_graph_csr validates it on the device), from the
+        /// hashed start of `seed`.
+        pub fn draw_graph_csr(w: &CsrMatrix<f64>, seed: u64) -> anyhow::Result<(Array2<f64>, SrxFa2Info)> {
+            let n = w.nrows();
+            let indptr: Vec<u64> = w.row_offsets().iter().map(|&v| v as u64).collect();
+            let indices: Vec<u32> = w.col_indices().iter().map(|&v| v as u32).collect();
+            let fopts = SrxFa2Opts { theta: 1.2, scaling_ratio: 2.0, gravity: 1.0, jitter_tolerance: 1.0, seed, n_iter: 500,
+                                     stop_after: 0, levels: 0, init: 1, strong_gravity: 0, linlog: 0 };
+            with_ctx(|c| {
+                let mut y = vec![0.0f64; n * 2];
+                let mut info: SrxFa2Info = unsafe { std::mem::zeroed() };
+                c.check(unsafe {
+                    srx_draw_graph_csr(c.0, indptr.as_ptr(), indices.as_ptr(), w.values().as_ptr(), n as u64, &fopts, std::ptr::null(),
+                                       y.as_mut_ptr(), &mut info)
+                })?;
+                Ok((Array2::from_shape_vec((n, 2), y).map_err(|e| anyhow!("draw_graph_csr: {e}"))?, info))
+            })
+        }
+        /// The speed rule of a ForceAtlas2 iteration on the host (srx_fa2_speed; no GPU): the new (speed, efficiency).
+        pub fn fa2_speed(n: u64, swing: f64, traction: f64, jitter_tolerance: f64, speed: f64, efficiency: f64)
+                         -> anyhow::Result<(f64, f64)> {
+            let (mut s, mut e) = (speed, efficiency);
+            if unsafe { srx_fa2_speed(n, swing, traction, jitter_tolerance, &mut s, &mut e) } != 0 {
+                bail!("fa2_speed: refused (n = {n}, swing = {swing}, traction = {traction})");
+            }
+            Ok((s, e))
+        }
         /// Moran's I and Geary's C per gene with their z-scores under normality; a constant gene has NaN statistics.
         pub struct Autocorr {
             pub morans_i: Vec<f64>,

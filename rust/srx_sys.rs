@@ -18,6 +18,8 @@ pub const SRX_TSNE_MAX_K: i32 = 64;
 pub const SRX_TSNE_MAX_LEVELS: i32 = 12;
 pub const SRX_TSNE_GROUP: i32 = 8;
 pub const SRX_TSNE_MAX_ITERS: i32 = 1048576;
+pub const SRX_FA2_GROUP: i32 = 8;
+pub const SRX_FA2_MAX_ITERS: i32 = 1048576;
 pub const SRX_DIFFMAP_GROUP: i32 = 8;
 pub const SRX_DIFFMAP_MAX_COMPS: i32 = 64;
 pub const SRX_DIFFMAP_MAX_NCV: i32 = 129;
@@ -92,6 +94,8 @@ pub const SRX_UMAP_INIT_PCA: i32 = 2;
 pub const SRX_TSNE_INIT_GIVEN: i32 = 0;
 pub const SRX_TSNE_INIT_RANDOM: i32 = 1;
 pub const SRX_TSNE_INIT_PCA: i32 = 2;
+pub const SRX_FA2_INIT_GIVEN: i32 = 0;
+pub const SRX_FA2_INIT_RANDOM: i32 = 1;
 pub const SRX_HARMONY_CORRECTED: i32 = 0;
 pub const SRX_HARMONY_R: i32 = 1;
 pub const SRX_HARMONY_CENTROIDS: i32 = 2;
@@ -706,6 +710,58 @@ pub struct SrxTsneForceInfo {      // `srx_tsne_force_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxFa2Opts {      // `srx_fa2_opts`
+    pub theta: f64,
+    pub scaling_ratio: f64,
+    pub gravity: f64,
+    pub jitter_tolerance: f64,
+    pub seed: u64,
+    pub n_iter: i32,
+    pub stop_after: i32,
+    pub levels: i32,
+    pub init: i32,
+    pub strong_gravity: i32,
+    pub linlog: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxFa2Info {      // `srx_fa2_info`
+    pub n: u64,
+    pub nnz: u64,
+    pub total_mass: u64,
+    pub n_iter: u32,
+    pub iters_run: u32,
+    pub levels: u32,
+    pub reserved: u32,
+    pub speed: f64,
+    pub speed_efficiency: f64,
+    pub swing: f64,
+    pub traction: f64,
+    pub side: f64,
+    pub cells_accepted: u64,
+    pub cells_exact: u64,
+    pub pairs_exact: u64,
+    pub pairs_coincident: u64,
+    pub ms: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxFa2ForceInfo {      // `srx_fa2_force_info`
+    pub levels: u32,
+    pub reserved: u32,
+    pub side: f64,
+    pub lo: [f64; 2 as usize],
+    pub total_mass: u64,
+    pub cells_accepted: u64,
+    pub cells_exact: u64,
+    pub pairs_exact: u64,
+    pub pairs_coincident: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxDiffmapOpts {      // `srx_diffmap_opts`
     pub tol: f64,
     pub seed: u64,
@@ -1149,6 +1205,17 @@ extern "C" {
                         embedding_out: *mut f64, info: *mut SrxTsneRunInfo) -> i32;
     pub fn srx_tsne_embedding_fetch(h: *mut SrxTsne, out: *mut f64) -> i32;
     pub fn srx_tsne_free(h: *mut SrxTsne);
+    pub fn srx_draw_graph(g: *mut SrxGraph, opts: *const SrxFa2Opts, init: *const f64, layout_out: *mut f64,
+                          info: *mut SrxFa2Info) -> i32;
+    pub fn srx_draw_graph_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64,
+                              n: u64, opts: *const SrxFa2Opts, init: *const f64, layout_out: *mut f64,
+                              info: *mut SrxFa2Info) -> i32;
+    pub fn srx_graph_layout_fetch(g: *mut SrxGraph, out: *mut f64) -> i32;
+    pub fn srx_draw_graph_forces(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64,
+                                 n: u64, Y: *const f64, opts: *const SrxFa2Opts, rep_out: *mut f64,
+                                 grav_out: *mut f64, attr_out: *mut f64, mass_out: *mut u32,
+                                 info: *mut SrxFa2ForceInfo) -> i32;
+    pub fn srx_fa2_speed(n: u64, S: f64, Tr: f64, jitter_tolerance: f64, speed: *mut f64, eff: *mut f64) -> i32;
     pub fn srx_diffmap(g: *mut SrxGraph, opts: *const SrxDiffmapOpts, evals_out: *mut f64, evecs_out: *mut f64,
                        info: *mut SrxDiffmapInfo) -> i32;
     pub fn srx_diffmap_csr(ctx: *mut SrxCtx, indptr: *const u64, indices: *const u32, weights: *const f64, n: u64,

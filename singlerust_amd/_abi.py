@@ -19,6 +19,8 @@ TSNE_MAX_K = 64
 TSNE_MAX_LEVELS = 12
 TSNE_GROUP = 8
 TSNE_MAX_ITERS = 1048576
+FA2_GROUP = 8
+FA2_MAX_ITERS = 1048576
 DIFFMAP_GROUP = 8
 DIFFMAP_MAX_COMPS = 64
 DIFFMAP_MAX_NCV = 129
@@ -94,6 +96,8 @@ UMAP_INIT_PCA = 2
 TSNE_INIT_GIVEN = 0
 TSNE_INIT_RANDOM = 1
 TSNE_INIT_PCA = 2
+FA2_INIT_GIVEN = 0
+FA2_INIT_RANDOM = 1
 HARMONY_CORRECTED = 0
 HARMONY_R = 1
 HARMONY_CENTROIDS = 2
@@ -376,6 +380,27 @@ class TsneForceInfo(C.Structure):      # srx_tsne_force_info
                 ("cells_accepted", C.c_uint64), ("cells_exact", C.c_uint64), ("pairs_exact", C.c_uint64)]
 
 
+class Fa2Opts(C.Structure):      # srx_fa2_opts
+    _fields_ = [("theta", C.c_double), ("scaling_ratio", C.c_double), ("gravity", C.c_double),
+                ("jitter_tolerance", C.c_double), ("seed", C.c_uint64), ("n_iter", C.c_int32),
+                ("stop_after", C.c_int32), ("levels", C.c_int32), ("init", C.c_int32), ("strong_gravity", C.c_int32),
+                ("linlog", C.c_int32)]
+
+
+class Fa2Info(C.Structure):      # srx_fa2_info
+    _fields_ = [("n", C.c_uint64), ("nnz", C.c_uint64), ("total_mass", C.c_uint64), ("n_iter", C.c_uint32),
+                ("iters_run", C.c_uint32), ("levels", C.c_uint32), ("reserved_", C.c_uint32), ("speed", C.c_double),
+                ("speed_efficiency", C.c_double), ("swing", C.c_double), ("traction", C.c_double),
+                ("side", C.c_double), ("cells_accepted", C.c_uint64), ("cells_exact", C.c_uint64),
+                ("pairs_exact", C.c_uint64), ("pairs_coincident", C.c_uint64), ("ms", C.c_double)]
+
+
+class Fa2ForceInfo(C.Structure):      # srx_fa2_force_info
+    _fields_ = [("levels", C.c_uint32), ("reserved_", C.c_uint32), ("side", C.c_double), ("lo", C.c_double * 2),
+                ("total_mass", C.c_uint64), ("cells_accepted", C.c_uint64), ("cells_exact", C.c_uint64),
+                ("pairs_exact", C.c_uint64), ("pairs_coincident", C.c_uint64)]
+
+
 class DiffmapOpts(C.Structure):      # srx_diffmap_opts
     _fields_ = [("tol", C.c_double), ("seed", C.c_uint64), ("n_comps", C.c_int32), ("ncv", C.c_int32),
                 ("max_matvecs", C.c_int32), ("density_normalize", C.c_int32)]
@@ -612,6 +637,12 @@ SIGNATURES = {
     "srx_tsne_run": (C.c_int32, [P, P, C.POINTER(TsneOpts), P, P, C.POINTER(TsneRunInfo)]),
     "srx_tsne_embedding_fetch": (C.c_int32, [P, P]),
     "srx_tsne_free": (None, [P]),
+    "srx_draw_graph": (C.c_int32, [P, C.POINTER(Fa2Opts), P, P, C.POINTER(Fa2Info)]),
+    "srx_draw_graph_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(Fa2Opts), P, P, C.POINTER(Fa2Info)]),
+    "srx_graph_layout_fetch": (C.c_int32, [P, P]),
+    "srx_draw_graph_forces": (C.c_int32, [P, P, P, P, C.c_uint64, P, C.POINTER(Fa2Opts), P, P, P, P,
+                                          C.POINTER(Fa2ForceInfo)]),
+    "srx_fa2_speed": (C.c_int32, [C.c_uint64, C.c_double, C.c_double, C.c_double, P, P]),
     "srx_diffmap": (C.c_int32, [P, C.POINTER(DiffmapOpts), P, P, C.POINTER(DiffmapInfo)]),
     "srx_diffmap_csr": (C.c_int32, [P, P, P, P, C.c_uint64, C.POINTER(DiffmapOpts), P, P, C.POINTER(DiffmapInfo)]),
     "srx_graph_diffmap_fetch": (C.c_int32, [P, P, P, P]),

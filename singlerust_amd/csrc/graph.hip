@@ -603,7 +603,7 @@ int32_t srx_graph_fetch_scales(srx_graph* g, double* rho, double* sigma) {
 
 void srx_graph_free(srx_graph* g) {
     if (!g) return;
-    if (g->d_block || g->d_cblock || g->d_labels || g->d_embed || g->d_dm_t || g->d_dm_evecs) {
+    if (g->d_block || g->d_cblock || g->d_labels || g->d_embed || g->d_dm_t || g->d_dm_evecs || g->d_layout) {
         (void)hipSetDevice(g->ctx->device);
         (void)hipStreamSynchronize(g->ctx->stream);
         if (g->d_block) (void)hipFree(g->d_block);
@@ -612,6 +612,7 @@ void srx_graph_free(srx_graph* g) {
         if (g->d_embed) (void)hipFree(g->d_embed);
         if (g->d_dm_t) (void)hipFree(g->d_dm_t);
         if (g->d_dm_evecs) (void)hipFree(g->d_dm_evecs);
+        if (g->d_layout) (void)hipFree(g->d_layout);
     }
     delete g;
 }

@@ -1,5 +1,5 @@
 // graph_handle.hpp — the srx_graph handle of srx.h: built by graph.hip, read where it lies by the graph algorithms (louvain.hip,
-// umap.hip, diffmap.hip, tsne.hip), and the union of a k-NN list with its transpose that graph.hip builds for C and tsne.hip for P.
+// umap.hip, diffmap.hip, tsne.hip, draw_graph.hip), and the union of a k-NN list with its transpose that graph.hip builds for C and tsne.hip for P.
 #pragma once
 
 #include "common.hpp"
@@ -36,6 +36,9 @@ struct srx_graph {
     std::vector<double> dm_evals;
     uint32_t dm_n_comps = 0;
     bool dm_t_valid = false, dm_valid = false;
+    // the layout of the last srx_draw_graph on this handle (draw_graph.hip): n x 2 f64, row-major
+    double* d_layout = nullptr;
+    bool layout_valid = false;
 };
 
 namespace srx {

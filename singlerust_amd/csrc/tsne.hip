@@ -33,6 +33,7 @@
 #include "graph_handle.hpp"
 #include "hash.hpp"
 #include "pca_internal.hpp"
+#include "pyramid.hpp"
 #include "scan.hpp"
 
 #include <cmath>
@@ -63,30 +64,9 @@ constexpr int kLdsCells = ((1 << (2 * (kLdsLevels + 1))) - 4) / 3;
 // the root is accepted at |H - log u| <= 9e-10: the header promises 1e-9 to a reader who evaluates H with another exp and log
 constexpr double kTsRootTol = 9e-10;
 constexpr unsigned long long kTsInfBits = 0x7FF0000000000000ull;
-constexpr unsigned long long kSign = 0x8000000000000000ull;
-// the small block (8-byte words); the first TS_ZEROED are cleared before every pyramid
-enum { TS_MAX0 = 0, TS_NMIN0, TS_MAX1, TS_NMIN1, TS_ACC, TS_EXACT, TS_PAIRS, TS_ZEROED, TS_SIDE = TS_ZEROED, TS_LO0, TS_LO1, TS_Z,
+// the small block (8-byte words) behind the bounds of pyramid.hpp; the first TS_ZEROED are cleared before every pyramid
+enum { TS_ACC = TS_BOUNDS_WORDS, TS_EXACT, TS_PAIRS, TS_ZEROED, TS_SIDE = TS_ZEROED, TS_LO0, TS_LO1, TS_Z,
        TS_KL, TS_ABSMAX, TS_PCAMAX, TS_WORDS = 16 };
-
-// first cell of level l (1-based) in the concatenated levels, and their total up to L
-__host__ __device__ __forceinline__ uint32_t level_off(int l) { return ((1u << (2 * l)) - 4u) / 3u; }
-
-// a finite double as an integer that orders as the double does
-__device__ __forceinline__ unsigned long long order_key(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b & kSign) ? ~b : (b | kSign);
-}
-__device__ __forceinline__ double order_val(unsigned long long key) {
-    return __longlong_as_double((long long)((key & kSign) ? (key ^ kSign) : ~key));
-}
-__device__ __forceinline__ uint32_t spread_bits(uint32_t x) {      // bit b -> bit 2 b (16 bits in)
-    x = (x | (x << 8)) & 0x00FF00FFu;
-    x = (x | (x << 4)) & 0x0F0F0F0Fu;
-    x = (x | (x << 2)) & 0x33333333u;
-    x = (x | (x << 1)) & 0x55555555u;
-    return x;
-}
-__device__ __forceinline__ double2 ts_load(const double* __restrict__ y, uint64_t i) { return reinterpret_cast<const double2*>(y)[i]; }
 
 // ---- affinities ------------------------------------------------------------------------------------------------------------------
 // the entropy of the lane's row at beta: x = D - m (0 on the lanes behind the row), every lane holds the same bits
@@ -239,23 +219,6 @@ __global__ void __launch_bounds__(256) k_tsne_bounds(const double* __restrict__ 
         const unsigned long long m = block_max<4>(k[c], s_wave);
         if (threadIdx.x == 0 && m) atomicMax(&small[TS_MAX0 + c], m);
     }
-}
-
-struct TsGeom {
-    double lo0, lo1, side;
-};
-__device__ __forceinline__ TsGeom ts_geom(const unsigned long long* __restrict__ small) {
-    TsGeom g;
-    g.lo0 = order_val(~small[TS_NMIN0]);
-    g.lo1 = order_val(~small[TS_NMIN1]);
-    const double e0 = order_val(small[TS_MAX0]) - g.lo0, e1 = order_val(small[TS_MAX1]) - g.lo1;
-    const double ext = e0 > e1 ? e0 : e1;
-    g.side = ext == 0.0 ? 1.0 : ext * (1.0 + 0x1p-20);
-    return g;
-}
-__device__ __forceinline__ uint32_t ts_quant(double v, double lo, double side) {
-    const double f = floor(((v - lo) / side) * 4294967296.0);
-    return (uint32_t)(f < 4294967295.0 ? f : 4294967295.0);
 }
 
 __global__ void __launch_bounds__(256) k_tsne_quant(const double* __restrict__ y, uint64_t n, int L, unsigned long long* __restrict__ small,
@@ -529,11 +492,28 @@ static unsigned ts_stride_grid(uint64_t items) {              // grid-stride ker
     return (unsigned)(b < 2048 ? b : 2048);
 }
 
-static int ts_levels(uint64_t n, int levels) {
+int pyramid_levels(uint64_t n, int levels) {
     if (levels) return levels;
     int L = 1;
     while (L < kTsMaxLevels && (1ull << (2 * (L + 1))) < n) ++L;
     return L;
+}
+
+void pyramid_bounds(srx_ctx* ctx, const double* d_y, uint64_t n, unsigned long long* d_small) {
+    hipLaunchKernelGGL(k_tsne_bounds, dim3(ts_stride_grid(n)), dim3(256), 0, ctx->stream, d_y, n, d_small);
+}
+
+void pyramid_up(srx_ctx* ctx, unsigned long long* d_a, unsigned long long* d_b, unsigned long long* d_c, int L) {
+    for (int src = L; src > 1;) {
+        const int nlev = src - 1 < 3 ? src - 1 : 3;
+        const uint64_t waves = ((1ull << (2 * src)) + kWave - 1) / kWave;
+        hipLaunchKernelGGL(k_tsne_up, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, ctx->stream, d_a, d_b, d_c, src, nlev);
+        src -= nlev;
+    }
+}
+
+void pyramid_absmax(srx_ctx* ctx, const double* d_x, uint64_t rows, uint64_t ld, unsigned long long* d_dst) {
+    hipLaunchKernelGGL(k_tsne_absmax, dim3(ts_stride_grid(rows * 2)), dim3(256), 0, ctx->stream, d_x, rows, ld, d_dst);
 }
 
 static SymCsr ts_csr(const srx_tsne* h) { return SymCsr{h->d_ptr, h->d_ind, h->d_dat, h->n, h->info.nnz}; }
@@ -684,14 +664,9 @@ static int32_t ts_repulsion(srx_ctx* ctx, const TsWork& w, const double* d_y, ui
     const unsigned pts = grid256(n);
     SRX_HIP(ctx, hipMemsetAsync(w.d_small, 0, TS_ZEROED * 8, st));
     SRX_HIP(ctx, hipMemsetAsync(w.d_cnt, 0, w.zero_bytes, st));
-    hipLaunchKernelGGL(k_tsne_bounds, dim3(ts_stride_grid(n)), dim3(256), 0, st, d_y, n, w.d_small);
+    pyramid_bounds(ctx, d_y, n, w.d_small);
     hipLaunchKernelGGL(k_tsne_quant, dim3(pts), dim3(256), 0, st, d_y, n, w.L, w.d_small, w.d_cnt, w.d_sx, w.d_sy, w.d_code);
-    for (int src = w.L; src > 1;) {
-        const int nlev = src - 1 < 3 ? src - 1 : 3;
-        const uint64_t waves = ((1ull << (2 * src)) + kWave - 1) / kWave;
-        hipLaunchKernelGGL(k_tsne_up, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, w.d_cnt, w.d_sx, w.d_sy, src, nlev);
-        src -= nlev;
-    }
+    pyramid_up(ctx, w.d_cnt, w.d_sx, w.d_sy, w.L);
     hipLaunchKernelGGL(k_tsne_cells, dim3(grid256(w.total)), dim3(256), 0, st, w.d_cnt, w.d_sx, w.d_sy, w.total, w.d_small, w.d_cx, w.d_cy,
                        w.d_cm);
     SRX_HIP(ctx, hipGetLastError());
@@ -736,7 +711,7 @@ static int32_t ts_opts(srx_ctx* ctx, const srx_tsne_opts* in, uint64_t n, TsOpts
     out->o = o;
     out->iters = (uint32_t)o.n_iter;
     out->run = (uint32_t)(o.stop_after ? o.stop_after : o.n_iter);
-    out->L = ts_levels(n, o.levels);
+    out->L = pyramid_levels(n, o.levels);
     const double au = (double)n / 48.0;
     out->eta = o.learning_rate != 0.0 ? o.learning_rate : (au > 50.0 ? au : 50.0);
     return SRX_OK;
@@ -778,10 +753,10 @@ static int32_t tsne_run(srx_tsne* h, const TsOpts& u, srx_mat* m, const double* 
         hipLaunchKernelGGL(k_tsne_init_random, dim3(grid256(count)), dim3(256), 0, st, d_y0, count, u.o.seed);
     } else if (u.o.init == SRX_TSNE_INIT_PCA) {
         const uint64_t ld = (uint64_t)scores_ld((int)m->pca.n_pc);
-        hipLaunchKernelGGL(k_tsne_absmax, dim3(ts_stride_grid(count)), dim3(256), 0, st, m->pca.d_scores, n, ld, w.d_small + TS_PCAMAX);
+        pyramid_absmax(ctx, m->pca.d_scores, n, ld, w.d_small + TS_PCAMAX);
         hipLaunchKernelGGL(k_tsne_init_pca, dim3(grid256(count)), dim3(256), 0, st, m->pca.d_scores, n, ld, w.d_small, d_y0);
     }
-    hipLaunchKernelGGL(k_tsne_absmax, dim3(ts_stride_grid(count)), dim3(256), 0, st, d_y0, n, (uint64_t)2, w.d_small + TS_ABSMAX);
+    pyramid_absmax(ctx, d_y0, n, 2, w.d_small + TS_ABSMAX);
     SRX_HIP(ctx, hipGetLastError());
     uint64_t hs[TS_WORDS];
     SRX_TRY(d2h(ctx, hs, w.d_small, sizeof hs));
@@ -891,7 +866,7 @@ int32_t srx_tsne_forces(srx_tsne* h, const double* Y, double theta, int32_t leve
     SRX_TRY(ts_check_theta_levels(ctx, theta, levels));
     const uint64_t n = h->n;
     srx_tsne_force_info fi{};
-    fi.levels = (uint32_t)ts_levels(n, levels);
+    fi.levels = (uint32_t)pyramid_levels(n, levels);
     if (n == 0) {
         if (info) *info = fi;
         return SRX_OK;
@@ -907,7 +882,7 @@ int32_t srx_tsne_forces(srx_tsne* h, const double* Y, double theta, int32_t leve
     SRX_TRY(h2d(ctx, d_y, Y, n * 16));
     hipStream_t st = ctx->stream;
     SRX_HIP(ctx, hipMemsetAsync(w.d_small, 0, TS_WORDS * 8, st));
-    hipLaunchKernelGGL(k_tsne_absmax, dim3(ts_stride_grid(n * 2)), dim3(256), 0, st, d_y, n, (uint64_t)2, w.d_small + TS_ABSMAX);
+    pyramid_absmax(ctx, d_y, n, 2, w.d_small + TS_ABSMAX);
     SRX_HIP(ctx, hipGetLastError());
     uint64_t hs[TS_WORDS];
     SRX_TRY(d2h(ctx, hs, w.d_small, sizeof hs));

@@ -1022,6 +1022,22 @@ public:
                                             out.empty() ? nullptr : out.data()));
         return out;
     }
+    // ForceAtlas2 layout of the connectivities, read where they lie (srx_draw_graph): n x 2, row-major.  `opts` null: the
+    // defaults (500 iterations from the hashed start); `init` (n x 2, e.g. paga_init_positions(p, pos, 2)) with
+    // opts->init = SRX_FA2_INIT_GIVEN; `info` (may be null) receives the call's srx_fa2_info
+    std::vector<double> draw_graph(const srx_fa2_opts* opts = nullptr, const std::vector<double>* init = nullptr,
+                                   srx_fa2_info* info = nullptr) const {
+        if (init && init->size() != info_n() * 2) throw Error(SRX_E_ARG, "draw_graph: the start is n x 2");
+        std::vector<double> y(info_n() * 2);
+        ctx_->check(srx_draw_graph(h_, opts, init && !init->empty() ? init->data() : nullptr, y.empty() ? nullptr : y.data(), info));
+        return y;
+    }
+    // the layout the last draw_graph() left on the device (srx_graph_layout_fetch)
+    std::vector<double> layout() const {
+        std::vector<double> y(info_n() * 2);
+        ctx_->check(srx_graph_layout_fetch(h_, y.empty() ? nullptr : y.data()));
+        return y;
+    }
     // Moran's I and Geary's C of every gene of `a` on the connectivities, read where they lie (srx_autocorr)
     Autocorr autocorr(const IMAnnData& a) const {
         Autocorr r(a.n_vars());
@@ -1077,6 +1093,27 @@ inline std::vector<std::uint32_t> louvain_csr(Context& ctx, const std::vector<st
     ctx.check(srx_louvain_csr(ctx.handle(), indptr.data(), indices.empty() ? nullptr : indices.data(),
                               weights.empty() ? nullptr : weights.data(), labels.size(), &o, labels.empty() ? nullptr : labels.data(), info));
     return labels;
+}
+// ForceAtlas2 layout of any symmetric weighted graph (as for louvain_csr): srx_draw_graph_csr; n x 2, row-major
+inline std::vector<double> draw_graph_csr(Context& ctx, const std::vector<std::uint64_t>& indptr, const std::vector<std::uint32_t>& indices,
+                                          const std::vector<double>& weights, const srx_fa2_opts* opts = nullptr,
+                                          const std::vector<double>* init = nullptr, srx_fa2_info* info = nullptr) {
+    if (indptr.empty() || indices.size() != weights.size() || indptr.back() != indices.size())
+        throw Error(SRX_E_ARG, "draw_graph_csr: indptr (n + 1), indices and weights (indptr[n] each) expected");
+    const std::size_t n = indptr.size() - 1;
+    if (init && init->size() != n * 2) throw Error(SRX_E_ARG, "draw_graph_csr: the start is n x 2");
+    std::vector<double> y(n * 2);
+    ctx.check(srx_draw_graph_csr(ctx.handle(), indptr.data(), indices.empty() ? nullptr : indices.data(),
+                                 weights.empty() ? nullptr : weights.data(), n, opts, init && !init->empty() ? init->data() : nullptr,
+                                 y.empty() ? nullptr : y.data(), info));
+    return y;
+}
+// the speed rule of a ForceAtlas2 iteration on the host (srx_fa2_speed; no GPU): the new (speed, efficiency)
+inline std::pair<double, double> fa2_speed(std::uint64_t n, double swing, double traction, double jitter_tolerance = 1.0, double speed = 1.0,
+                                           double efficiency = 1.0) {
+    const std::int32_t rc = srx_fa2_speed(n, swing, traction, jitter_tolerance, &speed, &efficiency);
+    if (rc != SRX_OK) throw Error(rc, srx_last_error(nullptr));
+    return {speed, efficiency};
 }
 // labels for new cells from host arrays (srx_knn_vote): their k-NN list among n_ref reference cells (n_query x k row-major)
 // and one label below n_groups per reference cell; per new cell the most frequent label (ties to the lowest) and its count

@@ -10,6 +10,7 @@ from ...anndata import DeviceCsr, Direction, FlexValue, IMAnnData
 from . import dim_red
 from .autocorr import autocorr_csr, autocorr_from_tables, autocorr_scales, gearys_c, gene_autocorr, morans_i
 from .diffmap import diffmap, diffmap_csr, dpt, dpt_from, graph_diffmap, graph_transitions
+from .draw_graph import draw_graph, draw_graph_csr, draw_graph_forces, fa2_speed, graph_layout
 from .doublets import Doublets, doublet_scores_knn, doublets_threshold, scrublet, simulate_doublets
 from .harmony import Harmony, encode_batches, harmony_integrate, harmony_points
 from .hvg import (highly_variable_genes_pearson, highly_variable_genes_seurat_v3, pca_pearson_residuals, pearson_gene_variance, pearson_gram,
