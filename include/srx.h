@@ -1978,6 +1978,85 @@ int32_t srx_knn_harmony(srx_harmony* h, const srx_knn_opts* opts, uint32_t* indi
 int32_t srx_neighbors_harmony(srx_harmony* h, const srx_knn_opts* opts, srx_knn_info* knn_info, srx_graph** out);
 void    srx_harmony_free(srx_harmony* h);
 
+/* ---- BBKNN: batch-balanced neighbours, their graph, and the trimming of a graph's connectivities -----------------------------
+ * What bbknn (Polanski et al. 2020; sc.external.pp.bbknn) gives obsp["distances"] / obsp["connectivities"]: the scores stay as
+ * they are, and every cell takes its neighbours from EACH batch, so that Louvain, UMAP, PAGA, diffusion maps, the t-SNE
+ * affinities and the SNN graph run unchanged on a batch-balanced graph.  Not in the reference.  The definition below is what
+ * is tested; the bbknn package, scanpy and umap-learn are NOT installed where this was built and the output has NOT been
+ * compared with any of them.
+ *
+ * Input: n points with d coordinates as srx_knn_* takes them (f64, row-major, finite, 1 <= d <= SRX_KNN_MAX_DIMS, the first
+ *   n_dims used); one batch label < B per point, batch b has n_b points; k_within = neighbors_within_batch (default 3).
+ * Distance, order, ties: exactly those of srx_knn_*: dist2 summed in f64 in difference form, in coordinate order; the
+ *   reported distance is its sqrt; the order is (distance, index of the ORIGINAL point), ties to the lower index.
+ * The list: row i holds K = k_within B - 1 entries: from every batch b != batch(i) the k_within nearest points of b, from its
+ *   own batch the k_within - 1 nearest points other than i itself; indices are those of the caller's points; the row is
+ *   ascending by (distance, index), the distance being the reported one (each batch's points are chosen by dist2, as
+ *   srx_knn_* chooses them; two dist2 one ulp apart can share their sqrt).  This is bbknn's list with the cell taken out: bbknn queries every batch for k_within
+ *   neighbours and finds the cell itself in its own batch, its n_neighbors = k_within B counts the cell, and umap-learn
+ *   then skips column 0.  This library's graph convention is "rows without self, T = log2(k + 1)", so the two agree with
+ *   k = K.  Stated departure: bbknn leaves "the cell is its own nearest neighbour" to the index; here self is excluded by
+ *   identity, so exact duplicates with lower indices cannot displace it.
+ * Graph: srx_neighbors_from_knn's graph of that list, unchanged: rho, sigma and A as there, C = A + A^T - A o A^T, D holds
+ *   the list (bbknn's set_op_mix_ratio = 1 and local_connectivity = 1 are its defaults and the only values built).
+ * Trimming of a symmetric graph C with an integer trim >= 1 (bbknn's `trimming`): for each row i let L_i be its stored
+ *   length; t_i = 0 when L_i <= trim, otherwise t_i is the trim-th largest stored value of row i, counted with multiplicity.
+ *   An entry (i, j) is kept if and only if C_ij >= t_i and C_ij >= t_j.  Values at a threshold are kept, so a trimmed row may
+ *   stay longer than trim.  The comparison is of the f64 values; C_ij and C_ji are the same bits, so the result is exactly
+ *   symmetric, has no diagonal and is bit-identical from call to call.  (bbknn computes the thresholds once and runs two
+ *   passes of "zero the row entries below the row's threshold, transpose": that loop equals the closed form.)
+ *   opts.trim < 0: the default 10 k_within B (bbknn's 10 * knn_distances.shape[1]); 0: no trimming; > 0: that value.
+ *   D, rho, sigma and the directed weights are never trimmed, as in bbknn.
+ * Refusals, each SRX_E_ARG with a message, nothing written: K outside 1 .. 64, i.e. k_within B <= 65, the limit every
+ *   consumer of a list has (3 neighbours per batch allow 21 batches); k_within < 1; B outside 1 .. 65; NULL labels with
+ *   B != 1; a label >= B (found on the device); a batch with fewer than k_within points, an empty batch included (bbknn
+ *   raises here too); those of srx_knn_points (NaN / Inf, d, n_dims, more than one rank, n >= 2^32 - 1).  There is no
+ *   include_self option.  n == 0 gives an empty graph.
+ * Not built: an approximate per-batch search (annoy / pynndescent / the IVF index above), other metrics, set_op_mix_ratio /
+ *   local_connectivity other than 1, sharded contexts.
+ * The result is an ordinary srx_graph with info.k = K: srx_louvain, srx_umap, srx_draw_graph, srx_paga, srx_diffmap,
+ *   srx_snn_graph, srx_tsne_affinities_graph and srx_autocorr read it unchanged. */
+typedef struct srx_bbknn_opts {
+    int32_t neighbors_within_batch;   /* 0 = 3 */
+    int32_t n_dims;                   /* 0 = all */
+    int64_t trim;                     /* < 0: 10 * k_within * B; 0: none; > 0: that many */
+} srx_bbknn_opts;                     /* NULL = {0, 0, -1} */
+typedef struct srx_trim_info {
+    uint64_t trim;                    /* value used; 0: none */
+    uint64_t rows_over_trim;          /* rows with L_i > trim */
+    uint64_t nnz_before, nnz_after, entries_trimmed;   /* stored (directed) entries; the difference is even */
+    uint64_t max_row_nnz_before, max_row_nnz_after, rows_emptied;
+    uint32_t wave_capacity, short_capacity;  /* longest row each selection route takes (as srx_snn_info) */
+    uint32_t reserved_[2];
+    uint64_t rows_wave, rows_short, rows_long;   /* rows over trim by selection route; they sum to rows_over_trim */
+} srx_trim_info;
+typedef struct srx_bbknn_info {
+    uint64_t n;
+    uint32_t n_batches, neighbors_within_batch, k /* K */, d;
+    uint64_t min_batch_cells, max_batch_cells;
+    uint32_t n_searches, reserved_;
+    uint64_t pairs_searched;          /* sum of n_query * n_ref over the searches */
+    uint64_t rows_certified, rows_recomputed;      /* summed over the searches */
+    srx_trim_info trim;
+    double ms, ms_sort, ms_search, ms_merge, ms_graph, ms_trim;   /* hipEvent times */
+} srx_bbknn_info;
+/* On the scores the last fit left on m, read where they lie (no host round trip, like srx_neighbors_result); batch: n host
+ * labels (NULL allowed when n_batches == 1).  opts and info may be NULL. */
+int32_t srx_bbknn_result(srx_mat* m, const uint32_t* batch, uint32_t n_batches, const srx_bbknn_opts* opts, srx_bbknn_info* info,
+                         srx_graph** out);
+/* On caller-supplied points (n x d f64, row-major, host).  indices_out / distances_out: n x K, either may be NULL, receive
+ * the list as defined; out may be NULL when only the list is wanted. */
+int32_t srx_bbknn_points(srx_ctx* ctx, const double* points, uint64_t n, uint64_t d, const uint32_t* batch, uint32_t n_batches,
+                         const srx_bbknn_opts* opts, uint32_t* indices_out, double* distances_out, srx_bbknn_info* info,
+                         srx_graph** out);
+/* On the corrected block of a Harmony handle, read where it lies. */
+int32_t srx_bbknn_harmony(srx_harmony* h, const uint32_t* batch, uint32_t n_batches, const srx_bbknn_opts* opts,
+                          srx_bbknn_info* info, srx_graph** out);
+/* The trimming alone, on the C block of ANY graph handle (neighbours, index, SNN, BBKNN), trim > 0.  g is untouched; *out is
+ * a new handle with a copy of g's D block, scales and directed weights and the trimmed C; its srx_graph_info is g's with
+ * nnz_connectivities and max_row_nnz updated.  info may be NULL. */
+int32_t srx_graph_trim(srx_graph* g, int64_t trim, srx_trim_info* info, srx_graph** out);
+
 /* ---- Doublet detection: simulate, project, score; what sc.pp.scrublet gives obs["doublet_score"], obs["predicted_doublet"] ---
  * Not in the reference.  This is Scrublet (Wolock et al. 2019) RESTATED below, with its random parent pairs replaced by a hash
  * so that the result is bit-identical from call to call and its embedding replaced by this library's pipeline.  The definition

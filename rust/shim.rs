@@ -1107,6 +1107,43 @@ pub mod processing_free {
                 out
             })
         }
+        /// BBKNN (srx_bbknn_result): batch-balanced neighbours over the resident scores, their graph, trimmed (`trim` < 0: the
+        /// default 10 * neighbors_within_batch * n_batches; 0: none).  `batch`: one label below `n_batches` per cell.  Returns
+        /// (distances, connectivities), both n_obs x n_obs CSR, and the call's counters.  Not compared with the bbknn package.
+        pub fn bbknn(adata: &IMAnnData, batch: &[u32], n_batches: u32, neighbors_within_batch: usize, n_pcs: usize, trim: i64)
+                     -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>, SrxBbknnInfo)> {
+            let opts = SrxBbknnOpts { neighbors_within_batch: neighbors_within_batch as i32, n_dims: n_pcs as i32, trim };
+            with_resident(adata, |x| {
+                let mut g: *mut SrxGraph = null_mut();
+                let mut info: SrxBbknnInfo = unsafe { std::mem::zeroed() };
+                x.ctx.check(unsafe { srx_bbknn_result(x.mat, batch.as_ptr(), n_batches, &opts, &mut info, &mut g) })?;
+                let out = graph_to_host(x.ctx, g).map(|(d, c)| (d, c, info));
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
+        /// BBKNN's trimming (srx_graph_trim) of the graph of a k-NN list the caller holds: (distances, trimmed connectivities).
+        pub fn trimmed_connectivities_from_knn(indices: &Array2<u32>, distances: &Array2<f64>, trim: i64)
+                                               -> anyhow::Result<(CsrMatrix<f64>, CsrMatrix<f64>, SrxTrimInfo)> {
+            let ((n, k), dd) = (indices.dim(), distances.dim());
+            if dd != (n, k) {
+                bail!("trimmed_connectivities_from_knn: indices are {n} x {k}, distances {} x {}", dd.0, dd.1);
+            }
+            let i: Vec<u32> = indices.iter().copied().collect();                   // row-major
+            let d: Vec<f64> = distances.iter().copied().collect();
+            with_ctx(|c| {
+                let mut src: *mut SrxGraph = null_mut();
+                c.check(unsafe { srx_neighbors_from_knn(c.0, i.as_ptr(), d.as_ptr(), n as u64, k as u32, &mut src) })?;
+                let mut g: *mut SrxGraph = null_mut();
+                let mut info: SrxTrimInfo = unsafe { std::mem::zeroed() };
+                let rc = unsafe { srx_graph_trim(src, trim, &mut info, &mut g) };
+                unsafe { srx_graph_free(src) };
+                c.check(rc)?;
+                let out = graph_to_host(c, g).map(|(d, t)| (d, t, info));
+                unsafe { srx_graph_free(g) };
+                out
+            })
+        }
         /// The options of the shared-nearest-neighbour graph as Seurat's FindNeighbors has them: Jaccard weights, every pair
         /// that shares a neighbour, the cell in its own set, pairs below `prune` dropped.
         pub fn snn_opts(prune: f64) -> SrxSnnOpts {

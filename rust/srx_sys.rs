@@ -914,6 +914,57 @@ pub struct SrxHarmonyInfo {      // `srx_harmony_info`
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct SrxBbknnOpts {      // `srx_bbknn_opts`
+    pub neighbors_within_batch: i32,
+    pub n_dims: i32,
+    pub trim: i64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxTrimInfo {      // `srx_trim_info`
+    pub trim: u64,
+    pub rows_over_trim: u64,
+    pub nnz_before: u64,
+    pub nnz_after: u64,
+    pub entries_trimmed: u64,
+    pub max_row_nnz_before: u64,
+    pub max_row_nnz_after: u64,
+    pub rows_emptied: u64,
+    pub wave_capacity: u32,
+    pub short_capacity: u32,
+    pub reserved: [u32; 2 as usize],
+    pub rows_wave: u64,
+    pub rows_short: u64,
+    pub rows_long: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct SrxBbknnInfo {      // `srx_bbknn_info`
+    pub n: u64,
+    pub n_batches: u32,
+    pub neighbors_within_batch: u32,
+    pub k: u32,
+    pub d: u32,
+    pub min_batch_cells: u64,
+    pub max_batch_cells: u64,
+    pub n_searches: u32,
+    pub reserved: u32,
+    pub pairs_searched: u64,
+    pub rows_certified: u64,
+    pub rows_recomputed: u64,
+    pub trim: SrxTrimInfo,
+    pub ms: f64,
+    pub ms_sort: f64,
+    pub ms_search: f64,
+    pub ms_merge: f64,
+    pub ms_graph: f64,
+    pub ms_trim: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct SrxDoubletOpts {      // `srx_doublet_opts`
     pub sim_ratio: f64,
     pub expected_rate: f64,
@@ -1254,6 +1305,14 @@ extern "C" {
     pub fn srx_neighbors_harmony(h: *mut SrxHarmony, opts: *const SrxKnnOpts, knn_info: *mut SrxKnnInfo,
                                  out: *mut *mut SrxGraph) -> i32;
     pub fn srx_harmony_free(h: *mut SrxHarmony);
+    pub fn srx_bbknn_result(m: *mut SrxMat, batch: *const u32, n_batches: u32, opts: *const SrxBbknnOpts,
+                            info: *mut SrxBbknnInfo, out: *mut *mut SrxGraph) -> i32;
+    pub fn srx_bbknn_points(ctx: *mut SrxCtx, points: *const f64, n: u64, d: u64, batch: *const u32,
+                            n_batches: u32, opts: *const SrxBbknnOpts, indices_out: *mut u32,
+                            distances_out: *mut f64, info: *mut SrxBbknnInfo, out: *mut *mut SrxGraph) -> i32;
+    pub fn srx_bbknn_harmony(h: *mut SrxHarmony, batch: *const u32, n_batches: u32, opts: *const SrxBbknnOpts,
+                             info: *mut SrxBbknnInfo, out: *mut *mut SrxGraph) -> i32;
+    pub fn srx_graph_trim(g: *mut SrxGraph, trim: i64, info: *mut SrxTrimInfo, out: *mut *mut SrxGraph) -> i32;
     pub fn srx_doublets_simulate(counts: *mut SrxMat, n_sim: u64, seed: u64, parents: *const u64,
                                  out: *mut *mut SrxMat, parents_out: *mut u64) -> i32;
     pub fn srx_doublet_scores_knn(ctx: *mut SrxCtx, indices: *const u32, n_obs: u64, n_sim: u64, k_adj: u32,

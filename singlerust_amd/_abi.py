@@ -459,6 +459,27 @@ class HarmonyInfo(C.Structure):      # srx_harmony_info
                 ("ms", C.c_double)]
 
 
+class BbknnOpts(C.Structure):      # srx_bbknn_opts
+    _fields_ = [("neighbors_within_batch", C.c_int32), ("n_dims", C.c_int32), ("trim", C.c_int64)]
+
+
+class TrimInfo(C.Structure):      # srx_trim_info
+    _fields_ = [("trim", C.c_uint64), ("rows_over_trim", C.c_uint64), ("nnz_before", C.c_uint64),
+                ("nnz_after", C.c_uint64), ("entries_trimmed", C.c_uint64), ("max_row_nnz_before", C.c_uint64),
+                ("max_row_nnz_after", C.c_uint64), ("rows_emptied", C.c_uint64), ("wave_capacity", C.c_uint32),
+                ("short_capacity", C.c_uint32), ("reserved_", C.c_uint32 * 2), ("rows_wave", C.c_uint64),
+                ("rows_short", C.c_uint64), ("rows_long", C.c_uint64)]
+
+
+class BbknnInfo(C.Structure):      # srx_bbknn_info
+    _fields_ = [("n", C.c_uint64), ("n_batches", C.c_uint32), ("neighbors_within_batch", C.c_uint32),
+                ("k", C.c_uint32), ("d", C.c_uint32), ("min_batch_cells", C.c_uint64),
+                ("max_batch_cells", C.c_uint64), ("n_searches", C.c_uint32), ("reserved_", C.c_uint32),
+                ("pairs_searched", C.c_uint64), ("rows_certified", C.c_uint64), ("rows_recomputed", C.c_uint64),
+                ("trim", TrimInfo), ("ms", C.c_double), ("ms_sort", C.c_double), ("ms_search", C.c_double),
+                ("ms_merge", C.c_double), ("ms_graph", C.c_double), ("ms_trim", C.c_double)]
+
+
 class DoubletOpts(C.Structure):      # srx_doublet_opts
     _fields_ = [("sim_ratio", C.c_double), ("expected_rate", C.c_double), ("stdev_rate", C.c_double),
                 ("target_sum", C.c_double), ("threshold", C.c_double), ("seed", C.c_uint64), ("k", C.c_int32),
@@ -667,6 +688,11 @@ SIGNATURES = {
     "srx_knn_harmony": (C.c_int32, [P, C.POINTER(KnnOpts), P, P, C.POINTER(KnnInfo)]),
     "srx_neighbors_harmony": (C.c_int32, [P, C.POINTER(KnnOpts), C.POINTER(KnnInfo), C.POINTER(P)]),
     "srx_harmony_free": (None, [P]),
+    "srx_bbknn_result": (C.c_int32, [P, P, C.c_uint32, C.POINTER(BbknnOpts), C.POINTER(BbknnInfo), C.POINTER(P)]),
+    "srx_bbknn_points": (C.c_int32, [P, P, C.c_uint64, C.c_uint64, P, C.c_uint32, C.POINTER(BbknnOpts), P, P,
+                                     C.POINTER(BbknnInfo), C.POINTER(P)]),
+    "srx_bbknn_harmony": (C.c_int32, [P, P, C.c_uint32, C.POINTER(BbknnOpts), C.POINTER(BbknnInfo), C.POINTER(P)]),
+    "srx_graph_trim": (C.c_int32, [P, C.c_int64, C.POINTER(TrimInfo), C.POINTER(P)]),
     "srx_doublets_simulate": (C.c_int32, [P, C.c_uint64, C.c_uint64, P, C.POINTER(P), P]),
     "srx_doublet_scores_knn": (C.c_int32, [P, P, C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, C.c_double, P, P]),
     "srx_doublets_threshold": (C.c_int32, [P, C.c_uint64, P, P, P]),

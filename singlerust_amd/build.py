@@ -17,7 +17,7 @@ OBJ = os.path.join(CSRC, "build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsrx_hip.so")
 
-SOURCES = ["ctx.hip", "transfer.hip", "matrix.hip", "rows.hip", "genes.hip", "select.hip", "comm.hip", "scan.hip", "pca_form.hip", "pca_solve.hip", "pca.hip", "synth.hip", "filter.hip", "csc.hip", "knn.hip", "graph.hip", "louvain.hip", "markers.hip", "umap.hip", "diffmap.hip", "harmony.hip", "symcsr.hip", "tsne.hip", "draw_graph.hip", "doublets.hip", "knn_ivf.hip", "pearson.hip", "dense_pca.hip", "pearson_pca.hip", "hvg_seurat.hip", "regress.hip", "gene_sets.hip", "paga.hip", "autocorr.hip", "ingest.hip", "snn.hip"]
+SOURCES = ["ctx.hip", "transfer.hip", "matrix.hip", "rows.hip", "genes.hip", "select.hip", "comm.hip", "scan.hip", "pca_form.hip", "pca_solve.hip", "pca.hip", "synth.hip", "filter.hip", "csc.hip", "knn.hip", "graph.hip", "louvain.hip", "markers.hip", "umap.hip", "diffmap.hip", "harmony.hip", "symcsr.hip", "tsne.hip", "draw_graph.hip", "doublets.hip", "knn_ivf.hip", "pearson.hip", "dense_pca.hip", "pearson_pca.hip", "hvg_seurat.hip", "regress.hip", "gene_sets.hip", "paga.hip", "autocorr.hip", "ingest.hip", "snn.hip", "bbknn.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
          "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]
 

@@ -45,6 +45,9 @@ int32_t knn_self_device(srx_ctx* ctx, const double* d_pts, uint64_t n, uint64_t 
                         const double** d_dist, uint64_t* n_out);                                                   // knn.hip
 int32_t graph_from_device_list(srx_ctx* ctx, const uint32_t* d_idx, const double* d_dist, uint64_t n, uint32_t k,
                                srx_graph** out);                                                                  // graph.hip
+int32_t bbknn_device(srx_ctx* ctx, const double* d_pts, const double* h_pts, size_t ld, uint64_t n, uint64_t d_full, const uint32_t* batch,
+                     uint32_t B, const srx_bbknn_opts* opts, uint32_t* indices_out, double* distances_out, srx_bbknn_info* info_out,
+                     srx_graph** out);                                                                            // bbknn.hip
 
 constexpr int kHmKT = 16;                // clusters per tile of k_hm_gemm_t
 constexpr int kHmRows = 32;              // rows staged per step of k_hm_gemm_t
@@ -737,6 +740,16 @@ int32_t srx_neighbors_harmony(srx_harmony* h, const srx_knn_opts* opts, srx_knn_
     uint64_t n = 0;
     SRX_TRY(knn_self_device(ctx, h->d_zc, h->n, h->d, (size_t)h->d, opts, nullptr, nullptr, knn_info, &d_idx, &d_dist, &n));
     return graph_from_device_list(ctx, d_idx, d_dist, n, (uint32_t)opts->k, out);
+}
+
+int32_t srx_bbknn_harmony(srx_harmony* h, const uint32_t* batch, uint32_t n_batches, const srx_bbknn_opts* opts, srx_bbknn_info* info,
+                          srx_graph** out) {
+    if (!h) return fail(nullptr, SRX_E_ARG, "null harmony handle");
+    srx_ctx* ctx = h->ctx;
+    if (!out) return fail(ctx, SRX_E_ARG, "bbknn: null output handle");
+    *out = nullptr;
+    SRX_HIP(ctx, hipSetDevice(ctx->device));
+    return bbknn_device(ctx, h->d_zc, nullptr, (size_t)h->d, h->n, h->d, batch, n_batches, opts, nullptr, nullptr, info, out);
 }
 
 void srx_harmony_free(srx_harmony* h) {

@@ -929,6 +929,32 @@ public:
         ctx_->check(srx_snn_graph(h_, opts, info, &g.h_));
         return g;
     }
+    // BBKNN (srx_bbknn_result): batch-balanced neighbours over the scores the last PCA on `a` left on the device, their graph,
+    // trimmed as opts say (null: 3 neighbours per batch, all PCs, trim = 10 * 3 * n_batches).  `batch`: one label below
+    // n_batches per cell.  The list has K = neighbors_within_batch * n_batches - 1 <= 64 entries per row.
+    static Graph bbknn_of(const IMAnnData& a, const std::vector<std::uint32_t>& batch, std::uint32_t n_batches,
+                          const srx_bbknn_opts* opts = nullptr, srx_bbknn_info* info = nullptr) {
+        Graph g(a.ctx());
+        a.ctx().check(srx_bbknn_result(a.x(), batch.empty() ? nullptr : batch.data(), n_batches, opts, info, &g.h_));
+        return g;
+    }
+    // ... of caller-supplied points (n x d row-major): srx_bbknn_points; `indices` / `distances` (may be null) receive the n x K list
+    static Graph bbknn_points(Context& ctx, const std::vector<double>& points, std::size_t d, const std::vector<std::uint32_t>& batch,
+                              std::uint32_t n_batches, const srx_bbknn_opts* opts = nullptr, srx_bbknn_info* info = nullptr,
+                              std::uint32_t* indices = nullptr, double* distances = nullptr) {
+        if (d == 0 || points.size() % d || (n_batches != 1 && batch.size() != points.size() / d))
+            throw Error(SRX_E_ARG, "Graph::bbknn_points: points must be n x d with one batch label per point");
+        Graph g(ctx);
+        ctx.check(srx_bbknn_points(ctx.handle(), points.empty() ? nullptr : points.data(), points.size() / d, d,
+                                   batch.empty() ? nullptr : batch.data(), n_batches, opts, indices, distances, info, &g.h_));
+        return g;
+    }
+    // BBKNN's trimming of the connectivities of any graph (srx_graph_trim): a new Graph, this one untouched
+    Graph trim(std::int64_t trim, srx_trim_info* info = nullptr) const {
+        Graph g(*ctx_);
+        ctx_->check(srx_graph_trim(h_, trim, info, &g.h_));
+        return g;
+    }
     Graph(Graph&& o) noexcept : ctx_(o.ctx_), h_(o.h_), knn_info_(o.knn_info_) { o.h_ = nullptr; }
     Graph& operator=(Graph&& o) noexcept {
         std::swap(ctx_, o.ctx_);

@@ -19,7 +19,7 @@ from .ingest import ingest, knn_vote, umap_transform
 from .louvain import graph_labels, louvain, louvain_csr
 from .markers import group_moments, rank_genes_groups
 from .paga import paga, paga_csr, paga_from_counts, paga_init_positions
-from .neighbors import KnnIndex, connectivities_from_knn, knn_index, knn_index_points, knn_points, neighbors, neighbors_approx
+from .neighbors import KnnIndex, bbknn, bbknn_points, connectivities_from_knn, knn_index, knn_index_points, knn_points, neighbors, neighbors_approx
 from .regress import pca_regress_scale, regress_fit, regress_gram, regress_out, scale
 from .snn import neighbors_snn, snn_graph, snn_min_shared
 from .score import cell_cycle_phase, gene_list_sums, qc_gene_fractions, score_genes, score_genes_cell_cycle, score_genes_controls

@@ -1,5 +1,6 @@
 """Exact k-nearest-neighbour graph of the cells over libsrx_hip (``srx_knn_result`` / ``srx_knn_points``) and the weighted
-graph built from it (``srx_neighbors_result`` / ``srx_neighbors_from_knn``: ``obsp["distances"]``, ``obsp["connectivities"]``).
+graph built from it (``srx_neighbors_result`` / ``srx_neighbors_from_knn``: ``obsp["distances"]``, ``obsp["connectivities"]``);
+the batch-balanced form of both (``bbknn`` / ``bbknn_points``: ``srx_bbknn_*``) and the trimming of a graph (``Graph.trim``).
 
 Not in the reference: it is the step that consumes ``obsm["X_pca"]`` and stands in front of what the reference's
 commented-out ``tsne`` / ``tsne_inplace`` (dim_red/mod.rs:159-227) would build from the scores.  Euclidean distance in
@@ -20,6 +21,16 @@ def _info_dict(info: F.KnnInfo) -> dict:
     return {"n_ref": int(info.n_ref), "n_query": int(info.n_query), "d": int(info.d), "k": int(info.k),
             "n_candidates": int(info.n_candidates), "rows_certified": int(info.rows_certified),
             "rows_recomputed": int(info.rows_recomputed)}
+
+
+def _trim_dict(info: F.TrimInfo) -> dict:
+    return {name: getattr(info, name) for name, _ in info._fields_ if name != "reserved_"}
+
+
+def _bbknn_dict(info: F.BbknnInfo) -> dict:
+    d = {name: getattr(info, name) for name, _ in info._fields_ if name not in ("reserved_", "trim")}
+    d["trim"] = _trim_dict(info.trim)
+    return d
 
 
 class Graph(OwnedHandle):
@@ -59,6 +70,17 @@ class Graph(OwnedHandle):
             return indptr, indices, data
         n = len(indptr) - 1
         return sp.csr_matrix((data, indices.astype(np.int64 if n >= 2 ** 31 else np.int32), indptr.astype(np.int64)), shape=(n, n))
+
+    def trim(self, trim: int) -> "Graph":
+        """BBKNN's trimming of the connectivities (``srx_graph_trim``) as a new ``Graph``; this one stays as it is.  Per row
+        the ``trim``-th largest value is the row's threshold (0 for a row of at most ``trim`` entries); an entry stays when it
+        reaches the thresholds of both its row and its column.  ``trim_info`` on the result holds the ``srx_trim_info``."""
+        info = F.TrimInfo()
+        h = C.c_void_p()
+        F.check(F.lib().srx_graph_trim(self._h, int(trim), C.byref(info), C.byref(h)), self.ctx.handle)
+        g = Graph(self.ctx, h)
+        g.trim_info = _trim_dict(info)
+        return g
 
 
 def connectivities_from_knn(ctx, indices, distances) -> Graph:
@@ -148,6 +170,83 @@ def neighbors(adata: IMAnnData, n_neighbors: int = 15, n_pcs=None, include_self:
     adata.uns["neighbors"] = {"params": {"n_neighbors": k, "n_pcs": None if n_pcs is None else int(n_pcs),
                                          "include_self": bool(include_self), "metric": "euclidean"},
                               "info": _info_dict(info)}
+    if use_rep is not None:
+        adata.uns["neighbors"]["params"]["use_rep"] = use_rep
+    return adata.uns["neighbors"]
+
+
+def _bbknn_opts(neighbors_within_batch, n_pcs, trim) -> F.BbknnOpts:
+    return F.BbknnOpts(int(neighbors_within_batch), int(n_pcs or 0), -1 if trim is None else int(trim))
+
+
+def _batch_labels(batch, n: int):
+    """(labels uint32 n, n_batches) of integer labels 0 .. B - 1 (``None``: one batch)."""
+    if batch is None:
+        return None, 1
+    b = np.asarray(batch)
+    if b.ndim != 1 or b.shape[0] != n or b.dtype.kind not in "iu":
+        raise ValueError("batch must be one integer label per point")
+    if n and int(b.min()) < 0:
+        raise ValueError("batch labels must not be negative")
+    return np.ascontiguousarray(b, dtype=np.uint32), int(b.max()) + 1 if n else 1
+
+
+def bbknn_points(ctx, points, batch, neighbors_within_batch: int = 3, n_dims=None, trim=None, n_batches=None, graph: bool = True):
+    """Batch-balanced neighbours of caller-supplied points (n x d f64; ``srx_bbknn_points``): every row takes
+    ``neighbors_within_batch`` neighbours from each batch (one fewer from its own, the point itself being left out).
+    ``batch``: integer labels 0 .. B - 1; ``trim``: None = 10 * neighbors_within_batch * B, 0 = none.
+    Returns (indices uint32 n x K, distances f64 n x K, ``Graph`` or None, info dict) with K = neighbors_within_batch * B - 1."""
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    if points.ndim != 2:
+        raise ValueError("points must be n x d")
+    n, d = points.shape
+    labels, B = _batch_labels(batch, n)
+    if n_batches is not None:
+        B = int(n_batches)
+    opts = _bbknn_opts(neighbors_within_batch, n_dims, trim)
+    kw = int(neighbors_within_batch) or 3
+    K = max(kw * B - 1, 0)
+    idx = np.zeros((n, K), dtype=np.uint32)
+    dist = np.zeros((n, K), dtype=np.float64)
+    info = F.BbknnInfo()
+    h = C.c_void_p()
+    F.check(F.lib().srx_bbknn_points(ctx.handle, F.ptr(points) if points.size else None, n, d, None if labels is None else F.ptr(labels), B,
+                                     C.byref(opts), F.ptr(idx) if idx.size else None, F.ptr(dist) if dist.size else None,
+                                     C.byref(info), C.byref(h) if graph else None), ctx.handle)
+    return idx, dist, Graph(ctx, h) if graph else None, _bbknn_dict(info)
+
+
+def bbknn(adata: IMAnnData, batch, neighbors_within_batch: int = 3, n_pcs=None, trim=None, use_rep=None) -> dict:
+    """BBKNN on the scores the last ``pca_inplace`` left on the device (``srx_bbknn_result``; no host round trip), or with
+    ``use_rep`` on the corrected scores of a ``harmony_integrate`` (``srx_bbknn_harmony``).  ``batch``: one integer label
+    0 .. B - 1 per cell, or the name of such a column of ``adata.obs``.  Writes ``obsp["distances"]``, ``obsp["connectivities"]``
+    and ``uns["neighbors"]`` the way ``neighbors(connectivities=True)`` does, with ``n_neighbors = neighbors_within_batch * B``
+    (bbknn counts the cell); the handle kept on the adata is what ``louvain``, ``umap``, ``paga``, ... read."""
+    ctx = adata.x().ctx
+    if isinstance(batch, str):
+        batch = adata.obs[batch]
+    labels, B = _batch_labels(batch, adata.n_obs())
+    opts = _bbknn_opts(neighbors_within_batch, n_pcs, trim)
+    info = F.BbknnInfo()
+    h = C.c_void_p()
+    lp = None if labels is None else F.ptr(labels)
+    if use_rep is None:
+        F.check(F.lib().srx_bbknn_result(adata.x().handle, lp, B, C.byref(opts), C.byref(info), C.byref(h)), ctx.handle)
+    else:
+        F.check(F.lib().srx_bbknn_harmony(_harmony_handle(adata, use_rep).handle, lp, B, C.byref(opts), C.byref(info), C.byref(h)),
+                ctx.handle)
+    g = Graph(ctx, h)
+    old = getattr(adata, "_graph", None)
+    if old is not None:
+        old.free()
+    adata._graph = g
+    adata.obsp["distances"] = g.matrix(F.GRAPH_DISTANCES)
+    adata.obsp["connectivities"] = g.matrix(F.GRAPH_CONNECTIVITIES)
+    kw = int(info.neighbors_within_batch)
+    adata.uns["neighbors"] = {"params": {"n_neighbors": kw * B, "n_pcs": None if n_pcs is None else int(n_pcs), "include_self": False,
+                                         "metric": "euclidean", "method": "bbknn", "neighbors_within_batch": kw,
+                                         "n_batches": B, "trim": int(info.trim.trim)},
+                              "info": _bbknn_dict(info), "graph": g.info()}
     if use_rep is not None:
         adata.uns["neighbors"]["params"]["use_rep"] = use_rep
     return adata.uns["neighbors"]
